@@ -19,9 +19,15 @@ lo_orderkey range of a lineorder N times as long (weak scaling; `--strong`: the 
 multiplexers, exactly like one PipelineExecutor per thread in the reference; the build sides are built on rank 0 and
 broadcast once over RCCL before the clock starts; no collective on the data path.
 
-Prints ONE JSON line (rank 0) with the contract fields plus `roofline` (dominant kernel = the pool kernel, algorithmic
-bytes per SURVEY.md 8(d) over HIP-event kernel time) and `cpu_baseline` (the reference itself, compiled from its
-sources by oracle/ref_build.mk, timed on this box's host cores on a stated contiguous sample).
+Prints ONE JSON line (rank 0) with the contract fields.  A plain run does only what that headline needs: set-up,
+warm-up, the K timed steps, the line.  `--full` adds everything else the benchmark measures: `roofline` (dominant
+kernel = the pool kernel, algorithmic bytes per SURVEY.md 8(d) over HIP-event kernel time, from a second pass of K
+steps), `cpu_baseline` (the reference itself, compiled from its sources by oracle/ref_build.mk, timed on this box's
+host cores on a stated contiguous sample) and, at N = 1, the `sub_records`.
+
+`--dump-outputs DIR` writes what the timed path returned in its last timed step -- the per-executor statistics of the
+multiplexers (COUNT(*) sink), the group cells of the GROUP BY sink -- as DIR/<name>.npy (float64), so that two builds
+can be compared output for output on the same seeded inputs.
 """
 import argparse
 import json
@@ -90,6 +96,31 @@ def algorithmic_bytes(joins_info, paths, tuples_per_path, stage_out):
                 total += inp * (K + 8 + alpha * (1 + K + 8)) + out * ((1 + K + 8) + 4)
             inp = out
     return total
+
+
+DUMP_MAX_BYTES = 64 << 20
+
+
+def dump_outputs(directory, arrays):
+    """--dump-outputs: every array as <directory>/<name>.npy in float64 (counters and sums well inside float64's exact
+    integers, the reward's doubles)"""
+    arrays = {name: np.asarray(a, dtype=np.float64) for name, a in arrays.items()}
+    total = sum(a.nbytes for a in arrays.values())
+    if total > DUMP_MAX_BYTES:
+        raise SystemExit("--dump-outputs: %d bytes exceed the %d-byte cap" % (total, DUMP_MAX_BYTES))
+    os.makedirs(directory, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(directory, name + ".npy"), a)
+
+
+def stats_arrays(results):
+    """the statistics polr_mpx_finish_many returned, one row per executor"""
+    return {"num_tuples_processed": [r["num_tuples_processed"] for r in results],
+            "num_intermediates": [r["num_intermediates"] for r in results],
+            "num_rounds": [r["num_rounds"] for r in results],
+            "input_tuple_count_per_path": [r["input_tuple_count_per_path"] for r in results],
+            "path_resistances": [r["path_resistances"] for r in results],
+            "stage_out": [r["stage_out"] for r in results]}
 
 
 def chunk_offsets_for(sel, n_rows, V):
@@ -242,8 +273,9 @@ class Case:
     pass
 
 
-def run_case(name, scale, args, env, steps, warmup, with_cpu):
-    """measure one workload; returns the record (dict).  env: torch, dist, dev, ctx, world, rank"""
+def run_case(name, scale, args, env, steps, warmup, with_cpu, dump=None):
+    """measure one workload; returns the record (dict).  env: torch, dist, dev, ctx, world, rank; dump: the
+    --dump-outputs directory (the headline record only)"""
     torch, dist, dev, ctx, world, rank = env["torch"], env["dist"], env["dev"], env["ctx"], env["world"], env["rank"]
     from polr_amd import capi, workloads, ssb_skew
     from polr_amd import dist as pdist
@@ -401,7 +433,7 @@ def run_case(name, scale, args, env, steps, warmup, with_cpu):
         # 1024-row vectors into the chunks the multiplexer sees; selection and chunk boundaries stay in HBM
         f3 = [(names.index(c), op, const) for c, op, const in (flt or [])]
         best = None
-        for _ in range(5):
+        for _ in range(5 if args.full else 1):  # (--full: the best of five calls for scan_info)
             torch.cuda.synchronize()
             t_s = time.perf_counter()
             n_tuples, n_chunks = pipe.scan_filter(f3, vector_size=V, lip_joins=lip_mask)
@@ -516,10 +548,13 @@ def run_case(name, scale, args, env, steps, warmup, with_cpu):
         dist.barrier()
     results = capi.stats_dicts(*raw_results[0])
     st = merged(results)
-    # ---- same K steps again with a HIP event pair around every pool-kernel launch (on the launch stream) to get the
-    # dominant kernel's device time for the roofline; kept out of the region `value` is computed from
+    if dump and rank == 0:
+        dump_outputs(dump, dict(stats_arrays(results), count_star=[sum(
+            st["stage_out"][p][k - 1] for p in range(len(paths)))]))
+    # ---- (--full) same K steps again with a HIP event pair around every pool-kernel launch (on the launch stream) to get
+    # the dominant kernel's device time for the roofline; kept out of the region `value` is computed from
     kernel_ms, launches, dt_events = 0.0, 0, None
-    if not args.no_kernel_events:
+    if args.full and not args.no_kernel_events:
         for m in all_mpxs:
             m.kernel_time()
             m.enable_timing(True)
@@ -814,7 +849,7 @@ def cpu_baseline_job_full(cases, args, budget_s=40.0, cap_tuples=6_000_000):
                       "thread (oracle/_ref is not built here)" % (cap, min(4, len(cases)))}
 
 
-def run_job_full(args, env, steps, warmup, with_cpu):
+def run_job_full(args, env, steps, warmup, with_cpu, dump=None):
     """BASELINE.json configs[3]: the 113 JOB-shaped pipelines (polr_amd/job_family.py), whole queries dealt round-robin
     to the ranks, nothing exchanged.  One step = one pass of EVERY pipeline of the rank (one pool launch each,
     enqueued back to back)."""
@@ -918,8 +953,12 @@ def run_job_full(args, env, steps, warmup, with_cpu):
     dt = time.perf_counter() - t0
     if world > 1:
         dist.barrier()
+    if dump and rank == 0:
+        # every pipeline's per-executor statistics, flattened and concatenated in pipeline order
+        per_case = [stats_arrays(stats[c["name"]]) for c in cases]
+        dump_outputs(dump, {f: np.concatenate([np.ravel(a[f]) for a in per_case]) for f in per_case[0]})
     kernel_ms, launches = 0.0, 0
-    if not args.no_kernel_events:
+    if args.full and not args.no_kernel_events:
         for c in cases:
             for m in c["mpxs"]:
                 m.kernel_time()
@@ -1046,7 +1085,7 @@ def spawn_ranks(n, argv=None, script=None, extra_env=None):
     return 0
 
 
-def run_q41_shipped(args, env, steps, warmup, with_cpu):
+def run_q41_shipped(args, env, steps, warmup, with_cpu, dump=None):
     """sub-record: SSB-skew Q4.1 AS THE REFERENCE SHIPS IT (benchmark/ssb-skew/queries/q4-1.sql) at SF100 -- the multiplexed
     star join with its own sink, `SUM(lo_revenue - lo_supplycost) GROUP BY d_year, c_nation`, all on the device: the flat
     pool launch emits the surviving tuples' row ids, the perfect-hash aggregate (polr_out_aggregate_grouped) folds them into
@@ -1112,19 +1151,23 @@ def run_q41_shipped(args, env, steps, warmup, with_cpu):
     dt = time.perf_counter() - t0
     stats = capi.finish_many(mpxs)
     vals, counts, dropped = result[0]
+    if dump:
+        dump_outputs(dump, dict(stats_arrays(stats), group_cells=vals, rows_dropped=[dropped]))
     groups = {}
     nv = keys[1][3]
     for g_, v in enumerate(vals):
         if v[0]:
             groups["%d/%d" % (keys[0][2] + g_ // nv, keys[1][2] + g_ % nv)] = int(v[1] - v[2])
     count_star = int(sum(v[0] for v in vals))
-    for m in mpxs:
-        m.kernel_time()
-        m.enable_timing(True)
-    for _ in range(steps):
-        step()
-    torch.cuda.synchronize()
-    kernel_ms = sum(m.kernel_time()[0] for m in mpxs) / steps
+    kernel_ms = None
+    if args.full:
+        for m in mpxs:
+            m.kernel_time()
+            m.enable_timing(True)
+        for _ in range(steps):
+            step()
+        torch.cuda.synchronize()
+        kernel_ms = round(sum(m.kernel_time()[0] for m in mpxs) / steps, 4)
     inter = sum(st["num_intermediates"] for st in stats)
     cpu = None
     if with_cpu:
@@ -1161,7 +1204,7 @@ def run_q41_shipped(args, env, steps, warmup, with_cpu):
                       "launch": "flat pipeline, emitting" if info.get("flat") else "generic pipeline, emitting"},
            "count_star": count_star, "groups": len(groups), "rows_dropped_by_the_group_domain": int(dropped),
            "profit_checksum": int(sum(groups.values())), "total_intermediates": int(inter),
-           "pool_kernel_ms_per_step": round(kernel_ms, 4),
+           "pool_kernel_ms_per_step": kernel_ms,
            "timed_region": {"gpu": ("reset of the group cells + routing and probing of every source chunk with the aggregate "
                                     "inside the launch; the group cells are read back every step") if fused else
                                    ("output cursor reset + routing and probing of every source chunk + row-id emission of the "
@@ -1247,7 +1290,14 @@ def main():
     ap.add_argument("--pin-path", type=int, default=None, help="measurement aid: make join order P of the bank path 0")
     ap.add_argument("--cpu-sample-rows", type=int, default=64_000_000,
                     help="SSB-skew CPU baseline: rows of each of the two contiguous lineorder samples")
+    ap.add_argument("--full", action="store_true",
+                    help="everything besides the headline: the HIP-event pass for `roofline`, `cpu_baseline`, the "
+                         "sub-records at N = 1 (--no-kernel-events, --no-cpu-baseline, --no-sub-records leave parts out)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step returned as DIR/<name>.npy (float64)")
     args = ap.parse_args()
+    if args.steps < 1:
+        raise SystemExit("--steps must be at least 1")
 
     os.environ.setdefault("GPU_MAX_HW_QUEUES", "8")
     import torch
@@ -1307,12 +1357,14 @@ def main():
     env = {"torch": torch, "dist": dist, "dev": dev, "ctx": ctx, "world": world, "rank": rank}
     if args.workload == "ssb_skew_q41_shipped":  # (the sub-record of the default line on its own)
         args.enumerator_name = "sample" if args.enumerator == "auto" else args.enumerator
-        head = run_q41_shipped(args, env, min(args.steps, 10), min(args.warmup, 2), with_cpu=not args.no_cpu_baseline)
+        head = run_q41_shipped(args, env, args.steps, args.warmup, with_cpu=args.full and not args.no_cpu_baseline,
+                               dump=args.dump_outputs)
         print(json.dumps(head))
         ctx.close()
         return
     if args.workload == "job_full":
-        head = run_job_full(args, env, args.steps, args.warmup, with_cpu=world == 1 and not args.no_cpu_baseline)
+        head = run_job_full(args, env, args.steps, args.warmup,
+                            with_cpu=args.full and world == 1 and not args.no_cpu_baseline, dump=args.dump_outputs)
         if rank == 0:
             print(json.dumps(head))
         ctx.close()
@@ -1322,9 +1374,11 @@ def main():
         return
     is_ssb = args.workload in SSB_QUERIES
     scale = args.scale if args.scale is not None else (100.0 if is_ssb else 1.0)
-    head = run_case(args.workload, scale, args, env, args.steps, args.warmup, with_cpu=world == 1 and not args.no_cpu_baseline)
+    head = run_case(args.workload, scale, args, env, args.steps, args.warmup,
+                    with_cpu=args.full and world == 1 and not args.no_cpu_baseline, dump=args.dump_outputs)
     subs = []
-    if world == 1 and not args.no_sub_records:
+    with_subs = args.full and world == 1 and not args.no_sub_records
+    if with_subs:
         saved = (args.executors, args.max_join_orders)
         for sub, sub_scale in (("job_q18", 1.0), ("job_light_01", 1.0)):
             if sub == args.workload:
@@ -1338,7 +1392,7 @@ def main():
             if r is not None:
                 subs.append(r)
         args.executors, args.max_join_orders = saved
-    if world == 1 and not args.no_sub_records and is_ssb and args.workload == "ssb_skew_q41":
+    if with_subs and args.workload == "ssb_skew_q41":
         try:
             r = run_q41_shipped(args, env, min(args.steps, 10), min(args.warmup, 2), with_cpu=not args.no_cpu_baseline)
         except SystemExit as e:

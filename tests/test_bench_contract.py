@@ -1,6 +1,7 @@
 """The driver's bench contract, checked on the lines this repository committed (profiles/r02_bench_default.json,
-profiles/r03_bench_default.json = stdout of `python bench.py` on the GPU box): one JSON object with the contract's keys,
-BASELINE.json's metric and unit, and the two objects this tier adds (`roofline`, `cpu_baseline`)."""
+profiles/r03_bench_default.json = stdout of `python bench.py` on the GPU box, what `python bench.py --full` prints now):
+one JSON object with the contract's keys, BASELINE.json's metric and unit, and the two objects this tier adds (`roofline`,
+`cpu_baseline`)."""
 import json
 import os
 
@@ -123,3 +124,28 @@ def test_bench_refuses_more_ranks_than_gpus():
     p = subprocess.run([sys.executable, os.path.join(common.ROOT, "bench.py"), "--gpus", "2"], env=env,
                        stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=300)
     assert p.returncode != 0 and "must agree" in p.stderr
+
+
+def test_dump_outputs_writes_float64_arrays_under_the_cap(tmp_path):
+    """`--dump-outputs DIR`: every array the timed path returned as DIR/<name>.npy in float64, one row per executor;
+    more than 64 MB in all is refused before anything is written"""
+    import importlib.util
+    import numpy as np
+    spec = importlib.util.spec_from_file_location("bench_mod", os.path.join(common.ROOT, "bench.py"))
+    bench = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(bench)
+    results = [{"num_tuples_processed": 3000 + e, "num_intermediates": 10 * e, "num_rounds": 4,
+                "input_tuple_count_per_path": [1000, 2000 + e], "path_resistances": [0.5, 0.25 * e],
+                "stage_out": [[7, 5, 3], [9, 6, 2 + e]]} for e in range(3)]
+    out = tmp_path / "dump"
+    bench.dump_outputs(str(out), dict(bench.stats_arrays(results), count_star=[11]))
+    got = {f.name[:-4]: np.load(f) for f in out.iterdir()}
+    assert set(got) == {"num_tuples_processed", "num_intermediates", "num_rounds", "input_tuple_count_per_path",
+                        "path_resistances", "stage_out", "count_star"}
+    assert all(a.dtype == np.float64 for a in got.values())
+    assert got["stage_out"].shape == (3, 2, 3) and got["stage_out"][2, 1, 2] == 4
+    assert got["input_tuple_count_per_path"].tolist() == [[1000, 2000], [1000, 2001], [1000, 2002]]
+    assert got["count_star"].tolist() == [11]
+    with pytest.raises(SystemExit):
+        bench.dump_outputs(str(tmp_path / "big"), {"x": np.zeros(bench.DUMP_MAX_BYTES // 8 + 1)})
+    assert not (tmp_path / "big").exists()

@@ -12,7 +12,7 @@ ROOT=$(pwd)
 OUT=$ROOT/gpurun_out/prof_$TAG
 mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp
-rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/trace -o trace -- python3 $ROOT/bench.py --steps 20 --warmup 3 --no-cpu-baseline $ARGS > $OUT/bench_under_rocprof.json 2> $OUT/trace.log || echo "rocprofv3 trace pass: exit status $?"
-rocprofv3 --pmc FETCH_SIZE --output-format csv -d $OUT/fetch -o fetch -- python3 $ROOT/bench.py --steps 4 --warmup 1 --no-cpu-baseline --no-kernel-events $ARGS > $OUT/bench_fetch.json 2> $OUT/fetch.log || echo "rocprofv3 fetch pass: exit status $?"
-rocprofv3 --pmc WRITE_SIZE --output-format csv -d $OUT/write -o write -- python3 $ROOT/bench.py --steps 4 --warmup 1 --no-cpu-baseline --no-kernel-events $ARGS > $OUT/bench_write.json 2> $OUT/write.log || echo "rocprofv3 write pass: exit status $?"
+rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/trace -o trace -- python3 $ROOT/bench.py --steps 20 --warmup 3 --full --no-cpu-baseline $ARGS > $OUT/bench_under_rocprof.json 2> $OUT/trace.log || echo "rocprofv3 trace pass: exit status $?"
+rocprofv3 --pmc FETCH_SIZE --output-format csv -d $OUT/fetch -o fetch -- python3 $ROOT/bench.py --steps 4 --warmup 1 --full --no-cpu-baseline --no-kernel-events $ARGS > $OUT/bench_fetch.json 2> $OUT/fetch.log || echo "rocprofv3 fetch pass: exit status $?"
+rocprofv3 --pmc WRITE_SIZE --output-format csv -d $OUT/write -o write -- python3 $ROOT/bench.py --steps 4 --warmup 1 --full --no-cpu-baseline --no-kernel-events $ARGS > $OUT/bench_write.json 2> $OUT/write.log || echo "rocprofv3 write pass: exit status $?"
 ls $OUT/trace/*kernel_stats.csv $OUT/fetch/*counter_collection.csv $OUT/write/*counter_collection.csv

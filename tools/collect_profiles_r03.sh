@@ -9,7 +9,7 @@ ROOT=$(pwd)
 OUT=$ROOT/gpurun_out/prof_r03_$TAG
 mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp
-ARGS="$* --no-cpu-baseline --no-sub-records"
+ARGS="$* --full --no-cpu-baseline --no-sub-records"
 echo "[1/7] kernel trace: $ARGS"
 rocprofv3 --kernel-trace --stats --kernel-include-regex "polr_" --output-format csv -d $OUT/trace -o t -- python3 $ROOT/bench.py $ARGS > $OUT/bench_under_trace.json 2> $OUT/trace.log || echo "trace exit $?"
 echo "[2/7] FETCH_SIZE"

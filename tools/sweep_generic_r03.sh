@@ -5,7 +5,7 @@ OUT=gpurun_out/sweep_generic_r03.txt
 : > $OUT
 run() {
 	echo "== $*" >> $OUT
-	env "$@" python3 bench.py --workload $WL --steps 20 --warmup 3 --no-cpu-baseline --no-sub-records $EXTRA 2>> gpurun_out/sweep_generic_r03.err | python3 -c "
+	env "$@" python3 bench.py --full --workload $WL --steps 20 --warmup 3 --no-cpu-baseline --no-sub-records $EXTRA 2>> "${OUT%.txt}.err" | python3 -c "
 import json,sys
 for l in sys.stdin:
     if l.startswith('{'):
