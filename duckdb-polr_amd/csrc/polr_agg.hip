@@ -25,21 +25,6 @@ struct AggPartial {
 	unsigned long long count; // rows that took part (non-NULL; all rows for COUNT(*))
 };
 
-__device__ __forceinline__ long long agg_cell(const DevCol &c, uint32_t row) {
-	const uint8_t *p = c.data + (uint64_t)row * c.width;
-	const bool sx = (c.flags & 1u) != 0;
-	switch (c.width) {
-	case 1:
-		return sx ? (long long)*(const int8_t *)p : (long long)*p;
-	case 2:
-		return sx ? (long long)*(const int16_t *)p : (long long)*(const uint16_t *)p;
-	case 4:
-		return sx ? (long long)*(const int32_t *)p : (long long)*(const uint32_t *)p;
-	default:
-		return *(const long long *)p;
-	}
-}
-
 // grid-stride over the output chunks; partials[blockIdx.x * n + a]
 __global__ __launch_bounds__(256) void polr_agg_kernel(DevOut out, uint32_t n_chunks, DevAggSet aggs,
                                                        AggPartial *__restrict__ partials) {
@@ -61,7 +46,7 @@ __global__ __launch_bounds__(256) void polr_agg_kernel(DevOut out, uint32_t n_ch
 				if (ag.src.valid && !ag.src.valid[row]) {
 					continue; // NULLs take no part
 				}
-				const long long v = agg_cell(ag.src, row);
+				const long long v = load_col_cell(ag.src, row);
 				cnt++;
 				const unsigned long long nl = lo + (unsigned long long)v;
 				hi += (v < 0 ? -1 : 0) + (nl < lo ? 1 : 0); // sign extension of v + carry
@@ -288,7 +273,7 @@ __global__ __launch_bounds__(256) void polr_group_agg_kernel(DevOut out, uint32_
 					ok = false;
 					break;
 				}
-				const long long v = agg_cell(gk.src, row);
+				const long long v = load_col_cell(gk.src, row);
 				const unsigned long long off = (unsigned long long)(v - gk.min_value);
 				if (off >= gk.n_values) {
 					ok = false;
@@ -311,7 +296,7 @@ __global__ __launch_bounds__(256) void polr_group_agg_kernel(DevOut out, uint32_
 				if (ag.src.valid && !ag.src.valid[row]) {
 					continue;
 				}
-				cell_add(c, agg_cell(ag.src, row));
+				cell_add(c, load_col_cell(ag.src, row));
 			}
 		}
 	}
@@ -542,7 +527,7 @@ __global__ __launch_bounds__(256) void polr_hash_agg_kernel(DevOut out, uint32_t
 					if (gk.src.valid && !gk.src.valid[row]) {
 						null_mask |= 1u << q;
 					} else {
-						key[q] = agg_cell(gk.src, row);
+						key[q] = load_col_cell(gk.src, row);
 					}
 					h = polr_murmurhash64(h ^ (uint64_t)key[q]) + q;
 				}
@@ -598,7 +583,7 @@ __global__ __launch_bounds__(256) void polr_hash_agg_kernel(DevOut out, uint32_t
 					if (ag.src.valid && !ag.src.valid[row]) {
 						continue;
 					}
-					cell_add(c, agg_cell(ag.src, row));
+					cell_add(c, load_col_cell(ag.src, row));
 				}
 			}
 		}

@@ -31,21 +31,7 @@ __global__ void polr_deserialize_col_kernel(const uint8_t *__restrict__ rows, ui
 }
 
 // ---- key normalisation ---------------------------------------------------------------------------
-__device__ __forceinline__ uint64_t build_cell(const DevCol &col, uint64_t r, bool sx) {
-	const uint8_t *p = col.data + r * col.width;
-	switch (col.width) {
-	case 1:
-		return sx ? (uint64_t)(int64_t)(int8_t)*p : (uint64_t)*p;
-	case 2:
-		return sx ? (uint64_t)(int64_t) * (const int16_t *)p : (uint64_t) * (const uint16_t *)p;
-	case 4:
-		return sx ? (uint64_t)(int64_t) * (const int32_t *)p : (uint64_t) * (const uint32_t *)p;
-	default:
-		return *(const uint64_t *)p;
-	}
-}
-
-// same convention as fetch_key() in polr_probe_device.h: plain form = zero-extended bit pattern, two 32-bit keys
+// same convention as the probe kernels' fetch_key(): plain form = zero-extended bit pattern, two 32-bit keys
 // packed; packed form = sum of (value - min) << shift (KeyPack, polr_device.h)
 __device__ __forceinline__ bool build_key(const DevCol *keys, uint32_t n_keys, uint64_t r, const KeyPack &pack,
                                           uint64_t &key) {
@@ -60,10 +46,10 @@ __device__ __forceinline__ bool build_key(const DevCol *keys, uint32_t n_keys, u
 			}
 			valid = false;
 		}
+		const uint64_t v = load_cell(as_global(col.data) + r * col.width, col.width, pack.packed && pack.sx[c] != 0);
 		if (pack.packed) {
-			key |= (build_cell(col, r, pack.sx[c] != 0) - (uint64_t)pack.min[c]) << pack.shift[c];
+			key |= (v - (uint64_t)pack.min[c]) << pack.shift[c];
 		} else {
-			const uint64_t v = build_cell(col, r, false);
 			key = c == 0 ? v : (key | (v << 32));
 		}
 	}
@@ -85,7 +71,7 @@ __global__ void polr_key_minmax_kernel(const DevCol *__restrict__ keys, uint32_t
 	for (uint32_t c = 0; c < n_keys; c++) {
 		long long lo = 0x7FFFFFFFFFFFFFFFll, hi = -0x7FFFFFFFFFFFFFFFll - 1;
 		if (valid && !(keys[c].valid && !keys[c].valid[r])) {
-			lo = hi = (long long)build_cell(keys[c], r, (keys[c].flags & 1u) != 0);
+			lo = hi = load_col_cell(keys[c], r);
 		}
 		for (int d = 32; d > 0; d >>= 1) {
 			const long long l2 = __shfl_xor(lo, d, 64), h2 = __shfl_xor(hi, d, 64);
@@ -290,47 +276,9 @@ __global__ void polr_pht_mark_kernel(const DevCol *__restrict__ keys, uint64_t n
 		atomicExch(&flags[1], 1u);
 		return;
 	}
-	const uint8_t *p = col.data + r * col.width;
+	const uint64_t v = load_cell(as_global(col.data) + r * col.width, col.width, is_signed != 0);
 	uint64_t idx;
-	bool in_range;
-	if (is_signed) {
-		int64_t v;
-		switch (col.width) {
-		case 1:
-			v = *(const int8_t *)p;
-			break;
-		case 2:
-			v = *(const int16_t *)p;
-			break;
-		case 4:
-			v = *(const int32_t *)p;
-			break;
-		default:
-			v = *(const int64_t *)p;
-			break;
-		}
-		in_range = v >= min_value && (uint64_t)(v - min_value) <= range;
-		idx = (uint64_t)(v - min_value);
-	} else {
-		uint64_t v;
-		switch (col.width) {
-		case 1:
-			v = *p;
-			break;
-		case 2:
-			v = *(const uint16_t *)p;
-			break;
-		case 4:
-			v = *(const uint32_t *)p;
-			break;
-		default:
-			v = *(const uint64_t *)p;
-			break;
-		}
-		in_range = v >= (uint64_t)min_value && v - (uint64_t)min_value <= range;
-		idx = v - (uint64_t)min_value;
-	}
-	if (!in_range) {
+	if (!perfect_index(v, is_signed != 0, min_value, range, idx)) {
 		return;
 	}
 	const uint32_t bit = 1u << (idx & 31);

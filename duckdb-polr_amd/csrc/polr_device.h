@@ -289,3 +289,295 @@ __host__ __device__ inline uint64_t polr_murmurhash64(uint64_t x) {
 	x ^= x >> 32;
 	return x;
 }
+
+// ---- the rules every device kernel shares ----------------------------------------------------------------------------
+// Data formats and key semantics that build, scan, probe and sink kernels must agree on bit for bit -- one definition
+// each.  They read through POLR_GLOBAL pointers (kernels that hold generic ones convert at the call with as_global).
+#if defined(__HIPCC__) || defined(__HIP_DEVICE_COMPILE__)
+// ---- wave helpers
+__device__ __forceinline__ uint32_t uni(uint32_t v) {
+	return __builtin_amdgcn_readfirstlane(v);
+}
+__device__ __forceinline__ uint64_t uni64(uint64_t v) {
+	uint32_t lo = __builtin_amdgcn_readfirstlane((uint32_t)v);
+	uint32_t hi = __builtin_amdgcn_readfirstlane((uint32_t)(v >> 32));
+	return ((uint64_t)hi << 32) | lo;
+}
+template <class T>
+__device__ __forceinline__ const T *uniptr(const T *p) {
+	return (const T *)uni64((uint64_t)p);
+}
+// rank of this lane among the lanes of `mask` below it
+__device__ __forceinline__ uint32_t lane_rank(uint64_t mask) {
+	return __builtin_amdgcn_mbcnt_hi((uint32_t)(mask >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)mask, 0));
+}
+__device__ __forceinline__ uint32_t wave_inclusive_scan(uint32_t v, uint32_t lane) {
+#pragma unroll
+	for (int d = 1; d < 64; d <<= 1) {
+		const uint32_t o = __shfl_up(v, d, 64);
+		if ((int)lane >= d) {
+			v += o;
+		}
+	}
+	return v;
+}
+__device__ __forceinline__ uint64_t wave_sum64(uint64_t v) { // the same sum in every lane
+#pragma unroll
+	for (int d = 32; d > 0; d >>= 1) {
+		v += __shfl_xor(v, d, 64);
+	}
+	return v;
+}
+
+// ---- cells: a 1/2/4/8-byte value widened to 64 bits, sign- or zero-extended
+__device__ __forceinline__ uint64_t load_cell(const POLR_GLOBAL uint8_t *p, uint32_t width, bool sign_extend) {
+	switch (width) {
+	case 1: {
+		const uint8_t v = *p;
+		return sign_extend ? (uint64_t)(int64_t)(int8_t)v : (uint64_t)v;
+	}
+	case 2: {
+		const uint16_t v = *(const POLR_GLOBAL uint16_t *)p;
+		return sign_extend ? (uint64_t)(int64_t)(int16_t)v : (uint64_t)v;
+	}
+	case 4: {
+		const uint32_t v = *(const POLR_GLOBAL uint32_t *)p;
+		return sign_extend ? (uint64_t)(int64_t)(int32_t)v : (uint64_t)v;
+	}
+	default:
+		return *(const POLR_GLOBAL uint64_t *)p;
+	}
+}
+// one cell of a column, as a signed 64-bit value (the column's flags say whether it is signed)
+__device__ __forceinline__ long long load_col_cell(const DevCol &c, uint64_t row) {
+	return (long long)load_cell(as_global(c.data) + row * c.width, c.width, (c.flags & 1u) != 0);
+}
+
+// ---- tuples of row ids: slot 0 the probe row, the others build ids
+template <int W>
+struct Tuple {
+	uint32_t s[W];
+};
+template <int W>
+__device__ __forceinline__ uint32_t tuple_slot(const Tuple<W> &t, int32_t slot) {
+	uint32_t v = t.s[0];
+#pragma unroll
+	for (int q = 1; q < W; q++) {
+		v = (q == slot) ? t.s[q] : v;
+	}
+	return v;
+}
+
+// composite key in packed form (KeyPack): per column (value - min) << shift; a value outside the build side's
+// [min, min + range] cannot match.  Everything comes from the stage's extension record.  A function of its own (like
+// preds_hold below): inlined into every place a stage fetches keys, the uncommon paths made the POLR_EXT objects the
+// slowest of the build by minutes -- the pipelines that take them can afford a call.
+template <int W>
+__device__ __attribute__((noinline)) bool fetch_key_packed(const POLR_GLOBAL StageExt *d, uint32_t n_keys, const Tuple<W> &t,
+                                                           uint64_t &key) {
+	bool valid = true;
+	key = 0;
+	for (uint32_t c = 0; c < n_keys; c++) {
+		const uint32_t row = tuple_slot<W>(t, d->key_slot[c]);
+		const POLR_GLOBAL uint8_t *kv = as_global(d->key_valid[c]);
+		const uint32_t w = d->key_width[c];
+		// (by VALUE: the probe column's own width and signedness -- a CAST'ed key; a value outside the build side's range
+		// cannot match, whichever type could or could not hold it)
+		const uint64_t v = load_cell(as_global(d->key_data[c]) + (uint64_t)row * w, w, d->key_sx[c] != 0);
+		uint64_t off = v - (uint64_t)d->pack.min[c];
+		if (kv && !kv[row]) {
+			if ((d->pack.null_eq >> c) & 1u) {
+				off = d->pack.range[c] + 1u; // IS NOT DISTINCT FROM: NULL is a key value of its own
+			} else {
+				valid = false;
+			}
+		} else if (off > d->pack.range[c]) {
+			valid = false;
+		}
+		key |= off << d->pack.shift[c];
+	}
+	if (!valid) {
+		key = 0;
+	}
+	return valid;
+}
+
+// the join's non-equality conditions on one (tuple, build row) pair (RowOperations::Match, row_match.cpp:59-119:
+// both sides valid and `left OP right`); descriptors come from the extension record -- joins that have any are rare
+template <int W>
+__device__ __attribute__((noinline)) bool preds_hold(const POLR_GLOBAL StageExt *d, uint32_t n_preds, const Tuple<W> &t,
+                                                     uint32_t id) {
+	bool ok = true;
+	for (uint32_t c = 0; c < n_preds; c++) {
+		const uint32_t row = tuple_slot<W>(t, d->pred_slot[c]);
+		const uint32_t w = d->pred_width[c];
+		const bool sx = d->pred_sx[c] != 0;
+		const POLR_GLOBAL uint8_t *lv = as_global(d->pred_valid[c]);
+		const POLR_GLOBAL uint8_t *rv = as_global(d->pred_bvalid[c]);
+		if ((lv && !lv[row]) || (rv && !rv[id])) {
+			ok = false;
+		}
+		if (d->pred_op[c] == POLR_PRED_STR_EQ) { // the strings behind a VARCHAR key's hash
+			ok = ok && polr_str_cells_equal(d->pred_data[c] + (uint64_t)row * 16u, d->pred_bdata[c] + (uint64_t)id * 16u);
+			continue;
+		}
+		const uint64_t l = load_cell(as_global(d->pred_data[c]) + (uint64_t)row * w, w, sx);
+		const uint64_t r = load_cell(as_global(d->pred_bdata[c]) + (uint64_t)id * w, w, sx);
+		bool h;
+		if (w == 8 && !sx) {
+			switch (d->pred_op[c]) {
+			case 0: h = l == r; break; // (POLR_CMP_EQ: the verifying comparison behind a hashed composite key)
+			case 1: h = l != r; break;
+			case 2: h = l < r; break;
+			case 3: h = l > r; break;
+			case 4: h = l <= r; break;
+			default: h = l >= r; break;
+			}
+		} else {
+			const int64_t a = (int64_t)l, b = (int64_t)r; // (narrow unsigned values are zero-extended: same order)
+			switch (d->pred_op[c]) {
+			case 0: h = a == b; break;
+			case 1: h = a != b; break;
+			case 2: h = a < b; break;
+			case 3: h = a > b; break;
+			case 4: h = a <= b; break;
+			default: h = a >= b; break;
+			}
+		}
+		ok = ok && h;
+	}
+	return ok;
+}
+
+// ---- indexes (layouts: top of this file)
+// KIND_PERFECT: is `key` inside [min, min + range] (compared signed or unsigned), and its bit / payload index
+__device__ __forceinline__ bool perfect_index(uint64_t key, bool key_signed, int64_t min_value, uint64_t range, uint64_t &idx) {
+	bool in_range;
+	if (key_signed) {
+		const int64_t v = (int64_t)key;
+		in_range = v >= min_value && (uint64_t)(v - min_value) <= range;
+		idx = (uint64_t)(v - min_value);
+	} else {
+		in_range = key >= (uint64_t)min_value && key - (uint64_t)min_value <= range;
+		idx = key - (uint64_t)min_value;
+	}
+	return in_range;
+}
+
+// Hash tables are probed linearly, one aligned 32-byte slot group per round trip: a wave waits for its slowest lane, so
+// what counts is the number of DEPENDENT loads of the unluckiest of 64 lanes; at load factor <= 0.5 a group of 4 (2)
+// slots almost always holds the end of the probe sequence.  A group step inspects the slots of one group (a, b: its two
+// 16-byte halves) from slot `first` on; the probe ends at an empty slot (a miss) or at the key.
+// KIND_S8: {key32, row} x 4
+__device__ __forceinline__ void s8_group_step(const uint4 a, const uint4 b, uint32_t first, uint32_t key, bool &searching,
+                                              bool &hit, uint32_t &row) {
+	const uint32_t kk[4] = {a.x, a.z, b.x, b.z};
+	const uint32_t rr[4] = {a.y, a.w, b.y, b.w};
+#pragma unroll
+	for (int j = 0; j < 4; j++) {
+		if (searching && (uint32_t)j >= first) {
+			if (rr[j] == S8_EMPTY_ROW) {
+				searching = false;
+			} else if (kk[j] == key) {
+				hit = true;
+				row = rr[j];
+				searching = false;
+			}
+		}
+	}
+}
+
+// KIND_S16: {key64, start, count} x 2.  The key S16_EMPTY_KEY marks empty slots: its run is the table's side entry
+// (sentinel_start, sentinel_count), found without a probe -- s16_begin_probe says whether a probe is needed
+__device__ __forceinline__ void s16_begin_probe(uint64_t key, bool valid, uint32_t sentinel_start, uint32_t sentinel_count,
+                                          bool &searching, uint32_t &start, uint32_t &count) {
+	start = 0;
+	count = 0;
+	searching = valid;
+	if (valid && key == S16_EMPTY_KEY) {
+		start = sentinel_start;
+		count = sentinel_count;
+		searching = false;
+	}
+}
+__device__ __forceinline__ void s16_group_step(const uint4 e0, const uint4 e1, uint32_t first, uint64_t key, bool &searching,
+                                               uint32_t &start, uint32_t &count) {
+	if (first == 0) {
+		const uint64_t k0 = ((uint64_t)e0.y << 32) | e0.x;
+		if (k0 == S16_EMPTY_KEY) {
+			searching = false;
+		} else if (k0 == key) {
+			start = e0.z;
+			count = e0.w;
+			searching = false;
+		}
+	}
+	if (searching) {
+		const uint64_t k1 = ((uint64_t)e1.y << 32) | e1.x;
+		if (k1 == S16_EMPTY_KEY) {
+			searching = false;
+		} else if (k1 == key) {
+			start = e1.z;
+			count = e1.w;
+			searching = false;
+		}
+	}
+}
+
+// ---- output: a DevOut is a stream of chunks; a wave fills one chunk at a time
+#define NO_CHUNK 0xFFFFFFFFu
+struct OutState {
+	uint32_t cur_chunk; // the chunk this wave fills, NO_CHUNK: none yet
+	uint32_t fill;      // tuples in it
+	bool emit;          // the current unit writes its final tuples
+	bool overflow;      // the chunks ran out (cursor[1] is raised): nothing more is written
+};
+__device__ __forceinline__ OutState out_state_init() {
+	return OutState {NO_CHUNK, 0u, false, false};
+}
+// the valid lanes of ballot `m` take consecutive places in the wave's chunks: `write(place)` stores this lane's tuple at
+// `place` of every slot.  A full chunk leaves its fill in chunk_count[] and the next one is claimed at cursor[0]; when
+// there are no more, cursor[1] is raised and the wave stops emitting
+template <class WriteFn>
+__device__ __forceinline__ void out_claim(const DevOut &out, OutState &os, uint32_t lane, uint64_t m, bool valid, WriteFn &&write) {
+	const uint32_t n = (uint32_t)__popcll(m);
+	const uint32_t rank = lane_rank(m);
+	uint32_t done = 0;
+	while (done < n) {
+		if (os.cur_chunk == NO_CHUNK || os.fill == out.chunk_capacity) {
+			if (os.cur_chunk != NO_CHUNK && lane == 0) {
+				as_global(out.chunk_count)[os.cur_chunk] = os.fill;
+			}
+			uint32_t nc = 0;
+			if (lane == 0) {
+				nc = atomicAdd(&out.cursor[0], 1u);
+			}
+			nc = uni(nc);
+			if (nc >= out.max_chunks) {
+				if (lane == 0) {
+					atomicExch(&out.cursor[1], 1u);
+				}
+				os.overflow = true;
+				os.cur_chunk = NO_CHUNK;
+				os.emit = false;
+				return;
+			}
+			os.cur_chunk = nc;
+			os.fill = 0;
+		}
+		const uint32_t room = out.chunk_capacity - os.fill;
+		const uint32_t take = (n - done) < room ? (n - done) : room;
+		if (valid && rank >= done && rank < done + take) {
+			write((uint64_t)os.cur_chunk * out.chunk_capacity + os.fill + (rank - done));
+		}
+		os.fill += take;
+		done += take;
+	}
+}
+// the wave is done: its last chunk's fill
+__device__ __forceinline__ void out_close(const DevOut &out, const OutState &os, uint32_t lane) {
+	if (os.cur_chunk != NO_CHUNK && lane == 0) {
+		as_global(out.chunk_count)[os.cur_chunk] = os.fill;
+	}
+}
+#endif

@@ -63,24 +63,17 @@ struct FlatStage {
 	uint32_t out_slot;     // emitting runs: the output slot of this join's build id (1 + its index in the original order)
 };
 
-__device__ __forceinline__ uint32_t flat_uni(uint32_t v) {
-	return __builtin_amdgcn_readfirstlane(v);
-}
-__device__ __forceinline__ uint64_t flat_uni64(uint64_t v) {
-	return ((uint64_t)flat_uni((uint32_t)(v >> 32)) << 32) | flat_uni((uint32_t)v);
-}
-
 __device__ __forceinline__ FlatStage flat_load_stage(const StageDesc *d_generic, uint32_t join_index) {
 	const POLR_GLOBAL StageDesc *d = as_global(d_generic);
 	FlatStage s;
 	s.out_slot = 1u + join_index;
-	s.keys = as_global((const uint32_t *)flat_uni64((uint64_t)d->key_data[0]));
-	s.valid = as_global((const uint8_t *)flat_uni64((uint64_t)d->key_valid[0]));
-	s.table = as_global((const uint32_t *)flat_uni64((uint64_t)d->table));
-	const uint32_t kind = flat_uni(d->kind);
-	s.kind_lds = kind | (flat_uni(d->lds_off1) << 8);
-	s.a = kind == KIND_PERFECT ? flat_uni((uint32_t)d->min_value) : flat_uni((uint32_t)d->mask);
-	s.b = flat_uni((uint32_t)d->range);
+	s.keys = as_global(uniptr((const uint32_t *)d->key_data[0]));
+	s.valid = as_global(uniptr(d->key_valid[0]));
+	s.table = as_global(uniptr((const uint32_t *)d->table));
+	const uint32_t kind = uni(d->kind);
+	s.kind_lds = kind | (uni(d->lds_off1) << 8);
+	s.a = kind == KIND_PERFECT ? uni((uint32_t)d->min_value) : uni((uint32_t)d->mask);
+	s.b = uni((uint32_t)d->range);
 	return s;
 }
 
@@ -96,17 +89,12 @@ struct FlatCtx {
 	// emitting runs (a materialising sink behind a bank of perfect tables): the final tuples as row ids, chunked like a
 	// DataChunk stream -- slot 0 the probe row, slot 1 + j the build id of join j = its key's offset in the perfect table
 	DevOut out;
-	bool emit, overflow;
-	uint32_t cur_chunk, fill;
+	OutState os;
 	POLR_LDS unsigned long long *fused_lds; // the workgroup's group cells of a fused GROUP BY sink, when they fit in LDS
 	// stage 0's next step, requested one step ahead (the key stream's HBM round trip overlaps the current step)
 	uint4 pf0, pf1;
 	uint64_t pf_pos; // source position the prefetched keys belong to; ~0: none
 };
-
-__device__ __forceinline__ uint32_t flat_rank(uint64_t m) {
-	return __builtin_amdgcn_mbcnt_hi((uint32_t)(m >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)m, 0));
-}
 
 // ---- membership test in two halves: issue (addresses + loads in flight), then resolve -------------------------
 // perfect table: 32-bit modular arithmetic, exact for signed and unsigned 4-byte keys while [min, max] lies inside the
@@ -174,6 +162,8 @@ __device__ __forceinline__ void flat_hash_lookup(const FlatStage &s, const uint3
 #pragma unroll
 			for (int i = 0; i < 4; i++) {
 				if (searching[i]) {
+					// (s8_group_step of polr_device.h, spelled out: called here it leaves the same result, but the flat
+					// kernels' register allocation changes -- 7 more spilled SGPRs at K = 2)
 					const uint32_t kk[4] = {a[i].x, a[i].z, b[i].x, b[i].z};
 					const uint32_t rr[4] = {a[i].y, a[i].w, b[i].y, b[i].w};
 #pragma unroll
@@ -215,23 +205,6 @@ __device__ __forceinline__ void flat_lookup(const FlatStage &s, const POLR_LDS u
 #define POLR_FLAT_EMIT 0 // 1: the build whose last join can write row ids (a counting run never pays for that code:
                          // inlined at every place a stage emits it cost the SF100 headline 6 % -- 96 more spilled SGPRs)
 #endif
-#define FLAT_NO_CHUNK 0xFFFFFFFFu
-// one cell of a column of the aggregate sinks, as a signed 64-bit value (narrow unsigned values zero-extended)
-__device__ __forceinline__ long long flat_sink_cell(const DevCol &c, uint32_t row) {
-	const POLR_GLOBAL uint8_t *p = as_global(c.data) + (uint64_t)row * c.width;
-	const bool sx = (c.flags & 1u) != 0;
-	switch (c.width) {
-	case 1:
-		return sx ? (long long)*(const POLR_GLOBAL int8_t *)p : (long long)*p;
-	case 2:
-		return sx ? (long long)*(const POLR_GLOBAL int16_t *)p : (long long)*(const POLR_GLOBAL uint16_t *)p;
-	case 4:
-		return sx ? (long long)*(const POLR_GLOBAL int32_t *)p : (long long)*(const POLR_GLOBAL uint32_t *)p;
-	default:
-		return *(const POLR_GLOBAL long long *)p;
-	}
-}
-
 // the fused GROUP BY sink (FusedSink, polr_device.h): slot 0 = the probe row, slot 1 + j = the build id of join j, which
 // the stage that probed join j holds (id[p], out_slot = 1 + j).  One lane = one surviving tuple.
 template <int K>
@@ -256,7 +229,7 @@ __device__ __forceinline__ void flat_fused_accumulate(FlatCtx<K> &c, uint32_t ro
 			ok = false;
 			break;
 		}
-		const unsigned long long off = (unsigned long long)(flat_sink_cell(gk.src, r) - gk.min_value);
+		const unsigned long long off = (unsigned long long)(load_col_cell(gk.src, r) - gk.min_value);
 		if (off >= gk.n_values) {
 			ok = false;
 			break;
@@ -295,7 +268,7 @@ __device__ __forceinline__ void flat_fused_accumulate(FlatCtx<K> &c, uint32_t ro
 			add(2u + 2u * a, 1ull);
 		}
 		if (ag.fn == POLR_DEV_AGG_SUM) {
-			add(1u + 2u * a, (unsigned long long)flat_sink_cell(ag.src, r));
+			add(1u + 2u * a, (unsigned long long)load_col_cell(ag.src, r));
 		}
 	}
 }
@@ -311,9 +284,7 @@ __device__ __forceinline__ void flat_out_write(FlatCtx<K> &c, uint32_t pos, bool
 	if (n == 0) {
 		return;
 	}
-	const uint32_t rank = flat_rank(m);
 	POLR_GLOBAL uint32_t *ids = as_global(c.out.ids);
-	POLR_GLOBAL uint32_t *chunk_count = as_global(c.out.chunk_count);
 	uint32_t row = 0, id[K];
 	if (valid) {
 		const uint64_t tp = c.unit_begin + pos;
@@ -333,44 +304,15 @@ __device__ __forceinline__ void flat_out_write(FlatCtx<K> &c, uint32_t pos, bool
 			id[p] = p < (int)c.k ? c.st[p].keys[row] - c.st[p].a : 0u;
 		}
 	}
-	uint32_t done = 0;
-	while (done < n) {
-		if (c.cur_chunk == FLAT_NO_CHUNK || c.fill == c.out.chunk_capacity) {
-			if (c.cur_chunk != FLAT_NO_CHUNK && c.lane == 0) {
-				chunk_count[c.cur_chunk] = c.fill;
-			}
-			uint32_t nc = 0;
-			if (c.lane == 0) {
-				nc = atomicAdd(&c.out.cursor[0], 1u);
-			}
-			nc = flat_uni(nc);
-			if (nc >= c.out.max_chunks) {
-				if (c.lane == 0) {
-					atomicExch(&c.out.cursor[1], 1u);
-				}
-				c.overflow = true;
-				c.cur_chunk = FLAT_NO_CHUNK;
-				c.emit = false;
-				return;
-			}
-			c.cur_chunk = nc;
-			c.fill = 0;
-		}
-		const uint32_t room = c.out.chunk_capacity - c.fill;
-		const uint32_t take = (n - done) < room ? (n - done) : room;
-		if (valid && rank >= done && rank < done + take) {
-			const uint64_t base = (uint64_t)c.cur_chunk * c.out.chunk_capacity + c.fill + (rank - done);
-			ids[base] = row;
+	out_claim(c.out, c.os, c.lane, m, valid, [&](uint64_t place) {
+		ids[place] = row;
 #pragma unroll
-			for (int p = 0; p < K; p++) {
-				if (p < (int)c.k) {
-					ids[(uint64_t)c.st[p].out_slot * c.out.slot_stride + base] = id[p];
-				}
+		for (int p = 0; p < K; p++) {
+			if (p < (int)c.k) {
+				ids[(uint64_t)c.st[p].out_slot * c.out.slot_stride + place] = id[p];
 			}
 		}
-		c.fill += take;
-		done += take;
-	}
+	});
 }
 
 // survivors of stage POS: count them; push their unit positions to the next stage's queue unless POS is the last join
@@ -379,7 +321,7 @@ __device__ __forceinline__ void flat_emit(FlatCtx<K> &c, const uint32_t (&pos)[F
 	const bool last = POS + 1 >= K || POS + 1 == (int)c.k;
 	uint32_t total = 0;
 #if POLR_FLAT_EMIT
-	if (last && c.emit) {
+	if (last && c.os.emit) {
 		// (ONE copy of the sink's code per place a stage emits, not F: the loop stays a loop -- the element is picked
 		// with selects -- or the emitting build is 2.4 ms where the counting build is 1.5)
 #pragma unroll 1
@@ -403,7 +345,7 @@ __device__ __forceinline__ void flat_emit(FlatCtx<K> &c, const uint32_t (&pos)[F
 			const uint64_t m = __ballot(hit[i]);
 			const uint32_t n = (uint32_t)__popcll(m);
 			if (!last && hit[i]) {
-				qq[qs + flat_rank(m)] = (uint16_t)pos[i];
+				qq[qs + lane_rank(m)] = (uint16_t)pos[i];
 			}
 			qs += n;
 			total += n;

@@ -55,46 +55,13 @@
 #endif
 #define GEN_STEP (64 * GEN_F)   // candidates per step
 #define GEN_SCRATCH_DWORDS (2 * GEN_STEP) // run starts, inclusive prefix of run lengths
-#define GEN_NO_CHUNK 0xFFFFFFFFu
 
-__device__ __forceinline__ uint32_t gen_uni(uint32_t v) {
-	return __builtin_amdgcn_readfirstlane(v);
-}
-__device__ __forceinline__ uint32_t gen_rank(uint64_t m) {
-	return __builtin_amdgcn_mbcnt_hi((uint32_t)(m >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)m, 0));
-}
-__device__ __forceinline__ uint64_t gen_wave_sum64(uint64_t v) { // the same sum in every lane
-#pragma unroll
-	for (int d = 32; d > 0; d >>= 1) {
-		v += __shfl_xor(v, d, 64);
-	}
-	return v;
-}
 __device__ __forceinline__ uint32_t gen_lane_get(uint32_t v, uint32_t lane_uniform) {
 	return (uint32_t)__builtin_amdgcn_readlane((int)v, (int)lane_uniform);
 }
 __device__ __forceinline__ void gen_lane_set(uint32_t &v, uint32_t lane_uniform, uint32_t value_uniform) {
 	// (v_writelane_b32 has no builtin in this compiler: a compare against the lane id and a select)
 	v = (__builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdgcn_mbcnt_lo(~0u, 0u)) == lane_uniform) ? value_uniform : v;
-}
-
-__device__ __forceinline__ uint64_t gen_load_cell(const POLR_GLOBAL uint8_t *p, uint32_t width, bool sign_extend) {
-	switch (width) {
-	case 1: {
-		const uint8_t v = *p;
-		return sign_extend ? (uint64_t)(int64_t)(int8_t)v : (uint64_t)v;
-	}
-	case 2: {
-		const uint16_t v = *(const POLR_GLOBAL uint16_t *)p;
-		return sign_extend ? (uint64_t)(int64_t)(int16_t)v : (uint64_t)v;
-	}
-	case 4: {
-		const uint32_t v = *(const POLR_GLOBAL uint32_t *)p;
-		return sign_extend ? (uint64_t)(int64_t)(int32_t)v : (uint64_t)v;
-	}
-	default:
-		return *(const POLR_GLOBAL uint64_t *)p;
-	}
 }
 
 // the part of a stage descriptor a step keeps in scalar registers
@@ -143,21 +110,6 @@ __device__ __forceinline__ GenStage gen_load_stage(const POLR_CONST StageDesc *d
 }
 
 template <int W>
-struct GenTuple {
-	uint32_t s[W];
-};
-
-template <int W>
-__device__ __forceinline__ uint32_t gen_slot(const GenTuple<W> &t, int32_t slot) {
-	uint32_t v = t.s[0];
-#pragma unroll
-	for (int q = 1; q < W; q++) {
-		v = (q == slot) ? t.s[q] : v;
-	}
-	return v;
-}
-
-template <int W>
 struct GenCtx {
 	uint32_t k, lane, qcap, full; // qcap: entries per queue; full = qcap / 2: a deeper stage runs when it holds this many
 	POLR_LDS uint32_t *q;         // queue that FEEDS stage p (p >= 1): q + (p - 1) * W * qcap, slot-major [W][qcap]
@@ -173,124 +125,46 @@ struct GenCtx {
 	bool mult; // tuple slot W - 1 carries the tuple's multiplicity (counting runs of pipelines with foldable joins)
 	// output (row ids)
 	DevOut out;
-	bool emit, overflow;
-	uint32_t cur_chunk, fill;
+	OutState os;
 };
 
 // ---- keys --------------------------------------------------------------------------------------------------------------
-#if POLR_EXT
-// composite key in packed form (KeyPack): per column (value - min) << shift; a value outside the build side's
-// [min, min + range] cannot match
-template <int W>
-__device__ __attribute__((noinline)) bool gen_fetch_key_packed(const POLR_GLOBAL StageExt *d, uint32_t n_keys, const GenTuple<W> &t,
-                                                               uint64_t &key) {
-	bool valid = true;
-	key = 0;
-	for (uint32_t c = 0; c < n_keys; c++) {
-		const uint32_t row = gen_slot<W>(t, d->key_slot[c]);
-		const POLR_GLOBAL uint8_t *kv = (const POLR_GLOBAL uint8_t *)d->key_valid[c];
-		const uint32_t w = d->key_width[c];
-		// (by VALUE: the probe column's own width and signedness -- a CAST'ed key; a value outside the build side's range
-		// cannot match, whichever type could or could not hold it)
-		const uint64_t v = gen_load_cell((const POLR_GLOBAL uint8_t *)d->key_data[c] + (uint64_t)row * w, w, d->key_sx[c] != 0);
-		uint64_t off = v - (uint64_t)d->pack.min[c];
-		if (kv && !kv[row]) {
-			if ((d->pack.null_eq >> c) & 1u) {
-				off = d->pack.range[c] + 1u; // IS NOT DISTINCT FROM: NULL is a key value of its own
-			} else {
-				valid = false;
-			}
-		} else if (off > d->pack.range[c]) {
-			valid = false;
-		}
-		key |= off << d->pack.shift[c];
-	}
-	if (!valid) {
-		key = 0;
-	}
-	return valid;
-}
-
-// the join's non-equality conditions on one (tuple, build row) pair: both sides valid and `left OP right`
-template <int W>
-__device__ __attribute__((noinline)) bool gen_preds_hold(const POLR_GLOBAL StageExt *d, uint32_t n_preds, const GenTuple<W> &t,
-                                                         uint32_t id) {
-	bool ok = true;
-	for (uint32_t c = 0; c < n_preds; c++) {
-		const uint32_t row = gen_slot<W>(t, d->pred_slot[c]);
-		const uint32_t w = d->pred_width[c];
-		const bool sx = d->pred_sx[c] != 0;
-		const POLR_GLOBAL uint8_t *lv = (const POLR_GLOBAL uint8_t *)d->pred_valid[c];
-		const POLR_GLOBAL uint8_t *rv = (const POLR_GLOBAL uint8_t *)d->pred_bvalid[c];
-		if ((lv && !lv[row]) || (rv && !rv[id])) {
-			ok = false;
-		}
-		if (d->pred_op[c] == POLR_PRED_STR_EQ) { // the strings behind a VARCHAR key's hash
-			ok = ok && polr_str_cells_equal(d->pred_data[c] + (uint64_t)row * 16u, d->pred_bdata[c] + (uint64_t)id * 16u);
-			continue;
-		}
-		const uint64_t l = gen_load_cell((const POLR_GLOBAL uint8_t *)d->pred_data[c] + (uint64_t)row * w, w, sx);
-		const uint64_t r = gen_load_cell((const POLR_GLOBAL uint8_t *)d->pred_bdata[c] + (uint64_t)id * w, w, sx);
-		bool h;
-		if (w == 8 && !sx) {
-			switch (d->pred_op[c]) {
-			case 0: h = l == r; break; // (POLR_CMP_EQ: the verifying comparison behind a hashed composite key)
-			case 1: h = l != r; break;
-			case 2: h = l < r; break;
-			case 3: h = l > r; break;
-			case 4: h = l <= r; break;
-			default: h = l >= r; break;
-			}
-		} else {
-			const int64_t a = (int64_t)l, b = (int64_t)r; // (narrow unsigned values are zero-extended: same order)
-			switch (d->pred_op[c]) {
-			case 0: h = a == b; break;
-			case 1: h = a != b; break;
-			case 2: h = a < b; break;
-			case 3: h = a > b; break;
-			case 4: h = a <= b; break;
-			default: h = a >= b; break;
-			}
-		}
-		ok = ok && h;
-	}
-	return ok;
-}
-#endif
-
 // key of one candidate; false for NULL (NULL never matches: join_hashtable.cpp:170-192,
 // perfect_hash_join_executor.cpp:272-277) and for inactive lanes
 template <int W>
-__device__ __forceinline__ bool gen_fetch_key(const GenStage &s, const GenTuple<W> &t, bool active, uint64_t &key) {
+__device__ __forceinline__ bool gen_fetch_key(const GenStage &s, const Tuple<W> &t, bool active, uint64_t &key) {
 	key = 0;
 	if (!active) {
 		return false;
 	}
 #if POLR_EXT
 	if (s.xflags & 1u) {
-		return gen_fetch_key_packed<W>(s.ext, s.n_keys, t, key);
+		return fetch_key_packed<W>(s.ext, s.n_keys, t, key);
 	}
 #endif
 	const bool sx = s.kind == KIND_PERFECT && s.key_signed != 0;
-	const uint32_t row0 = gen_slot<W>(t, s.key_slot0);
+	const uint32_t row0 = tuple_slot<W>(t, s.key_slot0);
 	bool valid = !(s.key_valid0 && !s.key_valid0[row0]);
 	if (s.key_width0 == 4) { // (the common case: one aligned dword per key)
 		const uint32_t v = ((const POLR_GLOBAL uint32_t *)s.key_data0)[row0];
 		key = sx ? (uint64_t)(int64_t)(int32_t)v : (uint64_t)v;
 	} else {
-		key = gen_load_cell(s.key_data0 + (uint64_t)row0 * s.key_width0, s.key_width0, sx);
+		key = load_cell(s.key_data0 + (uint64_t)row0 * s.key_width0, s.key_width0, sx);
 	}
 	if (s.n_keys > 1) {
-		const uint32_t row1 = gen_slot<W>(t, s.key_slot1);
+		const uint32_t row1 = tuple_slot<W>(t, s.key_slot1);
 		if (s.key_valid1 && !s.key_valid1[row1]) {
 			valid = false;
 		}
-		key |= gen_load_cell(s.key_data1 + (uint64_t)row1 * s.key_width1, s.key_width1, false) << 32;
+		key |= load_cell(s.key_data1 + (uint64_t)row1 * s.key_width1, s.key_width1, false) << 32;
 	}
 	return valid;
 }
 
 // ---- index lookups, GEN_F per lane in flight ---------------------------------------------------------------------------
+// (perfect_index, s8_group_step / s16_group_step and out_claim of polr_device.h, spelled out here and in gen_out_write:
+// called, they leave the same results but the generic kernels spill up to 26 more SGPRs -- and ran 2 % slower on the
+// JOB q18 / JOB-light shapes)
 // every lookup yields (start, count): perfect / unique-key tables count <= 1 with start = the build id itself;
 // repeated-key tables the run [start, start + count) of rowids[]
 __device__ __forceinline__ void gen_lookup_perfect(const GenStage &s, const uint64_t (&key)[GEN_F], const bool (&valid)[GEN_F],
@@ -439,48 +313,48 @@ __device__ __forceinline__ void gen_lookup_s16(const GenStage &s, const uint64_t
 // ---- output --------------------------------------------------------------------------------------------------------------
 // the final tuples of the wave's current unit go to its current output chunk (a DataChunk stream of row ids)
 template <int W>
-__device__ __forceinline__ void gen_out_write(GenCtx<W> &c, const GenTuple<W> &t, bool valid) {
-	if (!c.emit || c.out.ids == nullptr) {
+__device__ __forceinline__ void gen_out_write(GenCtx<W> &c, const Tuple<W> &t, bool valid) {
+	if (!c.os.emit || c.out.ids == nullptr) {
 		return;
 	}
 	const uint64_t m = __ballot(valid);
 	const uint32_t n = (uint32_t)__popcll(m);
-	const uint32_t rank = gen_rank(m);
+	const uint32_t rank = lane_rank(m);
 	POLR_GLOBAL uint32_t *ids = as_global(c.out.ids);
 	POLR_GLOBAL uint32_t *chunk_count = as_global(c.out.chunk_count);
 	uint32_t done = 0;
 	while (done < n) {
-		if (c.cur_chunk == GEN_NO_CHUNK || c.fill == c.out.chunk_capacity) {
-			if (c.cur_chunk != GEN_NO_CHUNK && c.lane == 0) {
-				chunk_count[c.cur_chunk] = c.fill;
+		if (c.os.cur_chunk == NO_CHUNK || c.os.fill == c.out.chunk_capacity) {
+			if (c.os.cur_chunk != NO_CHUNK && c.lane == 0) {
+				chunk_count[c.os.cur_chunk] = c.os.fill;
 			}
 			uint32_t nc = 0;
 			if (c.lane == 0) {
 				nc = atomicAdd(&c.out.cursor[0], 1u);
 			}
-			nc = gen_uni(nc);
+			nc = uni(nc);
 			if (nc >= c.out.max_chunks) {
 				if (c.lane == 0) {
 					atomicExch(&c.out.cursor[1], 1u);
 				}
-				c.overflow = true;
-				c.cur_chunk = GEN_NO_CHUNK;
-				c.emit = false;
+				c.os.overflow = true;
+				c.os.cur_chunk = NO_CHUNK;
+				c.os.emit = false;
 				return;
 			}
-			c.cur_chunk = nc;
-			c.fill = 0;
+			c.os.cur_chunk = nc;
+			c.os.fill = 0;
 		}
-		const uint32_t room = c.out.chunk_capacity - c.fill;
+		const uint32_t room = c.out.chunk_capacity - c.os.fill;
 		const uint32_t take = (n - done) < room ? (n - done) : room;
 		if (valid && rank >= done && rank < done + take) {
-			const uint64_t base = (uint64_t)c.cur_chunk * c.out.chunk_capacity + c.fill + (rank - done);
+			const uint64_t base = (uint64_t)c.os.cur_chunk * c.out.chunk_capacity + c.os.fill + (rank - done);
 #pragma unroll
 			for (int i = 0; i < W; i++) {
 				ids[(uint64_t)i * c.out.slot_stride + base] = t.s[i];
 			}
 		}
-		c.fill += take;
+		c.os.fill += take;
 		done += take;
 	}
 }
@@ -488,12 +362,12 @@ __device__ __forceinline__ void gen_out_write(GenCtx<W> &c, const GenTuple<W> &t
 // one sub-batch of (tuple, build id) pairs leaves stage `pos`: conditions, counter, next queue or output.
 // qs_next: fill of the next queue (updated); returns the number of tuples that passed (the sum of their multiplicities)
 template <int W>
-__device__ __forceinline__ uint64_t gen_emit(GenCtx<W> &c, const GenStage &s, uint32_t pos, bool last, GenTuple<W> t, uint32_t id,
+__device__ __forceinline__ uint64_t gen_emit(GenCtx<W> &c, const GenStage &s, uint32_t pos, bool last, Tuple<W> t, uint32_t id,
                                              bool valid, uint32_t &qs_next) {
 #if POLR_EXT
 	if (s.xflags >> 8) {
 		// (inactive lanes carry arbitrary ids: evaluate on the pairs only)
-		valid = valid && gen_preds_hold<W>(s.ext, s.xflags >> 8, t, id);
+		valid = valid && preds_hold<W>(s.ext, s.xflags >> 8, t, id);
 	}
 #endif
 #pragma unroll
@@ -507,7 +381,7 @@ __device__ __forceinline__ uint64_t gen_emit(GenCtx<W> &c, const GenStage &s, ui
 	} else {
 		if (valid) {
 			POLR_LDS uint32_t *qq = c.q + (size_t)pos * W * c.qcap; // (the queue that feeds stage pos + 1)
-			const uint32_t idx = qs_next + gen_rank(m);
+			const uint32_t idx = qs_next + lane_rank(m);
 #pragma unroll
 			for (int i = 0; i < W; i++) {
 				qq[i * c.qcap + idx] = t.s[i];
@@ -516,27 +390,16 @@ __device__ __forceinline__ uint64_t gen_emit(GenCtx<W> &c, const GenStage &s, ui
 		qs_next += n;
 	}
 	if (c.mult) {
-		return gen_wave_sum64(valid ? (uint64_t)t.s[W - 1] : 0ull);
+		return wave_sum64(valid ? (uint64_t)t.s[W - 1] : 0ull);
 	}
 	return n;
-}
-
-__device__ __forceinline__ uint32_t gen_inclusive_scan(uint32_t v, uint32_t lane) {
-#pragma unroll
-	for (int d = 1; d < 64; d <<= 1) {
-		const uint32_t o = __shfl_up(v, d, 64);
-		if ((int)lane >= d) {
-			v += o;
-		}
-	}
-	return v;
 }
 
 // candidate ci of the step that stage `pos` is working on: the tuple at the source position / queue entry it stands for
 // (candidates are numbered in the order they are consumed: the source front to back, a queue top to bottom)
 template <int W>
-__device__ __forceinline__ GenTuple<W> gen_candidate(const GenCtx<W> &c, uint32_t pos, uint32_t qs, uint32_t ci, bool active) {
-	GenTuple<W> t;
+__device__ __forceinline__ Tuple<W> gen_candidate(const GenCtx<W> &c, uint32_t pos, uint32_t qs, uint32_t ci, bool active) {
+	Tuple<W> t;
 #pragma unroll
 	for (int q = 0; q < W; q++) {
 		t.s[q] = 0;
@@ -575,7 +438,7 @@ __device__ __forceinline__ void gen_step(GenCtx<W> &c, const uint32_t pos) {
 		// the pending run of this stage: candidate 0 (still at the source front / the queue top) x its next build rows
 		const uint32_t gstart = gen_lane_get(c.v_gstart, pos);
 		const uint32_t n_emit = grem < room ? grem : room;
-		const GenTuple<W> t0 = gen_candidate<W>(c, pos, qs, 0u, true);
+		const Tuple<W> t0 = gen_candidate<W>(c, pos, qs, 0u, true);
 		for (uint32_t o0 = 0; o0 < n_emit; o0 += GEN_STEP) {
 			uint32_t id[GEN_F];
 #pragma unroll
@@ -610,7 +473,7 @@ __device__ __forceinline__ void gen_step(GenCtx<W> &c, const uint32_t pos) {
 		if (s.unique == 1 && n > room) {
 			n = room; // (at most one output per candidate: take what the next queue has room for)
 		}
-		GenTuple<W> t[GEN_F];
+		Tuple<W> t[GEN_F];
 		bool act[GEN_F], valid[GEN_F];
 		uint64_t key[GEN_F];
 		uint32_t start[GEN_F], count[GEN_F];
@@ -673,7 +536,7 @@ __device__ __forceinline__ void gen_step(GenCtx<W> &c, const uint32_t pos) {
 				consumed = 0;
 #pragma unroll
 				for (int i = 0; i < GEN_F; i++) {
-					const uint32_t incl = carry + gen_inclusive_scan(count[i] != 0u ? 1u : 0u, c.lane);
+					const uint32_t incl = carry + wave_inclusive_scan(count[i] != 0u ? 1u : 0u, c.lane);
 					carry = gen_lane_get(incl, 63);
 					keep[i] = act[i] && incl <= room;
 					consumed += (uint32_t)__popcll(__ballot(keep[i]));
@@ -702,13 +565,13 @@ __device__ __forceinline__ void gen_step(GenCtx<W> &c, const uint32_t pos) {
 			uint32_t incl[GEN_F];
 #pragma unroll
 			for (int i = 0; i < GEN_F; i++) {
-				incl[i] = carry + gen_inclusive_scan(count[i], c.lane);
+				incl[i] = carry + wave_inclusive_scan(count[i], c.lane);
 				sc_start[64 * i + c.lane] = start[i];
 				sc_pref[64 * i + c.lane] = incl[i];
 				carry = gen_lane_get(incl[i], 63);
 			}
 			const uint32_t total = carry;
-			if (last && !c.emit && (s.xflags >> 8) == 0) {
+			if (last && !c.os.emit && (s.xflags >> 8) == 0) {
 				// a counting sink: the run lengths are all it needs
 				if (c.mult) {
 					uint64_t w = 0;
@@ -716,7 +579,7 @@ __device__ __forceinline__ void gen_step(GenCtx<W> &c, const uint32_t pos) {
 					for (int i = 0; i < GEN_F; i++) {
 						w += (uint64_t)t[i].s[W - 1] * (uint64_t)count[i];
 					}
-					produced = gen_wave_sum64(w);
+					produced = wave_sum64(w);
 				} else {
 					produced = total;
 				}
@@ -769,7 +632,7 @@ __device__ __forceinline__ void gen_step(GenCtx<W> &c, const uint32_t pos) {
 #pragma unroll
 					for (int j = 0; j < GEN_F; j++) {
 						if (o0 + 64u * j < total_m) {
-							const GenTuple<W> tj = gen_candidate<W>(c, pos, qs, src[j], ov[j]);
+							const Tuple<W> tj = gen_candidate<W>(c, pos, qs, src[j], ov[j]);
 							produced += gen_emit<W>(c, s, pos, last, tj, id[j], ov[j], qs_next);
 						}
 					}
@@ -814,7 +677,7 @@ __device__ __forceinline__ void gen_run_unit(GenCtx<W> &c, uint32_t share_after,
 			}
 			pick = (uint32_t)__builtin_ctzll(waiting);
 		}
-		gen_step<W>(c, gen_uni(pick));
+		gen_step<W>(c, uni(pick));
 		if (++steps >= share_after) {
 			steps = 0;
 			share();

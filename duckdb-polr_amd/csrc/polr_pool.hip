@@ -87,10 +87,7 @@ __global__ __launch_bounds__(1024) void polr_pool_flat_kernel(const DevPipeline 
 		c.st[p].kind_lds = c.st[p].a = c.st[p].b = c.st[p].out_slot = 0;
 	}
 	c.out = out;
-	c.emit = false;
-	c.overflow = false;
-	c.cur_chunk = FLAT_NO_CHUNK;
-	c.fill = 0;
+	c.os = out_state_init();
 #if POLR_FLAT_EMIT
 	c.fused_lds = fused_lds;
 #else
@@ -121,7 +118,7 @@ __global__ __launch_bounds__(1024) void polr_pool_flat_kernel(const DevPipeline 
 			cur_path = u.path;
 		}
 #if POLR_FLAT_EMIT
-		c.emit = u.emit != 0 && out.ids != nullptr && !c.overflow;
+		c.os.emit = u.emit != 0 && out.ids != nullptr && !c.os.overflow;
 #endif
 		c.unit_begin = u.begin;
 		c.in_pos = u.begin;
@@ -149,9 +146,7 @@ __global__ __launch_bounds__(1024) void polr_pool_flat_kernel(const DevPipeline 
 		u = nxt;
 	}
 #if POLR_FLAT_EMIT
-	if (c.cur_chunk != FLAT_NO_CHUNK && c.lane == 0) {
-		out.chunk_count[c.cur_chunk] = c.fill;
-	}
+	out_close(out, c.os, c.lane);
 	if (fused_words) {
 		// every wave of the workgroup has left its loop: flush the cells that were touched to the workgroup's table
 		__syncthreads();

@@ -9,19 +9,6 @@ static __device__ unsigned long long polr_diag_router[16];
 #endif
 #include "polr_pool_device.h"
 
-__device__ __forceinline__ uint32_t uni(uint32_t v) {
-	return __builtin_amdgcn_readfirstlane(v);
-}
-__device__ __forceinline__ uint64_t uni64(uint64_t v) {
-	uint32_t lo = __builtin_amdgcn_readfirstlane((uint32_t)v);
-	uint32_t hi = __builtin_amdgcn_readfirstlane((uint32_t)(v >> 32));
-	return ((uint64_t)hi << 32) | lo;
-}
-template <class T>
-__device__ __forceinline__ const T *uniptr(const T *p) {
-	return (const T *)uni64((uint64_t)p);
-}
-
 // LDS a router wave needs: state + round scratch | saved state of a rehearsal | window of >= 256 chunk boundaries
 #define POOL_ROUTER_STATE ((POLR_RES_ROUTER_DWORDS + 3u) & ~3u)
 #define POOL_ROUTER_SAVE ((POLR_RES_HOT_DWORDS + 3u) & ~3u)

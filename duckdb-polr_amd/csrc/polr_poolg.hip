@@ -85,10 +85,7 @@ __global__ __launch_bounds__(64 * POOLG_WAVES, 4) void polr_pool_gen_kernel(cons
 	c.mult = uni(pipe->mult) != 0;
 	c.in_pos = c.in_end = 0;
 	c.out = out;
-	c.emit = false;
-	c.overflow = false;
-	c.cur_chunk = GEN_NO_CHUNK;
-	c.fill = 0;
+	c.os = out_state_init();
 	const POLR_CONST StageDesc *stages = (const POLR_CONST StageDesc *)uni64((uint64_t)pipe->stages);
 	c.stages = stages;
 	PoolUnit u;
@@ -216,7 +213,7 @@ __global__ __launch_bounds__(64 * POOLG_WAVES, 4) void polr_pool_gen_kernel(cons
 	while (polr_pool_next_unit(pp, u, c.lane)) {
 		TL_GOT
 		c.stages = stages + (size_t)u.path * POLR_KMAX;
-		c.emit = u.emit != 0 && !c.overflow;
+		c.os.emit = u.emit != 0 && !c.os.overflow;
 		if (u.kind == POLR_POOL_KIND_CONT) {
 			// a piece of somebody's unit: u.begin names the record it waits in
 			__builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
@@ -260,9 +257,7 @@ __global__ __launch_bounds__(64 * POOLG_WAVES, 4) void polr_pool_gen_kernel(cons
 		poolg_arrive(execs, u, ring, k, c.v_cnt_lo, c.v_cnt_hi, c.lane, POLR_POOL_TOKENS >> u.level);
 		TL_DONE(u)
 	}
-	if (c.cur_chunk != GEN_NO_CHUNK && c.lane == 0) {
-		out.chunk_count[c.cur_chunk] = c.fill;
-	}
+	out_close(out, c.os, c.lane);
 }
 
 // ---- launch ------------------------------------------------------------------------------------

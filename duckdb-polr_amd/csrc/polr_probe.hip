@@ -98,10 +98,7 @@ __global__ __launch_bounds__(256) void polr_path_kernel(const DevPipeline *__res
 	c.pend_wide = 0;
 	c.flush_token = 0;
 	c.out = out;
-	c.emit = false;
-	c.cur_chunk = NO_CHUNK;
-	c.fill = 0;
-	c.overflow = false;
+	c.os = out_state_init();
 
 	const StageDesc *stages = uniptr(pipe->stages);
 	int64_t cur_round = -1;
@@ -131,7 +128,7 @@ __global__ __launch_bounds__(256) void polr_path_kernel(const DevPipeline *__res
 			for (uint32_t i = c.lane; i < K * STAGE_DESC_DWORDS; i += 64) {
 				dst[i] = src[i];
 			}
-			c.emit = uni(rounds[r].emit) != 0 && !c.overflow;
+			c.os.emit = uni(rounds[r].emit) != 0 && !c.os.overflow;
 			c.wide_mask = stage_wide_mask<W, K>(src, c.k);
 		}
 		const uint64_t rb = uni64(rounds[r].begin);
@@ -151,9 +148,7 @@ __global__ __launch_bounds__(256) void polr_path_kernel(const DevPipeline *__res
 		STAMP(3)
 		flush_counts(c, counts, cur_round);
 	}
-	if (c.cur_chunk != NO_CHUNK && c.lane == 0) {
-		out.chunk_count[c.cur_chunk] = c.fill;
-	}
+	out_close(out, c.os, c.lane);
 	STAMP(4)
 	if (sr.mpx) {
 		// Arrival: every busy workgroup publishes its counters (device-scope atomics above), then takes a

@@ -1,6 +1,6 @@
-// duckdb-polr_amd/csrc/polr_probe_device.h -- the per-wave probe pipeline (device code) shared by the path kernel
-// (polr_probe.hip: one launch per routed round) and the pool kernel (polr_pool.hip: the whole run in one launch).
-// See polr_probe.hip for the execution model.  Needs POLR_K (compiled stage count) defined by the including file.
+// duckdb-polr_amd/csrc/polr_probe_device.h -- the per-wave probe pipeline (device code) of the path kernel
+// (polr_probe.hip: one launch per routed round).  See polr_probe.hip for the execution model.  Needs POLR_K (compiled
+// stage count) defined by the including file.  Cells, keys, table probes and output chunks: polr_device.h.
 #pragma once
 
 // POLR_EXT = 1 builds the generic pipeline with its uncommon parts (composite keys in packed form, non-equality join
@@ -46,7 +46,6 @@ template <int W, int K>
 __device__ __host__ constexpr int per_wave_dwords() {
 	return K * STAGE_DESC_DWORDS + qtotal<W, K>() + K * 64 * 2 + 64 * WIDE + wide_pend_slots<W, K>() * 64 * WIDE * 2;
 }
-#define NO_CHUNK 0xFFFFFFFFu
 
 // diagnostic build only (-DPOLR_DIAG_STAMPS): wall-clock stamps of workgroup 0 / wave 0 at the phase
 // boundaries of a self-routing launch, written to sr.stamps[iter*8 + i] (never compiled into the product)
@@ -58,46 +57,6 @@ __device__ __host__ constexpr int per_wave_dwords() {
 #else
 #define STAMP(i)
 #endif
-
-__device__ __forceinline__ uint32_t uni(uint32_t v) {
-	return __builtin_amdgcn_readfirstlane(v);
-}
-__device__ __forceinline__ uint64_t uni64(uint64_t v) {
-	uint32_t lo = __builtin_amdgcn_readfirstlane((uint32_t)v);
-	uint32_t hi = __builtin_amdgcn_readfirstlane((uint32_t)(v >> 32));
-	return ((uint64_t)hi << 32) | lo;
-}
-template <class T>
-__device__ __forceinline__ const T *uniptr(const T *p) {
-	return (const T *)uni64((uint64_t)p);
-}
-__device__ __forceinline__ uint32_t lane_rank(uint64_t mask) {
-	return __builtin_amdgcn_mbcnt_hi((uint32_t)(mask >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)mask, 0));
-}
-
-__device__ __forceinline__ uint64_t load_cell(const uint8_t *p, uint32_t width, bool sign_extend) {
-	switch (width) {
-	case 1: {
-		uint8_t v = *p;
-		return sign_extend ? (uint64_t)(int64_t)(int8_t)v : (uint64_t)v;
-	}
-	case 2: {
-		uint16_t v = *(const uint16_t *)p;
-		return sign_extend ? (uint64_t)(int64_t)(int16_t)v : (uint64_t)v;
-	}
-	case 4: {
-		uint32_t v = *(const uint32_t *)p;
-		return sign_extend ? (uint64_t)(int64_t)(int32_t)v : (uint64_t)v;
-	}
-	default:
-		return *(const uint64_t *)p;
-	}
-}
-
-template <int W>
-struct Tuple {
-	uint32_t s[W];
-};
 
 // per-stage descriptor pulled from LDS into wave-uniform registers
 struct Stage {
@@ -143,50 +102,6 @@ __device__ __forceinline__ Stage load_stage(const StageDesc *d) {
 	return s;
 }
 
-template <int W>
-__device__ __forceinline__ uint32_t tuple_slot(const Tuple<W> &t, int32_t slot) {
-	uint32_t v = t.s[0];
-#pragma unroll
-	for (int q = 1; q < W; q++) {
-		v = (q == slot) ? t.s[q] : v;
-	}
-	return v;
-}
-
-#if POLR_EXT
-// composite key in packed form (KeyPack): per column (value - min) << shift; a value outside the build side's
-// [min, min + range] cannot match.  Everything comes from the extension record in global memory.  A function of its own
-// (like preds_hold below): inlined into every place a stage fetches keys, the uncommon paths made the POLR_EXT objects
-// the slowest of the build by minutes -- the pipelines that take them can afford a call.
-template <int W>
-__device__ __attribute__((noinline)) bool fetch_key_packed(const StageExt *d, uint32_t n_keys, const Tuple<W> &t,
-                                                           uint64_t &key) {
-	bool valid = true;
-	key = 0;
-	for (uint32_t c = 0; c < n_keys; c++) {
-		const uint32_t row = tuple_slot<W>(t, d->key_slot[c]);
-		const uint8_t *kv = d->key_valid[c];
-		const uint32_t w = d->key_width[c];
-		const uint64_t v = load_cell(d->key_data[c] + (uint64_t)row * w, w, d->key_sx[c] != 0); // (the probe column's own type)
-		uint64_t off = v - (uint64_t)d->pack.min[c];
-		if (kv && !kv[row]) {
-			if ((d->pack.null_eq >> c) & 1u) {
-				off = d->pack.range[c] + 1u; // IS NOT DISTINCT FROM: NULL is a key value of its own
-			} else {
-				valid = false;
-			}
-		} else if (off > d->pack.range[c]) {
-			valid = false;
-		}
-		key |= off << d->pack.shift[c];
-	}
-	if (!valid) {
-		key = 0;
-	}
-	return valid;
-}
-#endif
-
 // key of this lane's tuple; false for NULL (NULL never matches: join_hashtable.cpp:170-192,
 // perfect_hash_join_executor.cpp:272-277)
 template <int W>
@@ -198,19 +113,19 @@ __device__ __forceinline__ bool fetch_key(const Stage &s, const StageDesc *desc,
 	}
 #if POLR_EXT
 	if (s.xflags & 1u) {
-		return fetch_key_packed<W>(uniptr(desc->ext), s.n_keys, t, key);
+		return fetch_key_packed<W>(as_global(uniptr(desc->ext)), s.n_keys, t, key);
 	}
 #endif
 	const bool sx = s.kind == KIND_PERFECT && s.key_signed != 0;
 	const uint32_t row0 = tuple_slot<W>(t, s.key_slot0);
 	bool valid = !(s.key_valid0 && !s.key_valid0[row0]);
-	key = load_cell(s.key_data0 + (uint64_t)row0 * s.key_width0, s.key_width0, sx);
+	key = load_cell(as_global(s.key_data0) + (uint64_t)row0 * s.key_width0, s.key_width0, sx);
 	if (s.n_keys > 1) {
 		const uint32_t row1 = tuple_slot<W>(t, s.key_slot1);
 		if (s.key_valid1 && !s.key_valid1[row1]) {
 			valid = false;
 		}
-		key |= load_cell(s.key_data1 + (uint64_t)row1 * s.key_width1, s.key_width1, false) << 32;
+		key |= load_cell(as_global(s.key_data1) + (uint64_t)row1 * s.key_width1, s.key_width1, false) << 32;
 	}
 	return valid;
 }
@@ -218,15 +133,7 @@ __device__ __forceinline__ bool fetch_key(const Stage &s, const StageDesc *desc,
 // ---- bucket probes ---------------------------------------------------------------------------
 __device__ __forceinline__ bool lookup_perfect(const Stage &s, uint64_t key, bool valid, uint32_t &id) {
 	uint64_t idx;
-	bool in_range;
-	if (s.key_signed) {
-		const int64_t v = (int64_t)key;
-		in_range = v >= s.min_value && (uint64_t)(v - s.min_value) <= s.range;
-		idx = (uint64_t)(v - s.min_value);
-	} else {
-		in_range = key >= (uint64_t)s.min_value && key - (uint64_t)s.min_value <= s.range;
-		idx = key - (uint64_t)s.min_value;
-	}
+	const bool in_range = perfect_index(key, s.key_signed != 0, s.min_value, s.range, idx);
 	bool hit = false;
 	if (valid && in_range) {
 		const uint32_t *bits = (const uint32_t *)s.table;
@@ -236,9 +143,7 @@ __device__ __forceinline__ bool lookup_perfect(const Stage &s, uint64_t key, boo
 	return hit;
 }
 
-// Linear probing, but one round trip inspects an aligned group of slots (32 bytes): a wave waits for its
-// slowest lane, so what counts is the number of DEPENDENT loads of the unluckiest of 64 lanes; at load
-// factor <= 0.5 a group of 4 (2) slots almost always holds the end of the probe sequence.
+// one slot group per round trip (s8_group_step / s16_group_step, polr_device.h)
 struct S8Probe { // one in-flight {key,row} probe
 	uint64_t group;
 	uint32_t first;
@@ -259,20 +164,7 @@ __device__ __forceinline__ void s8_begin(const Stage &s, uint64_t key, bool vali
 }
 
 __device__ __forceinline__ void s8_check(const Stage &s, S8Probe &p, const uint4 a, const uint4 b) {
-	const uint32_t kk[4] = {a.x, a.z, b.x, b.z};
-	const uint32_t rr[4] = {a.y, a.w, b.y, b.w};
-#pragma unroll
-	for (int i = 0; i < 4; i++) {
-		if (p.searching && (uint32_t)i >= p.first) {
-			if (rr[i] == S8_EMPTY_ROW) {
-				p.searching = false;
-			} else if (kk[i] == p.k32) {
-				p.hit = true;
-				p.id = rr[i];
-				p.searching = false;
-			}
-		}
-	}
+	s8_group_step(a, b, p.first, p.k32, p.searching, p.hit, p.id);
 	p.first = 0;
 	p.group = (p.group + 1) & (s.mask >> 2);
 }
@@ -300,40 +192,14 @@ struct S16Probe { // one in-flight {key64,start,count} probe
 
 __device__ __forceinline__ void s16_begin(const Stage &s, uint64_t key, bool valid, S16Probe &p) {
 	p.key = key;
-	p.start = 0;
-	p.count = 0;
-	p.searching = valid;
-	if (valid && key == S16_EMPTY_KEY) {
-		p.start = s.sentinel_start;
-		p.count = s.sentinel_count;
-		p.searching = false;
-	}
+	s16_begin_probe(key, valid, s.sentinel_start, s.sentinel_count, p.searching, p.start, p.count);
 	const uint64_t h = polr_murmurhash64(key) & s.mask;
 	p.group = h >> 1; // 2 slots per group
 	p.first = (uint32_t)(h & 1);
 }
 
 __device__ __forceinline__ void s16_check(const Stage &s, S16Probe &p, const uint4 e0, const uint4 e1) {
-	if (p.first == 0) {
-		const uint64_t k0 = ((uint64_t)e0.y << 32) | e0.x;
-		if (k0 == S16_EMPTY_KEY) {
-			p.searching = false;
-		} else if (k0 == p.key) {
-			p.start = e0.z;
-			p.count = e0.w;
-			p.searching = false;
-		}
-	}
-	if (p.searching) {
-		const uint64_t k1 = ((uint64_t)e1.y << 32) | e1.x;
-		if (k1 == S16_EMPTY_KEY) {
-			p.searching = false;
-		} else if (k1 == p.key) {
-			p.start = e1.z;
-			p.count = e1.w;
-			p.searching = false;
-		}
-	}
+	s16_group_step(e0, e1, p.first, p.key, p.searching, p.start, p.count);
 	p.first = 0;
 	p.group = (p.group + 1) & (s.mask >> 1);
 }
@@ -374,99 +240,21 @@ struct WaveCtx {
 	uint32_t *wpend_start, *wpend_pref; // [2][256]: slot 0 = stage 0, slot 1 = the last stage
 	// output
 	DevOut out;
-	bool emit;
-	uint32_t cur_chunk, fill;
-	bool overflow;
+	OutState os;
 };
 
 template <int W, int K>
 __device__ __forceinline__ void out_write(WaveCtx<W, K> &c, const Tuple<W> &t, bool valid) {
-	if (!c.emit || c.out.ids == nullptr) {
+	if (!c.os.emit || c.out.ids == nullptr) {
 		return;
 	}
-	const uint64_t m = __ballot(valid);
-	const uint32_t n = (uint32_t)__popcll(m);
-	const uint32_t rank = lane_rank(m);
-	uint32_t done = 0;
-	while (done < n) {
-		if (c.cur_chunk == NO_CHUNK || c.fill == c.out.chunk_capacity) {
-			if (c.cur_chunk != NO_CHUNK && c.lane == 0) {
-				c.out.chunk_count[c.cur_chunk] = c.fill;
-			}
-			uint32_t nc = 0;
-			if (c.lane == 0) {
-				nc = atomicAdd(&c.out.cursor[0], 1u);
-			}
-			nc = uni(nc);
-			if (nc >= c.out.max_chunks) {
-				if (c.lane == 0) {
-					atomicExch(&c.out.cursor[1], 1u);
-				}
-				c.overflow = true;
-				c.cur_chunk = NO_CHUNK;
-				c.emit = false;
-				return;
-			}
-			c.cur_chunk = nc;
-			c.fill = 0;
-		}
-		const uint32_t room = c.out.chunk_capacity - c.fill;
-		const uint32_t take = (n - done) < room ? (n - done) : room;
-		if (valid && rank >= done && rank < done + take) {
-			const uint64_t base = (uint64_t)c.cur_chunk * c.out.chunk_capacity + c.fill + (rank - done);
+	POLR_GLOBAL uint32_t *ids = as_global(c.out.ids);
+	out_claim(c.out, c.os, c.lane, __ballot(valid), valid, [&](uint64_t place) {
 #pragma unroll
-			for (int i = 0; i < W; i++) {
-				c.out.ids[(uint64_t)i * c.out.slot_stride + base] = t.s[i];
-			}
+		for (int i = 0; i < W; i++) {
+			ids[(uint64_t)i * c.out.slot_stride + place] = t.s[i];
 		}
-		c.fill += take;
-		done += take;
-	}
-}
-
-// the join's non-equality conditions on one (tuple, build row) pair (RowOperations::Match, row_match.cpp:59-119:
-// both sides valid and `left OP right`); descriptors come from the extension record -- joins that have any are rare
-template <int W>
-__device__ __attribute__((noinline)) bool preds_hold(const StageExt *d, uint32_t n_preds, const Tuple<W> &t, uint32_t id) {
-	bool ok = true;
-	for (uint32_t c = 0; c < n_preds; c++) {
-		const uint32_t row = tuple_slot<W>(t, d->pred_slot[c]);
-		const uint32_t w = d->pred_width[c];
-		const bool sx = d->pred_sx[c] != 0;
-		const uint8_t *lv = d->pred_valid[c], *rv = d->pred_bvalid[c];
-		if ((lv && !lv[row]) || (rv && !rv[id])) {
-			ok = false;
-		}
-		if (d->pred_op[c] == POLR_PRED_STR_EQ) { // the strings behind a VARCHAR key's hash
-			ok = ok && polr_str_cells_equal(d->pred_data[c] + (uint64_t)row * 16u, d->pred_bdata[c] + (uint64_t)id * 16u);
-			continue;
-		}
-		const uint64_t l = load_cell(d->pred_data[c] + (uint64_t)row * w, w, sx);
-		const uint64_t r = load_cell(d->pred_bdata[c] + (uint64_t)id * w, w, sx);
-		bool h;
-		if (w == 8 && !sx) {
-			switch (d->pred_op[c]) {
-			case 0: h = l == r; break; // (POLR_CMP_EQ: the verifying comparison behind a hashed composite key)
-			case 1: h = l != r; break;
-			case 2: h = l < r; break;
-			case 3: h = l > r; break;
-			case 4: h = l <= r; break;
-			default: h = l >= r; break;
-			}
-		} else {
-			const int64_t a = (int64_t)l, b = (int64_t)r; // (narrow unsigned values are zero-extended: same order)
-			switch (d->pred_op[c]) {
-			case 0: h = a == b; break;
-			case 1: h = a != b; break;
-			case 2: h = a < b; break;
-			case 3: h = a > b; break;
-			case 4: h = a <= b; break;
-			default: h = a >= b; break;
-			}
-		}
-		ok = ok && h;
-	}
-	return ok;
+	});
 }
 
 // push the matches of stage POS to the next stage (or to the output when POS is the last join)
@@ -475,7 +263,7 @@ __device__ __forceinline__ void emit_tuples(WaveCtx<W, K> &c, const Stage &s, Tu
 #if POLR_EXT
 	if (s.xflags >> 8) {
 		// (inactive lanes carry arbitrary ids: evaluate on the matches only)
-		valid = valid && preds_hold<W>(uniptr(c.desc[POS].ext), s.xflags >> 8, t, id);
+		valid = valid && preds_hold<W>(as_global(uniptr(c.desc[POS].ext)), s.xflags >> 8, t, id);
 	}
 #endif
 #pragma unroll
@@ -501,17 +289,6 @@ __device__ __forceinline__ void emit_tuples(WaveCtx<W, K> &c, const Stage &s, Tu
 		}
 		c.qsize[POS + 1] = qs + n;
 	}
-}
-
-__device__ __forceinline__ uint32_t wave_inclusive_scan(uint32_t v, uint32_t lane) {
-#pragma unroll
-	for (int d = 1; d < 64; d <<= 1) {
-		const uint32_t o = __shfl_up(v, d, 64);
-		if ((int)lane >= d) {
-			v += o;
-		}
-	}
-	return v;
 }
 
 // continue the pending expansion of stage POS: emit the next <= 64 (tuple, build row) pairs

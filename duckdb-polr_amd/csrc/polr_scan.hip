@@ -67,34 +67,11 @@ __device__ __forceinline__ bool lip_contains(const DevLip &f, uint64_t row) {
 	if (f.key_valid && !f.key_valid[row]) {
 		return false; // NULL never joins
 	}
-	const uint8_t *p = f.key_data + row * f.key_width;
-	uint64_t key;
-	switch (f.key_width) {
-	case 1:
-		key = f.key_signed && f.kind == KIND_PERFECT ? (uint64_t)(int64_t)*(const int8_t *)p : (uint64_t)*p;
-		break;
-	case 2:
-		key = f.key_signed && f.kind == KIND_PERFECT ? (uint64_t)(int64_t)*(const int16_t *)p : (uint64_t)*(const uint16_t *)p;
-		break;
-	case 4:
-		key = f.key_signed && f.kind == KIND_PERFECT ? (uint64_t)(int64_t)*(const int32_t *)p : (uint64_t)*(const uint32_t *)p;
-		break;
-	default:
-		key = *(const uint64_t *)p;
-		break;
-	}
+	const uint64_t key = load_cell(as_global(f.key_data) + row * f.key_width, f.key_width, f.key_signed && f.kind == KIND_PERFECT);
 	if (f.kind == KIND_PERFECT) {
 		uint64_t idx;
-		bool in_range;
-		if (f.key_signed) {
-			const int64_t v = (int64_t)key;
-			in_range = v >= f.min_value && (uint64_t)(v - f.min_value) <= f.range;
-			idx = (uint64_t)(v - f.min_value);
-		} else {
-			in_range = key >= (uint64_t)f.min_value && key - (uint64_t)f.min_value <= f.range;
-			idx = key - (uint64_t)f.min_value;
-		}
-		return in_range && ((((const uint32_t *)f.table)[idx >> 5] >> (idx & 31)) & 1u);
+		return perfect_index(key, f.key_signed != 0, f.min_value, f.range, idx) &&
+		       ((as_global((const uint32_t *)f.table)[idx >> 5] >> (idx & 31)) & 1u);
 	}
 	if (f.kind == KIND_S8) {
 		const uint2 *tab = (const uint2 *)f.table; // {key32, row}
@@ -156,47 +133,17 @@ __device__ __forceinline__ bool row_passes_filters(const DevFilterSet &fs, uint6
 			ok = ok && valid;
 			continue;
 		}
-		const uint8_t *p = f.data + row * f.width;
+		const uint64_t v = load_cell(as_global(f.data) + row * f.width, f.width, f.is_signed != 0);
 		bool r;
 		if (f.is_signed) {
-			int64_t v;
-			switch (f.width) {
-			case 1:
-				v = *(const int8_t *)p;
-				break;
-			case 2:
-				v = *(const int16_t *)p;
-				break;
-			case 4:
-				v = *(const int32_t *)p;
-				break;
-			default:
-				v = *(const int64_t *)p;
-				break;
-			}
-			const int64_t c = f.constant;
-			r = f.op == POLR_CMP_EQ   ? v == c
-			    : f.op == POLR_CMP_NE ? v != c
-			    : f.op == POLR_CMP_LT ? v < c
-			    : f.op == POLR_CMP_GT ? v > c
-			    : f.op == POLR_CMP_LE ? v <= c
-			                          : v >= c;
+			const int64_t a = (int64_t)v, c = f.constant;
+			r = f.op == POLR_CMP_EQ   ? a == c
+			    : f.op == POLR_CMP_NE ? a != c
+			    : f.op == POLR_CMP_LT ? a < c
+			    : f.op == POLR_CMP_GT ? a > c
+			    : f.op == POLR_CMP_LE ? a <= c
+			                          : a >= c;
 		} else {
-			uint64_t v;
-			switch (f.width) {
-			case 1:
-				v = *p;
-				break;
-			case 2:
-				v = *(const uint16_t *)p;
-				break;
-			case 4:
-				v = *(const uint32_t *)p;
-				break;
-			default:
-				v = *(const uint64_t *)p;
-				break;
-			}
 			const uint64_t c = (uint64_t)f.constant; // (host: constant >= 0 for unsigned columns)
 			r = f.op == POLR_CMP_EQ   ? v == c
 			    : f.op == POLR_CMP_NE ? v != c
@@ -353,9 +300,7 @@ __global__ __launch_bounds__(256) void polr_tscan_write_kernel(DevFilterSet fs, 
 			const bool pass = row < end && row_passes(fs, lip, row);
 			const uint64_t m = __ballot(pass);
 			if (pass) {
-				const uint32_t rank =
-				    __builtin_amdgcn_mbcnt_hi((uint32_t)(m >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)m, 0));
-				sel[out + rank] = (uint32_t)row;
+				sel[out + lane_rank(m)] = (uint32_t)row;
 			}
 			out += (uint64_t)__popcll(m);
 		}

@@ -223,9 +223,12 @@ def test_device_matches_oracle(gpu_ctx, name):
 def test_pool_launch_and_path_kernel_agree_on_all_113(gpu_ctx):
     """every join order of every one of the 113 pipelines through the POOL launch (generic pipeline of
     polr_gen_device.h with multiplicity folding, or the flat pipeline) and through the per-round path kernel
-    (polr_probe_device.h): two independent implementations of RunPath; the tuples every join produces at every position
-    of every join order must be identical (what the multiplexer's reward is computed from), and COUNT(*) the same down
-    every join order"""
+    (polr_probe_device.h): two implementations of RunPath.  Both take their cell, key, table-probe and output rules
+    from polr_device.h; those rules are checked independently against the oracle and the
+    reference fixtures (test_device_matches_the_reference_on_every_query, test_key_semantics.py, test_varchar_keys.py).
+    This cross-check covers what differs: scheduling, queues, expansion and multiplicities -- the tuples every join
+    produces at every position of every join order must be identical (what the multiplexer's reward is computed from),
+    and COUNT(*) the same down every join order"""
     from polr_amd import capi
     t = jf.Tables(scale=0.03)
     checked = 0

@@ -1,6 +1,7 @@
 """diagnostic / cross-check: every join order of every JOB-shaped pipeline through the POOL launch (generic pipeline of
-polr_gen_device.h, or the flat one) and through the per-round path kernel (polr_probe_device.h) -- two independent
-implementations of RunPath; their per-(join order, position) tuple counts must be identical.
+polr_gen_device.h, or the flat one) and through the per-round path kernel (polr_probe_device.h) -- two implementations of
+RunPath that differ in scheduling, queues, expansion and multiplicities; their per-(join order, position) tuple counts must
+be identical.
    python3 tools/check_job_paths.py [scale] [query ...]"""
 import os
 import sys
