@@ -1986,6 +1986,7 @@ int polr_probe_rounds_async(polr_pipeline *p, void *stream, const polr_round *ro
 	if (out && out->pipe != p) {
 		POLR_FAIL(ctx, POLR_E_INVALID, "output object belongs to another pipeline");
 	}
+	POLR_REFUSE_FUSED(ctx, out);
 	uint64_t total = 0;
 	for (uint32_t r = 0; r < n_rounds; r++) {
 		if (rounds[r].path >= p->n_paths) {
@@ -2077,6 +2078,7 @@ int polr_probe_rounds(polr_pipeline *p, void *stream, const polr_round *rounds, 
 		return POLR_E_INVALID;
 	}
 	polr_ctx *ctx = p->ctx;
+	POLR_REFUSE_FUSED(ctx, out);
 	HIPCHK(ctx, hipSetDevice(ctx->device));
 	hipStream_t st = polr_stream(ctx, stream);
 	const uint64_t need = (uint64_t)n_rounds * p->k;

@@ -168,6 +168,19 @@ static inline hipStream_t polr_stream(polr_ctx *ctx, void *stream) {
 	return stream ? (hipStream_t)stream : ctx->stream;
 }
 
+// Only the flat pool kernel folds tuples into a fused GROUP BY sink (DevOut::fused).  The entry points that launch the
+// per-round path kernel refuse such an output before they enqueue anything: that kernel would write row ids instead and
+// leave the group cells empty.
+#define POLR_REFUSE_FUSED(ctx_, out_)                                                                                  \
+	do {                                                                                                               \
+		if ((out_) && (out_)->fused_dev) {                                                                             \
+			POLR_FAIL(ctx_, POLR_E_UNSUPPORTED,                                                                        \
+			          "%s: the output has a fused GROUP BY sink, which only the pool launch fills "                     \
+			          "(polr_mpx_run_resident*, polr_mpx_run_backpressure)",                                           \
+			          __func__);                                                                                       \
+		}                                                                                                              \
+	} while (0)
+
 // kernels / launchers implemented in polr_build.hip and polr_probe.hip
 size_t polr_path_lds_bytes(uint32_t k, uint32_t W, uint32_t waves_per_block);
 int polr_path_occupancy(uint32_t k, uint32_t W, uint32_t waves_per_block);

@@ -509,6 +509,7 @@ int polr_mpx_run(polr_mpx *m, void *stream, uint64_t chunk_begin, uint64_t chunk
 	if (!m) {
 		return POLR_E_INVALID;
 	}
+	POLR_REFUSE_FUSED(m->pipe->ctx, out);
 	RunState rs;
 	int rc = run_begin(rs, m, stream, chunk_begin, chunk_end, out, 1);
 	while (!rc && !rs.finished) {
@@ -524,9 +525,10 @@ int polr_mpx_run(polr_mpx *m, void *stream, uint64_t chunk_begin, uint64_t chunk
 int polr_mpx_run_many(polr_mpx **ms, void **streams, const uint64_t *chunk_begin, const uint64_t *chunk_end,
                       uint32_t n, polr_out *out) {
 	POLR_ENTRY();
-	if (!ms || !chunk_begin || !chunk_end || n == 0) {
+	if (!ms || !ms[0] || !chunk_begin || !chunk_end || n == 0) {
 		return POLR_E_INVALID;
 	}
+	POLR_REFUSE_FUSED(ms[0]->pipe->ctx, out);
 	std::vector<RunState> rs(n);
 	int rc = POLR_OK;
 	for (uint32_t i = 0; i < n && !rc; i++) {

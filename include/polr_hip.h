@@ -369,7 +369,9 @@ int polr_out_aggregate_hashed(polr_out *o, void *stream, const polr_group_key *c
  * (polr_pipeline_launch_info(p, 1): flat) -- the star joins of SSB; COUNT(*), COUNT and SUM over columns of at most 4
  * bytes, at most 4096 groups; POLR_E_UNSUPPORTED otherwise (then: polr_out_aggregate_grouped over the emitted row ids).
  * polr_out_reset zeroes the cells; every run with this `out` adds to them; polr_out_fused_result reads them (results as
- * for polr_out_aggregate_grouped).  keys == NULL un-fuses. */
+ * for polr_out_aggregate_grouped).  keys == NULL un-fuses.  Only the pool launch (polr_mpx_run_resident*,
+ * polr_mpx_run_backpressure) fills the cells: polr_probe_rounds, polr_probe_rounds_async, polr_mpx_run and
+ * polr_mpx_run_many return POLR_E_UNSUPPORTED for an `out` with a fused sink and enqueue nothing. */
 int polr_out_fuse_grouped(polr_out *o, const polr_group_key *keys, uint32_t n_keys, const polr_agg_spec *specs,
                           uint32_t n_aggs);
 int polr_out_fused_result(polr_out *o, void *stream, polr_agg_value *results, uint64_t n_groups, uint64_t *n_dropped);
