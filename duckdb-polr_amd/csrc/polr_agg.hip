@@ -14,6 +14,7 @@
 #include <stdint.h>
 #include <string.h>
 
+#include <algorithm>
 #include <vector>
 
 #include "polr_internal.h"
@@ -953,20 +954,58 @@ extern "C" int polr_out_fused_result(polr_out *o, void *stream, polr_agg_value *
 
 // ---- VARCHAR: string heaps on the device and the MIN / MAX sink over string_t cells -------------------------------------
 // (string_type.hpp:23-28: {u32 length, char inlined[12]} or {u32 length, char prefix[4], char *ptr})
-__global__ __launch_bounds__(256) void polr_rebase_strings_kernel(uint4 *cells, uint64_t n, uint64_t host_base, uint64_t host_end,
-                                                                  uint64_t dev_base, unsigned long long *outside) {
+// one host range of a heap and where its copy lives on the device; a column's ranges sorted by host_base, disjoint
+struct HeapRange {
+	uint64_t host_base, bytes, dev_base;
+};
+
+// the range that holds all of [ptr, ptr + len), or -1 (ranges sorted and disjoint: at most one can)
+__device__ __forceinline__ int find_heap_range(const HeapRange *r, uint32_t n, uint64_t ptr, uint32_t len) {
+	uint32_t lo = 0, hi = n; // -> the first range whose host_base lies above ptr
+	while (lo < hi) {
+		const uint32_t mid = (lo + hi) / 2;
+		if (r[mid].host_base <= ptr) {
+			lo = mid + 1;
+		} else {
+			hi = mid;
+		}
+	}
+	if (lo == 0) {
+		return -1;
+	}
+	const HeapRange &h = r[lo - 1];
+	return (len <= h.bytes && ptr - h.host_base <= h.bytes - len) ? (int)(lo - 1) : -1; // (no wrap-around at 2^64)
+}
+
+// rewrite = 0: count the non-NULL long cells that no range holds; rewrite = 1 (after a count of 0): rebase those cells onto
+// the device copies and zero the cells of NULL rows (the reference leaves them uninitialised: nothing may follow them)
+__global__ __launch_bounds__(256) void polr_rebase_strings_kernel(uint4 *cells, const uint8_t *__restrict__ valid, uint64_t n,
+                                                                  const HeapRange *__restrict__ ranges, uint32_t n_ranges,
+                                                                  int rewrite, unsigned long long *outside) {
 	const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
 	if (i >= n) {
 		return;
 	}
-	uint4 c = cells[i];
-	if (c.x > 12u) {
-		const uint64_t ptr = ((uint64_t)c.w << 32) | c.z;
-		if (ptr < host_base || ptr + c.x > host_end) {
-			atomicAdd(outside, 1ull); // (a cell pointing outside the heap it was said to live in)
-			return;
+	if (valid && !valid[i]) {
+		if (rewrite) {
+			cells[i] = make_uint4(0, 0, 0, 0);
 		}
-		const uint64_t moved = ptr - host_base + dev_base;
+		return;
+	}
+	uint4 c = cells[i];
+	if (c.x <= 12u) {
+		return;
+	}
+	const uint64_t ptr = ((uint64_t)c.w << 32) | c.z;
+	const int r = find_heap_range(ranges, n_ranges, ptr, c.x);
+	if (r < 0) {
+		if (!rewrite) {
+			atomicAdd(outside, 1ull); // (a cell pointing outside the heap it was said to live in)
+		}
+		return;
+	}
+	if (rewrite) {
+		const uint64_t moved = ptr - ranges[r].host_base + ranges[r].dev_base;
 		c.z = (uint32_t)moved;
 		c.w = (uint32_t)(moved >> 32);
 		cells[i] = c;
@@ -1072,49 +1111,92 @@ __global__ __launch_bounds__(256) void polr_agg_string_kernel(DevOut out, uint32
 	}
 }
 
-static int set_string_heap(polr_ctx *ctx, std::vector<OwnedCol *> cols, uint64_t n_rows, const void *heap_base, uint64_t heap_bytes,
-                           std::vector<void *> &owner) {
-	if (!heap_base || heap_bytes == 0) {
-		return POLR_E_INVALID;
+// all or nothing: the ranges are checked, copied and every cell validated before any cell is rewritten; on an error the
+// column is as it was and no device memory is kept
+static int set_string_heaps(polr_ctx *ctx, OwnedCol *c, uint64_t n_rows, const polr_heap_range *ranges, uint32_t n_ranges,
+                            std::vector<void *> &owner) {
+	if (!ranges || n_ranges == 0) {
+		POLR_FAIL(ctx, POLR_E_INVALID, "a string heap needs at least one range");
 	}
-	for (OwnedCol *c : cols) {
-		if (c->width != 16) {
-			POLR_FAIL(ctx, POLR_E_INVALID, "a string heap belongs to a column of 16-byte string cells (this one: %u bytes)", c->width);
+	if (c->width != 16) {
+		POLR_FAIL(ctx, POLR_E_INVALID, "a string heap belongs to a column of 16-byte string cells (this one: %u bytes)", c->width);
+	}
+	if (c->strings_rebased) {
+		POLR_FAIL(ctx, POLR_E_INVALID, "the column's string cells point into a device heap already");
+	}
+	std::vector<HeapRange> hr(n_ranges);
+	std::vector<uint32_t> order(n_ranges);
+	uint64_t total = 0;
+	for (uint32_t r = 0; r < n_ranges; r++) {
+		const uint64_t base = (uint64_t)ranges[r].base, bytes = ranges[r].bytes;
+		if (!base || bytes == 0 || base + bytes < base) {
+			POLR_FAIL(ctx, POLR_E_INVALID, "heap range %u: empty, NULL or past the end of the address space", r);
 		}
+		order[r] = r;
+		total += bytes;
+	}
+	std::sort(order.begin(), order.end(),
+	          [&](uint32_t a, uint32_t b) { return (uint64_t)ranges[a].base < (uint64_t)ranges[b].base; });
+	uint64_t at = 0;
+	for (uint32_t r = 0; r < n_ranges; r++) {
+		const polr_heap_range &x = ranges[order[r]];
+		if (r && (uint64_t)x.base < hr[r - 1].host_base + hr[r - 1].bytes) {
+			POLR_FAIL(ctx, POLR_E_INVALID, "heap ranges %u and %u overlap", order[r - 1], order[r]);
+		}
+		hr[r].host_base = (uint64_t)x.base;
+		hr[r].bytes = x.bytes;
+		hr[r].dev_base = at; // (offset for now: the device address once the copy exists)
+		at += x.bytes;
 	}
 	HIPCHK(ctx, hipSetDevice(ctx->device));
-	void *heap = nullptr;
+	uint8_t *heap = nullptr;
+	HeapRange *d_ranges = nullptr;
 	unsigned long long *outside = nullptr;
-	HIPCHK(ctx, hipMalloc(&heap, heap_bytes));
-	hipError_t e = hipMalloc((void **)&outside, 8);
-	e = e == hipSuccess ? hipMemcpyAsync(heap, heap_base, heap_bytes, hipMemcpyHostToDevice, ctx->stream) : e;
+	hipError_t e = hipMalloc((void **)&heap, total);
+	e = e == hipSuccess ? hipMalloc((void **)&d_ranges, n_ranges * sizeof(HeapRange)) : e;
+	e = e == hipSuccess ? hipMalloc((void **)&outside, 8) : e;
+	for (uint32_t r = 0; r < n_ranges && e == hipSuccess; r++) {
+		e = hipMemcpyAsync(heap + hr[r].dev_base, (const void *)hr[r].host_base, hr[r].bytes, hipMemcpyHostToDevice, ctx->stream);
+		hr[r].dev_base += (uint64_t)heap;
+	}
+	e = e == hipSuccess ? hipMemcpyAsync(d_ranges, hr.data(), n_ranges * sizeof(HeapRange), hipMemcpyHostToDevice, ctx->stream) : e;
 	e = e == hipSuccess ? hipMemsetAsync(outside, 0, 8, ctx->stream) : e;
+	const dim3 grid((unsigned)((n_rows + 255) / 256));
 	if (e == hipSuccess && n_rows) {
-		for (OwnedCol *c : cols) {
-			hipLaunchKernelGGL(polr_rebase_strings_kernel, dim3((unsigned)((n_rows + 255) / 256)), dim3(256), 0, ctx->stream,
-			                   (uint4 *)c->data, n_rows, (uint64_t)heap_base, (uint64_t)heap_base + heap_bytes, (uint64_t)heap, outside);
-		}
+		hipLaunchKernelGGL(polr_rebase_strings_kernel, grid, dim3(256), 0, ctx->stream, (uint4 *)c->data, c->valid, n_rows, d_ranges,
+		                   n_ranges, 0, outside);
 	}
 	unsigned long long bad = 0;
 	e = e == hipSuccess ? hipMemcpyAsync(&bad, outside, 8, hipMemcpyDeviceToHost, ctx->stream) : e;
 	e = e == hipSuccess ? hipStreamSynchronize(ctx->stream) : e;
+	if (e == hipSuccess && !bad && n_rows) {
+		hipLaunchKernelGGL(polr_rebase_strings_kernel, grid, dim3(256), 0, ctx->stream, (uint4 *)c->data, c->valid, n_rows, d_ranges,
+		                   n_ranges, 1, outside);
+		e = hipStreamSynchronize(ctx->stream);
+	}
+	if (d_ranges) {
+		hipFree(d_ranges);
+	}
 	if (outside) {
 		hipFree(outside);
 	}
 	if (e != hipSuccess || bad) {
-		hipFree(heap);
+		if (heap) {
+			hipFree(heap);
+		}
 		if (e != hipSuccess) {
 			POLR_FAIL(ctx, POLR_E_HIP, "string heap upload failed: %s", hipGetErrorString(e));
 		}
-		POLR_FAIL(ctx, POLR_E_INVALID, "%llu string cells point outside the heap given for their column", bad);
+		POLR_FAIL(ctx, POLR_E_INVALID, "%llu non-NULL string cells point outside the heap ranges given for their column", bad);
 	}
 	owner.push_back(heap);
+	c->strings_rebased = true;
 	return POLR_OK;
 }
 
 extern "C" {
 
-int polr_ht_set_payload_heap(polr_ht *ht, uint32_t payload_col, const void *heap_base, uint64_t heap_bytes) {
+int polr_ht_set_payload_heaps(polr_ht *ht, uint32_t payload_col, const polr_heap_range *ranges, uint32_t n_ranges) {
 	POLR_ENTRY();
 	if (!ht || payload_col >= ht->n_payload) {
 		return POLR_E_INVALID;
@@ -1123,10 +1205,15 @@ int polr_ht_set_payload_heap(polr_ht *ht, uint32_t payload_col, const void *heap
 		// (a finalized perfect table keeps a re-ordered copy of every payload column: rebase before finalizing)
 		POLR_FAIL(ht->ctx, POLR_E_INVALID, "set the string heap of a payload column before the table is finalized");
 	}
-	return set_string_heap(ht->ctx, {&ht->payload[payload_col]}, ht->n_rows_in, heap_base, heap_bytes, ht->heaps);
+	return set_string_heaps(ht->ctx, &ht->payload[payload_col], ht->n_rows_in, ranges, n_ranges, ht->heaps);
 }
 
-int polr_pipeline_set_probe_heap(polr_pipeline *p, uint32_t probe_col, const void *heap_base, uint64_t heap_bytes) {
+int polr_ht_set_payload_heap(polr_ht *ht, uint32_t payload_col, const void *heap_base, uint64_t heap_bytes) {
+	const polr_heap_range r = {heap_base, heap_bytes};
+	return polr_ht_set_payload_heaps(ht, payload_col, &r, 1);
+}
+
+int polr_pipeline_set_probe_heaps(polr_pipeline *p, uint32_t probe_col, const polr_heap_range *ranges, uint32_t n_ranges) {
 	POLR_ENTRY();
 	if (!p || probe_col >= p->n_probe_cols) {
 		return POLR_E_INVALID;
@@ -1135,7 +1222,12 @@ int polr_pipeline_set_probe_heap(polr_pipeline *p, uint32_t probe_col, const voi
 		POLR_FAIL(p->ctx, POLR_E_INVALID, "probe column %u lives in the caller's device memory: its cells must point into HBM already",
 		          probe_col);
 	}
-	return set_string_heap(p->ctx, {&p->probe_cols[probe_col]}, p->n_probe_rows, heap_base, heap_bytes, p->heaps);
+	return set_string_heaps(p->ctx, &p->probe_cols[probe_col], p->n_probe_rows, ranges, n_ranges, p->heaps);
+}
+
+int polr_pipeline_set_probe_heap(polr_pipeline *p, uint32_t probe_col, const void *heap_base, uint64_t heap_bytes) {
+	const polr_heap_range r = {heap_base, heap_bytes};
+	return polr_pipeline_set_probe_heaps(p, probe_col, &r, 1);
 }
 
 int polr_out_aggregate_string(polr_out *o, void *stream, uint32_t fn, int32_t src_join, uint32_t src_col, char *dst,

@@ -54,6 +54,7 @@ struct OwnedCol {
 	uint32_t width = 0;
 	uint32_t flags = 0;
 	bool owned = true;
+	bool strings_rebased = false; // string cells point into a device heap (set_string_heaps): a second upload is refused
 };
 
 struct polr_ht {

@@ -37,6 +37,7 @@ EXPORTS = [
     "polr_ctx_set_pool_tuning", "polr_ctx_get_stream",
     "polr_ht_set_payload_heap", "polr_pipeline_set_probe_heap", "polr_out_aggregate_string", "polr_ht_set_key_flags",
     "polr_out_fuse_grouped", "polr_out_fused_result", "polr_out_aggregate_hashed",
+    "polr_ht_set_payload_heaps", "polr_pipeline_set_probe_heaps",
 ]
 
 
@@ -76,6 +77,18 @@ class ScanFilter(C.Structure):
 
 
 CMP = {"=": 0, "==": 0, "!=": 1, "<>": 1, "<": 2, ">": 3, "<=": 4, ">=": 5, "is null": 6, "is not null": 7}
+
+
+class HeapRange(C.Structure):
+    _fields_ = [("base", C.c_void_p), ("bytes", C.c_uint64)]
+
+
+def _heap_ranges(blocks):
+    """[uint8 numpy array per heap block] -> polr_heap_range array (keeps the blocks alive with it)"""
+    blocks = [np.ascontiguousarray(b, dtype=np.uint8) for b in blocks]
+    arr = (HeapRange * max(len(blocks), 1))(*[HeapRange(b.ctypes.data, b.nbytes) for b in blocks])
+    arr._keep = blocks
+    return arr
 
 
 class AggSpec(C.Structure):
@@ -339,6 +352,13 @@ class HashTable:
         self.ctx.check(self.ctx.L.polr_ht_set_payload_heap(self.h, payload_col, heap.ctypes.data, heap.nbytes))
         return self
 
+    def set_payload_heaps(self, payload_col, blocks):
+        """polr_ht_set_payload_heaps: a heap made of several blocks (one range each; before finalize)"""
+        L = self.ctx.L
+        L.polr_ht_set_payload_heaps.argtypes = [C.c_void_p, C.c_uint32, C.POINTER(HeapRange), C.c_uint32]
+        self.ctx.check(L.polr_ht_set_payload_heaps(self.h, payload_col, _heap_ranges(blocks), len(blocks)))
+        return self
+
     @classmethod
     def from_rows(cls, ctx, rows, n_rows, row_width, col_offset, col_width, col_signed, n_keys, n_payload):
         rows = np.ascontiguousarray(rows, dtype=np.uint8)
@@ -448,6 +468,12 @@ class Pipeline:
         """polr_pipeline_set_probe_heap: the string heap the cells of probe column `probe_col` point into"""
         heap = np.ascontiguousarray(heap, dtype=np.uint8)
         self.ctx.check(self.ctx.L.polr_pipeline_set_probe_heap(self.h, probe_col, heap.ctypes.data, heap.nbytes))
+
+    def set_probe_heaps(self, probe_col, blocks):
+        """polr_pipeline_set_probe_heaps: a heap made of several blocks (one range each)"""
+        L = self.ctx.L
+        L.polr_pipeline_set_probe_heaps.argtypes = [C.c_void_p, C.c_uint32, C.POINTER(HeapRange), C.c_uint32]
+        self.ctx.check(L.polr_pipeline_set_probe_heaps(self.h, probe_col, _heap_ranges(blocks), len(blocks)))
 
     def set_selection(self, sel, device=False, n=None):
         if sel is None:

@@ -379,8 +379,25 @@ int polr_out_fused_result(polr_out *o, void *stream, polr_agg_value *results, ui
  * A width-16 column holds string_t cells (src/include/duckdb/common/types/string_type.hpp:23-28: 4-byte length; up to 12
  * characters inline; longer: a 4-byte prefix and an 8-byte pointer into a string heap).  RowOperations::Gather copies such
  * cells as they are, the pointer staying into the table's heap (row_gather.cpp:47-86).  A column with non-inlined strings
- * needs that heap on the device: these calls copy the `heap_bytes` bytes at `heap_base` (the address range the uploaded
- * cells' pointers lie in) into HBM and rebase the pointers of the column's cells; owned by the table / pipeline. */
+ * needs that heap on the device.  The reference's heaps (StringHeap, a row layout's heap) are lists of blocks: the *_heaps
+ * calls take one {base, bytes} range per block, copy every range into HBM and rebase the pointers of the column's cells onto
+ * the copies; the heap copy is owned by the table / pipeline.  The contract:
+ *  - ranges must be non-empty, non-NULL and disjoint; every non-NULL cell longer than 12 bytes must lie wholly inside one
+ *    of them (length and pointer of the cell), else POLR_E_INVALID;
+ *  - the cells of NULL rows (column validity 0) are never read -- the reference leaves them uninitialised -- and are
+ *    zeroed (an empty string), so no later kernel follows their pointers;
+ *  - all or nothing: every cell is checked before any is rewritten; on an error the cells are exactly as they were and
+ *    no device heap is kept, so a corrected call may follow;
+ *  - once per column: a second call on a column whose cells were rebased returns POLR_E_INVALID and changes nothing;
+ *  - a payload column's heap is set before the table is finalized (a perfect table keeps a re-ordered copy of the cells).
+ * polr_ht_set_payload_heap / polr_pipeline_set_probe_heap are the same with the one range [heap_base, heap_base +
+ * heap_bytes). */
+typedef struct polr_heap_range {
+	const void *base;
+	uint64_t bytes;
+} polr_heap_range;
+int polr_ht_set_payload_heaps(polr_ht *ht, uint32_t payload_col, const polr_heap_range *ranges, uint32_t n_ranges);
+int polr_pipeline_set_probe_heaps(polr_pipeline *p, uint32_t probe_col, const polr_heap_range *ranges, uint32_t n_ranges);
 int polr_ht_set_payload_heap(polr_ht *ht, uint32_t payload_col, const void *heap_base, uint64_t heap_bytes);
 int polr_pipeline_set_probe_heap(polr_pipeline *p, uint32_t probe_col, const void *heap_base, uint64_t heap_bytes);
 /* MIN / MAX (fn = POLR_AGG_MIN / POLR_AGG_MAX) of a VARCHAR column over the pipeline's output rows, reduced on the

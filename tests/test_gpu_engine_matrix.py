@@ -27,6 +27,7 @@ import numpy as np
 import pytest
 
 from common import orc
+from joinref import Join, Ref, device_rows, sort_rows
 from polr_amd import capi
 
 pytestmark = pytest.mark.gpu
@@ -34,108 +35,6 @@ pytestmark = pytest.mark.gpu
 DTYPES = [np.int8, np.uint8, np.int16, np.uint16, np.int32, np.uint32, np.int64, np.uint64]
 U64 = 0xFFFFFFFFFFFFFFFF
 MAX_WAVE_CHUNKS = 8192  # one partially filled chunk per emitting wave (polr_out_create)
-
-
-# ---- the numpy reference ------------------------------------------------------------------------------------------------
-class Join:
-    """one build side: key column (+ validity), optional payload, probe column it is keyed by, perfect range or hash"""
-
-    def __init__(self, keys, src, perfect=None, valid=None, payload=(), payload_valid=None):
-        self.keys = np.ascontiguousarray(keys)
-        self.src = src
-        self.perfect = perfect
-        self.valid = None if valid is None else np.ascontiguousarray(valid, dtype=np.uint8)
-        self.payload = [np.ascontiguousarray(p) for p in payload]
-        self.payload_valid = payload_valid or [None] * len(self.payload)
-        ok = np.ones(len(self.keys), bool) if self.valid is None else self.valid.astype(bool)
-        rows = np.nonzero(ok)[0]
-        self.order = rows[np.argsort(self.keys[rows], kind="stable")].astype(np.int64)
-        self.sorted = self.keys[self.order]
-        if perfect is not None:
-            # device build id of a perfect table = key - min (modulo 2^64: min may be a uint64's int64 bit pattern); back
-            # to the build row, as pht_orig_rows() maps it.  Every build key lies inside [min, max].
-            off = self.keys[rows].astype(np.uint64) - np.uint64(perfect[0] & U64)
-            size = ((perfect[1] - perfect[0]) & U64) + 1
-            assert (off < np.uint64(size)).all()
-            self.id_to_row = np.full(size, -1, np.int64)
-            self.id_to_row[off.astype(np.int64)] = rows
-
-    def device(self, ctx):
-        ht = capi.HashTable.from_columns(ctx, [self.keys], self.payload, key_valid=[self.valid],
-                                         payload_valid=self.payload_valid)
-        if self.perfect is not None:
-            assert ht.finalize_perfect(*self.perfect)
-            assert ht.info()["kind"] == 1
-        else:
-            ht.finalize_hash()
-        return ht
-
-    def oracle(self):
-        oht = orc.HashTable([self.keys], self.payload, key_valid=[self.valid], payload_valid=self.payload_valid)
-        if self.perfect is not None:
-            assert oht.make_perfect(*self.perfect)
-        return orc.JoinSpec(oht, [(-1, self.src)])
-
-
-class Ref:
-    """the join result of probe columns x joins, restricted to the probe rows in `sel` (None: all)"""
-
-    def __init__(self, pcols, pvalid, joins, sel=None):
-        self.pcols, self.joins = pcols, joins
-        n = len(pcols[0])
-        self.n = n
-        insel = np.ones(n, bool)
-        if sel is not None:
-            insel[:] = False
-            insel[sel] = True
-        self.starts, self.counts = [], []
-        for j in joins:
-            pk = pcols[j.src]
-            left = np.searchsorted(j.sorted, pk, "left")
-            right = np.searchsorted(j.sorted, pk, "right")
-            cnt = (right - left).astype(np.int64)
-            if pvalid is not None and pvalid[j.src] is not None:
-                cnt[~pvalid[j.src].astype(bool)] = 0  # NULL never matches
-            cnt[~insel] = 0
-            self.starts.append(left.astype(np.int64))
-            self.counts.append(cnt)
-
-    def stage_counts(self, path):
-        prod = np.ones(self.n, np.int64)
-        out = []
-        for j in path:
-            prod = prod * self.counts[j]
-            out.append(int(prod.sum()))
-        return out
-
-    def rows(self):
-        """(n_rows, 1 + k) int64: probe row, then the build row of every join in the original join order"""
-        live = np.ones(self.n, bool)
-        for c in self.counts:
-            live &= c > 0
-        t = np.nonzero(live)[0].astype(np.int64)[:, None]
-        for x, j in enumerate(self.joins):
-            r = t[:, 0]
-            c = self.counts[x][r]
-            rep = np.repeat(np.arange(len(t)), c)
-            within = np.arange(len(rep)) - np.repeat(np.cumsum(c) - c, c)
-            b = j.order[np.repeat(self.starts[x][r], c) + within]
-            t = np.column_stack([t[rep], b])
-        return t
-
-
-def sort_rows(a):
-    a = np.asarray(a, dtype=np.int64)
-    return a[np.lexsort(a.T[::-1])] if len(a) else a.reshape(0, a.shape[1] if a.ndim == 2 else 1)
-
-
-def device_rows(ids, joins):
-    """device row ids -> build rows (perfect tables report key offsets)"""
-    rows = ids.astype(np.int64)
-    for x, j in enumerate(joins):
-        if j.perfect is not None:
-            rows[:, 1 + x] = j.id_to_row[rows[:, 1 + x]]
-    return rows
 
 
 def chunks_for(n_rows, cap):
