@@ -319,8 +319,9 @@ __global__ __launch_bounds__(256) void polr_group_agg_kernel(DevOut out, uint32_
 	}
 }
 
-static int resolve_agg_col(polr_pipeline *p, int32_t src_join, uint32_t src_col, const OwnedCol **c, uint32_t *slot,
-                           const char *what, uint32_t idx) {
+// the column (src_join, src_col) names and the slot of the output's row ids that indexes it, whatever its width
+static int locate_agg_col(polr_pipeline *p, int32_t src_join, uint32_t src_col, const OwnedCol **c, uint32_t *slot,
+                          const char *what, uint32_t idx) {
 	polr_ctx *ctx = p->ctx;
 	if (src_join < 0) {
 		if (src_col >= p->n_probe_cols) {
@@ -336,8 +337,18 @@ static int resolve_agg_col(polr_pipeline *p, int32_t src_join, uint32_t src_col,
 		*c = ht->kind == KIND_PERFECT ? &ht->pcols[src_col] : &ht->payload[src_col];
 		*slot = 1 + (uint32_t)src_join;
 	}
+	return POLR_OK;
+}
+
+// ... and an integer column of up to 8 bytes: what every cell-valued sink reads
+static int resolve_agg_col(polr_pipeline *p, int32_t src_join, uint32_t src_col, const OwnedCol **c, uint32_t *slot,
+                           const char *what, uint32_t idx) {
+	int rc = locate_agg_col(p, src_join, src_col, c, slot, what, idx);
+	if (rc) {
+		return rc;
+	}
 	if ((*c)->width > 8 || ((*c)->width == 8 && !((*c)->flags & 1u))) {
-		POLR_FAIL(ctx, POLR_E_UNSUPPORTED, "%s %u: only integer columns of up to 8 bytes (signed if 8)", what, idx);
+		POLR_FAIL(p->ctx, POLR_E_UNSUPPORTED, "%s %u: only integer columns of up to 8 bytes (signed if 8)", what, idx);
 	}
 	return POLR_OK;
 }
@@ -592,9 +603,10 @@ __global__ __launch_bounds__(256) void polr_hash_agg_kernel(DevOut out, uint32_t
 }
 
 // the groups that exist, compacted: [idx] <- slot
+// (reps / reps_out: the representative string cells of the VARCHAR sink further down, or nullptr)
 __global__ __launch_bounds__(256) void polr_hash_agg_compact_kernel(HashAggTable t, uint32_t n_cols, uint32_t n_aggs, long long *keys_out,
                                                                     uint32_t *nulls_out, GroupCell *cells_out, unsigned long long *cursor,
-                                                                    uint64_t max_groups) {
+                                                                    uint64_t max_groups, const uint4 *reps, uint4 *reps_out) {
 	for (uint64_t s = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; s <= t.mask; s += (uint64_t)gridDim.x * blockDim.x) {
 		if (t.state[s] != 2u) {
 			continue;
@@ -605,6 +617,9 @@ __global__ __launch_bounds__(256) void polr_hash_agg_compact_kernel(HashAggTable
 		}
 		for (uint32_t q = 0; q < n_cols; q++) {
 			keys_out[idx * n_cols + q] = t.keys[s * n_cols + q];
+			if (reps) {
+				reps_out[idx * n_cols + q] = reps[s * n_cols + q];
+			}
 		}
 		nulls_out[idx] = t.nulls[s];
 		for (uint32_t a = 0; a < n_aggs; a++) {
@@ -741,7 +756,7 @@ extern "C" int polr_out_aggregate_hashed(polr_out *o, void *stream, const polr_g
 			                   gs, as, t);
 		}
 		hipLaunchKernelGGL(polr_hash_agg_compact_kernel, dim3(256), dim3(256), 0, st, t, n_cols, n_aggs, okeys, onulls, ocells, cnt + 2,
-		                   max_groups);
+		                   max_groups, (const uint4 *)nullptr, (uint4 *)nullptr);
 		e = hipMemcpyAsync(h_cnt, cnt, sizeof(h_cnt), hipMemcpyDeviceToHost, st);
 		e = e == hipSuccess ? hipStreamSynchronize(st) : e;
 	}
@@ -1111,6 +1126,9 @@ __global__ __launch_bounds__(256) void polr_agg_string_kernel(DevOut out, uint32
 	}
 }
 
+// (defined with the VARCHAR GROUP BY sink below) POLR_OK when a kernel may follow the string pointers of the column
+static int check_string_col_on_device(polr_out *o, hipStream_t st, const OwnedCol *c, uint32_t slot, const char *what, uint32_t idx);
+
 // all or nothing: the ranges are checked, copied and every cell validated before any cell is rewritten; on an error the
 // column is as it was and no device memory is kept
 static int set_string_heaps(polr_ctx *ctx, OwnedCol *c, uint64_t n_rows, const polr_heap_range *ranges, uint32_t n_ranges,
@@ -1273,6 +1291,12 @@ int polr_out_aggregate_string(polr_out *o, void *stream, uint32_t fn, int32_t sr
 	if (o->n_chunks == 0) {
 		return POLR_OK;
 	}
+	{ // a column whose heap never came may hold inline strings only: refused before a pointer is followed
+		int rc = check_string_col_on_device(o, st, c, slot, "string aggregate, column", src_col);
+		if (rc) {
+			return rc;
+		}
+	}
 	const uint32_t n_blocks = std::max<uint32_t>(1, std::min<uint32_t>(o->n_chunks, (uint32_t)ctx->n_cus * 4));
 	StrPartial *part = nullptr;
 	HIPCHK(ctx, hipMalloc((void **)&part, ((size_t)n_blocks + 1) * sizeof(StrPartial)));
@@ -1307,3 +1331,492 @@ int polr_out_aggregate_string(polr_out *o, void *stream, uint32_t fn, int32_t sr
 }
 
 } // extern "C"
+
+// ---- the general GROUP BY sink with VARCHAR group columns (SSB: GROUP BY d_year, c_nation / c_city, s_city, d_year / p_brand) ----
+// The table of polr_hash_agg_kernel with, per VARCHAR column, the 64-bit hash of the string's value in the slot's key word and
+// a representative string_t cell beside it (reps[slot][column]; its pointer stays good: it points into the device heap the
+// table / pipeline owns).  A probing row compares the key words -- integer values and string hashes -- and only for a slot
+// that agrees in all of them the strings themselves (polr_str_equal: length, then prefix / inline characters from the two
+// cells, then the heap bytes), so a slot of another group almost never costs a heap read.
+//
+// COMBINE: few hot groups is the common shape (Q4.1: 35 groups for every surviving row).  Once every lane knows its slot,
+// the lanes of a wave that resolved to the SAME slot are folded into their lowest lane -- the leader walks its peers with
+// v_readlane, the work is bounded by 64 peers per wave and aggregate whatever the distribution -- and only leaders and
+// lanes alone on their slot issue atomics: one per distinct slot, aggregate and wave.  !COMBINE: every lane for itself.
+#ifndef POLR_HASH_AGG_WAVE_COMBINE
+#define POLR_HASH_AGG_WAVE_COMBINE 1
+#endif
+#define POLR_NO_SLOT 0xFFFFFFFFu
+
+template <bool COMBINE>
+__global__ __launch_bounds__(256) void polr_hash_agg_str_kernel(DevOut out, uint32_t n_chunks, DevGroupSet groups, DevAggSet aggs,
+                                                                HashAggTable t, uint4 *reps, uint32_t str_mask) {
+	const uint32_t lane = threadIdx.x & 63u;
+	for (uint32_t chunk = blockIdx.x; chunk < n_chunks; chunk += gridDim.x) {
+		const uint32_t n = out.chunk_count[chunk];
+		const uint64_t chunk_base = (uint64_t)chunk * out.chunk_capacity;
+		for (uint32_t i0 = 0; i0 < n; i0 += blockDim.x) {
+			const uint32_t i = i0 + threadIdx.x;
+			const bool active = i < n;
+			long long key[POLR_MAX_GROUP_KEYS] = {0, 0, 0};
+			uint4 cell[POLR_MAX_GROUP_KEYS];
+			uint32_t null_mask = 0;
+			uint64_t h = 0x9E3779B97F4A7C15ull;
+#pragma unroll
+			for (uint32_t q = 0; q < POLR_MAX_GROUP_KEYS; q++) {
+				cell[q] = make_uint4(0, 0, 0, 0);
+				if (active && q < groups.n) {
+					const DevGroupKey &gk = groups.k[q];
+					const uint32_t row = out.ids[(uint64_t)gk.slot * out.slot_stride + chunk_base + i];
+					if (gk.src.valid && !gk.src.valid[row]) {
+						null_mask |= 1u << q; // (the cell of a NULL row is never read)
+					} else if ((str_mask >> q) & 1u) {
+						cell[q] = ((const uint4 *)gk.src.data)[row];
+						key[q] = (long long)polr_str_hash(cell[q]);
+					} else {
+						key[q] = load_col_cell(gk.src, row);
+					}
+					h = polr_murmurhash64(h ^ (uint64_t)key[q]) + q;
+				}
+			}
+			h = polr_murmurhash64(h ^ null_mask);
+			uint64_t s = h & t.mask;
+			bool done = !active;
+			uint64_t probes = 0;
+			while (__syncthreads_or(!done)) { // (every lane of the workgroup takes part in every iteration)
+				if (!done) {
+					uint32_t st = __hip_atomic_load(&t.state[s], __ATOMIC_ACQUIRE, __HIP_MEMORY_SCOPE_AGENT);
+					if (st == 0u) {
+						if (atomicCAS(&t.state[s], 0u, 1u) == 0u) {
+							if (atomicAdd(t.n_groups, 1ull) >= t.max_groups) {
+								atomicExch(t.overflow, 1ull); // (more groups than the caller made room for)
+							}
+#pragma unroll
+							for (uint32_t q = 0; q < POLR_MAX_GROUP_KEYS; q++) {
+								if (q < groups.n) {
+									t.keys[s * groups.n + q] = key[q];
+									reps[s * groups.n + q] = cell[q];
+								}
+							}
+							t.nulls[s] = null_mask;
+							__hip_atomic_store(&t.state[s], 2u, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_AGENT);
+							st = 2u;
+						}
+					}
+					if (st == 2u) {
+						bool same = t.nulls[s] == null_mask;
+#pragma unroll
+						for (uint32_t q = 0; q < POLR_MAX_GROUP_KEYS; q++) {
+							if (q < groups.n) {
+								same = same && t.keys[s * groups.n + q] == key[q];
+							}
+						}
+						if (same) { // (the hashes agree: now the strings)
+#pragma unroll
+							for (uint32_t q = 0; q < POLR_MAX_GROUP_KEYS; q++) {
+								if (q < groups.n && ((str_mask & ~null_mask) >> q) & 1u) {
+									same = same && polr_str_equal(reps[s * groups.n + q], cell[q]);
+								}
+							}
+						}
+						if (same) {
+							done = true;
+						} else {
+							s = (s + 1) & t.mask;
+							if (++probes > t.mask) { // (a full table: cannot happen with capacity >= 2 x max_groups before overflow)
+								atomicExch(t.overflow, 1ull);
+								done = true;
+								s = ~0ull;
+							}
+						}
+					}
+					// (st == 1: somebody is writing this slot's key: look again in the next iteration)
+				}
+			}
+			// every lane of the wave is here, with its slot or none (capacity <= 2^25: a slot fits 32 bits)
+			const uint32_t s32 = (active && s != ~0ull) ? (uint32_t)s : POLR_NO_SLOT;
+			uint32_t lead = lane;  // the lowest lane of the wave with this lane's slot
+			uint64_t shared = 0;   // the lanes whose slot another lane of the wave has too
+			if (COMBINE) {
+				uint64_t todo = __ballot(s32 != POLR_NO_SLOT);
+				while (todo) {
+					const int l = __builtin_ctzll(todo);
+					const uint32_t ls = (uint32_t)__builtin_amdgcn_readlane((int)s32, l);
+					const uint64_t peers = __ballot(s32 == ls);
+					if (s32 == ls) {
+						lead = (uint32_t)l;
+					}
+					if (peers & (peers - 1)) {
+						shared |= peers;
+					}
+					todo &= ~peers;
+				}
+			}
+			for (uint32_t a = 0; a < aggs.n; a++) {
+				const DevAgg &ag = aggs.a[a];
+				bool have = s32 != POLR_NO_SLOT;
+				long long v = 0;
+				if (have && ag.fn != POLR_AGG_COUNT_STAR) {
+					const uint32_t row = out.ids[(uint64_t)ag.slot * out.slot_stride + chunk_base + i];
+					if (ag.src.valid && !ag.src.valid[row]) {
+						have = false; // NULLs take no part
+					} else {
+						v = load_col_cell(ag.src, row);
+					}
+				}
+				unsigned long long cnt = have ? 1ull : 0ull, lo = (unsigned long long)v & 0xFFFFFFFFull;
+				long long hi = v >> 32, mn = v, mx = v;
+				if (COMBINE) {
+					uint64_t m = shared;
+					while (m) {
+						const int l = __builtin_ctzll(m);
+						const bool mine = lead == (uint32_t)l;
+						const uint64_t peers = __ballot(mine);
+						const uint64_t with = __ballot(mine && have);
+						unsigned long long w_lo = 0;
+						long long w_hi = 0, w_mn = 0x7FFFFFFFFFFFFFFFll, w_mx = (long long)0x8000000000000000ull;
+						if (ag.fn == POLR_AGG_SUM) {
+							for (uint64_t b = with; b; b &= b - 1) {
+								const int j = __builtin_ctzll(b);
+								w_lo += (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)lo, j);
+								w_hi += (long long)__builtin_amdgcn_readlane((int)hi, j); // (v >> 32 fits 32 bits)
+							}
+						} else if (ag.fn == POLR_AGG_MIN || ag.fn == POLR_AGG_MAX) {
+							for (uint64_t b = with; b; b &= b - 1) {
+								const int j = __builtin_ctzll(b);
+								const long long o = (long long)(((uint64_t)(uint32_t)__builtin_amdgcn_readlane((int)(v >> 32), j) << 32) |
+								                                (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)v, j));
+								w_mn = o < w_mn ? o : w_mn;
+								w_mx = o > w_mx ? o : w_mx;
+							}
+						}
+						if (mine) {
+							have = lane == (uint32_t)l && with != 0; // (the leader speaks for its peers)
+							cnt = (unsigned long long)__popcll(with);
+							lo = w_lo;
+							hi = w_hi;
+							mn = w_mn;
+							mx = w_mx;
+						}
+						m &= ~peers;
+					}
+				}
+				if (have) {
+					GroupCell *c = &t.cells[(uint64_t)s32 * aggs.n + a];
+					switch (ag.fn) { // (only the words cell_to_value reads for this function)
+					case POLR_AGG_SUM:
+						atomicAdd(&c->lo32, lo);
+						atomicAdd((unsigned long long *)&c->hi32, (unsigned long long)hi);
+						break;
+					case POLR_AGG_MIN:
+						atomicMin(&c->mn, mn);
+						break;
+					case POLR_AGG_MAX:
+						atomicMax(&c->mx, mx);
+						break;
+					default:
+						break;
+					}
+					atomicAdd(&c->count, cnt);
+				}
+			}
+		}
+	}
+}
+
+// the guard of a VARCHAR column whose cells were never rebased onto a device heap: the non-NULL cells among the output rows
+// that are longer than 12 bytes -- their pointers are the host's.  Reads the length word of a cell and nothing else.
+__global__ __launch_bounds__(256) void polr_count_long_cells_kernel(DevOut out, uint32_t n_chunks, DevCol src, uint32_t slot,
+                                                                    unsigned long long *__restrict__ n_long) {
+	unsigned long long mine = 0;
+	for (uint32_t chunk = blockIdx.x; chunk < n_chunks; chunk += gridDim.x) {
+		const uint32_t n = out.chunk_count[chunk];
+		const uint32_t *ids = out.ids + (uint64_t)slot * out.slot_stride + (uint64_t)chunk * out.chunk_capacity;
+		for (uint32_t i = threadIdx.x; i < n; i += blockDim.x) {
+			const uint32_t row = ids[i];
+			if (src.valid && !src.valid[row]) {
+				continue;
+			}
+			mine += *(const uint32_t *)(src.data + (uint64_t)row * 16u) > 12u ? 1u : 0u;
+		}
+	}
+	mine = wave_sum64(mine);
+	if ((threadIdx.x & 63u) == 0 && mine) {
+		atomicAdd(n_long, mine);
+	}
+}
+
+// POLR_OK when the column may be read by a kernel that follows string pointers
+static int check_string_col_on_device(polr_out *o, hipStream_t st, const OwnedCol *c, uint32_t slot, const char *what, uint32_t idx) {
+	polr_ctx *ctx = o->pipe->ctx;
+	if (c->strings_rebased || !c->owned || o->n_chunks == 0) {
+		return POLR_OK; // (rebased here; or the caller's own device memory, whose cells point into HBM by contract)
+	}
+	unsigned long long *n_long = nullptr, h_long = 0;
+	HIPCHK(ctx, hipMalloc((void **)&n_long, 8));
+	hipError_t e = hipMemsetAsync(n_long, 0, 8, st);
+	if (e == hipSuccess) {
+		DevCol src;
+		src.data = c->data;
+		src.valid = c->valid;
+		src.width = c->width;
+		src.flags = c->flags;
+		const uint32_t n_blocks = std::max<uint32_t>(1, std::min<uint32_t>(o->n_chunks, (uint32_t)ctx->n_cus * 4));
+		hipLaunchKernelGGL(polr_count_long_cells_kernel, dim3(n_blocks), dim3(256), 0, st, o->dev, o->n_chunks, src, slot, n_long);
+		e = hipMemcpyAsync(&h_long, n_long, 8, hipMemcpyDeviceToHost, st);
+		e = e == hipSuccess ? hipStreamSynchronize(st) : e;
+	}
+	hipFree(n_long);
+	if (e != hipSuccess) {
+		POLR_FAIL(ctx, POLR_E_HIP, "string column check failed: %s", hipGetErrorString(e));
+	}
+	if (h_long) {
+		POLR_FAIL(ctx, POLR_E_INVALID,
+		          "%s %u: %llu output rows hold strings longer than 12 bytes, but the column's heap was never put on the device "
+		          "(polr_ht_set_payload_heaps / polr_pipeline_set_probe_heaps)",
+		          what, idx, h_long);
+	}
+	return POLR_OK;
+}
+
+// the groups' strings as records {u32 length, bytes} at the offsets the host laid out (offsets[g * n_cols + c])
+__global__ __launch_bounds__(256) void polr_group_strings_kernel(const uint4 *__restrict__ reps, const uint32_t *__restrict__ nulls,
+                                                                 const long long *__restrict__ offsets, uint64_t n_groups,
+                                                                 uint32_t n_cols, uint32_t str_mask, uint8_t *__restrict__ arena,
+                                                                 uint64_t arena_bytes) {
+	const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+	if (i >= n_groups * n_cols) {
+		return;
+	}
+	const uint32_t q = (uint32_t)(i % n_cols);
+	if (!((str_mask >> q) & 1u) || ((nulls[i / n_cols] >> q) & 1u)) {
+		return;
+	}
+	const uint4 c = reps[i];
+	const uint64_t off = (uint64_t)offsets[i];
+	if (off > arena_bytes || arena_bytes - off < 4ull + c.x) {
+		return; // (never past the arena, whatever the offsets say)
+	}
+	uint8_t *dst = arena + off;
+	for (uint32_t j = 0; j < 4; j++) {
+		dst[j] = (uint8_t)(c.x >> (8u * j));
+	}
+	for (uint32_t j = 0; j < c.x; j++) {
+		dst[4 + j] = (uint8_t)str_byte(c, j);
+	}
+}
+
+extern "C" int polr_out_column_width(polr_out *o, int32_t src_join, uint32_t src_col, uint32_t *width) {
+	if (!o || !width) {
+		return POLR_E_INVALID;
+	}
+	const OwnedCol *c = nullptr;
+	uint32_t slot = 0;
+	int rc = locate_agg_col(o->pipe, src_join, src_col, &c, &slot, "column", src_col);
+	if (rc) {
+		return rc;
+	}
+	*width = c->width;
+	return POLR_OK;
+}
+
+extern "C" int polr_out_aggregate_hashed_str(polr_out *o, void *stream, const polr_group_key *cols, uint32_t n_cols,
+                                             const polr_agg_spec *specs, uint32_t n_aggs, uint64_t max_groups, int64_t *group_keys,
+                                             uint32_t *group_nulls, polr_agg_value *results, uint64_t *n_groups, uint8_t *str_bytes,
+                                             uint64_t str_cap, uint64_t *str_used) {
+	POLR_ENTRY();
+	if (!o || !cols || !specs || !group_keys || !group_nulls || !results || !n_groups || !str_used || (!str_bytes && str_cap) ||
+	    n_cols == 0 || n_aggs == 0 || max_groups == 0) {
+		return POLR_E_INVALID;
+	}
+	polr_pipeline *p = o->pipe;
+	polr_ctx *ctx = p->ctx;
+	if (n_cols > POLR_MAX_GROUP_KEYS || n_aggs > POLR_MAX_AGGS || max_groups > (1ull << 24)) {
+		POLR_FAIL(ctx, POLR_E_UNSUPPORTED, "at most %d group columns, %d aggregates and 2^24 groups", POLR_MAX_GROUP_KEYS,
+		          POLR_MAX_AGGS);
+	}
+	*str_used = 0;
+	DevGroupSet gs;
+	memset(&gs, 0, sizeof(gs));
+	gs.n = n_cols;
+	const OwnedCol *gcol[POLR_MAX_GROUP_KEYS] = {};
+	uint32_t str_mask = 0;
+	for (uint32_t q = 0; q < n_cols; q++) {
+		const OwnedCol *c = nullptr;
+		uint32_t slot = 0;
+		int rc = locate_agg_col(p, cols[q].src_join, cols[q].src_col, &c, &slot, "group column", q);
+		if (rc) {
+			return rc;
+		}
+		if (c->width == 16) {
+			str_mask |= 1u << q;
+		} else if (c->width > 8 || (c->width == 8 && !(c->flags & 1u))) {
+			POLR_FAIL(ctx, POLR_E_UNSUPPORTED, "group column %u: an integer column of up to 8 bytes (signed if 8) or a VARCHAR column", q);
+		}
+		gcol[q] = c;
+		gs.k[q].src.data = c->data;
+		gs.k[q].src.valid = c->valid;
+		gs.k[q].src.width = c->width;
+		gs.k[q].src.flags = c->flags;
+		gs.k[q].slot = slot;
+	}
+	if (!str_mask) { // integer columns only: the integer sink itself
+		return polr_out_aggregate_hashed(o, stream, cols, n_cols, specs, n_aggs, max_groups, group_keys, group_nulls, results, n_groups);
+	}
+	DevAggSet as;
+	memset(&as, 0, sizeof(as));
+	as.n = n_aggs;
+	for (uint32_t a = 0; a < n_aggs; a++) {
+		if (specs[a].fn > POLR_AGG_MAX) {
+			POLR_FAIL(ctx, POLR_E_INVALID, "aggregate %u: unknown function %u", a, specs[a].fn);
+		}
+		as.a[a].fn = specs[a].fn;
+		if (specs[a].fn == POLR_AGG_COUNT_STAR) {
+			continue;
+		}
+		const OwnedCol *c = nullptr;
+		uint32_t slot = 0;
+		int rc = resolve_agg_col(p, specs[a].src_join, specs[a].src_col, &c, &slot, "aggregate", a);
+		if (rc) {
+			return rc;
+		}
+		as.a[a].src.data = c->data;
+		as.a[a].src.valid = c->valid;
+		as.a[a].src.width = c->width;
+		as.a[a].src.flags = c->flags;
+		as.a[a].slot = slot;
+	}
+	HIPCHK(ctx, hipSetDevice(ctx->device));
+	hipStream_t st = polr_stream(ctx, stream);
+	if (!o->stats_valid) {
+		int rc = polr_out_stats(o, stream, nullptr, nullptr, nullptr);
+		if (rc) {
+			return rc;
+		}
+	}
+	for (uint32_t q = 0; q < n_cols; q++) { // before any kernel that follows a string pointer is enqueued
+		if ((str_mask >> q) & 1u) {
+			int rc = check_string_col_on_device(o, st, gcol[q], gs.k[q].slot, "group column", q);
+			if (rc) {
+				return rc;
+			}
+		}
+	}
+	uint64_t capacity = 1024;
+	while (capacity < 2 * max_groups) {
+		capacity <<= 1;
+	}
+	HashAggTable t;
+	memset(&t, 0, sizeof(t));
+	t.mask = capacity - 1;
+	t.max_groups = max_groups;
+	// one allocation: state, nulls, counters, keys, representative cells, group cells, and the compacted outputs behind them
+	const size_t b_state = capacity * 4, b_nulls = capacity * 4, b_cnt = 64, b_keys = capacity * n_cols * 8,
+	             b_reps = capacity * n_cols * 16, b_cells = capacity * n_aggs * sizeof(GroupCell),
+	             b_okeys = (max_groups * n_cols * 8 + 15) & ~(size_t)15, // (the uint4 cells behind it stay 16-byte aligned)
+	             b_oreps = max_groups * n_cols * 16, b_onulls = (max_groups * 4 + 15) & ~(size_t)15,
+	             b_ocells = max_groups * n_aggs * sizeof(GroupCell);
+	uint8_t *base = nullptr;
+	HIPCHK(ctx, hipMalloc((void **)&base, b_state + b_nulls + b_cnt + b_keys + b_reps + b_cells + b_okeys + b_oreps + b_onulls + b_ocells));
+	uint8_t *at = base;
+	t.state = (uint32_t *)at;
+	at += b_state;
+	t.nulls = (uint32_t *)at;
+	at += b_nulls;
+	unsigned long long *cnt = (unsigned long long *)at; // [0] groups, [1] overflow, [2] compaction cursor
+	at += b_cnt;
+	t.n_groups = cnt;
+	t.overflow = cnt + 1;
+	t.keys = (long long *)at;
+	at += b_keys;
+	uint4 *reps = (uint4 *)at;
+	at += b_reps;
+	t.cells = (GroupCell *)at;
+	at += b_cells;
+	long long *okeys = (long long *)at;
+	at += b_okeys;
+	uint4 *oreps = (uint4 *)at;
+	at += b_oreps;
+	uint32_t *onulls = (uint32_t *)at;
+	at += b_onulls;
+	GroupCell *ocells = (GroupCell *)at;
+	hipError_t e = hipMemsetAsync(base, 0, b_state + b_nulls + b_cnt, st);
+	unsigned long long h_cnt[3] = {0, 0, 0};
+	if (e == hipSuccess) {
+		hipLaunchKernelGGL(polr_hash_agg_init_kernel, dim3(256), dim3(256), 0, st, t, n_aggs);
+		if (o->n_chunks) {
+			hipLaunchKernelGGL(polr_hash_agg_str_kernel<POLR_HASH_AGG_WAVE_COMBINE != 0>, dim3(std::min<uint32_t>(o->n_chunks, 2048u)),
+			                   dim3(256), 0, st, o->dev, o->n_chunks, gs, as, t, reps, str_mask);
+		}
+		hipLaunchKernelGGL(polr_hash_agg_compact_kernel, dim3(256), dim3(256), 0, st, t, n_cols, n_aggs, okeys, onulls, ocells, cnt + 2,
+		                   max_groups, (const uint4 *)reps, oreps);
+		e = hipMemcpyAsync(h_cnt, cnt, sizeof(h_cnt), hipMemcpyDeviceToHost, st);
+		e = e == hipSuccess ? hipStreamSynchronize(st) : e;
+	}
+	const bool too_many = h_cnt[1] || h_cnt[0] > max_groups;
+	const uint64_t g_n = too_many ? 0 : h_cnt[0];
+	std::vector<GroupCell> hcells(g_n * n_aggs);
+	std::vector<uint4> hreps(g_n * n_cols);
+	std::vector<uint32_t> hnulls(g_n);
+	std::vector<long long> hkeys(g_n * n_cols);
+	uint64_t used = 0;
+	if (e == hipSuccess && g_n) {
+		e = hipMemcpy(hkeys.data(), okeys, g_n * n_cols * 8, hipMemcpyDeviceToHost);
+		e = e == hipSuccess ? hipMemcpy(hnulls.data(), onulls, g_n * 4, hipMemcpyDeviceToHost) : e;
+		e = e == hipSuccess ? hipMemcpy(hreps.data(), oreps, g_n * n_cols * 16, hipMemcpyDeviceToHost) : e;
+		e = e == hipSuccess ? hipMemcpy(hcells.data(), ocells, g_n * n_aggs * sizeof(GroupCell), hipMemcpyDeviceToHost) : e;
+		// lay the records out: a VARCHAR column's key word becomes the offset of its record (0 for NULL)
+		for (uint64_t g = 0; g < g_n && e == hipSuccess; g++) {
+			for (uint32_t q = 0; q < n_cols; q++) {
+				if (!((str_mask >> q) & 1u)) {
+					continue;
+				}
+				long long &k = hkeys[g * n_cols + q];
+				k = 0;
+				if (!((hnulls[g] >> q) & 1u)) {
+					k = (long long)used;
+					used += 4ull + hreps[g * n_cols + q].x;
+				}
+			}
+		}
+	}
+	uint8_t *arena = nullptr;
+	if (e == hipSuccess && g_n && used && used <= str_cap) {
+		e = hipMalloc((void **)&arena, used);
+		e = e == hipSuccess ? hipMemcpyAsync(okeys, hkeys.data(), g_n * n_cols * 8, hipMemcpyHostToDevice, st) : e;
+		if (e == hipSuccess) {
+			const uint64_t n_rec = g_n * n_cols;
+			hipLaunchKernelGGL(polr_group_strings_kernel, dim3((unsigned)((n_rec + 255) / 256)), dim3(256), 0, st, (const uint4 *)oreps,
+			                   (const uint32_t *)onulls, (const long long *)okeys, g_n, n_cols, str_mask, arena, used);
+			e = hipMemcpyAsync(str_bytes, arena, used, hipMemcpyDeviceToHost, st);
+			e = e == hipSuccess ? hipStreamSynchronize(st) : e;
+		}
+	}
+	if (arena) {
+		hipFree(arena);
+	}
+	hipFree(base);
+	if (e != hipSuccess) {
+		POLR_FAIL(ctx, POLR_E_HIP, "hash aggregate failed: %s", hipGetErrorString(e));
+	}
+	*n_groups = h_cnt[0];
+	if (too_many) {
+		POLR_FAIL(ctx, POLR_E_OVERFLOW, "the result has %llu groups or more, the caller made room for %llu",
+		          (unsigned long long)h_cnt[0], (unsigned long long)max_groups);
+	}
+	*str_used = used;
+	if (used > str_cap) { // (nothing was written: group_keys, group_nulls, results and str_bytes are as they were)
+		POLR_FAIL(ctx, POLR_E_OVERFLOW, "the groups' strings take %llu bytes, the caller made room for %llu", (unsigned long long)used,
+		          (unsigned long long)str_cap);
+	}
+	if (g_n) {
+		memcpy(group_keys, hkeys.data(), g_n * n_cols * 8);
+		memcpy(group_nulls, hnulls.data(), g_n * 4);
+	}
+	for (uint64_t g = 0; g < g_n; g++) {
+		for (uint32_t a = 0; a < n_aggs; a++) {
+			cell_to_value(hcells[g * n_aggs + a], specs[a].fn, results[g * n_aggs + a]);
+		}
+	}
+	return POLR_OK;
+}

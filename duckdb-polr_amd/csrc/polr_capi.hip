@@ -594,6 +594,7 @@ static int alloc_perfect_cols(polr_ht *ht, uint64_t size) {
 		c.width = ht->payload[i].width;
 		c.flags = ht->payload[i].flags;
 		c.owned = true;
+		c.strings_rebased = ht->payload[i].strings_rebased; // (the re-ordered copy holds the same cells)
 		int rc = dev_alloc(ctx, (void **)&c.data, size * c.width, &ht->device_bytes);
 		if (!rc) {
 			rc = dev_alloc(ctx, (void **)&c.valid, size, &ht->device_bytes);

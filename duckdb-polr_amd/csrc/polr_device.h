@@ -112,8 +112,10 @@ struct DevPath {
 // hold the same string -- the verifying condition of a VARCHAR join key (POLR_CMP_STR_EQ): the key itself is the 64-bit
 // hash the engine computed for the bucket, as in JoinHashTable::Hash + RowOperations::Match
 #define POLR_PRED_STR_EQ 8u
-__device__ __forceinline__ bool polr_str_cells_equal(const uint8_t *a_cell, const uint8_t *b_cell) {
-	const uint4 a = *(const uint4 *)a_cell, b = *(const uint4 *)b_cell;
+// (cells in registers: the one definition of "the same string" -- the join condition below and the VARCHAR group columns of
+// the general GROUP BY sink, polr_agg.hip.  Lengths first, then the characters: the padding of an inline cell and the
+// pointer of a long one are never compared.)
+__device__ __forceinline__ bool polr_str_equal(const uint4 &a, const uint4 &b) {
 	if (a.x != b.x) {
 		return false;
 	}
@@ -140,6 +142,9 @@ __device__ __forceinline__ bool polr_str_cells_equal(const uint8_t *a_cell, cons
 		}
 	}
 	return true;
+}
+__device__ __forceinline__ bool polr_str_cells_equal(const uint8_t *a_cell, const uint8_t *b_cell) {
+	return polr_str_equal(*(const uint4 *)a_cell, *(const uint4 *)b_cell);
 }
 
 struct StageExt {
@@ -289,6 +294,46 @@ __host__ __device__ inline uint64_t polr_murmurhash64(uint64_t x) {
 	x ^= x >> 32;
 	return x;
 }
+
+#if defined(__HIPCC__) || defined(__HIP_DEVICE_COMPILE__)
+// 64-bit hash of a string_t cell's value: the length, then the characters 8 at a time (the last group zero-padded) --
+// inline strings from the cell (padding masked off), long ones through the pointer, never past the string's end.  Equal
+// strings hash equally whatever their padding or heap address; a NULL row's cell must not be handed in.
+__device__ __forceinline__ uint64_t polr_str_hash(const uint4 &c) {
+	const uint32_t n = c.x;
+	uint64_t h = polr_murmurhash64(0x9E3779B97F4A7C15ull ^ n);
+	if (n <= 12u) {
+		uint32_t w[3] = {c.y, c.z, c.w};
+#pragma unroll
+		for (uint32_t i = 0; i < 3; i++) {
+			const uint32_t left = n > 4u * i ? n - 4u * i : 0u;
+			w[i] &= left >= 4u ? 0xFFFFFFFFu : (left ? (1u << (8u * left)) - 1u : 0u);
+		}
+		if (n) {
+			h = polr_murmurhash64(h ^ (((uint64_t)w[1] << 32) | w[0]));
+		}
+		if (n > 8u) {
+			h = polr_murmurhash64(h ^ w[2]);
+		}
+		return h;
+	}
+	const uint8_t *p = (const uint8_t *)(((uint64_t)c.w << 32) | c.z);
+	uint32_t i = 0;
+	for (; i + 8u <= n; i += 8u) {
+		uint64_t w;
+		__builtin_memcpy(&w, p + i, 8);
+		h = polr_murmurhash64(h ^ w);
+	}
+	if (i < n) {
+		uint64_t w = 0;
+		for (uint32_t j = 0; i + j < n; j++) {
+			w |= (uint64_t)p[i + j] << (8u * j);
+		}
+		h = polr_murmurhash64(h ^ w);
+	}
+	return h;
+}
+#endif
 
 // ---- the rules every device kernel shares ----------------------------------------------------------------------------
 // Data formats and key semantics that build, scan, probe and sink kernels must agree on bit for bit -- one definition

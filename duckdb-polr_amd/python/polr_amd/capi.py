@@ -37,7 +37,7 @@ EXPORTS = [
     "polr_ctx_set_pool_tuning", "polr_ctx_get_stream",
     "polr_ht_set_payload_heap", "polr_pipeline_set_probe_heap", "polr_out_aggregate_string", "polr_ht_set_key_flags",
     "polr_out_fuse_grouped", "polr_out_fused_result", "polr_out_aggregate_hashed",
-    "polr_ht_set_payload_heaps", "polr_pipeline_set_probe_heaps",
+    "polr_ht_set_payload_heaps", "polr_pipeline_set_probe_heaps", "polr_out_aggregate_hashed_str", "polr_out_column_width",
 ]
 
 
@@ -202,6 +202,8 @@ def load():
     L.polr_out_aggregate_grouped.argtypes = [vp, vp, vp, u32, vp, u32, vp, C.c_uint64, vp]
     L.polr_out_fuse_grouped.argtypes = [vp, vp, u32, vp, u32]
     L.polr_out_aggregate_hashed.argtypes = [vp, vp, vp, u32, vp, u32, C.c_uint64, vp, vp, vp, vp]
+    L.polr_out_column_width.argtypes = [vp, C.c_int32, u32, P(u32)]
+    L.polr_out_aggregate_hashed_str.argtypes = [vp, vp, vp, u32, vp, u32, C.c_uint64, vp, vp, vp, vp, vp, C.c_uint64, vp]
     L.polr_out_fused_result.argtypes = [vp, vp, vp, C.c_uint64, vp]
     L.polr_mpx_run_resident.argtypes = [vp, vp, vp, vp, u32, vp, u32]
     L.polr_mpx_run_resident_morsels.argtypes = [vp, vp, C.c_uint64, C.c_uint64, u32, u32, vp, u32]
@@ -626,6 +628,58 @@ class Output:
                         for a in range(na)]
         return out
 
+    def _col_width(self, src_join, src_col):
+        """polr_out_column_width: cell width of a probe column (src_join < 0) or of a payload column of join src_join"""
+        w = C.c_uint32()
+        self.ctx.check(self.ctx.L.polr_out_column_width(self.h, src_join, src_col, C.byref(w)))
+        return w.value
+
+    def aggregate_hashed_str(self, cols, specs, max_groups, str_cap=None, stream=None):
+        """polr_out_aggregate_hashed_str: the general GROUP BY whose group columns may be VARCHAR (width-16 string_t
+        columns, grouped by the strings' bytes) or integer, in any mix.  cols / specs as in aggregate_hashed ->
+        {group key tuple: [value per aggregate]} with bytes for a VARCHAR column, int for an integer one, None for NULL.
+        The byte arena of the groups' strings is sized here (str_cap: a first guess) and the call repeated once with the
+        exact size when the guess was too small."""
+        nk, na = len(cols), len(specs)
+        ka = (GroupKey * nk)()
+        for i, (sj, sc) in enumerate(cols):
+            ka[i].src_join, ka[i].src_col = sj, sc
+        sa = (AggSpec * na)()
+        for i, (fn, sj, sc) in enumerate(specs):
+            sa[i].fn, sa[i].src_join, sa[i].src_col = AGG[fn] if isinstance(fn, str) else fn, sj, sc
+        keys = np.zeros((max_groups, nk), dtype=np.int64)
+        nulls = np.zeros((max_groups,), dtype=np.uint32)
+        res = (AggValue * (max_groups * na))()
+        n, used = C.c_uint64(), C.c_uint64()
+        cap = max(4096, 24 * max_groups) if str_cap is None else int(str_cap)
+        for attempt in (0, 1):
+            arena = np.zeros((cap,), dtype=np.uint8)
+            rc = self.ctx.L.polr_out_aggregate_hashed_str(self.h, stream, ka, nk, sa, na, max_groups, keys.ctypes.data,
+                                                          nulls.ctypes.data, res, C.byref(n), arena.ctypes.data, cap,
+                                                          C.byref(used))
+            if rc == E_OVERFLOW and attempt == 0 and used.value > cap:  # (the strings did not fit; the groups did)
+                cap = used.value
+                continue
+            self.ctx.check(rc)
+            break
+        raw = arena.tobytes()
+        is_str = [self._col_width(sj, sc) == 16 for sj, sc in cols]
+        out = {}
+        for g in range(n.value):
+            key = []
+            for c in range(nk):
+                if (nulls[g] >> c) & 1:
+                    key.append(None)
+                elif is_str[c]:
+                    at = int(keys[g, c])
+                    ln = int.from_bytes(raw[at:at + 4], "little")
+                    key.append(raw[at + 4:at + 4 + ln])
+                else:
+                    key.append(int(keys[g, c]))
+            out[tuple(key)] = [None if res[g * na + a].is_null else (res[g * na + a].hi << 64) + (res[g * na + a].lo & 0xFFFFFFFFFFFFFFFF)
+                               for a in range(na)]
+        return out
+
     def fuse_grouped(self, keys, specs):
         """polr_out_fuse_grouped: fold the join result into group cells inside the run (flat pipelines of perfect tables;
         COUNT(*) / COUNT / SUM).  keys / specs as in aggregate_grouped; keys=None un-fuses.  reset() zeroes the cells."""
@@ -908,10 +962,12 @@ def build_joins(ctx, wl, auto=False):
     for j in wl["joins"]:
         pv = [j.get("payload_valid", {}).get(n) for n in j["payload"].keys()]
         # VARCHAR payload columns (j["strings"]: name -> bytes per build row) go behind the fixed-width ones, as 16-byte
-        # string_t cells + one heap each (string_payload_index gives their column number)
+        # string_t cells + one heap each (string_payload_index gives their column number); j["strings_valid"]: name ->
+        # validity bytes of such a column (absent: no NULLs)
         strs = [string_cells(v) for v in j.get("strings", {}).values()]
         ht = HashTable.from_columns(ctx, j["keys"], list(j["payload"].values()) + [c for c, _h in strs],
-                                    key_valid=j.get("key_valid"), payload_valid=pv + [None] * len(strs))
+                                    key_valid=j.get("key_valid"),
+                                    payload_valid=pv + [j.get("strings_valid", {}).get(n) for n in j.get("strings", {})])
         for i, (_c, heap) in enumerate(strs):
             ht.set_payload_heap(len(j["payload"]) + i, heap)
         # j["key_flags"]: per key column KEY_BY_VALUE (the probe side reads another integer type: a CAST'ed key) and / or

@@ -363,6 +363,34 @@ int polr_out_aggregate_grouped(polr_out *o, void *stream, const polr_group_key *
 int polr_out_aggregate_hashed(polr_out *o, void *stream, const polr_group_key *cols, uint32_t n_cols,
                               const polr_agg_spec *specs, uint32_t n_aggs, uint64_t max_groups, int64_t *group_keys,
                               uint32_t *group_nulls, polr_agg_value *results, uint64_t *n_groups);
+/* The general GROUP BY sink with VARCHAR group columns (SSB: GROUP BY d_year, c_nation; c_city, s_city, d_year; d_year,
+ * p_brand).  Each of the 1..3 group columns is taken for what it is: a width-16 column holds string_t cells (see "VARCHAR
+ * columns" below) and groups by the string's VALUE -- two rows are in one group iff their lengths and all their bytes are
+ * equal (bytes unsigned; \0 and 0x80-0xFF are ordinary bytes; the empty string is a group and is not NULL; the padding of
+ * an inline cell and the heap address of a long string play no part) --; a column of up to 8 bytes groups as in
+ * polr_out_aggregate_hashed (unsigned 64-bit: POLR_E_UNSUPPORTED).  NULL is a group value of its own per column; the cell of
+ * a NULL row is never read.  The aggregates are those of polr_out_aggregate over integer columns.  With integer columns only
+ * the call IS polr_out_aggregate_hashed (and *str_used = 0).
+ * Results as for polr_out_aggregate_hashed, except that for a VARCHAR column group_keys[g * n_cols + c] is the byte offset
+ * in str_bytes of the record {uint32 length (little endian), bytes} of the group's string (0, and to be ignored, when the
+ * column's group_nulls bit is set).  *str_used = the bytes the records take.  str_cap < *str_used: POLR_E_OVERFLOW with
+ * *n_groups and *str_used exact and group_keys, group_nulls, results and str_bytes untouched -- one retry with str_cap =
+ * *str_used succeeds.  More than max_groups groups: POLR_E_OVERFLOW as for polr_out_aggregate_hashed, *str_used = 0.
+ * The strings of a VARCHAR column longer than 12 bytes are read through the cells' pointers, so they must be on the device:
+ * the column's heap was handed over (polr_ht_set_payload_heaps / polr_pipeline_set_probe_heaps), or the column lives in
+ * the caller's device memory (POLR_COL_DEVICE: its cells point into HBM by contract).  For a column the library uploaded
+ * whose heap it never got, the call first counts the non-NULL cells longer than 12 bytes among the output rows (reading
+ * their length word and nothing else); any such cell: POLR_E_INVALID, before a kernel that follows a pointer is enqueued.
+ * All-inline columns need no heap.  MIN / MAX of a VARCHAR per group, and VARCHAR columns in polr_out_aggregate_grouped and
+ * polr_out_fuse_grouped, are not provided. */
+int polr_out_aggregate_hashed_str(polr_out *o, void *stream, const polr_group_key *cols, uint32_t n_cols,
+                                  const polr_agg_spec *specs, uint32_t n_aggs, uint64_t max_groups, int64_t *group_keys,
+                                  uint32_t *group_nulls, polr_agg_value *results, uint64_t *n_groups, uint8_t *str_bytes,
+                                  uint64_t str_cap, uint64_t *str_used);
+/* Cell width in bytes of the column (src_join, src_col) as the sinks address it (src_join = -1: probe column): 16 = a VARCHAR
+ * column of string_t cells, 1 / 2 / 4 / 8 an integer one.  How a caller of polr_out_aggregate_hashed_str that did not create
+ * the tables itself (a broadcast copy, polr_ht_alloc_like) tells which group_keys entries are offsets. */
+int polr_out_column_width(polr_out *o, int32_t src_join, uint32_t src_col, uint32_t *width);
 /* The same GROUP BY FUSED into the run (SSB-skew Q4.1 as shipped: benchmark/ssb-skew/queries/q4-1.sql): an output object
  * with a fused sink makes the pipeline's LAST join fold every surviving tuple into the group cells instead of writing its
  * row ids -- nothing of the join result is written or read back.  For FLAT pipelines whose joins are all perfect tables
@@ -403,7 +431,9 @@ int polr_pipeline_set_probe_heap(polr_pipeline *p, uint32_t probe_col, const voi
 /* MIN / MAX (fn = POLR_AGG_MIN / POLR_AGG_MAX) of a VARCHAR column over the pipeline's output rows, reduced on the
  * device (src/function/aggregate/distributive/minmax.cpp over string_t: bytes compared as unsigned, a proper prefix
  * sorts first; NULLs take no part).  The winning string's bytes go to dst (at most dst_cap of them), *len = its whole
- * length; *is_null = 1 when no row had a non-NULL value. */
+ * length; *is_null = 1 when no row had a non-NULL value.  A column the library uploaded whose heap it never got may hold
+ * inline strings only: a non-NULL cell longer than 12 bytes among the output rows is POLR_E_INVALID (found by a pass that
+ * reads the cells' length words only), as for polr_out_aggregate_hashed_str. */
 int polr_out_aggregate_string(polr_out *o, void *stream, uint32_t fn, int32_t src_join, uint32_t src_col, char *dst,
                               uint32_t dst_cap, uint32_t *len, uint32_t *is_null);
 void polr_out_destroy(polr_out *o);
