@@ -94,6 +94,93 @@ __global__ __launch_bounds__(256) void polr_agg_kernel(DevOut out, uint32_t n_ch
 	}
 }
 
+int polr_out_col(polr_pipeline *p, int32_t src_join, uint32_t src_col, OutCol *c, const char *what, uint32_t idx) {
+	if (src_join < 0) {
+		if (src_col >= p->n_probe_cols) {
+			POLR_FAIL(p->ctx, POLR_E_INVALID, "%s %u: probe column %u out of range", what, idx, src_col);
+		}
+		c->col = &p->probe_cols[src_col];
+		c->slot = 0;
+	} else {
+		if ((uint32_t)src_join >= p->k || src_col >= p->hts[src_join]->n_payload) {
+			POLR_FAIL(p->ctx, POLR_E_INVALID, "%s %u: build column (%d,%u) out of range", what, idx, src_join, src_col);
+		}
+		c->col = &build_col(p->hts[src_join], src_col);
+		c->slot = 1 + (uint32_t)src_join;
+	}
+	c->dev = dev_col(*c->col);
+	return POLR_OK;
+}
+
+int polr_out_int_col(polr_pipeline *p, int32_t src_join, uint32_t src_col, OutCol *c, const char *what, uint32_t idx) {
+	int rc = polr_out_col(p, src_join, src_col, c, what, idx);
+	if (!rc && (c->dev.width > 8 || (c->dev.width == 8 && !(c->dev.flags & 1u)))) {
+		POLR_FAIL(p->ctx, POLR_E_UNSUPPORTED, "%s %u: only integer columns of up to 8 bytes (signed if 8)", what, idx);
+	}
+	return rc;
+}
+
+// one aggregate as the sink kernels read it: POLR_E_INVALID for an unknown function or a column out of range,
+// POLR_E_UNSUPPORTED for a column other than an integer of up to 8 bytes
+static int build_agg(polr_pipeline *p, const polr_agg_spec &s, uint32_t a, DevAgg *ag) {
+	if (s.fn > POLR_AGG_MAX) {
+		POLR_FAIL(p->ctx, POLR_E_INVALID, "aggregate %u: unknown function %u", a, s.fn);
+	}
+	ag->fn = s.fn;
+	if (s.fn == POLR_AGG_COUNT_STAR) {
+		return POLR_OK;
+	}
+	OutCol c;
+	int rc = polr_out_int_col(p, s.src_join, s.src_col, &c, "aggregate", a);
+	if (rc) {
+		return rc;
+	}
+	ag->src = c.dev;
+	ag->slot = c.slot;
+	return POLR_OK;
+}
+
+static int build_agg_set(polr_pipeline *p, const polr_agg_spec *specs, uint32_t n_aggs, DevAggSet *set) {
+	memset(set, 0, sizeof(*set));
+	set->n = n_aggs;
+	for (uint32_t a = 0; a < n_aggs; a++) {
+		int rc = build_agg(p, specs[a], a, &set->a[a]);
+		if (rc) {
+			return rc;
+		}
+	}
+	return POLR_OK;
+}
+
+// what the C ABI reports for an aggregate: COUNT is never NULL; the others are NULL when no row took part
+static polr_agg_value agg_value(uint32_t fn, __int128 sum, long long mn, long long mx, unsigned long long count) {
+	polr_agg_value v;
+	memset(&v, 0, sizeof(v));
+	v.count = count;
+	switch (fn) {
+	case POLR_AGG_COUNT_STAR:
+	case POLR_AGG_COUNT:
+		v.lo = (int64_t)count;
+		break;
+	case POLR_AGG_SUM:
+		v.is_null = count == 0;
+		v.lo = (int64_t)(unsigned long long)sum;
+		v.hi = (int64_t)(sum >> 64);
+		break;
+	case POLR_AGG_MIN:
+		v.is_null = count == 0;
+		v.lo = count ? mn : 0;
+		v.hi = (count && mn < 0) ? -1 : 0;
+		break;
+	default:
+		v.is_null = count == 0;
+		v.lo = count ? mx : 0;
+		v.hi = (count && mx < 0) ? -1 : 0;
+		break;
+	}
+	return v;
+}
+
 extern "C" {
 
 int polr_out_aggregate(polr_out *o, void *stream, const polr_agg_spec *specs, uint32_t n_aggs,
@@ -108,50 +195,15 @@ int polr_out_aggregate(polr_out *o, void *stream, const polr_agg_spec *specs, ui
 		POLR_FAIL(ctx, POLR_E_UNSUPPORTED, "at most %d aggregates per call", POLR_MAX_AGGS);
 	}
 	DevAggSet set;
-	memset(&set, 0, sizeof(set));
-	set.n = n_aggs;
-	for (uint32_t a = 0; a < n_aggs; a++) {
-		const polr_agg_spec &s = specs[a];
-		if (s.fn > POLR_AGG_MAX) {
-			POLR_FAIL(ctx, POLR_E_INVALID, "aggregate %u: unknown function %u", a, s.fn);
-		}
-		set.a[a].fn = s.fn;
-		if (s.fn == POLR_AGG_COUNT_STAR) {
-			continue;
-		}
-		const OwnedCol *c;
-		if (s.src_join < 0) {
-			if (s.src_col >= p->n_probe_cols) {
-				POLR_FAIL(ctx, POLR_E_INVALID, "aggregate %u: probe column %u out of range", a, s.src_col);
-			}
-			c = &p->probe_cols[s.src_col];
-			set.a[a].slot = 0;
-		} else {
-			if ((uint32_t)s.src_join >= p->k || s.src_col >= p->hts[s.src_join]->n_payload) {
-				POLR_FAIL(ctx, POLR_E_INVALID, "aggregate %u: build column (%d,%u) out of range", a, s.src_join, s.src_col);
-			}
-			const polr_ht *ht = p->hts[s.src_join];
-			c = ht->kind == KIND_PERFECT ? &ht->pcols[s.src_col] : &ht->payload[s.src_col];
-			set.a[a].slot = 1 + (uint32_t)s.src_join;
-		}
-		if (c->width > 8) {
-			POLR_FAIL(ctx, POLR_E_UNSUPPORTED, "aggregate %u: only integer columns of up to 8 bytes", a);
-		}
-		if (c->width == 8 && !(c->flags & 1u)) {
-			POLR_FAIL(ctx, POLR_E_UNSUPPORTED, "aggregate %u: unsigned 64-bit column", a);
-		}
-		set.a[a].src.data = c->data;
-		set.a[a].src.valid = c->valid;
-		set.a[a].src.width = c->width;
-		set.a[a].src.flags = c->flags;
+	int rc = build_agg_set(p, specs, n_aggs, &set);
+	if (rc) {
+		return rc;
 	}
 	HIPCHK(ctx, hipSetDevice(ctx->device));
 	hipStream_t st = polr_stream(ctx, stream);
-	if (!o->stats_valid) {
-		int rc = polr_out_stats(o, stream, nullptr, nullptr, nullptr);
-		if (rc) {
-			return rc;
-		}
+	rc = out_ensure_stats(o, stream);
+	if (rc) {
+		return rc;
 	}
 	const uint32_t n_blocks = std::max<uint32_t>(1, std::min<uint32_t>(o->n_chunks, (uint32_t)ctx->n_cus * 8));
 	std::vector<AggPartial> host((size_t)n_blocks * n_aggs);
@@ -177,30 +229,7 @@ int polr_out_aggregate(polr_out *o, void *stream, const polr_agg_spec *specs, ui
 			mx = r.mx > mx ? r.mx : mx;
 			cnt += r.count;
 		}
-		polr_agg_value &v = results[a];
-		memset(&v, 0, sizeof(v));
-		v.count = cnt;
-		switch (specs[a].fn) {
-		case POLR_AGG_COUNT_STAR:
-		case POLR_AGG_COUNT:
-			v.lo = (int64_t)cnt; // COUNT is never NULL
-			break;
-		case POLR_AGG_SUM:
-			v.is_null = cnt == 0;
-			v.lo = (int64_t)(unsigned long long)sum;
-			v.hi = (int64_t)(sum >> 64);
-			break;
-		case POLR_AGG_MIN:
-			v.is_null = cnt == 0;
-			v.lo = cnt ? mn : 0;
-			v.hi = (cnt && mn < 0) ? -1 : 0;
-			break;
-		default:
-			v.is_null = cnt == 0;
-			v.lo = cnt ? mx : 0;
-			v.hi = (cnt && mx < 0) ? -1 : 0;
-			break;
-		}
+		results[a] = agg_value(specs[a].fn, sum, mn, mx, cnt);
 	}
 	return POLR_OK;
 }
@@ -231,14 +260,14 @@ __device__ __forceinline__ void cell_add(GroupCell *c, long long v) {
 	atomicAdd(&c->count, 1ull);
 }
 
-__global__ __launch_bounds__(256) void polr_group_init_kernel(GroupCell *cells, uint32_t n) {
-	const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
-	if (i < n) {
-		cells[i].lo32 = 0;
-		cells[i].hi32 = 0;
-		cells[i].mn = 0x7FFFFFFFFFFFFFFFll;
-		cells[i].mx = (long long)0x8000000000000000ull;
-		cells[i].count = 0;
+// a cell no row has reached: the sums and the count 0, MIN / MAX at the far ends
+__device__ __forceinline__ GroupCell empty_cell() {
+	return GroupCell {0, 0, 0x7FFFFFFFFFFFFFFFll, (long long)0x8000000000000000ull, 0};
+}
+
+__global__ __launch_bounds__(256) void polr_group_init_kernel(GroupCell *cells, uint64_t n) {
+	for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (uint64_t)gridDim.x * blockDim.x) {
+		cells[i] = empty_cell();
 	}
 }
 
@@ -250,11 +279,7 @@ __global__ __launch_bounds__(256) void polr_group_agg_kernel(DevOut out, uint32_
 	const uint32_t n_cells = groups.n_groups * aggs.n;
 	if (use_lds) {
 		for (uint32_t i = threadIdx.x; i < n_cells; i += blockDim.x) {
-			local[i].lo32 = 0;
-			local[i].hi32 = 0;
-			local[i].mn = 0x7FFFFFFFFFFFFFFFll;
-			local[i].mx = (long long)0x8000000000000000ull;
-			local[i].count = 0;
+			local[i] = empty_cell();
 		}
 		__syncthreads();
 	}
@@ -319,43 +344,14 @@ __global__ __launch_bounds__(256) void polr_group_agg_kernel(DevOut out, uint32_
 	}
 }
 
-// the column (src_join, src_col) names and the slot of the output's row ids that indexes it, whatever its width
-static int locate_agg_col(polr_pipeline *p, int32_t src_join, uint32_t src_col, const OwnedCol **c, uint32_t *slot,
-                          const char *what, uint32_t idx) {
-	polr_ctx *ctx = p->ctx;
-	if (src_join < 0) {
-		if (src_col >= p->n_probe_cols) {
-			POLR_FAIL(ctx, POLR_E_INVALID, "%s %u: probe column %u out of range", what, idx, src_col);
-		}
-		*c = &p->probe_cols[src_col];
-		*slot = 0;
-	} else {
-		if ((uint32_t)src_join >= p->k || src_col >= p->hts[src_join]->n_payload) {
-			POLR_FAIL(ctx, POLR_E_INVALID, "%s %u: build column (%d,%u) out of range", what, idx, src_join, src_col);
-		}
-		const polr_ht *ht = p->hts[src_join];
-		*c = ht->kind == KIND_PERFECT ? &ht->pcols[src_col] : &ht->payload[src_col];
-		*slot = 1 + (uint32_t)src_join;
-	}
-	return POLR_OK;
-}
-
-// ... and an integer column of up to 8 bytes: what every cell-valued sink reads
-static int resolve_agg_col(polr_pipeline *p, int32_t src_join, uint32_t src_col, const OwnedCol **c, uint32_t *slot,
-                           const char *what, uint32_t idx) {
-	int rc = locate_agg_col(p, src_join, src_col, c, slot, what, idx);
-	if (rc) {
-		return rc;
-	}
-	if ((*c)->width > 8 || ((*c)->width == 8 && !((*c)->flags & 1u))) {
-		POLR_FAIL(p->ctx, POLR_E_UNSUPPORTED, "%s %u: only integer columns of up to 8 bytes (signed if 8)", what, idx);
-	}
-	return POLR_OK;
+static polr_agg_value cell_value(const GroupCell &c, uint32_t fn) {
+	return agg_value(fn, ((__int128)c.hi32 << 32) + (__int128)c.lo32, c.mn, c.mx, c.count);
 }
 
 extern "C" int polr_out_aggregate_grouped(polr_out *o, void *stream, const polr_group_key *keys, uint32_t n_keys,
                                           const polr_agg_spec *specs, uint32_t n_aggs, polr_agg_value *results,
                                           uint64_t n_groups, uint64_t *n_dropped) {
+	POLR_ENTRY();
 	if (!o || !keys || !specs || !results || n_keys == 0 || n_aggs == 0) {
 		return POLR_E_INVALID;
 	}
@@ -369,9 +365,8 @@ extern "C" int polr_out_aggregate_grouped(polr_out *o, void *stream, const polr_
 	gs.n = n_keys;
 	uint64_t groups = 1;
 	for (uint32_t q = 0; q < n_keys; q++) {
-		const OwnedCol *c = nullptr;
-		uint32_t slot = 0;
-		int rc = resolve_agg_col(p, keys[q].src_join, keys[q].src_col, &c, &slot, "group column", q);
+		OutCol c;
+		int rc = polr_out_int_col(p, keys[q].src_join, keys[q].src_col, &c, "group column", q);
 		if (rc) {
 			return rc;
 		}
@@ -382,11 +377,8 @@ extern "C" int polr_out_aggregate_grouped(polr_out *o, void *stream, const polr_
 		if (groups > (1u << 20)) {
 			POLR_FAIL(ctx, POLR_E_UNSUPPORTED, "more than 2^20 groups: not a perfect-hash aggregate");
 		}
-		gs.k[q].src.data = c->data;
-		gs.k[q].src.valid = c->valid;
-		gs.k[q].src.width = c->width;
-		gs.k[q].src.flags = c->flags;
-		gs.k[q].slot = slot;
+		gs.k[q].src = c.dev;
+		gs.k[q].slot = c.slot;
 		gs.k[q].n_values = keys[q].n_values;
 		gs.k[q].min_value = keys[q].min_value;
 	}
@@ -396,35 +388,15 @@ extern "C" int polr_out_aggregate_grouped(polr_out *o, void *stream, const polr_
 	}
 	gs.n_groups = (uint32_t)groups;
 	DevAggSet as;
-	memset(&as, 0, sizeof(as));
-	as.n = n_aggs;
-	for (uint32_t a = 0; a < n_aggs; a++) {
-		if (specs[a].fn > POLR_AGG_MAX) {
-			POLR_FAIL(ctx, POLR_E_INVALID, "aggregate %u: unknown function %u", a, specs[a].fn);
-		}
-		as.a[a].fn = specs[a].fn;
-		if (specs[a].fn == POLR_AGG_COUNT_STAR) {
-			continue;
-		}
-		const OwnedCol *c = nullptr;
-		uint32_t slot = 0;
-		int rc = resolve_agg_col(p, specs[a].src_join, specs[a].src_col, &c, &slot, "aggregate", a);
-		if (rc) {
-			return rc;
-		}
-		as.a[a].src.data = c->data;
-		as.a[a].src.valid = c->valid;
-		as.a[a].src.width = c->width;
-		as.a[a].src.flags = c->flags;
-		as.a[a].slot = slot;
+	int rc = build_agg_set(p, specs, n_aggs, &as);
+	if (rc) {
+		return rc;
 	}
 	HIPCHK(ctx, hipSetDevice(ctx->device));
 	hipStream_t st = polr_stream(ctx, stream);
-	if (!o->stats_valid) {
-		int rc = polr_out_stats(o, stream, nullptr, nullptr, nullptr);
-		if (rc) {
-			return rc;
-		}
+	rc = out_ensure_stats(o, stream);
+	if (rc) {
+		return rc;
 	}
 	const uint32_t n_cells = (uint32_t)groups * n_aggs;
 	std::vector<GroupCell> host(n_cells);
@@ -435,7 +407,7 @@ extern "C" int polr_out_aggregate_grouped(polr_out *o, void *stream, const polr_
 	e = e == hipSuccess ? hipMalloc((void **)&dropped, 8) : e;
 	e = e == hipSuccess ? hipMemsetAsync(dropped, 0, 8, st) : e;
 	if (e == hipSuccess) {
-		hipLaunchKernelGGL(polr_group_init_kernel, dim3((n_cells + 255) / 256), dim3(256), 0, st, table, n_cells);
+		hipLaunchKernelGGL(polr_group_init_kernel, dim3((n_cells + 255) / 256), dim3(256), 0, st, table, (uint64_t)n_cells);
 		if (o->n_chunks) {
 			const int use_lds = n_cells <= POLR_GROUP_LDS_CELLS;
 			const uint32_t n_blocks = std::max<uint32_t>(1, std::min<uint32_t>(o->n_chunks, (uint32_t)ctx->n_cus * 4));
@@ -457,33 +429,7 @@ extern "C" int polr_out_aggregate_grouped(polr_out *o, void *stream, const polr_
 		POLR_FAIL(ctx, POLR_E_HIP, "grouped aggregate failed: %s", hipGetErrorString(e));
 	}
 	for (uint32_t i = 0; i < n_cells; i++) {
-		const GroupCell &c = host[i];
-		polr_agg_value &v = results[i];
-		memset(&v, 0, sizeof(v));
-		v.count = c.count;
-		const uint32_t fn = specs[i % n_aggs].fn;
-		const __int128 sum = ((__int128)c.hi32 << 32) + (__int128)c.lo32;
-		switch (fn) {
-		case POLR_AGG_COUNT_STAR:
-		case POLR_AGG_COUNT:
-			v.lo = (int64_t)c.count;
-			break;
-		case POLR_AGG_SUM:
-			v.is_null = c.count == 0;
-			v.lo = (int64_t)(unsigned long long)sum;
-			v.hi = (int64_t)(sum >> 64);
-			break;
-		case POLR_AGG_MIN:
-			v.is_null = c.count == 0;
-			v.lo = c.count ? c.mn : 0;
-			v.hi = (c.count && c.mn < 0) ? -1 : 0;
-			break;
-		default:
-			v.is_null = c.count == 0;
-			v.lo = c.count ? c.mx : 0;
-			v.hi = (c.count && c.mx < 0) ? -1 : 0;
-			break;
-		}
+		results[i] = cell_value(host[i], specs[i % n_aggs].fn);
 	}
 	if (n_dropped) {
 		*n_dropped = h_dropped;
@@ -491,299 +437,6 @@ extern "C" int polr_out_aggregate_grouped(polr_out *o, void *stream, const polr_
 	return POLR_OK;
 }
 
-
-// ---- the general GROUP BY sink: group columns of any integer domain (PhysicalHashAggregate,
-// src/execution/operator/aggregate/physical_hash_aggregate.cpp -- the plan when the group columns' statistics do not allow
-// a perfect-hash aggregate) -----------------------------------------------------------------------------------------------
-// An open-addressing table of groups in global memory: state[s] = 0 empty / 1 being written / 2 ready, the group's key
-// values (NULL is a group value of its own, as GROUP BY has it: a bit per column) and its cells.  A row claims an empty
-// slot with a compare-and-swap and publishes its key; every other row of the group finds the key and adds to the cells.
-// A lane that meets a slot "being written" does not wait inside the iteration -- the writer may be a lane of its own wave,
-// which runs in lockstep -- it comes back to the slot in the next iteration of the loop all lanes share.
-struct HashAggTable {
-	uint32_t *state;
-	long long *keys;          // [capacity][n_cols]
-	uint32_t *nulls;          // [capacity]: bit c = group column c is NULL
-	GroupCell *cells;         // [capacity][n_aggs]
-	unsigned long long *n_groups, *overflow;
-	uint64_t mask;            // capacity - 1
-	uint64_t max_groups;
-};
-
-__global__ __launch_bounds__(256) void polr_hash_agg_init_kernel(HashAggTable t, uint32_t n_aggs) {
-	const uint64_t n = (t.mask + 1) * n_aggs;
-	for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (uint64_t)gridDim.x * blockDim.x) {
-		t.cells[i].lo32 = 0;
-		t.cells[i].hi32 = 0;
-		t.cells[i].mn = 0x7FFFFFFFFFFFFFFFll;
-		t.cells[i].mx = (long long)0x8000000000000000ull;
-		t.cells[i].count = 0;
-	}
-}
-
-__global__ __launch_bounds__(256) void polr_hash_agg_kernel(DevOut out, uint32_t n_chunks, DevGroupSet groups, DevAggSet aggs,
-                                                            HashAggTable t) {
-	for (uint32_t chunk = blockIdx.x; chunk < n_chunks; chunk += gridDim.x) {
-		const uint32_t n = out.chunk_count[chunk];
-		const uint64_t chunk_base = (uint64_t)chunk * out.chunk_capacity;
-		for (uint32_t i0 = 0; i0 < n; i0 += blockDim.x) {
-			const uint32_t i = i0 + threadIdx.x;
-			const bool active = i < n;
-			long long key[POLR_MAX_GROUP_KEYS] = {0, 0, 0};
-			uint32_t null_mask = 0;
-			uint64_t h = 0x9E3779B97F4A7C15ull;
-			if (active) {
-				for (uint32_t q = 0; q < groups.n; q++) {
-					const DevGroupKey &gk = groups.k[q];
-					const uint32_t row = out.ids[(uint64_t)gk.slot * out.slot_stride + chunk_base + i];
-					if (gk.src.valid && !gk.src.valid[row]) {
-						null_mask |= 1u << q;
-					} else {
-						key[q] = load_col_cell(gk.src, row);
-					}
-					h = polr_murmurhash64(h ^ (uint64_t)key[q]) + q;
-				}
-				h = polr_murmurhash64(h ^ null_mask);
-			}
-			uint64_t s = h & t.mask;
-			bool done = !active;
-			uint64_t probes = 0;
-			while (__syncthreads_or(!done)) { // (every lane of the workgroup takes part in every iteration)
-				if (!done) {
-					uint32_t st = __hip_atomic_load(&t.state[s], __ATOMIC_ACQUIRE, __HIP_MEMORY_SCOPE_AGENT);
-					if (st == 0u) {
-						if (atomicCAS(&t.state[s], 0u, 1u) == 0u) {
-							if (atomicAdd(t.n_groups, 1ull) >= t.max_groups) {
-								atomicExch(t.overflow, 1ull); // (more groups than the caller made room for)
-							}
-							for (uint32_t q = 0; q < groups.n; q++) {
-								t.keys[s * groups.n + q] = key[q];
-							}
-							t.nulls[s] = null_mask;
-							__hip_atomic_store(&t.state[s], 2u, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_AGENT);
-							st = 2u;
-						}
-					}
-					if (st == 2u) {
-						bool same = t.nulls[s] == null_mask;
-						for (uint32_t q = 0; q < groups.n; q++) {
-							same = same && t.keys[s * groups.n + q] == key[q];
-						}
-						if (same) {
-							done = true;
-						} else {
-							s = (s + 1) & t.mask;
-							if (++probes > t.mask) { // (a full table: cannot happen with capacity >= 2 x max_groups before overflow)
-								atomicExch(t.overflow, 1ull);
-								done = true;
-								s = ~0ull;
-							}
-						}
-					}
-					// (st == 1: somebody is writing this slot's key: look again in the next iteration)
-				}
-			}
-			if (active && s != ~0ull) {
-				for (uint32_t a = 0; a < aggs.n; a++) {
-					const DevAgg &ag = aggs.a[a];
-					GroupCell *c = &t.cells[s * aggs.n + a];
-					if (ag.fn == POLR_AGG_COUNT_STAR) {
-						atomicAdd(&c->count, 1ull);
-						continue;
-					}
-					const uint32_t row = out.ids[(uint64_t)ag.slot * out.slot_stride + chunk_base + i];
-					if (ag.src.valid && !ag.src.valid[row]) {
-						continue;
-					}
-					cell_add(c, load_col_cell(ag.src, row));
-				}
-			}
-		}
-	}
-}
-
-// the groups that exist, compacted: [idx] <- slot
-// (reps / reps_out: the representative string cells of the VARCHAR sink further down, or nullptr)
-__global__ __launch_bounds__(256) void polr_hash_agg_compact_kernel(HashAggTable t, uint32_t n_cols, uint32_t n_aggs, long long *keys_out,
-                                                                    uint32_t *nulls_out, GroupCell *cells_out, unsigned long long *cursor,
-                                                                    uint64_t max_groups, const uint4 *reps, uint4 *reps_out) {
-	for (uint64_t s = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; s <= t.mask; s += (uint64_t)gridDim.x * blockDim.x) {
-		if (t.state[s] != 2u) {
-			continue;
-		}
-		const unsigned long long idx = atomicAdd(cursor, 1ull);
-		if (idx >= max_groups) {
-			continue;
-		}
-		for (uint32_t q = 0; q < n_cols; q++) {
-			keys_out[idx * n_cols + q] = t.keys[s * n_cols + q];
-			if (reps) {
-				reps_out[idx * n_cols + q] = reps[s * n_cols + q];
-			}
-		}
-		nulls_out[idx] = t.nulls[s];
-		for (uint32_t a = 0; a < n_aggs; a++) {
-			cells_out[idx * n_aggs + a] = t.cells[s * n_aggs + a];
-		}
-	}
-}
-
-static void cell_to_value(const GroupCell &c, uint32_t fn, polr_agg_value &v) {
-	memset(&v, 0, sizeof(v));
-	v.count = c.count;
-	const __int128 sum = ((__int128)c.hi32 << 32) + (__int128)c.lo32;
-	switch (fn) {
-	case POLR_AGG_COUNT_STAR:
-	case POLR_AGG_COUNT:
-		v.lo = (int64_t)c.count;
-		break;
-	case POLR_AGG_SUM:
-		v.is_null = c.count == 0;
-		v.lo = (int64_t)(unsigned long long)sum;
-		v.hi = (int64_t)(sum >> 64);
-		break;
-	case POLR_AGG_MIN:
-		v.is_null = c.count == 0;
-		v.lo = c.count ? c.mn : 0;
-		v.hi = (c.count && c.mn < 0) ? -1 : 0;
-		break;
-	default:
-		v.is_null = c.count == 0;
-		v.lo = c.count ? c.mx : 0;
-		v.hi = (c.count && c.mx < 0) ? -1 : 0;
-		break;
-	}
-}
-
-extern "C" int polr_out_aggregate_hashed(polr_out *o, void *stream, const polr_group_key *cols, uint32_t n_cols,
-                                         const polr_agg_spec *specs, uint32_t n_aggs, uint64_t max_groups, int64_t *group_keys,
-                                         uint32_t *group_nulls, polr_agg_value *results, uint64_t *n_groups) {
-	if (!o || !cols || !specs || !group_keys || !group_nulls || !results || !n_groups || n_cols == 0 || n_aggs == 0 ||
-	    max_groups == 0) {
-		return POLR_E_INVALID;
-	}
-	polr_pipeline *p = o->pipe;
-	polr_ctx *ctx = p->ctx;
-	if (n_cols > POLR_MAX_GROUP_KEYS || n_aggs > POLR_MAX_AGGS || max_groups > (1ull << 24)) {
-		POLR_FAIL(ctx, POLR_E_UNSUPPORTED, "at most %d group columns, %d aggregates and 2^24 groups", POLR_MAX_GROUP_KEYS,
-		          POLR_MAX_AGGS);
-	}
-	DevGroupSet gs;
-	memset(&gs, 0, sizeof(gs));
-	gs.n = n_cols;
-	for (uint32_t q = 0; q < n_cols; q++) {
-		const OwnedCol *c = nullptr;
-		uint32_t slot = 0;
-		int rc = resolve_agg_col(p, cols[q].src_join, cols[q].src_col, &c, &slot, "group column", q);
-		if (rc) {
-			return rc;
-		}
-		gs.k[q].src.data = c->data;
-		gs.k[q].src.valid = c->valid;
-		gs.k[q].src.width = c->width;
-		gs.k[q].src.flags = c->flags;
-		gs.k[q].slot = slot;
-	}
-	DevAggSet as;
-	memset(&as, 0, sizeof(as));
-	as.n = n_aggs;
-	for (uint32_t a = 0; a < n_aggs; a++) {
-		if (specs[a].fn > POLR_AGG_MAX) {
-			POLR_FAIL(ctx, POLR_E_INVALID, "aggregate %u: unknown function %u", a, specs[a].fn);
-		}
-		as.a[a].fn = specs[a].fn;
-		if (specs[a].fn == POLR_AGG_COUNT_STAR) {
-			continue;
-		}
-		const OwnedCol *c = nullptr;
-		uint32_t slot = 0;
-		int rc = resolve_agg_col(p, specs[a].src_join, specs[a].src_col, &c, &slot, "aggregate", a);
-		if (rc) {
-			return rc;
-		}
-		as.a[a].src.data = c->data;
-		as.a[a].src.valid = c->valid;
-		as.a[a].src.width = c->width;
-		as.a[a].src.flags = c->flags;
-		as.a[a].slot = slot;
-	}
-	HIPCHK(ctx, hipSetDevice(ctx->device));
-	hipStream_t st = polr_stream(ctx, stream);
-	if (!o->stats_valid) {
-		int rc = polr_out_stats(o, stream, nullptr, nullptr, nullptr);
-		if (rc) {
-			return rc;
-		}
-	}
-	uint64_t capacity = 1024;
-	while (capacity < 2 * max_groups) {
-		capacity <<= 1;
-	}
-	HashAggTable t;
-	memset(&t, 0, sizeof(t));
-	t.mask = capacity - 1;
-	t.max_groups = max_groups;
-	// one allocation: state, nulls, counters, keys, cells, and the compacted outputs behind them
-	const size_t b_state = capacity * 4, b_nulls = capacity * 4, b_cnt = 64, b_keys = capacity * n_cols * 8,
-	             b_cells = capacity * n_aggs * sizeof(GroupCell), b_okeys = max_groups * n_cols * 8, b_onulls = max_groups * 4,
-	             b_ocells = max_groups * n_aggs * sizeof(GroupCell);
-	uint8_t *base = nullptr;
-	HIPCHK(ctx, hipMalloc((void **)&base, b_state + b_nulls + b_cnt + b_keys + b_cells + b_okeys + b_onulls + b_ocells));
-	uint8_t *at = base;
-	t.state = (uint32_t *)at;
-	at += b_state;
-	t.nulls = (uint32_t *)at;
-	at += b_nulls;
-	unsigned long long *cnt = (unsigned long long *)at; // [0] groups, [1] overflow, [2] compaction cursor
-	at += b_cnt;
-	t.n_groups = cnt;
-	t.overflow = cnt + 1;
-	t.keys = (long long *)at;
-	at += b_keys;
-	t.cells = (GroupCell *)at;
-	at += b_cells;
-	long long *okeys = (long long *)at;
-	at += b_okeys;
-	uint32_t *onulls = (uint32_t *)at;
-	at += b_onulls;
-	GroupCell *ocells = (GroupCell *)at;
-	hipError_t e = hipMemsetAsync(base, 0, b_state + b_nulls + b_cnt, st);
-	unsigned long long h_cnt[3] = {0, 0, 0};
-	if (e == hipSuccess) {
-		hipLaunchKernelGGL(polr_hash_agg_init_kernel, dim3(256), dim3(256), 0, st, t, n_aggs);
-		if (o->n_chunks) {
-			hipLaunchKernelGGL(polr_hash_agg_kernel, dim3(std::min<uint32_t>(o->n_chunks, 2048u)), dim3(256), 0, st, o->dev, o->n_chunks,
-			                   gs, as, t);
-		}
-		hipLaunchKernelGGL(polr_hash_agg_compact_kernel, dim3(256), dim3(256), 0, st, t, n_cols, n_aggs, okeys, onulls, ocells, cnt + 2,
-		                   max_groups, (const uint4 *)nullptr, (uint4 *)nullptr);
-		e = hipMemcpyAsync(h_cnt, cnt, sizeof(h_cnt), hipMemcpyDeviceToHost, st);
-		e = e == hipSuccess ? hipStreamSynchronize(st) : e;
-	}
-	std::vector<GroupCell> hcells;
-	if (e == hipSuccess && !h_cnt[1] && h_cnt[0] <= max_groups && h_cnt[0]) {
-		const uint64_t g = h_cnt[0];
-		hcells.resize(g * n_aggs);
-		e = hipMemcpy(group_keys, okeys, g * n_cols * 8, hipMemcpyDeviceToHost);
-		e = e == hipSuccess ? hipMemcpy(group_nulls, onulls, g * 4, hipMemcpyDeviceToHost) : e;
-		e = e == hipSuccess ? hipMemcpy(hcells.data(), ocells, g * n_aggs * sizeof(GroupCell), hipMemcpyDeviceToHost) : e;
-	}
-	hipFree(base);
-	if (e != hipSuccess) {
-		POLR_FAIL(ctx, POLR_E_HIP, "hash aggregate failed: %s", hipGetErrorString(e));
-	}
-	*n_groups = h_cnt[0];
-	if (h_cnt[1] || h_cnt[0] > max_groups) {
-		POLR_FAIL(ctx, POLR_E_OVERFLOW, "the result has %llu groups or more, the caller made room for %llu",
-		          (unsigned long long)h_cnt[0], (unsigned long long)max_groups);
-	}
-	for (uint64_t g = 0; g < h_cnt[0]; g++) {
-		for (uint32_t a = 0; a < n_aggs; a++) {
-			cell_to_value(hcells[g * n_aggs + a], specs[a].fn, results[g * n_aggs + a]);
-		}
-	}
-	return POLR_OK;
-}
 
 // ---- the GROUP BY sink fused into an emitting flat pipeline (FusedSink, polr_device.h; polr_flat_device.h) -------------
 static_assert(POLR_AGG_COUNT_STAR == POLR_DEV_AGG_COUNT_STAR && POLR_AGG_COUNT == POLR_DEV_AGG_COUNT &&
@@ -810,6 +463,7 @@ __global__ __launch_bounds__(256) void polr_fused_reduce_kernel(const unsigned l
 
 extern "C" int polr_out_fuse_grouped(polr_out *o, const polr_group_key *keys, uint32_t n_keys, const polr_agg_spec *specs,
                                      uint32_t n_aggs) {
+	POLR_ENTRY();
 	if (!o) {
 		return POLR_E_INVALID;
 	}
@@ -844,9 +498,8 @@ extern "C" int polr_out_fuse_grouped(polr_out *o, const polr_group_key *keys, ui
 	fs.groups.n = n_keys;
 	uint64_t groups = 1;
 	for (uint32_t q = 0; q < n_keys; q++) {
-		const OwnedCol *c = nullptr;
-		uint32_t slot = 0;
-		int rc = resolve_agg_col(p, keys[q].src_join, keys[q].src_col, &c, &slot, "group column", q);
+		OutCol c;
+		int rc = polr_out_int_col(p, keys[q].src_join, keys[q].src_col, &c, "group column", q);
 		if (rc) {
 			return rc;
 		}
@@ -854,42 +507,28 @@ extern "C" int polr_out_fuse_grouped(polr_out *o, const polr_group_key *keys, ui
 		if (keys[q].n_values == 0 || groups > 4096) {
 			POLR_FAIL(ctx, POLR_E_UNSUPPORTED, "group column %u: a fused sink holds at most 4096 groups", q);
 		}
-		fs.groups.k[q].src.data = c->data;
-		fs.groups.k[q].src.valid = c->valid;
-		fs.groups.k[q].src.width = c->width;
-		fs.groups.k[q].src.flags = c->flags;
-		fs.groups.k[q].slot = slot;
+		fs.groups.k[q].src = c.dev;
+		fs.groups.k[q].slot = c.slot;
 		fs.groups.k[q].n_values = keys[q].n_values;
 		fs.groups.k[q].min_value = keys[q].min_value;
 	}
 	fs.groups.n_groups = (uint32_t)groups;
 	fs.aggs.n = n_aggs;
-	for (uint32_t a = 0; a < n_aggs; a++) {
+	for (uint32_t a = 0; a < n_aggs; a++) { // (per aggregate, in this order: the first refusal decides the return code)
 		if (specs[a].fn > POLR_AGG_SUM) {
 			POLR_FAIL(ctx, POLR_E_UNSUPPORTED, "aggregate %u: a fused sink computes COUNT(*), COUNT and SUM", a);
 		}
-		fs.aggs.a[a].fn = specs[a].fn;
-		o->fused_fn[a] = specs[a].fn;
-		o->fused_has_valid[a] = false;
-		if (specs[a].fn == POLR_AGG_COUNT_STAR) {
-			continue;
-		}
-		const OwnedCol *c = nullptr;
-		uint32_t slot = 0;
-		int rc = resolve_agg_col(p, specs[a].src_join, specs[a].src_col, &c, &slot, "aggregate", a);
+		const DevAgg &ag = fs.aggs.a[a];
+		int rc = build_agg(p, specs[a], a, &fs.aggs.a[a]);
 		if (rc) {
 			return rc;
 		}
-		if (specs[a].fn == POLR_AGG_SUM && c->width > 4) {
+		if (ag.fn == POLR_AGG_SUM && ag.src.width > 4) {
 			// (the cells hold plain 64-bit sums: exact for 2^32 rows of values below 2^31)
 			POLR_FAIL(ctx, POLR_E_UNSUPPORTED, "aggregate %u: a fused SUM takes columns of at most 4 bytes", a);
 		}
-		fs.aggs.a[a].src.data = c->data;
-		fs.aggs.a[a].src.valid = c->valid;
-		fs.aggs.a[a].src.width = c->width;
-		fs.aggs.a[a].src.flags = c->flags;
-		fs.aggs.a[a].slot = slot;
-		o->fused_has_valid[a] = c->valid != nullptr;
+		o->fused_fn[a] = ag.fn;
+		o->fused_has_valid[a] = ag.src.valid != nullptr;
 	}
 	const uint32_t words = (uint32_t)groups * (1u + 2u * n_aggs);
 	fs.n_tables = POLR_FUSED_TABLES;
@@ -920,6 +559,7 @@ extern "C" int polr_out_fuse_grouped(polr_out *o, const polr_group_key *keys, ui
 }
 
 extern "C" int polr_out_fused_result(polr_out *o, void *stream, polr_agg_value *results, uint64_t n_groups, uint64_t *n_dropped) {
+	POLR_ENTRY();
 	if (!o || !results) {
 		return POLR_E_INVALID;
 	}
@@ -948,17 +588,8 @@ extern "C" int polr_out_fused_result(polr_out *o, void *stream, polr_agg_value *
 	for (uint32_t g = 0; g < o->fused_groups; g++) {
 		const unsigned long long *c = &host[(size_t)g * (1u + 2u * n_aggs)];
 		for (uint32_t a = 0; a < n_aggs; a++) {
-			polr_agg_value &v = results[(size_t)g * n_aggs + a];
-			memset(&v, 0, sizeof(v));
 			const uint64_t count = o->fused_fn[a] == POLR_AGG_COUNT_STAR || !o->fused_has_valid[a] ? c[0] : c[2u + 2u * a];
-			v.count = count;
-			if (o->fused_fn[a] == POLR_AGG_SUM) {
-				v.is_null = count == 0;
-				v.lo = (int64_t)c[1u + 2u * a];
-				v.hi = v.lo < 0 ? -1 : 0;
-			} else {
-				v.lo = (int64_t)count;
-			}
+			results[(size_t)g * n_aggs + a] = agg_value(o->fused_fn[a], (int64_t)c[1u + 2u * a], 0, 0, count);
 		}
 	}
 	if (n_dropped) {
@@ -1126,8 +757,55 @@ __global__ __launch_bounds__(256) void polr_agg_string_kernel(DevOut out, uint32
 	}
 }
 
-// (defined with the VARCHAR GROUP BY sink below) POLR_OK when a kernel may follow the string pointers of the column
-static int check_string_col_on_device(polr_out *o, hipStream_t st, const OwnedCol *c, uint32_t slot, const char *what, uint32_t idx);
+// the guard of a VARCHAR column whose cells were never rebased onto a device heap: the non-NULL cells among the output rows
+// that are longer than 12 bytes -- their pointers are the host's.  Reads the length word of a cell and nothing else.
+__global__ __launch_bounds__(256) void polr_count_long_cells_kernel(DevOut out, uint32_t n_chunks, DevCol src, uint32_t slot,
+                                                                    unsigned long long *__restrict__ n_long) {
+	unsigned long long mine = 0;
+	for (uint32_t chunk = blockIdx.x; chunk < n_chunks; chunk += gridDim.x) {
+		const uint32_t n = out.chunk_count[chunk];
+		const uint32_t *ids = out.ids + (uint64_t)slot * out.slot_stride + (uint64_t)chunk * out.chunk_capacity;
+		for (uint32_t i = threadIdx.x; i < n; i += blockDim.x) {
+			const uint32_t row = ids[i];
+			if (src.valid && !src.valid[row]) {
+				continue;
+			}
+			mine += *(const uint32_t *)(src.data + (uint64_t)row * 16u) > 12u ? 1u : 0u;
+		}
+	}
+	mine = wave_sum64(mine);
+	if ((threadIdx.x & 63u) == 0 && mine) {
+		atomicAdd(n_long, mine);
+	}
+}
+
+// POLR_OK when the column may be read by a kernel that follows string pointers
+static int check_string_col_on_device(polr_out *o, hipStream_t st, const OutCol &c, const char *what, uint32_t idx) {
+	polr_ctx *ctx = o->pipe->ctx;
+	if (c.col->strings_rebased || !c.col->owned || o->n_chunks == 0) {
+		return POLR_OK; // (rebased here; or the caller's own device memory, whose cells point into HBM by contract)
+	}
+	unsigned long long *n_long = nullptr, h_long = 0;
+	HIPCHK(ctx, hipMalloc((void **)&n_long, 8));
+	hipError_t e = hipMemsetAsync(n_long, 0, 8, st);
+	if (e == hipSuccess) {
+		const uint32_t n_blocks = std::max<uint32_t>(1, std::min<uint32_t>(o->n_chunks, (uint32_t)ctx->n_cus * 4));
+		hipLaunchKernelGGL(polr_count_long_cells_kernel, dim3(n_blocks), dim3(256), 0, st, o->dev, o->n_chunks, c.dev, c.slot, n_long);
+		e = hipMemcpyAsync(&h_long, n_long, 8, hipMemcpyDeviceToHost, st);
+		e = e == hipSuccess ? hipStreamSynchronize(st) : e;
+	}
+	hipFree(n_long);
+	if (e != hipSuccess) {
+		POLR_FAIL(ctx, POLR_E_HIP, "string column check failed: %s", hipGetErrorString(e));
+	}
+	if (h_long) {
+		POLR_FAIL(ctx, POLR_E_INVALID,
+		          "%s %u: %llu output rows hold strings longer than 12 bytes, but the column's heap was never put on the device "
+		          "(polr_ht_set_payload_heaps / polr_pipeline_set_probe_heaps)",
+		          what, idx, h_long);
+	}
+	return POLR_OK;
+}
 
 // all or nothing: the ranges are checked, copied and every cell validated before any cell is rewritten; on an error the
 // column is as it was and no device memory is kept
@@ -1259,55 +937,36 @@ int polr_out_aggregate_string(polr_out *o, void *stream, uint32_t fn, int32_t sr
 	if (fn != POLR_AGG_MIN && fn != POLR_AGG_MAX) {
 		POLR_FAIL(ctx, POLR_E_UNSUPPORTED, "string aggregate %u (MIN or MAX)", fn);
 	}
-	const OwnedCol *c;
-	uint32_t slot;
-	if (src_join < 0) {
-		if (src_col >= p->n_probe_cols) {
-			POLR_FAIL(ctx, POLR_E_INVALID, "probe column %u out of range", src_col);
-		}
-		c = &p->probe_cols[src_col];
-		slot = 0;
-	} else {
-		if ((uint32_t)src_join >= p->k || src_col >= p->hts[src_join]->n_payload) {
-			POLR_FAIL(ctx, POLR_E_INVALID, "build column (%d,%u) out of range", src_join, src_col);
-		}
-		const polr_ht *ht = p->hts[src_join];
-		c = ht->kind == KIND_PERFECT ? &ht->pcols[src_col] : &ht->payload[src_col];
-		slot = 1 + (uint32_t)src_join;
+	OutCol c;
+	int rc = polr_out_col(p, src_join, src_col, &c, "string aggregate, column", src_col);
+	if (rc) {
+		return rc;
 	}
-	if (c->width != 16) {
-		POLR_FAIL(ctx, POLR_E_INVALID, "not a VARCHAR column (%u-byte cells)", c->width);
+	if (c.dev.width != 16) {
+		POLR_FAIL(ctx, POLR_E_INVALID, "not a VARCHAR column (%u-byte cells)", c.dev.width);
 	}
 	HIPCHK(ctx, hipSetDevice(ctx->device));
 	hipStream_t st = polr_stream(ctx, stream);
-	if (!o->stats_valid) {
-		int rc = polr_out_stats(o, stream, nullptr, nullptr, nullptr);
-		if (rc) {
-			return rc;
-		}
+	rc = out_ensure_stats(o, stream);
+	if (rc) {
+		return rc;
 	}
 	*len = 0;
 	*is_null = 1;
 	if (o->n_chunks == 0) {
 		return POLR_OK;
 	}
-	{ // a column whose heap never came may hold inline strings only: refused before a pointer is followed
-		int rc = check_string_col_on_device(o, st, c, slot, "string aggregate, column", src_col);
-		if (rc) {
-			return rc;
-		}
+	// a column whose heap never came may hold inline strings only: refused before a pointer is followed
+	rc = check_string_col_on_device(o, st, c, "string aggregate, column", src_col);
+	if (rc) {
+		return rc;
 	}
 	const uint32_t n_blocks = std::max<uint32_t>(1, std::min<uint32_t>(o->n_chunks, (uint32_t)ctx->n_cus * 4));
 	StrPartial *part = nullptr;
 	HIPCHK(ctx, hipMalloc((void **)&part, ((size_t)n_blocks + 1) * sizeof(StrPartial)));
-	DevCol src;
-	src.data = c->data;
-	src.valid = c->valid;
-	src.width = c->width;
-	src.flags = c->flags;
-	hipLaunchKernelGGL(polr_agg_string_kernel, dim3(n_blocks), dim3(256), 0, st, o->dev, o->n_chunks, src, slot,
+	hipLaunchKernelGGL(polr_agg_string_kernel, dim3(n_blocks), dim3(256), 0, st, o->dev, o->n_chunks, c.dev, c.slot,
 	                   fn == POLR_AGG_MAX ? 1 : 0, (const StrPartial *)nullptr, 0u, part);
-	hipLaunchKernelGGL(polr_agg_string_kernel, dim3(1), dim3(256), 0, st, o->dev, 0u, src, slot, fn == POLR_AGG_MAX ? 1 : 0,
+	hipLaunchKernelGGL(polr_agg_string_kernel, dim3(1), dim3(256), 0, st, o->dev, 0u, c.dev, c.slot, fn == POLR_AGG_MAX ? 1 : 0,
 	                   (const StrPartial *)part, n_blocks, part + n_blocks);
 	StrPartial win;
 	hipError_t e = hipMemcpyAsync(&win, part + n_blocks, sizeof(win), hipMemcpyDeviceToHost, st);
@@ -1332,25 +991,42 @@ int polr_out_aggregate_string(polr_out *o, void *stream, uint32_t fn, int32_t sr
 
 } // extern "C"
 
-// ---- the general GROUP BY sink with VARCHAR group columns (SSB: GROUP BY d_year, c_nation / c_city, s_city, d_year / p_brand) ----
-// The table of polr_hash_agg_kernel with, per VARCHAR column, the 64-bit hash of the string's value in the slot's key word and
-// a representative string_t cell beside it (reps[slot][column]; its pointer stays good: it points into the device heap the
-// table / pipeline owns).  A probing row compares the key words -- integer values and string hashes -- and only for a slot
-// that agrees in all of them the strings themselves (polr_str_equal: length, then prefix / inline characters from the two
-// cells, then the heap bytes), so a slot of another group almost never costs a heap read.
+
+// ---- the general GROUP BY sink: group columns of any integer domain or VARCHAR (PhysicalHashAggregate,
+// src/execution/operator/aggregate/physical_hash_aggregate.cpp -- the plan when the group columns' statistics do not allow
+// a perfect-hash aggregate; SSB: GROUP BY d_year, c_nation / c_city, s_city, d_year / p_brand) ------------------------------
+// An open-addressing table of groups in global memory: state[s] = 0 empty / 1 being written / 2 ready, the group's key
+// words (NULL is a group value of its own, as GROUP BY has it: a bit per column) and its cells.  A row claims an empty
+// slot with a compare-and-swap and publishes its key; every other row of the group finds the key and adds to the cells.
+// A lane that meets a slot "being written" does not wait inside the iteration -- the writer may be a lane of its own wave,
+// which runs in lockstep -- it comes back to the slot in the next iteration of the loop all lanes share.
 //
-// COMBINE: few hot groups is the common shape (Q4.1: 35 groups for every surviving row).  Once every lane knows its slot,
-// the lanes of a wave that resolved to the SAME slot are folded into their lowest lane -- the leader walks its peers with
+// STR (some group column is VARCHAR): such a column's key word is the 64-bit hash of the string's value, and a
+// representative string_t cell sits beside it (reps[slot][column]; its pointer stays good: it points into the device heap
+// the table / pipeline owns).  A probing row compares the key words -- integer values and string hashes -- and only for a
+// slot that agrees in all of them the strings themselves (polr_str_equal: length, then prefix / inline characters from the
+// two cells, then the heap bytes), so a slot of another group almost never costs a heap read.
+//
+// Few hot groups is the common shape (Q4.1: 35 groups for every surviving row).  Once every lane knows its slot, the lanes
+// of a wave that resolved to the SAME slot are folded into their lowest lane -- the leader walks its peers with
 // v_readlane, the work is bounded by 64 peers per wave and aggregate whatever the distribution -- and only leaders and
-// lanes alone on their slot issue atomics: one per distinct slot, aggregate and wave.  !COMBINE: every lane for itself.
-#ifndef POLR_HASH_AGG_WAVE_COMBINE
-#define POLR_HASH_AGG_WAVE_COMBINE 1
-#endif
+// lanes alone on their slot issue atomics: one per distinct slot, aggregate and wave, and only on the words cell_value
+// reads for the aggregate's function.
+struct HashAggTable {
+	uint32_t *state;
+	long long *keys;          // [capacity][n_cols]
+	uint32_t *nulls;          // [capacity]: bit c = group column c is NULL
+	GroupCell *cells;         // [capacity][n_aggs]
+	unsigned long long *n_groups, *overflow;
+	uint64_t mask;            // capacity - 1
+	uint64_t max_groups;
+};
+
 #define POLR_NO_SLOT 0xFFFFFFFFu
 
-template <bool COMBINE>
-__global__ __launch_bounds__(256) void polr_hash_agg_str_kernel(DevOut out, uint32_t n_chunks, DevGroupSet groups, DevAggSet aggs,
-                                                                HashAggTable t, uint4 *reps, uint32_t str_mask) {
+template <bool STR>
+__global__ __launch_bounds__(256) void polr_hash_agg_kernel(DevOut out, uint32_t n_chunks, DevGroupSet groups, DevAggSet aggs,
+                                                            HashAggTable t, uint4 *reps, uint32_t str_mask) {
 	const uint32_t lane = threadIdx.x & 63u;
 	for (uint32_t chunk = blockIdx.x; chunk < n_chunks; chunk += gridDim.x) {
 		const uint32_t n = out.chunk_count[chunk];
@@ -1359,7 +1035,7 @@ __global__ __launch_bounds__(256) void polr_hash_agg_str_kernel(DevOut out, uint
 			const uint32_t i = i0 + threadIdx.x;
 			const bool active = i < n;
 			long long key[POLR_MAX_GROUP_KEYS] = {0, 0, 0};
-			uint4 cell[POLR_MAX_GROUP_KEYS];
+			uint4 cell[POLR_MAX_GROUP_KEYS]; // (STR only)
 			uint32_t null_mask = 0;
 			uint64_t h = 0x9E3779B97F4A7C15ull;
 #pragma unroll
@@ -1370,7 +1046,7 @@ __global__ __launch_bounds__(256) void polr_hash_agg_str_kernel(DevOut out, uint
 					const uint32_t row = out.ids[(uint64_t)gk.slot * out.slot_stride + chunk_base + i];
 					if (gk.src.valid && !gk.src.valid[row]) {
 						null_mask |= 1u << q; // (the cell of a NULL row is never read)
-					} else if ((str_mask >> q) & 1u) {
+					} else if (STR && ((str_mask >> q) & 1u)) {
 						cell[q] = ((const uint4 *)gk.src.data)[row];
 						key[q] = (long long)polr_str_hash(cell[q]);
 					} else {
@@ -1395,7 +1071,9 @@ __global__ __launch_bounds__(256) void polr_hash_agg_str_kernel(DevOut out, uint
 							for (uint32_t q = 0; q < POLR_MAX_GROUP_KEYS; q++) {
 								if (q < groups.n) {
 									t.keys[s * groups.n + q] = key[q];
-									reps[s * groups.n + q] = cell[q];
+									if (STR) {
+										reps[s * groups.n + q] = cell[q];
+									}
 								}
 							}
 							t.nulls[s] = null_mask;
@@ -1411,7 +1089,7 @@ __global__ __launch_bounds__(256) void polr_hash_agg_str_kernel(DevOut out, uint
 								same = same && t.keys[s * groups.n + q] == key[q];
 							}
 						}
-						if (same) { // (the hashes agree: now the strings)
+						if (STR && same) { // (the hashes agree: now the strings)
 #pragma unroll
 							for (uint32_t q = 0; q < POLR_MAX_GROUP_KEYS; q++) {
 								if (q < groups.n && ((str_mask & ~null_mask) >> q) & 1u) {
@@ -1437,20 +1115,18 @@ __global__ __launch_bounds__(256) void polr_hash_agg_str_kernel(DevOut out, uint
 			const uint32_t s32 = (active && s != ~0ull) ? (uint32_t)s : POLR_NO_SLOT;
 			uint32_t lead = lane;  // the lowest lane of the wave with this lane's slot
 			uint64_t shared = 0;   // the lanes whose slot another lane of the wave has too
-			if (COMBINE) {
-				uint64_t todo = __ballot(s32 != POLR_NO_SLOT);
-				while (todo) {
-					const int l = __builtin_ctzll(todo);
-					const uint32_t ls = (uint32_t)__builtin_amdgcn_readlane((int)s32, l);
-					const uint64_t peers = __ballot(s32 == ls);
-					if (s32 == ls) {
-						lead = (uint32_t)l;
-					}
-					if (peers & (peers - 1)) {
-						shared |= peers;
-					}
-					todo &= ~peers;
+			uint64_t todo = __ballot(s32 != POLR_NO_SLOT);
+			while (todo) {
+				const int l = __builtin_ctzll(todo);
+				const uint32_t ls = (uint32_t)__builtin_amdgcn_readlane((int)s32, l);
+				const uint64_t peers = __ballot(s32 == ls);
+				if (s32 == ls) {
+					lead = (uint32_t)l;
 				}
+				if (peers & (peers - 1)) {
+					shared |= peers;
+				}
+				todo &= ~peers;
 			}
 			for (uint32_t a = 0; a < aggs.n; a++) {
 				const DevAgg &ag = aggs.a[a];
@@ -1466,44 +1142,42 @@ __global__ __launch_bounds__(256) void polr_hash_agg_str_kernel(DevOut out, uint
 				}
 				unsigned long long cnt = have ? 1ull : 0ull, lo = (unsigned long long)v & 0xFFFFFFFFull;
 				long long hi = v >> 32, mn = v, mx = v;
-				if (COMBINE) {
-					uint64_t m = shared;
-					while (m) {
-						const int l = __builtin_ctzll(m);
-						const bool mine = lead == (uint32_t)l;
-						const uint64_t peers = __ballot(mine);
-						const uint64_t with = __ballot(mine && have);
-						unsigned long long w_lo = 0;
-						long long w_hi = 0, w_mn = 0x7FFFFFFFFFFFFFFFll, w_mx = (long long)0x8000000000000000ull;
-						if (ag.fn == POLR_AGG_SUM) {
-							for (uint64_t b = with; b; b &= b - 1) {
-								const int j = __builtin_ctzll(b);
-								w_lo += (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)lo, j);
-								w_hi += (long long)__builtin_amdgcn_readlane((int)hi, j); // (v >> 32 fits 32 bits)
-							}
-						} else if (ag.fn == POLR_AGG_MIN || ag.fn == POLR_AGG_MAX) {
-							for (uint64_t b = with; b; b &= b - 1) {
-								const int j = __builtin_ctzll(b);
-								const long long o = (long long)(((uint64_t)(uint32_t)__builtin_amdgcn_readlane((int)(v >> 32), j) << 32) |
-								                                (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)v, j));
-								w_mn = o < w_mn ? o : w_mn;
-								w_mx = o > w_mx ? o : w_mx;
-							}
+				uint64_t m = shared;
+				while (m) {
+					const int l = __builtin_ctzll(m);
+					const bool mine = lead == (uint32_t)l;
+					const uint64_t peers = __ballot(mine);
+					const uint64_t with = __ballot(mine && have);
+					unsigned long long w_lo = 0;
+					long long w_hi = 0, w_mn = 0x7FFFFFFFFFFFFFFFll, w_mx = (long long)0x8000000000000000ull;
+					if (ag.fn == POLR_AGG_SUM) {
+						for (uint64_t b = with; b; b &= b - 1) {
+							const int j = __builtin_ctzll(b);
+							w_lo += (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)lo, j);
+							w_hi += (long long)__builtin_amdgcn_readlane((int)hi, j); // (v >> 32 fits 32 bits)
 						}
-						if (mine) {
-							have = lane == (uint32_t)l && with != 0; // (the leader speaks for its peers)
-							cnt = (unsigned long long)__popcll(with);
-							lo = w_lo;
-							hi = w_hi;
-							mn = w_mn;
-							mx = w_mx;
+					} else if (ag.fn == POLR_AGG_MIN || ag.fn == POLR_AGG_MAX) {
+						for (uint64_t b = with; b; b &= b - 1) {
+							const int j = __builtin_ctzll(b);
+							const long long o = (long long)(((uint64_t)(uint32_t)__builtin_amdgcn_readlane((int)(v >> 32), j) << 32) |
+							                                (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)v, j));
+							w_mn = o < w_mn ? o : w_mn;
+							w_mx = o > w_mx ? o : w_mx;
 						}
-						m &= ~peers;
 					}
+					if (mine) {
+						have = lane == (uint32_t)l && with != 0; // (the leader speaks for its peers)
+						cnt = (unsigned long long)__popcll(with);
+						lo = w_lo;
+						hi = w_hi;
+						mn = w_mn;
+						mx = w_mx;
+					}
+					m &= ~peers;
 				}
 				if (have) {
 					GroupCell *c = &t.cells[(uint64_t)s32 * aggs.n + a];
-					switch (ag.fn) { // (only the words cell_to_value reads for this function)
+					switch (ag.fn) { // (only the words cell_value reads for this function)
 					case POLR_AGG_SUM:
 						atomicAdd(&c->lo32, lo);
 						atomicAdd((unsigned long long *)&c->hi32, (unsigned long long)hi);
@@ -1524,59 +1198,30 @@ __global__ __launch_bounds__(256) void polr_hash_agg_str_kernel(DevOut out, uint
 	}
 }
 
-// the guard of a VARCHAR column whose cells were never rebased onto a device heap: the non-NULL cells among the output rows
-// that are longer than 12 bytes -- their pointers are the host's.  Reads the length word of a cell and nothing else.
-__global__ __launch_bounds__(256) void polr_count_long_cells_kernel(DevOut out, uint32_t n_chunks, DevCol src, uint32_t slot,
-                                                                    unsigned long long *__restrict__ n_long) {
-	unsigned long long mine = 0;
-	for (uint32_t chunk = blockIdx.x; chunk < n_chunks; chunk += gridDim.x) {
-		const uint32_t n = out.chunk_count[chunk];
-		const uint32_t *ids = out.ids + (uint64_t)slot * out.slot_stride + (uint64_t)chunk * out.chunk_capacity;
-		for (uint32_t i = threadIdx.x; i < n; i += blockDim.x) {
-			const uint32_t row = ids[i];
-			if (src.valid && !src.valid[row]) {
-				continue;
+// the groups that exist, compacted: [idx] <- slot
+// (reps / reps_out: the representative string cells, or nullptr)
+__global__ __launch_bounds__(256) void polr_hash_agg_compact_kernel(HashAggTable t, uint32_t n_cols, uint32_t n_aggs, long long *keys_out,
+                                                                    uint32_t *nulls_out, GroupCell *cells_out, unsigned long long *cursor,
+                                                                    uint64_t max_groups, const uint4 *reps, uint4 *reps_out) {
+	for (uint64_t s = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; s <= t.mask; s += (uint64_t)gridDim.x * blockDim.x) {
+		if (t.state[s] != 2u) {
+			continue;
+		}
+		const unsigned long long idx = atomicAdd(cursor, 1ull);
+		if (idx >= max_groups) {
+			continue;
+		}
+		for (uint32_t q = 0; q < n_cols; q++) {
+			keys_out[idx * n_cols + q] = t.keys[s * n_cols + q];
+			if (reps) {
+				reps_out[idx * n_cols + q] = reps[s * n_cols + q];
 			}
-			mine += *(const uint32_t *)(src.data + (uint64_t)row * 16u) > 12u ? 1u : 0u;
+		}
+		nulls_out[idx] = t.nulls[s];
+		for (uint32_t a = 0; a < n_aggs; a++) {
+			cells_out[idx * n_aggs + a] = t.cells[s * n_aggs + a];
 		}
 	}
-	mine = wave_sum64(mine);
-	if ((threadIdx.x & 63u) == 0 && mine) {
-		atomicAdd(n_long, mine);
-	}
-}
-
-// POLR_OK when the column may be read by a kernel that follows string pointers
-static int check_string_col_on_device(polr_out *o, hipStream_t st, const OwnedCol *c, uint32_t slot, const char *what, uint32_t idx) {
-	polr_ctx *ctx = o->pipe->ctx;
-	if (c->strings_rebased || !c->owned || o->n_chunks == 0) {
-		return POLR_OK; // (rebased here; or the caller's own device memory, whose cells point into HBM by contract)
-	}
-	unsigned long long *n_long = nullptr, h_long = 0;
-	HIPCHK(ctx, hipMalloc((void **)&n_long, 8));
-	hipError_t e = hipMemsetAsync(n_long, 0, 8, st);
-	if (e == hipSuccess) {
-		DevCol src;
-		src.data = c->data;
-		src.valid = c->valid;
-		src.width = c->width;
-		src.flags = c->flags;
-		const uint32_t n_blocks = std::max<uint32_t>(1, std::min<uint32_t>(o->n_chunks, (uint32_t)ctx->n_cus * 4));
-		hipLaunchKernelGGL(polr_count_long_cells_kernel, dim3(n_blocks), dim3(256), 0, st, o->dev, o->n_chunks, src, slot, n_long);
-		e = hipMemcpyAsync(&h_long, n_long, 8, hipMemcpyDeviceToHost, st);
-		e = e == hipSuccess ? hipStreamSynchronize(st) : e;
-	}
-	hipFree(n_long);
-	if (e != hipSuccess) {
-		POLR_FAIL(ctx, POLR_E_HIP, "string column check failed: %s", hipGetErrorString(e));
-	}
-	if (h_long) {
-		POLR_FAIL(ctx, POLR_E_INVALID,
-		          "%s %u: %llu output rows hold strings longer than 12 bytes, but the column's heap was never put on the device "
-		          "(polr_ht_set_payload_heaps / polr_pipeline_set_probe_heaps)",
-		          what, idx, h_long);
-	}
-	return POLR_OK;
 }
 
 // the groups' strings as records {u32 length, bytes} at the offsets the host laid out (offsets[g * n_cols + c])
@@ -1607,26 +1252,26 @@ __global__ __launch_bounds__(256) void polr_group_strings_kernel(const uint4 *__
 }
 
 extern "C" int polr_out_column_width(polr_out *o, int32_t src_join, uint32_t src_col, uint32_t *width) {
+	POLR_ENTRY();
 	if (!o || !width) {
 		return POLR_E_INVALID;
 	}
-	const OwnedCol *c = nullptr;
-	uint32_t slot = 0;
-	int rc = locate_agg_col(o->pipe, src_join, src_col, &c, &slot, "column", src_col);
+	OutCol c;
+	int rc = polr_out_col(o->pipe, src_join, src_col, &c, "column", src_col);
 	if (rc) {
 		return rc;
 	}
-	*width = c->width;
+	*width = c.dev.width;
 	return POLR_OK;
 }
 
-extern "C" int polr_out_aggregate_hashed_str(polr_out *o, void *stream, const polr_group_key *cols, uint32_t n_cols,
-                                             const polr_agg_spec *specs, uint32_t n_aggs, uint64_t max_groups, int64_t *group_keys,
-                                             uint32_t *group_nulls, polr_agg_value *results, uint64_t *n_groups, uint8_t *str_bytes,
-                                             uint64_t str_cap, uint64_t *str_used) {
-	POLR_ENTRY();
-	if (!o || !cols || !specs || !group_keys || !group_nulls || !results || !n_groups || !str_used || (!str_bytes && str_cap) ||
-	    n_cols == 0 || n_aggs == 0 || max_groups == 0) {
+// both entry points of the general GROUP BY; strings: VARCHAR group columns are allowed, their values go to str_bytes
+static int aggregate_hashed(polr_out *o, void *stream, const polr_group_key *cols, uint32_t n_cols, const polr_agg_spec *specs,
+                            uint32_t n_aggs, uint64_t max_groups, int64_t *group_keys, uint32_t *group_nulls,
+                            polr_agg_value *results, uint64_t *n_groups, bool strings, uint8_t *str_bytes, uint64_t str_cap,
+                            uint64_t *str_used) {
+	if (!o || !cols || !specs || !group_keys || !group_nulls || !results || !n_groups || n_cols == 0 || n_aggs == 0 ||
+	    max_groups == 0 || (strings && (!str_used || (!str_bytes && str_cap)))) {
 		return POLR_E_INVALID;
 	}
 	polr_pipeline *p = o->pipe;
@@ -1635,68 +1280,41 @@ extern "C" int polr_out_aggregate_hashed_str(polr_out *o, void *stream, const po
 		POLR_FAIL(ctx, POLR_E_UNSUPPORTED, "at most %d group columns, %d aggregates and 2^24 groups", POLR_MAX_GROUP_KEYS,
 		          POLR_MAX_AGGS);
 	}
-	*str_used = 0;
+	if (strings) {
+		*str_used = 0;
+	}
 	DevGroupSet gs;
 	memset(&gs, 0, sizeof(gs));
 	gs.n = n_cols;
-	const OwnedCol *gcol[POLR_MAX_GROUP_KEYS] = {};
+	OutCol gcol[POLR_MAX_GROUP_KEYS];
 	uint32_t str_mask = 0;
 	for (uint32_t q = 0; q < n_cols; q++) {
-		const OwnedCol *c = nullptr;
-		uint32_t slot = 0;
-		int rc = locate_agg_col(p, cols[q].src_join, cols[q].src_col, &c, &slot, "group column", q);
+		int rc = polr_out_col(p, cols[q].src_join, cols[q].src_col, &gcol[q], "group column", q);
+		if (!rc && strings && gcol[q].dev.width == 16) {
+			str_mask |= 1u << q;
+		} else if (!rc) {
+			rc = polr_out_int_col(p, cols[q].src_join, cols[q].src_col, &gcol[q], "group column", q);
+		}
 		if (rc) {
 			return rc;
 		}
-		if (c->width == 16) {
-			str_mask |= 1u << q;
-		} else if (c->width > 8 || (c->width == 8 && !(c->flags & 1u))) {
-			POLR_FAIL(ctx, POLR_E_UNSUPPORTED, "group column %u: an integer column of up to 8 bytes (signed if 8) or a VARCHAR column", q);
-		}
-		gcol[q] = c;
-		gs.k[q].src.data = c->data;
-		gs.k[q].src.valid = c->valid;
-		gs.k[q].src.width = c->width;
-		gs.k[q].src.flags = c->flags;
-		gs.k[q].slot = slot;
-	}
-	if (!str_mask) { // integer columns only: the integer sink itself
-		return polr_out_aggregate_hashed(o, stream, cols, n_cols, specs, n_aggs, max_groups, group_keys, group_nulls, results, n_groups);
+		gs.k[q].src = gcol[q].dev;
+		gs.k[q].slot = gcol[q].slot;
 	}
 	DevAggSet as;
-	memset(&as, 0, sizeof(as));
-	as.n = n_aggs;
-	for (uint32_t a = 0; a < n_aggs; a++) {
-		if (specs[a].fn > POLR_AGG_MAX) {
-			POLR_FAIL(ctx, POLR_E_INVALID, "aggregate %u: unknown function %u", a, specs[a].fn);
-		}
-		as.a[a].fn = specs[a].fn;
-		if (specs[a].fn == POLR_AGG_COUNT_STAR) {
-			continue;
-		}
-		const OwnedCol *c = nullptr;
-		uint32_t slot = 0;
-		int rc = resolve_agg_col(p, specs[a].src_join, specs[a].src_col, &c, &slot, "aggregate", a);
-		if (rc) {
-			return rc;
-		}
-		as.a[a].src.data = c->data;
-		as.a[a].src.valid = c->valid;
-		as.a[a].src.width = c->width;
-		as.a[a].src.flags = c->flags;
-		as.a[a].slot = slot;
+	int rc = build_agg_set(p, specs, n_aggs, &as);
+	if (rc) {
+		return rc;
 	}
 	HIPCHK(ctx, hipSetDevice(ctx->device));
 	hipStream_t st = polr_stream(ctx, stream);
-	if (!o->stats_valid) {
-		int rc = polr_out_stats(o, stream, nullptr, nullptr, nullptr);
-		if (rc) {
-			return rc;
-		}
+	rc = out_ensure_stats(o, stream);
+	if (rc) {
+		return rc;
 	}
 	for (uint32_t q = 0; q < n_cols; q++) { // before any kernel that follows a string pointer is enqueued
 		if ((str_mask >> q) & 1u) {
-			int rc = check_string_col_on_device(o, st, gcol[q], gs.k[q].slot, "group column", q);
+			rc = check_string_col_on_device(o, st, gcol[q], "group column", q);
 			if (rc) {
 				return rc;
 			}
@@ -1710,11 +1328,13 @@ extern "C" int polr_out_aggregate_hashed_str(polr_out *o, void *stream, const po
 	memset(&t, 0, sizeof(t));
 	t.mask = capacity - 1;
 	t.max_groups = max_groups;
-	// one allocation: state, nulls, counters, keys, representative cells, group cells, and the compacted outputs behind them
+	// one allocation: state, nulls, counters, keys, representative cells (VARCHAR only), group cells, and the compacted
+	// outputs behind them
+	const size_t rep_bytes = str_mask ? 16 : 0;
 	const size_t b_state = capacity * 4, b_nulls = capacity * 4, b_cnt = 64, b_keys = capacity * n_cols * 8,
-	             b_reps = capacity * n_cols * 16, b_cells = capacity * n_aggs * sizeof(GroupCell),
+	             b_reps = capacity * n_cols * rep_bytes, b_cells = capacity * n_aggs * sizeof(GroupCell),
 	             b_okeys = (max_groups * n_cols * 8 + 15) & ~(size_t)15, // (the uint4 cells behind it stay 16-byte aligned)
-	             b_oreps = max_groups * n_cols * 16, b_onulls = (max_groups * 4 + 15) & ~(size_t)15,
+	             b_oreps = max_groups * n_cols * rep_bytes, b_onulls = (max_groups * 4 + 15) & ~(size_t)15,
 	             b_ocells = max_groups * n_aggs * sizeof(GroupCell);
 	uint8_t *base = nullptr;
 	HIPCHK(ctx, hipMalloc((void **)&base, b_state + b_nulls + b_cnt + b_keys + b_reps + b_cells + b_okeys + b_oreps + b_onulls + b_ocells));
@@ -1729,13 +1349,13 @@ extern "C" int polr_out_aggregate_hashed_str(polr_out *o, void *stream, const po
 	t.overflow = cnt + 1;
 	t.keys = (long long *)at;
 	at += b_keys;
-	uint4 *reps = (uint4 *)at;
+	uint4 *reps = str_mask ? (uint4 *)at : nullptr;
 	at += b_reps;
 	t.cells = (GroupCell *)at;
 	at += b_cells;
 	long long *okeys = (long long *)at;
 	at += b_okeys;
-	uint4 *oreps = (uint4 *)at;
+	uint4 *oreps = str_mask ? (uint4 *)at : nullptr;
 	at += b_oreps;
 	uint32_t *onulls = (uint32_t *)at;
 	at += b_onulls;
@@ -1743,10 +1363,14 @@ extern "C" int polr_out_aggregate_hashed_str(polr_out *o, void *stream, const po
 	hipError_t e = hipMemsetAsync(base, 0, b_state + b_nulls + b_cnt, st);
 	unsigned long long h_cnt[3] = {0, 0, 0};
 	if (e == hipSuccess) {
-		hipLaunchKernelGGL(polr_hash_agg_init_kernel, dim3(256), dim3(256), 0, st, t, n_aggs);
+		hipLaunchKernelGGL(polr_group_init_kernel, dim3(256), dim3(256), 0, st, t.cells, capacity * n_aggs);
 		if (o->n_chunks) {
-			hipLaunchKernelGGL(polr_hash_agg_str_kernel<POLR_HASH_AGG_WAVE_COMBINE != 0>, dim3(std::min<uint32_t>(o->n_chunks, 2048u)),
-			                   dim3(256), 0, st, o->dev, o->n_chunks, gs, as, t, reps, str_mask);
+			const dim3 grid(std::min<uint32_t>(o->n_chunks, 2048u));
+			if (str_mask) {
+				hipLaunchKernelGGL(polr_hash_agg_kernel<true>, grid, dim3(256), 0, st, o->dev, o->n_chunks, gs, as, t, reps, str_mask);
+			} else {
+				hipLaunchKernelGGL(polr_hash_agg_kernel<false>, grid, dim3(256), 0, st, o->dev, o->n_chunks, gs, as, t, reps, str_mask);
+			}
 		}
 		hipLaunchKernelGGL(polr_hash_agg_compact_kernel, dim3(256), dim3(256), 0, st, t, n_cols, n_aggs, okeys, onulls, ocells, cnt + 2,
 		                   max_groups, (const uint4 *)reps, oreps);
@@ -1756,17 +1380,21 @@ extern "C" int polr_out_aggregate_hashed_str(polr_out *o, void *stream, const po
 	const bool too_many = h_cnt[1] || h_cnt[0] > max_groups;
 	const uint64_t g_n = too_many ? 0 : h_cnt[0];
 	std::vector<GroupCell> hcells(g_n * n_aggs);
-	std::vector<uint4> hreps(g_n * n_cols);
-	std::vector<uint32_t> hnulls(g_n);
-	std::vector<long long> hkeys(g_n * n_cols);
+	// integer columns only: keys and NULL bits go to the caller's arrays at once; with VARCHAR columns they are staged here
+	// until the strings' records fit, so that an arena too small leaves the caller's arrays as they were
+	std::vector<uint4> hreps(str_mask ? g_n * n_cols : 0);
+	std::vector<long long> skeys(str_mask ? g_n * n_cols : 0);
+	std::vector<uint32_t> snulls(str_mask ? g_n : 0);
+	long long *hkeys = str_mask ? skeys.data() : (long long *)group_keys;
+	uint32_t *hnulls = str_mask ? snulls.data() : group_nulls;
 	uint64_t used = 0;
 	if (e == hipSuccess && g_n) {
-		e = hipMemcpy(hkeys.data(), okeys, g_n * n_cols * 8, hipMemcpyDeviceToHost);
-		e = e == hipSuccess ? hipMemcpy(hnulls.data(), onulls, g_n * 4, hipMemcpyDeviceToHost) : e;
-		e = e == hipSuccess ? hipMemcpy(hreps.data(), oreps, g_n * n_cols * 16, hipMemcpyDeviceToHost) : e;
+		e = hipMemcpy(hkeys, okeys, g_n * n_cols * 8, hipMemcpyDeviceToHost);
+		e = e == hipSuccess ? hipMemcpy(hnulls, onulls, g_n * 4, hipMemcpyDeviceToHost) : e;
+		e = e == hipSuccess && str_mask ? hipMemcpy(hreps.data(), oreps, g_n * n_cols * 16, hipMemcpyDeviceToHost) : e;
 		e = e == hipSuccess ? hipMemcpy(hcells.data(), ocells, g_n * n_aggs * sizeof(GroupCell), hipMemcpyDeviceToHost) : e;
 		// lay the records out: a VARCHAR column's key word becomes the offset of its record (0 for NULL)
-		for (uint64_t g = 0; g < g_n && e == hipSuccess; g++) {
+		for (uint64_t g = 0; g < g_n && e == hipSuccess && str_mask; g++) {
 			for (uint32_t q = 0; q < n_cols; q++) {
 				if (!((str_mask >> q) & 1u)) {
 					continue;
@@ -1783,7 +1411,7 @@ extern "C" int polr_out_aggregate_hashed_str(polr_out *o, void *stream, const po
 	uint8_t *arena = nullptr;
 	if (e == hipSuccess && g_n && used && used <= str_cap) {
 		e = hipMalloc((void **)&arena, used);
-		e = e == hipSuccess ? hipMemcpyAsync(okeys, hkeys.data(), g_n * n_cols * 8, hipMemcpyHostToDevice, st) : e;
+		e = e == hipSuccess ? hipMemcpyAsync(okeys, hkeys, g_n * n_cols * 8, hipMemcpyHostToDevice, st) : e;
 		if (e == hipSuccess) {
 			const uint64_t n_rec = g_n * n_cols;
 			hipLaunchKernelGGL(polr_group_strings_kernel, dim3((unsigned)((n_rec + 255) / 256)), dim3(256), 0, st, (const uint4 *)oreps,
@@ -1804,19 +1432,38 @@ extern "C" int polr_out_aggregate_hashed_str(polr_out *o, void *stream, const po
 		POLR_FAIL(ctx, POLR_E_OVERFLOW, "the result has %llu groups or more, the caller made room for %llu",
 		          (unsigned long long)h_cnt[0], (unsigned long long)max_groups);
 	}
-	*str_used = used;
+	if (strings) {
+		*str_used = used;
+	}
 	if (used > str_cap) { // (nothing was written: group_keys, group_nulls, results and str_bytes are as they were)
 		POLR_FAIL(ctx, POLR_E_OVERFLOW, "the groups' strings take %llu bytes, the caller made room for %llu", (unsigned long long)used,
 		          (unsigned long long)str_cap);
 	}
-	if (g_n) {
-		memcpy(group_keys, hkeys.data(), g_n * n_cols * 8);
-		memcpy(group_nulls, hnulls.data(), g_n * 4);
+	if (str_mask && g_n) {
+		memcpy(group_keys, hkeys, g_n * n_cols * 8);
+		memcpy(group_nulls, hnulls, g_n * 4);
 	}
 	for (uint64_t g = 0; g < g_n; g++) {
 		for (uint32_t a = 0; a < n_aggs; a++) {
-			cell_to_value(hcells[g * n_aggs + a], specs[a].fn, results[g * n_aggs + a]);
+			results[g * n_aggs + a] = cell_value(hcells[g * n_aggs + a], specs[a].fn);
 		}
 	}
 	return POLR_OK;
+}
+
+extern "C" int polr_out_aggregate_hashed(polr_out *o, void *stream, const polr_group_key *cols, uint32_t n_cols,
+                                         const polr_agg_spec *specs, uint32_t n_aggs, uint64_t max_groups, int64_t *group_keys,
+                                         uint32_t *group_nulls, polr_agg_value *results, uint64_t *n_groups) {
+	POLR_ENTRY();
+	return aggregate_hashed(o, stream, cols, n_cols, specs, n_aggs, max_groups, group_keys, group_nulls, results, n_groups, false,
+	                        nullptr, 0, nullptr);
+}
+
+extern "C" int polr_out_aggregate_hashed_str(polr_out *o, void *stream, const polr_group_key *cols, uint32_t n_cols,
+                                             const polr_agg_spec *specs, uint32_t n_aggs, uint64_t max_groups, int64_t *group_keys,
+                                             uint32_t *group_nulls, polr_agg_value *results, uint64_t *n_groups, uint8_t *str_bytes,
+                                             uint64_t str_cap, uint64_t *str_used) {
+	POLR_ENTRY();
+	return aggregate_hashed(o, stream, cols, n_cols, specs, n_aggs, max_groups, group_keys, group_nulls, results, n_groups, true,
+	                        str_bytes, str_cap, str_used);
 }

@@ -687,12 +687,7 @@ int polr_ht_finalize_perfect(polr_ht *ht, int64_t min_value, int64_t max_value, 
 	}
 	if (!rc) {
 		for (uint32_t i = 0; i < ht->n_payload; i++) {
-			DevCol src;
-			src.data = ht->payload[i].data;
-			src.valid = ht->payload[i].valid;
-			src.width = ht->payload[i].width;
-			src.flags = ht->payload[i].flags;
-			polr_launch_pht_gather(st, ht->bits, ht->idx_row, size, src, ht->pcols[i].data, ht->pcols[i].valid);
+			polr_launch_pht_gather(st, ht->bits, ht->idx_row, size, dev_col(ht->payload[i]), ht->pcols[i].data, ht->pcols[i].valid);
 		}
 		hipError_t e = hipStreamSynchronize(st);
 		if (e != hipSuccess) {
@@ -906,8 +901,8 @@ static void ht_buffers(const polr_ht *ht, std::vector<void *> &ptrs, std::vector
 		ptrs.push_back(ht->rowids);
 		bytes.push_back(std::max<uint64_t>(ht->n_rows_in * 4, 16));
 	}
-	const std::vector<OwnedCol> &cols = ht->kind == KIND_PERFECT ? ht->pcols : ht->payload;
-	for (auto &c : cols) {
+	for (uint32_t i = 0; i < ht->n_payload; i++) {
+		const OwnedCol &c = build_col(ht, i);
 		ptrs.push_back(c.data);
 		bytes.push_back(std::max<uint64_t>(rows * c.width, 16));
 		if (c.valid) {
@@ -967,11 +962,11 @@ int polr_ht_export(const polr_ht *ht, void *meta, uint64_t *meta_bytes, void **d
 		m.key_sem[i] = ht->key_flags[i];
 	}
 	m.pack = ht->pack;
-	const std::vector<OwnedCol> &cols = ht->kind == KIND_PERFECT ? ht->pcols : ht->payload;
 	for (uint32_t i = 0; i < ht->n_payload; i++) {
-		m.payload_width[i] = cols[i].width;
-		m.payload_flags[i] = cols[i].flags;
-		m.payload_has_valid[i] = cols[i].valid ? 1 : 0;
+		const OwnedCol &c = build_col(ht, i);
+		m.payload_width[i] = c.width;
+		m.payload_flags[i] = c.flags;
+		m.payload_has_valid[i] = c.valid ? 1 : 0;
 	}
 	memcpy(meta, &m, sizeof(m));
 	for (size_t i = 0; i < ptrs.size(); i++) {
@@ -1106,8 +1101,7 @@ static void build_stage_descs(const polr_pipeline *p, const DevPipeline &dp, std
 			data = p->probe_cols[sc].data;
 			valid = p->probe_cols[sc].valid;
 		} else {
-			const polr_ht *src = p->hts[sj];
-			const OwnedCol &col = src->kind == KIND_PERFECT ? src->pcols[sc] : src->payload[sc];
+			const OwnedCol &col = build_col(p->hts[sj], sc);
 			slot = dp.slot_of_join[sj];
 			data = col.data;
 			valid = col.valid;
@@ -1115,8 +1109,7 @@ static void build_stage_descs(const polr_pipeline *p, const DevPipeline &dp, std
 	};
 	// width and signedness of the column a key is READ from (a key compared by value may differ from the build column)
 	auto source_type = [&](int32_t sj, int32_t sc, uint32_t &width, uint32_t &sx) {
-		const OwnedCol &col = sj < 0 ? p->probe_cols[sc]
-		                             : (p->hts[sj]->kind == KIND_PERFECT ? p->hts[sj]->pcols[sc] : p->hts[sj]->payload[sc]);
+		const OwnedCol &col = sj < 0 ? p->probe_cols[sc] : build_col(p->hts[sj], sc);
 		width = col.width;
 		sx = (col.flags & 1u) ? 1u : 0u;
 	};
@@ -1147,8 +1140,7 @@ static void build_stage_descs(const polr_pipeline *p, const DevPipeline &dp, std
 				x.pack = ht->pack;
 				x.n_preds = dj.n_preds;
 				for (uint32_t c = 0; c < dj.n_preds; c++) {
-					const OwnedCol &bcol =
-					    ht->kind == KIND_PERFECT ? ht->pcols[dj.pred_build_col[c]] : ht->payload[dj.pred_build_col[c]];
+					const OwnedCol &bcol = build_col(ht, dj.pred_build_col[c]);
 					x.pred_op[c] = dj.pred_op[c];
 					x.pred_width[c] = bcol.width;
 					x.pred_sx[c] = (bcol.flags & 1u) ? 1u : 0u;
@@ -1397,7 +1389,7 @@ int polr_pipeline_create(polr_ctx *ctx, const polr_col *probe_cols, uint32_t n_p
 				}
 				width = joins[sj].ht->payload[sc].width;
 			}
-			const OwnedCol &bcol = ht->kind == KIND_PERFECT ? ht->pcols[bc] : ht->payload[bc];
+			const OwnedCol &bcol = build_col(ht, bc);
 			if (op == POLR_CMP_STR_EQ) {
 				if (width != 16 || bcol.width != 16) {
 					POLR_FAIL(ctx, POLR_E_INVALID, "join %u condition %u: STR_EQ compares two columns of 16-byte string cells "
@@ -1781,11 +1773,9 @@ int polr_out_fetch_ids(polr_out *o, void *stream, uint32_t *dst, uint64_t dst_ro
 	}
 	polr_ctx *ctx = o->pipe->ctx;
 	hipStream_t st = polr_stream(ctx, stream);
-	if (!o->stats_valid) {
-		int rc = polr_out_stats(o, stream, nullptr, nullptr, nullptr);
-		if (rc) {
-			return rc;
-		}
+	int rc = out_ensure_stats(o, stream);
+	if (rc) {
+		return rc;
 	}
 	if (dst_rows < o->n_rows) {
 		POLR_FAIL(ctx, POLR_E_INVALID, "destination holds %llu rows, output has %llu", (unsigned long long)dst_rows,
@@ -1816,40 +1806,21 @@ int polr_out_materialize(polr_out *o, void *stream, int32_t src_join, uint32_t s
 	polr_pipeline *p = o->pipe;
 	polr_ctx *ctx = p->ctx;
 	hipStream_t st = polr_stream(ctx, stream);
-	if (!o->stats_valid) {
-		int rc = polr_out_stats(o, stream, nullptr, nullptr, nullptr);
-		if (rc) {
-			return rc;
-		}
+	int rc = out_ensure_stats(o, stream);
+	if (rc) {
+		return rc;
 	}
 	if (dst_rows < o->n_rows) {
 		POLR_FAIL(ctx, POLR_E_INVALID, "destination holds %llu rows, output has %llu", (unsigned long long)dst_rows,
 		          (unsigned long long)o->n_rows);
 	}
-	DevCol src;
-	uint32_t slot;
-	if (src_join < 0) {
-		if (src_col >= p->n_probe_cols) {
-			POLR_FAIL(ctx, POLR_E_INVALID, "probe column %u out of range", src_col);
-		}
-		const OwnedCol &c = p->probe_cols[src_col];
-		src.data = c.data;
-		src.valid = c.valid;
-		src.width = c.width;
-		src.flags = c.flags;
-		slot = 0;
-	} else {
-		if ((uint32_t)src_join >= p->k || src_col >= p->hts[src_join]->n_payload) {
-			POLR_FAIL(ctx, POLR_E_INVALID, "build column (%d,%u) out of range", src_join, src_col);
-		}
-		const polr_ht *ht = p->hts[src_join];
-		const OwnedCol &c = ht->kind == KIND_PERFECT ? ht->pcols[src_col] : ht->payload[src_col];
-		src.data = c.data;
-		src.valid = c.valid;
-		src.width = c.width;
-		src.flags = c.flags;
-		slot = 1 + (uint32_t)src_join;
+	OutCol c;
+	rc = polr_out_col(p, src_join, src_col, &c, "column", src_col);
+	if (rc) {
+		return rc;
 	}
+	const DevCol &src = c.dev;
+	const uint32_t slot = c.slot;
 	if (o->n_rows == 0) {
 		return POLR_OK;
 	}

@@ -169,6 +169,36 @@ static inline hipStream_t polr_stream(polr_ctx *ctx, void *stream) {
 	return stream ? (hipStream_t)stream : ctx->stream;
 }
 
+// the copy of build column i that the kernels read: a perfect table's re-ordered copy, else the payload as uploaded
+static inline const OwnedCol &build_col(const polr_ht *ht, uint32_t i) {
+	return ht->kind == KIND_PERFECT ? ht->pcols[i] : ht->payload[i];
+}
+
+static inline DevCol dev_col(const OwnedCol &c) {
+	DevCol d;
+	d.data = c.data;
+	d.valid = c.valid;
+	d.width = c.width;
+	d.flags = c.flags;
+	return d;
+}
+
+// the statistics every reader of an output needs (chunk count, prefix): computed once after a run
+static inline int out_ensure_stats(polr_out *o, void *stream) {
+	return o->stats_valid ? POLR_OK : polr_out_stats(o, stream, nullptr, nullptr, nullptr);
+}
+
+// column (src_join, src_col) of a pipeline's output, as a sink reads it (polr_agg.hip)
+struct OutCol {
+	const OwnedCol *col;
+	uint32_t slot; // the output's row ids that index it: 0 probe, 1 + j join j
+	DevCol dev;
+};
+// POLR_E_INVALID for a column out of range ("<what> <idx>: ..." in the context's error)
+int polr_out_col(polr_pipeline *p, int32_t src_join, uint32_t src_col, OutCol *c, const char *what, uint32_t idx);
+// ... and POLR_E_UNSUPPORTED for anything but an integer column of up to 8 bytes (signed if 8): what cell-valued sinks read
+int polr_out_int_col(polr_pipeline *p, int32_t src_join, uint32_t src_col, OutCol *c, const char *what, uint32_t idx);
+
 // Only the flat pool kernel folds tuples into a fused GROUP BY sink (DevOut::fused).  The entry points that launch the
 // per-round path kernel refuse such an output before they enqueue anything: that kernel would write row ids instead and
 // leave the group cells empty.

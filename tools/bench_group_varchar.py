@@ -1,9 +1,9 @@
 """Times polr_out_aggregate_hashed_str against polr_out_aggregate_hashed (integer codes) over the same materialised output.
 usage: python tools/bench_group_varchar.py <library.so> <tag>   -> one JSON line per shape (host clock around the C call, which
-ends in a synchronise: 3 warm-up calls, then 9 timed ones; median, min, max).  The A/B of the wave combine: run it on
-duckdb-polr_amd/libpolr_hip.so and on libpolr_hip_plainagg.so (`make -C duckdb-polr_amd plainagg`), alternating, one process
-each; kernel times: the same command under `rocprofv3 --kernel-trace --stats -- python ...` in a run of its own.
-Results: profiles/README.md"""
+ends in a synchronise: 3 warm-up calls, then 9 timed ones; median, min, max).  Both entry points run polr_hash_agg_kernel:
+the string sink its <true>, the integer sink its <false> instance.  To compare two builds of the library, run it on each,
+alternating, one process each; kernel times: the same command under `rocprofv3 --kernel-trace --stats -- python ...` in a
+run of its own per library.  Results: profiles/README.md"""
 import ctypes as C
 import json
 import os
