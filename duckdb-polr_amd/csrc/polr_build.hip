@@ -413,6 +413,12 @@ extern "C++" void polr_launch_s16_build(hipStream_t st, const DevCol *keys_dev, 
 	(void)rowids;
 }
 
+// exclusive scan of block_sums[n_blocks] in place, the total to *total (the middle pass above, for other block-sum scans:
+// the dictionary encoder's rank step, polr_dict.hip)
+extern "C++" void polr_launch_scan_blocksums(hipStream_t st, uint32_t *block_sums, uint32_t n_blocks, uint32_t *total) {
+	hipLaunchKernelGGL(polr_scan_blocksums_kernel, dim3(1), dim3(1024), 0, st, block_sums, n_blocks, total);
+}
+
 extern "C++" void polr_launch_s16_scatter(hipStream_t st, uint64_t n_rows, const uint4 *slots,
                                           const uint32_t *slot_of_row, uint32_t *cursor, uint32_t *rowids,
                                           uint32_t sentinel_start, uint32_t *sentinel_cursor) {

@@ -833,6 +833,11 @@ void polr_ht_destroy(polr_ht *ht) {
 	for (void *h : ht->heaps) {
 		hipFree(h);
 	}
+	for (DictCol &d : ht->dicts) {
+		if (d.cells) {
+			hipFree(d.cells);
+		}
+	}
 	if (ht->kind == KIND_PERFECT) {
 		if (ht->bits) {
 			hipFree(ht->bits);

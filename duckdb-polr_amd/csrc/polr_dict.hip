@@ -1,0 +1,473 @@
+// duckdb-polr_amd/csrc/polr_dict.hip -- dictionary encoding of a VARCHAR payload column of a build side
+// (polr_ht_encode_dictionary / polr_ht_fetch_dictionary of include/polr_hip.h).
+//
+// A group column that is a payload column of a build side has at most as many distinct values as the build side has rows,
+// and the build side is uploaded once: the strings are hashed and compared ONCE PER BUILD ROW here, at build time, and the
+// column becomes dense 4-byte codes -- an ordinary integer payload column for the perfect-hash sink and the fused sink
+// (polr_out_aggregate_grouped, polr_out_fuse_grouped), whose probe side then reads one 4-byte cell per surviving tuple.
+//
+// Codes are deterministic: the code of a value is the number of distinct non-NULL values whose first occurrence (lowest
+// build row) comes before its own, i.e. 0 .. n_codes - 1 in order of first appearance; NULL rows get n_codes.  Three
+// steps over the build rows, all on the device, nothing read back before the final count:
+//   insert  every non-NULL row finds or claims the slot of its string in an open-addressing table (capacity a power of two
+//           >= 2 x rows) and lowers the slot's first_row to its own row number;
+//   rank    row r is a first occurrence iff first_row[slot_of_row[r]] == r; an exclusive prefix sum of that flag over the
+//           rows is the first occurrence's code, the total is n_codes;
+//   assign  code[r] = the code of r's slot, NULL rows n_codes.
+#include <algorithm>
+#include <cstring>
+
+#include "polr_internal.h"
+
+#define POLR_DICT_NO_SLOT 0xFFFFFFFFu
+#define POLR_DICT_BLOCK 256u
+#define POLR_DICT_ITEMS 4u // rows per thread of the rank step: 1024 rows per workgroup
+
+struct DictTable {
+	uint32_t *state;     // [capacity] 0 empty / 1 being written / 2 ready
+	uint64_t *hash;      // [capacity] polr_str_hash of the slot's string
+	uint4 *rep;          // [capacity] the claimer's cell
+	uint32_t *first_row; // [capacity] lowest build row that holds the slot's string (0xFFFFFFFF: none yet)
+	uint32_t *code;      // [capacity] the slot's code (rank step)
+	uint64_t mask;       // capacity - 1
+};
+
+// scalars: [0] n_codes, [1] some row is NULL, [2] the table was full (cannot happen: capacity >= 2 x rows)
+enum { DICT_N_CODES = 0, DICT_HAS_NULL = 1, DICT_FULL = 2, DICT_SCALARS = 4 };
+
+__global__ __launch_bounds__(256) void polr_dict_init_kernel(DictTable t) {
+	for (uint64_t s = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; s <= t.mask; s += (uint64_t)gridDim.x * blockDim.x) {
+		t.state[s] = 0u;
+		t.first_row[s] = 0xFFFFFFFFu;
+	}
+}
+
+// the guard of a column whose cells were never rebased onto a device heap: its non-NULL cells longer than 12 bytes (their
+// pointers are the host's).  Reads the length word of a cell and nothing else.
+__global__ __launch_bounds__(256) void polr_dict_count_long_kernel(const uint4 *__restrict__ cells, const uint8_t *__restrict__ valid,
+                                                                   uint64_t n, unsigned long long *__restrict__ n_long) {
+	unsigned long long mine = 0;
+	for (uint64_t r = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; r < n; r += (uint64_t)gridDim.x * blockDim.x) {
+		if (valid && !valid[r]) {
+			continue;
+		}
+		mine += *(const uint32_t *)(cells + r) > 12u ? 1u : 0u;
+	}
+	mine = wave_sum64(mine);
+	if ((threadIdx.x & 63u) == 0 && mine) {
+		atomicAdd(n_long, mine);
+	}
+}
+
+// true in the lowest lane of every set of lanes that `want` it and hold the same value; to be called by all lanes of the
+// wave.  One step per distinct value among those lanes: few distinct values is the common shape.
+__device__ __forceinline__ bool dict_first_of_equals(uint32_t v, bool want, uint32_t lane) {
+	uint64_t todo = __ballot(want);
+	bool first = false;
+	while (todo) {
+		const int l = __builtin_ctzll(todo);
+		const uint32_t lv = (uint32_t)__builtin_amdgcn_readlane((int)v, l);
+		first = first || lane == (uint32_t)l;
+		todo &= ~__ballot(want && v == lv);
+	}
+	return first;
+}
+
+// insert: the claim protocol of the general GROUP BY sink (polr_hash_agg_kernel, polr_agg.hip): a row claims an empty slot
+// with a compare-and-swap, writes hash and cell, and publishes them with a release store of state 2; every other row reads
+// the state with an acquire load.  A lane that meets a slot "being written" does not wait inside the iteration -- the writer
+// may be a lane of its own wave, which runs in lockstep -- it looks again in the next iteration of the loop all lanes share.
+// Few distinct values is the common shape (5 nations over millions of customers): hash + one slot read + one comparison.
+__global__ __launch_bounds__(256) void polr_dict_insert_kernel(const uint4 *__restrict__ cells, const uint8_t *__restrict__ valid,
+                                                               uint64_t n, DictTable t, uint32_t *__restrict__ slot_of_row,
+                                                               uint32_t *__restrict__ scalars) {
+	const uint32_t lane = threadIdx.x & 63u;
+	// (every thread of a workgroup makes the same number of trips: the probe loop below is a workgroup-wide one)
+	for (uint64_t base = (uint64_t)blockIdx.x * blockDim.x; base < n; base += (uint64_t)gridDim.x * blockDim.x) {
+		const uint64_t r = base + threadIdx.x;
+		const bool in_range = r < n;
+		const bool is_null = in_range && valid && !valid[r];
+		const bool active = in_range && !is_null;
+		uint4 cell = make_uint4(0, 0, 0, 0);
+		uint64_t h = 0;
+		if (active) { // (the cell of a NULL row is never read)
+			cell = cells[r];
+			h = polr_str_hash(cell);
+		}
+		if (__ballot(is_null) && lane == 0) {
+			atomicOr(&scalars[DICT_HAS_NULL], 1u);
+		}
+		uint64_t s = h & t.mask;
+		bool done = !active;
+		uint64_t probes = 0;
+		while (__syncthreads_or(!done)) {
+			const uint32_t st = done ? 3u : __hip_atomic_load(&t.state[s], __ATOMIC_ACQUIRE, __HIP_MEMORY_SCOPE_AGENT);
+			// (of the lanes of a wave that found the same slot empty, one tries to claim it: a fresh table is not hit by
+			// one compare-and-swap per row)
+			if (dict_first_of_equals((uint32_t)s, st == 0u, lane)) {
+				if (atomicCAS(&t.state[s], 0u, 1u) == 0u) {
+					t.hash[s] = h;
+					t.rep[s] = cell;
+					__hip_atomic_store(&t.state[s], 2u, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_AGENT);
+					done = true;
+				}
+			} else if (st == 2u) {
+				if (t.hash[s] == h && polr_str_equal(t.rep[s], cell)) {
+					done = true;
+				} else {
+					s = (s + 1) & t.mask;
+					if (++probes > t.mask) {
+						atomicOr(&scalars[DICT_FULL], 1u);
+						done = true;
+						s = ~0ull;
+					}
+				}
+			}
+			// (an empty slot left to another lane, st == 1, or the compare-and-swap lost: somebody is writing this slot:
+			// look again in the next iteration)
+		}
+		const uint32_t s32 = (active && s != ~0ull) ? (uint32_t)s : POLR_DICT_NO_SLOT;
+		if (in_range) {
+			slot_of_row[r] = s32;
+		}
+		// first_row[slot] = min over the slot's rows.  A row not below the value already there has nothing to add; of the
+		// others, rows rise with the lane, so the lowest lane of the wave on a slot speaks for all of them: one atomic per
+		// wave and distinct slot at most, whatever the distribution (every row on one slot: one per wave).
+		const bool below = s32 != POLR_DICT_NO_SLOT &&
+		                   (uint32_t)r < __hip_atomic_load(&t.first_row[s32], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+		if (dict_first_of_equals(s32, below, lane)) {
+			atomicMin(&t.first_row[s32], (uint32_t)r);
+		}
+	}
+}
+
+__device__ __forceinline__ bool dict_is_first(const DictTable &t, const uint32_t *__restrict__ slot_of_row, uint64_t r, uint64_t n) {
+	if (r >= n) {
+		return false;
+	}
+	const uint32_t s = slot_of_row[r];
+	return s != POLR_DICT_NO_SLOT && t.first_row[s] == (uint32_t)r;
+}
+
+// rank, pass 1: first occurrences per 1024 rows
+__global__ __launch_bounds__(256) void polr_dict_rank_reduce_kernel(DictTable t, const uint32_t *__restrict__ slot_of_row, uint64_t n,
+                                                                    uint32_t *__restrict__ block_sums) {
+	__shared__ uint32_t wave_sum[POLR_DICT_BLOCK / 64];
+	const uint64_t base = (uint64_t)blockIdx.x * POLR_DICT_BLOCK * POLR_DICT_ITEMS;
+	uint32_t mine = 0;
+	for (uint32_t i = 0; i < POLR_DICT_ITEMS; i++) {
+		mine += (uint32_t)__popcll(__ballot(dict_is_first(t, slot_of_row, base + i * POLR_DICT_BLOCK + threadIdx.x, n)));
+	}
+	if ((threadIdx.x & 63u) == 0) {
+		wave_sum[threadIdx.x >> 6] = mine; // (the ballots' counts: the same in every lane)
+	}
+	__syncthreads();
+	if (threadIdx.x == 0) {
+		uint32_t sum = 0;
+		for (uint32_t w = 0; w < POLR_DICT_BLOCK / 64; w++) {
+			sum += wave_sum[w];
+		}
+		block_sums[blockIdx.x] = sum;
+	}
+}
+
+// rank, pass 3 (pass 2: the block-sum scan of polr_build.hip): every first occurrence gets its code = the first occurrences
+// before it; the code goes to its slot, its row to row_of_code[code] (where the representative cells are taken from)
+__global__ __launch_bounds__(256) void polr_dict_rank_apply_kernel(DictTable t, const uint32_t *__restrict__ slot_of_row, uint64_t n,
+                                                                   const uint32_t *__restrict__ block_sums,
+                                                                   uint32_t *__restrict__ row_of_code) {
+	__shared__ uint32_t wave_sum[POLR_DICT_BLOCK / 64];
+	const uint32_t wave = threadIdx.x >> 6;
+	const uint64_t base = (uint64_t)blockIdx.x * POLR_DICT_BLOCK * POLR_DICT_ITEMS;
+	uint32_t run = block_sums[blockIdx.x];
+	for (uint32_t i = 0; i < POLR_DICT_ITEMS; i++) {
+		const uint64_t r = base + i * POLR_DICT_BLOCK + threadIdx.x;
+		const bool first = dict_is_first(t, slot_of_row, r, n);
+		const uint64_t firsts = __ballot(first);
+		if ((threadIdx.x & 63u) == 0) {
+			wave_sum[wave] = (uint32_t)__popcll(firsts);
+		}
+		__syncthreads();
+		uint32_t before = 0, all = 0;
+		for (uint32_t w = 0; w < POLR_DICT_BLOCK / 64; w++) {
+			before += w < wave ? wave_sum[w] : 0u;
+			all += wave_sum[w];
+		}
+		if (first) {
+			const uint32_t code = run + before + lane_rank(firsts);
+			t.code[slot_of_row[r]] = code;
+			row_of_code[code] = (uint32_t)r;
+		}
+		run += all;
+		__syncthreads(); // (wave_sum is written again in the next round)
+	}
+}
+
+// assign: the code column
+__global__ __launch_bounds__(256) void polr_dict_assign_kernel(DictTable t, const uint32_t *__restrict__ slot_of_row, uint64_t n,
+                                                               const uint32_t *__restrict__ scalars, uint32_t *__restrict__ codes) {
+	const uint32_t n_codes = scalars[DICT_N_CODES];
+	for (uint64_t r = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; r < n; r += (uint64_t)gridDim.x * blockDim.x) {
+		const uint32_t s = slot_of_row[r];
+		codes[r] = s == POLR_DICT_NO_SLOT ? n_codes : t.code[s];
+	}
+}
+
+// the representative cell of every code: the cell of its first occurrence
+__global__ __launch_bounds__(256) void polr_dict_reps_kernel(const uint4 *__restrict__ cells, const uint32_t *__restrict__ row_of_code,
+                                                             uint32_t n_codes, uint4 *__restrict__ reps) {
+	const uint32_t c = blockIdx.x * blockDim.x + threadIdx.x;
+	if (c < n_codes) {
+		reps[c] = cells[row_of_code[c]];
+	}
+}
+
+// the dictionary's strings as records {u32 length, bytes} at the offsets the host laid out
+__global__ __launch_bounds__(256) void polr_dict_records_kernel(const uint4 *__restrict__ reps, const uint64_t *__restrict__ offsets,
+                                                                uint32_t n_codes, uint8_t *__restrict__ arena, uint64_t arena_bytes) {
+	const uint32_t c = blockIdx.x * blockDim.x + threadIdx.x;
+	if (c >= n_codes) {
+		return;
+	}
+	const uint4 cell = reps[c];
+	const uint64_t off = offsets[c];
+	if (off > arena_bytes || arena_bytes - off < 4ull + cell.x) {
+		return; // (never past the arena, whatever the offsets say)
+	}
+	uint8_t *dst = arena + off;
+	for (uint32_t j = 0; j < 4; j++) {
+		dst[j] = (uint8_t)(cell.x >> (8u * j));
+	}
+	if (cell.x <= 12u) {
+		const uint32_t w[3] = {cell.y, cell.z, cell.w};
+		for (uint32_t j = 0; j < cell.x; j++) {
+			dst[4 + j] = (uint8_t)(w[j >> 2] >> (8u * (j & 3u)));
+		}
+	} else {
+		const uint8_t *p = (const uint8_t *)(((uint64_t)cell.w << 32) | cell.z);
+		for (uint32_t j = 0; j < cell.x; j++) {
+			dst[4 + j] = p[j];
+		}
+	}
+}
+
+static uint32_t dict_grid(uint64_t n, int n_cus) {
+	return (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>((n + 255) / 256, (uint64_t)n_cus * 8));
+}
+
+extern "C" int polr_ht_encode_dictionary(polr_ht *ht, uint32_t payload_col, void *stream, uint32_t *code_col, uint32_t *n_codes,
+                                         uint32_t *has_null) {
+	POLR_ENTRY();
+	if (!ht || !code_col || !n_codes || !has_null) {
+		return POLR_E_INVALID;
+	}
+	polr_ctx *ctx = ht->ctx;
+	if (ht->kind != KIND_NONE) {
+		// (a finalized perfect table keeps a re-ordered copy of every payload column, and the engines hold the column array)
+		POLR_FAIL(ctx, POLR_E_INVALID, "a payload column is dictionary-encoded before the table is finalized");
+	}
+	if (payload_col >= ht->n_payload) {
+		POLR_FAIL(ctx, POLR_E_INVALID, "payload column %u of %u", payload_col, ht->n_payload);
+	}
+	const OwnedCol src = ht->payload[payload_col];
+	if (src.width != 16) {
+		POLR_FAIL(ctx, POLR_E_INVALID, "a dictionary is made of a column of 16-byte string cells (this one: %u bytes)", src.width);
+	}
+	for (const DictCol &d : ht->dicts) {
+		if (d.src_col == payload_col) {
+			POLR_FAIL(ctx, POLR_E_INVALID, "payload column %u is encoded already (code column %u)", payload_col, d.code_col);
+		}
+	}
+	if (ht->n_payload >= 62) {
+		// (polr_ht_export / polr_ht_alloc_like describe at most 62 payload columns: no table is made that cannot be shipped)
+		POLR_FAIL(ctx, POLR_E_UNSUPPORTED, "the table has %u payload columns already: a code column would be the 63rd, more than "
+		                                   "polr_ht_export carries", ht->n_payload);
+	}
+	const uint64_t n = ht->n_rows_in;
+	if (n > (1ull << 30)) {
+		POLR_FAIL(ctx, POLR_E_UNSUPPORTED, "a dictionary over %llu build rows exceeds the 32-bit slot space", (unsigned long long)n);
+	}
+	HIPCHK(ctx, hipSetDevice(ctx->device));
+	hipStream_t st = polr_stream(ctx, stream);
+	if (st != ctx->stream) {
+		// (the column's cells were uploaded, and rebased onto their heap, on the context's stream)
+		HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+	}
+	const uint4 *cells = (const uint4 *)src.data;
+	const uint64_t capacity = [&] {
+		uint64_t c = 1024;
+		while (c < 2 * n) {
+			c <<= 1;
+		}
+		return c;
+	}();
+	const uint32_t n_blocks = (uint32_t)std::max<uint64_t>(1, (n + POLR_DICT_BLOCK * POLR_DICT_ITEMS - 1) / (POLR_DICT_BLOCK * POLR_DICT_ITEMS));
+	// one scratch allocation: the table, the per-row and per-block arrays, the scalars
+	const size_t b_rep = capacity * 16, b_hash = capacity * 8, b_state = capacity * 4, b_first = capacity * 4, b_code = capacity * 4,
+	             b_slot = (n * 4 + 15) & ~(size_t)15, b_roc = (n * 4 + 15) & ~(size_t)15, b_sums = ((size_t)n_blocks * 4 + 15) & ~(size_t)15,
+	             b_scalars = 64;
+	uint8_t *base = nullptr;
+	OwnedCol codes;
+	codes.width = 4;
+	codes.flags = 0;
+	codes.owned = true;
+	const uint64_t acct = std::max<uint64_t>(n * 4, 16); // (what polr_ht_export reports for a column)
+	HIPCHK(ctx, hipMalloc((void **)&codes.data, acct));
+	hipError_t e = hipMalloc((void **)&base, b_rep + b_hash + b_state + b_first + b_code + b_slot + b_roc + b_sums + b_scalars);
+	DictTable t;
+	memset(&t, 0, sizeof(t));
+	uint8_t *at = base;
+	t.rep = (uint4 *)at;
+	at += b_rep;
+	t.hash = (uint64_t *)at;
+	at += b_hash;
+	t.state = (uint32_t *)at;
+	at += b_state;
+	t.first_row = (uint32_t *)at;
+	at += b_first;
+	t.code = (uint32_t *)at;
+	at += b_code;
+	uint32_t *slot_of_row = (uint32_t *)at;
+	at += b_slot;
+	uint32_t *row_of_code = (uint32_t *)at;
+	at += b_roc;
+	uint32_t *block_sums = (uint32_t *)at;
+	at += b_sums;
+	uint32_t *scalars = (uint32_t *)at;
+	t.mask = capacity - 1;
+	uint32_t h_scalars[DICT_SCALARS] = {0, 0, 0, 0};
+	unsigned long long h_long = 0;
+	if (e == hipSuccess && n && src.owned && !src.strings_rebased) {
+		// the library uploaded the column and its heap never came: inline strings only, checked before a pointer is followed
+		unsigned long long *n_long = (unsigned long long *)(scalars + 8);
+		e = hipMemsetAsync(n_long, 0, 8, st);
+		if (e == hipSuccess) {
+			hipLaunchKernelGGL(polr_dict_count_long_kernel, dim3(dict_grid(n, ctx->n_cus)), dim3(256), 0, st, cells,
+			                   (const uint8_t *)src.valid, n, n_long);
+			e = hipMemcpyAsync(&h_long, n_long, 8, hipMemcpyDeviceToHost, st);
+			e = e == hipSuccess ? hipStreamSynchronize(st) : e;
+		}
+	}
+	if (e == hipSuccess && !h_long) {
+		e = hipMemsetAsync(scalars, 0, DICT_SCALARS * 4, st);
+	}
+	if (e == hipSuccess && !h_long && n) {
+		hipLaunchKernelGGL(polr_dict_init_kernel, dim3(dict_grid(capacity, ctx->n_cus)), dim3(256), 0, st, t);
+		hipLaunchKernelGGL(polr_dict_insert_kernel, dim3(dict_grid(n, ctx->n_cus)), dim3(256), 0, st, cells, (const uint8_t *)src.valid, n, t,
+		                   slot_of_row, scalars);
+		hipLaunchKernelGGL(polr_dict_rank_reduce_kernel, dim3(n_blocks), dim3(POLR_DICT_BLOCK), 0, st, t, (const uint32_t *)slot_of_row, n,
+		                   block_sums);
+		polr_launch_scan_blocksums(st, block_sums, n_blocks, &scalars[DICT_N_CODES]);
+		hipLaunchKernelGGL(polr_dict_rank_apply_kernel, dim3(n_blocks), dim3(POLR_DICT_BLOCK), 0, st, t, (const uint32_t *)slot_of_row, n,
+		                   (const uint32_t *)block_sums, row_of_code);
+		hipLaunchKernelGGL(polr_dict_assign_kernel, dim3(dict_grid(n, ctx->n_cus)), dim3(256), 0, st, t, (const uint32_t *)slot_of_row, n,
+		                   (const uint32_t *)scalars, (uint32_t *)codes.data);
+	}
+	if (e == hipSuccess && !h_long) { // the final count
+		e = hipMemcpyAsync(h_scalars, scalars, sizeof(h_scalars), hipMemcpyDeviceToHost, st);
+		e = e == hipSuccess ? hipStreamSynchronize(st) : e;
+	}
+	DictCol d;
+	d.src_col = payload_col;
+	d.code_col = ht->n_payload;
+	d.n_codes = h_scalars[DICT_N_CODES];
+	d.has_null = h_scalars[DICT_HAS_NULL];
+	const bool ok = e == hipSuccess && !h_long && !h_scalars[DICT_FULL];
+	if (ok && d.n_codes) {
+		e = hipMalloc((void **)&d.cells, (size_t)d.n_codes * 16);
+		if (e == hipSuccess) {
+			hipLaunchKernelGGL(polr_dict_reps_kernel, dim3((d.n_codes + 255) / 256), dim3(256), 0, st, cells, (const uint32_t *)row_of_code,
+			                   d.n_codes, d.cells);
+			e = hipStreamSynchronize(st);
+		}
+	}
+	if (base) {
+		hipFree(base);
+	}
+	if (!ok || e != hipSuccess) { // the table is exactly as it was
+		hipFree(codes.data);
+		if (d.cells) {
+			hipFree(d.cells);
+		}
+		if (e != hipSuccess) {
+			POLR_FAIL(ctx, POLR_E_HIP, "dictionary encoding failed: %s", hipGetErrorString(e));
+		}
+		if (h_long) {
+			POLR_FAIL(ctx, POLR_E_INVALID,
+			          "payload column %u: %llu build rows hold strings longer than 12 bytes, but the column's heap was never put on the "
+			          "device (polr_ht_set_payload_heaps)",
+			          payload_col, h_long);
+		}
+		POLR_FAIL(ctx, POLR_E_HIP, "dictionary encoding failed: the string table filled up");
+	}
+	// from here on an ordinary payload column: 4 bytes, unsigned, no validity array
+	ht->payload.push_back(codes);
+	ht->n_payload++;
+	ht->device_bytes += acct + (uint64_t)d.n_codes * 16;
+	ht->dicts.push_back(d);
+	*code_col = d.code_col;
+	*n_codes = d.n_codes;
+	*has_null = d.has_null;
+	return POLR_OK;
+}
+
+extern "C" int polr_ht_fetch_dictionary(polr_ht *ht, uint32_t code_col, void *stream, uint64_t *offsets, uint64_t n_offsets,
+                                        uint8_t *str_bytes, uint64_t str_cap, uint64_t *str_used) {
+	POLR_ENTRY();
+	if (!ht || !str_used || (!offsets && n_offsets) || (!str_bytes && str_cap)) {
+		return POLR_E_INVALID;
+	}
+	polr_ctx *ctx = ht->ctx;
+	const DictCol *d = nullptr;
+	for (const DictCol &x : ht->dicts) {
+		if (x.code_col == code_col) {
+			d = &x;
+		}
+	}
+	if (!d) {
+		// (also a table made by polr_ht_alloc_like / received by polr_bcast_build: it carries the codes, not the strings)
+		POLR_FAIL(ctx, POLR_E_INVALID, "payload column %u is not a code column whose dictionary this table holds", code_col);
+	}
+	*str_used = 0;
+	if (d->n_codes == 0) {
+		return POLR_OK;
+	}
+	HIPCHK(ctx, hipSetDevice(ctx->device));
+	hipStream_t st = polr_stream(ctx, stream);
+	std::vector<uint4> reps(d->n_codes);
+	HIPCHK(ctx, hipMemcpyAsync(reps.data(), d->cells, (size_t)d->n_codes * 16, hipMemcpyDeviceToHost, st));
+	HIPCHK(ctx, hipStreamSynchronize(st));
+	std::vector<uint64_t> offs(d->n_codes);
+	uint64_t used = 0;
+	for (uint32_t c = 0; c < d->n_codes; c++) {
+		offs[c] = used;
+		used += 4ull + reps[c].x;
+	}
+	*str_used = used;
+	if (used > str_cap || n_offsets < d->n_codes) { // (nothing was written: offsets and str_bytes are as they were)
+		POLR_FAIL(ctx, POLR_E_OVERFLOW, "the dictionary has %u strings in %llu bytes, the caller made room for %llu and %llu", d->n_codes,
+		          (unsigned long long)used, (unsigned long long)n_offsets, (unsigned long long)str_cap);
+	}
+	uint8_t *arena = nullptr;
+	uint64_t *d_offs = nullptr;
+	hipError_t e = hipMalloc((void **)&arena, used);
+	e = e == hipSuccess ? hipMalloc((void **)&d_offs, (size_t)d->n_codes * 8) : e;
+	e = e == hipSuccess ? hipMemcpyAsync(d_offs, offs.data(), (size_t)d->n_codes * 8, hipMemcpyHostToDevice, st) : e;
+	if (e == hipSuccess) {
+		hipLaunchKernelGGL(polr_dict_records_kernel, dim3((d->n_codes + 255) / 256), dim3(256), 0, st, (const uint4 *)d->cells,
+		                   (const uint64_t *)d_offs, d->n_codes, arena, used);
+		e = hipMemcpyAsync(str_bytes, arena, used, hipMemcpyDeviceToHost, st);
+		e = e == hipSuccess ? hipStreamSynchronize(st) : e;
+	}
+	if (arena) {
+		hipFree(arena);
+	}
+	if (d_offs) {
+		hipFree(d_offs);
+	}
+	if (e != hipSuccess) {
+		POLR_FAIL(ctx, POLR_E_HIP, "dictionary fetch failed: %s", hipGetErrorString(e));
+	}
+	memcpy(offsets, offs.data(), (size_t)d->n_codes * 8);
+	return POLR_OK;
+}

@@ -57,6 +57,14 @@ struct OwnedCol {
 	bool strings_rebased = false; // string cells point into a device heap (set_string_heaps): a second upload is refused
 };
 
+// the dictionary of a code column (polr_ht_encode_dictionary, polr_dict.hip): one representative string_t cell per code,
+// pointing into the heap the table owns
+struct DictCol {
+	uint32_t code_col = 0, src_col = 0; // payload columns: the codes, and the VARCHAR column they encode
+	uint32_t n_codes = 0, has_null = 0;
+	uint4 *cells = nullptr;             // device, [n_codes]
+};
+
 struct polr_ht {
 	polr_ctx *ctx = nullptr;
 	uint32_t n_keys = 0, n_payload = 0;
@@ -82,6 +90,7 @@ struct polr_ht {
 	uint32_t *idx_row = nullptr;
 	std::vector<OwnedCol> pcols;
 	std::vector<void *> heaps; // string heaps of VARCHAR payload columns (polr_ht_set_payload_heap), owned
+	std::vector<DictCol> dicts; // dictionaries of the code columns (polr_ht_encode_dictionary), cells owned
 	uint32_t is_dense = 0, has_null = 0;
 	uint64_t device_bytes = 0;
 };
@@ -246,6 +255,7 @@ void polr_launch_s16_build(hipStream_t st, const DevCol *keys_dev, uint32_t n_ke
                            uint4 *slots,
                            uint64_t capacity, uint32_t *slot_of_row, uint32_t *cursor, uint32_t *rowids,
                            uint32_t *block_sums, uint32_t *scalars, unsigned long long *n_valid);
+void polr_launch_scan_blocksums(hipStream_t st, uint32_t *block_sums, uint32_t n_blocks, uint32_t *total);
 void polr_launch_s16_scatter(hipStream_t st, uint64_t n_rows, const uint4 *slots, const uint32_t *slot_of_row,
                              uint32_t *cursor, uint32_t *rowids, uint32_t sentinel_start, uint32_t *sentinel_cursor);
 void polr_launch_s16_to_s8(hipStream_t st, const uint4 *slots, uint64_t capacity, const uint32_t *rowids, uint2 *s8);

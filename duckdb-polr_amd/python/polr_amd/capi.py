@@ -38,6 +38,7 @@ EXPORTS = [
     "polr_ht_set_payload_heap", "polr_pipeline_set_probe_heap", "polr_out_aggregate_string", "polr_ht_set_key_flags",
     "polr_out_fuse_grouped", "polr_out_fused_result", "polr_out_aggregate_hashed",
     "polr_ht_set_payload_heaps", "polr_pipeline_set_probe_heaps", "polr_out_aggregate_hashed_str", "polr_out_column_width",
+    "polr_ht_encode_dictionary", "polr_ht_fetch_dictionary",
 ]
 
 
@@ -204,6 +205,8 @@ def load():
     L.polr_out_aggregate_hashed.argtypes = [vp, vp, vp, u32, vp, u32, C.c_uint64, vp, vp, vp, vp]
     L.polr_out_column_width.argtypes = [vp, C.c_int32, u32, P(u32)]
     L.polr_out_aggregate_hashed_str.argtypes = [vp, vp, vp, u32, vp, u32, C.c_uint64, vp, vp, vp, vp, vp, C.c_uint64, vp]
+    L.polr_ht_encode_dictionary.argtypes = [vp, u32, vp, P(u32), P(u32), P(u32)]
+    L.polr_ht_fetch_dictionary.argtypes = [vp, u32, vp, vp, u64, vp, u64, P(u64)]
     L.polr_out_fused_result.argtypes = [vp, vp, vp, C.c_uint64, vp]
     L.polr_mpx_run_resident.argtypes = [vp, vp, vp, vp, u32, vp, u32]
     L.polr_mpx_run_resident_morsels.argtypes = [vp, vp, C.c_uint64, C.c_uint64, u32, u32, vp, u32]
@@ -360,6 +363,38 @@ class HashTable:
         L.polr_ht_set_payload_heaps.argtypes = [C.c_void_p, C.c_uint32, C.POINTER(HeapRange), C.c_uint32]
         self.ctx.check(L.polr_ht_set_payload_heaps(self.h, payload_col, _heap_ranges(blocks), len(blocks)))
         return self
+
+    def encode_dictionary(self, payload_col, stream=None):
+        """polr_ht_encode_dictionary (before finalize): VARCHAR payload column `payload_col` -> one more payload column of
+        4-byte codes, 0 .. n_codes - 1 in order of first appearance, NULL rows n_codes -> (code_col, n_codes, has_null)"""
+        col, n, null = C.c_uint32(), C.c_uint32(), C.c_uint32()
+        self.ctx.check(self.ctx.L.polr_ht_encode_dictionary(self.h, payload_col, stream, C.byref(col), C.byref(n),
+                                                            C.byref(null)))
+        self.__dict__.setdefault("_n_codes", {})[col.value] = n.value  # (dictionary() sizes its offsets by it)
+        return col.value, n.value, null.value
+
+    def dictionary(self, code_col, str_cap=4096, stream=None):
+        """polr_ht_fetch_dictionary: the strings of code column `code_col` (as encode_dictionary of this object returned
+        it), [bytes] indexed by code.  The byte arena is sized here (str_cap: a first guess) and the call repeated once
+        with the exact size when the guess was too small."""
+        n_codes = getattr(self, "_n_codes", {}).get(code_col, 0)  # (not encoded through this object: the call refuses)
+        used = C.c_uint64()
+        for attempt in (0, 1):
+            offs = np.zeros((max(n_codes, 1),), dtype=np.uint64)
+            arena = np.zeros((max(str_cap, 1),), dtype=np.uint8)
+            rc = self.ctx.L.polr_ht_fetch_dictionary(self.h, code_col, stream, offs.ctypes.data, n_codes, arena.ctypes.data,
+                                                     str_cap, C.byref(used))
+            if rc == E_OVERFLOW and attempt == 0 and used.value > str_cap:
+                str_cap = used.value
+                continue
+            self.ctx.check(rc)
+            break
+        raw = arena.tobytes()
+        out = []
+        for at in offs[:n_codes].tolist():
+            ln = int.from_bytes(raw[at:at + 4], "little")
+            out.append(raw[at + 4:at + 4 + ln])
+        return out
 
     @classmethod
     def from_rows(cls, ctx, rows, n_rows, row_width, col_offset, col_width, col_signed, n_keys, n_payload):
@@ -953,6 +988,12 @@ def string_payload_index(j, col):
     return len(j["payload"]) + list(j.get("strings", {}).keys()).index(col)
 
 
+def dictionary_payload_index(j, col):
+    """(payload column number of the code column of VARCHAR column `col` of workload join `j`, (n_codes, has_null)) as
+    build_joins made it for j["dictionary"]"""
+    return j["dictionary_cols"][col]
+
+
 def build_joins(ctx, wl, auto=False):
     """upload + finalize the build sides of a workload dict.  auto=False: the way the reference's planner would
     (perfect table where the plan allows it and the build has no duplicate, hash table otherwise);
@@ -970,6 +1011,13 @@ def build_joins(ctx, wl, auto=False):
                                     payload_valid=pv + [j.get("strings_valid", {}).get(n) for n in j.get("strings", {})])
         for i, (_c, heap) in enumerate(strs):
             ht.set_payload_heap(len(j["payload"]) + i, heap)
+        # j["dictionary"]: names of j["strings"] columns to dictionary-encode (HashTable.encode_dictionary: one code column
+        # each, behind all the others; dictionary_payload_index gives its column number and (n_codes, has_null))
+        if j.get("dictionary"):
+            j["dictionary_cols"] = {}
+            for col in j["dictionary"]:
+                code_col, n_codes, has_null = ht.encode_dictionary(string_payload_index(j, col))
+                j["dictionary_cols"][col] = (code_col, (n_codes, has_null))
         # j["key_flags"]: per key column KEY_BY_VALUE (the probe side reads another integer type: a CAST'ed key) and / or
         # KEY_NULL_EQUAL (IS NOT DISTINCT FROM)
         for c, f in enumerate(j.get("key_flags", [])):

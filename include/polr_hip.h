@@ -381,8 +381,9 @@ int polr_out_aggregate_hashed(polr_out *o, void *stream, const polr_group_key *c
  * the caller's device memory (POLR_COL_DEVICE: its cells point into HBM by contract).  For a column the library uploaded
  * whose heap it never got, the call first counts the non-NULL cells longer than 12 bytes among the output rows (reading
  * their length word and nothing else); any such cell: POLR_E_INVALID, before a kernel that follows a pointer is enqueued.
- * All-inline columns need no heap.  MIN / MAX of a VARCHAR per group, and VARCHAR columns in polr_out_aggregate_grouped and
- * polr_out_fuse_grouped, are not provided. */
+ * All-inline columns need no heap.  MIN / MAX of a VARCHAR per group is not provided.  polr_out_aggregate_grouped and
+ * polr_out_fuse_grouped take a VARCHAR column of a BUILD side through its code column (polr_ht_encode_dictionary below);
+ * probe-side VARCHAR group columns stay with this sink. */
 int polr_out_aggregate_hashed_str(polr_out *o, void *stream, const polr_group_key *cols, uint32_t n_cols,
                                   const polr_agg_spec *specs, uint32_t n_aggs, uint64_t max_groups, int64_t *group_keys,
                                   uint32_t *group_nulls, polr_agg_value *results, uint64_t *n_groups, uint8_t *str_bytes,
@@ -428,6 +429,45 @@ int polr_ht_set_payload_heaps(polr_ht *ht, uint32_t payload_col, const polr_heap
 int polr_pipeline_set_probe_heaps(polr_pipeline *p, uint32_t probe_col, const polr_heap_range *ranges, uint32_t n_ranges);
 int polr_ht_set_payload_heap(polr_ht *ht, uint32_t payload_col, const void *heap_base, uint64_t heap_bytes);
 int polr_pipeline_set_probe_heap(polr_pipeline *p, uint32_t probe_col, const void *heap_base, uint64_t heap_bytes);
+/* ---- dictionary codes for VARCHAR build columns (SSB: every grouped query groups by a VARCHAR of a dimension table --
+ * c_nation, s_nation, c_city, s_city, p_brand) -----------------------------------------------------------------------
+ * A group column that is a payload column of a build side has at most as many distinct values as the build side has
+ * rows, and the build side is uploaded once.  polr_ht_encode_dictionary encodes VARCHAR payload column `payload_col` of a
+ * table that is NOT YET FINALIZED once per build row, on the device, into dense codes, and appends ONE payload column to
+ * the table: index *code_col = the table's payload count before the call, 4 bytes wide, unsigned, no validity array.  From
+ * then on it is an ordinary payload column for every consumer -- polr_ht_export / polr_ht_alloc_like, finalize (a perfect
+ * table re-orders it with the others), polr_out_materialize, polr_out_column_width (4), join conditions and all sinks:
+ * polr_out_aggregate_grouped and polr_out_fuse_grouped group by the strings of a build side through it, with a domain that
+ * is tight by construction, and the probe side reads one 4-byte cell per surviving tuple.
+ *  - Two rows get the same code iff their strings are equal as for polr_out_aggregate_hashed_str: same length, same bytes;
+ *    the padding of an inline cell and the heap address play no part.
+ *  - Codes are deterministic: the code of a value is the number of distinct non-NULL values whose first occurrence (lowest
+ *    build row, rows as uploaded) comes before its own -- 0 .. *n_codes - 1 in order of first appearance.  Rows whose KEY is
+ *    NULL are encoded like any other.
+ *  - A NULL row (column validity 0) gets code *n_codes; its cell is never read.  *has_null = 1 iff there is one.  So
+ *    n_values = *n_codes + *has_null makes NULL a group of its own (GROUP BY), n_values = *n_codes leaves NULL rows to
+ *    *n_dropped of polr_out_aggregate_grouped.
+ *  - Refusals, each leaving the table exactly as it was (payload count included): a finalized table (as for
+ *    polr_ht_set_payload_heaps), a column that is not 16 bytes wide, a column that is encoded already: POLR_E_INVALID; a
+ *    column the library uploaded whose heap never came and that holds a non-NULL cell longer than 12 bytes: POLR_E_INVALID,
+ *    found by a pass over the build rows that reads length words only, before any kernel follows a pointer (set the heap,
+ *    then encode).  A table that has 62 payload columns already: POLR_E_UNSUPPORTED (polr_ht_export carries 62).  A table
+ *    of 0 rows encodes to *n_codes = 0.
+ *  - `stream` as for polr_ht_finalize_*; the call waits for the context's own stream first (uploads and heaps went there)
+ *    and returns after the codes are complete.  While it runs it holds scratch memory of 36 bytes per slot of a string
+ *    table of 2 to 4 slots per build row, plus 8 bytes per build row -- up to about 150 bytes per build row, freed before
+ *    it returns: sized for dimension tables; POLR_E_HIP (table untouched) when the device cannot give that much.
+ * The table keeps one representative string_t cell per code (pointing into the heap it owns); polr_ht_fetch_dictionary
+ * reads them: offsets[c] = byte offset in str_bytes of the record {uint32 length (little endian), bytes} of code c,
+ * c < n_codes; *str_used = the bytes the records take.  str_cap < *str_used or n_offsets < n_codes: POLR_E_OVERFLOW with
+ * *str_used exact and offsets / str_bytes untouched -- one retry with *str_used succeeds.  POLR_E_INVALID for a column that
+ * is not a code column of this table, a table that was never encoded, and a table made by polr_ht_alloc_like / received
+ * by polr_bcast_build (they carry the codes, not the strings: the rank that built the table holds the dictionary).
+ * Not provided: sorted (lexicographic) codes; dictionaries of probe-side columns. */
+int polr_ht_encode_dictionary(polr_ht *ht, uint32_t payload_col, void *stream, uint32_t *code_col, uint32_t *n_codes,
+                              uint32_t *has_null);
+int polr_ht_fetch_dictionary(polr_ht *ht, uint32_t code_col, void *stream, uint64_t *offsets, uint64_t n_offsets,
+                             uint8_t *str_bytes, uint64_t str_cap, uint64_t *str_used);
 /* MIN / MAX (fn = POLR_AGG_MIN / POLR_AGG_MAX) of a VARCHAR column over the pipeline's output rows, reduced on the
  * device (src/function/aggregate/distributive/minmax.cpp over string_t: bytes compared as unsigned, a proper prefix
  * sorts first; NULLs take no part).  The winning string's bytes go to dst (at most dst_cap of them), *len = its whole
