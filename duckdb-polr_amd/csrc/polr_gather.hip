@@ -135,8 +135,9 @@ hipError_t polr_launch_poolg_kernelx(uint32_t W, uint32_t k, uint32_t n_blocks, 
 #define DECL_POOL_K(KK)                                                                                                \
 	size_t polr_pool_flat_lds_bytes_k##KK(uint32_t waves_per_block, uint32_t table_dwords);                           \
 	size_t polr_pool_flat_wave_bytes_k##KK();                                                                         \
-	int polr_pool_flat_occupancy_k##KK(uint32_t waves_per_block, uint32_t table_dwords);                              \
-	int polr_pool_flat_occupancy_e_k##KK(uint32_t waves_per_block, uint32_t table_dwords);                            \
+	uint32_t polr_pool_flat_router_areas_k##KK(uint32_t waves_per_block, uint32_t table_dwords);                      \
+	int polr_pool_flat_occupancy_k##KK(uint32_t waves_per_block, uint32_t table_dwords, uint32_t fused_words);        \
+	int polr_pool_flat_occupancy_e_k##KK(uint32_t waves_per_block, uint32_t table_dwords, uint32_t fused_words);      \
 	hipError_t polr_launch_pool_flat_kernel_k##KK(uint32_t n_blocks, uint32_t waves_per_block, uint32_t table_dwords, \
 	                                              hipStream_t stream, const DevPipeline *pipe,                        \
 	                                              const ResidentExec *execs, PoolRun *run, DevOut out,                \
@@ -244,13 +245,19 @@ extern "C++" size_t polr_pool_flat_wave_bytes(uint32_t k) {
 	            polr_pool_flat_wave_bytes_k8())
 }
 
-extern "C++" int polr_pool_flat_occupancy(uint32_t k, uint32_t wpb, uint32_t table_dwords, bool emit) {
+extern "C++" uint32_t polr_pool_flat_router_areas(uint32_t k, uint32_t wpb, uint32_t table_dwords) {
+	POOL_SWITCH(k, polr_pool_flat_router_areas_k2(wpb, table_dwords), polr_pool_flat_router_areas_k4(wpb, table_dwords),
+	            polr_pool_flat_router_areas_k6(wpb, table_dwords), polr_pool_flat_router_areas_k8(wpb, table_dwords))
+}
+
+extern "C++" int polr_pool_flat_occupancy(uint32_t k, uint32_t wpb, uint32_t table_dwords, bool emit, uint32_t fused_words) {
+	const uint32_t fw = fused_words;
 	if (emit) {
-		POOL_SWITCH(k, polr_pool_flat_occupancy_e_k2(wpb, table_dwords), polr_pool_flat_occupancy_e_k4(wpb, table_dwords),
-		            polr_pool_flat_occupancy_e_k6(wpb, table_dwords), polr_pool_flat_occupancy_e_k8(wpb, table_dwords))
+		POOL_SWITCH(k, polr_pool_flat_occupancy_e_k2(wpb, table_dwords, fw), polr_pool_flat_occupancy_e_k4(wpb, table_dwords, fw),
+		            polr_pool_flat_occupancy_e_k6(wpb, table_dwords, fw), polr_pool_flat_occupancy_e_k8(wpb, table_dwords, fw))
 	}
-	POOL_SWITCH(k, polr_pool_flat_occupancy_k2(wpb, table_dwords), polr_pool_flat_occupancy_k4(wpb, table_dwords),
-	            polr_pool_flat_occupancy_k6(wpb, table_dwords), polr_pool_flat_occupancy_k8(wpb, table_dwords))
+	POOL_SWITCH(k, polr_pool_flat_occupancy_k2(wpb, table_dwords, fw), polr_pool_flat_occupancy_k4(wpb, table_dwords, fw),
+	            polr_pool_flat_occupancy_k6(wpb, table_dwords, fw), polr_pool_flat_occupancy_k8(wpb, table_dwords, fw))
 }
 
 // emit: the run may write row ids (the build of the flat kernel that carries that code)

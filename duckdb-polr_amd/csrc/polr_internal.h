@@ -237,7 +237,10 @@ hipError_t polr_launch_pool_kernel(uint32_t W, uint32_t k, uint32_t n_blocks, hi
                                    const ResidentExec *execs, PoolRun *run, DevOut out, bool ext);
 size_t polr_pool_flat_lds_bytes(uint32_t k, uint32_t waves_per_block, uint32_t table_dwords);
 size_t polr_pool_flat_wave_bytes(uint32_t k);
-int polr_pool_flat_occupancy(uint32_t k, uint32_t waves_per_block, uint32_t table_dwords, bool emit);
+// routers a probe workgroup of the flat kernel can host in its own LDS (0: only router workgroups)
+uint32_t polr_pool_flat_router_areas(uint32_t k, uint32_t waves_per_block, uint32_t table_dwords);
+// fused_words: 8-byte cells of a fused sink the launch keeps in LDS (the occupancy of the launch as it is made)
+int polr_pool_flat_occupancy(uint32_t k, uint32_t waves_per_block, uint32_t table_dwords, bool emit, uint32_t fused_words = 0);
 hipError_t polr_launch_pool_flat_kernel(uint32_t k, uint32_t n_blocks, uint32_t waves_per_block, uint32_t table_dwords,
                                         hipStream_t stream, const DevPipeline *pipe, const ResidentExec *execs,
                                         PoolRun *run, DevOut out, bool emit, uint32_t fused_words);

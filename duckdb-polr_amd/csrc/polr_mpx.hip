@@ -615,7 +615,18 @@ static int run_resident_impl(polr_mpx **ms, void *stream, const uint64_t *chunk_
 	const DevPipeline &dp = (materialize && !flat) ? p->host_mat : p->host_count;
 	const uint32_t wq = dp.W + (dp.mult ? 1u : 0u); // slots per queued tuple: ids (+ multiplicity)
 	const uint32_t wpb = flat ? p->flat_wpb : polr_pool_waves_per_block(dp.k, wq);
-	int occ = wpb == 0 ? 0 : (flat ? polr_pool_flat_occupancy(dp.k, wpb, dp.lds_table_dwords, materialize) : polr_pool_occupancy(dp.k, wq, dp.ext != 0));
+	// a fused GROUP BY sink keeps its cells in the workgroup's LDS when they fit behind the bit tables, the queues and
+	// the router areas (160 KB per workgroup), else in its table in global memory.  (Decided BEFORE the grid is sized:
+	// the workgroups per CU are those of the launch as it is made -- a workgroup that is not co-resident would take
+	// its routers' executors with it.)
+	uint32_t fused_words = 0;
+	if (flat && wpb && out && out->fused_dev) {
+		const uint64_t words = (uint64_t)out->fused_groups * (1u + 2u * out->fused_aggs);
+		if (polr_pool_flat_lds_bytes(dp.k, wpb, dp.lds_table_dwords) + 8 + words * 8 <= 160u * 1024u) {
+			fused_words = (uint32_t)words;
+		}
+	}
+	int occ = wpb == 0 ? 0 : (flat ? polr_pool_flat_occupancy(dp.k, wpb, dp.lds_table_dwords, materialize, fused_words) : polr_pool_occupancy(dp.k, wq, dp.ext != 0));
 	if (occ < 1) {
 		POLR_FAIL(ctx, POLR_E_UNSUPPORTED, "pool kernel does not fit on a CU (per-wave LDS queues: too many joins x carried ids)");
 	}
@@ -627,14 +638,19 @@ static int run_resident_impl(polr_mpx **ms, void *stream, const uint64_t *chunk_
 	if (share > 16) {
 		POLR_FAIL(ctx, POLR_E_INVALID, "device share 1/%u: at most 16 runs side by side", share);
 	}
-	// grid: router workgroups first (one wave per executor), then the pool; never more than is co-resident
+	// grid: never more than is co-resident.  Mixed layout (flat kernel, whose workgroup owns its CU): every workgroup
+	// probes and hosts the routers of executors b, b + n_blocks, .. in its first waves -- as long as the router areas of
+	// the workgroups (polr_pool_flat_router_areas, never all waves) can host all executors.  Else the separate layout:
+	// router workgroups first (one wave per executor), then the pool.  (The generic kernel runs two workgroups per CU
+	// with its LDS nearly used up: router areas there would cost the second workgroup; it keeps router workgroups.)
 	const uint32_t capacity = std::max<uint32_t>((uint32_t)ctx->n_cus * (uint32_t)occ / share, 2u);
-	const uint32_t n_router_blocks = (n + wpb - 1) / wpb;
+	const uint32_t router_areas = flat ? std::min<uint32_t>(polr_pool_flat_router_areas(dp.k, wpb, dp.lds_table_dwords), wpb - 1u) : 0u;
+	const bool mixed = (uint64_t)n <= (uint64_t)capacity * router_areas;
+	const uint32_t n_router_blocks = mixed ? 0u : (n + wpb - 1) / wpb;
 	if (n_router_blocks + 1 > capacity) {
 		POLR_FAIL(ctx, POLR_E_UNSUPPORTED, "%u executors do not fit on the device at once", n);
 	}
 	const uint32_t n_blocks = capacity;
-	const uint32_t n_workers = n_blocks - n_router_blocks;
 	for (uint32_t i = 0; i < n; i++) {
 		// (work still queued on `st` needs no host synchronisation: everything a run touches is ordered by the
 		// stream -- consecutive passes can be enqueued back to back)
@@ -654,7 +670,7 @@ static int run_resident_impl(polr_mpx **ms, void *stream, const uint64_t *chunk_
 	}
 	// unit rings: sized for everything the executors of this run can have in flight (two slots each) plus the EXIT
 	// entries, with a factor of two to spare
-	const uint32_t pool_waves = n_workers * wpb;
+	const uint32_t pool_waves = mixed ? n_blocks * wpb - n : (n_blocks - n_router_blocks) * wpb;
 	// Rings in use: every ring must have probe waves that serve it.  Ring capacity: a round of U units leaves at most
 	// U / R + 1 entries on a ring; the executors that have rounds in flight (a of them, at most POLR_SLOTS rounds each) published them
 	// when at least a executors were still routing, so all their lo units together are at most POLR_SLOTS x (4 x pool_waves + 17 a);
@@ -725,6 +741,8 @@ static int run_resident_impl(polr_mpx **ms, void *stream, const uint64_t *chunk_
 	hr->sync = m0->pool_dev;
 	hr->n_exec = n;
 	hr->n_router_blocks = n_router_blocks;
+	hr->routers_per_block = mixed ? n / n_blocks : 0u;
+	hr->routers_rem = mixed ? n % n_blocks : 0u;
 	hr->n_rings = n_rings;
 	{
 		const polr_pool_tuning &tn = ctx->tuning; // (polr_ctx_set_pool_tuning; 0 = default)
@@ -836,15 +854,6 @@ static int run_resident_impl(polr_mpx **ms, void *stream, const uint64_t *chunk_
 		HIPCHK(ctx, hipEventRecord(m0->ev_start[ev], st));
 	}
 	const ResidentExec *execs_dev = (const ResidentExec *)(m0->execs_dev + POOL_HEADER_BYTES);
-	// a fused GROUP BY sink keeps its cells in the workgroup's LDS when they fit behind the bit tables and the queues
-	// (160 KB per workgroup), else in its table in global memory
-	uint32_t fused_words = 0;
-	if (flat && out && out->fused_dev) {
-		const uint64_t words = (uint64_t)out->fused_groups * (1u + 2u * out->fused_aggs);
-		if (polr_pool_flat_lds_bytes(dp.k, wpb, dp.lds_table_dwords) + 8 + words * 8 <= 160u * 1024u) {
-			fused_words = (uint32_t)words;
-		}
-	}
 	hipError_t e =
 	    flat ? polr_launch_pool_flat_kernel(dp.k, n_blocks, wpb, dp.lds_table_dwords, st, p->dev_count, execs_dev,
 	                                        (PoolRun *)m0->execs_dev, dout, materialize, fused_words)

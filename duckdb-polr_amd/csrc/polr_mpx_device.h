@@ -323,7 +323,9 @@ struct ResidentExec {
 };
 
 #define POLR_RES_HOT_DWORDS (offsetof(DevMpx, stage_out) / 4)
-#define POLR_RES_ROUTER_DWORDS (POLR_RES_HOT_DWORDS + 32)
+// behind the hot state: the round being decided and, for a pool router, what it carries from step to step
+// (polr_pool_device.h: POOL_RT_*)
+#define POLR_RES_ROUTER_DWORDS (POLR_RES_HOT_DWORDS + 48)
 
 // PushFinalize's closing FinalizePathRun (polar_pipeline_executor.cpp:150-151); lane 0 of the caller,
 // counters already absorbed.  m: the state being worked on (LDS copy or HBM)
@@ -406,7 +408,9 @@ __device__ __forceinline__ void polr_offs_cache_fill(OffsCache &oc, const Reside
 //                                     current one (FirstUninitialised, :94-180 / :198-252),
 // and the tuple count is min(init_tuple_count, rest of the chunk) (:84-92, :182-196, :254-265) -- none of which
 // reads a reward.  ALTERNATE cycles through the paths per chunk (:440-452).  Everything else: no.
-__device__ __forceinline__ bool polr_can_speculate(const volatile polr::MultiplexerCore &core) {
+// (Core: a volatile polr::MultiplexerCore, in whatever address space the caller keeps it)
+template <class Core>
+__device__ __forceinline__ bool polr_can_speculate(const Core &core) {
 	if (core.num_cache_flushing_skips != 0) {
 		return false; // a routing window is open
 	}

@@ -1,10 +1,12 @@
 // duckdb-polr_amd/csrc/polr_pool.hip -- the whole run in ONE launch (gfx950): routers + a pool of probe waves; the
 // FLAT pipeline's kernel (the generic pipeline's: polr_poolg.hip).
 //
-// Grid: the first `n_router_blocks` workgroups host the routers (one WAVE per executor: the multiplexer of
-// src/execution/operator/polr/physical_multiplexer.cpp:100-184 with its RoutingStrategy, state in LDS for the whole
-// run); every other workgroup is part of the probe pool.  Protocol: polr_pool_device.h.  One kernel per compiled
-// stage count K (-DPOLR_K):
+// Grid: one WAVE per executor routes (the multiplexer of src/execution/operator/polr/physical_multiplexer.cpp:100-184
+// with its RoutingStrategy, state in LDS for the whole run), every other wave is part of the probe pool.  A workgroup
+// of this kernel owns its CU, so the routers sit INSIDE the probe workgroups, one or two in each (the mixed layout,
+// pool_role): every CU issues probe requests.  Executor counts the workgroups' router areas cannot host take the
+// separate layout -- the first `n_router_blocks` workgroups are routers only.  Protocol: polr_pool_device.h.  One
+// kernel per compiled stage count K (-DPOLR_K):
 //   polr_pool_flat_kernel<K>     the flat pipeline of polr_flat_device.h (counting runs over banks of single-key,
 //                                unique-match joins on probe columns), up to 1024-thread workgroups that share the
 //                                LDS-resident bit tables.
@@ -32,6 +34,22 @@
 POOL_DIAG_ENTRY(PASTE_TL(polr_diag_router_k, POLR_K), PASTE_TL(polr_diag_timeline_set_k, POLR_K))
 #endif
 
+#if POLR_FLAT_EMIT
+// every wave of the workgroup has left its loop (probe waves: EXIT; routers: finished): flush the cells of the fused
+// sink that were touched to the workgroup's table.  Called by ALL waves of the workgroup.
+__device__ __forceinline__ void flat_fused_flush(const DevOut &out, POLR_LDS unsigned long long *fused_lds, uint32_t fused_words) {
+	__syncthreads();
+	const FusedSink *f = out.fused;
+	unsigned long long *table = f->cells + (size_t)(blockIdx.x % f->n_tables) * f->words_per_table;
+	for (uint32_t i = threadIdx.x; i < fused_words; i += blockDim.x) {
+		const unsigned long long v = fused_lds[i];
+		if (v) {
+			__hip_atomic_fetch_add(&table[i], v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+		}
+	}
+}
+#endif
+
 // (EMIT only tells the two builds' kernels apart by name: what differs is compiled in or out by POLR_FLAT_EMIT)
 template <int K, int EMIT>
 __global__ __launch_bounds__(1024) void polr_pool_flat_kernel(const DevPipeline *__restrict__ pipe,
@@ -43,20 +61,22 @@ __global__ __launch_bounds__(1024) void polr_pool_flat_kernel(const DevPipeline 
 	const uint32_t k = uni(pipe->k);
 	PoolRun rh;
 	pool_load_run(run, rh);
-	if (blockIdx.x < rh.n_router_blocks) {
-		pool_router_wave(execs, run, rh, k, FLAT_STEP0, lds, router_dwords);
-		return;
-	}
+	const PoolRole role = pool_role(rh);
+	const bool router_block = blockIdx.x < rh.n_router_blocks; // (the separate layout: nothing but routers here)
 #if POLR_FLAT_EMIT
 	// a fused GROUP BY sink whose cells fit: this workgroup's cells start from zero (published by the barrier below)
+	if (router_block) {
+		fused_words = 0;
+	}
 	POLR_LDS unsigned long long *fused_lds = fused_words ? as_lds((unsigned long long *)(lds + fused_off)) : nullptr;
 	for (uint32_t i = threadIdx.x; i < fused_words; i += blockDim.x) {
 		fused_lds[i] = 0ull;
 	}
 #endif
-	// the bit tables that fit stay in LDS for the whole run: one cooperative copy per workgroup
+	// the bit tables that fit stay in LDS for the whole run: one cooperative copy per workgroup.  Router waves of a
+	// probe workgroup take part in it and in its barrier.
 	{
-		const uint32_t n_tab = uni(pipe->n_lds_tables);
+		const uint32_t n_tab = router_block ? 0u : uni(pipe->n_lds_tables);
 		for (uint32_t t = 0; t < n_tab; t++) {
 			const uint32_t *src = uniptr(pipe->lds_table_src[t]);
 			const uint32_t off = uni(pipe->lds_table_off[t]);
@@ -67,10 +87,23 @@ __global__ __launch_bounds__(1024) void polr_pool_flat_kernel(const DevPipeline 
 		}
 		__syncthreads();
 	}
+	if (role.router) {
+		// a router of a probe workgroup: its area lies behind the probe queues of all waves; of a router workgroup:
+		// wave r uses [r * router_dwords, (r + 1) * router_dwords)
+		const uint32_t area = router_block ? router_dwords : POOL_ROUTER_MIN_DWORDS;
+		uint32_t *base = lds + (router_block ? 0u : table_dwords + (blockDim.x >> 6) * lds_per_wave) + role.router_index * area;
+		pool_router_wave(execs, run, rh, role.exec, k, FLAT_STEP0, base, area);
+#if POLR_FLAT_EMIT
+		if (fused_words) {
+			flat_fused_flush(out, fused_lds, fused_words); // (with the probe waves: there is a barrier in it)
+		}
+#endif
+		return;
+	}
 	// probe wave g of the pool serves ring g % n_rings (dealt wave by wave, not workgroup by workgroup: the units of a
 	// round go to all rings alike, so every ring needs the same number of waves -- 240 workgroups over 64 rings left a
 	// quarter of the rings with 3 workgroups instead of 4, and every round waited for those)
-	const uint32_t pool_wave = (blockIdx.x - rh.n_router_blocks) * (blockDim.x >> 6) + wave_in_block;
+	const uint32_t pool_wave = role.pool_wave;
 	const uint32_t ring = pool_wave & (rh.n_rings - 1u);
 	FlatCtx<K> c;
 	c.k = k;
@@ -103,7 +136,7 @@ __global__ __launch_bounds__(1024) void polr_pool_flat_kernel(const DevPipeline 
 	PoolPoller pp;
 	polr_pool_poller_init(pp, run, rh.sync, ring, rh.lo_cap, rh.hi_cap, pool_wave / rh.n_rings, rh.hi_lottery, rh.idle_sleep,
 	                      rh.timeout_ticks);
-	TL_BEGIN(rh.n_router_blocks)
+	TL_BEGIN(pool_wave)
 	bool have = polr_pool_next_unit(pp, u, c.lane);
 	while (have) {
 		TL_GOT
@@ -148,16 +181,7 @@ __global__ __launch_bounds__(1024) void polr_pool_flat_kernel(const DevPipeline 
 #if POLR_FLAT_EMIT
 	out_close(out, c.os, c.lane);
 	if (fused_words) {
-		// every wave of the workgroup has left its loop: flush the cells that were touched to the workgroup's table
-		__syncthreads();
-		const FusedSink *f = out.fused;
-		unsigned long long *table = f->cells + (size_t)(blockIdx.x % f->n_tables) * f->words_per_table;
-		for (uint32_t i = threadIdx.x; i < fused_words; i += blockDim.x) {
-			const unsigned long long v = fused_lds[i];
-			if (v) {
-				__hip_atomic_fetch_add(&table[i], v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-			}
-		}
+		flat_fused_flush(out, fused_lds, fused_words);
 	}
 #endif
 }
@@ -170,12 +194,26 @@ static size_t pool_flat_wave_dwords() {
 	return (size_t)flat_per_wave_dwords<POLR_K>();
 }
 
-// dynamic LDS of the flat kernel in dwords: tables + probe queues, never less than its router waves need (router
-// wave r of a router workgroup uses [r * stride, (r + 1) * stride) with stride = total / waves)
+// dynamic LDS of the flat kernel in dwords: tables + probe queues + the router areas of a probe workgroup (up to
+// POOL_ROUTER_RESERVE, as many as fit: a function of the pipeline alone, not of the executors of a run), never less
+// than a router workgroup's waves need (router wave r of a router workgroup uses [r * stride, (r + 1) * stride) with
+// stride = total / waves).  How many routers a probe workgroup can host follows from it: polr_pool_flat_router_areas.
 static size_t pool_flat_lds_dwords(uint32_t waves_per_block, uint32_t table_dwords) {
 	const size_t probe = table_dwords + pool_flat_wave_dwords() * waves_per_block;
+	const size_t room = probe < POOL_LDS_DWORDS_MAX ? (POOL_LDS_DWORDS_MAX - probe) / POOL_ROUTER_MIN_DWORDS : 0;
+	const size_t mixed = probe + (size_t)POOL_ROUTER_MIN_DWORDS * (room < POOL_ROUTER_RESERVE ? room : POOL_ROUTER_RESERVE);
 	const size_t router = (size_t)POOL_ROUTER_MIN_DWORDS * waves_per_block;
-	return probe > router ? probe : router;
+	return mixed > router ? mixed : router;
+}
+
+// the launch's LDS in bytes, a fused sink's cells (fused_words 8-byte words behind everything else) included
+static size_t pool_flat_launch_lds(uint32_t waves_per_block, uint32_t table_dwords, uint32_t fused_words, uint32_t *fused_off) {
+	const size_t dwords = pool_flat_lds_dwords(waves_per_block, table_dwords);
+	const uint32_t off = (uint32_t)((dwords + 1) & ~(size_t)1);
+	if (fused_off) {
+		*fused_off = off;
+	}
+	return (fused_words ? (size_t)off + 2 * (size_t)fused_words : dwords) * sizeof(uint32_t);
 }
 
 static hipError_t pool_flat_prepare(size_t lds) {
@@ -206,10 +244,18 @@ extern "C++" size_t PASTE(polr_pool_flat_lds_bytes_k, POLR_K)(uint32_t waves_per
 extern "C++" size_t PASTE(polr_pool_flat_wave_bytes_k, POLR_K)() {
 	return pool_flat_wave_dwords() * sizeof(uint32_t);
 }
+
+// routers a probe workgroup can host (the mixed layout): the areas behind its probe queues
+extern "C++" uint32_t PASTE(polr_pool_flat_router_areas_k, POLR_K)(uint32_t waves_per_block, uint32_t table_dwords) {
+	const size_t probe = table_dwords + pool_flat_wave_dwords() * waves_per_block;
+	const size_t areas = (pool_flat_lds_dwords(waves_per_block, table_dwords) - probe) / POOL_ROUTER_MIN_DWORDS;
+	return (uint32_t)(areas < POOL_ROUTER_RESERVE ? areas : POOL_ROUTER_RESERVE);
+}
 #endif
 
-extern "C++" int FLAT_EXPORT(polr_pool_flat_occupancy_)(uint32_t waves_per_block, uint32_t table_dwords) {
-	const size_t lds = pool_flat_lds_dwords(waves_per_block, table_dwords) * sizeof(uint32_t);
+// (fused_words: as for the launch -- the workgroups per CU of the launch as it will be made)
+extern "C++" int FLAT_EXPORT(polr_pool_flat_occupancy_)(uint32_t waves_per_block, uint32_t table_dwords, uint32_t fused_words) {
+	const size_t lds = pool_flat_launch_lds(waves_per_block, table_dwords, fused_words, nullptr);
 	int blocks = 0;
 	if (pool_flat_prepare(lds) != hipSuccess ||
 	    hipOccupancyMaxActiveBlocksPerMultiprocessor(&blocks, (const void *)polr_pool_flat_kernel<POLR_K, POLR_FLAT_EMIT>,
@@ -225,8 +271,8 @@ extern "C++" hipError_t FLAT_EXPORT(polr_launch_pool_flat_kernel_)(uint32_t n_bl
                                                                       PoolRun *run, DevOut out, uint32_t fused_words) {
 	// (fused_words: 64-bit group cells of a fused GROUP BY sink to keep in LDS behind everything else; 0: none)
 	const size_t dwords = pool_flat_lds_dwords(waves_per_block, table_dwords);
-	const uint32_t fused_off = (uint32_t)((dwords + 1) & ~(size_t)1);
-	const size_t lds = (fused_words ? (size_t)fused_off + 2 * (size_t)fused_words : dwords) * sizeof(uint32_t);
+	uint32_t fused_off = 0;
+	const size_t lds = pool_flat_launch_lds(waves_per_block, table_dwords, fused_words, &fused_off);
 	hipError_t e = pool_flat_prepare(lds);
 	if (e != hipSuccess) {
 		return e;

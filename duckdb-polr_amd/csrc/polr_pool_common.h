@@ -9,15 +9,12 @@ static __device__ unsigned long long polr_diag_router[16];
 #endif
 #include "polr_pool_device.h"
 
-// LDS a router wave needs: state + round scratch | saved state of a rehearsal | window of >= 256 chunk boundaries
-#define POOL_ROUTER_STATE ((POLR_RES_ROUTER_DWORDS + 3u) & ~3u)
-#define POOL_ROUTER_SAVE ((POLR_RES_HOT_DWORDS + 3u) & ~3u)
-#define POOL_ROUTER_MIN_DWORDS (POOL_ROUTER_STATE + POOL_ROUTER_SAVE + 2u * 256u)
-
 __device__ __forceinline__ void pool_load_run(const PoolRun *run, PoolRun &rh) {
 	rh.sync = (PoolSync *)uni64((uint64_t)run->sync);
 	rh.n_exec = uni(run->n_exec);
 	rh.n_router_blocks = uni(run->n_router_blocks);
+	rh.routers_per_block = uni(run->routers_per_block);
+	rh.routers_rem = uni(run->routers_rem);
 	rh.pool_waves = uni(run->pool_waves);
 	rh.lo_cap = uni(run->lo_cap);
 	rh.hi_cap = uni(run->hi_cap);
@@ -62,24 +59,53 @@ __device__ __forceinline__ void pool_load_exec(const ResidentExec *xp, ResidentE
 	}
 }
 
-// the router waves of a router workgroup; router_dwords: LDS dwords per router wave
-__device__ __forceinline__ void pool_router_wave(const ResidentExec *execs, PoolRun *run, const PoolRun &rh, uint32_t k,
-                                                 uint32_t gran, uint32_t *lds, uint32_t router_dwords) {
+// Who is who in the grid.  Separate layout: the first n_router_blocks workgroups are routers (wave w of workgroup b:
+// executor b * waves + w), the others probe.  Mixed layout (n_router_blocks == 0): every workgroup probes, and its
+// first waves route -- executor e in wave e / n_blocks of workgroup e % n_blocks.  Probe waves are numbered densely
+// over the grid, router waves skipped: rings, the hi lottery and the EXIT count see pool_waves waves, no gaps.
+struct PoolRole {
+	bool router;
+	uint32_t exec;          // router: its executor (>= n_exec: a spare wave of the last router workgroup)
+	uint32_t router_index;  // router: which router of its workgroup
+	uint32_t pool_wave;     // probe wave: its number in the pool
+};
+__device__ __forceinline__ PoolRole pool_role(const PoolRun &rh) {
 	const uint32_t wave_in_block = threadIdx.x >> 6;
 	const uint32_t wpb = blockDim.x >> 6;
-	const uint32_t exec = blockIdx.x * wpb + wave_in_block;
+	PoolRole r;
+	if (blockIdx.x < rh.n_router_blocks) {
+		r.router = true;
+		r.exec = blockIdx.x * wpb + wave_in_block;
+		r.router_index = wave_in_block;
+		r.pool_wave = 0;
+		return r;
+	}
+	const uint32_t pb = blockIdx.x - rh.n_router_blocks;
+	const uint32_t mine = rh.routers_per_block + (pb < rh.routers_rem ? 1u : 0u);
+	const uint32_t before = pb * rh.routers_per_block + (pb < rh.routers_rem ? pb : rh.routers_rem);
+	r.router = wave_in_block < mine;
+	r.exec = pb + wave_in_block * (gridDim.x - rh.n_router_blocks);
+	r.router_index = wave_in_block;
+	r.pool_wave = pb * wpb - before + wave_in_block - mine;
+	return r;
+}
+
+// one router wave; base: its LDS area of router_dwords dwords
+__device__ __forceinline__ void pool_router_wave(const ResidentExec *execs, PoolRun *run, const PoolRun &rh, uint32_t exec,
+                                                 uint32_t k, uint32_t gran, uint32_t *base, uint32_t router_dwords) {
 	if (exec >= rh.n_exec) {
 		return;
 	}
 	// a router is one wave of mostly scalar-style, dependent code that everybody else waits for: it gets the SIMD's
 	// issue slots ahead of the probe waves it shares the SIMD with
 	__builtin_amdgcn_s_setprio(3);
+	asm volatile("; polr-router-begin"); // (tools/spill_report.py tells the router's code from the probe loop's by these)
 	ResidentExec x;
 	pool_load_exec(execs + exec, x);
-	uint32_t *base = lds + (size_t)wave_in_block * router_dwords;
 	const uint32_t cache_dwords = router_dwords - POOL_ROUTER_STATE - POOL_ROUTER_SAVE;
 	polr_pool_router(x, run, rh, exec, k, gran, threadIdx.x & 63, base, (uint64_t *)(base + POOL_ROUTER_STATE + POOL_ROUTER_SAVE),
 	                 cache_dwords / 2, base + POOL_ROUTER_STATE);
+	asm volatile("; polr-router-end");
 }
 
 // diagnostic build only (-DPOLR_DIAG_TIMELINE, `make diag`; never compiled into the product): every probe wave writes
@@ -87,11 +113,11 @@ __device__ __forceinline__ void pool_router_wave(const ResidentExec *execs, Pool
 #ifdef POLR_DIAG_TIMELINE
 static __device__ unsigned long long *polr_diag_tl;
 static __device__ uint32_t polr_diag_tl_cap;
-#define TL_BEGIN(first_block_)                                                                                         \
+#define TL_BEGIN(pool_wave_)                                                                                           \
 	unsigned long long tl_wait = wall_clock64();                                                                       \
 	unsigned long long tl_got = 0, tl_run = 0;                                                                         \
 	uint32_t tl_n = 0;                                                                                                 \
-	const uint32_t tl_wave = (blockIdx.x - (first_block_)) * (blockDim.x >> 6) + (threadIdx.x >> 6);
+	const uint32_t tl_wave = (pool_wave_);
 #define TL_GOT tl_got = wall_clock64();
 #define TL_RUN tl_run = wall_clock64();
 #define TL_DONE(u_)                                                                                                    \
@@ -123,7 +149,7 @@ static __device__ uint32_t polr_diag_tl_cap;
 	}
 #else
 #define POOL_DIAG_ENTRY(router_name_, timeline_name_)
-#define TL_BEGIN(first_block_)
+#define TL_BEGIN(pool_wave_)
 #define TL_GOT
 #define TL_RUN
 #define TL_DONE(u_)

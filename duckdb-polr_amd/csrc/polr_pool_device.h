@@ -76,6 +76,15 @@
 // of its unit to the pool (work sharing, polr_poolg.hip) halves what its own arrival is worth and hands the other half
 // on with the piece, `level` halvings deep (entry bits 32..36) -- the router waits for the tokens of the units it
 // published, however they were cut up on the way.
+// LDS a router wave needs: state + round scratch | saved state of a rehearsal | window of >= 256 chunk boundaries
+#define POOL_ROUTER_STATE ((POLR_RES_ROUTER_DWORDS + 3u) & ~3u)
+#define POOL_ROUTER_SAVE ((POLR_RES_HOT_DWORDS + 3u) & ~3u)
+#define POOL_ROUTER_MIN_DWORDS (POOL_ROUTER_STATE + POOL_ROUTER_SAVE + 2u * 256u)
+// router areas a probe workgroup of the flat kernel keeps behind its probe queues when they fit (the mixed layout);
+// a fixed reserve: the LDS of a launch does not depend on how many executors it runs
+#define POOL_ROUTER_RESERVE 2u
+#define POOL_LDS_DWORDS_MAX (160u * 1024u / 4u) // LDS of a CU
+
 #define POLR_POOL_TOKENS 65536ull
 #define POLR_POOL_MAX_LEVEL 16u
 
@@ -112,7 +121,10 @@ __device__ __forceinline__ PoolEntry *polr_pool_hi(PoolSync *s, uint32_t ring, u
 struct PoolRun {
 	PoolSync *sync;
 	uint32_t n_exec;
-	uint32_t n_router_blocks;
+	uint32_t n_router_blocks;               // router workgroups in front of the grid (the separate layout), or 0 and
+	uint32_t routers_per_block, routers_rem; // the mixed layout: workgroup b hosts routers_per_block (+ 1 if b < routers_rem)
+	                                        // routers in its first waves -- executor e is wave e / n_blocks of workgroup
+	                                        // e % n_blocks -- and its other waves probe
 	uint32_t pool_waves;                    // all probe waves
 	uint32_t lo_cap, hi_cap;                // entries per ring (powers of two), as in *sync
 	uint32_t hi_tuples;                     // rounds of up to this many tuples go to the hi queues
@@ -216,7 +228,7 @@ __device__ __forceinline__ uint64_t polr_pool_absorb(DevMpx *m, DevMpx *mg, unsi
 	}
 	// lanes j*8 now hold counter j
 	uint64_t s = 0;
-	const uint32_t last_path = (uint32_t)((volatile DevMpx *)m)->last_path;
+	const uint32_t last_path = (uint32_t)((volatile POLR_LDS DevMpx *)as_lds(m))->last_path; // (m: a router's LDS state)
 	for (uint32_t jj = 0; jj < k; jj++) {
 		const unsigned long long c = __shfl(v, jj * 8, 64);
 		if (lane == 0 && !discard && c) {
@@ -479,6 +491,59 @@ __device__ __forceinline__ bool polr_pool_next_unit(PoolPoller &pp, PoolUnit &u,
 }
 
 // ---- the router of one executor: ONE full wave, for the whole run ----------------------------------
+// A router shares its kernel with the probe loop, whose register budget (128 VGPRs at 16 waves per workgroup) the
+// router's single-lane 64-bit arithmetic does not fit into: left to itself the compiler spills the step loop to
+// scratch memory, and every reload is a dependent round trip on the path everybody waits for.  So
+//   * whatever lives from step to step -- arrival targets, the rehearsed rounds, the watchdog's report -- sits in the
+//     router's own LDS words (POOL_RT_*, behind the hot state), not in registers;
+//   * whatever the loop reads back from LDS or memory is made wave-uniform (uni): counters, flags and conditions then
+//     stay in scalar registers;
+//   * the routing decision is a function of its own (polr_pool_route_lane0): its temporaries do not overlap the loop's
+//     live ranges, and it fits the registers a callee may use without saving any.
+// tools/spill_report.py counts the spill instructions of the step loop (between the two markers below): none.
+//
+// dword offsets from lds + POLR_RES_HOT_DWORDS (POLR_RES_ROUTER_DWORDS covers them)
+#define POOL_RT_ROUND 0u   // DevRound: what the routing step decides (6 dwords)
+#define POOL_RT_PREFIX 8u  // 2 x 8 bytes and
+#define POOL_RT_US 12u     // 1 dword: what polr_router_route writes besides (unused by the pool)
+#define POOL_RT_TARGET 16u // unsigned long long[POLR_SLOTS]: tokens published in each slot so far
+#define POOL_RT_AHEAD 24u  // uint32_t[POLR_SLOTS][4]: {begin, count, path, emit} of rehearsed round i at [i % POLR_SLOTS]
+#define POOL_RT_DIAG 40u   // the watchdog's report: want, got (8 bytes each), slot, rounds in flight, "it was mine"
+static_assert(POLR_SLOTS == 4, "POOL_RT_* layout");
+static_assert(POLR_RES_ROUTER_DWORDS >= POLR_RES_HOT_DWORDS + POOL_RT_DIAG + 7u, "router words");
+static_assert(POLR_RES_HOT_DWORDS % 2 == 0, "8-byte words behind the hot state");
+
+// One routing decision on the state in `lds` (the real one, or the shadow swapped in), by ONE lane: the round goes to
+// the POOL_RT_ROUND words.  The arithmetic is polr_routing.h's, untouched.  (LDS pointers by address space: the
+// routing code's accesses stay LDS instructions although it is not inlined into the kernel.)
+static __device__ __forceinline__ void polr_pool_route_lane0(POLR_LDS uint32_t *lds_state, uint32_t pool_waves, uint64_t oc_base,
+                                                          uint64_t oc_n, POLR_LDS uint64_t *oc_data, uint32_t path_plus1) {
+	uint32_t *lds = (uint32_t *)lds_state;
+	DevMpx *m = (DevMpx *)lds;
+	DevRound *round = (DevRound *)(lds + POLR_RES_HOT_DWORDS + POOL_RT_ROUND);
+	OffsCache oc;
+	oc.base = oc_base;
+	oc.n = oc_n;
+	oc.data = (uint64_t *)oc_data;
+	polr_router_route(m, round, (uint64_t *)(lds + POLR_RES_HOT_DWORDS + POOL_RT_PREFIX),
+	                  lds + POLR_RES_HOT_DWORDS + POOL_RT_US, pool_waves, &oc, false);
+	if (path_plus1) {
+		// BACKPRESSURE (src/parallel/pipeline.cpp:147-156, polar_config.cpp:128-147): this executor IS one
+		// join order; its multiplexer routes DEFAULT_PATH, the order it stands for replaces path 0
+		round->path = path_plus1 - 1u;
+		m->last_path = path_plus1 - 1u;
+	}
+}
+
+// This lane's number, computed where it is asked for.  Inside the step loop every phase asks again: addresses derived
+// from a lane number that is computed once in front of the loop are loop invariants the compiler keeps alive across
+// the routing arithmetic -- the last values it spilled there.
+__device__ __forceinline__ uint32_t pool_lane_now() {
+	uint32_t l;
+	asm volatile("v_mbcnt_lo_u32_b32 %0, -1, 0\n\tv_mbcnt_hi_u32_b32 %0, -1, %0" : "=v"(l));
+	return l;
+}
+
 // lds: POLR_RES_ROUTER_DWORDS dwords of state + scratch_lds: POLR_RES_HOT_DWORDS dwords (saved state of a rehearsal);
 // cache_lds / cache_cap: window of the chunk-offset array in 8-byte entries.
 __device__ __forceinline__ void polr_pool_router(const ResidentExec &x, PoolRun *run, const PoolRun &rh, uint32_t exec,
@@ -515,16 +580,21 @@ __device__ __forceinline__ void polr_pool_router(const ResidentExec &x, PoolRun 
 		}
 	}
 	DevMpx *m = (DevMpx *)lds;
-	volatile uint32_t *const host_words = mg->progress;
+	// what the whole wave reads back after lane 0 wrote it: volatile, and by address space (a volatile access through a
+	// generic pointer stays a FLAT instruction with a 64-bit address of its own to keep)
+	volatile POLR_LDS DevMpx *const vm = (volatile POLR_LDS DevMpx *)as_lds(lds);
+	volatile POLR_LDS DevMpx *const vshadow = (volatile POLR_LDS DevMpx *)as_lds(scratch_lds);
+	volatile POLR_LDS uint32_t *const rt = as_lds(lds) + POLR_RES_HOT_DWORDS; // the router's own words (POOL_RT_*)
+	volatile uint32_t *const host_words = (volatile uint32_t *)uni64((uint64_t)mg->progress);
 	__builtin_amdgcn_wave_barrier();
 	RT_T(rt_e1)
 	RT_ADD(8, rt_e1 - rt_entry)
 	if (lane == 0) {
 		m->progress = nullptr; // nobody on the host follows the steps of a one-launch run
 	}
-	DevRound *round = (DevRound *)(lds + POLR_RES_HOT_DWORDS); // 24 bytes
-	uint64_t *prefix = (uint64_t *)(lds + POLR_RES_HOT_DWORDS + 8);
-	uint32_t *us = lds + POLR_RES_HOT_DWORDS + 12;
+	const volatile POLR_LDS DevRound *const round = (const volatile POLR_LDS DevRound *)(rt + POOL_RT_ROUND);
+	volatile POLR_LDS unsigned long long *const target = (volatile POLR_LDS unsigned long long *)(rt + POOL_RT_TARGET);
+	volatile POLR_LDS uint32_t *const ahead = rt + POOL_RT_AHEAD;
 	OffsCache oc;
 	oc.base = 0;
 	oc.n = 0;
@@ -560,6 +630,7 @@ __device__ __forceinline__ void polr_pool_router(const ResidentExec &x, PoolRun 
 		m->n_chunks = x.n_chunks;
 		m->n_tuples = x.n_tuples;
 		m->done = x.chunk_begin >= x.chunk_end ? 1 : 0;
+		rt[POOL_RT_DIAG + 6] = 0; // (no watchdog of this router has fired)
 	}
 	__builtin_amdgcn_wave_barrier();
 	RT_T(rt_e2)
@@ -569,82 +640,73 @@ __device__ __forceinline__ void polr_pool_router(const ResidentExec &x, PoolRun 
 		// one dependent global load after the other on its single lane)
 		polr_offs_cache_fill(oc, x, x.chunk_begin, cache_cap, lane);
 	}
-	unsigned long long target[POLR_SLOTS];
-	if (((volatile DevMpx *)m)->res_valid) {
-#pragma unroll
-		for (uint32_t s = 0; s < POLR_SLOTS; s++) {
-			target[s] = ((volatile DevMpx *)m)->res_target[s];
+	if (uni(vm->res_valid)) {
+		if (lane < POLR_SLOTS) {
+			target[lane] = vm->res_target[lane];
 		}
 	} else {
 #pragma unroll
 		for (uint32_t s = 0; s < POLR_SLOTS; s++) {
-			target[s] = polr_pool_arrived(x.sync, s, lane);
+			const unsigned long long t = polr_pool_arrived(x.sync, s, lane);
+			if (lane == 0) {
+				target[s] = t;
+			}
 			if (s) {
 				polr_pool_absorb(m, mg, x.counts + s * bank_stride, k, lane, true);
 			}
 		}
 	}
+	__builtin_amdgcn_wave_barrier();
 	// Rounds in flight, oldest first: the FRONT one is decided (the state has routed it); the ones behind it were
 	// rehearsed ahead on a copy of the state (the shadow) and published already -- every real step that follows must
 	// decide exactly them, in order.  Round i of the run sits in slot i % POLR_SLOTS, so the front's slot is
-	// (n_pub - n_fly) % POLR_SLOTS.
+	// (n_pub - n_fly) % POLR_SLOTS; a rehearsed round is remembered at ahead[i % POLR_SLOTS].
 	RT_T(rt_e3)
 	RT_ADD(10, rt_e3 - rt_entry)
 	uint32_t n_steps = 0;
 	uint32_t range_i = 0; // further ranges of this executor taken so far (ResidentExec::more_begin / more_end)
 	uint32_t n_pub = 0; // rounds published so far
 	uint32_t n_fly = 0; // published, counters not absorbed yet
-	PoolRoundOut ahead[POLR_SLOTS - 1] = {}; // the rehearsed rounds behind the front (statically indexed: registers)
-	bool shadow_valid = false;               // scratch_lds holds the state as it will be after the last rehearsed round
-	bool shadow_ended = false;               // the rehearsal ran off the end of the source: nothing more to publish ahead
+	bool shadow_valid = false; // scratch_lds holds the state as it will be after the last rehearsed round
+	bool shadow_ended = false; // the rehearsal ran off the end of the source: nothing more to publish ahead
 	bool failed = false;
-	// what this router's own watchdog was waiting for when it fired (reported by polr_mpx_finish)
-	bool diag_timed = false;
-	unsigned long long diag_want = 0, diag_got = 0;
-	uint32_t diag_slot = 0, diag_fly = 0;
 	uint32_t rot = exec; // units of consecutive rounds start on different rings
 	// one routing step on whatever state sits in `lds` (the real one, or the shadow swapped in): the round it decides
 	auto route_here = [&](PoolRoundOut &r) -> bool {
 		// (asked for before the routing code runs, used after it: a sizing hint, one global round trip off the path)
+		const uint32_t lane = pool_lane_now();
 		const uint32_t done_now = __hip_atomic_load(&run->routers_done, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 		if (lane == 0) {
-			polr_router_route(m, round, prefix, us, rh.pool_waves, &oc, false);
-			if (x.path_plus1) {
-				// BACKPRESSURE (src/parallel/pipeline.cpp:147-156, polar_config.cpp:128-147): this executor IS one
-				// join order; its multiplexer routes DEFAULT_PATH, the order it stands for replaces path 0
-				round->path = x.path_plus1 - 1u;
-				m->last_path = x.path_plus1 - 1u;
-			}
+			polr_pool_route_lane0(as_lds(lds), rh.pool_waves, oc.base, oc.n, as_lds(oc.data), x.path_plus1);
 		}
 		__builtin_amdgcn_wave_barrier();
-		const bool done = ((volatile DevMpx *)m)->done != 0;
-		const volatile DevRound *vr = round;
-		r.begin = (uint32_t)vr->begin;
-		r.count = (uint32_t)vr->count;
-		r.path = vr->path;
-		r.emit = vr->emit;
+		const bool done = uni(vm->done) != 0;
+		r.begin = uni((uint32_t)round->begin);
+		r.count = uni((uint32_t)round->count);
+		r.path = uni(round->path);
+		r.emit = uni(round->emit);
 		// a round is cut for the executors that are still routing: the last ones get the whole pool
 		// (routers_done counts executors that have finished ROUTING; their terminal rounds may still be queued, which
 		// is what the lo queue is for)
-		const uint32_t active = done_now < rh.n_exec ? rh.n_exec - done_now : 1u;
-		const bool terminal = ((volatile DevMpx *)m)->core.num_cache_flushing_skips == polr::kIdxMax;
+		const uint32_t dn = uni(done_now);
+		const uint32_t active = dn < rh.n_exec ? rh.n_exec - dn : 1u;
+		const bool terminal = uni64(vm->core.num_cache_flushing_skips) == polr::kIdxMax;
 		polr_pool_size_units(r.count, rh.pool_waves, active, gran, rh.hi_tuples, rh.units_x, rh.hi_unit, terminal, r);
 		return done;
 	};
 	auto publish = [&](const PoolRoundOut &r) {
+		const uint32_t lane = pool_lane_now();
 		const uint32_t slot = n_pub & (POLR_SLOTS - 1u);
 		polr_pool_publish(rh, sync, exec, slot, r, rot, lane);
 		rot += r.n_units;
-#pragma unroll
-		for (uint32_t s = 0; s < POLR_SLOTS; s++) {
-			if (s == slot) {
-				target[s] += (unsigned long long)r.n_units * POLR_POOL_TOKENS;
-			}
+		if (lane == 0) {
+			target[slot] = target[slot] + (unsigned long long)r.n_units * POLR_POOL_TOKENS;
 		}
 		n_pub++;
 		n_fly++;
 	};
 	auto swap_shadow = [&]() {
+		const uint32_t lane = pool_lane_now();
 		__builtin_amdgcn_wave_barrier();
 		for (uint32_t i = lane; i < POLR_RES_HOT_DWORDS; i += 64) {
 			const uint32_t a = lds[i], b = scratch_lds[i];
@@ -653,39 +715,39 @@ __device__ __forceinline__ void polr_pool_router(const ResidentExec &x, PoolRun 
 		}
 		__builtin_amdgcn_wave_barrier();
 	};
+	asm volatile("; polr-router-steps-begin");
 	while (true) {
 		__builtin_amdgcn_wave_barrier();
 		const uint32_t front_slot = (n_pub - n_fly) & (POLR_SLOTS - 1u);
 		RT_T(rt0)
 		// (1) the oldest round in flight has to be complete before its counters can be absorbed
 		if (n_fly) {
-			unsigned long long want = 0;
-#pragma unroll
-			for (uint32_t s = 0; s < POLR_SLOTS; s++) {
-				want = s == front_slot ? target[s] : want;
-			}
+			const uint32_t lane = pool_lane_now();
+			const unsigned long long want = uni64(target[front_slot]);
 			const unsigned long long t0 = wall_clock64();
 			uint32_t spins = 0;
-			while (polr_pool_arrived(x.sync, front_slot, lane) != want) {
+			while (uni64(polr_pool_arrived(x.sync, front_slot, lane)) != want) {
 				__builtin_amdgcn_s_sleep(1);
 				if ((++spins & 7u) == 0) { // (every spin is a round trip to the arrival counters: a look every ~10 us)
-					uint32_t ab = __hip_atomic_load(&run->abort, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+					const uint32_t ab = uni(__hip_atomic_load(&run->abort, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT));
 					if (ab || wall_clock64() - t0 > rh.timeout_ticks) {
 						failed = true; // a probe wave is missing
 						if (!ab) { // (this router's own watchdog: say what it was waiting for, polr_mpx_finish reports it)
-							diag_want = want;
-							diag_slot = front_slot;
-							diag_fly = n_fly;
-							diag_timed = true;
+							const unsigned long long got = polr_pool_arrived(x.sync, front_slot, lane);
+							if (lane == 0) {
+								volatile POLR_LDS unsigned long long *d64 = (volatile POLR_LDS unsigned long long *)(rt + POOL_RT_DIAG);
+								d64[0] = want;
+								d64[1] = got;
+								rt[POOL_RT_DIAG + 4] = front_slot;
+								rt[POOL_RT_DIAG + 5] = n_fly;
+								rt[POOL_RT_DIAG + 6] = 1u;
+							}
 						}
 						break;
 					}
 				}
 			}
 			if (failed) {
-				if (diag_timed) {
-					diag_got = polr_pool_arrived(x.sync, front_slot, lane);
-				}
 				break;
 			}
 		}
@@ -693,6 +755,7 @@ __device__ __forceinline__ void polr_pool_router(const ResidentExec &x, PoolRun 
 		RT_ADD(0, rt1 - rt0)
 		// (2) the real step
 		if (!(reset && n_steps == 0)) { // (a reset run starts on the bank it dropped at entry)
+			const uint32_t lane = pool_lane_now();
 			const uint64_t got = polr_pool_absorb(m, mg, x.counts + (n_fly ? front_slot : 0u) * bank_stride, k, lane, false);
 			if (lane == 0) {
 				m->core.AddNumIntermediates(got);
@@ -701,7 +764,7 @@ __device__ __forceinline__ void polr_pool_router(const ResidentExec &x, PoolRun 
 		}
 		if (!x.morsel_cursor && range_i < x.n_more) {
 			// this executor's current range is used up and it owns another one: go on there, same multiplexer state
-			const uint64_t ci = ((volatile DevMpx *)m)->chunk_idx, ce = ((volatile DevMpx *)m)->chunk_end;
+			const uint64_t ci = uni64(vm->chunk_idx), ce = uni64(vm->chunk_end);
 			if (ci >= ce) {
 				uint64_t nb = 0, ne = 0;
 #pragma unroll
@@ -711,7 +774,7 @@ __device__ __forceinline__ void polr_pool_router(const ResidentExec &x, PoolRun 
 						ne = x.more_end[j];
 					}
 				}
-				if (lane == 0) {
+				if (pool_lane_now() == 0) {
 					m->chunk_idx = nb;
 					m->chunk_end = ne;
 					m->done = nb >= ne ? 1 : 0;
@@ -720,7 +783,7 @@ __device__ __forceinline__ void polr_pool_router(const ResidentExec &x, PoolRun 
 				__builtin_amdgcn_wave_barrier();
 			}
 		}
-		if (lane == 0 && x.morsel_cursor && m->chunk_idx >= m->chunk_end) {
+		if (x.morsel_cursor && pool_lane_now() == 0 && m->chunk_idx >= m->chunk_end) {
 			// this executor's morsel is used up (or it has none yet): pull the next one
 			const unsigned long long next = atomicAdd(x.morsel_cursor, (unsigned long long)x.morsel_chunks);
 			if (next < x.morsel_end) {
@@ -741,14 +804,11 @@ __device__ __forceinline__ void polr_pool_router(const ResidentExec &x, PoolRun 
 			RT_ADD(2, rt3 - rt2)
 			if (n_fly > 1) {
 				// this round is already out: the real decision must be the rehearsed one, bit for bit
-				const PoolRoundOut &sp = ahead[0];
-				if (done || r.begin != sp.begin || r.count != sp.count || r.path != sp.path || r.emit != sp.emit) {
+				volatile POLR_LDS uint32_t *sp = ahead + 4u * ((n_pub - n_fly + 1u) & (POLR_SLOTS - 1u));
+				const uint32_t sp_begin = uni(sp[0]), sp_count = uni(sp[1]), sp_path = uni(sp[2]), sp_emit = uni(sp[3]);
+				if (done || r.begin != sp_begin || r.count != sp_count || r.path != sp_path || r.emit != sp_emit) {
 					failed = true; // (cannot happen while polr_can_speculate is right; never continue on a wrong round)
 					break;
-				}
-#pragma unroll
-				for (uint32_t i = 0; i + 1 < POLR_SLOTS - 1; i++) {
-					ahead[i] = ahead[i + 1];
 				}
 				n_fly--;
 			} else {
@@ -772,9 +832,10 @@ __device__ __forceinline__ void polr_pool_router(const ResidentExec &x, PoolRun 
 		// are still outstanding, decide it on the shadow and publish it in the next slot
 		while (n_fly < POLR_SLOTS && !shadow_ended) {
 			if (!shadow_valid) {
-				if (!polr_can_speculate(((volatile DevMpx *)m)->core)) {
+				if (!uni(polr_can_speculate(vm->core) ? 1u : 0u)) {
 					break;
 				}
+				const uint32_t lane = pool_lane_now();
 				__builtin_amdgcn_wave_barrier();
 				for (uint32_t i = lane; i < POLR_RES_HOT_DWORDS; i += 64) {
 					scratch_lds[i] = lds[i];
@@ -784,7 +845,7 @@ __device__ __forceinline__ void polr_pool_router(const ResidentExec &x, PoolRun 
 					((DevMpx *)scratch_lds)->log_enabled = 0; // (no trace of a rehearsal)
 				}
 				shadow_valid = true;
-			} else if (!polr_can_speculate(((volatile DevMpx *)scratch_lds)->core)) {
+			} else if (!uni(polr_can_speculate(vshadow->core) ? 1u : 0u)) {
 				break;
 			}
 			// the rehearsal runs IN PLACE (the routing code only ever sees the one LDS object, which keeps its accesses
@@ -797,38 +858,41 @@ __device__ __forceinline__ void polr_pool_router(const ResidentExec &x, PoolRun 
 				shadow_ended = true; // (a rehearsal that runs off the end of the source publishes nothing)
 				break;
 			}
-#pragma unroll
-			for (uint32_t i = 0; i < POLR_SLOTS - 1; i++) {
-				if (i + 1 == n_fly) {
-					ahead[i] = r2;
-				}
+			if (pool_lane_now() == 0) { // (round n_pub of the run: the real step that decides it looks here)
+				volatile POLR_LDS uint32_t *sp = ahead + 4u * (n_pub & (POLR_SLOTS - 1u));
+				sp[0] = r2.begin;
+				sp[1] = r2.count;
+				sp[2] = r2.path;
+				sp[3] = r2.emit;
 			}
 			publish(r2);
 		}
 		RT_T(rt6)
 		RT_ADD(4, rt6 - rt5)
 		// while the pool probes: keep the boundaries of the chunks ahead in LDS
-		{
-			const uint64_t ci = ((volatile DevMpx *)m)->chunk_idx;
-			if (x.chunk_offsets && ci - oc.base >= oc.n / 2) { // (also the first fill: n == 0)
-				polr_offs_cache_fill(oc, x, ci, cache_cap, lane);
+		if (x.chunk_offsets) {
+			const uint64_t ci = uni64(vm->chunk_idx);
+			if (ci - oc.base >= oc.n / 2) { // (also the first fill: n == 0)
+				polr_offs_cache_fill(oc, x, ci, cache_cap, pool_lane_now());
 			}
 		}
 	}
+	asm volatile("; polr-router-steps-end");
+	__builtin_amdgcn_wave_barrier();
 	if (failed) {
 		if (lane == 0) {
 			__hip_atomic_store(&run->abort, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 			if (host_words) {
 				host_words[2] = 1;
 			}
-			if (diag_timed && host_words) { // (the pinned words of THIS executor's multiplexer)
+			if (rt[POOL_RT_DIAG + 6] && host_words) { // (the pinned words of THIS executor's multiplexer)
 				host_words[5] = exec;
-				host_words[6] = diag_slot;
-				host_words[7] = diag_fly;
-				host_words[8] = (uint32_t)diag_want;
-				host_words[9] = (uint32_t)(diag_want >> 32);
-				host_words[10] = (uint32_t)diag_got;
-				host_words[11] = (uint32_t)(diag_got >> 32);
+				host_words[6] = rt[POOL_RT_DIAG + 4];
+				host_words[7] = rt[POOL_RT_DIAG + 5];
+				host_words[8] = rt[POOL_RT_DIAG + 0];
+				host_words[9] = rt[POOL_RT_DIAG + 1];
+				host_words[10] = rt[POOL_RT_DIAG + 2];
+				host_words[11] = rt[POOL_RT_DIAG + 3];
 				host_words[4] = 1u;
 			}
 		}

@@ -66,7 +66,9 @@ __global__ __launch_bounds__(64 * POOLG_WAVES, 4) void polr_pool_gen_kernel(cons
 	PoolRun rh;
 	pool_load_run(run, rh);
 	if (blockIdx.x < rh.n_router_blocks) {
-		pool_router_wave(execs, run, rh, k, 64, lds, lds_per_wave); // (units of big rounds: multiples of 64 tuples)
+		// (units of big rounds: multiples of 64 tuples; router wave r uses the LDS of probe wave r)
+		pool_router_wave(execs, run, rh, blockIdx.x * (blockDim.x >> 6) + wave_in_block, k, 64,
+		                 lds + (size_t)wave_in_block * lds_per_wave, lds_per_wave);
 		return;
 	}
 	// probe wave g of the pool serves ring g % n_rings (dealt wave by wave: every ring the same number of waves)
@@ -209,7 +211,7 @@ __global__ __launch_bounds__(64 * POOLG_WAVES, 4) void polr_pool_gen_kernel(cons
 		}
 	};
 	const uint32_t share_after = rh.share_recs ? rh.share_after : 0xFFFFFFFFu;
-	TL_BEGIN(rh.n_router_blocks)
+	TL_BEGIN(pool_wave)
 	while (polr_pool_next_unit(pp, u, c.lane)) {
 		TL_GOT
 		c.stages = stages + (size_t)u.path * POLR_KMAX;

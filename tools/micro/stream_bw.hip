@@ -10,10 +10,13 @@
 // Prints GB/s of the bytes asked for (keys x 4) and of the lines touched (64-byte lines, counted exactly on the host
 // from the same hash).
 //   hipcc --offload-arch=gfx950 -O3 -o tools/micro/stream_bw tools/micro/stream_bw.hip && tools/micro/stream_bw [rows_millions]
+//   tools/micro/stream_bw wg1024 [rows_millions]   the 0.08 / 0.20 / 0.40 mix as 1 024-thread workgroups, one per CU, on
+//                                                  232 and on 256 of them (routers on CUs of their own, or in every CU's workgroup)
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <stdio.h>
 #include <stdlib.h>
+#include <string.h>
 #include <vector>
 
 #define CHECK(x)                                                                                                       \
@@ -56,9 +59,9 @@ struct Thr {
 	uint32_t t[3];
 };
 
-__global__ __launch_bounds__(256) void bw_mix(const uint4 *__restrict__ a, const uint32_t *__restrict__ b,
-                                              const uint32_t *__restrict__ c, const uint32_t *__restrict__ d, uint64_t n16,
-                                              Thr thr, unsigned long long *out) {
+__device__ __forceinline__ void bw_mix_body(const uint4 *__restrict__ a, const uint32_t *__restrict__ b,
+                                            const uint32_t *__restrict__ c, const uint32_t *__restrict__ d, uint64_t n16,
+                                            Thr thr, unsigned long long *out) {
 	uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
 	const uint64_t step = (uint64_t)gridDim.x * blockDim.x;
 	uint32_t acc = 0;
@@ -93,6 +96,24 @@ __global__ __launch_bounds__(256) void bw_mix(const uint4 *__restrict__ a, const
 	}
 }
 
+__global__ __launch_bounds__(256) void bw_mix(const uint4 *__restrict__ a, const uint32_t *__restrict__ b,
+                                              const uint32_t *__restrict__ c, const uint32_t *__restrict__ d, uint64_t n16,
+                                              Thr thr, unsigned long long *out) {
+	bw_mix_body(a, b, c, d, n16, thr, out);
+}
+
+// the same pass in the pool kernel's workgroup shape: 1 024 threads and enough dynamic LDS that a CU holds one
+// workgroup (mode "wg1024": how much do the last 24 of 256 CUs add when 232 already issue the mix?)
+__global__ __launch_bounds__(1024) void bw_mix_wg(const uint4 *__restrict__ a, const uint32_t *__restrict__ b,
+                                                  const uint32_t *__restrict__ c, const uint32_t *__restrict__ d,
+                                                  uint64_t n16, Thr thr, unsigned long long *out) {
+	extern __shared__ uint32_t hold[];
+	if (n16 == ~0ull) {
+		hold[threadIdx.x] = 1; // (never: keeps the allocation in use)
+	}
+	bw_mix_body(a, b, c, d, n16, thr, out);
+}
+
 static double time_ms(hipEvent_t e0, hipEvent_t e1) {
 	float ms = 0;
 	CHECK(hipEventElapsedTime(&ms, e0, e1));
@@ -100,6 +121,11 @@ static double time_ms(hipEvent_t e0, hipEvent_t e1) {
 }
 
 int main(int argc, char **argv) {
+	const bool wg1024 = argc > 1 && strcmp(argv[1], "wg1024") == 0;
+	if (wg1024) {
+		argc--;
+		argv++;
+	}
 	const uint64_t rows = (uint64_t)(argc > 1 ? atof(argv[1]) : 600.0) * 1000000ull / 4 * 4;
 	const uint64_t n16 = rows / 4;
 	uint32_t *col[4];
@@ -116,9 +142,42 @@ int main(int argc, char **argv) {
 	hipDeviceProp_t prop;
 	CHECK(hipGetDeviceProperties(&prop, 0));
 	const int cus = prop.multiProcessorCount;
+	const int reps = 5;
+	if (wg1024) {
+		// 0.08 / 0.20 / 0.40, one 1 024-thread workgroup per CU (100 KB of LDS each), on 232 and on 256 workgroups,
+		// alternating, four times each: the spread of a grid size's own repeats is what a difference is held against
+		Thr thr;
+		const double mx[3] = {0.08, 0.2, 0.4};
+		for (int s = 0; s < 3; s++) {
+			thr.t[s] = (uint32_t)(mx[s] * 4294967295.0);
+		}
+		const size_t lds = 100 * 1024;
+		CHECK(hipFuncSetAttribute((const void *)bw_mix_wg, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+		int per_cu = 0;
+		CHECK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, (const void *)bw_mix_wg, 1024, lds));
+		printf("{\"rows\": %llu, \"cus\": %d, \"mode\": \"wg1024\", \"survive\": [0.08, 0.20, 0.40], \"workgroups_per_cu\": %d, "
+		       "\"results\": [\n", (unsigned long long)rows, cus, per_cu);
+		bool first_wg = true;
+		for (int round = 0; round < 4; round++) {
+			for (int grid : {232, 256}) {
+				bw_mix_wg<<<grid, 1024, lds>>>((const uint4 *)col[0], col[1], col[2], col[3], n16, thr, out);
+				CHECK(hipDeviceSynchronize());
+				CHECK(hipEventRecord(e0));
+				for (int r = 0; r < reps; r++) {
+					bw_mix_wg<<<grid, 1024, lds>>>((const uint4 *)col[0], col[1], col[2], col[3], n16, thr, out);
+				}
+				CHECK(hipEventRecord(e1));
+				CHECK(hipEventSynchronize(e1));
+				printf("%s {\"kernel\": \"mix_wg1024\", \"grid\": %d, \"round\": %d, \"ms\": %.4f}", first_wg ? "" : ",\n", grid, round,
+				       time_ms(e0, e1) / reps);
+				first_wg = false;
+			}
+		}
+		printf("\n]}\n");
+		return 0;
+	}
 	printf("{\"rows\": %llu, \"cus\": %d, \"results\": [\n", (unsigned long long)rows, cus);
 	bool first = true;
-	const int reps = 5;
 	for (int wg_per_cu : {2, 4, 8}) {
 		const int grid = cus * wg_per_cu;
 		bw_stream<<<grid, 256>>>((const uint4 *)col[0], n16, out);
