@@ -26,34 +26,146 @@ struct AggPartial {
 	unsigned long long count; // rows that took part (non-NULL; all rows for COUNT(*))
 };
 
+// ---- aggregate ARGUMENTS that are `left OP right` (polr_out_aggregate*_expr): what the reference evaluates in the projection
+// under its aggregate operators, with the checked operators of src/include/duckdb/common/operator/{add,subtract,multiply}.hpp
+// (TryAddOperator / TrySubtractOperator / TryMultiplyOperator: the exact result must lie in the result type, else
+// OutOfRangeException).  The expression form has a set of its own -- FusedSink embeds DevAgg / DevAggSet, whose layout
+// stays -- and the sink kernels are compiled once per set type: with DevAggSet they are the kernels they were.
+struct DevExprAgg {
+	DevCol src[2];    // left, right operand ([0] alone for POLR_ARG_COLUMN)
+	uint32_t slot[2]; // the row ids that index them
+	uint32_t fn, op;
+	long long lo, hi; // the range of the declared result type
+};
+struct DevExprAggSet {
+	DevExprAgg a[POLR_MAX_AGGS];
+	uint32_t n;
+	uint32_t pad;
+	unsigned long long *oor; // [POLR_MAX_AGGS]: arguments out of range, added by every wave under the first aggregate IT saw one for
+};
+template <class SET>
+struct is_expr_set {
+	static constexpr bool value = false;
+};
+template <>
+struct is_expr_set<DevExprAggSet> {
+	static constexpr bool value = true;
+};
+
+// a lane's count of out-of-range arguments and the lowest aggregate index it saw one for
+struct OorCount {
+	unsigned long long n;
+	uint32_t first;
+};
+
+// The argument of aggregate `ag` for the output row at position `at` of every slot's row-id array: false = NULL (an operand is
+// NULL: the row takes no part and cannot overflow) or out of range (counted; the call will fail and no result leaves).
+// Operands are cells of at most 8 bytes, signed if 8, so both are exact in 64 bits and the overflow flag of the 64-bit
+// operation plus the comparison with [lo, hi] is the reference's test for every result type up to BIGINT.
+__device__ __forceinline__ bool expr_arg(const DevOut &out, uint64_t at, const DevExprAgg &ag, uint32_t a, long long *v, OorCount *oor) {
+	const uint32_t r0 = out.ids[(uint64_t)ag.slot[0] * out.slot_stride + at];
+	if (ag.op == POLR_ARG_COLUMN) {
+		if (ag.src[0].valid && !ag.src[0].valid[r0]) {
+			return false;
+		}
+		*v = load_col_cell(ag.src[0], r0);
+		return true;
+	}
+	// (both operands of one source: the row id is read once)
+	const uint32_t r1 = ag.slot[1] == ag.slot[0] ? r0 : out.ids[(uint64_t)ag.slot[1] * out.slot_stride + at];
+	if ((ag.src[0].valid && !ag.src[0].valid[r0]) || (ag.src[1].valid && !ag.src[1].valid[r1])) {
+		return false;
+	}
+	const long long x = load_col_cell(ag.src[0], r0), y = load_col_cell(ag.src[1], r1);
+	long long r;
+	bool over;
+	switch (ag.op) {
+	case POLR_ARG_ADD:
+		over = __builtin_add_overflow(x, y, &r);
+		break;
+	case POLR_ARG_SUB:
+		over = __builtin_sub_overflow(x, y, &r);
+		break;
+	default:
+		over = __builtin_mul_overflow(x, y, &r);
+		break;
+	}
+	if (over || r < ag.lo || r > ag.hi) {
+		oor->n++;
+		oor->first = a < oor->first ? a : oor->first;
+		return false;
+	}
+	*v = r;
+	return true;
+}
+
+// once per wave, all lanes converged: one atomic, and none when the wave saw nothing out of range
+__device__ __forceinline__ void flush_oor(unsigned long long *oor, const OorCount &mine) {
+	const unsigned long long n = wave_sum64(mine.n);
+	if (n) {
+		uint32_t first = mine.first;
+#pragma unroll
+		for (int d = 32; d > 0; d >>= 1) {
+			const uint32_t o = (uint32_t)__shfl_xor((int)first, d, 64);
+			first = o < first ? o : first;
+		}
+		if ((threadIdx.x & 63u) == 0) {
+			atomicAdd(&oor[first], n);
+		}
+	}
+}
+
 // grid-stride over the output chunks; partials[blockIdx.x * n + a]
-__global__ __launch_bounds__(256) void polr_agg_kernel(DevOut out, uint32_t n_chunks, DevAggSet aggs,
+template <class SET>
+__global__ __launch_bounds__(256) void polr_agg_kernel(DevOut out, uint32_t n_chunks, SET aggs,
                                                        AggPartial *__restrict__ partials) {
+	constexpr bool EXPR = is_expr_set<SET>::value;
+	OorCount my_oor = {0, 0xFFFFFFFFu};
 	__shared__ AggPartial wave_part[4][POLR_MAX_AGGS];
 	const uint32_t lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
 	for (uint32_t a = 0; a < aggs.n; a++) {
-		const DevAgg ag = aggs.a[a];
+		const auto ag = aggs.a[a];
 		unsigned long long lo = 0, cnt = 0;
 		long long hi = 0, mn = 0x7FFFFFFFFFFFFFFFll, mx = (long long)0x8000000000000000ull;
 		for (uint32_t chunk = blockIdx.x; chunk < n_chunks; chunk += gridDim.x) {
 			const uint32_t n = out.chunk_count[chunk];
-			const uint32_t *ids = out.ids + (uint64_t)ag.slot * out.slot_stride + (uint64_t)chunk * out.chunk_capacity;
-			for (uint32_t i = threadIdx.x; i < n; i += blockDim.x) {
-				if (ag.fn == POLR_AGG_COUNT_STAR) {
+			if constexpr (EXPR) {
+				const uint64_t chunk_base = (uint64_t)chunk * out.chunk_capacity;
+				for (uint32_t i = threadIdx.x; i < n; i += blockDim.x) {
+					if (ag.fn == POLR_AGG_COUNT_STAR) {
+						cnt++;
+						continue;
+					}
+					long long v;
+					if (!expr_arg(out, chunk_base + i, ag, a, &v, &my_oor)) {
+						continue; // a NULL operand, or out of range
+					}
 					cnt++;
-					continue;
+					const unsigned long long nl = lo + (unsigned long long)v;
+					hi += (v < 0 ? -1 : 0) + (nl < lo ? 1 : 0);
+					lo = nl;
+					mn = v < mn ? v : mn;
+					mx = v > mx ? v : mx;
 				}
-				const uint32_t row = ids[i];
-				if (ag.src.valid && !ag.src.valid[row]) {
-					continue; // NULLs take no part
+			} else {
+				const uint32_t *ids = out.ids + (uint64_t)ag.slot * out.slot_stride + (uint64_t)chunk * out.chunk_capacity;
+				for (uint32_t i = threadIdx.x; i < n; i += blockDim.x) {
+					if (ag.fn == POLR_AGG_COUNT_STAR) {
+						cnt++;
+						continue;
+					}
+					const uint32_t row = ids[i];
+					if (ag.src.valid && !ag.src.valid[row]) {
+						continue; // NULLs take no part
+					}
+					const long long v = load_col_cell(ag.src, row);
+					cnt++;
+					const unsigned long long nl = lo + (unsigned long long)v;
+					hi += (v < 0 ? -1 : 0) + (nl < lo ? 1 : 0); // sign extension of v + carry
+					lo = nl;
+					mn = v < mn ? v : mn;
+					mx = v > mx ? v : mx;
 				}
-				const long long v = load_col_cell(ag.src, row);
-				cnt++;
-				const unsigned long long nl = lo + (unsigned long long)v;
-				hi += (v < 0 ? -1 : 0) + (nl < lo ? 1 : 0); // sign extension of v + carry
-				lo = nl;
-				mn = v < mn ? v : mn;
-				mx = v > mx ? v : mx;
 			}
 		}
 		// wave reduction (128-bit add with carry, min, max, count)
@@ -76,6 +188,9 @@ __global__ __launch_bounds__(256) void polr_agg_kernel(DevOut out, uint32_t n_ch
 			wave_part[wave][a].mx = mx;
 			wave_part[wave][a].count = cnt;
 		}
+	}
+	if constexpr (EXPR) {
+		flush_oor(aggs.oor, my_oor);
 	}
 	__syncthreads();
 	if (threadIdx.x < aggs.n) {
@@ -152,6 +267,99 @@ static int build_agg_set(polr_pipeline *p, const polr_agg_spec *specs, uint32_t 
 	return POLR_OK;
 }
 
+// the expression form: POLR_E_INVALID for an unknown function or operator, a column out of range, a result width other than
+// 1 / 2 / 4 / 8 and a result type that cannot hold an operand type; POLR_E_UNSUPPORTED for operand columns other than integers
+// of up to 8 bytes (signed if 8) and for an unsigned 8-byte result
+static int build_expr_agg(polr_pipeline *p, const polr_agg_expr &s, uint32_t a, DevExprAgg *ag) {
+	if (s.fn > POLR_AGG_MAX) {
+		POLR_FAIL(p->ctx, POLR_E_INVALID, "aggregate %u: unknown function %u", a, s.fn);
+	}
+	ag->fn = s.fn;
+	ag->op = POLR_ARG_COLUMN;
+	if (s.fn == POLR_AGG_COUNT_STAR) {
+		return POLR_OK;
+	}
+	if (s.op > POLR_ARG_MUL) {
+		POLR_FAIL(p->ctx, POLR_E_INVALID, "aggregate %u: unknown operator %u", a, s.op);
+	}
+	ag->op = s.op;
+	const uint32_t n_operands = s.op == POLR_ARG_COLUMN ? 1u : 2u;
+	for (uint32_t x = 0; x < n_operands; x++) {
+		OutCol c;
+		int rc = polr_out_int_col(p, s.src_join[x], s.src_col[x], &c, "aggregate", a);
+		if (rc) {
+			return rc;
+		}
+		ag->src[x] = c.dev;
+		ag->slot[x] = c.slot;
+	}
+	if (s.op == POLR_ARG_COLUMN) {
+		ag->src[1] = ag->src[0];
+		ag->slot[1] = ag->slot[0];
+		return POLR_OK;
+	}
+	const uint32_t rw = s.result_width;
+	const bool rsigned = (s.result_flags & POLR_COL_SIGNED) != 0;
+	if (rw != 1 && rw != 2 && rw != 4 && rw != 8) {
+		POLR_FAIL(p->ctx, POLR_E_INVALID, "aggregate %u: result width %u (1, 2, 4 or 8 bytes)", a, rw);
+	}
+	if (rw == 8 && !rsigned) {
+		POLR_FAIL(p->ctx, POLR_E_UNSUPPORTED, "aggregate %u: an 8-byte result type must be signed", a);
+	}
+	for (uint32_t x = 0; x < 2; x++) { // (lossless implicit casts only: same signedness and no narrower, or unsigned into a wider signed)
+		const uint32_t w = ag->src[x].width;
+		const bool sgn = (ag->src[x].flags & 1u) != 0;
+		const bool holds = sgn == rsigned ? w <= rw : (!sgn && w < rw);
+		if (!holds) {
+			POLR_FAIL(p->ctx, POLR_E_INVALID, "aggregate %u: a %ssigned %u-byte result cannot hold every value of its %s operand (%ssigned, %u bytes)",
+			          a, rsigned ? "" : "un", rw, x ? "right" : "left", sgn ? "" : "un", w);
+		}
+	}
+	if (rsigned) {
+		ag->hi = (long long)(0x7FFFFFFFFFFFFFFFull >> (64u - 8u * rw));
+		ag->lo = -ag->hi - 1;
+	} else {
+		ag->lo = 0;
+		ag->hi = (long long)(0xFFFFFFFFFFFFFFFFull >> (64u - 8u * rw));
+	}
+	return POLR_OK;
+}
+
+static int build_expr_set(polr_pipeline *p, const polr_agg_expr *specs, uint32_t n_aggs, DevExprAggSet *set) {
+	memset(set, 0, sizeof(*set));
+	set->n = n_aggs;
+	for (uint32_t a = 0; a < n_aggs; a++) {
+		int rc = build_expr_agg(p, specs[a], a, &set->a[a]);
+		if (rc) {
+			return rc;
+		}
+	}
+	return POLR_OK;
+}
+
+// the sinks' host code serves both forms: exactly one of specs / exprs is given
+static uint32_t agg_fn(const polr_agg_spec *specs, const polr_agg_expr *exprs, uint32_t a) {
+	return exprs ? exprs[a].fn : specs[a].fn;
+}
+
+// the out-of-range counters of a call as the kernels left them -> POLR_E_RANGE, or POLR_OK when all are 0
+static int check_range(polr_ctx *ctx, const unsigned long long *oor, uint64_t *n_out_of_range) {
+	unsigned long long total = 0;
+	uint32_t first = POLR_MAX_AGGS;
+	for (uint32_t a = 0; a < POLR_MAX_AGGS; a++) {
+		total += oor[a];
+		first = oor[a] && first == POLR_MAX_AGGS ? a : first;
+	}
+	if (n_out_of_range) {
+		*n_out_of_range = total;
+	}
+	if (total) {
+		POLR_FAIL(ctx, POLR_E_RANGE, "aggregate %u: %llu arguments of this call lie outside their result type (the reference: "
+		          "OutOfRangeException, Overflow in addition / subtraction / multiplication); no result was written", first, total);
+	}
+	return POLR_OK;
+}
+
 // what the C ABI reports for an aggregate: COUNT is never NULL; the others are NULL when no row took part
 static polr_agg_value agg_value(uint32_t fn, __int128 sum, long long mn, long long mx, unsigned long long count) {
 	polr_agg_value v;
@@ -181,12 +389,9 @@ static polr_agg_value agg_value(uint32_t fn, __int128 sum, long long mn, long lo
 	return v;
 }
 
-extern "C" {
-
-int polr_out_aggregate(polr_out *o, void *stream, const polr_agg_spec *specs, uint32_t n_aggs,
-                       polr_agg_value *results) {
-	POLR_ENTRY();
-	if (!o || !specs || !results || n_aggs == 0) {
+static int aggregate_ungrouped(polr_out *o, void *stream, const polr_agg_spec *specs, const polr_agg_expr *exprs, uint32_t n_aggs,
+                               polr_agg_value *results, uint64_t *n_out_of_range) {
+	if (!o || (!specs && !exprs) || !results || n_aggs == 0) {
 		return POLR_E_INVALID;
 	}
 	polr_pipeline *p = o->pipe;
@@ -195,7 +400,8 @@ int polr_out_aggregate(polr_out *o, void *stream, const polr_agg_spec *specs, ui
 		POLR_FAIL(ctx, POLR_E_UNSUPPORTED, "at most %d aggregates per call", POLR_MAX_AGGS);
 	}
 	DevAggSet set;
-	int rc = build_agg_set(p, specs, n_aggs, &set);
+	DevExprAggSet eset;
+	int rc = exprs ? build_expr_set(p, exprs, n_aggs, &eset) : build_agg_set(p, specs, n_aggs, &set);
 	if (rc) {
 		return rc;
 	}
@@ -207,15 +413,33 @@ int polr_out_aggregate(polr_out *o, void *stream, const polr_agg_spec *specs, ui
 	}
 	const uint32_t n_blocks = std::max<uint32_t>(1, std::min<uint32_t>(o->n_chunks, (uint32_t)ctx->n_cus * 8));
 	std::vector<AggPartial> host((size_t)n_blocks * n_aggs);
+	unsigned long long h_oor[POLR_MAX_AGGS] = {0};
 	if (o->n_chunks) {
 		AggPartial *part = nullptr;
-		HIPCHK(ctx, hipMalloc((void **)&part, host.size() * sizeof(AggPartial)));
-		hipLaunchKernelGGL(polr_agg_kernel, dim3(n_blocks), dim3(256), 0, st, o->dev, o->n_chunks, set, part);
-		hipError_t e = hipMemcpyAsync(host.data(), part, host.size() * sizeof(AggPartial), hipMemcpyDeviceToHost, st);
+		// (the expression form: its out-of-range counters behind the partials)
+		HIPCHK(ctx, hipMalloc((void **)&part, host.size() * sizeof(AggPartial) + (exprs ? sizeof(h_oor) : 0)));
+		hipError_t e = hipSuccess;
+		if (exprs) {
+			eset.oor = (unsigned long long *)(part + host.size());
+			e = hipMemsetAsync(eset.oor, 0, sizeof(h_oor), st);
+			if (e == hipSuccess) {
+				hipLaunchKernelGGL(polr_agg_kernel<DevExprAggSet>, dim3(n_blocks), dim3(256), 0, st, o->dev, o->n_chunks, eset, part);
+				e = hipMemcpyAsync(h_oor, eset.oor, sizeof(h_oor), hipMemcpyDeviceToHost, st);
+			}
+		} else {
+			hipLaunchKernelGGL(polr_agg_kernel<DevAggSet>, dim3(n_blocks), dim3(256), 0, st, o->dev, o->n_chunks, set, part);
+		}
+		e = e == hipSuccess ? hipMemcpyAsync(host.data(), part, host.size() * sizeof(AggPartial), hipMemcpyDeviceToHost, st) : e;
 		e = e == hipSuccess ? hipStreamSynchronize(st) : e;
 		hipFree(part);
 		if (e != hipSuccess) {
 			POLR_FAIL(ctx, POLR_E_HIP, "aggregate failed: %s", hipGetErrorString(e));
+		}
+	}
+	if (exprs) {
+		rc = check_range(ctx, h_oor, n_out_of_range);
+		if (rc) {
+			return rc;
 		}
 	}
 	for (uint32_t a = 0; a < n_aggs; a++) {
@@ -229,9 +453,29 @@ int polr_out_aggregate(polr_out *o, void *stream, const polr_agg_spec *specs, ui
 			mx = r.mx > mx ? r.mx : mx;
 			cnt += r.count;
 		}
-		results[a] = agg_value(specs[a].fn, sum, mn, mx, cnt);
+		results[a] = agg_value(agg_fn(specs, exprs, a), sum, mn, mx, cnt);
 	}
 	return POLR_OK;
+}
+
+extern "C" {
+
+int polr_out_aggregate(polr_out *o, void *stream, const polr_agg_spec *specs, uint32_t n_aggs,
+                       polr_agg_value *results) {
+	POLR_ENTRY();
+	if (!specs) {
+		return POLR_E_INVALID;
+	}
+	return aggregate_ungrouped(o, stream, specs, nullptr, n_aggs, results, nullptr);
+}
+
+int polr_out_aggregate_expr(polr_out *o, void *stream, const polr_agg_expr *specs, uint32_t n_aggs, polr_agg_value *results,
+                            uint64_t *n_out_of_range) {
+	POLR_ENTRY();
+	if (!specs) {
+		return POLR_E_INVALID;
+	}
+	return aggregate_ungrouped(o, stream, nullptr, specs, n_aggs, results, n_out_of_range);
 }
 
 } // extern "C"
@@ -271,9 +515,12 @@ __global__ __launch_bounds__(256) void polr_group_init_kernel(GroupCell *cells, 
 	}
 }
 
+template <class SET>
 __global__ __launch_bounds__(256) void polr_group_agg_kernel(DevOut out, uint32_t n_chunks, DevGroupSet groups,
-                                                             DevAggSet aggs, GroupCell *__restrict__ table,
+                                                             SET aggs, GroupCell *__restrict__ table,
                                                              unsigned long long *__restrict__ dropped, int use_lds) {
+	constexpr bool EXPR = is_expr_set<SET>::value;
+	OorCount my_oor = {0, 0xFFFFFFFFu};
 	extern __shared__ __attribute__((aligned(16))) unsigned char lds_raw[];
 	GroupCell *local = (GroupCell *)lds_raw;
 	const uint32_t n_cells = groups.n_groups * aggs.n;
@@ -309,25 +556,43 @@ __global__ __launch_bounds__(256) void polr_group_agg_kernel(DevOut out, uint32_
 			}
 			if (!ok) {
 				my_dropped++;
+				if constexpr (EXPR) { // (the reference's projection sees the row before the GROUP BY does: its range is checked)
+					for (uint32_t a = 0; a < aggs.n; a++) {
+						long long v;
+						if (aggs.a[a].fn != POLR_AGG_COUNT_STAR) {
+							expr_arg(out, chunk_base + i, aggs.a[a], a, &v, &my_oor);
+						}
+					}
+				}
 				continue;
 			}
 			for (uint32_t a = 0; a < aggs.n; a++) {
-				const DevAgg &ag = aggs.a[a];
+				const auto &ag = aggs.a[a];
 				GroupCell *c = &dst[g * aggs.n + a];
 				if (ag.fn == POLR_AGG_COUNT_STAR) {
 					atomicAdd(&c->count, 1ull);
 					continue;
 				}
-				const uint32_t row = out.ids[(uint64_t)ag.slot * out.slot_stride + chunk_base + i];
-				if (ag.src.valid && !ag.src.valid[row]) {
-					continue;
+				if constexpr (EXPR) {
+					long long v;
+					if (expr_arg(out, chunk_base + i, ag, a, &v, &my_oor)) {
+						cell_add(c, v);
+					}
+				} else {
+					const uint32_t row = out.ids[(uint64_t)ag.slot * out.slot_stride + chunk_base + i];
+					if (ag.src.valid && !ag.src.valid[row]) {
+						continue;
+					}
+					cell_add(c, load_col_cell(ag.src, row));
 				}
-				cell_add(c, load_col_cell(ag.src, row));
 			}
 		}
 	}
 	if (my_dropped) {
 		atomicAdd(dropped, my_dropped);
+	}
+	if constexpr (EXPR) {
+		flush_oor(aggs.oor, my_oor);
 	}
 	if (use_lds) {
 		__syncthreads();
@@ -348,11 +613,10 @@ static polr_agg_value cell_value(const GroupCell &c, uint32_t fn) {
 	return agg_value(fn, ((__int128)c.hi32 << 32) + (__int128)c.lo32, c.mn, c.mx, c.count);
 }
 
-extern "C" int polr_out_aggregate_grouped(polr_out *o, void *stream, const polr_group_key *keys, uint32_t n_keys,
-                                          const polr_agg_spec *specs, uint32_t n_aggs, polr_agg_value *results,
-                                          uint64_t n_groups, uint64_t *n_dropped) {
-	POLR_ENTRY();
-	if (!o || !keys || !specs || !results || n_keys == 0 || n_aggs == 0) {
+static int aggregate_grouped(polr_out *o, void *stream, const polr_group_key *keys, uint32_t n_keys, const polr_agg_spec *specs,
+                             const polr_agg_expr *exprs, uint32_t n_aggs, polr_agg_value *results, uint64_t n_groups,
+                             uint64_t *n_dropped, uint64_t *n_out_of_range) {
+	if (!o || !keys || (!specs && !exprs) || !results || n_keys == 0 || n_aggs == 0) {
 		return POLR_E_INVALID;
 	}
 	polr_pipeline *p = o->pipe;
@@ -388,7 +652,8 @@ extern "C" int polr_out_aggregate_grouped(polr_out *o, void *stream, const polr_
 	}
 	gs.n_groups = (uint32_t)groups;
 	DevAggSet as;
-	int rc = build_agg_set(p, specs, n_aggs, &as);
+	DevExprAggSet es;
+	int rc = exprs ? build_expr_set(p, exprs, n_aggs, &es) : build_agg_set(p, specs, n_aggs, &as);
 	if (rc) {
 		return rc;
 	}
@@ -400,23 +665,30 @@ extern "C" int polr_out_aggregate_grouped(polr_out *o, void *stream, const polr_
 	}
 	const uint32_t n_cells = (uint32_t)groups * n_aggs;
 	std::vector<GroupCell> host(n_cells);
-	unsigned long long h_dropped = 0;
+	unsigned long long h_cnt[1 + POLR_MAX_AGGS] = {0}; // [0] dropped rows, [1 ..] the expression form's out-of-range counters
+	const size_t cnt_bytes = exprs ? sizeof(h_cnt) : 8;
 	GroupCell *table = nullptr;
 	unsigned long long *dropped = nullptr;
 	hipError_t e = hipMalloc((void **)&table, (size_t)n_cells * sizeof(GroupCell));
-	e = e == hipSuccess ? hipMalloc((void **)&dropped, 8) : e;
-	e = e == hipSuccess ? hipMemsetAsync(dropped, 0, 8, st) : e;
+	e = e == hipSuccess ? hipMalloc((void **)&dropped, cnt_bytes) : e;
+	e = e == hipSuccess ? hipMemsetAsync(dropped, 0, cnt_bytes, st) : e;
+	es.oor = dropped + 1;
 	if (e == hipSuccess) {
 		hipLaunchKernelGGL(polr_group_init_kernel, dim3((n_cells + 255) / 256), dim3(256), 0, st, table, (uint64_t)n_cells);
 		if (o->n_chunks) {
 			const int use_lds = n_cells <= POLR_GROUP_LDS_CELLS;
 			const uint32_t n_blocks = std::max<uint32_t>(1, std::min<uint32_t>(o->n_chunks, (uint32_t)ctx->n_cus * 4));
-			hipLaunchKernelGGL(polr_group_agg_kernel, dim3(n_blocks), dim3(256),
-			                   use_lds ? (size_t)n_cells * sizeof(GroupCell) : 0, st, o->dev, o->n_chunks, gs, as, table,
-			                   dropped, use_lds);
+			const size_t lds = use_lds ? (size_t)n_cells * sizeof(GroupCell) : 0;
+			if (exprs) {
+				hipLaunchKernelGGL(polr_group_agg_kernel<DevExprAggSet>, dim3(n_blocks), dim3(256), lds, st, o->dev, o->n_chunks, gs, es,
+				                   table, dropped, use_lds);
+			} else {
+				hipLaunchKernelGGL(polr_group_agg_kernel<DevAggSet>, dim3(n_blocks), dim3(256), lds, st, o->dev, o->n_chunks, gs, as,
+				                   table, dropped, use_lds);
+			}
 		}
 		e = hipMemcpyAsync(host.data(), table, (size_t)n_cells * sizeof(GroupCell), hipMemcpyDeviceToHost, st);
-		e = e == hipSuccess ? hipMemcpyAsync(&h_dropped, dropped, 8, hipMemcpyDeviceToHost, st) : e;
+		e = e == hipSuccess ? hipMemcpyAsync(h_cnt, dropped, cnt_bytes, hipMemcpyDeviceToHost, st) : e;
 		e = e == hipSuccess ? hipStreamSynchronize(st) : e;
 	}
 	if (table) {
@@ -428,13 +700,39 @@ extern "C" int polr_out_aggregate_grouped(polr_out *o, void *stream, const polr_
 	if (e != hipSuccess) {
 		POLR_FAIL(ctx, POLR_E_HIP, "grouped aggregate failed: %s", hipGetErrorString(e));
 	}
+	if (exprs) {
+		rc = check_range(ctx, h_cnt + 1, n_out_of_range);
+		if (rc) {
+			return rc;
+		}
+	}
 	for (uint32_t i = 0; i < n_cells; i++) {
-		results[i] = cell_value(host[i], specs[i % n_aggs].fn);
+		results[i] = cell_value(host[i], agg_fn(specs, exprs, i % n_aggs));
 	}
 	if (n_dropped) {
-		*n_dropped = h_dropped;
+		*n_dropped = h_cnt[0];
 	}
 	return POLR_OK;
+}
+
+extern "C" int polr_out_aggregate_grouped(polr_out *o, void *stream, const polr_group_key *keys, uint32_t n_keys,
+                                          const polr_agg_spec *specs, uint32_t n_aggs, polr_agg_value *results,
+                                          uint64_t n_groups, uint64_t *n_dropped) {
+	POLR_ENTRY();
+	if (!specs) {
+		return POLR_E_INVALID;
+	}
+	return aggregate_grouped(o, stream, keys, n_keys, specs, nullptr, n_aggs, results, n_groups, n_dropped, nullptr);
+}
+
+extern "C" int polr_out_aggregate_grouped_expr(polr_out *o, void *stream, const polr_group_key *keys, uint32_t n_keys,
+                                               const polr_agg_expr *specs, uint32_t n_aggs, polr_agg_value *results,
+                                               uint64_t n_groups, uint64_t *n_dropped, uint64_t *n_out_of_range) {
+	POLR_ENTRY();
+	if (!specs) {
+		return POLR_E_INVALID;
+	}
+	return aggregate_grouped(o, stream, keys, n_keys, nullptr, specs, n_aggs, results, n_groups, n_dropped, n_out_of_range);
 }
 
 
@@ -1024,9 +1322,11 @@ struct HashAggTable {
 
 #define POLR_NO_SLOT 0xFFFFFFFFu
 
-template <bool STR>
-__global__ __launch_bounds__(256) void polr_hash_agg_kernel(DevOut out, uint32_t n_chunks, DevGroupSet groups, DevAggSet aggs,
+template <bool STR, class SET>
+__global__ __launch_bounds__(256) void polr_hash_agg_kernel(DevOut out, uint32_t n_chunks, DevGroupSet groups, SET aggs,
                                                             HashAggTable t, uint4 *reps, uint32_t str_mask) {
+	constexpr bool EXPR = is_expr_set<SET>::value;
+	OorCount my_oor = {0, 0xFFFFFFFFu};
 	const uint32_t lane = threadIdx.x & 63u;
 	for (uint32_t chunk = blockIdx.x; chunk < n_chunks; chunk += gridDim.x) {
 		const uint32_t n = out.chunk_count[chunk];
@@ -1129,10 +1429,15 @@ __global__ __launch_bounds__(256) void polr_hash_agg_kernel(DevOut out, uint32_t
 				todo &= ~peers;
 			}
 			for (uint32_t a = 0; a < aggs.n; a++) {
-				const DevAgg &ag = aggs.a[a];
+				const auto &ag = aggs.a[a];
 				bool have = s32 != POLR_NO_SLOT;
 				long long v = 0;
-				if (have && ag.fn != POLR_AGG_COUNT_STAR) {
+				if constexpr (EXPR) {
+					if (active && ag.fn != POLR_AGG_COUNT_STAR) { // (a row that found no slot is checked all the same)
+						have = expr_arg(out, chunk_base + i, ag, a, &v, &my_oor) && have;
+						v = have ? v : 0;
+					}
+				} else if (have && ag.fn != POLR_AGG_COUNT_STAR) {
 					const uint32_t row = out.ids[(uint64_t)ag.slot * out.slot_stride + chunk_base + i];
 					if (ag.src.valid && !ag.src.valid[row]) {
 						have = false; // NULLs take no part
@@ -1195,6 +1500,9 @@ __global__ __launch_bounds__(256) void polr_hash_agg_kernel(DevOut out, uint32_t
 				}
 			}
 		}
+	}
+	if constexpr (EXPR) {
+		flush_oor(aggs.oor, my_oor);
 	}
 }
 
@@ -1266,11 +1574,12 @@ extern "C" int polr_out_column_width(polr_out *o, int32_t src_join, uint32_t src
 }
 
 // both entry points of the general GROUP BY; strings: VARCHAR group columns are allowed, their values go to str_bytes
+// (exactly one of specs / exprs; n_out_of_range: the expression form's, may be NULL)
 static int aggregate_hashed(polr_out *o, void *stream, const polr_group_key *cols, uint32_t n_cols, const polr_agg_spec *specs,
-                            uint32_t n_aggs, uint64_t max_groups, int64_t *group_keys, uint32_t *group_nulls,
-                            polr_agg_value *results, uint64_t *n_groups, bool strings, uint8_t *str_bytes, uint64_t str_cap,
-                            uint64_t *str_used) {
-	if (!o || !cols || !specs || !group_keys || !group_nulls || !results || !n_groups || n_cols == 0 || n_aggs == 0 ||
+                            const polr_agg_expr *exprs, uint32_t n_aggs, uint64_t max_groups, int64_t *group_keys,
+                            uint32_t *group_nulls, polr_agg_value *results, uint64_t *n_groups, bool strings, uint8_t *str_bytes,
+                            uint64_t str_cap, uint64_t *str_used, uint64_t *n_out_of_range) {
+	if (!o || !cols || (!specs && !exprs) || !group_keys || !group_nulls || !results || !n_groups || n_cols == 0 || n_aggs == 0 ||
 	    max_groups == 0 || (strings && (!str_used || (!str_bytes && str_cap)))) {
 		return POLR_E_INVALID;
 	}
@@ -1302,7 +1611,8 @@ static int aggregate_hashed(polr_out *o, void *stream, const polr_group_key *col
 		gs.k[q].slot = gcol[q].slot;
 	}
 	DevAggSet as;
-	int rc = build_agg_set(p, specs, n_aggs, &as);
+	DevExprAggSet es;
+	int rc = exprs ? build_expr_set(p, exprs, n_aggs, &es) : build_agg_set(p, specs, n_aggs, &as);
 	if (rc) {
 		return rc;
 	}
@@ -1331,7 +1641,7 @@ static int aggregate_hashed(polr_out *o, void *stream, const polr_group_key *col
 	// one allocation: state, nulls, counters, keys, representative cells (VARCHAR only), group cells, and the compacted
 	// outputs behind them
 	const size_t rep_bytes = str_mask ? 16 : 0;
-	const size_t b_state = capacity * 4, b_nulls = capacity * 4, b_cnt = 64, b_keys = capacity * n_cols * 8,
+	const size_t b_state = capacity * 4, b_nulls = capacity * 4, b_cnt = 128, b_keys = capacity * n_cols * 8,
 	             b_reps = capacity * n_cols * rep_bytes, b_cells = capacity * n_aggs * sizeof(GroupCell),
 	             b_okeys = (max_groups * n_cols * 8 + 15) & ~(size_t)15, // (the uint4 cells behind it stay 16-byte aligned)
 	             b_oreps = max_groups * n_cols * rep_bytes, b_onulls = (max_groups * 4 + 15) & ~(size_t)15,
@@ -1343,8 +1653,10 @@ static int aggregate_hashed(polr_out *o, void *stream, const polr_group_key *col
 	at += b_state;
 	t.nulls = (uint32_t *)at;
 	at += b_nulls;
-	unsigned long long *cnt = (unsigned long long *)at; // [0] groups, [1] overflow, [2] compaction cursor
+	// [0] groups, [1] overflow, [2] compaction cursor, [8 .. 15] the expression form's out-of-range counters
+	unsigned long long *cnt = (unsigned long long *)at;
 	at += b_cnt;
+	es.oor = cnt + 8;
 	t.n_groups = cnt;
 	t.overflow = cnt + 1;
 	t.keys = (long long *)at;
@@ -1361,15 +1673,23 @@ static int aggregate_hashed(polr_out *o, void *stream, const polr_group_key *col
 	at += b_onulls;
 	GroupCell *ocells = (GroupCell *)at;
 	hipError_t e = hipMemsetAsync(base, 0, b_state + b_nulls + b_cnt, st);
-	unsigned long long h_cnt[3] = {0, 0, 0};
+	unsigned long long h_cnt[8 + POLR_MAX_AGGS] = {0};
 	if (e == hipSuccess) {
 		hipLaunchKernelGGL(polr_group_init_kernel, dim3(256), dim3(256), 0, st, t.cells, capacity * n_aggs);
 		if (o->n_chunks) {
 			const dim3 grid(std::min<uint32_t>(o->n_chunks, 2048u));
-			if (str_mask) {
-				hipLaunchKernelGGL(polr_hash_agg_kernel<true>, grid, dim3(256), 0, st, o->dev, o->n_chunks, gs, as, t, reps, str_mask);
+			if (exprs && str_mask) {
+				hipLaunchKernelGGL((polr_hash_agg_kernel<true, DevExprAggSet>), grid, dim3(256), 0, st, o->dev, o->n_chunks, gs, es, t, reps,
+				                   str_mask);
+			} else if (exprs) {
+				hipLaunchKernelGGL((polr_hash_agg_kernel<false, DevExprAggSet>), grid, dim3(256), 0, st, o->dev, o->n_chunks, gs, es, t, reps,
+				                   str_mask);
+			} else if (str_mask) {
+				hipLaunchKernelGGL((polr_hash_agg_kernel<true, DevAggSet>), grid, dim3(256), 0, st, o->dev, o->n_chunks, gs, as, t, reps,
+				                   str_mask);
 			} else {
-				hipLaunchKernelGGL(polr_hash_agg_kernel<false>, grid, dim3(256), 0, st, o->dev, o->n_chunks, gs, as, t, reps, str_mask);
+				hipLaunchKernelGGL((polr_hash_agg_kernel<false, DevAggSet>), grid, dim3(256), 0, st, o->dev, o->n_chunks, gs, as, t, reps,
+				                   str_mask);
 			}
 		}
 		hipLaunchKernelGGL(polr_hash_agg_compact_kernel, dim3(256), dim3(256), 0, st, t, n_cols, n_aggs, okeys, onulls, ocells, cnt + 2,
@@ -1378,7 +1698,11 @@ static int aggregate_hashed(polr_out *o, void *stream, const polr_group_key *col
 		e = e == hipSuccess ? hipStreamSynchronize(st) : e;
 	}
 	const bool too_many = h_cnt[1] || h_cnt[0] > max_groups;
-	const uint64_t g_n = too_many ? 0 : h_cnt[0];
+	bool out_of_range = false; // (the reference's query fails: nothing is copied to the caller)
+	for (uint32_t a = 0; a < POLR_MAX_AGGS; a++) {
+		out_of_range = out_of_range || h_cnt[8 + a] != 0;
+	}
+	const uint64_t g_n = too_many || out_of_range ? 0 : h_cnt[0];
 	std::vector<GroupCell> hcells(g_n * n_aggs);
 	// integer columns only: keys and NULL bits go to the caller's arrays at once; with VARCHAR columns they are staged here
 	// until the strings' records fit, so that an arena too small leaves the caller's arrays as they were
@@ -1427,6 +1751,12 @@ static int aggregate_hashed(polr_out *o, void *stream, const polr_group_key *col
 	if (e != hipSuccess) {
 		POLR_FAIL(ctx, POLR_E_HIP, "hash aggregate failed: %s", hipGetErrorString(e));
 	}
+	if (exprs) {
+		rc = check_range(ctx, h_cnt + 8, n_out_of_range);
+		if (rc) {
+			return rc;
+		}
+	}
 	*n_groups = h_cnt[0];
 	if (too_many) {
 		POLR_FAIL(ctx, POLR_E_OVERFLOW, "the result has %llu groups or more, the caller made room for %llu",
@@ -1445,7 +1775,7 @@ static int aggregate_hashed(polr_out *o, void *stream, const polr_group_key *col
 	}
 	for (uint64_t g = 0; g < g_n; g++) {
 		for (uint32_t a = 0; a < n_aggs; a++) {
-			results[g * n_aggs + a] = cell_value(hcells[g * n_aggs + a], specs[a].fn);
+			results[g * n_aggs + a] = cell_value(hcells[g * n_aggs + a], agg_fn(specs, exprs, a));
 		}
 	}
 	return POLR_OK;
@@ -1455,8 +1785,11 @@ extern "C" int polr_out_aggregate_hashed(polr_out *o, void *stream, const polr_g
                                          const polr_agg_spec *specs, uint32_t n_aggs, uint64_t max_groups, int64_t *group_keys,
                                          uint32_t *group_nulls, polr_agg_value *results, uint64_t *n_groups) {
 	POLR_ENTRY();
-	return aggregate_hashed(o, stream, cols, n_cols, specs, n_aggs, max_groups, group_keys, group_nulls, results, n_groups, false,
-	                        nullptr, 0, nullptr);
+	if (!specs) {
+		return POLR_E_INVALID;
+	}
+	return aggregate_hashed(o, stream, cols, n_cols, specs, nullptr, n_aggs, max_groups, group_keys, group_nulls, results, n_groups,
+	                        false, nullptr, 0, nullptr, nullptr);
 }
 
 extern "C" int polr_out_aggregate_hashed_str(polr_out *o, void *stream, const polr_group_key *cols, uint32_t n_cols,
@@ -1464,6 +1797,21 @@ extern "C" int polr_out_aggregate_hashed_str(polr_out *o, void *stream, const po
                                              uint32_t *group_nulls, polr_agg_value *results, uint64_t *n_groups, uint8_t *str_bytes,
                                              uint64_t str_cap, uint64_t *str_used) {
 	POLR_ENTRY();
-	return aggregate_hashed(o, stream, cols, n_cols, specs, n_aggs, max_groups, group_keys, group_nulls, results, n_groups, true,
-	                        str_bytes, str_cap, str_used);
+	if (!specs) {
+		return POLR_E_INVALID;
+	}
+	return aggregate_hashed(o, stream, cols, n_cols, specs, nullptr, n_aggs, max_groups, group_keys, group_nulls, results, n_groups,
+	                        true, str_bytes, str_cap, str_used, nullptr);
+}
+
+extern "C" int polr_out_aggregate_hashed_expr(polr_out *o, void *stream, const polr_group_key *cols, uint32_t n_cols,
+                                              const polr_agg_expr *specs, uint32_t n_aggs, uint64_t max_groups, int64_t *group_keys,
+                                              uint32_t *group_nulls, polr_agg_value *results, uint64_t *n_groups,
+                                              uint8_t *str_bytes, uint64_t str_cap, uint64_t *str_used, uint64_t *n_out_of_range) {
+	POLR_ENTRY();
+	if (!specs) {
+		return POLR_E_INVALID;
+	}
+	return aggregate_hashed(o, stream, cols, n_cols, nullptr, specs, n_aggs, max_groups, group_keys, group_nulls, results, n_groups,
+	                        true, str_bytes, str_cap, str_used, n_out_of_range);
 }

@@ -19,6 +19,7 @@ CMP_PRED = {"=": 0, "==": 0, "<>": 1, "!=": 1, "<": 2, ">": 3, "<=": 4, ">=": 5,
 COL_SIGNED, COL_DEVICE = 1, 2
 
 OK, E_NO_DEVICE, E_INVALID, E_UNSUPPORTED, E_HIP, E_DUPLICATE, E_OVERFLOW = 0, -1, -2, -3, -4, -5, -6
+E_RANGE = -7  # an aggregate argument `left OP right` outside its result type (PolrError.count: how many)
 
 ROUTING = {"alternate": 0, "adaptive_reinit": 1, "dynamic": 2, "init_once": 3, "opportunistic": 4,
            "default_path": 5, "backpressure": 6, "exponential_backoff": 7}
@@ -39,13 +40,15 @@ EXPORTS = [
     "polr_out_fuse_grouped", "polr_out_fused_result", "polr_out_aggregate_hashed",
     "polr_ht_set_payload_heaps", "polr_pipeline_set_probe_heaps", "polr_out_aggregate_hashed_str", "polr_out_column_width",
     "polr_ht_encode_dictionary", "polr_ht_fetch_dictionary",
+    "polr_out_aggregate_expr", "polr_out_aggregate_grouped_expr", "polr_out_aggregate_hashed_expr",
 ]
 
 
 class PolrError(RuntimeError):
-    def __init__(self, code, text):
+    def __init__(self, code, text, count=None):
         super().__init__("polr error %d: %s" % (code, text))
         self.code = code
+        self.count = count  # E_RANGE: the arguments out of range (*n_out_of_range)
 
 
 class Col(C.Structure):
@@ -102,6 +105,33 @@ class AggValue(C.Structure):
 
 
 AGG = {"count_star": 0, "count": 1, "sum": 2, "min": 3, "max": 4}
+
+
+class AggExpr(C.Structure):
+    """polr_agg_expr: an aggregate whose argument is a column or `left OP right`"""
+    _fields_ = [("fn", C.c_uint32), ("op", C.c_uint32), ("src_join", C.c_int32 * 2), ("src_col", C.c_uint32 * 2),
+                ("result_width", C.c_uint32), ("result_flags", C.c_uint32)]
+
+
+ARG = {"column": 0, "+": 1, "-": 2, "*": 3}
+
+
+def make_agg_exprs(specs):
+    """[(fn, op, (join, col), (join, col) or None, result_dtype or None)] -> polr_agg_expr array.  op in ARG (or a number);
+    result_dtype: anything numpy.dtype() takes, the type the reference's binder gave the expression; with op "column" the
+    right operand and the result type are ignored (None will do)"""
+    arr = (AggExpr * max(len(specs), 1))()
+    for i, (fn, op, left, right, rtype) in enumerate(specs):
+        arr[i].fn = AGG[fn] if isinstance(fn, str) else fn
+        arr[i].op = ARG[op] if isinstance(op, str) else op
+        right = right if right is not None else left
+        arr[i].src_join[0], arr[i].src_col[0] = left
+        arr[i].src_join[1], arr[i].src_col[1] = right
+        if rtype is not None:
+            dt = np.dtype(rtype)
+            arr[i].result_width = dt.itemsize
+            arr[i].result_flags = COL_SIGNED if dt.kind == "i" else 0
+    return arr
 
 
 class LaunchInfo(C.Structure):
@@ -205,6 +235,9 @@ def load():
     L.polr_out_aggregate_hashed.argtypes = [vp, vp, vp, u32, vp, u32, C.c_uint64, vp, vp, vp, vp]
     L.polr_out_column_width.argtypes = [vp, C.c_int32, u32, P(u32)]
     L.polr_out_aggregate_hashed_str.argtypes = [vp, vp, vp, u32, vp, u32, C.c_uint64, vp, vp, vp, vp, vp, C.c_uint64, vp]
+    L.polr_out_aggregate_expr.argtypes = [vp, vp, vp, u32, vp, vp]
+    L.polr_out_aggregate_grouped_expr.argtypes = [vp, vp, vp, u32, vp, u32, vp, C.c_uint64, vp, vp]
+    L.polr_out_aggregate_hashed_expr.argtypes = [vp, vp, vp, u32, vp, u32, C.c_uint64, vp, vp, vp, vp, vp, C.c_uint64, vp, vp]
     L.polr_ht_encode_dictionary.argtypes = [vp, u32, vp, P(u32), P(u32), P(u32)]
     L.polr_ht_fetch_dictionary.argtypes = [vp, u32, vp, vp, u64, vp, u64, P(u64)]
     L.polr_out_fused_result.argtypes = [vp, vp, vp, C.c_uint64, vp]
@@ -289,6 +322,12 @@ class Context:
     def check(self, rc):
         if rc != OK:
             raise PolrError(rc, self.L.polr_last_error(self.h).decode())
+
+    def check_range(self, rc, n_out_of_range):
+        """check() for the *_expr sinks: POLR_E_RANGE carries the count of arguments out of range"""
+        if rc == E_RANGE:
+            raise PolrError(rc, self.L.polr_last_error(self.h).decode(), count=n_out_of_range.value)
+        self.check(rc)
 
     def sync(self, stream=None):
         self.check(self.L.polr_ctx_sync(self.h, stream))
@@ -696,6 +735,77 @@ class Output:
                 cap = used.value
                 continue
             self.ctx.check(rc)
+            break
+        raw = arena.tobytes()
+        is_str = [self._col_width(sj, sc) == 16 for sj, sc in cols]
+        out = {}
+        for g in range(n.value):
+            key = []
+            for c in range(nk):
+                if (nulls[g] >> c) & 1:
+                    key.append(None)
+                elif is_str[c]:
+                    at = int(keys[g, c])
+                    ln = int.from_bytes(raw[at:at + 4], "little")
+                    key.append(raw[at + 4:at + 4 + ln])
+                else:
+                    key.append(int(keys[g, c]))
+            out[tuple(key)] = [None if res[g * na + a].is_null else (res[g * na + a].hi << 64) + (res[g * na + a].lo & 0xFFFFFFFFFFFFFFFF)
+                               for a in range(na)]
+        return out
+
+    def aggregate_expr(self, specs, stream=None):
+        """polr_out_aggregate_expr: ungrouped aggregates whose argument is a column or `left OP right`.  specs = [(fn, op,
+        (join, col), (join, col), result_dtype)] (make_agg_exprs) -> [python int or None]; an argument outside result_dtype
+        for some output row: PolrError with code E_RANGE and .count"""
+        n = len(specs)
+        arr = make_agg_exprs(specs)
+        res = (AggValue * n)()
+        oor = C.c_uint64()
+        self.ctx.check_range(self.ctx.L.polr_out_aggregate_expr(self.h, stream, arr, n, res, C.byref(oor)), oor)
+        return [None if r.is_null else (r.hi << 64) + (r.lo & 0xFFFFFFFFFFFFFFFF) for r in res]
+
+    def aggregate_grouped_expr(self, keys, specs, stream=None):
+        """polr_out_aggregate_grouped_expr: keys as in aggregate_grouped, specs as in aggregate_expr -> (values, counts,
+        n_dropped) as aggregate_grouped"""
+        nk, na = len(keys), len(specs)
+        ka = (GroupKey * nk)()
+        n_groups = 1
+        for i, (sj, sc, mn, nv) in enumerate(keys):
+            ka[i].src_join, ka[i].src_col, ka[i].min_value, ka[i].n_values = sj, sc, int(mn), int(nv)
+            n_groups *= int(nv)
+        sa = make_agg_exprs(specs)
+        res = (AggValue * (n_groups * na))()
+        dropped, oor = C.c_uint64(), C.c_uint64()
+        self.ctx.check_range(self.ctx.L.polr_out_aggregate_grouped_expr(self.h, stream, ka, nk, sa, na, res, n_groups,
+                                                                        C.byref(dropped), C.byref(oor)), oor)
+        vals = [[None if res[g * na + a].is_null else (res[g * na + a].hi << 64) + (res[g * na + a].lo & 0xFFFFFFFFFFFFFFFF)
+                 for a in range(na)] for g in range(n_groups)]
+        counts = [[res[g * na + a].count for a in range(na)] for g in range(n_groups)]
+        return vals, counts, dropped.value
+
+    def aggregate_hashed_expr(self, cols, specs, max_groups, str_cap=None, stream=None):
+        """polr_out_aggregate_hashed_expr: the general GROUP BY (integer and VARCHAR group columns, as aggregate_hashed_str)
+        with specs as in aggregate_expr -> {group key tuple: [value per aggregate]}"""
+        nk, na = len(cols), len(specs)
+        ka = (GroupKey * nk)()
+        for i, (sj, sc) in enumerate(cols):
+            ka[i].src_join, ka[i].src_col = sj, sc
+        sa = make_agg_exprs(specs)
+        keys = np.zeros((max_groups, nk), dtype=np.int64)
+        nulls = np.zeros((max_groups,), dtype=np.uint32)
+        res = (AggValue * (max_groups * na))()
+        n, used, oor = C.c_uint64(), C.c_uint64(), C.c_uint64()
+        cap = max(4096, 24 * max_groups) if str_cap is None else int(str_cap)
+        for attempt in (0, 1):
+            arena = np.zeros((cap,), dtype=np.uint8)
+            rc = self.ctx.L.polr_out_aggregate_hashed_expr(self.h, stream, ka, nk, sa, na, max_groups, keys.ctypes.data,
+                                                           nulls.ctypes.data, res, C.byref(n), arena.ctypes.data, cap,
+                                                           C.byref(used), C.byref(oor))
+            if rc == E_OVERFLOW and attempt == 0 and used.value > cap:  # (the strings did not fit; the groups did)
+                cap = used.value
+                continue
+            self.ctx.check_range(rc, oor)
             break
         raw = arena.tobytes()
         is_str = [self._col_width(sj, sc) == 16 for sj, sc in cols]

@@ -503,6 +503,55 @@ def ssb_q11(sf=0.2, seed=SEED):
             "sql_where": "d_year = 1993 AND lo_discount >= 1 AND lo_discount <= 3 AND lo_quantity < 25"}
 
 
+def ssb_flight1(sf=0.2, seed=SEED):
+    """SSB flight 1 as shipped (benchmark/ssb/queries/q1-1.sql .. q1-3.sql): SELECT SUM(lo_extendedprice * lo_discount)
+    FROM lineorder, date WHERE lo_orderdate = d_datekey AND <a date predicate> AND <discount and quantity ranges>.
+    The lineorder of ssb_q11; its date dimension with two more columns derived from the synthetic day index i (the
+    position of the day within its d_year: month = a twelfth of the year's days, week = seven days):
+    d_yearmonthnum = d_year * 100 + month (1..12) and d_weeknuminyear (1..53).
+
+    -> {"probe": lineorder, "date_full": the whole dimension, "queries": {"q1.1" | "q1.2" | "q1.3": {"filter": the pushed-down
+    probe filters, "keep": the build side's row mask, "sql_where": both as the reference reads them}}};
+    ssb_flight1_query(wl, name) is one query as a workload of the usual shape (one join: the plain path)."""
+    base = ssb_q11(sf=sf, seed=seed)
+    d_keys, d_year = base["date_full"]["d_datekey"], base["date_full"]["d_year"]
+    n_d = len(d_keys)
+    first = np.searchsorted(d_year, d_year, side="left")  # the first day of every day's year
+    day = np.arange(n_d) - first
+    days_in_year = np.bincount(d_year - d_year[0])[d_year - d_year[0]]
+    month = (day * 12 // days_in_year + 1).astype(np.uint32)
+    d_yearmonthnum = d_year.astype(np.uint32) * 100 + month
+    d_week = (day // 7 + 1).astype(np.uint16)
+    date_full = {"d_datekey": d_keys, "d_year": d_year, "d_yearmonthnum": d_yearmonthnum, "d_weeknuminyear": d_week}
+
+    def between(col, lo, hi):
+        return [(col, ">=", lo), (col, "<=", hi)], "%s >= %d AND %s <= %d" % (col, lo, col, hi)
+
+    queries = {}
+    for name, keep, date_sql, disc, qty_filter, qty_sql in (
+            ("q1.1", d_year == 1993, "d_year = 1993", (1, 3), [("lo_quantity", "<", 25)], "lo_quantity < 25"),
+            ("q1.2", d_yearmonthnum == 199401, "d_yearmonthnum = 199401", (4, 6)) + between("lo_quantity", 26, 35),
+            ("q1.3", (d_week == 6) & (d_year == 1994), "d_weeknuminyear = 6 AND d_year = 1994", (5, 7)) +
+            between("lo_quantity", 26, 35)):
+        disc_filter, disc_sql = between("lo_discount", *disc)
+        queries[name] = {"filter": disc_filter + qty_filter, "keep": keep,
+                         "sql_where": "%s AND %s AND %s" % (date_sql, disc_sql, qty_sql)}
+    return {"name": "ssb_flight1", "probe": {"name": "lineorder", "cols": base["probe"]["cols"]}, "date_full": date_full,
+            "queries": queries}
+
+
+def ssb_flight1_query(wl, name):
+    """query `name` of ssb_flight1() as a workload: the filtered probe side and the date rows its predicate keeps"""
+    q = wl["queries"][name]
+    keep = q["keep"]
+    full = wl["date_full"]
+    jd = {"name": "date", "keys": [full["d_datekey"][keep]], "key_names": ["d_datekey"],
+          "payload": {c: full[c][keep] for c in ("d_year", "d_yearmonthnum", "d_weeknuminyear")},
+          "key_src": [(-1, 0)], "perfect": None}
+    return {"name": "ssb_flight1_" + name, "probe": {"name": "lineorder", "cols": wl["probe"]["cols"], "filter": q["filter"]},
+            "joins": [jd], "date_full": full, "sql_where": q["sql_where"]}
+
+
 def default_paths(k, kind="each_last_once"):
     """Join orders a deterministic enumerator of the reference yields when no join depends on
     another (EachLastOnceEnumeration / EachFirstOnceEnumeration, polar_enumeration_algo.cpp:610-667)."""

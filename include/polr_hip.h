@@ -42,7 +42,9 @@ enum {
 	POLR_E_HIP = -4,         /* a HIP runtime call failed; text in polr_last_error */
 	POLR_E_DUPLICATE = -5,   /* perfect-hash build saw a duplicate key: caller keeps the chained table,
 	                            like perfect_hash_join_executor.cpp:112-114 */
-	POLR_E_OVERFLOW = -6     /* output buffer too small; counters are still exact */
+	POLR_E_OVERFLOW = -6,    /* output buffer too small; counters are still exact */
+	POLR_E_RANGE = -7        /* an aggregate argument `left OP right` lies outside its result type for some output row: the
+	                            reference's OutOfRangeException ("Overflow in multiplication of ..."); no result is written */
 };
 
 /* MultiplexerRouting (src/include/duckdb/main/config.hpp:41-50), same order */
@@ -321,7 +323,8 @@ int polr_out_materialize(polr_out *o, void *stream, int32_t src_join, uint32_t s
  * device -- no column is materialised, only the results leave.  NULLs take no part; SUM is exact in 128 bits
  * (DuckDB: SUM(INTEGER|BIGINT) -> HUGEINT, sum.cpp:113-144) and, like MIN / MAX, NULL over no rows; COUNT is
  * never NULL.  The output object must have been filled by a materialising run (polr_probe_rounds / polr_mpx_run*
- * with an `out`).  VARCHAR / unsigned 64-bit columns: POLR_E_UNSUPPORTED. */
+ * with an `out`).  VARCHAR / unsigned 64-bit columns: POLR_E_UNSUPPORTED.  An argument that is a product, sum or
+ * difference of two columns: the *_expr forms below. */
 enum { POLR_AGG_COUNT_STAR = 0, POLR_AGG_COUNT = 1, POLR_AGG_SUM = 2, POLR_AGG_MIN = 3, POLR_AGG_MAX = 4 };
 typedef struct polr_agg_spec {
 	uint32_t fn;       /* POLR_AGG_* */
@@ -392,11 +395,57 @@ int polr_out_aggregate_hashed_str(polr_out *o, void *stream, const polr_group_ke
  * column of string_t cells, 1 / 2 / 4 / 8 an integer one.  How a caller of polr_out_aggregate_hashed_str that did not create
  * the tables itself (a broadcast copy, polr_ht_alloc_like) tells which group_keys entries are offsets. */
 int polr_out_column_width(polr_out *o, int32_t src_join, uint32_t src_col, uint32_t *width);
+/* ---- aggregate arguments that are `left OP right` ------------------------------------------------------------------
+ * SSB flight 1 is SUM(lo_extendedprice * lo_discount), flight 4 SUM(lo_revenue - lo_supplycost): the argument of an
+ * aggregate is an expression.  The reference evaluates it in a projection under PhysicalUngroupedAggregate /
+ * PhysicalPerfectHashAggregate / PhysicalHashAggregate; polr_agg_expr stands for the BoundFunctionExpression (+, -, *) that
+ * is the child of a BoundAggregateExpression, with BoundReferenceExpression children.  Here the sink kernels gather both
+ * operands by the row ids they read anyway -- no column is materialised -- under the reference's semantics
+ * (src/include/duckdb/common/operator/{add,subtract,multiply}.hpp):
+ *  - op = POLR_ARG_COLUMN: the argument is column (src_join[0], src_col[0]); the remaining fields are ignored and the answer
+ *    is that of the call without _expr on the same output.
+ *  - otherwise the argument is (src_join[0], src_col[0]) OP (src_join[1], src_col[1]); each operand an integer column of the
+ *    probe table (src_join = -1) or of a build side, of up to 8 bytes, signed if 8 (else POLR_E_UNSUPPORTED); the two may
+ *    come from different sources.
+ *  - result_width (1, 2, 4 or 8 bytes) and result_flags (POLR_COL_SIGNED; an 8-byte result must be signed, else
+ *    POLR_E_UNSUPPORTED) are the type the reference's binder gave the expression (typeof(expr)).  It must hold the whole
+ *    range of both operand types -- the implicit casts the binder adds are lossless --, else POLR_E_INVALID.
+ *  - a row whose left or right operand is NULL has a NULL argument: it takes no part in COUNT, SUM, MIN or MAX and cannot
+ *    overflow.
+ *  - EVERY output row with two non-NULL operands is checked, rows that polr_out_aggregate_grouped_expr drops for their
+ *    group key included (the projection runs before the GROUP BY): when the exact result of some row lies outside the
+ *    result type the call returns POLR_E_RANGE, *n_out_of_range (may be NULL) is the exact number of such (row, aggregate)
+ *    arguments over all aggregates of the call, every result buffer (results, group_keys, group_nulls, str_bytes) and
+ *    *n_groups / *n_dropped are as they were, and polr_last_error names the first aggregate index with such a row and
+ *    the count.  On success *n_out_of_range = 0.
+ * Within range the value is an ordinary signed 64-bit cell: sums are exact in 128 bits, results as for the plain calls.
+ * Not provided: constant operands, nested expressions, division, DOUBLE / HUGEINT results; polr_out_fuse_grouped takes
+ * plain columns only. */
+enum { POLR_ARG_COLUMN = 0, POLR_ARG_ADD = 1, POLR_ARG_SUB = 2, POLR_ARG_MUL = 3 };
+typedef struct polr_agg_expr {
+	uint32_t fn;           /* POLR_AGG_* (COUNT(*): everything else is ignored) */
+	uint32_t op;           /* POLR_ARG_* */
+	int32_t src_join[2];   /* left, right operand: -1 = probe-table column, j >= 0 = payload column of join j */
+	uint32_t src_col[2];
+	uint32_t result_width; /* bytes */
+	uint32_t result_flags; /* POLR_COL_SIGNED */
+} polr_agg_expr;
+int polr_out_aggregate_expr(polr_out *o, void *stream, const polr_agg_expr *specs, uint32_t n_aggs, polr_agg_value *results,
+                            uint64_t *n_out_of_range);
+int polr_out_aggregate_grouped_expr(polr_out *o, void *stream, const polr_group_key *keys, uint32_t n_keys,
+                                    const polr_agg_expr *specs, uint32_t n_aggs, polr_agg_value *results, uint64_t n_groups,
+                                    uint64_t *n_dropped, uint64_t *n_out_of_range);
+/* integer and VARCHAR group columns, as polr_out_aggregate_hashed_str */
+int polr_out_aggregate_hashed_expr(polr_out *o, void *stream, const polr_group_key *cols, uint32_t n_cols,
+                                   const polr_agg_expr *specs, uint32_t n_aggs, uint64_t max_groups, int64_t *group_keys,
+                                   uint32_t *group_nulls, polr_agg_value *results, uint64_t *n_groups, uint8_t *str_bytes,
+                                   uint64_t str_cap, uint64_t *str_used, uint64_t *n_out_of_range);
 /* The same GROUP BY FUSED into the run (SSB-skew Q4.1 as shipped: benchmark/ssb-skew/queries/q4-1.sql): an output object
  * with a fused sink makes the pipeline's LAST join fold every surviving tuple into the group cells instead of writing its
  * row ids -- nothing of the join result is written or read back.  For FLAT pipelines whose joins are all perfect tables
  * (polr_pipeline_launch_info(p, 1): flat) -- the star joins of SSB; COUNT(*), COUNT and SUM over columns of at most 4
  * bytes, at most 4096 groups; POLR_E_UNSUPPORTED otherwise (then: polr_out_aggregate_grouped over the emitted row ids).
+ * Plain columns only: an argument `left OP right` goes to polr_out_aggregate_grouped_expr over the emitted row ids.
  * polr_out_reset zeroes the cells; every run with this `out` adds to them; polr_out_fused_result reads them (results as
  * for polr_out_aggregate_grouped).  keys == NULL un-fuses.  Only the pool launch (polr_mpx_run_resident*,
  * polr_mpx_run_backpressure) fills the cells: polr_probe_rounds, polr_probe_rounds_async, polr_mpx_run and
