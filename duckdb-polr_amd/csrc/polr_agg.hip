@@ -15,6 +15,7 @@
 #include <string.h>
 
 #include <algorithm>
+#include <type_traits>
 #include <vector>
 
 #include "polr_internal.h"
@@ -30,7 +31,9 @@ struct AggPartial {
 // under its aggregate operators, with the checked operators of src/include/duckdb/common/operator/{add,subtract,multiply}.hpp
 // (TryAddOperator / TrySubtractOperator / TryMultiplyOperator: the exact result must lie in the result type, else
 // OutOfRangeException).  The expression form has a set of its own -- FusedSink embeds DevAgg / DevAggSet, whose layout
-// stays -- and the sink kernels are compiled once per set type: with DevAggSet they are the kernels they were.
+// stays -- and the sink kernels are compiled once per set type.  The set type decides how an argument is fetched (arg_value)
+// and what tallies the arguments out of range (Oor): each kernel has one body, and the plain form pays for neither the
+// operator dispatch nor the range compare.
 struct DevExprAgg {
 	DevCol src[2];    // left, right operand ([0] alone for POLR_ARG_COLUMN)
 	uint32_t slot[2]; // the row ids that index them
@@ -43,26 +46,41 @@ struct DevExprAggSet {
 	uint32_t pad;
 	unsigned long long *oor; // [POLR_MAX_AGGS]: arguments out of range, added by every wave under the first aggregate IT saw one for
 };
-template <class SET>
-struct is_expr_set {
-	static constexpr bool value = false;
-};
-template <>
-struct is_expr_set<DevExprAggSet> {
-	static constexpr bool value = true;
-};
 
 // a lane's count of out-of-range arguments and the lowest aggregate index it saw one for
 struct OorCount {
-	unsigned long long n;
-	uint32_t first;
+	unsigned long long n = 0;
+	uint32_t first = 0xFFFFFFFFu;
+};
+// ... and the plain form's: a column is never out of range
+struct NoOor {};
+
+template <class SET>
+struct set_traits {
+	static constexpr bool expr = false;
+	using Oor = NoOor;
+};
+template <>
+struct set_traits<DevExprAggSet> {
+	static constexpr bool expr = true;
+	using Oor = OorCount;
 };
 
 // The argument of aggregate `ag` for the output row at position `at` of every slot's row-id array: false = NULL (an operand is
 // NULL: the row takes no part and cannot overflow) or out of range (counted; the call will fail and no result leaves).
-// Operands are cells of at most 8 bytes, signed if 8, so both are exact in 64 bits and the overflow flag of the 64-bit
-// operation plus the comparison with [lo, hi] is the reference's test for every result type up to BIGINT.
-__device__ __forceinline__ bool expr_arg(const DevOut &out, uint64_t at, const DevExprAgg &ag, uint32_t a, long long *v, OorCount *oor) {
+// The plain form: the column's cell.
+__device__ __forceinline__ bool arg_value(const DevOut &out, uint64_t at, const DevAgg &ag, uint32_t, long long *v, NoOor *) {
+	const uint32_t row = out.ids[(uint64_t)ag.slot * out.slot_stride + at];
+	if (ag.src.valid && !ag.src.valid[row]) {
+		return false;
+	}
+	*v = load_col_cell(ag.src, row);
+	return true;
+}
+
+// The expression form.  Operands are cells of at most 8 bytes, signed if 8, so both are exact in 64 bits and the overflow flag
+// of the 64-bit operation plus the comparison with [lo, hi] is the reference's test for every result type up to BIGINT.
+__device__ __forceinline__ bool arg_value(const DevOut &out, uint64_t at, const DevExprAgg &ag, uint32_t a, long long *v, OorCount *oor) {
 	const uint32_t r0 = out.ids[(uint64_t)ag.slot[0] * out.slot_stride + at];
 	if (ag.op == POLR_ARG_COLUMN) {
 		if (ag.src[0].valid && !ag.src[0].valid[r0]) {
@@ -100,7 +118,10 @@ __device__ __forceinline__ bool expr_arg(const DevOut &out, uint64_t at, const D
 }
 
 // once per wave, all lanes converged: one atomic, and none when the wave saw nothing out of range
-__device__ __forceinline__ void flush_oor(unsigned long long *oor, const OorCount &mine) {
+__device__ __forceinline__ void flush_oor(const DevAggSet &, const NoOor &) {
+}
+__device__ __forceinline__ void flush_oor(const DevExprAggSet &aggs, const OorCount &mine) {
+	unsigned long long *oor = aggs.oor;
 	const unsigned long long n = wave_sum64(mine.n);
 	if (n) {
 		uint32_t first = mine.first;
@@ -119,8 +140,7 @@ __device__ __forceinline__ void flush_oor(unsigned long long *oor, const OorCoun
 template <class SET>
 __global__ __launch_bounds__(256) void polr_agg_kernel(DevOut out, uint32_t n_chunks, SET aggs,
                                                        AggPartial *__restrict__ partials) {
-	constexpr bool EXPR = is_expr_set<SET>::value;
-	OorCount my_oor = {0, 0xFFFFFFFFu};
+	typename set_traits<SET>::Oor my_oor;
 	__shared__ AggPartial wave_part[4][POLR_MAX_AGGS];
 	const uint32_t lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
 	for (uint32_t a = 0; a < aggs.n; a++) {
@@ -129,43 +149,22 @@ __global__ __launch_bounds__(256) void polr_agg_kernel(DevOut out, uint32_t n_ch
 		long long hi = 0, mn = 0x7FFFFFFFFFFFFFFFll, mx = (long long)0x8000000000000000ull;
 		for (uint32_t chunk = blockIdx.x; chunk < n_chunks; chunk += gridDim.x) {
 			const uint32_t n = out.chunk_count[chunk];
-			if constexpr (EXPR) {
-				const uint64_t chunk_base = (uint64_t)chunk * out.chunk_capacity;
-				for (uint32_t i = threadIdx.x; i < n; i += blockDim.x) {
-					if (ag.fn == POLR_AGG_COUNT_STAR) {
-						cnt++;
-						continue;
-					}
-					long long v;
-					if (!expr_arg(out, chunk_base + i, ag, a, &v, &my_oor)) {
-						continue; // a NULL operand, or out of range
-					}
+			const uint64_t chunk_base = (uint64_t)chunk * out.chunk_capacity;
+			for (uint32_t i = threadIdx.x; i < n; i += blockDim.x) {
+				if (ag.fn == POLR_AGG_COUNT_STAR) {
 					cnt++;
-					const unsigned long long nl = lo + (unsigned long long)v;
-					hi += (v < 0 ? -1 : 0) + (nl < lo ? 1 : 0);
-					lo = nl;
-					mn = v < mn ? v : mn;
-					mx = v > mx ? v : mx;
+					continue;
 				}
-			} else {
-				const uint32_t *ids = out.ids + (uint64_t)ag.slot * out.slot_stride + (uint64_t)chunk * out.chunk_capacity;
-				for (uint32_t i = threadIdx.x; i < n; i += blockDim.x) {
-					if (ag.fn == POLR_AGG_COUNT_STAR) {
-						cnt++;
-						continue;
-					}
-					const uint32_t row = ids[i];
-					if (ag.src.valid && !ag.src.valid[row]) {
-						continue; // NULLs take no part
-					}
-					const long long v = load_col_cell(ag.src, row);
-					cnt++;
-					const unsigned long long nl = lo + (unsigned long long)v;
-					hi += (v < 0 ? -1 : 0) + (nl < lo ? 1 : 0); // sign extension of v + carry
-					lo = nl;
-					mn = v < mn ? v : mn;
-					mx = v > mx ? v : mx;
+				long long v;
+				if (!arg_value(out, chunk_base + i, ag, a, &v, &my_oor)) {
+					continue; // NULLs take no part; nor does an argument out of range
 				}
+				cnt++;
+				const unsigned long long nl = lo + (unsigned long long)v;
+				hi += (v < 0 ? -1 : 0) + (nl < lo ? 1 : 0); // sign extension of v + carry
+				lo = nl;
+				mn = v < mn ? v : mn;
+				mx = v > mx ? v : mx;
 			}
 		}
 		// wave reduction (128-bit add with carry, min, max, count)
@@ -189,9 +188,7 @@ __global__ __launch_bounds__(256) void polr_agg_kernel(DevOut out, uint32_t n_ch
 			wave_part[wave][a].count = cnt;
 		}
 	}
-	if constexpr (EXPR) {
-		flush_oor(aggs.oor, my_oor);
-	}
+	flush_oor(aggs, my_oor);
 	__syncthreads();
 	if (threadIdx.x < aggs.n) {
 		const uint32_t a = threadIdx.x;
@@ -255,18 +252,6 @@ static int build_agg(polr_pipeline *p, const polr_agg_spec &s, uint32_t a, DevAg
 	return POLR_OK;
 }
 
-static int build_agg_set(polr_pipeline *p, const polr_agg_spec *specs, uint32_t n_aggs, DevAggSet *set) {
-	memset(set, 0, sizeof(*set));
-	set->n = n_aggs;
-	for (uint32_t a = 0; a < n_aggs; a++) {
-		int rc = build_agg(p, specs[a], a, &set->a[a]);
-		if (rc) {
-			return rc;
-		}
-	}
-	return POLR_OK;
-}
-
 // the expression form: POLR_E_INVALID for an unknown function or operator, a column out of range, a result width other than
 // 1 / 2 / 4 / 8 and a result type that cannot hold an operand type; POLR_E_UNSUPPORTED for operand columns other than integers
 // of up to 8 bytes (signed if 8) and for an unsigned 8-byte result
@@ -325,39 +310,104 @@ static int build_expr_agg(polr_pipeline *p, const polr_agg_expr &s, uint32_t a, 
 	return POLR_OK;
 }
 
-static int build_expr_set(polr_pipeline *p, const polr_agg_expr *specs, uint32_t n_aggs, DevExprAggSet *set) {
-	memset(set, 0, sizeof(*set));
-	set->n = n_aggs;
-	for (uint32_t a = 0; a < n_aggs; a++) {
-		int rc = build_expr_agg(p, specs[a], a, &set->a[a]);
+// The aggregates of one sink call, in the form the call was made in: the function codes agg_value / cell_value need and the
+// device set of that form.  The entry point names the specs; the sink builds them where its refusals have their turn.
+struct SinkAggs {
+	SinkAggs(const polr_agg_spec *specs, uint32_t n_aggs) : n(n_aggs), expr(false), specs(specs) {
+	}
+	SinkAggs(const polr_agg_expr *specs, uint32_t n_aggs) : n(n_aggs), expr(true), specs(specs) {
+	}
+	uint32_t n;
+	bool expr;
+	const void *specs; // polr_agg_expr[n] if expr, else polr_agg_spec[n]
+	uint32_t fn[POLR_MAX_AGGS];
+	DevAggSet cols;      // !expr
+	DevExprAggSet exprs; // expr
+};
+
+// (n <= POLR_MAX_AGGS: the caller has checked)
+static int build_sink_aggs(polr_pipeline *p, SinkAggs *s) {
+	memset(&s->cols, 0, sizeof(s->cols));
+	memset(&s->exprs, 0, sizeof(s->exprs));
+	s->cols.n = s->exprs.n = s->n;
+	for (uint32_t a = 0; a < s->n; a++) {
+		int rc = s->expr ? build_expr_agg(p, ((const polr_agg_expr *)s->specs)[a], a, &s->exprs.a[a])
+		                 : build_agg(p, ((const polr_agg_spec *)s->specs)[a], a, &s->cols.a[a]);
 		if (rc) {
 			return rc;
 		}
+		s->fn[a] = s->expr ? s->exprs.a[a].fn : s->cols.a[a].fn;
 	}
 	return POLR_OK;
 }
 
-// the sinks' host code serves both forms: exactly one of specs / exprs is given
-static uint32_t agg_fn(const polr_agg_spec *specs, const polr_agg_expr *exprs, uint32_t a) {
-	return exprs ? exprs[a].fn : specs[a].fn;
+// f(the device set of the call's form): where a sink's kernel is instantiated per set type
+template <class F>
+static void with_set(const SinkAggs &s, F &&f) {
+	if (s.expr) {
+		f(s.exprs);
+	} else {
+		f(s.cols);
+	}
 }
 
-// the out-of-range counters of a call as the kernels left them -> POLR_E_RANGE, or POLR_OK when all are 0
-static int check_range(polr_ctx *ctx, const unsigned long long *oor, uint64_t *n_out_of_range) {
-	unsigned long long total = 0;
-	uint32_t first = POLR_MAX_AGGS;
-	for (uint32_t a = 0; a < POLR_MAX_AGGS; a++) {
-		total += oor[a];
-		first = oor[a] && first == POLR_MAX_AGGS ? a : first;
+// A sink's counters on the device: `own` words of the sink's, and behind them -- the expression form only -- the out-of-range
+// counters of its aggregates.
+struct SinkCounters {
+	static constexpr uint32_t MAX_OWN = 8;
+	SinkCounters(const SinkAggs &aggs, uint32_t own) : own(own), n(own + (aggs.expr ? POLR_MAX_AGGS : 0)) {
 	}
-	if (n_out_of_range) {
-		*n_out_of_range = total;
+	size_t bytes() const {
+		return (size_t)n * 8;
 	}
-	if (total) {
-		POLR_FAIL(ctx, POLR_E_RANGE, "aggregate %u: %llu arguments of this call lie outside their result type (the reference: "
-		          "OutOfRangeException, Overflow in addition / subtraction / multiplication); no result was written", first, total);
+	void place(unsigned long long *at, SinkAggs *aggs) {
+		dev = at;
+		aggs->exprs.oor = at + own;
 	}
-	return POLR_OK;
+	hipError_t zero(hipStream_t st) {
+		return n ? hipMemsetAsync(dev, 0, bytes(), st) : hipSuccess;
+	}
+	hipError_t fetch(hipStream_t st) {
+		return n ? hipMemcpyAsync(host, dev, bytes(), hipMemcpyDeviceToHost, st) : hipSuccess;
+	}
+	// the arguments out of range of the call; first: the lowest aggregate that had one
+	unsigned long long out_of_range(uint32_t *first = nullptr) const {
+		unsigned long long total = 0;
+		for (uint32_t a = POLR_MAX_AGGS; a-- > 0;) {
+			total += host[own + a];
+			if (host[own + a] && first) {
+				*first = a;
+			}
+		}
+		return total;
+	}
+	// the counters as the kernels left them -> POLR_E_RANGE, or POLR_OK when all are 0
+	int check_range(polr_ctx *ctx, uint64_t *n_out_of_range) const {
+		uint32_t first = 0;
+		const unsigned long long total = out_of_range(&first);
+		if (n_out_of_range) {
+			*n_out_of_range = total;
+		}
+		if (total) {
+			POLR_FAIL(ctx, POLR_E_RANGE, "aggregate %u: %llu arguments of this call lie outside their result type (the reference: "
+			          "OutOfRangeException, Overflow in addition / subtraction / multiplication); no result was written", first, total);
+		}
+		return POLR_OK;
+	}
+	uint32_t own, n;
+	unsigned long long *dev = nullptr;
+	unsigned long long host[MAX_OWN + POLR_MAX_AGGS] = {0};
+};
+
+// a group column as the sink kernels read it (domain: the perfect-hash sinks'; the hashed sink ignores it)
+static DevGroupKey dev_group_key(const polr_group_key &k, const OutCol &c) {
+	DevGroupKey g;
+	memset(&g, 0, sizeof(g));
+	g.src = c.dev;
+	g.slot = c.slot;
+	g.n_values = k.n_values;
+	g.min_value = k.min_value;
+	return g;
 }
 
 // what the C ABI reports for an aggregate: COUNT is never NULL; the others are NULL when no row took part
@@ -389,9 +439,10 @@ static polr_agg_value agg_value(uint32_t fn, __int128 sum, long long mn, long lo
 	return v;
 }
 
-static int aggregate_ungrouped(polr_out *o, void *stream, const polr_agg_spec *specs, const polr_agg_expr *exprs, uint32_t n_aggs,
-                               polr_agg_value *results, uint64_t *n_out_of_range) {
-	if (!o || (!specs && !exprs) || !results || n_aggs == 0) {
+// (n_out_of_range: the expression form's, may be NULL)
+static int aggregate_ungrouped(polr_out *o, void *stream, SinkAggs &aggs, polr_agg_value *results, uint64_t *n_out_of_range) {
+	const uint32_t n_aggs = aggs.n;
+	if (!o || !aggs.specs || !results || n_aggs == 0) {
 		return POLR_E_INVALID;
 	}
 	polr_pipeline *p = o->pipe;
@@ -399,9 +450,7 @@ static int aggregate_ungrouped(polr_out *o, void *stream, const polr_agg_spec *s
 	if (n_aggs > POLR_MAX_AGGS) {
 		POLR_FAIL(ctx, POLR_E_UNSUPPORTED, "at most %d aggregates per call", POLR_MAX_AGGS);
 	}
-	DevAggSet set;
-	DevExprAggSet eset;
-	int rc = exprs ? build_expr_set(p, exprs, n_aggs, &eset) : build_agg_set(p, specs, n_aggs, &set);
+	int rc = build_sink_aggs(p, &aggs);
 	if (rc) {
 		return rc;
 	}
@@ -413,21 +462,17 @@ static int aggregate_ungrouped(polr_out *o, void *stream, const polr_agg_spec *s
 	}
 	const uint32_t n_blocks = std::max<uint32_t>(1, std::min<uint32_t>(o->n_chunks, (uint32_t)ctx->n_cus * 8));
 	std::vector<AggPartial> host((size_t)n_blocks * n_aggs);
-	unsigned long long h_oor[POLR_MAX_AGGS] = {0};
+	SinkCounters cnt(aggs, 0);
 	if (o->n_chunks) {
 		AggPartial *part = nullptr;
-		// (the expression form: its out-of-range counters behind the partials)
-		HIPCHK(ctx, hipMalloc((void **)&part, host.size() * sizeof(AggPartial) + (exprs ? sizeof(h_oor) : 0)));
-		hipError_t e = hipSuccess;
-		if (exprs) {
-			eset.oor = (unsigned long long *)(part + host.size());
-			e = hipMemsetAsync(eset.oor, 0, sizeof(h_oor), st);
-			if (e == hipSuccess) {
-				hipLaunchKernelGGL(polr_agg_kernel<DevExprAggSet>, dim3(n_blocks), dim3(256), 0, st, o->dev, o->n_chunks, eset, part);
-				e = hipMemcpyAsync(h_oor, eset.oor, sizeof(h_oor), hipMemcpyDeviceToHost, st);
-			}
-		} else {
-			hipLaunchKernelGGL(polr_agg_kernel<DevAggSet>, dim3(n_blocks), dim3(256), 0, st, o->dev, o->n_chunks, set, part);
+		HIPCHK(ctx, hipMalloc((void **)&part, host.size() * sizeof(AggPartial) + cnt.bytes())); // (the counters behind the partials)
+		cnt.place((unsigned long long *)(part + host.size()), &aggs);
+		hipError_t e = cnt.zero(st);
+		if (e == hipSuccess) {
+			with_set(aggs, [&](const auto &set) {
+				hipLaunchKernelGGL(polr_agg_kernel, dim3(n_blocks), dim3(256), 0, st, o->dev, o->n_chunks, set, part);
+			});
+			e = cnt.fetch(st);
 		}
 		e = e == hipSuccess ? hipMemcpyAsync(host.data(), part, host.size() * sizeof(AggPartial), hipMemcpyDeviceToHost, st) : e;
 		e = e == hipSuccess ? hipStreamSynchronize(st) : e;
@@ -436,24 +481,22 @@ static int aggregate_ungrouped(polr_out *o, void *stream, const polr_agg_spec *s
 			POLR_FAIL(ctx, POLR_E_HIP, "aggregate failed: %s", hipGetErrorString(e));
 		}
 	}
-	if (exprs) {
-		rc = check_range(ctx, h_oor, n_out_of_range);
-		if (rc) {
-			return rc;
-		}
+	rc = cnt.check_range(ctx, n_out_of_range);
+	if (rc) {
+		return rc;
 	}
 	for (uint32_t a = 0; a < n_aggs; a++) {
 		__int128 sum = 0;
 		long long mn = 0x7FFFFFFFFFFFFFFFll, mx = (long long)0x8000000000000000ull;
-		unsigned long long cnt = 0;
+		unsigned long long n_rows = 0;
 		for (uint32_t b = 0; b < n_blocks && o->n_chunks; b++) {
 			const AggPartial &r = host[(size_t)b * n_aggs + a];
 			sum += ((__int128)r.sum_hi << 64) + (__int128)r.sum_lo;
 			mn = r.mn < mn ? r.mn : mn;
 			mx = r.mx > mx ? r.mx : mx;
-			cnt += r.count;
+			n_rows += r.count;
 		}
-		results[a] = agg_value(agg_fn(specs, exprs, a), sum, mn, mx, cnt);
+		results[a] = agg_value(aggs.fn[a], sum, mn, mx, n_rows);
 	}
 	return POLR_OK;
 }
@@ -463,19 +506,15 @@ extern "C" {
 int polr_out_aggregate(polr_out *o, void *stream, const polr_agg_spec *specs, uint32_t n_aggs,
                        polr_agg_value *results) {
 	POLR_ENTRY();
-	if (!specs) {
-		return POLR_E_INVALID;
-	}
-	return aggregate_ungrouped(o, stream, specs, nullptr, n_aggs, results, nullptr);
+	SinkAggs aggs(specs, n_aggs);
+	return aggregate_ungrouped(o, stream, aggs, results, nullptr);
 }
 
 int polr_out_aggregate_expr(polr_out *o, void *stream, const polr_agg_expr *specs, uint32_t n_aggs, polr_agg_value *results,
                             uint64_t *n_out_of_range) {
 	POLR_ENTRY();
-	if (!specs) {
-		return POLR_E_INVALID;
-	}
-	return aggregate_ungrouped(o, stream, nullptr, specs, n_aggs, results, n_out_of_range);
+	SinkAggs aggs(specs, n_aggs);
+	return aggregate_ungrouped(o, stream, aggs, results, n_out_of_range);
 }
 
 } // extern "C"
@@ -519,8 +558,7 @@ template <class SET>
 __global__ __launch_bounds__(256) void polr_group_agg_kernel(DevOut out, uint32_t n_chunks, DevGroupSet groups,
                                                              SET aggs, GroupCell *__restrict__ table,
                                                              unsigned long long *__restrict__ dropped, int use_lds) {
-	constexpr bool EXPR = is_expr_set<SET>::value;
-	OorCount my_oor = {0, 0xFFFFFFFFu};
+	typename set_traits<SET>::Oor my_oor;
 	extern __shared__ __attribute__((aligned(16))) unsigned char lds_raw[];
 	GroupCell *local = (GroupCell *)lds_raw;
 	const uint32_t n_cells = groups.n_groups * aggs.n;
@@ -556,11 +594,11 @@ __global__ __launch_bounds__(256) void polr_group_agg_kernel(DevOut out, uint32_
 			}
 			if (!ok) {
 				my_dropped++;
-				if constexpr (EXPR) { // (the reference's projection sees the row before the GROUP BY does: its range is checked)
+				if constexpr (set_traits<SET>::expr) { // (the reference's projection sees the row before the GROUP BY does: its range is checked)
 					for (uint32_t a = 0; a < aggs.n; a++) {
 						long long v;
 						if (aggs.a[a].fn != POLR_AGG_COUNT_STAR) {
-							expr_arg(out, chunk_base + i, aggs.a[a], a, &v, &my_oor);
+							arg_value(out, chunk_base + i, aggs.a[a], a, &v, &my_oor);
 						}
 					}
 				}
@@ -573,17 +611,9 @@ __global__ __launch_bounds__(256) void polr_group_agg_kernel(DevOut out, uint32_
 					atomicAdd(&c->count, 1ull);
 					continue;
 				}
-				if constexpr (EXPR) {
-					long long v;
-					if (expr_arg(out, chunk_base + i, ag, a, &v, &my_oor)) {
-						cell_add(c, v);
-					}
-				} else {
-					const uint32_t row = out.ids[(uint64_t)ag.slot * out.slot_stride + chunk_base + i];
-					if (ag.src.valid && !ag.src.valid[row]) {
-						continue;
-					}
-					cell_add(c, load_col_cell(ag.src, row));
+				long long v;
+				if (arg_value(out, chunk_base + i, ag, a, &v, &my_oor)) { // (NULLs take no part)
+					cell_add(c, v);
 				}
 			}
 		}
@@ -591,9 +621,7 @@ __global__ __launch_bounds__(256) void polr_group_agg_kernel(DevOut out, uint32_
 	if (my_dropped) {
 		atomicAdd(dropped, my_dropped);
 	}
-	if constexpr (EXPR) {
-		flush_oor(aggs.oor, my_oor);
-	}
+	flush_oor(aggs, my_oor);
 	if (use_lds) {
 		__syncthreads();
 		for (uint32_t i = threadIdx.x; i < n_cells; i += blockDim.x) {
@@ -613,10 +641,10 @@ static polr_agg_value cell_value(const GroupCell &c, uint32_t fn) {
 	return agg_value(fn, ((__int128)c.hi32 << 32) + (__int128)c.lo32, c.mn, c.mx, c.count);
 }
 
-static int aggregate_grouped(polr_out *o, void *stream, const polr_group_key *keys, uint32_t n_keys, const polr_agg_spec *specs,
-                             const polr_agg_expr *exprs, uint32_t n_aggs, polr_agg_value *results, uint64_t n_groups,
-                             uint64_t *n_dropped, uint64_t *n_out_of_range) {
-	if (!o || !keys || (!specs && !exprs) || !results || n_keys == 0 || n_aggs == 0) {
+static int aggregate_grouped(polr_out *o, void *stream, const polr_group_key *keys, uint32_t n_keys, SinkAggs &aggs,
+                             polr_agg_value *results, uint64_t n_groups, uint64_t *n_dropped, uint64_t *n_out_of_range) {
+	const uint32_t n_aggs = aggs.n;
+	if (!o || !keys || !aggs.specs || !results || n_keys == 0 || n_aggs == 0) {
 		return POLR_E_INVALID;
 	}
 	polr_pipeline *p = o->pipe;
@@ -641,19 +669,14 @@ static int aggregate_grouped(polr_out *o, void *stream, const polr_group_key *ke
 		if (groups > (1u << 20)) {
 			POLR_FAIL(ctx, POLR_E_UNSUPPORTED, "more than 2^20 groups: not a perfect-hash aggregate");
 		}
-		gs.k[q].src = c.dev;
-		gs.k[q].slot = c.slot;
-		gs.k[q].n_values = keys[q].n_values;
-		gs.k[q].min_value = keys[q].min_value;
+		gs.k[q] = dev_group_key(keys[q], c);
 	}
 	if (groups != n_groups) {
 		POLR_FAIL(ctx, POLR_E_INVALID, "results hold %llu groups, the domains span %llu", (unsigned long long)n_groups,
 		          (unsigned long long)groups);
 	}
 	gs.n_groups = (uint32_t)groups;
-	DevAggSet as;
-	DevExprAggSet es;
-	int rc = exprs ? build_expr_set(p, exprs, n_aggs, &es) : build_agg_set(p, specs, n_aggs, &as);
+	int rc = build_sink_aggs(p, &aggs);
 	if (rc) {
 		return rc;
 	}
@@ -665,30 +688,26 @@ static int aggregate_grouped(polr_out *o, void *stream, const polr_group_key *ke
 	}
 	const uint32_t n_cells = (uint32_t)groups * n_aggs;
 	std::vector<GroupCell> host(n_cells);
-	unsigned long long h_cnt[1 + POLR_MAX_AGGS] = {0}; // [0] dropped rows, [1 ..] the expression form's out-of-range counters
-	const size_t cnt_bytes = exprs ? sizeof(h_cnt) : 8;
+	SinkCounters cnt(aggs, 1); // [0] dropped rows
 	GroupCell *table = nullptr;
 	unsigned long long *dropped = nullptr;
 	hipError_t e = hipMalloc((void **)&table, (size_t)n_cells * sizeof(GroupCell));
-	e = e == hipSuccess ? hipMalloc((void **)&dropped, cnt_bytes) : e;
-	e = e == hipSuccess ? hipMemsetAsync(dropped, 0, cnt_bytes, st) : e;
-	es.oor = dropped + 1;
+	e = e == hipSuccess ? hipMalloc((void **)&dropped, cnt.bytes()) : e;
+	cnt.place(dropped, &aggs);
+	e = e == hipSuccess ? cnt.zero(st) : e;
 	if (e == hipSuccess) {
 		hipLaunchKernelGGL(polr_group_init_kernel, dim3((n_cells + 255) / 256), dim3(256), 0, st, table, (uint64_t)n_cells);
 		if (o->n_chunks) {
 			const int use_lds = n_cells <= POLR_GROUP_LDS_CELLS;
 			const uint32_t n_blocks = std::max<uint32_t>(1, std::min<uint32_t>(o->n_chunks, (uint32_t)ctx->n_cus * 4));
 			const size_t lds = use_lds ? (size_t)n_cells * sizeof(GroupCell) : 0;
-			if (exprs) {
-				hipLaunchKernelGGL(polr_group_agg_kernel<DevExprAggSet>, dim3(n_blocks), dim3(256), lds, st, o->dev, o->n_chunks, gs, es,
-				                   table, dropped, use_lds);
-			} else {
-				hipLaunchKernelGGL(polr_group_agg_kernel<DevAggSet>, dim3(n_blocks), dim3(256), lds, st, o->dev, o->n_chunks, gs, as,
-				                   table, dropped, use_lds);
-			}
+			with_set(aggs, [&](const auto &set) {
+				hipLaunchKernelGGL(polr_group_agg_kernel, dim3(n_blocks), dim3(256), lds, st, o->dev, o->n_chunks, gs, set, table, dropped,
+				                   use_lds);
+			});
 		}
 		e = hipMemcpyAsync(host.data(), table, (size_t)n_cells * sizeof(GroupCell), hipMemcpyDeviceToHost, st);
-		e = e == hipSuccess ? hipMemcpyAsync(h_cnt, dropped, cnt_bytes, hipMemcpyDeviceToHost, st) : e;
+		e = e == hipSuccess ? cnt.fetch(st) : e;
 		e = e == hipSuccess ? hipStreamSynchronize(st) : e;
 	}
 	if (table) {
@@ -700,17 +719,15 @@ static int aggregate_grouped(polr_out *o, void *stream, const polr_group_key *ke
 	if (e != hipSuccess) {
 		POLR_FAIL(ctx, POLR_E_HIP, "grouped aggregate failed: %s", hipGetErrorString(e));
 	}
-	if (exprs) {
-		rc = check_range(ctx, h_cnt + 1, n_out_of_range);
-		if (rc) {
-			return rc;
-		}
+	rc = cnt.check_range(ctx, n_out_of_range);
+	if (rc) {
+		return rc;
 	}
 	for (uint32_t i = 0; i < n_cells; i++) {
-		results[i] = cell_value(host[i], agg_fn(specs, exprs, i % n_aggs));
+		results[i] = cell_value(host[i], aggs.fn[i % n_aggs]);
 	}
 	if (n_dropped) {
-		*n_dropped = h_cnt[0];
+		*n_dropped = cnt.host[0];
 	}
 	return POLR_OK;
 }
@@ -719,20 +736,16 @@ extern "C" int polr_out_aggregate_grouped(polr_out *o, void *stream, const polr_
                                           const polr_agg_spec *specs, uint32_t n_aggs, polr_agg_value *results,
                                           uint64_t n_groups, uint64_t *n_dropped) {
 	POLR_ENTRY();
-	if (!specs) {
-		return POLR_E_INVALID;
-	}
-	return aggregate_grouped(o, stream, keys, n_keys, specs, nullptr, n_aggs, results, n_groups, n_dropped, nullptr);
+	SinkAggs aggs(specs, n_aggs);
+	return aggregate_grouped(o, stream, keys, n_keys, aggs, results, n_groups, n_dropped, nullptr);
 }
 
 extern "C" int polr_out_aggregate_grouped_expr(polr_out *o, void *stream, const polr_group_key *keys, uint32_t n_keys,
                                                const polr_agg_expr *specs, uint32_t n_aggs, polr_agg_value *results,
                                                uint64_t n_groups, uint64_t *n_dropped, uint64_t *n_out_of_range) {
 	POLR_ENTRY();
-	if (!specs) {
-		return POLR_E_INVALID;
-	}
-	return aggregate_grouped(o, stream, keys, n_keys, nullptr, specs, n_aggs, results, n_groups, n_dropped, n_out_of_range);
+	SinkAggs aggs(specs, n_aggs);
+	return aggregate_grouped(o, stream, keys, n_keys, aggs, results, n_groups, n_dropped, n_out_of_range);
 }
 
 
@@ -805,10 +818,7 @@ extern "C" int polr_out_fuse_grouped(polr_out *o, const polr_group_key *keys, ui
 		if (keys[q].n_values == 0 || groups > 4096) {
 			POLR_FAIL(ctx, POLR_E_UNSUPPORTED, "group column %u: a fused sink holds at most 4096 groups", q);
 		}
-		fs.groups.k[q].src = c.dev;
-		fs.groups.k[q].slot = c.slot;
-		fs.groups.k[q].n_values = keys[q].n_values;
-		fs.groups.k[q].min_value = keys[q].min_value;
+		fs.groups.k[q] = dev_group_key(keys[q], c);
 	}
 	fs.groups.n_groups = (uint32_t)groups;
 	fs.aggs.n = n_aggs;
@@ -1325,8 +1335,7 @@ struct HashAggTable {
 template <bool STR, class SET>
 __global__ __launch_bounds__(256) void polr_hash_agg_kernel(DevOut out, uint32_t n_chunks, DevGroupSet groups, SET aggs,
                                                             HashAggTable t, uint4 *reps, uint32_t str_mask) {
-	constexpr bool EXPR = is_expr_set<SET>::value;
-	OorCount my_oor = {0, 0xFFFFFFFFu};
+	typename set_traits<SET>::Oor my_oor;
 	const uint32_t lane = threadIdx.x & 63u;
 	for (uint32_t chunk = blockIdx.x; chunk < n_chunks; chunk += gridDim.x) {
 		const uint32_t n = out.chunk_count[chunk];
@@ -1432,18 +1441,11 @@ __global__ __launch_bounds__(256) void polr_hash_agg_kernel(DevOut out, uint32_t
 				const auto &ag = aggs.a[a];
 				bool have = s32 != POLR_NO_SLOT;
 				long long v = 0;
-				if constexpr (EXPR) {
-					if (active && ag.fn != POLR_AGG_COUNT_STAR) { // (a row that found no slot is checked all the same)
-						have = expr_arg(out, chunk_base + i, ag, a, &v, &my_oor) && have;
-						v = have ? v : 0;
-					}
-				} else if (have && ag.fn != POLR_AGG_COUNT_STAR) {
-					const uint32_t row = out.ids[(uint64_t)ag.slot * out.slot_stride + chunk_base + i];
-					if (ag.src.valid && !ag.src.valid[row]) {
-						have = false; // NULLs take no part
-					} else {
-						v = load_col_cell(ag.src, row);
-					}
+				// (the expression form checks the range of a row that found no slot all the same; the plain form need not load for it)
+				const bool fetch = set_traits<SET>::expr ? active : have;
+				if (fetch && ag.fn != POLR_AGG_COUNT_STAR) {
+					have = arg_value(out, chunk_base + i, ag, a, &v, &my_oor) && have; // (NULLs take no part)
+					v = have ? v : 0;
 				}
 				unsigned long long cnt = have ? 1ull : 0ull, lo = (unsigned long long)v & 0xFFFFFFFFull;
 				long long hi = v >> 32, mn = v, mx = v;
@@ -1501,9 +1503,7 @@ __global__ __launch_bounds__(256) void polr_hash_agg_kernel(DevOut out, uint32_t
 			}
 		}
 	}
-	if constexpr (EXPR) {
-		flush_oor(aggs.oor, my_oor);
-	}
+	flush_oor(aggs, my_oor);
 }
 
 // the groups that exist, compacted: [idx] <- slot
@@ -1573,13 +1573,14 @@ extern "C" int polr_out_column_width(polr_out *o, int32_t src_join, uint32_t src
 	return POLR_OK;
 }
 
-// both entry points of the general GROUP BY; strings: VARCHAR group columns are allowed, their values go to str_bytes
-// (exactly one of specs / exprs; n_out_of_range: the expression form's, may be NULL)
-static int aggregate_hashed(polr_out *o, void *stream, const polr_group_key *cols, uint32_t n_cols, const polr_agg_spec *specs,
-                            const polr_agg_expr *exprs, uint32_t n_aggs, uint64_t max_groups, int64_t *group_keys,
-                            uint32_t *group_nulls, polr_agg_value *results, uint64_t *n_groups, bool strings, uint8_t *str_bytes,
-                            uint64_t str_cap, uint64_t *str_used, uint64_t *n_out_of_range) {
-	if (!o || !cols || (!specs && !exprs) || !group_keys || !group_nulls || !results || !n_groups || n_cols == 0 || n_aggs == 0 ||
+// the entry points of the general GROUP BY; strings: VARCHAR group columns are allowed, their values go to str_bytes
+// (n_out_of_range: the expression form's, may be NULL)
+static int aggregate_hashed(polr_out *o, void *stream, const polr_group_key *cols, uint32_t n_cols, SinkAggs &aggs,
+                            uint64_t max_groups, int64_t *group_keys, uint32_t *group_nulls, polr_agg_value *results,
+                            uint64_t *n_groups, bool strings, uint8_t *str_bytes, uint64_t str_cap, uint64_t *str_used,
+                            uint64_t *n_out_of_range) {
+	const uint32_t n_aggs = aggs.n;
+	if (!o || !cols || !aggs.specs || !group_keys || !group_nulls || !results || !n_groups || n_cols == 0 || n_aggs == 0 ||
 	    max_groups == 0 || (strings && (!str_used || (!str_bytes && str_cap)))) {
 		return POLR_E_INVALID;
 	}
@@ -1607,12 +1608,9 @@ static int aggregate_hashed(polr_out *o, void *stream, const polr_group_key *col
 		if (rc) {
 			return rc;
 		}
-		gs.k[q].src = gcol[q].dev;
-		gs.k[q].slot = gcol[q].slot;
+		gs.k[q] = dev_group_key(cols[q], gcol[q]);
 	}
-	DevAggSet as;
-	DevExprAggSet es;
-	int rc = exprs ? build_expr_set(p, exprs, n_aggs, &es) : build_agg_set(p, specs, n_aggs, &as);
+	int rc = build_sink_aggs(p, &aggs);
 	if (rc) {
 		return rc;
 	}
@@ -1641,7 +1639,8 @@ static int aggregate_hashed(polr_out *o, void *stream, const polr_group_key *col
 	// one allocation: state, nulls, counters, keys, representative cells (VARCHAR only), group cells, and the compacted
 	// outputs behind them
 	const size_t rep_bytes = str_mask ? 16 : 0;
-	const size_t b_state = capacity * 4, b_nulls = capacity * 4, b_cnt = 128, b_keys = capacity * n_cols * 8,
+	SinkCounters hc(aggs, SinkCounters::MAX_OWN); // [0] groups, [1] overflow, [2] compaction cursor
+	const size_t b_state = capacity * 4, b_nulls = capacity * 4, b_cnt = sizeof(hc.host), b_keys = capacity * n_cols * 8,
 	             b_reps = capacity * n_cols * rep_bytes, b_cells = capacity * n_aggs * sizeof(GroupCell),
 	             b_okeys = (max_groups * n_cols * 8 + 15) & ~(size_t)15, // (the uint4 cells behind it stay 16-byte aligned)
 	             b_oreps = max_groups * n_cols * rep_bytes, b_onulls = (max_groups * 4 + 15) & ~(size_t)15,
@@ -1653,10 +1652,9 @@ static int aggregate_hashed(polr_out *o, void *stream, const polr_group_key *col
 	at += b_state;
 	t.nulls = (uint32_t *)at;
 	at += b_nulls;
-	// [0] groups, [1] overflow, [2] compaction cursor, [8 .. 15] the expression form's out-of-range counters
 	unsigned long long *cnt = (unsigned long long *)at;
 	at += b_cnt;
-	es.oor = cnt + 8;
+	hc.place(cnt, &aggs);
 	t.n_groups = cnt;
 	t.overflow = cnt + 1;
 	t.keys = (long long *)at;
@@ -1672,36 +1670,28 @@ static int aggregate_hashed(polr_out *o, void *stream, const polr_group_key *col
 	uint32_t *onulls = (uint32_t *)at;
 	at += b_onulls;
 	GroupCell *ocells = (GroupCell *)at;
-	hipError_t e = hipMemsetAsync(base, 0, b_state + b_nulls + b_cnt, st);
-	unsigned long long h_cnt[8 + POLR_MAX_AGGS] = {0};
+	hipError_t e = hipMemsetAsync(base, 0, b_state + b_nulls + b_cnt, st); // (the counters with the table's state)
+	const unsigned long long *h_cnt = hc.host;
 	if (e == hipSuccess) {
 		hipLaunchKernelGGL(polr_group_init_kernel, dim3(256), dim3(256), 0, st, t.cells, capacity * n_aggs);
 		if (o->n_chunks) {
 			const dim3 grid(std::min<uint32_t>(o->n_chunks, 2048u));
-			if (exprs && str_mask) {
-				hipLaunchKernelGGL((polr_hash_agg_kernel<true, DevExprAggSet>), grid, dim3(256), 0, st, o->dev, o->n_chunks, gs, es, t, reps,
-				                   str_mask);
-			} else if (exprs) {
-				hipLaunchKernelGGL((polr_hash_agg_kernel<false, DevExprAggSet>), grid, dim3(256), 0, st, o->dev, o->n_chunks, gs, es, t, reps,
-				                   str_mask);
-			} else if (str_mask) {
-				hipLaunchKernelGGL((polr_hash_agg_kernel<true, DevAggSet>), grid, dim3(256), 0, st, o->dev, o->n_chunks, gs, as, t, reps,
-				                   str_mask);
-			} else {
-				hipLaunchKernelGGL((polr_hash_agg_kernel<false, DevAggSet>), grid, dim3(256), 0, st, o->dev, o->n_chunks, gs, as, t, reps,
-				                   str_mask);
-			}
+			with_set(aggs, [&](const auto &set) {
+				using SET = std::decay_t<decltype(set)>;
+				if (str_mask) {
+					hipLaunchKernelGGL((polr_hash_agg_kernel<true, SET>), grid, dim3(256), 0, st, o->dev, o->n_chunks, gs, set, t, reps, str_mask);
+				} else {
+					hipLaunchKernelGGL((polr_hash_agg_kernel<false, SET>), grid, dim3(256), 0, st, o->dev, o->n_chunks, gs, set, t, reps, str_mask);
+				}
+			});
 		}
 		hipLaunchKernelGGL(polr_hash_agg_compact_kernel, dim3(256), dim3(256), 0, st, t, n_cols, n_aggs, okeys, onulls, ocells, cnt + 2,
 		                   max_groups, (const uint4 *)reps, oreps);
-		e = hipMemcpyAsync(h_cnt, cnt, sizeof(h_cnt), hipMemcpyDeviceToHost, st);
+		e = hc.fetch(st);
 		e = e == hipSuccess ? hipStreamSynchronize(st) : e;
 	}
 	const bool too_many = h_cnt[1] || h_cnt[0] > max_groups;
-	bool out_of_range = false; // (the reference's query fails: nothing is copied to the caller)
-	for (uint32_t a = 0; a < POLR_MAX_AGGS; a++) {
-		out_of_range = out_of_range || h_cnt[8 + a] != 0;
-	}
+	const bool out_of_range = hc.out_of_range() != 0; // (the reference's query fails: nothing is copied to the caller)
 	const uint64_t g_n = too_many || out_of_range ? 0 : h_cnt[0];
 	std::vector<GroupCell> hcells(g_n * n_aggs);
 	// integer columns only: keys and NULL bits go to the caller's arrays at once; with VARCHAR columns they are staged here
@@ -1751,11 +1741,9 @@ static int aggregate_hashed(polr_out *o, void *stream, const polr_group_key *col
 	if (e != hipSuccess) {
 		POLR_FAIL(ctx, POLR_E_HIP, "hash aggregate failed: %s", hipGetErrorString(e));
 	}
-	if (exprs) {
-		rc = check_range(ctx, h_cnt + 8, n_out_of_range);
-		if (rc) {
-			return rc;
-		}
+	rc = hc.check_range(ctx, n_out_of_range);
+	if (rc) {
+		return rc;
 	}
 	*n_groups = h_cnt[0];
 	if (too_many) {
@@ -1775,7 +1763,7 @@ static int aggregate_hashed(polr_out *o, void *stream, const polr_group_key *col
 	}
 	for (uint64_t g = 0; g < g_n; g++) {
 		for (uint32_t a = 0; a < n_aggs; a++) {
-			results[g * n_aggs + a] = cell_value(hcells[g * n_aggs + a], agg_fn(specs, exprs, a));
+			results[g * n_aggs + a] = cell_value(hcells[g * n_aggs + a], aggs.fn[a]);
 		}
 	}
 	return POLR_OK;
@@ -1785,11 +1773,9 @@ extern "C" int polr_out_aggregate_hashed(polr_out *o, void *stream, const polr_g
                                          const polr_agg_spec *specs, uint32_t n_aggs, uint64_t max_groups, int64_t *group_keys,
                                          uint32_t *group_nulls, polr_agg_value *results, uint64_t *n_groups) {
 	POLR_ENTRY();
-	if (!specs) {
-		return POLR_E_INVALID;
-	}
-	return aggregate_hashed(o, stream, cols, n_cols, specs, nullptr, n_aggs, max_groups, group_keys, group_nulls, results, n_groups,
-	                        false, nullptr, 0, nullptr, nullptr);
+	SinkAggs aggs(specs, n_aggs);
+	return aggregate_hashed(o, stream, cols, n_cols, aggs, max_groups, group_keys, group_nulls, results, n_groups, false, nullptr, 0,
+	                        nullptr, nullptr);
 }
 
 extern "C" int polr_out_aggregate_hashed_str(polr_out *o, void *stream, const polr_group_key *cols, uint32_t n_cols,
@@ -1797,11 +1783,9 @@ extern "C" int polr_out_aggregate_hashed_str(polr_out *o, void *stream, const po
                                              uint32_t *group_nulls, polr_agg_value *results, uint64_t *n_groups, uint8_t *str_bytes,
                                              uint64_t str_cap, uint64_t *str_used) {
 	POLR_ENTRY();
-	if (!specs) {
-		return POLR_E_INVALID;
-	}
-	return aggregate_hashed(o, stream, cols, n_cols, specs, nullptr, n_aggs, max_groups, group_keys, group_nulls, results, n_groups,
-	                        true, str_bytes, str_cap, str_used, nullptr);
+	SinkAggs aggs(specs, n_aggs);
+	return aggregate_hashed(o, stream, cols, n_cols, aggs, max_groups, group_keys, group_nulls, results, n_groups, true, str_bytes,
+	                        str_cap, str_used, nullptr);
 }
 
 extern "C" int polr_out_aggregate_hashed_expr(polr_out *o, void *stream, const polr_group_key *cols, uint32_t n_cols,
@@ -1809,9 +1793,7 @@ extern "C" int polr_out_aggregate_hashed_expr(polr_out *o, void *stream, const p
                                               uint32_t *group_nulls, polr_agg_value *results, uint64_t *n_groups,
                                               uint8_t *str_bytes, uint64_t str_cap, uint64_t *str_used, uint64_t *n_out_of_range) {
 	POLR_ENTRY();
-	if (!specs) {
-		return POLR_E_INVALID;
-	}
-	return aggregate_hashed(o, stream, cols, n_cols, nullptr, specs, n_aggs, max_groups, group_keys, group_nulls, results, n_groups,
-	                        true, str_bytes, str_cap, str_used, n_out_of_range);
+	SinkAggs aggs(specs, n_aggs);
+	return aggregate_hashed(o, stream, cols, n_cols, aggs, max_groups, group_keys, group_nulls, results, n_groups, true, str_bytes,
+	                        str_cap, str_used, n_out_of_range);
 }

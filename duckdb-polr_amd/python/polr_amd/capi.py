@@ -144,6 +144,38 @@ class GroupKey(C.Structure):
                 ("pad", C.c_uint32)]
 
 
+def _agg_specs(specs):
+    """[(fn, src_join, src_col)] with fn in AGG (or a number) -> polr_agg_spec array"""
+    arr = (AggSpec * len(specs))()
+    for i, (fn, sj, sc) in enumerate(specs):
+        arr[i].fn, arr[i].src_join, arr[i].src_col = AGG[fn] if isinstance(fn, str) else fn, sj, sc
+    return arr
+
+
+def _group_keys(keys):
+    """[(src_join, src_col)], or with domains [(src_join, src_col, min, n_values)] -> (polr_group_key array, the number of
+    groups the domains span)"""
+    arr = (GroupKey * len(keys))()
+    n_groups = 1
+    for i, (sj, sc, *domain) in enumerate(keys):
+        arr[i].src_join, arr[i].src_col = sj, sc
+        if domain:
+            arr[i].min_value, arr[i].n_values = int(domain[0]), int(domain[1])
+            n_groups *= int(domain[1])
+    return arr, n_groups
+
+
+def _agg_int(r):
+    """polr_agg_value -> python int (the 128-bit two's complement value), or None for NULL"""
+    return None if r.is_null else (r.hi << 64) + (r.lo & 0xFFFFFFFFFFFFFFFF)
+
+
+def _agg_grid(res, n_groups, na):
+    """polr_agg_value[n_groups * na] -> (values[n_groups][na], counts[n_groups][na])"""
+    return ([[_agg_int(res[g * na + a]) for a in range(na)] for g in range(n_groups)],
+            [[res[g * na + a].count for a in range(na)] for g in range(n_groups)])
+
+
 class HtInfo(C.Structure):
     _fields_ = [("kind", C.c_uint32), ("n_keys", C.c_uint32), ("n_rows", C.c_uint64), ("capacity", C.c_uint64),
                 ("max_run", C.c_uint64), ("device_bytes", C.c_uint64), ("is_dense", C.c_uint32),
@@ -647,60 +679,25 @@ class Output:
     def aggregate(self, specs, stream=None):
         """polr_out_aggregate: specs = [(fn, src_join, src_col)] with fn in AGG -> [python int or None]
         (ungrouped COUNT(*) / COUNT / SUM / MIN / MAX over the output, reduced on the device)"""
-        n = len(specs)
-        arr = (AggSpec * n)()
-        for i, (fn, sj, sc) in enumerate(specs):
-            arr[i].fn, arr[i].src_join, arr[i].src_col = AGG[fn] if isinstance(fn, str) else fn, sj, sc
-        res = (AggValue * n)()
-        self.ctx.check(self.ctx.L.polr_out_aggregate(self.h, stream, arr, n, res))
-        out = []
-        for r in res:
-            out.append(None if r.is_null else (r.hi << 64) + (r.lo & 0xFFFFFFFFFFFFFFFF))
-        return out
+        res = (AggValue * len(specs))()
+        self.ctx.check(self.ctx.L.polr_out_aggregate(self.h, stream, _agg_specs(specs), len(specs), res))
+        return [_agg_int(r) for r in res]
 
     def aggregate_grouped(self, keys, specs, stream=None):
         """polr_out_aggregate_grouped: keys = [(src_join, src_col, min, n_values)], specs as in aggregate() ->
         (values[n_groups][n_aggs] of python int / None, counts[n_groups][n_aggs], n_dropped)"""
-        nk, na = len(keys), len(specs)
-        ka = (GroupKey * nk)()
-        n_groups = 1
-        for i, (sj, sc, mn, nv) in enumerate(keys):
-            ka[i].src_join, ka[i].src_col, ka[i].min_value, ka[i].n_values = sj, sc, int(mn), int(nv)
-            n_groups *= int(nv)
-        sa = (AggSpec * na)()
-        for i, (fn, sj, sc) in enumerate(specs):
-            sa[i].fn, sa[i].src_join, sa[i].src_col = AGG[fn] if isinstance(fn, str) else fn, sj, sc
+        ka, n_groups = _group_keys(keys)
+        na = len(specs)
         res = (AggValue * (n_groups * na))()
         dropped = C.c_uint64()
-        self.ctx.check(self.ctx.L.polr_out_aggregate_grouped(self.h, stream, ka, nk, sa, na, res, n_groups,
-                                                             C.byref(dropped)))
-        vals = [[None if res[g * na + a].is_null else (res[g * na + a].hi << 64) + (res[g * na + a].lo & 0xFFFFFFFFFFFFFFFF)
-                 for a in range(na)] for g in range(n_groups)]
-        counts = [[res[g * na + a].count for a in range(na)] for g in range(n_groups)]
-        return vals, counts, dropped.value
+        self.ctx.check(self.ctx.L.polr_out_aggregate_grouped(self.h, stream, ka, len(keys), _agg_specs(specs), na, res,
+                                                             n_groups, C.byref(dropped)))
+        return _agg_grid(res, n_groups, na) + (dropped.value,)
 
     def aggregate_hashed(self, cols, specs, max_groups, stream=None):
         """polr_out_aggregate_hashed: GROUP BY over group columns of any integer domain.  cols = [(src_join, src_col)],
         specs as in aggregate() -> {group key tuple (None = NULL): [value per aggregate (python int / None)]}"""
-        nk, na = len(cols), len(specs)
-        ka = (GroupKey * nk)()
-        for i, (sj, sc) in enumerate(cols):
-            ka[i].src_join, ka[i].src_col = sj, sc
-        sa = (AggSpec * na)()
-        for i, (fn, sj, sc) in enumerate(specs):
-            sa[i].fn, sa[i].src_join, sa[i].src_col = AGG[fn] if isinstance(fn, str) else fn, sj, sc
-        keys = np.zeros((max_groups, nk), dtype=np.int64)
-        nulls = np.zeros((max_groups,), dtype=np.uint32)
-        res = (AggValue * (max_groups * na))()
-        n = C.c_uint64()
-        self.ctx.check(self.ctx.L.polr_out_aggregate_hashed(self.h, stream, ka, nk, sa, na, max_groups, keys.ctypes.data,
-                                                            nulls.ctypes.data, res, C.byref(n)))
-        out = {}
-        for g in range(n.value):
-            key = tuple(None if (nulls[g] >> c) & 1 else int(keys[g, c]) for c in range(nk))
-            out[key] = [None if res[g * na + a].is_null else (res[g * na + a].hi << 64) + (res[g * na + a].lo & 0xFFFFFFFFFFFFFFFF)
-                        for a in range(na)]
-        return out
+        return self._hashed(self.ctx.L.polr_out_aggregate_hashed, cols, _agg_specs(specs), len(specs), max_groups, stream)
 
     def _col_width(self, src_join, src_col):
         """polr_out_column_width: cell width of a probe column (src_join < 0) or of a payload column of join src_join"""
@@ -708,107 +705,28 @@ class Output:
         self.ctx.check(self.ctx.L.polr_out_column_width(self.h, src_join, src_col, C.byref(w)))
         return w.value
 
-    def aggregate_hashed_str(self, cols, specs, max_groups, str_cap=None, stream=None):
-        """polr_out_aggregate_hashed_str: the general GROUP BY whose group columns may be VARCHAR (width-16 string_t
-        columns, grouped by the strings' bytes) or integer, in any mix.  cols / specs as in aggregate_hashed ->
-        {group key tuple: [value per aggregate]} with bytes for a VARCHAR column, int for an integer one, None for NULL.
-        The byte arena of the groups' strings is sized here (str_cap: a first guess) and the call repeated once with the
-        exact size when the guess was too small."""
-        nk, na = len(cols), len(specs)
-        ka = (GroupKey * nk)()
-        for i, (sj, sc) in enumerate(cols):
-            ka[i].src_join, ka[i].src_col = sj, sc
-        sa = (AggSpec * na)()
-        for i, (fn, sj, sc) in enumerate(specs):
-            sa[i].fn, sa[i].src_join, sa[i].src_col = AGG[fn] if isinstance(fn, str) else fn, sj, sc
-        keys = np.zeros((max_groups, nk), dtype=np.int64)
-        nulls = np.zeros((max_groups,), dtype=np.uint32)
-        res = (AggValue * (max_groups * na))()
-        n, used = C.c_uint64(), C.c_uint64()
-        cap = max(4096, 24 * max_groups) if str_cap is None else int(str_cap)
-        for attempt in (0, 1):
-            arena = np.zeros((cap,), dtype=np.uint8)
-            rc = self.ctx.L.polr_out_aggregate_hashed_str(self.h, stream, ka, nk, sa, na, max_groups, keys.ctypes.data,
-                                                          nulls.ctypes.data, res, C.byref(n), arena.ctypes.data, cap,
-                                                          C.byref(used))
-            if rc == E_OVERFLOW and attempt == 0 and used.value > cap:  # (the strings did not fit; the groups did)
-                cap = used.value
-                continue
-            self.ctx.check(rc)
-            break
-        raw = arena.tobytes()
-        is_str = [self._col_width(sj, sc) == 16 for sj, sc in cols]
-        out = {}
-        for g in range(n.value):
-            key = []
-            for c in range(nk):
-                if (nulls[g] >> c) & 1:
-                    key.append(None)
-                elif is_str[c]:
-                    at = int(keys[g, c])
-                    ln = int.from_bytes(raw[at:at + 4], "little")
-                    key.append(raw[at + 4:at + 4 + ln])
-                else:
-                    key.append(int(keys[g, c]))
-            out[tuple(key)] = [None if res[g * na + a].is_null else (res[g * na + a].hi << 64) + (res[g * na + a].lo & 0xFFFFFFFFFFFFFFFF)
-                               for a in range(na)]
-        return out
-
-    def aggregate_expr(self, specs, stream=None):
-        """polr_out_aggregate_expr: ungrouped aggregates whose argument is a column or `left OP right`.  specs = [(fn, op,
-        (join, col), (join, col), result_dtype)] (make_agg_exprs) -> [python int or None]; an argument outside result_dtype
-        for some output row: PolrError with code E_RANGE and .count"""
-        n = len(specs)
-        arr = make_agg_exprs(specs)
-        res = (AggValue * n)()
-        oor = C.c_uint64()
-        self.ctx.check_range(self.ctx.L.polr_out_aggregate_expr(self.h, stream, arr, n, res, C.byref(oor)), oor)
-        return [None if r.is_null else (r.hi << 64) + (r.lo & 0xFFFFFFFFFFFFFFFF) for r in res]
-
-    def aggregate_grouped_expr(self, keys, specs, stream=None):
-        """polr_out_aggregate_grouped_expr: keys as in aggregate_grouped, specs as in aggregate_expr -> (values, counts,
-        n_dropped) as aggregate_grouped"""
-        nk, na = len(keys), len(specs)
-        ka = (GroupKey * nk)()
-        n_groups = 1
-        for i, (sj, sc, mn, nv) in enumerate(keys):
-            ka[i].src_join, ka[i].src_col, ka[i].min_value, ka[i].n_values = sj, sc, int(mn), int(nv)
-            n_groups *= int(nv)
-        sa = make_agg_exprs(specs)
-        res = (AggValue * (n_groups * na))()
-        dropped, oor = C.c_uint64(), C.c_uint64()
-        self.ctx.check_range(self.ctx.L.polr_out_aggregate_grouped_expr(self.h, stream, ka, nk, sa, na, res, n_groups,
-                                                                        C.byref(dropped), C.byref(oor)), oor)
-        vals = [[None if res[g * na + a].is_null else (res[g * na + a].hi << 64) + (res[g * na + a].lo & 0xFFFFFFFFFFFFFFFF)
-                 for a in range(na)] for g in range(n_groups)]
-        counts = [[res[g * na + a].count for a in range(na)] for g in range(n_groups)]
-        return vals, counts, dropped.value
-
-    def aggregate_hashed_expr(self, cols, specs, max_groups, str_cap=None, stream=None):
-        """polr_out_aggregate_hashed_expr: the general GROUP BY (integer and VARCHAR group columns, as aggregate_hashed_str)
-        with specs as in aggregate_expr -> {group key tuple: [value per aggregate]}"""
-        nk, na = len(cols), len(specs)
-        ka = (GroupKey * nk)()
-        for i, (sj, sc) in enumerate(cols):
-            ka[i].src_join, ka[i].src_col = sj, sc
-        sa = make_agg_exprs(specs)
+    def _hashed(self, entry, cols, sa, na, max_groups, stream, strings=False, str_cap=None, ranged=False):
+        """one of the three polr_out_aggregate_hashed* entry points -> {group key tuple: [value per aggregate]}.  strings: the
+        entry point takes the byte arena of the groups' strings, sized here (str_cap: a first guess) and the call repeated
+        once with the exact size when the guess was too small; ranged: it reports arguments out of range"""
+        nk = len(cols)
+        ka, _ = _group_keys(cols)
         keys = np.zeros((max_groups, nk), dtype=np.int64)
         nulls = np.zeros((max_groups,), dtype=np.uint32)
         res = (AggValue * (max_groups * na))()
         n, used, oor = C.c_uint64(), C.c_uint64(), C.c_uint64()
-        cap = max(4096, 24 * max_groups) if str_cap is None else int(str_cap)
+        cap = (max(4096, 24 * max_groups) if str_cap is None else int(str_cap)) if strings else 0
         for attempt in (0, 1):
             arena = np.zeros((cap,), dtype=np.uint8)
-            rc = self.ctx.L.polr_out_aggregate_hashed_expr(self.h, stream, ka, nk, sa, na, max_groups, keys.ctypes.data,
-                                                           nulls.ctypes.data, res, C.byref(n), arena.ctypes.data, cap,
-                                                           C.byref(used), C.byref(oor))
+            tail = ((arena.ctypes.data, cap, C.byref(used)) if strings else ()) + ((C.byref(oor),) if ranged else ())
+            rc = entry(self.h, stream, ka, nk, sa, na, max_groups, keys.ctypes.data, nulls.ctypes.data, res, C.byref(n), *tail)
             if rc == E_OVERFLOW and attempt == 0 and used.value > cap:  # (the strings did not fit; the groups did)
                 cap = used.value
                 continue
             self.ctx.check_range(rc, oor)
             break
         raw = arena.tobytes()
-        is_str = [self._col_width(sj, sc) == 16 for sj, sc in cols]
+        is_str = [strings and self._col_width(sj, sc) == 16 for sj, sc in cols]
         out = {}
         for g in range(n.value):
             key = []
@@ -821,9 +739,44 @@ class Output:
                     key.append(raw[at + 4:at + 4 + ln])
                 else:
                     key.append(int(keys[g, c]))
-            out[tuple(key)] = [None if res[g * na + a].is_null else (res[g * na + a].hi << 64) + (res[g * na + a].lo & 0xFFFFFFFFFFFFFFFF)
-                               for a in range(na)]
+            out[tuple(key)] = [_agg_int(res[g * na + a]) for a in range(na)]
         return out
+
+    def aggregate_hashed_str(self, cols, specs, max_groups, str_cap=None, stream=None):
+        """polr_out_aggregate_hashed_str: the general GROUP BY whose group columns may be VARCHAR (width-16 string_t
+        columns, grouped by the strings' bytes) or integer, in any mix.  cols / specs as in aggregate_hashed ->
+        {group key tuple: [value per aggregate]} with bytes for a VARCHAR column, int for an integer one, None for NULL.
+        The byte arena of the groups' strings is sized here (str_cap: a first guess) and the call repeated once with the
+        exact size when the guess was too small."""
+        return self._hashed(self.ctx.L.polr_out_aggregate_hashed_str, cols, _agg_specs(specs), len(specs), max_groups, stream,
+                            strings=True, str_cap=str_cap)
+
+    def aggregate_expr(self, specs, stream=None):
+        """polr_out_aggregate_expr: ungrouped aggregates whose argument is a column or `left OP right`.  specs = [(fn, op,
+        (join, col), (join, col), result_dtype)] (make_agg_exprs) -> [python int or None]; an argument outside result_dtype
+        for some output row: PolrError with code E_RANGE and .count"""
+        res = (AggValue * len(specs))()
+        oor = C.c_uint64()
+        self.ctx.check_range(self.ctx.L.polr_out_aggregate_expr(self.h, stream, make_agg_exprs(specs), len(specs), res,
+                                                                C.byref(oor)), oor)
+        return [_agg_int(r) for r in res]
+
+    def aggregate_grouped_expr(self, keys, specs, stream=None):
+        """polr_out_aggregate_grouped_expr: keys as in aggregate_grouped, specs as in aggregate_expr -> (values, counts,
+        n_dropped) as aggregate_grouped"""
+        ka, n_groups = _group_keys(keys)
+        na = len(specs)
+        res = (AggValue * (n_groups * na))()
+        dropped, oor = C.c_uint64(), C.c_uint64()
+        self.ctx.check_range(self.ctx.L.polr_out_aggregate_grouped_expr(self.h, stream, ka, len(keys), make_agg_exprs(specs), na,
+                                                                        res, n_groups, C.byref(dropped), C.byref(oor)), oor)
+        return _agg_grid(res, n_groups, na) + (dropped.value,)
+
+    def aggregate_hashed_expr(self, cols, specs, max_groups, str_cap=None, stream=None):
+        """polr_out_aggregate_hashed_expr: the general GROUP BY (integer and VARCHAR group columns, as aggregate_hashed_str)
+        with specs as in aggregate_expr -> {group key tuple: [value per aggregate]}"""
+        return self._hashed(self.ctx.L.polr_out_aggregate_hashed_expr, cols, make_agg_exprs(specs), len(specs), max_groups,
+                            stream, strings=True, str_cap=str_cap, ranged=True)
 
     def fuse_grouped(self, keys, specs):
         """polr_out_fuse_grouped: fold the join result into group cells inside the run (flat pipelines of perfect tables;
@@ -832,17 +785,9 @@ class Output:
             self.ctx.check(self.ctx.L.polr_out_fuse_grouped(self.h, None, 0, None, 0))
             self._fused = None
             return
-        nk, na = len(keys), len(specs)
-        ka = (GroupKey * nk)()
-        n_groups = 1
-        for i, (sj, sc, mn, nv) in enumerate(keys):
-            ka[i].src_join, ka[i].src_col, ka[i].min_value, ka[i].n_values = sj, sc, int(mn), int(nv)
-            n_groups *= int(nv)
-        sa = (AggSpec * na)()
-        for i, (fn, sj, sc) in enumerate(specs):
-            sa[i].fn, sa[i].src_join, sa[i].src_col = AGG[fn] if isinstance(fn, str) else fn, sj, sc
-        self.ctx.check(self.ctx.L.polr_out_fuse_grouped(self.h, ka, nk, sa, na))
-        self._fused = (n_groups, na)
+        ka, n_groups = _group_keys(keys)
+        self.ctx.check(self.ctx.L.polr_out_fuse_grouped(self.h, ka, len(keys), _agg_specs(specs), len(specs)))
+        self._fused = (n_groups, len(specs))
 
     def fused_result(self, stream=None):
         """polr_out_fused_result -> (values[n_groups][n_aggs], counts[n_groups][n_aggs], n_dropped), as aggregate_grouped"""
@@ -850,10 +795,7 @@ class Output:
         res = (AggValue * (n_groups * na))()
         dropped = C.c_uint64()
         self.ctx.check(self.ctx.L.polr_out_fused_result(self.h, stream, res, n_groups, C.byref(dropped)))
-        vals = [[None if res[g * na + a].is_null else (res[g * na + a].hi << 64) + (res[g * na + a].lo & 0xFFFFFFFFFFFFFFFF)
-                 for a in range(na)] for g in range(n_groups)]
-        counts = [[res[g * na + a].count for a in range(na)] for g in range(n_groups)]
-        return vals, counts, dropped.value
+        return _agg_grid(res, n_groups, na) + (dropped.value,)
 
     def aggregate_string(self, fn, src_join, src_col, stream=None, cap=4096):
         """polr_out_aggregate_string: MIN / MAX of a VARCHAR column over the output rows -> bytes, or None (no non-NULL row)"""

@@ -361,6 +361,49 @@ def test_refusals(gpu_ctx):
     s.close()
 
 
+def test_hashed_expr_range_wins_over_group_overflow(gpu_ctx):
+    """more groups than the 1024-slot minimum table holds, max_groups = 16: rows that find no slot are range-checked all the
+    same, POLR_E_RANGE comes before the POLR_E_OVERFLOW of the groups, and nothing is written -- but *str_used, which the
+    call zeroes before it starts, as polr_out_aggregate_hashed_str does"""
+    s = Star(n=6000, seed=97, extra=full_columns).run(gpu_ctx, "path")
+    gcols = [(-1, 1), s.col("p_int16")]
+    fk1 = s.values(*gcols[0])[0].astype(np.int64)
+    g1, ok1 = s.values(*gcols[1])
+    pairs = np.stack([fk1, np.where(ok1, g1.astype(np.int64), 1 << 40)], axis=1)  # (NULL is a group value of its own)
+    assert len(np.unique(pairs, axis=0)) > 1024
+    ka = (capi.GroupKey * 2)()
+    for i, (sj, sc) in enumerate(gcols):
+        ka[i].src_join, ka[i].src_col = sj, sc
+    max_groups = 16
+
+    def call(left, right, op, rt):
+        specs = [("count_star", "column", left, None, None)] + [(fn, op, left, right, rt) for fn in ("count", "sum", "min", "max")]
+        res = (capi.AggValue * (max_groups * len(specs)))()
+        C.memset(res, SENTINEL, C.sizeof(res))
+        gkeys = np.full((max_groups, 2), -3, np.int64)
+        gnulls = np.full(max_groups, 0xABCD, np.uint32)
+        arena = np.full(64, SENTINEL, np.uint8)
+        n_g, used, oor = C.c_uint64(55), C.c_uint64(66), C.c_uint64(77)
+        rc = gpu_ctx.L.polr_out_aggregate_hashed_expr(s.out.h, None, ka, 2, capi.make_agg_exprs(specs), len(specs), max_groups,
+                                                      gkeys.ctypes.data, gnulls.ctypes.data, res, C.byref(n_g), arena.ctypes.data,
+                                                      64, C.byref(used), C.byref(oor))
+        untouched = (bytes(res) == bytes([SENTINEL]) * C.sizeof(res) and (gkeys == -3).all() and (gnulls == 0xABCD).all()
+                     and (arena == SENTINEL).all())
+        return rc, oor.value, n_g.value, used.value, untouched
+
+    left, right = s.col("p_int32"), s.col("b0_int32")
+    (lv, lok), (rv, rok) = s.values(*left), s.values(*right)
+    _, bad = expr_values("*", lv, lok, rv, rok, np.int32)
+    assert bad > 0
+    rc, oor, n_g, used, untouched = call(left, right, "*", np.int32)
+    assert rc == capi.E_RANGE and oor == 4 * bad
+    assert untouched and n_g == 55 and used == 0
+    # the same output and groups, an expression that stays in range: the groups do not fit
+    rc, oor, n_g, used, untouched = call(s.col("p_int8"), s.col("b0_int8"), "+", np.int16)
+    assert rc == capi.E_OVERFLOW and oor == 0 and n_g > max_groups and untouched
+    s.close()
+
+
 def test_fused_sink_is_unchanged(gpu_ctx):
     """polr_out_fuse_grouped takes polr_agg_spec -- plain columns -- as before, and answers as polr_out_aggregate_grouped_expr
     does for the column form over the emitted row ids"""
