@@ -7,6 +7,7 @@ import pytest
 import common
 from common import orc
 from polr_amd import host
+from mpxreplay import replay
 from test_oracle_golden import SCENARIOS, scenario, scenario_paths
 
 V = 1024
@@ -58,27 +59,7 @@ def test_host_multiplexer_replays_reference_trace(name, key):
     if routing == "exponential_backoff":
         kw["regret_budget"] = n / 10240.0 / 10 / 1
     mpx = host.HostMultiplexer(len(paths), routing, **kw)
-    # the routing loop: path of a bypass chunk = the current path of the multiplexer
-    n_chunks = (n + V - 1) // V
-    c, skips, in_process, cur_path = 0, 0, False, 0
-    while c < n_chunks:
-        c0, size = c * V, min(V, n - c * V)
-        if skips > 0 and not in_process:
-            take = min(skips, n_chunks - c)
-            begin, end = c0, min(n, (c + take) * V)
-            mpx.increase_input(end - begin)
-            if skips != 2**64 - 1:
-                skips -= take
-            mpx.set_skips(skips)
-            c += take
-        else:
-            more, off, cnt, cur_path, skips = mpx.execute(size)
-            begin, end = c0 + off, c0 + off + cnt
-            in_process = more
-            if not more:
-                c += 1
-        mpx.add_intermediates(int(prefix[end, cur_path] - prefix[begin, cur_path]))
-    mpx.finalize_path_run()
+    replay(mpx, prefix, n, V)  # the routing loop
     rounds = [int(x) for x in mpx.log_csv().strip().splitlines()[1:]]
     assert rounds == g["rounds"]
     assert mpx.tuple_counts() == g["tuple_counts"]
