@@ -68,6 +68,13 @@ struct polr_mpx {
 	polr_mpx_stats *stats_host = nullptr; // pinned, mapped: closing statistics of a POLR_RUN_FINISH run
 	polr_mpx_stats *stats_host_dev = nullptr;
 	bool stats_in_host = false;
+	// range stealing (polr_mpx_run_resident_stealing): the claim words of the runs this multiplexer leads + the
+	// executors' counters behind them, and what they are initialised from with every launch
+	unsigned long long *steal_dev = nullptr;
+	uint32_t steal_cap = 0;
+	std::vector<unsigned long long> steal_host;
+	bool steal_run = false;            // the last run of this multiplexer was a stealing run (its counters are in done_host)
+	polr_steal_stats steal_stats = {}; // picked up by polr_mpx_finish(_many)
 	// optional per-launch timing (measurement only)
 	bool timing = false;
 	std::vector<hipEvent_t> ev_start, ev_stop;
@@ -92,6 +99,17 @@ static hipError_t adopt_stream(polr_mpx *m, hipStream_t st) {
 	}
 	m->last_stream = st;
 	return e;
+}
+
+// after the stream of a run has been synchronised: the stealing counters its router left in the pinned words
+static void collect_steal_stats(polr_mpx *m) {
+	memset(&m->steal_stats, 0, sizeof(m->steal_stats));
+	if (m->steal_run) {
+		volatile uint32_t *w = (volatile uint32_t *)m->done_host;
+		m->steal_stats.chunks_routed = w[12];
+		m->steal_stats.chunks_stolen = w[13];
+		m->steal_stats.n_steals = w[14];
+	}
 }
 
 static void drain_events(polr_mpx *m) {
@@ -441,6 +459,7 @@ static int run_begin(RunState &rs, polr_mpx *m, void *stream, uint64_t chunk_beg
 	                   (const uint64_t *)m->chunk_offsets_dev, m->n_chunks, p->n_tuples);
 	m->steps_base = ((volatile uint32_t *)m->done_host)[0];
 	((volatile uint32_t *)m->done_host)[1] = 0;
+	m->steal_run = false;
 	// prime: route the first round of this run into the descriptor slot the next launch reads
 	const uint32_t slot0 = m->iter & 1u;
 	hipLaunchKernelGGL(polr_mpx_router_kernel, dim3(1), dim3(64), 0, st, m->dev, m->round_dev + slot0,
@@ -567,7 +586,8 @@ static_assert(sizeof(PoolRun) <= POOL_HEADER_BYTES, "run header");
 // ranges_per_exec > 1: chunk_begin / chunk_end are [n][ranges_per_exec] (executor i routes its ranges in order)
 static int run_resident_impl(polr_mpx **ms, void *stream, const uint64_t *chunk_begin, const uint64_t *chunk_end,
                              uint32_t n, polr_out *out, uint32_t flags, uint64_t morsel_begin, uint64_t morsel_end,
-                             uint32_t morsel_chunks, bool backpressure = false, uint32_t ranges_per_exec = 1) {
+                             uint32_t morsel_chunks, bool backpressure = false, uint32_t ranges_per_exec = 1,
+                             uint32_t grant_chunks = 0) {
 	if (!ms || n == 0 || !ms[0] || (morsel_chunks == 0 && (!chunk_begin || !chunk_end))) {
 		return POLR_E_INVALID;
 	}
@@ -596,6 +616,23 @@ static int run_resident_impl(polr_mpx **ms, void *stream, const uint64_t *chunk_
 			if (cb > ce || ce > ms[i]->n_chunks) {
 				POLR_FAIL(ctx, POLR_E_INVALID, "chunks [%llu, %llu) outside the %llu source chunks", (unsigned long long)cb,
 				          (unsigned long long)ce, (unsigned long long)ms[i]->n_chunks);
+			}
+		}
+	}
+	if (grant_chunks) {
+		// range stealing rests on the words describing pairwise disjoint pieces of the table (polr_steal.h)
+		std::vector<std::pair<uint64_t, uint64_t>> pieces;
+		for (uint32_t i = 0; i < n; i++) {
+			if (chunk_begin[i] < chunk_end[i]) {
+				pieces.emplace_back(chunk_begin[i], chunk_end[i]);
+			}
+		}
+		std::sort(pieces.begin(), pieces.end());
+		for (size_t i = 1; i < pieces.size(); i++) {
+			if (pieces[i].first < pieces[i - 1].second) {
+				POLR_FAIL(ctx, POLR_E_INVALID, "range stealing needs pairwise disjoint ranges: chunks [%llu, %llu) and [%llu, %llu) overlap",
+				          (unsigned long long)pieces[i - 1].first, (unsigned long long)pieces[i - 1].second,
+				          (unsigned long long)pieces[i].first, (unsigned long long)pieces[i].second);
 			}
 		}
 	}
@@ -733,6 +770,17 @@ static int run_resident_impl(polr_mpx **ms, void *stream, const uint64_t *chunk_
 		m0->pool_hi_cap = hc;
 		m0->pool_dirty = false;
 	}
+	if (grant_chunks && m0->steal_cap < n) {
+		if (m0->steal_dev) {
+			HIPCHK(ctx, hipStreamSynchronize(st));
+			hipFree(m0->steal_dev);
+			m0->steal_dev = nullptr;
+			m0->steal_cap = 0;
+		}
+		const uint32_t cap = std::max<uint32_t>(n, 8);
+		HIPCHK(ctx, hipMalloc((void **)&m0->steal_dev, (size_t)cap * 5 * sizeof(unsigned long long)));
+		m0->steal_cap = cap;
+	}
 	std::vector<char> host(execs_bytes, 0);
 	PoolRun *hr = (PoolRun *)host.data();
 	ResidentExec *ex = (ResidentExec *)(host.data() + POOL_HEADER_BYTES);
@@ -804,6 +852,9 @@ static int run_resident_impl(polr_mpx **ms, void *stream, const uint64_t *chunk_
 		ex[i].morsel_end = morsel_end;
 		ex[i].morsel_chunks = morsel_chunks;
 		ex[i].path_plus1 = backpressure ? i + 1 : 0;
+		ex[i].steal_words = grant_chunks ? m0->steal_dev : nullptr;
+		ex[i].grant_chunks = grant_chunks;
+		m->steal_run = grant_chunks != 0;
 		ex[i].chunk_offsets = m->chunk_offsets_dev;
 		ex[i].n_chunks = m->n_chunks;
 		ex[i].n_tuples = p->n_tuples;
@@ -827,6 +878,16 @@ static int run_resident_impl(polr_mpx **ms, void *stream, const uint64_t *chunk_
 	if (morsel_chunks) {
 		const unsigned long long first = morsel_begin;
 		HIPCHK(ctx, hipMemcpyAsync(cursor_dev, &first, 8, hipMemcpyHostToDevice, st));
+	}
+	if (grant_chunks) {
+		// the claim words (and the zeroed counters behind them) with EVERY launch: the device consumes them, so a pass
+		// that repeats the previous one and re-sends no descriptors still needs them fresh
+		m0->steal_host.assign((size_t)n * 5, 0ull);
+		for (uint32_t i = 0; i < n; i++) {
+			m0->steal_host[i] = polr_steal::pack((uint32_t)chunk_begin[i], (uint32_t)chunk_end[i]);
+		}
+		HIPCHK(ctx, hipMemcpyAsync(m0->steal_dev, m0->steal_host.data(), (size_t)n * 5 * sizeof(unsigned long long),
+		                           hipMemcpyHostToDevice, st));
 	}
 	DevOut dout;
 	memset(&dout, 0, sizeof(dout));
@@ -885,6 +946,35 @@ int polr_mpx_run_resident(polr_mpx **ms, void *stream, const uint64_t *chunk_beg
                           uint32_t n, polr_out *out, uint32_t flags) {
 	POLR_ENTRY();
 	return run_resident_impl(ms, stream, chunk_begin, chunk_end, n, out, flags, 0, 0, 0);
+}
+
+// Range stealing (protocol: polr_steal.h; router side: polr_pool_steal_pull).  Every executor routes its own contiguous
+// range grant by grant; one that has run dry takes the far half of whoever has most left and goes on there with the
+// multiplexer state it has.
+// Deterministic: the row set, COUNT(*) and the routed tuples -- every chunk of the ranges is routed exactly once.
+// Not deterministic once a steal has happened: which executor routes which chunks, hence per-executor traces and the
+// total intermediates (as with morsels, and as in the multi-threaded reference).
+// Reproducible all the same: while no executor has two grants to give (grant_chunks >= half of every range) nobody can
+// steal, and the run IS the fixed-range run of polr_mpx_run_resident, decision for decision.
+int polr_mpx_run_resident_stealing(polr_mpx **ms, void *stream, const uint64_t *chunk_begin, const uint64_t *chunk_end,
+                                   uint32_t grant_chunks, uint32_t n, polr_out *out, uint32_t flags) {
+	POLR_ENTRY();
+	if (!ms || n == 0 || !ms[0] || !chunk_begin || !chunk_end) {
+		return POLR_E_INVALID;
+	}
+	if (grant_chunks == 0) {
+		POLR_FAIL(ms[0]->pipe->ctx, POLR_E_INVALID, "range stealing needs a grant of at least one chunk");
+	}
+	return run_resident_impl(ms, stream, chunk_begin, chunk_end, n, out, flags, 0, 0, 0, false, 1, grant_chunks);
+}
+
+int polr_mpx_steal_stats(polr_mpx *m, polr_steal_stats *stats) {
+	POLR_ENTRY();
+	if (!m || !stats) {
+		return POLR_E_INVALID;
+	}
+	*stats = m->steal_stats;
+	return POLR_OK;
 }
 
 int polr_mpx_run_resident_morsels(polr_mpx **ms, void *stream, uint64_t chunk_begin, uint64_t chunk_end,
@@ -994,6 +1084,7 @@ int polr_mpx_finish(polr_mpx *m, void *stream, polr_mpx_stats *stats) {
 		POLR_FAIL(ctx, POLR_E_HIP, "multiplexer finish failed: %s", hipGetErrorString(e));
 	}
 	m->pending_sync = false;
+	collect_steal_stats(m);
 	if (((volatile uint32_t *)m->done_host)[2]) {
 		((volatile uint32_t *)m->done_host)[2] = 0;
 		m->pool_dirty = true;
@@ -1043,6 +1134,7 @@ int polr_mpx_finish_many(polr_mpx **ms, uint32_t n, polr_mpx_stats *stats) {
 			memcpy(&stats[i], m->stats_host, sizeof(polr_mpx_stats));
 		}
 		m->pending_sync = false;
+		collect_steal_stats(m);
 		if (m->timing) {
 			drain_events(m);
 		}
@@ -1163,6 +1255,9 @@ void polr_mpx_destroy(polr_mpx *m) {
 	}
 	if (m->share_dev) {
 		hipFree(m->share_dev);
+	}
+	if (m->steal_dev) {
+		hipFree(m->steal_dev);
 	}
 	if (m->pool_dev) {
 		hipFree(m->pool_dev);

@@ -11,6 +11,7 @@
 #include "../../include/polr_hip.h"
 #include "polr_device.h"
 #include "polr_routing.h"
+#include "polr_steal.h"
 
 #define POLR_SLOTS 4 // rounds one executor can have in flight in a one-launch run (see ResidentSync)
 
@@ -318,8 +319,12 @@ struct ResidentExec {
 	// further chunk ranges of this executor, routed one after the other behind [chunk_begin, chunk_end) with the same
 	// multiplexer state (polr_mpx_run_resident_ranges: a static list of morsels per executor)
 	uint32_t n_more;
-	uint32_t pad2;
+	uint32_t grant_chunks; // stealing mode: chunks per grant
 	uint64_t more_begin[POLR_MORE_RANGES], more_end[POLR_MORE_RANGES];
+	// stealing mode (steal_words != nullptr; polr_steal.h, polr_mpx_run_resident_stealing): one claim word per executor
+	// of the run, this executor's at [its index]; [chunk_begin, chunk_end) is what its word starts with.  Behind the
+	// n words: unsigned long long[n][4] = {chunks routed, chunks stolen as thief, steals, -} per executor.
+	unsigned long long *steal_words;
 };
 
 #define POLR_RES_HOT_DWORDS (offsetof(DevMpx, stage_out) / 4)
@@ -375,7 +380,7 @@ __device__ __forceinline__ void polr_offs_cache_fill(OffsCache &oc, const Reside
 		n = cap;
 	}
 	// (never beyond the executor's own range: the boundary after its last chunk is the last entry it reads)
-	if (!x.morsel_cursor && x.chunk_end >= from && n > x.chunk_end - from + 1) {
+	if (!x.morsel_cursor && !x.steal_words && x.chunk_end >= from && n > x.chunk_end - from + 1) {
 		n = x.chunk_end - from + 1;
 	}
 	__builtin_amdgcn_wave_barrier();

@@ -51,7 +51,8 @@ __device__ __forceinline__ void pool_load_exec(const ResidentExec *xp, ResidentE
 	x.morsel_chunks = uni(xp->morsel_chunks);
 	x.path_plus1 = uni(xp->path_plus1);
 	x.n_more = uni(xp->n_more);
-	x.pad2 = 0;
+	x.grant_chunks = uni(xp->grant_chunks);
+	x.steal_words = (unsigned long long *)uni64((uint64_t)xp->steal_words);
 #pragma unroll
 	for (int j = 0; j < POLR_MORE_RANGES; j++) {
 		x.more_begin[j] = uni64(xp->more_begin[j]);

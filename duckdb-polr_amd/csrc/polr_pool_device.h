@@ -544,6 +544,71 @@ __device__ __forceinline__ uint32_t pool_lane_now() {
 	return l;
 }
 
+// Stealing mode (polr_steal.h): this executor's grant is used up (or it has none yet).  Full wave.  Claim the next
+// grant of its own word; if the word is empty, steal the far half of whoever has most left -- victim scan lane-parallel
+// over the n words, a wave reduction with the protocol's own order -- and claim from there.  Leaves chunk_idx >=
+// chunk_end when nobody has two grants left: the next routing step then ends the executor.  Nobody waits for anybody,
+// so there is nothing here for a watchdog.  Counters (fire and forget): unsigned long long[4] per executor behind the
+// words = {chunks routed, chunks stolen, steals}.
+// (Cold: once per grant, behind a wave-uniform branch of the step loop, everything it needs passed as scalars.)
+__device__ __forceinline__ void polr_pool_steal_pull(DevMpx *m, unsigned long long *words, uint32_t n, uint32_t self_v,
+                                                     uint32_t grant) {
+	const uint32_t lane = pool_lane_now();
+	const uint32_t self = uni(self_v); // (the executor's number arrives in a vector register; addresses made from it here stay scalar)
+	unsigned long long *ctr = words + n + 4u * (size_t)self;
+	uint32_t b = 0, e = 0;
+	while (true) {
+		uint32_t got = 0;
+		if (lane == 0) {
+			got = polr_steal::claim(words + self, grant, &b, &e) ? 1u : 0u;
+		}
+		if (__builtin_amdgcn_readfirstlane(got)) {
+			if (lane == 0) {
+				m->chunk_idx = b;
+				m->chunk_end = e;
+				m->done = 0;
+				__hip_atomic_fetch_add(&ctr[0], (unsigned long long)(e - b), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+			}
+			return;
+		}
+		uint32_t best_rem = 0, best = 0xFFFFFFFFu, best_lo = 0, best_hi = 0;
+		for (uint32_t i = lane; i < n; i += 64) {
+			if (i == self) {
+				continue;
+			}
+			const uint64_t v = polr_steal::word_load(words + i);
+			const uint32_t rem = polr_steal::remainder_of(v);
+			if (polr_steal::better_victim(rem, i, best_rem, best)) {
+				best_rem = rem;
+				best = i;
+				best_lo = (uint32_t)v;
+				best_hi = (uint32_t)(v >> 32);
+			}
+		}
+		for (int d = 32; d > 0; d >>= 1) {
+			const uint32_t o_rem = __shfl_xor(best_rem, d, 64), o_idx = __shfl_xor(best, d, 64);
+			const uint32_t o_lo = __shfl_xor(best_lo, d, 64), o_hi = __shfl_xor(best_hi, d, 64);
+			if (polr_steal::better_victim(o_rem, o_idx, best_rem, best)) {
+				best_rem = o_rem;
+				best = o_idx;
+				best_lo = o_lo;
+				best_hi = o_hi;
+			}
+		}
+		int r = -1;
+		if (lane == 0 && best != 0xFFFFFFFFu) {
+			r = polr_steal::take(words, best, ((uint64_t)best_hi << 32) | best_lo, self, grant, &b, &e);
+			if (r > 0) {
+				__hip_atomic_fetch_add(&ctr[1], (unsigned long long)(e - b), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+				__hip_atomic_fetch_add(&ctr[2], 1ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+			}
+		}
+		if (__builtin_amdgcn_readfirstlane(r) < 0) {
+			return; // (nobody has two grants left)
+		}
+	}
+}
+
 // lds: POLR_RES_ROUTER_DWORDS dwords of state + scratch_lds: POLR_RES_HOT_DWORDS dwords (saved state of a rehearsal);
 // cache_lds / cache_cap: window of the chunk-offset array in 8-byte entries.
 __device__ __forceinline__ void polr_pool_router(const ResidentExec &x, PoolRun *run, const PoolRun &rh, uint32_t exec,
@@ -624,12 +689,15 @@ __device__ __forceinline__ void polr_pool_router(const ResidentExec &x, PoolRun 
 		}
 	}
 	if (lane == 0) {
-		m->chunk_idx = x.morsel_cursor ? 0 : x.chunk_begin;
-		m->chunk_end = x.morsel_cursor ? 0 : x.chunk_end;
+		// (stealing mode: the executor starts with an empty grant -- its first step claims, or steals, even when its own
+		// range is empty)
+		const bool pulls = x.morsel_cursor || x.steal_words;
+		m->chunk_idx = pulls ? 0 : x.chunk_begin;
+		m->chunk_end = pulls ? 0 : x.chunk_end;
 		m->chunk_offsets = x.chunk_offsets;
 		m->n_chunks = x.n_chunks;
 		m->n_tuples = x.n_tuples;
-		m->done = x.chunk_begin >= x.chunk_end ? 1 : 0;
+		m->done = x.chunk_begin >= x.chunk_end && !x.steal_words ? 1 : 0;
 		rt[POOL_RT_DIAG + 6] = 0; // (no watchdog of this router has fired)
 	}
 	__builtin_amdgcn_wave_barrier();
@@ -792,6 +860,11 @@ __device__ __forceinline__ void polr_pool_router(const ResidentExec &x, PoolRun 
 				m->done = 0;
 			}
 		}
+		if (x.steal_words && uni64(vm->chunk_idx) >= uni64(vm->chunk_end)) {
+			// this executor's grant is used up: the next one of its own range, else half of somebody else's
+			// (like a morsel boundary: a rehearsal that ran off the grant published nothing, so n_fly <= 1 here)
+			polr_pool_steal_pull(m, x.steal_words, rh.n_exec, exec, x.grant_chunks);
+		}
 		n_steps++;
 		__builtin_amdgcn_wave_barrier();
 		RT_T(rt2)
@@ -898,6 +971,13 @@ __device__ __forceinline__ void polr_pool_router(const ResidentExec &x, PoolRun 
 		}
 	}
 	__builtin_amdgcn_wave_barrier();
+	if (x.steal_words && lane == 0 && host_words) {
+		// this executor's stealing counters leave with the run's statistics (polr_mpx_steal_stats)
+		const unsigned long long *ctr = x.steal_words + rh.n_exec + 4u * (size_t)uni(exec);
+		host_words[12] = (uint32_t)__hip_atomic_load(&ctr[0], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+		host_words[13] = (uint32_t)__hip_atomic_load(&ctr[1], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+		host_words[14] = (uint32_t)__hip_atomic_load(&ctr[2], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+	}
 	if (x.flags & POLR_RUN_FINISH) {
 		if (lane == 0) {
 			polr_close_run(m);

@@ -41,6 +41,7 @@ EXPORTS = [
     "polr_ht_set_payload_heaps", "polr_pipeline_set_probe_heaps", "polr_out_aggregate_hashed_str", "polr_out_column_width",
     "polr_ht_encode_dictionary", "polr_ht_fetch_dictionary",
     "polr_out_aggregate_expr", "polr_out_aggregate_grouped_expr", "polr_out_aggregate_hashed_expr",
+    "polr_mpx_run_resident_stealing", "polr_mpx_steal_stats",
 ]
 
 
@@ -194,6 +195,10 @@ class MpxStats(C.Structure):
                 ("stage_out", (C.c_uint64 * MAX_JOINS) * MAX_PATHS)]
 
 
+class StealStats(C.Structure):
+    _fields_ = [("chunks_routed", C.c_uint64), ("chunks_stolen", C.c_uint64), ("n_steals", C.c_uint32), ("pad", C.c_uint32)]
+
+
 _lib = None
 
 
@@ -275,6 +280,8 @@ def load():
     L.polr_out_fused_result.argtypes = [vp, vp, vp, C.c_uint64, vp]
     L.polr_mpx_run_resident.argtypes = [vp, vp, vp, vp, u32, vp, u32]
     L.polr_mpx_run_resident_morsels.argtypes = [vp, vp, C.c_uint64, C.c_uint64, u32, u32, vp, u32]
+    L.polr_mpx_run_resident_stealing.argtypes = [vp, vp, vp, vp, u32, u32, vp, u32]
+    L.polr_mpx_steal_stats.argtypes = [vp, vp]
     L.polr_mpx_run_backpressure.argtypes = [vp, vp, C.c_uint64, C.c_uint64, u32, vp, u32]
     L.polr_mpx_enable_timing.argtypes = [vp, C.c_int]
     L.polr_mpx_kernel_time.argtypes = [vp, P(C.c_double), P(u64)]
@@ -866,6 +873,13 @@ class DeviceMultiplexer:
                 "path_resistances": [st.path_resistances[i] for i in range(P)],
                 "stage_out": [[st.stage_out[i][j] for j in range(self.pipe.k)] for i in range(P)]}
 
+    def steal_stats(self):
+        """polr_mpx_steal_stats: this executor's counters of its last run, after finish / finish_many (zeros unless that
+        run was a run_resident_stealing)"""
+        st = StealStats()
+        self.ctx.check(self.ctx.L.polr_mpx_steal_stats(self.h, C.byref(st)))
+        return {"chunks_routed": st.chunks_routed, "chunks_stolen": st.chunks_stolen, "n_steals": st.n_steals}
+
     def reset(self, stream=None):
         self.ctx.check(self.ctx.L.polr_mpx_reset(self.h, stream))
 
@@ -958,6 +972,20 @@ def run_resident_morsels(mpxs, chunk_begin, chunk_end, morsel_chunks=120, out=No
                                                   out.h if out else None,
                                                   (RUN_RESET if reset else 0) | (RUN_FINISH if finish else 0) |
                                                   ((share & 0xFF) << 8 if share > 1 else 0)))
+
+
+def run_resident_stealing(mpxs, ranges, grant_chunks, out=None, reset=False, finish=False, share=1):
+    """polr_mpx_run_resident_stealing: mpxs[i] owns the chunks ranges[i] = (begin, end) (pairwise disjoint, may be empty)
+    and takes them grant_chunks at a time; an executor that has run dry steals the far half of whoever has most left"""
+    ctx = mpxs[0].ctx
+    n = len(mpxs)
+    hs = (C.c_void_p * n)(*[m.h for m in mpxs])
+    b = np.ascontiguousarray([r[0] for r in ranges], dtype=np.uint64)
+    e = np.ascontiguousarray([r[1] for r in ranges], dtype=np.uint64)
+    ctx.check(ctx.L.polr_mpx_run_resident_stealing(hs, None, b.ctypes.data, e.ctypes.data, grant_chunks, n,
+                                                   out.h if out else None,
+                                                   (RUN_RESET if reset else 0) | (RUN_FINISH if finish else 0) |
+                                                   ((share & 0xFF) << 8 if share > 1 else 0)))
 
 
 def run_backpressure(mpxs, chunk_begin, chunk_end, morsel_chunks=120, out=None, reset=True, finish=True):

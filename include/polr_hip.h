@@ -625,6 +625,25 @@ int polr_mpx_run_resident_ranges(polr_mpx **ms, void *stream, const uint64_t *ra
  * and total intermediates are not. */
 int polr_mpx_run_resident_morsels(polr_mpx **ms, void *stream, uint64_t chunk_begin, uint64_t chunk_end,
                                   uint32_t morsel_chunks, uint32_t n, polr_out *out, uint32_t flags);
+/* Range stealing: as polr_mpx_run_resident -- executor i owns the contiguous chunks [chunk_begin[i], chunk_end[i]), which
+ * may be empty -- but it takes them `grant_chunks` chunks at a time, and an executor that has run dry takes the far half
+ * (in whole grants) of the executor that has most left, and goes on there with the multiplexer state it has: what the
+ * reference's worker threads get from the task scheduler (pipeline.cpp:145-174).  An executor keeps to one stretch of the
+ * table as long as it has one; only the tail of the run is rebalanced.
+ * Deterministic: row set, COUNT(*), routed tuples.  Not deterministic once a steal has happened: per-executor traces and
+ * total intermediates.  While no range holds two grants nobody can steal, and the run is the fixed-range run of
+ * polr_mpx_run_resident, decision for decision.
+ * POLR_E_INVALID: grant_chunks == 0, a range outside the source, ranges that are not pairwise disjoint (the protocol
+ * rests on it).  flags as for polr_mpx_run_resident. */
+int polr_mpx_run_resident_stealing(polr_mpx **ms, void *stream, const uint64_t *chunk_begin, const uint64_t *chunk_end,
+                                   uint32_t grant_chunks, uint32_t n, polr_out *out, uint32_t flags);
+typedef struct polr_steal_stats {
+	uint64_t chunks_routed; /* source chunks this executor routed */
+	uint64_t chunks_stolen; /* of these, taken from other executors' ranges (always whole grants) */
+	uint32_t n_steals, pad;
+} polr_steal_stats;
+/* this executor's counters of its last run; after polr_mpx_finish(_many); zeros after any run that was not a stealing run */
+int polr_mpx_steal_stats(polr_mpx *m, polr_steal_stats *stats);
 /* MultiplexerRouting::BACKPRESSURE (src/parallel/pipeline.cpp:147-156, src/parallel/polar_config.cpp:128-147): the
  * reference schedules ONE task per join order over a single shared source state, so the join orders race for the
  * source and the cheaper ones end up with more of it.  ms: one multiplexer per join order of the pipeline (created with
