@@ -44,7 +44,7 @@ struct polr_mpx {
 	uint64_t scan_generation = 0;    // ... of this scan
 	uint32_t *log_path = nullptr;
 	uint64_t *log_tuples = nullptr, *log_inter = nullptr;
-	uint32_t *done_host = nullptr;        // pinned, mapped: [0] routing steps completed, [1] done
+	volatile uint32_t *done_host = nullptr;    // pinned, mapped: the words the device reports in (PolrHostWord)
 	volatile uint32_t *progress_dev = nullptr; // the device's view of done_host
 	uint32_t steps_base = 0;
 	bool pending_sync = false;
@@ -101,15 +101,55 @@ static hipError_t adopt_stream(polr_mpx *m, hipStream_t st) {
 	return e;
 }
 
+// Replace the device buffer *buf (capacity *cap, in the caller's units) by one of `bytes` bytes and capacity new_cap, for
+// work about to be enqueued on `st`.  What is queued on `st` may still use the old one: synchronise before freeing it.
+template <typename T, typename Cap>
+static int grow_buffer(polr_ctx *ctx, hipStream_t st, T **buf, Cap *cap, Cap new_cap, size_t bytes) {
+	if (*buf) {
+		HIPCHK(ctx, hipStreamSynchronize(st));
+		hipFree(*buf);
+		*buf = nullptr;
+		*cap = 0;
+	}
+	HIPCHK(ctx, hipMalloc((void **)buf, bytes));
+	*cap = new_cap;
+	return POLR_OK;
+}
+
 // after the stream of a run has been synchronised: the stealing counters its router left in the pinned words
 static void collect_steal_stats(polr_mpx *m) {
 	memset(&m->steal_stats, 0, sizeof(m->steal_stats));
 	if (m->steal_run) {
-		volatile uint32_t *w = (volatile uint32_t *)m->done_host;
-		m->steal_stats.chunks_routed = w[12];
-		m->steal_stats.chunks_stolen = w[13];
-		m->steal_stats.n_steals = w[14];
+		m->steal_stats.chunks_routed = m->done_host[POLR_HW_CHUNKS_ROUTED];
+		m->steal_stats.chunks_stolen = m->done_host[POLR_HW_CHUNKS_STOLEN];
+		m->steal_stats.n_steals = m->done_host[POLR_HW_STEALS];
 	}
+}
+
+// optional per-launch timing: take the next event pair of `m` (made on demand) and record its start on `st` ...
+static int timing_start(polr_mpx *m, hipStream_t st, size_t *ev) {
+	if (!m->timing) {
+		return POLR_OK;
+	}
+	polr_ctx *ctx = m->pipe->ctx;
+	*ev = m->ev_used++;
+	if (*ev >= m->ev_start.size()) {
+		hipEvent_t a, b;
+		HIPCHK(ctx, hipEventCreate(&a));
+		HIPCHK(ctx, hipEventCreate(&b));
+		m->ev_start.push_back(a);
+		m->ev_stop.push_back(b);
+	}
+	HIPCHK(ctx, hipEventRecord(m->ev_start[*ev], st));
+	return POLR_OK;
+}
+
+// ... and its stop, behind the launch
+static int timing_stop(polr_mpx *m, hipStream_t st, size_t ev) {
+	if (m->timing) {
+		HIPCHK(m->pipe->ctx, hipEventRecord(m->ev_stop[ev], st));
+	}
+	return POLR_OK;
 }
 
 static void drain_events(polr_mpx *m) {
@@ -240,10 +280,10 @@ int polr_mpx_create(polr_pipeline *p, const polr_mpx_config *cfg, polr_mpx **out
 	e = e == hipSuccess ? hipMalloc((void **)&m->log_path, max_log * 4) : e;
 	e = e == hipSuccess ? hipMalloc((void **)&m->log_tuples, max_log * 8) : e;
 	e = e == hipSuccess ? hipMalloc((void **)&m->log_inter, max_log * 8) : e;
-	e = e == hipSuccess ? hipHostMalloc((void **)&m->done_host, 64, hipHostMallocMapped) : e;
+	e = e == hipSuccess ? hipHostMalloc((void **)&m->done_host, POLR_HOST_WORDS_BYTES, hipHostMallocMapped) : e;
 	if (e == hipSuccess) {
-		memset(m->done_host, 0, 64);
-		e = hipHostGetDevicePointer((void **)&m->progress_dev, m->done_host, 0);
+		memset((void *)m->done_host, 0, POLR_HOST_WORDS_BYTES);
+		e = hipHostGetDevicePointer((void **)&m->progress_dev, (void *)m->done_host, 0);
 	}
 	e = e == hipSuccess ? hipMemset(m->counts_dev, 0, POLR_SLOTS * POLR_NSHARD * POLR_KMAX * 8) : e;
 	e = e == hipSuccess ? hipMalloc((void **)&m->sync_dev, sizeof(ResidentSync)) : e;
@@ -339,6 +379,45 @@ static int order_pool_launch(polr_ctx *ctx, hipStream_t st, uint32_t share) {
 	return POLR_OK;
 }
 
+// The shape of a pool launch of pipeline `p`: which kernel, on which descriptors, how wide its workgroups are and how
+// many of them a CU holds.  (The part of the preparation that asks the kernels' own occupancy and LDS functions.)
+struct PoolShape {
+	bool flat;             // the flat pipeline's kernel (polr_pool.hip), else the generic one (polr_poolg.hip)
+	const DevPipeline *dp; // the variant of the pipeline's descriptors the launch runs on
+	uint32_t wq;           // slots per queued tuple: ids (+ multiplicity)
+	uint32_t wpb;          // waves per workgroup; 0: does not fit at all
+	uint32_t fused_words;  // 8-byte cells of a fused GROUP BY sink the launch keeps in LDS
+	uint32_t router_areas; // routers a probe workgroup of the flat kernel can host in its own LDS
+	int occ;               // workgroups per CU, as the occupancy function returned it; < 1: does not fit on a CU
+};
+
+static PoolShape pool_shape(polr_pipeline *p, bool materialize, const polr_out *out) {
+	PoolShape sh;
+	// a bank of single-key unique-match joins takes the flat pipeline -- counting runs always, emitting runs when every
+	// join is a perfect table (polr_flat_device.h); it runs on the counting variant's descriptors either way
+	sh.flat = p->host_count.flat != 0 && (!materialize || p->flat_emit);
+	const DevPipeline &dp = (materialize && !sh.flat) ? p->host_mat : p->host_count;
+	sh.dp = &dp;
+	sh.wq = dp.W + (dp.mult ? 1u : 0u);
+	sh.wpb = sh.flat ? p->flat_wpb : polr_pool_waves_per_block(dp.k, sh.wq);
+	// a fused GROUP BY sink keeps its cells in the workgroup's LDS when they fit behind the bit tables, the queues and
+	// the router areas (160 KB per workgroup), else in its table in global memory.  (Decided BEFORE the grid is sized:
+	// the workgroups per CU are those of the launch as it is made -- a workgroup that is not co-resident would take
+	// its routers' executors with it.)
+	sh.fused_words = 0;
+	if (sh.flat && sh.wpb && out && out->fused_dev) {
+		const uint64_t words = (uint64_t)out->fused_groups * (1u + 2u * out->fused_aggs);
+		if (polr_pool_flat_lds_bytes(dp.k, sh.wpb, dp.lds_table_dwords) + 8 + words * 8 <= 160u * 1024u) {
+			sh.fused_words = (uint32_t)words;
+		}
+	}
+	sh.occ = sh.wpb == 0 ? 0
+	                     : (sh.flat ? polr_pool_flat_occupancy(dp.k, sh.wpb, dp.lds_table_dwords, materialize, sh.fused_words)
+	                                : polr_pool_occupancy(dp.k, sh.wq, dp.ext != 0));
+	sh.router_areas = sh.flat && sh.occ >= 1 ? polr_pool_flat_router_areas(dp.k, sh.wpb, dp.lds_table_dwords) : 0u;
+	return sh;
+}
+
 int polr_pipeline_launch_info(polr_pipeline *p, int materialize, polr_launch_info *info) {
 	POLR_ENTRY();
 	if (!p || !info) {
@@ -346,26 +425,22 @@ int polr_pipeline_launch_info(polr_pipeline *p, int materialize, polr_launch_inf
 	}
 	polr_ctx *ctx = p->ctx;
 	HIPCHK(ctx, hipSetDevice(ctx->device));
-	const bool mat = materialize != 0;
-	const bool flat = p->host_count.flat != 0 && (!mat || p->flat_emit);
-	const DevPipeline &dp = (mat && !flat) ? p->host_mat : p->host_count;
-	const uint32_t wq = dp.W + (dp.mult ? 1u : 0u); // slots per queued tuple in the pool launch: ids (+ multiplicity)
-	const uint32_t wpb = flat ? p->flat_wpb : polr_pool_waves_per_block(dp.k, wq);
+	const PoolShape sh = pool_shape(p, materialize != 0, nullptr); // (the occupancy without a fused sink's cells)
+	const DevPipeline &dp = *sh.dp;
 	memset(info, 0, sizeof(*info));
-	info->waves_per_workgroup = wpb;
-	const int occ = wpb == 0 ? 0 : (flat ? polr_pool_flat_occupancy(dp.k, wpb, dp.lds_table_dwords, mat) : polr_pool_occupancy(dp.k, wq, dp.ext != 0));
-	if (occ < 1) {
+	info->waves_per_workgroup = sh.wpb;
+	if (sh.occ < 1) {
 		POLR_FAIL(ctx, POLR_E_UNSUPPORTED, "per-wave LDS queues exceed 160 KB (too many joins x carried ids)");
 	}
-	info->workgroups_per_cu = (uint32_t)std::max(0, std::min(occ, 8));
-	info->lds_bytes_per_workgroup = (uint32_t)(flat ? polr_pool_flat_lds_bytes(dp.k, wpb, dp.lds_table_dwords)
-	                                                : polr_pool_lds_bytes(dp.k, wq));
+	info->workgroups_per_cu = (uint32_t)std::min(sh.occ, 8);
+	info->lds_bytes_per_workgroup = (uint32_t)(sh.flat ? polr_pool_flat_lds_bytes(dp.k, sh.wpb, dp.lds_table_dwords)
+	                                                   : polr_pool_lds_bytes(dp.k, sh.wq));
 	info->compiled_stages = dp.k <= 2 ? 2 : (dp.k <= 4 ? 4 : (dp.k <= 6 ? 6 : 8));
-	info->tuple_slots = flat ? dp.W : wq;
+	info->tuple_slots = sh.flat ? dp.W : sh.wq;
 	info->n_cus = (uint32_t)ctx->n_cus;
-	info->flat = flat ? 1u : 0u;
-	info->lds_tables = flat ? dp.n_lds_tables : 0u;
-	info->lds_table_bytes = flat ? dp.lds_table_dwords * 4u : 0u;
+	info->flat = sh.flat ? 1u : 0u;
+	info->lds_tables = sh.flat ? dp.n_lds_tables : 0u;
+	info->lds_table_bytes = sh.flat ? dp.lds_table_dwords * 4u : 0u;
 	return POLR_OK;
 }
 
@@ -457,8 +532,8 @@ static int run_begin(RunState &rs, polr_mpx *m, void *stream, uint64_t chunk_beg
 	}
 	hipLaunchKernelGGL(polr_mpx_set_range_kernel, dim3(1), dim3(1), 0, st, m->dev, chunk_begin, chunk_end,
 	                   (const uint64_t *)m->chunk_offsets_dev, m->n_chunks, p->n_tuples);
-	m->steps_base = ((volatile uint32_t *)m->done_host)[0];
-	((volatile uint32_t *)m->done_host)[1] = 0;
+	m->steps_base = m->done_host[POLR_HW_STEPS];
+	m->done_host[POLR_HW_DONE] = 0;
 	m->steal_run = false;
 	// prime: route the first round of this run into the descriptor slot the next launch reads
 	const uint32_t slot0 = m->iter & 1u;
@@ -486,12 +561,11 @@ static int run_begin(RunState &rs, polr_mpx *m, void *stream, uint64_t chunk_beg
 static int run_pump(RunState &rs) {
 	polr_mpx *m = rs.m;
 	polr_ctx *ctx = m->pipe->ctx;
-	volatile uint32_t *prog = (volatile uint32_t *)m->done_host;
 	const uint32_t look_ahead = 3;
-	const uint32_t steps = prog[0] - rs.base_steps; // 1 after the prime step, +1 per routed launch
-	if (prog[1] && steps >= 1) {
+	const uint32_t steps = m->done_host[POLR_HW_STEPS] - rs.base_steps; // 1 after the prime step, +1 per routed launch
+	if (m->done_host[POLR_HW_DONE] && steps >= 1) {
 		rs.finished = true; // the router has seen the end of the range
-		m->steps_base = prog[0];
+		m->steps_base = m->done_host[POLR_HW_STEPS];
 		m->pending_sync = true; // the queued tail is drained by whoever synchronises next
 		return POLR_OK;
 	}
@@ -499,16 +573,9 @@ static int run_pump(RunState &rs) {
 		return POLR_OK; // enough launches in flight
 	}
 	size_t ev = 0;
-	if (m->timing) {
-		ev = m->ev_used++;
-		if (ev >= m->ev_start.size()) {
-			hipEvent_t a, b;
-			HIPCHK(ctx, hipEventCreate(&a));
-			HIPCHK(ctx, hipEventCreate(&b));
-			m->ev_start.push_back(a);
-			m->ev_stop.push_back(b);
-		}
-		HIPCHK(ctx, hipEventRecord(m->ev_start[ev], rs.st));
+	int rc = timing_start(m, rs.st, &ev);
+	if (rc) {
+		return rc;
 	}
 	rs.sr.iter = m->iter++;
 	hipError_t e = polr_launch_path_kernel(rs.W, rs.k, rs.max_blocks, rs.wpb, rs.st, rs.dpd, m->round_dev,
@@ -516,11 +583,8 @@ static int run_pump(RunState &rs) {
 	if (e != hipSuccess) {
 		POLR_FAIL(ctx, POLR_E_HIP, "path kernel launch failed: %s", hipGetErrorString(e));
 	}
-	if (m->timing) {
-		HIPCHK(ctx, hipEventRecord(m->ev_stop[ev], rs.st));
-	}
 	rs.launched++;
-	return POLR_OK;
+	return timing_stop(m, rs.st, ev);
 }
 
 int polr_mpx_run(polr_mpx *m, void *stream, uint64_t chunk_begin, uint64_t chunk_end, polr_out *out) {
@@ -572,27 +636,56 @@ int polr_mpx_run_many(polr_mpx **ms, void **streams, const uint64_t *chunk_begin
 // The whole run in ONE launch (polr_pool.hip): one router wave per executor + a pool of probe waves that serves
 // the rounds of all executors; routing decisions never leave the device, the host only enqueues.  Asynchronous:
 // polr_mpx_finish / _finish_many synchronise.
-static uint32_t next_pow2_u32(uint64_t v) {
-	uint32_t p = 1;
-	while (p < v) {
-		p <<= 1;
-	}
-	return p;
+//
+// run_resident_impl prepares it in phases: validate the request, the launch's shape (pool_shape), its plan
+// (polr_pool_plan.h), the device buffers, the descriptors, enqueue.  Every refusal (POLR_E_INVALID /
+// POLR_E_UNSUPPORTED: validate_request, plan_run) happens before the first change to any multiplexer's state and
+// before anything is enqueued.
+
+// where the executors of a run get their chunks from, and how the run is made (filled by the five entry points)
+struct ResidentRequest {
+	const uint64_t *range_begin, *range_end; // [n][ranges_per_exec]: executor i routes its ranges in order (unless morsels)
+	uint32_t ranges_per_exec;
+	uint64_t morsel_begin, morsel_end; // morsel_chunks != 0: the executors share these chunks, pulled from one cursor
+	uint32_t morsel_chunks;
+	bool backpressure;     // executor i sends everything down join order i
+	uint32_t grant_chunks; // != 0: range stealing, chunks per grant
+	uint32_t flags;
+	polr_out *out;
+};
+
+// executor i routes the ranges_per_exec ranges [i][..] of begin / end, in order
+static ResidentRequest ranges_request(const uint64_t *begin, const uint64_t *end, uint32_t ranges_per_exec, polr_out *out,
+                                      uint32_t flags) {
+	ResidentRequest rq = {};
+	rq.range_begin = begin;
+	rq.range_end = end;
+	rq.ranges_per_exec = ranges_per_exec;
+	rq.out = out;
+	rq.flags = flags;
+	return rq;
+}
+
+// the executors share the chunks [begin, end) and pull them morsel_chunks at a time
+static ResidentRequest morsel_request(uint64_t begin, uint64_t end, uint32_t morsel_chunks, polr_out *out, uint32_t flags) {
+	ResidentRequest rq = {};
+	rq.ranges_per_exec = 1;
+	rq.morsel_begin = begin;
+	rq.morsel_end = end;
+	rq.morsel_chunks = morsel_chunks;
+	rq.out = out;
+	rq.flags = flags;
+	return rq;
 }
 
 #define POOL_HEADER_BYTES 512
 static_assert(sizeof(PoolRun) <= POOL_HEADER_BYTES, "run header");
 
-// ranges_per_exec > 1: chunk_begin / chunk_end are [n][ranges_per_exec] (executor i routes its ranges in order)
-static int run_resident_impl(polr_mpx **ms, void *stream, const uint64_t *chunk_begin, const uint64_t *chunk_end,
-                             uint32_t n, polr_out *out, uint32_t flags, uint64_t morsel_begin, uint64_t morsel_end,
-                             uint32_t morsel_chunks, bool backpressure = false, uint32_t ranges_per_exec = 1,
-                             uint32_t grant_chunks = 0) {
-	if (!ms || n == 0 || !ms[0] || (morsel_chunks == 0 && (!chunk_begin || !chunk_end))) {
+static int validate_request(polr_mpx **ms, uint32_t n, const ResidentRequest &rq) {
+	if (!ms || n == 0 || !ms[0] || (rq.morsel_chunks == 0 && (!rq.range_begin || !rq.range_end))) {
 		return POLR_E_INVALID;
 	}
-	polr_mpx *m0 = ms[0];
-	polr_pipeline *p = m0->pipe;
+	polr_pipeline *p = ms[0]->pipe;
 	polr_ctx *ctx = p->ctx;
 	if (n > 4096) {
 		POLR_FAIL(ctx, POLR_E_UNSUPPORTED, "at most 4096 executors per run");
@@ -600,7 +693,7 @@ static int run_resident_impl(polr_mpx **ms, void *stream, const uint64_t *chunk_
 	if (p->n_tuples >= 0xFFFFFFF0ull) {
 		POLR_FAIL(ctx, POLR_E_UNSUPPORTED, "source partition too large for 32-bit tuple positions");
 	}
-	if (out && out->pipe != p) {
+	if (rq.out && rq.out->pipe != p) {
 		POLR_FAIL(ctx, POLR_E_INVALID, "output object belongs to another pipeline");
 	}
 	for (uint32_t i = 0; i < n; i++) {
@@ -610,21 +703,21 @@ static int run_resident_impl(polr_mpx **ms, void *stream, const uint64_t *chunk_
 		if (!ms[i]->chunk_offsets_owned && (!p->scan_valid || ms[i]->scan_generation != p->scan_generation)) {
 			POLR_FAIL(ctx, POLR_E_INVALID, "the pipeline was scanned again: call polr_mpx_use_scan_chunks");
 		}
-		for (uint32_t r = 0; r < (morsel_chunks ? 1u : ranges_per_exec); r++) {
-			const uint64_t cb = morsel_chunks ? morsel_begin : chunk_begin[(size_t)i * ranges_per_exec + r];
-			const uint64_t ce = morsel_chunks ? morsel_end : chunk_end[(size_t)i * ranges_per_exec + r];
+		for (uint32_t r = 0; r < (rq.morsel_chunks ? 1u : rq.ranges_per_exec); r++) {
+			const uint64_t cb = rq.morsel_chunks ? rq.morsel_begin : rq.range_begin[(size_t)i * rq.ranges_per_exec + r];
+			const uint64_t ce = rq.morsel_chunks ? rq.morsel_end : rq.range_end[(size_t)i * rq.ranges_per_exec + r];
 			if (cb > ce || ce > ms[i]->n_chunks) {
 				POLR_FAIL(ctx, POLR_E_INVALID, "chunks [%llu, %llu) outside the %llu source chunks", (unsigned long long)cb,
 				          (unsigned long long)ce, (unsigned long long)ms[i]->n_chunks);
 			}
 		}
 	}
-	if (grant_chunks) {
+	if (rq.grant_chunks) {
 		// range stealing rests on the words describing pairwise disjoint pieces of the table (polr_steal.h)
 		std::vector<std::pair<uint64_t, uint64_t>> pieces;
 		for (uint32_t i = 0; i < n; i++) {
-			if (chunk_begin[i] < chunk_end[i]) {
-				pieces.emplace_back(chunk_begin[i], chunk_end[i]);
+			if (rq.range_begin[i] < rq.range_end[i]) {
+				pieces.emplace_back(rq.range_begin[i], rq.range_end[i]);
 			}
 		}
 		std::sort(pieces.begin(), pieces.end());
@@ -636,295 +729,222 @@ static int run_resident_impl(polr_mpx **ms, void *stream, const uint64_t *chunk_
 			}
 		}
 	}
-	{
-		std::vector<polr_mpx *> sorted(ms, ms + n);
-		std::sort(sorted.begin(), sorted.end());
-		if (std::adjacent_find(sorted.begin(), sorted.end()) != sorted.end()) {
-			POLR_FAIL(ctx, POLR_E_INVALID, "the same multiplexer twice in one run");
-		}
+	std::vector<polr_mpx *> sorted(ms, ms + n);
+	std::sort(sorted.begin(), sorted.end());
+	if (std::adjacent_find(sorted.begin(), sorted.end()) != sorted.end()) {
+		POLR_FAIL(ctx, POLR_E_INVALID, "the same multiplexer twice in one run");
 	}
-	HIPCHK(ctx, hipSetDevice(ctx->device));
-	hipStream_t st = stream ? (hipStream_t)stream : m0->own_stream;
-	const bool materialize = out != nullptr;
-	// a bank of single-key unique-match joins takes the flat pipeline -- counting runs always, emitting runs when every
-	// join is a perfect table (polr_flat_device.h); it runs on the counting variant's descriptors either way
-	const bool flat = p->host_count.flat != 0 && (!materialize || p->flat_emit);
-	const DevPipeline &dp = (materialize && !flat) ? p->host_mat : p->host_count;
-	const uint32_t wq = dp.W + (dp.mult ? 1u : 0u); // slots per queued tuple: ids (+ multiplicity)
-	const uint32_t wpb = flat ? p->flat_wpb : polr_pool_waves_per_block(dp.k, wq);
-	// a fused GROUP BY sink keeps its cells in the workgroup's LDS when they fit behind the bit tables, the queues and
-	// the router areas (160 KB per workgroup), else in its table in global memory.  (Decided BEFORE the grid is sized:
-	// the workgroups per CU are those of the launch as it is made -- a workgroup that is not co-resident would take
-	// its routers' executors with it.)
-	uint32_t fused_words = 0;
-	if (flat && wpb && out && out->fused_dev) {
-		const uint64_t words = (uint64_t)out->fused_groups * (1u + 2u * out->fused_aggs);
-		if (polr_pool_flat_lds_bytes(dp.k, wpb, dp.lds_table_dwords) + 8 + words * 8 <= 160u * 1024u) {
-			fused_words = (uint32_t)words;
-		}
-	}
-	int occ = wpb == 0 ? 0 : (flat ? polr_pool_flat_occupancy(dp.k, wpb, dp.lds_table_dwords, materialize, fused_words) : polr_pool_occupancy(dp.k, wq, dp.ext != 0));
-	if (occ < 1) {
+	return POLR_OK;
+}
+
+// the plan of a launch of shape `sh` for n executors, and the share of the device it is sized for; refuses what does
+// not fit on a CU, a share beyond 16 and more executors than fit on the device
+static int plan_run(polr_ctx *ctx, const PoolShape &sh, uint32_t n, uint64_t n_tuples, uint32_t flags, uint32_t *share,
+                    PoolPlan *plan) {
+	if (sh.occ < 1) {
 		POLR_FAIL(ctx, POLR_E_UNSUPPORTED, "pool kernel does not fit on a CU (per-wave LDS queues: too many joins x carried ids)");
 	}
-	occ = std::min(occ, 8);
-	uint32_t share = std::max<uint32_t>((flags >> 8) & 0xFFu, 1u);
+	*share = std::max<uint32_t>((flags >> 8) & 0xFFu, 1u);
 	if (ctx->tuning.device_share) { // (polr_ctx_set_pool_tuning)
-		share = ctx->tuning.device_share;
+		*share = ctx->tuning.device_share;
 	}
-	if (share > 16) {
-		POLR_FAIL(ctx, POLR_E_INVALID, "device share 1/%u: at most 16 runs side by side", share);
+	if (*share > 16) {
+		POLR_FAIL(ctx, POLR_E_INVALID, "device share 1/%u: at most 16 runs side by side", *share);
 	}
-	// grid: never more than is co-resident.  Mixed layout (flat kernel, whose workgroup owns its CU): every workgroup
-	// probes and hosts the routers of executors b, b + n_blocks, .. in its first waves -- as long as the router areas of
-	// the workgroups (polr_pool_flat_router_areas, never all waves) can host all executors.  Else the separate layout:
-	// router workgroups first (one wave per executor), then the pool.  (The generic kernel runs two workgroups per CU
-	// with its LDS nearly used up: router areas there would cost the second workgroup; it keeps router workgroups.)
-	const uint32_t capacity = std::max<uint32_t>((uint32_t)ctx->n_cus * (uint32_t)occ / share, 2u);
-	const uint32_t router_areas = flat ? std::min<uint32_t>(polr_pool_flat_router_areas(dp.k, wpb, dp.lds_table_dwords), wpb - 1u) : 0u;
-	const bool mixed = (uint64_t)n <= (uint64_t)capacity * router_areas;
-	const uint32_t n_router_blocks = mixed ? 0u : (n + wpb - 1) / wpb;
-	if (n_router_blocks + 1 > capacity) {
+	*plan = polr_pool_plan((uint32_t)ctx->n_cus, sh.occ, *share, sh.flat, sh.wq, sh.wpb, sh.router_areas, n, n_tuples,
+	                       ctx->tuning);
+	if (!plan->fits) {
 		POLR_FAIL(ctx, POLR_E_UNSUPPORTED, "%u executors do not fit on the device at once", n);
 	}
-	const uint32_t n_blocks = capacity;
-	for (uint32_t i = 0; i < n; i++) {
-		// (work still queued on `st` needs no host synchronisation: everything a run touches is ordered by the
-		// stream -- consecutive passes can be enqueued back to back)
-		HIPCHK(ctx, adopt_stream(ms[i], st));
-	}
-	const size_t execs_bytes = POOL_HEADER_BYTES + (size_t)n * sizeof(ResidentExec) + 64;
+	return POLR_OK;
+}
+
+// the buffers of the runs `m0` leads, large enough for this one: descriptors, work-sharing records, unit rings, claim words
+static int ensure_run_buffers(polr_mpx *m0, hipStream_t st, uint32_t n, const PoolPlan &pl, bool stealing) {
+	polr_ctx *ctx = m0->pipe->ctx;
 	if (m0->execs_cap < n) {
-		if (m0->execs_dev) {
-			HIPCHK(ctx, hipStreamSynchronize(st));
-			hipFree(m0->execs_dev);
-			m0->execs_dev = nullptr;
-		}
 		const uint32_t cap = std::max<uint32_t>(n, 8);
-		HIPCHK(ctx, hipMalloc((void **)&m0->execs_dev, POOL_HEADER_BYTES + (size_t)cap * sizeof(ResidentExec) + 64));
-		m0->execs_cap = cap;
 		m0->execs_host.clear();
+		int rc = grow_buffer(ctx, st, &m0->execs_dev, &m0->execs_cap, cap,
+		                     POOL_HEADER_BYTES + (size_t)cap * sizeof(ResidentExec) + 64);
+		if (rc) {
+			return rc;
+		}
 	}
-	// unit rings: sized for everything the executors of this run can have in flight (two slots each) plus the EXIT
-	// entries, with a factor of two to spare
-	const uint32_t pool_waves = mixed ? n_blocks * wpb - n : (n_blocks - n_router_blocks) * wpb;
-	// Rings in use: every ring must have probe waves that serve it.  Ring capacity: a round of U units leaves at most
-	// U / R + 1 entries on a ring; the executors that have rounds in flight (a of them, at most POLR_SLOTS rounds each) published them
-	// when at least a executors were still routing, so all their lo units together are at most POLR_SLOTS x (4 x pool_waves + 17 a);
-	// a hi round has at most POLR_POOL_HI_TUPLES / 64 units.  Twice that, plus the EXIT entries.
-	uint32_t n_rings = 1;
-	while (n_rings * 2 <= std::min<uint32_t>(POLR_POOL_RINGS, pool_waves)) {
-		n_rings *= 2;
-	}
-	const uint64_t R = n_rings;
-	// (+ a round larger than target x 65 536 tuples has tuples / 65 536 units)
-	const uint32_t lo_cap = next_pow2_u32(2ull * ((4ull * POLR_SLOTS * pool_waves + 17ull * POLR_SLOTS * n +
-	                                               (uint64_t)POLR_SLOTS * (p->n_tuples >> 16)) / R +
-	                                              (uint64_t)POLR_SLOTS * n + pool_waves / R + 16) + 64);
-	// (+ work sharing: a probe wave has at most one shared piece outstanding, published on the ring after its own)
-	const uint32_t hi_cap = next_pow2_u32(
-	    2ull * ((uint64_t)POLR_SLOTS * n * (POLR_POOL_HI_TUPLES / POLR_POOL_HI_UNIT / R + 1) + pool_waves / R + 1) + 64);
-	if (((volatile uint32_t *)m0->done_host)[2]) {
+	if (m0->done_host[POLR_HW_GIVEN_UP]) {
 		// an earlier run on these rings was given up (whoever finished it): probe waves left holding tickets
 		m0->pool_dirty = true;
 		if (!m0->pending_sync) {
-			((volatile uint32_t *)m0->done_host)[2] = 0; // (nothing in flight that could still report it)
+			m0->done_host[POLR_HW_GIVEN_UP] = 0; // (nothing in flight that could still report it)
 		}
 	}
-	// work sharing (generic pipeline only): records of 8 + 64 x (words per queued tuple) dwords, one per probe wave, and
-	// their flags -- all flags are 0 between runs (a record is released by the wave that took it) unless a run was given up
-	const uint32_t share_after = flat ? 0xFFFFFFFFu : (ctx->tuning.share_after ? ctx->tuning.share_after : 32u);
-	const uint32_t share_stride = 8u + 64u * wq;
-	uint32_t *share_recs = nullptr, *share_flags = nullptr;
-	if (share_after != 0xFFFFFFFFu) {
-		const size_t need = ((size_t)pool_waves * share_stride + pool_waves) * sizeof(uint32_t);
+	// work-sharing records, one per probe wave, and their flags: all flags are 0 between runs (a record is released by the
+	// wave that took it) unless a run was given up
+	if (pl.share_after != 0xFFFFFFFFu) {
+		const size_t need = ((size_t)pl.pool_waves * pl.share_stride + pl.pool_waves) * sizeof(uint32_t);
 		if (m0->share_bytes < need) {
-			if (m0->share_dev) {
-				HIPCHK(ctx, hipStreamSynchronize(st));
-				hipFree(m0->share_dev);
-				m0->share_dev = nullptr;
-				m0->share_bytes = 0;
+			int rc = grow_buffer(ctx, st, &m0->share_dev, &m0->share_bytes, need, need);
+			if (rc) {
+				return rc;
 			}
-			HIPCHK(ctx, hipMalloc((void **)&m0->share_dev, need));
-			m0->share_bytes = need;
 			HIPCHK(ctx, hipMemsetAsync(m0->share_dev, 0, need, st));
 		} else if (m0->pool_dirty) {
 			HIPCHK(ctx, hipMemsetAsync(m0->share_dev, 0, m0->share_bytes, st));
 		}
-		share_recs = m0->share_dev;
-		share_flags = m0->share_dev + (size_t)pool_waves * share_stride;
 	}
-	if (!m0->pool_dev || m0->pool_lo_cap < lo_cap || m0->pool_hi_cap < hi_cap || m0->pool_dirty) {
-		if (m0->pool_dev && (m0->pool_lo_cap < lo_cap || m0->pool_hi_cap < hi_cap)) {
-			HIPCHK(ctx, hipStreamSynchronize(st));
-			hipFree(m0->pool_dev);
-			m0->pool_dev = nullptr;
-		}
-		const uint32_t lc = std::max(lo_cap, m0->pool_lo_cap), hc = std::max(hi_cap, m0->pool_hi_cap);
+	// unit rings: never smaller than before; zeroed when new or when a run on them was given up
+	const bool too_small = m0->pool_lo_cap < pl.lo_cap || m0->pool_hi_cap < pl.hi_cap;
+	if (!m0->pool_dev || too_small || m0->pool_dirty) {
+		const uint32_t lc = std::max(pl.lo_cap, m0->pool_lo_cap), hc = std::max(pl.hi_cap, m0->pool_hi_cap);
 		const size_t bytes = sizeof(PoolSync) + (size_t)POLR_POOL_RINGS * (2 * (size_t)lc + hc) * sizeof(PoolEntry);
-		if (!m0->pool_dev) {
-			HIPCHK(ctx, hipMalloc((void **)&m0->pool_dev, bytes));
+		if (!m0->pool_dev || too_small) {
+			int rc = grow_buffer(ctx, st, &m0->pool_dev, &m0->pool_lo_cap, lc, bytes);
+			if (rc) {
+				return rc;
+			}
 		}
 		HIPCHK(ctx, hipMemsetAsync(m0->pool_dev, 0, bytes, st));
 		m0->pool_lo_cap = lc;
 		m0->pool_hi_cap = hc;
 		m0->pool_dirty = false;
 	}
-	if (grant_chunks && m0->steal_cap < n) {
-		if (m0->steal_dev) {
-			HIPCHK(ctx, hipStreamSynchronize(st));
-			hipFree(m0->steal_dev);
-			m0->steal_dev = nullptr;
-			m0->steal_cap = 0;
-		}
+	if (stealing && m0->steal_cap < n) {
 		const uint32_t cap = std::max<uint32_t>(n, 8);
-		HIPCHK(ctx, hipMalloc((void **)&m0->steal_dev, (size_t)cap * 5 * sizeof(unsigned long long)));
-		m0->steal_cap = cap;
+		return grow_buffer(ctx, st, &m0->steal_dev, &m0->steal_cap, cap, (size_t)cap * 5 * sizeof(unsigned long long));
 	}
-	std::vector<char> host(execs_bytes, 0);
+	return POLR_OK;
+}
+
+// where the morsel cursor of the runs `m0` leads sits: behind the executor descriptors
+static unsigned long long *morsel_cursor_dev(polr_mpx *m0) {
+	return (unsigned long long *)(m0->execs_dev + POOL_HEADER_BYTES + (size_t)m0->execs_cap * sizeof(ResidentExec));
+}
+
+// the run header (from the plan) and the executor descriptors (from the request), as they go to the device; marks the
+// multiplexers as taking part in this run
+static std::vector<char> fill_descriptors(polr_mpx **ms, uint32_t n, const ResidentRequest &rq, const PoolPlan &pl) {
+	polr_mpx *m0 = ms[0];
+	std::vector<char> host(POOL_HEADER_BYTES + (size_t)n * sizeof(ResidentExec), 0);
 	PoolRun *hr = (PoolRun *)host.data();
 	ResidentExec *ex = (ResidentExec *)(host.data() + POOL_HEADER_BYTES);
-	unsigned long long *cursor_dev =
-	    (unsigned long long *)(m0->execs_dev + POOL_HEADER_BYTES + (size_t)m0->execs_cap * sizeof(ResidentExec));
+	const bool sharing = pl.share_after != 0xFFFFFFFFu;
 	hr->sync = m0->pool_dev;
 	hr->n_exec = n;
-	hr->n_router_blocks = n_router_blocks;
-	hr->routers_per_block = mixed ? n / n_blocks : 0u;
-	hr->routers_rem = mixed ? n % n_blocks : 0u;
-	hr->n_rings = n_rings;
-	{
-		const polr_pool_tuning &tn = ctx->tuning; // (polr_ctx_set_pool_tuning; 0 = default)
-		hr->units_x = tn.units_x ? tn.units_x : 4u; // (ring capacities are sized for 4)
-		// tuples per unit of a small round.  Default: flat: two steps of the pipeline's stage 0 (1 024 tuples = one
-		// exploration slice of init_tuple_count in one
-		// unit: measured 1.52 ms against 1.55-1.56 with 512 on the SF100 run), generic: a wide step of 256.  64-tuple units
-		// finish a lone small round soonest, but a unit costs its wave the same chain of dependent round trips whatever
-		// its size, and with hundreds of executors exploring that wave time is what the pool runs out of (measured on
-		// the SF100 run: 2.29 ms with 64-tuple units, 1.77 ms with 512)
-		{
-			// the fewest probe waves any ring has; the lottery divides them into at most 8 classes
-			const uint32_t min_waves = pool_waves / n_rings;
-			uint32_t lot = 1;
-			while (lot * 2 <= std::min<uint32_t>(8, min_waves)) {
-				lot *= 2;
-			}
-			hr->hi_lottery = (tn.hi_lottery >= 1 && tn.hi_lottery <= lot) ? tn.hi_lottery : lot;
-		}
-		// (generic pipelines with few executors: 64 -- an exploration slice spread over 16 waves; measured on the 113
-		// JOB-shaped pipelines, 8 executors each: 46.9 ms per pass against 47.4 with 128 and 49.8 with 256)
-		hr->hi_unit = tn.hi_unit ? tn.hi_unit : (flat ? 1024u : (n <= 64u ? 64u : 256u));
-	}
-	for (uint32_t r = 0; r < POLR_POOL_RINGS; r++) {
-		hr->worker_waves[r] = r < n_rings ? (pool_waves + n_rings - 1 - r) / n_rings : 0u; // (wave g serves ring g % n_rings)
-	}
-	hr->pool_waves = pool_waves;
-	hr->lo_cap = m0->pool_lo_cap;
+	hr->n_router_blocks = pl.n_router_blocks;
+	hr->routers_per_block = pl.routers_per_block;
+	hr->routers_rem = pl.routers_rem;
+	hr->n_rings = pl.n_rings;
+	hr->units_x = pl.units_x;
+	hr->hi_lottery = pl.hi_lottery;
+	hr->hi_unit = pl.hi_unit;
+	memcpy(hr->worker_waves, pl.worker_waves, sizeof(hr->worker_waves));
+	hr->pool_waves = pl.pool_waves;
+	hr->lo_cap = m0->pool_lo_cap; // (the rings as they are: never smaller than the plan's)
 	hr->hi_cap = m0->pool_hi_cap;
-	// (the size up to which a round is latency-critical)
-	hr->hi_tuples = ctx->tuning.hi_tuples_p1 ? std::min<uint32_t>(ctx->tuning.hi_tuples_p1 - 1u, POLR_POOL_HI_TUPLES)
-	                                         : POLR_POOL_HI_TUPLES;
-	hr->idle_sleep = ctx->tuning.idle_sleep == 16 ? 16u : 64u; // (an idle probe wave's longest back-off)
-	// watchdog: ticks of the 100 MHz wall clock (default 4 s: a wait this long is a lost run)
-	hr->timeout_ticks = ctx->tuning.watchdog_us ? (unsigned long long)ctx->tuning.watchdog_us * 100ull : POLR_RES_TIMEOUT_TICKS;
-	hr->share_recs = share_recs;
-	hr->share_flags = share_flags;
-	hr->share_stride = share_stride;
-	hr->share_after = share_after;
+	hr->hi_tuples = pl.hi_tuples;
+	hr->idle_sleep = pl.idle_sleep;
+	hr->timeout_ticks = pl.timeout_ticks;
+	hr->share_recs = sharing ? m0->share_dev : nullptr;
+	hr->share_flags = sharing ? m0->share_dev + (size_t)pl.pool_waves * pl.share_stride : nullptr;
+	hr->share_stride = pl.share_stride;
+	hr->share_after = pl.share_after;
 	hr->routers_done = 0;
 	hr->abort = 0;
 	// the rings belong to the multiplexer that leads the run: a run that is given up says so in ITS host words too,
 	// whichever router saw the watchdog fire (the leader's own router may have finished long before)
 	hr->host_words = m0->progress_dev;
+	const uint32_t rpe = rq.ranges_per_exec;
 	for (uint32_t i = 0; i < n; i++) {
 		polr_mpx *m = ms[i];
 		m->leader = m0;
 		ex[i].mpx = m->dev;
 		ex[i].sync = m->sync_dev;
 		ex[i].counts = m->counts_dev;
-		ex[i].chunk_begin = morsel_chunks ? 0 : chunk_begin[(size_t)i * ranges_per_exec];
-		ex[i].chunk_end = morsel_chunks ? 0 : chunk_end[(size_t)i * ranges_per_exec];
-		ex[i].n_more = morsel_chunks ? 0 : ranges_per_exec - 1;
-		for (uint32_t r = 1; r < ranges_per_exec && !morsel_chunks; r++) {
-			ex[i].more_begin[r - 1] = chunk_begin[(size_t)i * ranges_per_exec + r];
-			ex[i].more_end[r - 1] = chunk_end[(size_t)i * ranges_per_exec + r];
+		if (rq.morsel_chunks) {
+			ex[i].morsel_cursor = morsel_cursor_dev(m0);
+		} else {
+			ex[i].chunk_begin = rq.range_begin[(size_t)i * rpe];
+			ex[i].chunk_end = rq.range_end[(size_t)i * rpe];
+			ex[i].n_more = rpe - 1;
+			for (uint32_t r = 1; r < rpe; r++) {
+				ex[i].more_begin[r - 1] = rq.range_begin[(size_t)i * rpe + r];
+				ex[i].more_end[r - 1] = rq.range_end[(size_t)i * rpe + r];
+			}
 		}
-		ex[i].morsel_cursor = morsel_chunks ? cursor_dev : nullptr;
-		ex[i].morsel_end = morsel_end;
-		ex[i].morsel_chunks = morsel_chunks;
-		ex[i].path_plus1 = backpressure ? i + 1 : 0;
-		ex[i].steal_words = grant_chunks ? m0->steal_dev : nullptr;
-		ex[i].grant_chunks = grant_chunks;
-		m->steal_run = grant_chunks != 0;
+		ex[i].morsel_end = rq.morsel_end;
+		ex[i].morsel_chunks = rq.morsel_chunks;
+		ex[i].path_plus1 = rq.backpressure ? i + 1 : 0;
+		ex[i].steal_words = rq.grant_chunks ? m0->steal_dev : nullptr;
+		ex[i].grant_chunks = rq.grant_chunks;
+		m->steal_run = rq.grant_chunks != 0;
 		ex[i].chunk_offsets = m->chunk_offsets_dev;
 		ex[i].n_chunks = m->n_chunks;
-		ex[i].n_tuples = p->n_tuples;
-		ex[i].flags = flags;
-		ex[i].pad = 0;
+		ex[i].n_tuples = m->pipe->n_tuples;
+		ex[i].flags = rq.flags;
 		ex[i].stats_out = m->stats_host_dev;
-		m->stats_in_host = (flags & POLR_RUN_FINISH) != 0;
-		((volatile uint32_t *)m->done_host)[1] = 0;
+		m->stats_in_host = (rq.flags & POLR_RUN_FINISH) != 0;
+		m->done_host[POLR_HW_DONE] = 0;
 	}
+	return host;
+}
+
+// everything that goes onto the stream: the descriptors, what the device consumes with every launch, the launch
+static int enqueue_run(polr_mpx **ms, hipStream_t st, uint32_t n, const ResidentRequest &rq, const PoolShape &sh,
+                       const PoolPlan &pl, uint32_t share, const std::vector<char> &host) {
+	polr_mpx *m0 = ms[0];
+	polr_pipeline *p = m0->pipe;
+	polr_ctx *ctx = p->ctx;
 	// A pass that repeats the previous one (same executors, ranges, flags: every step of a measurement loop) finds its
 	// descriptors on the device already; only the two words the device writes (routers_done, abort) are cleared.
 	// Otherwise: one copy (pageable source: staged by the runtime before the call returns).
-	const size_t used = POOL_HEADER_BYTES + (size_t)n * sizeof(ResidentExec);
-	if (m0->execs_host.size() == used && memcmp(m0->execs_host.data(), host.data(), used) == 0) {
+	if (m0->execs_host == host) {
 		static_assert(offsetof(PoolRun, abort) == offsetof(PoolRun, routers_done) + 4, "cleared together");
 		HIPCHK(ctx, hipMemsetAsync(m0->execs_dev + offsetof(PoolRun, routers_done), 0, 8, st));
 	} else {
-		HIPCHK(ctx, hipMemcpyAsync(m0->execs_dev, host.data(), used, hipMemcpyHostToDevice, st));
-		m0->execs_host.assign(host.begin(), host.begin() + used);
+		HIPCHK(ctx, hipMemcpyAsync(m0->execs_dev, host.data(), host.size(), hipMemcpyHostToDevice, st));
+		m0->execs_host = host;
 	}
-	if (morsel_chunks) {
-		const unsigned long long first = morsel_begin;
-		HIPCHK(ctx, hipMemcpyAsync(cursor_dev, &first, 8, hipMemcpyHostToDevice, st));
+	if (rq.morsel_chunks) {
+		const unsigned long long first = rq.morsel_begin;
+		HIPCHK(ctx, hipMemcpyAsync(morsel_cursor_dev(m0), &first, 8, hipMemcpyHostToDevice, st));
 	}
-	if (grant_chunks) {
+	if (rq.grant_chunks) {
 		// the claim words (and the zeroed counters behind them) with EVERY launch: the device consumes them, so a pass
 		// that repeats the previous one and re-sends no descriptors still needs them fresh
 		m0->steal_host.assign((size_t)n * 5, 0ull);
 		for (uint32_t i = 0; i < n; i++) {
-			m0->steal_host[i] = polr_steal::pack((uint32_t)chunk_begin[i], (uint32_t)chunk_end[i]);
+			m0->steal_host[i] = polr_steal::pack((uint32_t)rq.range_begin[i], (uint32_t)rq.range_end[i]);
 		}
 		HIPCHK(ctx, hipMemcpyAsync(m0->steal_dev, m0->steal_host.data(), (size_t)n * 5 * sizeof(unsigned long long),
 		                           hipMemcpyHostToDevice, st));
 	}
 	DevOut dout;
 	memset(&dout, 0, sizeof(dout));
-	if (out) {
-		dout = out->dev;
-		out->stats_valid = false;
+	if (rq.out) {
+		dout = rq.out->dev;
+		rq.out->stats_valid = false;
 	}
 	// order this launch behind the pool launches of other streams it must not share the device with
-	{
-		int rc_o = order_pool_launch(ctx, st, share);
-		if (rc_o) {
-			return rc_o;
-		}
-	}
+	int rc = order_pool_launch(ctx, st, share);
 	size_t ev = 0;
-	if (m0->timing) {
-		ev = m0->ev_used++;
-		if (ev >= m0->ev_start.size()) {
-			hipEvent_t a, b;
-			HIPCHK(ctx, hipEventCreate(&a));
-			HIPCHK(ctx, hipEventCreate(&b));
-			m0->ev_start.push_back(a);
-			m0->ev_stop.push_back(b);
-		}
-		HIPCHK(ctx, hipEventRecord(m0->ev_start[ev], st));
+	rc = rc ? rc : timing_start(m0, st, &ev);
+	if (rc) {
+		return rc;
 	}
+	const bool materialize = rq.out != nullptr;
+	const DevPipeline &dp = *sh.dp;
 	const ResidentExec *execs_dev = (const ResidentExec *)(m0->execs_dev + POOL_HEADER_BYTES);
 	hipError_t e =
-	    flat ? polr_launch_pool_flat_kernel(dp.k, n_blocks, wpb, dp.lds_table_dwords, st, p->dev_count, execs_dev,
-	                                        (PoolRun *)m0->execs_dev, dout, materialize, fused_words)
-	         : polr_launch_pool_kernel(wq, dp.k, n_blocks, st, materialize ? p->dev_mat : p->dev_count, execs_dev,
-	                                   (PoolRun *)m0->execs_dev, dout, dp.ext != 0);
+	    sh.flat ? polr_launch_pool_flat_kernel(dp.k, pl.n_blocks, sh.wpb, dp.lds_table_dwords, st, p->dev_count, execs_dev,
+	                                           (PoolRun *)m0->execs_dev, dout, materialize, sh.fused_words)
+	            : polr_launch_pool_kernel(sh.wq, dp.k, pl.n_blocks, st, materialize ? p->dev_mat : p->dev_count, execs_dev,
+	                                      (PoolRun *)m0->execs_dev, dout, dp.ext != 0);
 	if (e != hipSuccess) {
 		POLR_FAIL(ctx, POLR_E_HIP, "pool kernel launch failed: %s", hipGetErrorString(e));
 	}
-	if (m0->timing) {
-		HIPCHK(ctx, hipEventRecord(m0->ev_stop[ev], st));
+	rc = timing_stop(m0, st, ev);
+	if (rc) {
+		return rc;
 	}
 	HIPCHK(ctx, hipEventRecord(ctx->pool_launches.back().done, st)); // (the entry order_pool_launch made for this launch)
 	for (uint32_t i = 0; i < n; i++) {
@@ -933,19 +953,49 @@ static int run_resident_impl(polr_mpx **ms, void *stream, const uint64_t *chunk_
 	return POLR_OK;
 }
 
+static int run_resident_impl(polr_mpx **ms, void *stream, uint32_t n, const ResidentRequest &rq) {
+	int rc = validate_request(ms, n, rq);
+	if (rc) {
+		return rc;
+	}
+	polr_mpx *m0 = ms[0];
+	polr_pipeline *p = m0->pipe;
+	polr_ctx *ctx = p->ctx;
+	HIPCHK(ctx, hipSetDevice(ctx->device));
+	const PoolShape sh = pool_shape(p, rq.out != nullptr, rq.out);
+	uint32_t share;
+	PoolPlan pl;
+	rc = plan_run(ctx, sh, n, p->n_tuples, rq.flags, &share, &pl);
+	if (rc) {
+		return rc;
+	}
+	// (nothing is refused from here on: the multiplexers' state changes and work is enqueued)
+	hipStream_t st = stream ? (hipStream_t)stream : m0->own_stream;
+	for (uint32_t i = 0; i < n; i++) {
+		// (work still queued on `st` needs no host synchronisation: everything a run touches is ordered by the
+		// stream -- consecutive passes can be enqueued back to back)
+		HIPCHK(ctx, adopt_stream(ms[i], st));
+	}
+	rc = ensure_run_buffers(m0, st, n, pl, rq.grant_chunks != 0);
+	if (rc) {
+		return rc;
+	}
+	return enqueue_run(ms, st, n, rq, sh, pl, share, fill_descriptors(ms, n, rq, pl));
+}
+
 int polr_mpx_run_resident_ranges(polr_mpx **ms, void *stream, const uint64_t *range_begin, const uint64_t *range_end,
                                  uint32_t ranges_per_executor, uint32_t n, polr_out *out, uint32_t flags) {
 	POLR_ENTRY();
 	if (ranges_per_executor < 1 || ranges_per_executor > POLR_MORE_RANGES + 1) {
 		return POLR_E_INVALID;
 	}
-	return run_resident_impl(ms, stream, range_begin, range_end, n, out, flags, 0, 0, 0, false, ranges_per_executor);
+	return run_resident_impl(ms, stream, n, ranges_request(range_begin, range_end, ranges_per_executor, out, flags));
 }
 
 int polr_mpx_run_resident(polr_mpx **ms, void *stream, const uint64_t *chunk_begin, const uint64_t *chunk_end,
                           uint32_t n, polr_out *out, uint32_t flags) {
 	POLR_ENTRY();
-	return run_resident_impl(ms, stream, chunk_begin, chunk_end, n, out, flags, 0, 0, 0);
+	return run_resident_impl(ms, stream, n, ranges_request(chunk_begin, chunk_end, 1, out, flags));
 }
 
 // Range stealing (protocol: polr_steal.h; router side: polr_pool_steal_pull).  Every executor routes its own contiguous
@@ -965,7 +1015,9 @@ int polr_mpx_run_resident_stealing(polr_mpx **ms, void *stream, const uint64_t *
 	if (grant_chunks == 0) {
 		POLR_FAIL(ms[0]->pipe->ctx, POLR_E_INVALID, "range stealing needs a grant of at least one chunk");
 	}
-	return run_resident_impl(ms, stream, chunk_begin, chunk_end, n, out, flags, 0, 0, 0, false, 1, grant_chunks);
+	ResidentRequest rq = ranges_request(chunk_begin, chunk_end, 1, out, flags);
+	rq.grant_chunks = grant_chunks;
+	return run_resident_impl(ms, stream, n, rq);
 }
 
 int polr_mpx_steal_stats(polr_mpx *m, polr_steal_stats *stats) {
@@ -983,7 +1035,7 @@ int polr_mpx_run_resident_morsels(polr_mpx **ms, void *stream, uint64_t chunk_be
 	if (morsel_chunks == 0) {
 		return POLR_E_INVALID;
 	}
-	return run_resident_impl(ms, stream, nullptr, nullptr, n, out, flags, chunk_begin, chunk_end, morsel_chunks);
+	return run_resident_impl(ms, stream, n, morsel_request(chunk_begin, chunk_end, morsel_chunks, out, flags));
 }
 
 // BACKPRESSURE routing (MultiplexerRouting::BACKPRESSURE): one executor per join order, all pulling morsels from one
@@ -1006,7 +1058,9 @@ int polr_mpx_run_backpressure(polr_mpx **ms, void *stream, uint64_t chunk_begin,
 			POLR_FAIL(ctx, POLR_E_INVALID, "multiplexer %u does not route BACKPRESSURE / DEFAULT_PATH", i);
 		}
 	}
-	return run_resident_impl(ms, stream, nullptr, nullptr, n, out, flags, chunk_begin, chunk_end, morsel_chunks, true);
+	ResidentRequest rq = morsel_request(chunk_begin, chunk_end, morsel_chunks, out, flags);
+	rq.backpressure = true;
+	return run_resident_impl(ms, stream, n, rq);
 }
 
 int polr_mpx_reset(polr_mpx *m, void *stream) {
@@ -1026,7 +1080,7 @@ int polr_mpx_reset(polr_mpx *m, void *stream) {
 	HIPCHK(ctx, hipMemsetAsync(m->counts_dev, 0, POLR_SLOTS * POLR_NSHARD * POLR_KMAX * 8, st));
 	hipLaunchKernelGGL(polr_mpx_init_kernel, dim3(1), dim3(1), 0, st, m->dev, m->cfg, m->pipe->n_paths,
 	                   m->pipe->n_tuples, m->n_chunks, m->log_path, m->log_tuples, m->log_inter, m->wide0_mask,
-	                   m->progress_dev, ((volatile uint32_t *)m->done_host)[0]);
+	                   m->progress_dev, m->done_host[POLR_HW_STEPS]);
 	return POLR_OK;
 }
 
@@ -1058,6 +1112,62 @@ int polr_mpx_kernel_time(polr_mpx *m, double *total_ms, uint64_t *n_launches) {
 	return POLR_OK;
 }
 
+// Finishing a run, per multiplexer: enqueue_close, synchronise its stream, settle.
+// enqueue_close: the closing kernel and the read-back of its statistics into *stats -- unless the resident run closed
+// itself (POLR_RUN_FINISH): nothing to launch
+static hipError_t enqueue_close(polr_mpx *m, hipStream_t st, polr_mpx_stats *stats) {
+	if (m->stats_in_host) {
+		return hipSuccess;
+	}
+	if (!m->stats_dev) {
+		hipError_t e = hipMalloc((void **)&m->stats_dev, sizeof(polr_mpx_stats));
+		if (e != hipSuccess) {
+			return e;
+		}
+	}
+	hipLaunchKernelGGL(polr_mpx_finish_kernel, dim3(1), dim3(64), 0, st, m->dev, m->counts_dev, m->pipe->k, m->stats_dev);
+	return hipMemcpyAsync(stats, m->stats_dev, sizeof(polr_mpx_stats), hipMemcpyDeviceToHost, st);
+}
+
+// settle: after the stream of `m` has been synchronised.  true: its run was given up (the word is read and cleared)
+static bool settle(polr_mpx *m, polr_mpx_stats *stats) {
+	if (m->stats_in_host) {
+		memcpy(stats, m->stats_host, sizeof(polr_mpx_stats));
+	}
+	m->pending_sync = false;
+	collect_steal_stats(m);
+	if (m->timing) {
+		drain_events(m);
+	}
+	const bool given_up = m->done_host[POLR_HW_GIVEN_UP] != 0;
+	m->done_host[POLR_HW_GIVEN_UP] = 0;
+	return given_up;
+}
+
+// the rings of a run that was given up are re-initialised before the next one: they belong to the multiplexer that led it
+static void mark_rings_dirty(polr_mpx *m) {
+	m->pool_dirty = true;
+	if (m->leader) {
+		m->leader->pool_dirty = true;
+	}
+}
+
+// whose watchdog fired, and on what: a router that saw it leaves the wait it gave up on in its pinned words; appended to
+// `who` (and the words released for the next run)
+static void report_watchdog(polr_mpx *m, std::string &who) {
+	volatile uint32_t *w = m->done_host;
+	if (!w[POLR_HW_DIAG_VALID]) {
+		return;
+	}
+	char buf[200];
+	snprintf(buf, sizeof(buf), "%s executor %u: slot %u, %u round(s) in flight, %llu of %llu arrival tokens (65536 per unit)",
+	         who.empty() ? ";" : ",", w[POLR_HW_DIAG_EXEC], w[POLR_HW_DIAG_SLOT], w[POLR_HW_DIAG_IN_FLIGHT],
+	         ((unsigned long long)w[POLR_HW_DIAG_ARRIVED_HI] << 32) | w[POLR_HW_DIAG_ARRIVED_LO],
+	         ((unsigned long long)w[POLR_HW_DIAG_WANTED_HI] << 32) | w[POLR_HW_DIAG_WANTED_LO]);
+	who += buf;
+	w[POLR_HW_DIAG_VALID] = 0;
+}
+
 int polr_mpx_finish(polr_mpx *m, void *stream, polr_mpx_stats *stats) {
 	POLR_ENTRY();
 	if (!m || !stats) {
@@ -1067,34 +1177,16 @@ int polr_mpx_finish(polr_mpx *m, void *stream, polr_mpx_stats *stats) {
 	HIPCHK(ctx, hipSetDevice(ctx->device));
 	hipStream_t st = pick_stream(m, stream);
 	HIPCHK(ctx, adopt_stream(m, st));
-	hipError_t e = hipSuccess;
-	if (m->stats_in_host) { // the resident run closed itself: nothing to launch
-		e = hipStreamSynchronize(st);
-		memcpy(stats, m->stats_host, sizeof(polr_mpx_stats));
-	} else {
-		if (!m->stats_dev) {
-			HIPCHK(ctx, hipMalloc((void **)&m->stats_dev, sizeof(polr_mpx_stats)));
-		}
-		hipLaunchKernelGGL(polr_mpx_finish_kernel, dim3(1), dim3(64), 0, st, m->dev, m->counts_dev, m->pipe->k,
-		                   m->stats_dev);
-		e = hipMemcpyAsync(stats, m->stats_dev, sizeof(polr_mpx_stats), hipMemcpyDeviceToHost, st);
-		e = e == hipSuccess ? hipStreamSynchronize(st) : e;
-	}
+	hipError_t e = enqueue_close(m, st, stats);
+	e = e == hipSuccess ? hipStreamSynchronize(st) : e;
 	if (e != hipSuccess) {
 		POLR_FAIL(ctx, POLR_E_HIP, "multiplexer finish failed: %s", hipGetErrorString(e));
 	}
-	m->pending_sync = false;
-	collect_steal_stats(m);
-	if (((volatile uint32_t *)m->done_host)[2]) {
-		((volatile uint32_t *)m->done_host)[2] = 0;
-		m->pool_dirty = true;
-		if (m->leader) {
-			m->leader->pool_dirty = true; // (the rings of the run belong to its first multiplexer)
-		}
-		POLR_FAIL(ctx, POLR_E_HIP, "run timed out waiting for its probe waves (results incomplete)");
-	}
-	if (m->timing) {
-		drain_events(m);
+	if (settle(m, stats)) {
+		mark_rings_dirty(m);
+		std::string who;
+		report_watchdog(m, who);
+		POLR_FAIL(ctx, POLR_E_HIP, "run timed out waiting for its probe waves (results incomplete)%s", who.c_str());
 	}
 	return POLR_OK;
 }
@@ -1109,60 +1201,26 @@ int polr_mpx_finish_many(polr_mpx **ms, uint32_t n, polr_mpx_stats *stats) {
 	polr_ctx *ctx = ms[0]->pipe->ctx;
 	HIPCHK(ctx, hipSetDevice(ctx->device));
 	for (uint32_t i = 0; i < n; i++) {
-		polr_mpx *m = ms[i];
-		hipStream_t st = m->last_stream ? m->last_stream : m->own_stream;
-		if (m->stats_in_host) {
-			continue; // closed inside its resident run
-		}
-		if (!m->stats_dev) {
-			HIPCHK(ctx, hipMalloc((void **)&m->stats_dev, sizeof(polr_mpx_stats)));
-		}
-		hipLaunchKernelGGL(polr_mpx_finish_kernel, dim3(1), dim3(64), 0, st, m->dev, m->counts_dev, m->pipe->k,
-		                   m->stats_dev);
-		HIPCHK(ctx, hipMemcpyAsync(&stats[i], m->stats_dev, sizeof(polr_mpx_stats), hipMemcpyDeviceToHost, st));
+		HIPCHK(ctx, enqueue_close(ms[i], pick_stream(ms[i], nullptr), &stats[i]));
 	}
 	bool timed_out = false;
 	hipStream_t synced = nullptr;
 	for (uint32_t i = 0; i < n; i++) {
-		polr_mpx *m = ms[i];
-		hipStream_t st = m->last_stream ? m->last_stream : m->own_stream;
+		hipStream_t st = pick_stream(ms[i], nullptr);
 		if (st != synced) { // (executors of a resident run share one stream)
 			HIPCHK(ctx, hipStreamSynchronize(st));
 			synced = st;
 		}
-		if (m->stats_in_host) {
-			memcpy(&stats[i], m->stats_host, sizeof(polr_mpx_stats));
-		}
-		m->pending_sync = false;
-		collect_steal_stats(m);
-		if (m->timing) {
-			drain_events(m);
-		}
-		if (((volatile uint32_t *)m->done_host)[2]) {
-			((volatile uint32_t *)m->done_host)[2] = 0;
-			timed_out = true;
-		}
-		if (timed_out) {
+		timed_out = settle(ms[i], &stats[i]) || timed_out;
+		if (timed_out) { // (and every executor behind the first one that timed out)
 			ms[0]->pool_dirty = true;
-			m->pool_dirty = true;
-			if (m->leader) {
-				m->leader->pool_dirty = true; // (the multiplexer that led the run owns its rings)
-			}
+			mark_rings_dirty(ms[i]);
 		}
 	}
 	if (timed_out) {
-		// whose watchdog fired, and on what (the routers that saw it leave theirs in their pinned words)
 		std::string who;
 		for (uint32_t i = 0; i < n; i++) {
-			volatile uint32_t *w = (volatile uint32_t *)ms[i]->done_host;
-			if (w && w[4]) {
-				char buf[200];
-				snprintf(buf, sizeof(buf), "%s executor %u: slot %u, %u round(s) in flight, %llu of %llu arrival tokens (65536 per unit)",
-				         who.empty() ? ";" : ",", w[5], w[6], w[7], ((unsigned long long)w[11] << 32) | w[10],
-				         ((unsigned long long)w[9] << 32) | w[8]);
-				who += buf;
-				w[4] = 0;
-			}
+			report_watchdog(ms[i], who);
 		}
 		POLR_FAIL(ctx, POLR_E_HIP, "run timed out waiting for its probe waves (results incomplete)%s", who.c_str());
 	}
@@ -1242,7 +1300,7 @@ void polr_mpx_destroy(polr_mpx *m) {
 		hipFree(m->log_inter);
 	}
 	if (m->done_host) {
-		hipHostFree(m->done_host);
+		hipHostFree((void *)m->done_host);
 	}
 	if (m->sync_dev) {
 		hipFree(m->sync_dev);

@@ -10,10 +10,30 @@
 
 #include "../../include/polr_hip.h"
 #include "polr_device.h"
+#include "polr_pool_plan.h" // POLR_SLOTS, POLR_RES_TIMEOUT_TICKS
 #include "polr_routing.h"
 #include "polr_steal.h"
 
-#define POLR_SLOTS 4 // rounds one executor can have in flight in a one-launch run (see ResidentSync)
+// The pinned, mapped host words of a multiplexer: 64 bytes the device writes with plain stores (DevMpx::progress, the
+// pool routers' host_words) and the host reads and clears (polr_mpx::done_host).  Indices into that array.
+enum PolrHostWord {
+	POLR_HW_STEPS = 0,    // routing steps completed (monotonic across runs: the host throttles on differences)
+	POLR_HW_DONE = 1,     // the router has seen the end of the range
+	POLR_HW_GIVEN_UP = 2, // a watchdog fired in a run this multiplexer led or took part in: the run was given up
+	                      // (3: unused)
+	POLR_HW_DIAG_VALID = 4, // words 5..11 describe the wait this executor's router gave up on
+	POLR_HW_DIAG_EXEC = 5,
+	POLR_HW_DIAG_SLOT = 6,
+	POLR_HW_DIAG_IN_FLIGHT = 7,                                 // rounds in flight
+	POLR_HW_DIAG_WANTED_LO = 8, POLR_HW_DIAG_WANTED_HI = 9,     // arrival tokens waited for
+	POLR_HW_DIAG_ARRIVED_LO = 10, POLR_HW_DIAG_ARRIVED_HI = 11, // ... and arrived
+	POLR_HW_CHUNKS_ROUTED = 12, // stealing runs (polr_steal_stats): this executor's counters
+	POLR_HW_CHUNKS_STOLEN = 13,
+	POLR_HW_STEALS = 14,
+	POLR_HW_COUNT = 16
+};
+#define POLR_HOST_WORDS_BYTES 64
+static_assert(POLR_HW_COUNT * sizeof(uint32_t) <= POLR_HOST_WORDS_BYTES, "the host words fit their allocation");
 
 struct DevMpx {
 	polr::MultiplexerCore core;
@@ -32,7 +52,7 @@ struct DevMpx {
 	uint64_t last_path; // path of the round whose counters are still to be absorbed
 	uint32_t wide0_mask; // bit p: stage 0 of join order p takes the wide (256 tuples per step) path
 	uint32_t pad2;
-	// host-visible progress words (pinned, mapped host memory): [0] = routing steps completed, [1] = done
+	// host-visible progress words (pinned, mapped host memory), indexed by PolrHostWord
 	volatile uint32_t *progress;
 	uint32_t steps_done, pad3;
 	// what a fresh MultiplexerState is built from (a resident run can reset itself)
@@ -94,8 +114,8 @@ __device__ __forceinline__ void polr_publish_progress(DevMpx *m) {
 		// plain stores to mapped host memory: they land in order of issue soon enough; a stale read on the
 		// host costs at most one extra (empty) launch, never correctness -- no system-scope fence on the
 		// critical path of every routing step
-		m->progress[1] = m->done;
-		m->progress[0] = m->steps_done;
+		m->progress[POLR_HW_DONE] = m->done;
+		m->progress[POLR_HW_STEPS] = m->steps_done;
 	}
 }
 
@@ -286,8 +306,6 @@ __device__ __forceinline__ void polr_router_route(DevMpx *m, DevRound *round, ui
 
 // ==== one-launch runs: what a router and the probe pool share per executor ==========================
 // (protocol: polr_pool_device.h)
-#define POLR_RES_TIMEOUT_TICKS 400000000ull // 4 s of the 100 MHz wall clock: a wait this long is a lost run
-
 // Round SLOTS per executor: while the pool probes round r the router may already have published the rounds after it
 // whose decisions cannot depend on the intermediates still outstanding (the exploration rounds of an init phase,
 // ALTERNATE): up to POLR_SLOTS dependent-latency rounds overlap.  Each slot has its own counter bank and arrivals.

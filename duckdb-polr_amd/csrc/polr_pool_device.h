@@ -62,10 +62,8 @@
 #define RT_FLUSH
 #endif
 
-#define POLR_POOL_RINGS 64 // unit queues; counters and arrivals are sharded 8 ways (ring & 7)
+// (POLR_POOL_RINGS, POLR_POOL_HI_TUPLES, POLR_POOL_HI_UNIT: polr_pool_plan.h, which sizes the launch from them)
 #define POLR_POOL_SHARDS 8
-#define POLR_POOL_HI_TUPLES 4096u // rounds up to this many tuples are latency-critical (exploration slices)
-#define POLR_POOL_HI_UNIT 64u // smallest unit of a small round (ring capacities are sized for it)
 #ifndef POLR_POOL_LOTTERY_PATIENCE
 #define POLR_POOL_LOTTERY_PATIENCE 64u // idle polls (> 100 us) after which a wave tries for ANY hi ticket, every 16th poll
 #endif
@@ -138,8 +136,8 @@ struct PoolRun {
 	                                        // every ring has waves that serve it
 	uint32_t routers_done;                  // device: routers that have finished
 	uint32_t abort;                         // device: a watchdog fired
-	volatile uint32_t *host_words;          // pinned words of the run's FIRST multiplexer (it owns the rings): [2] = 1 when
-	                                        // the run was given up, whichever router saw it
+	volatile uint32_t *host_words;          // pinned words of the run's FIRST multiplexer (it owns the rings):
+	                                        // POLR_HW_GIVEN_UP = 1 when the run was given up, whichever router saw it
 	unsigned long long timeout_ticks;       // watchdog: longest wait, ticks of the 100 MHz wall clock
 	uint32_t *share_recs;                   // work sharing (generic pipeline): one record of share_stride dwords per probe wave,
 	uint32_t *share_flags;                  // and its "full" flag; nullptr: off
@@ -956,17 +954,17 @@ __device__ __forceinline__ void polr_pool_router(const ResidentExec &x, PoolRun 
 		if (lane == 0) {
 			__hip_atomic_store(&run->abort, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 			if (host_words) {
-				host_words[2] = 1;
+				host_words[POLR_HW_GIVEN_UP] = 1;
 			}
 			if (rt[POOL_RT_DIAG + 6] && host_words) { // (the pinned words of THIS executor's multiplexer)
-				host_words[5] = exec;
-				host_words[6] = rt[POOL_RT_DIAG + 4];
-				host_words[7] = rt[POOL_RT_DIAG + 5];
-				host_words[8] = rt[POOL_RT_DIAG + 0];
-				host_words[9] = rt[POOL_RT_DIAG + 1];
-				host_words[10] = rt[POOL_RT_DIAG + 2];
-				host_words[11] = rt[POOL_RT_DIAG + 3];
-				host_words[4] = 1u;
+				host_words[POLR_HW_DIAG_EXEC] = exec;
+				host_words[POLR_HW_DIAG_SLOT] = rt[POOL_RT_DIAG + 4];
+				host_words[POLR_HW_DIAG_IN_FLIGHT] = rt[POOL_RT_DIAG + 5];
+				host_words[POLR_HW_DIAG_WANTED_LO] = rt[POOL_RT_DIAG + 0];
+				host_words[POLR_HW_DIAG_WANTED_HI] = rt[POOL_RT_DIAG + 1];
+				host_words[POLR_HW_DIAG_ARRIVED_LO] = rt[POOL_RT_DIAG + 2];
+				host_words[POLR_HW_DIAG_ARRIVED_HI] = rt[POOL_RT_DIAG + 3];
+				host_words[POLR_HW_DIAG_VALID] = 1u;
 			}
 		}
 	}
@@ -974,9 +972,9 @@ __device__ __forceinline__ void polr_pool_router(const ResidentExec &x, PoolRun 
 	if (x.steal_words && lane == 0 && host_words) {
 		// this executor's stealing counters leave with the run's statistics (polr_mpx_steal_stats)
 		const unsigned long long *ctr = x.steal_words + rh.n_exec + 4u * (size_t)uni(exec);
-		host_words[12] = (uint32_t)__hip_atomic_load(&ctr[0], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-		host_words[13] = (uint32_t)__hip_atomic_load(&ctr[1], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-		host_words[14] = (uint32_t)__hip_atomic_load(&ctr[2], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+		host_words[POLR_HW_CHUNKS_ROUTED] = (uint32_t)__hip_atomic_load(&ctr[0], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+		host_words[POLR_HW_CHUNKS_STOLEN] = (uint32_t)__hip_atomic_load(&ctr[1], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+		host_words[POLR_HW_STEALS] = (uint32_t)__hip_atomic_load(&ctr[2], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 	}
 	if (x.flags & POLR_RUN_FINISH) {
 		if (lane == 0) {
@@ -994,8 +992,8 @@ __device__ __forceinline__ void polr_pool_router(const ResidentExec &x, PoolRun 
 		}
 		m->progress = host_words;
 		if (host_words) { // what a per-round run would have published: the run is over
-			host_words[1] = m->done;
-			host_words[0] = m->steps_done;
+			host_words[POLR_HW_DONE] = m->done;
+			host_words[POLR_HW_STEPS] = m->steps_done;
 		}
 	}
 	__builtin_amdgcn_wave_barrier();

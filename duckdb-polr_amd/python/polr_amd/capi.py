@@ -279,6 +279,7 @@ def load():
     L.polr_ht_fetch_dictionary.argtypes = [vp, u32, vp, vp, u64, vp, u64, P(u64)]
     L.polr_out_fused_result.argtypes = [vp, vp, vp, C.c_uint64, vp]
     L.polr_mpx_run_resident.argtypes = [vp, vp, vp, vp, u32, vp, u32]
+    L.polr_mpx_run_resident_ranges.argtypes = [vp, vp, vp, vp, u32, u32, vp, u32]
     L.polr_mpx_run_resident_morsels.argtypes = [vp, vp, C.c_uint64, C.c_uint64, u32, u32, vp, u32]
     L.polr_mpx_run_resident_stealing.argtypes = [vp, vp, vp, vp, u32, u32, vp, u32]
     L.polr_mpx_steal_stats.argtypes = [vp, vp]
@@ -866,12 +867,7 @@ class DeviceMultiplexer:
     def finish(self, stream=None):
         st = MpxStats()
         self.ctx.check(self.ctx.L.polr_mpx_finish(self.h, stream, C.byref(st)))
-        P = self.pipe.n_paths
-        return {"num_tuples_processed": st.num_tuples_processed, "num_intermediates": st.num_intermediates,
-                "num_rounds": st.num_rounds,
-                "input_tuple_count_per_path": [st.input_tuple_count_per_path[i] for i in range(P)],
-                "path_resistances": [st.path_resistances[i] for i in range(P)],
-                "stage_out": [[st.stage_out[i][j] for j in range(self.pipe.k)] for i in range(P)]}
+        return _stats_dict(st, self.pipe.n_paths, self.pipe.k)
 
     def steal_stats(self):
         """polr_mpx_steal_stats: this executor's counters of its last run, after finish / finish_many (zeros unless that
@@ -917,7 +913,7 @@ class DeviceMultiplexer:
 def run_many(mpxs, ranges, out=None):
     """polr_mpx_run_many: mpxs[i] routes chunks ranges[i] = (begin, end) concurrently (own streams)"""
     n = len(mpxs)
-    hs = (C.c_void_p * n)(*[m.h for m in mpxs])
+    hs = _handles(mpxs)
     b = np.ascontiguousarray([r[0] for r in ranges], dtype=np.uint64)
     e = np.ascontiguousarray([r[1] for r in ranges], dtype=np.uint64)
     ctx = mpxs[0].ctx
@@ -935,16 +931,26 @@ def _stats_dict(st, P, k):
 RUN_RESET, RUN_FINISH = 1, 2
 
 
+def _handles(mpxs):
+    """the handle array the polr_mpx_*_many / _run_resident* entry points take"""
+    return (C.c_void_p * len(mpxs))(*[m.h for m in mpxs])
+
+
+def _run_flags(reset, finish, share):
+    """POLR_RUN_RESET | POLR_RUN_FINISH | POLR_RUN_SHARE(share)"""
+    return (RUN_RESET if reset else 0) | (RUN_FINISH if finish else 0) | ((share & 0xFF) << 8 if share > 1 else 0)
+
+
 def run_resident(mpxs, ranges, out=None, reset=False, finish=False, share=1, stream=None):
     """polr_mpx_run_resident: the same run as ONE launch (device-resident routing loop);
     reset / finish fold polr_mpx_reset / the closing FinalizePathRun into the same launch"""
     ctx = mpxs[0].ctx
     n = len(mpxs)
-    hs = (C.c_void_p * n)(*[m.h for m in mpxs])
+    hs = _handles(mpxs)
     b = np.ascontiguousarray([r[0] for r in ranges], dtype=np.uint64)
     e = np.ascontiguousarray([r[1] for r in ranges], dtype=np.uint64)
     ctx.check(ctx.L.polr_mpx_run_resident(hs, stream, b.ctypes.data, e.ctypes.data, n, out.h if out else None,
-                                          (RUN_RESET if reset else 0) | (RUN_FINISH if finish else 0) | ((share & 0xFF) << 8 if share > 1 else 0)))
+                                          _run_flags(reset, finish, share)))
 
 
 def run_resident_ranges(mpxs, range_lists, out=None, reset=False, finish=False, share=1):
@@ -952,26 +958,22 @@ def run_resident_ranges(mpxs, range_lists, out=None, reset=False, finish=False, 
     ctx = mpxs[0].ctx
     n = len(mpxs)
     r = len(range_lists[0])
-    hs = (C.c_void_p * n)(*[m.h for m in mpxs])
+    hs = _handles(mpxs)
     flat = [x for lst in range_lists for x in lst]
     b = (C.c_uint64 * (n * r))(*[x[0] for x in flat])
     e = (C.c_uint64 * (n * r))(*[x[1] for x in flat])
-    ctx.L.polr_mpx_run_resident_ranges.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32,
-                                                  C.c_void_p, C.c_uint32]
     ctx.check(ctx.L.polr_mpx_run_resident_ranges(hs, None, b, e, r, n, out.h if out else None,
-                                                 (RUN_RESET if reset else 0) | (RUN_FINISH if finish else 0) |
-                                                 ((share & 0xFF) << 8 if share > 1 else 0)))
+                                                 _run_flags(reset, finish, share)))
 
 
 def run_resident_morsels(mpxs, chunk_begin, chunk_end, morsel_chunks=120, out=None, reset=False, finish=False, share=1):
     """polr_mpx_run_resident_morsels: the executors share [chunk_begin, chunk_end) and pull morsels from one cursor"""
     ctx = mpxs[0].ctx
     n = len(mpxs)
-    hs = (C.c_void_p * n)(*[m.h for m in mpxs])
+    hs = _handles(mpxs)
     ctx.check(ctx.L.polr_mpx_run_resident_morsels(hs, None, chunk_begin, chunk_end, morsel_chunks, n,
                                                   out.h if out else None,
-                                                  (RUN_RESET if reset else 0) | (RUN_FINISH if finish else 0) |
-                                                  ((share & 0xFF) << 8 if share > 1 else 0)))
+                                                  _run_flags(reset, finish, share)))
 
 
 def run_resident_stealing(mpxs, ranges, grant_chunks, out=None, reset=False, finish=False, share=1):
@@ -979,29 +981,28 @@ def run_resident_stealing(mpxs, ranges, grant_chunks, out=None, reset=False, fin
     and takes them grant_chunks at a time; an executor that has run dry steals the far half of whoever has most left"""
     ctx = mpxs[0].ctx
     n = len(mpxs)
-    hs = (C.c_void_p * n)(*[m.h for m in mpxs])
+    hs = _handles(mpxs)
     b = np.ascontiguousarray([r[0] for r in ranges], dtype=np.uint64)
     e = np.ascontiguousarray([r[1] for r in ranges], dtype=np.uint64)
     ctx.check(ctx.L.polr_mpx_run_resident_stealing(hs, None, b.ctypes.data, e.ctypes.data, grant_chunks, n,
                                                    out.h if out else None,
-                                                   (RUN_RESET if reset else 0) | (RUN_FINISH if finish else 0) |
-                                                   ((share & 0xFF) << 8 if share > 1 else 0)))
+                                                   _run_flags(reset, finish, share)))
 
 
 def run_backpressure(mpxs, chunk_begin, chunk_end, morsel_chunks=120, out=None, reset=True, finish=True):
     """polr_mpx_run_backpressure: one executor per join order racing for morsels of the source"""
     ctx = mpxs[0].ctx
     n = len(mpxs)
-    hs = (C.c_void_p * n)(*[m.h for m in mpxs])
+    hs = _handles(mpxs)
     ctx.check(ctx.L.polr_mpx_run_backpressure(hs, None, chunk_begin, chunk_end, morsel_chunks, out.h if out else None,
-                                              (RUN_RESET if reset else 0) | (RUN_FINISH if finish else 0)))
+                                              _run_flags(reset, finish, 1)))
 
 
 def finish_many_raw(mpxs):
     """polr_mpx_finish_many: settles the run(s) of these multiplexers and returns their statistics as the C structs
     (stats_dicts() turns them into dictionaries -- host-side bookkeeping a measurement keeps outside its clock)"""
     n = len(mpxs)
-    hs = (C.c_void_p * n)(*[m.h for m in mpxs])
+    hs = _handles(mpxs)
     stats = (MpxStats * n)()
     ctx = mpxs[0].ctx
     ctx.check(ctx.L.polr_mpx_finish_many(hs, n, stats))
