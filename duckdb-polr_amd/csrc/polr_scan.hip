@@ -55,7 +55,8 @@ struct DevLip {
 	uint64_t mask;
 	int64_t min_value;
 	uint64_t range;
-	uint32_t key_width, key_signed, kind, pad;
+	uint32_t key_width, key_signed, kind;
+	uint32_t sentinel_count; // S16: build rows whose key is the slots' empty marker (kept beside the table)
 };
 struct DevLipSet {
 	DevLip f[POLR_KMAX];
@@ -90,7 +91,7 @@ __device__ __forceinline__ bool lip_contains(const DevLip &f, uint64_t row) {
 	}
 	// KIND_S16: {key64, start, count}
 	if (key == S16_EMPTY_KEY) {
-		return true; // (the sentinel key has a side entry: let the join decide)
+		return f.sentinel_count != 0; // (the all-ones key is the empty marker: its rows are counted beside the table)
 	}
 	const uint4 *tab = (const uint4 *)f.table;
 	uint64_t h = polr_murmurhash64(key) & f.mask;
@@ -388,6 +389,7 @@ int polr_pipeline_scan_filter_lip(polr_pipeline *p, void *stream, const polr_sca
 			f.mask = dj.mask;
 			f.min_value = dj.min_value;
 			f.range = dj.range;
+			f.sentinel_count = dj.sentinel_count;
 		}
 	}
 	HIPCHK(ctx, hipSetDevice(ctx->device));

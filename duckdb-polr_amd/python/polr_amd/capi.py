@@ -579,6 +579,7 @@ class Pipeline:
         ctx.check(ctx.L.polr_pipeline_create(ctx.h, _col_array(pc), len(pc), n_probe_rows, jd, self.k,
                                              paths.ctypes.data, self.n_paths, C.byref(h)))
         self.h = h
+        self.scan = (0, 0)  # (n_selected, n_chunks) of the last scan_filter: what fetch_scan sizes its arrays by
 
     def set_probe_heap(self, probe_col, heap):
         """polr_pipeline_set_probe_heap: the string heap the cells of probe column `probe_col` point into"""

@@ -283,9 +283,12 @@ int polr_pipeline_scan_filter(polr_pipeline *p, void *stream, const polr_scan_fi
  * PipelineExecutor::FetchFromSource src/parallel/pipeline_executor.cpp:396-465 probing
  * PhysicalHashJoin::ProbeBloomFilter physical_hash_join.cpp:579-635 for every join with build_bloom_filter
  * (eligibility physical_join.cpp:57-107: one condition, key traced back to a source column).  The reference's filter is
- * a bloom filter sized from a planner estimate; here it is the join's own index (no false positives): the survivors are
- * a subset of the reference's, the pipeline's output rows are the same.  POLR_E_INVALID for a join that is not keyed
- * by one source column. */
+ * a bloom filter sized from a planner estimate; here it is the join's own index (no false positives): a source row
+ * survives exactly when its key is not NULL and equals a non-NULL build key of every named join -- the 8-byte key of
+ * all ones included, which a repeated-key table keeps beside its slots.  The survivors are a subset of the
+ * reference's, the pipeline's output rows are the same.  POLR_E_INVALID for a join that is not keyed by one source
+ * column or a mask bit beyond the pipeline's joins, POLR_E_UNSUPPORTED for a join in packed form (its key compared by
+ * value or NULL = NULL); a refused call leaves the scan result before it in place. */
 int polr_pipeline_scan_filter_lip(polr_pipeline *p, void *stream, const polr_scan_filter *filters, uint32_t n_filters,
                                   uint32_t lip_joins, uint32_t vector_size, uint64_t *n_selected, uint64_t *n_chunks);
 /* read the scan result back (tests): sel[n_selected], chunk_offsets[n_chunks + 1]; either may be NULL */

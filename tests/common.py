@@ -77,3 +77,15 @@ def oracle_output_digest(wl, out_rows):
     for src_join, arr, valid in output_columns(wl):
         cols.append(orc.materialize_column(out_rows, k, src_join, arr, valid))
     return rows_digest_from_columns(cols)
+
+
+def chunk_bounds(sel, n, V):
+    """ascending surviving rows of an n-row table -> (sel, boundaries of the chunks: one per V-row vector with a survivor)"""
+    bounds = np.searchsorted(sel, np.arange(0, n + V, V, dtype=np.int64)).astype(np.uint64)
+    if len(bounds) < 2:
+        return sel, np.zeros(1, dtype=np.uint64)
+    nonempty = np.concatenate([[True], bounds[1:] != bounds[:-1]])
+    offs = bounds[nonempty]
+    if len(offs) == 0 or offs[-1] != len(sel):
+        offs = np.concatenate([offs, [len(sel)]]).astype(np.uint64)
+    return sel, offs

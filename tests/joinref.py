@@ -1,6 +1,7 @@
 """The plain numpy reference of an equi-join that the GPU matrices check the device against (tests/test_gpu_engine_matrix.py,
-tests/test_gpu_sink_matrix.py): the build keys sorted, np.searchsorted for each probe row's run of matching build rows, NULL
-never matching on either side; the row set expanded join by join."""
+tests/test_gpu_sink_matrix.py, tests/test_gpu_scan_lip.py): the build keys sorted, np.searchsorted for each probe row's
+run of matching build rows, NULL never matching on either side; the row set expanded join by join.  And the key cases
+(8 key types x perfect / unique / repeated tables) the engine matrix and the LIP scan tests share."""
 import numpy as np
 
 from common import orc
@@ -108,6 +109,74 @@ def device_rows(ids, joins):
         if j.perfect is not None:
             rows[:, 1 + x] = j.id_to_row[rows[:, 1 + x]]
     return rows
+
+
+# ---- key types x table kinds (tests/test_gpu_engine_matrix.py::test_key_types, tests/test_gpu_scan_lip.py) ---------------------
+DTYPES = [np.int8, np.uint8, np.int16, np.uint16, np.int32, np.uint32, np.int64, np.uint64]
+MAX_WAVE_CHUNKS = 8192  # one partially filled chunk per emitting wave (polr_out_create)
+
+
+def chunks_for(n_rows, cap):
+    return (n_rows + cap - 1) // cap + MAX_WAVE_CHUNKS
+
+
+def _perfect_ranges(dt):
+    info = np.iinfo(dt)
+    if info.bits <= 16:
+        return {"perfect": (int(info.min), int(info.max))}  # the whole domain (type min, max, 0 and -1 inside)
+    R = 3000
+    if info.min < 0:
+        return {"perfect_lo": (int(info.min), int(info.min) + R), "perfect_mid": (-R // 2, R // 2),
+                "perfect_hi": (int(info.max) - R, int(info.max))}
+    hi = (int(info.max) - R, int(info.max))
+    if info.bits == 64:  # above 2^63: min and max passed as their int64 bit patterns
+        hi = (hi[0] - (1 << 64), -1)
+    return {"perfect_lo": (0, R), "perfect_hi": hi}
+
+
+KEY_CASES = [(dt, kind) for dt in DTYPES for kind in list(_perfect_ranges(dt)) + ["unique", "repeated"]]
+
+
+def _specials(dt):
+    info = np.iinfo(dt)
+    return [int(info.min), int(info.max), 0, -1 if info.min < 0 else int(info.max), 1]
+
+
+def _key_case(dt, kind, seed, n_probe=20_000):
+    rng = np.random.default_rng(seed)
+    info = np.iinfo(dt)
+    lo_t, hi_t = int(info.min), int(info.max)
+
+    def arr(vals):
+        return np.array([int(v) for v in vals], dtype=np.uint64 if dt == np.uint64 else np.int64).astype(dt)
+
+    def rand(lo, hi, n):  # python ints in [lo, hi], any width
+        return [lo + x % (hi - lo + 1) for x in rng.integers(0, 2**64, n, dtype=np.uint64).tolist()]
+
+    if kind.startswith("perfect"):
+        lo, hi = _perfect_ranges(dt)[kind]
+        ulo, uhi = (lo & U64, hi & U64) if dt == np.uint64 else (lo, hi)
+        inner = sorted(set(rand(ulo, uhi, min(2000, uhi - ulo + 1))))
+        must = [ulo, ulo + 1, uhi - 1, uhi] + [s for s in (0, -1) if ulo <= s <= uhi]
+        bk = sorted(set(inner + must))
+        bk = [v for v in bk if v not in (ulo + 2, uhi - 2)]  # holes next to both ends
+        edges = [ulo - 1, ulo, ulo + 1, ulo + 2, uhi - 2, uhi - 1, uhi, uhi + 1]
+        near = rand(max(lo_t, ulo - 40), min(hi_t, uhi + 40), n_probe // 2)
+        perfect = (lo, hi)
+    else:
+        n_b = 150 if info.bits == 8 else 3000
+        vals = list(dict.fromkeys(_specials(dt) + rand(lo_t, hi_t, 4 * n_b)))[:n_b]
+        bk = vals if kind == "unique" else [v for i, v in enumerate(vals) for _ in range(1 + i % 3)]
+        edges = []
+        near = [bk[i] for i in rng.integers(0, len(bk), n_probe // 2)]
+        perfect = None
+    pk = _specials(dt) + [e for e in edges if lo_t <= e <= hi_t] + near
+    pk += rand(lo_t, hi_t, n_probe - len(pk))
+    bk, pk = rng.permutation(arr(bk)), rng.permutation(arr(pk))
+    bvalid = (rng.random(len(bk)) > 0.03).astype(np.uint8)
+    pvalid = (rng.random(len(pk)) > 0.03).astype(np.uint8)
+    pay = (np.arange(len(bk)) % 97).astype(np.int32)
+    return Join(bk, 0, perfect, bvalid, [pay]), [pk], [pvalid]
 
 
 # ---- the inputs of tests/golden/hash_groupby.json (tests/golden/make_golden_hashagg.py) -----------------------------------------

@@ -20,25 +20,18 @@ Every pipeline asserts `launch_info(materialize)["flat"]`, so each case records 
                    test_flat_k6_against_k7 (k = 7),      (emitting), test_wrap_around_        1/2/8-byte unique],
                    test_flat_mixed_perfect_and_s8 (emit) clusters[s8] (emitting),             test_wrap_around_clusters[s16-*],
                                                          test_output_chunks[generic]          test_key_types_under_a_selection
-The LIP scan's own probe loop: test_wrap_around_clusters (scan_filter with lip_joins=1)."""
+The LIP scan's own probe loop: test_wrap_around_clusters (scan_filter with lip_joins=1); every key type and table kind of
+test_key_types, the all-ones key and several joins in one scan: tests/test_gpu_scan_lip.py."""
 import ctypes as C
 
 import numpy as np
 import pytest
 
 from common import orc
-from joinref import Join, Ref, device_rows, sort_rows
+from joinref import KEY_CASES, Join, Ref, _key_case, chunks_for, device_rows, sort_rows
 from polr_amd import capi
 
 pytestmark = pytest.mark.gpu
-
-DTYPES = [np.int8, np.uint8, np.int16, np.uint16, np.int32, np.uint32, np.int64, np.uint64]
-U64 = 0xFFFFFFFFFFFFFFFF
-MAX_WAVE_CHUNKS = 8192  # one partially filled chunk per emitting wave (polr_out_create)
-
-
-def chunks_for(n_rows, cap):
-    return (n_rows + cap - 1) // cap + MAX_WAVE_CHUNKS
 
 
 def oracle_check(pcols, pvalid, joins, paths, ref, want_rows):
@@ -105,65 +98,6 @@ def check_engines(ctx, pcols, pvalid, joins, paths, flat, sel=None, emit_flat=No
 
 
 # ---- a. key types x table kinds x engines --------------------------------------------------------------------------------
-def _perfect_ranges(dt):
-    info = np.iinfo(dt)
-    if info.bits <= 16:
-        return {"perfect": (int(info.min), int(info.max))}  # the whole domain (type min, max, 0 and -1 inside)
-    R = 3000
-    if info.min < 0:
-        return {"perfect_lo": (int(info.min), int(info.min) + R), "perfect_mid": (-R // 2, R // 2),
-                "perfect_hi": (int(info.max) - R, int(info.max))}
-    hi = (int(info.max) - R, int(info.max))
-    if info.bits == 64:  # above 2^63: min and max passed as their int64 bit patterns
-        hi = (hi[0] - (1 << 64), -1)
-    return {"perfect_lo": (0, R), "perfect_hi": hi}
-
-
-KEY_CASES = [(dt, kind) for dt in DTYPES for kind in list(_perfect_ranges(dt)) + ["unique", "repeated"]]
-
-
-def _specials(dt):
-    info = np.iinfo(dt)
-    return [int(info.min), int(info.max), 0, -1 if info.min < 0 else int(info.max), 1]
-
-
-def _key_case(dt, kind, seed, n_probe=20_000):
-    rng = np.random.default_rng(seed)
-    info = np.iinfo(dt)
-    lo_t, hi_t = int(info.min), int(info.max)
-
-    def arr(vals):
-        return np.array([int(v) for v in vals], dtype=np.uint64 if dt == np.uint64 else np.int64).astype(dt)
-
-    def rand(lo, hi, n):  # python ints in [lo, hi], any width
-        return [lo + x % (hi - lo + 1) for x in rng.integers(0, 2**64, n, dtype=np.uint64).tolist()]
-
-    if kind.startswith("perfect"):
-        lo, hi = _perfect_ranges(dt)[kind]
-        ulo, uhi = (lo & U64, hi & U64) if dt == np.uint64 else (lo, hi)
-        inner = sorted(set(rand(ulo, uhi, min(2000, uhi - ulo + 1))))
-        must = [ulo, ulo + 1, uhi - 1, uhi] + [s for s in (0, -1) if ulo <= s <= uhi]
-        bk = sorted(set(inner + must))
-        bk = [v for v in bk if v not in (ulo + 2, uhi - 2)]  # holes next to both ends
-        edges = [ulo - 1, ulo, ulo + 1, ulo + 2, uhi - 2, uhi - 1, uhi, uhi + 1]
-        near = rand(max(lo_t, ulo - 40), min(hi_t, uhi + 40), n_probe // 2)
-        perfect = (lo, hi)
-    else:
-        n_b = 150 if info.bits == 8 else 3000
-        vals = list(dict.fromkeys(_specials(dt) + rand(lo_t, hi_t, 4 * n_b)))[:n_b]
-        bk = vals if kind == "unique" else [v for i, v in enumerate(vals) for _ in range(1 + i % 3)]
-        edges = []
-        near = [bk[i] for i in rng.integers(0, len(bk), n_probe // 2)]
-        perfect = None
-    pk = _specials(dt) + [e for e in edges if lo_t <= e <= hi_t] + near
-    pk += rand(lo_t, hi_t, n_probe - len(pk))
-    bk, pk = rng.permutation(arr(bk)), rng.permutation(arr(pk))
-    bvalid = (rng.random(len(bk)) > 0.03).astype(np.uint8)
-    pvalid = (rng.random(len(pk)) > 0.03).astype(np.uint8)
-    pay = (np.arange(len(bk)) % 97).astype(np.int32)
-    return Join(bk, 0, perfect, bvalid, [pay]), [pk], [pvalid]
-
-
 def _engines_of(dt, kind):
     """(flat for counting, flat for emitting, the hash table kind) the library must choose"""
     four = np.dtype(dt).itemsize == 4
