@@ -1634,6 +1634,9 @@ void polr_pipeline_destroy(polr_pipeline *p) {
 		hipFree(p->scan_sums);
 		hipFree(p->scan_totals);
 	}
+	if (p->scan_str_tails) {
+		hipFree(p->scan_str_tails);
+	}
 	if (p->dev_mat) {
 		hipFree(p->dev_mat);
 	}

@@ -113,6 +113,7 @@ struct polr_pipeline {
 	uint32_t *scan_sel = nullptr;
 	unsigned long long *scan_packed = nullptr, *scan_sums = nullptr, *scan_totals = nullptr;
 	uint64_t scan_cap_rows = 0, scan_cap_vec = 0;
+	uint8_t *scan_str_tails = nullptr; // polr_pipeline_scan_filter_str: the VARCHAR constants' bytes beyond 12, re-uploaded per call
 	bool scan_valid = false;      // a scan result is installed (selection + chunk boundaries)
 	uint64_t scan_generation = 0; // bumped by every scan: multiplexers must re-attach (polr_mpx_use_scan_chunks)
 	std::vector<polr_ht *> hts;

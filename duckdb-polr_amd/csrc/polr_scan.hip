@@ -15,6 +15,13 @@
 // and the result -- selection + chunk boundaries -- stays on the device, installed in the pipeline; a
 // multiplexer takes the boundaries with polr_mpx_use_scan_chunks.  Algorithmic bytes: 2 x (sum of filter column
 // widths [+ validity bytes]) per table row + 4 per surviving row.
+//
+// VARCHAR constant comparisons (polr_pipeline_scan_filter_str; the reference pushes =, <, >, <=, >= against a VARCHAR
+// constant and the prefix range of LIKE 'abc%' into the scan: filter_combiner.cpp:391-398, :426-485, evaluated on
+// string_t by ColumnSegment::FilterSelection column_segment.cpp:435-442): the count and write kernels exist a second
+// time with a DevStrSet beside the integer filters, so a scan without string filters runs the code it always ran.  A row
+// costs one 16-byte cell load per distinct VARCHAR filter column (2 x 16 over the two passes); the comparison is
+// polr_strcmp.h.  The heap is read only for a cell longer than 12 bytes whose first four bytes tie with a constant's.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <string.h>
@@ -23,6 +30,7 @@
 #include <vector>
 
 #include "polr_internal.h"
+#include "polr_strcmp.h"
 
 struct DevFilter {
 	const uint8_t *data;
@@ -38,6 +46,28 @@ struct DevFilter {
 struct DevFilterSet {
 	DevFilter f[POLR_MAX_FILTERS];
 	uint32_t n;
+	uint32_t pad;
+};
+
+// The VARCHAR comparisons of a scan, grouped by column on the host: column c is compared against cmp[first .. first + n),
+// so the cell of a row is loaded once however many constants it meets (a LIKE range is two).  The constants travel by
+// value -- length and first 12 bytes (polr_str_const) --; the bytes beyond 12 of the long ones lie in the pipeline's
+// scan_str_tails buffer at tail_off.
+struct DevStrCmp {
+	polr_str_const c;
+	uint32_t op; // POLR_CMP_EQ .. POLR_CMP_GE
+	uint32_t tail_off;
+};
+struct DevStrCol {
+	const uint8_t *data;
+	const uint8_t *valid;
+	uint32_t first, n;
+};
+struct DevStrSet {
+	DevStrCol col[POLR_MAX_FILTERS];
+	DevStrCmp cmp[POLR_MAX_FILTERS];
+	const uint8_t *tails;
+	uint32_t n_cols;
 	uint32_t pad;
 };
 
@@ -113,8 +143,34 @@ __device__ __forceinline__ bool lip_contains(const DevLip &f, uint64_t row) {
 
 __device__ __forceinline__ bool row_passes_filters(const DevFilterSet &fs, uint64_t row);
 
-__device__ __forceinline__ bool row_passes(const DevFilterSet &fs, const DevLipSet &lip, uint64_t row) {
+// every comparison of every VARCHAR filter column holds for the row.  The validity byte comes first: the cell of a NULL
+// row is never loaded, let alone its pointer followed (the reference leaves such cells as they were).
+__device__ __forceinline__ bool row_passes_str(const DevStrSet &ss, uint64_t row) {
+	bool ok = true;
+	for (uint32_t c = 0; c < ss.n_cols; c++) {
+		const DevStrCol &col = ss.col[c];
+		if (col.valid && !as_global(col.valid)[row]) {
+			ok = false; // NULL passes no comparison, <> included
+		}
+		if (ok) {
+			const uint4 cell = load_global_x4(as_global((const uint32_t *)col.data) + row * 4);
+			for (uint32_t i = col.first; i < col.first + col.n; i++) {
+				const DevStrCmp &f = ss.cmp[i];
+				ok = ok && polr_str_cmp_holds(polr_str_cmp3(cell.x, cell.y, cell.z, cell.w, f.c, ss.tails + f.tail_off), f.op);
+			}
+		}
+	}
+	return ok;
+}
+
+// STR: the kernel has VARCHAR comparisons (ss != nullptr); they are evaluated for the rows the integer filters keep,
+// LIP for the rows both keep
+template <bool STR>
+__device__ __forceinline__ bool row_passes(const DevFilterSet &fs, const DevStrSet *ss, const DevLipSet &lip, uint64_t row) {
 	bool ok = row_passes_filters(fs, row);
+	if constexpr (STR) {
+		ok = ok && row_passes_str(*ss, row);
+	}
 	for (uint32_t i = 0; i < lip.n; i++) {
 		ok = ok && lip_contains(lip.f[i], row);
 	}
@@ -158,25 +214,40 @@ __device__ __forceinline__ bool row_passes_filters(const DevFilterSet &fs, uint6
 	return ok;
 }
 
-// one wave per vector (grid-stride); counts[v] = survivors of vector v, packed with its non-empty flag
-__global__ __launch_bounds__(256) void polr_tscan_count_kernel(DevFilterSet fs, DevLipSet lip, uint64_t n_rows, uint32_t V,
-                                                              uint64_t n_vec, unsigned long long *__restrict__ packed) {
-	const uint32_t lane = threadIdx.x & 63;
-	const uint64_t wave = ((uint64_t)blockIdx.x * blockDim.x + threadIdx.x) >> 6;
-	const uint64_t n_waves = ((uint64_t)gridDim.x * blockDim.x) >> 6;
+// one wave per vector (grid-stride); counts[v] = survivors of vector v, packed with its non-empty flag.  (The kernels
+// compute the wave ids: blockDim is read cheapest in the kernel function itself.)
+template <bool STR>
+__device__ __forceinline__ void tscan_count(uint32_t lane, uint64_t wave, uint64_t n_waves, const DevFilterSet &fs, const DevStrSet *ss, const DevLipSet &lip, uint64_t n_rows,
+                                            uint32_t V, uint64_t n_vec, unsigned long long *__restrict__ packed) {
 	for (uint64_t v = wave; v < n_vec; v += n_waves) {
 		const uint64_t begin = v * V;
 		const uint64_t end = begin + V < n_rows ? begin + V : n_rows;
 		uint32_t cnt = 0;
 		for (uint64_t r0 = begin; r0 < end; r0 += 64) {
 			const uint64_t row = r0 + lane;
-			const bool pass = row < end && row_passes(fs, lip, row);
+			const bool pass = row < end && row_passes<STR>(fs, ss, lip, row);
 			cnt += (uint32_t)__popcll(__ballot(pass));
 		}
 		if (lane == 0) {
 			packed[v] = (unsigned long long)cnt | (cnt ? (1ull << PACK_SHIFT) : 0ull);
 		}
 	}
+}
+__global__ __launch_bounds__(256) void polr_tscan_count_kernel(DevFilterSet fs, DevLipSet lip, uint64_t n_rows, uint32_t V,
+                                                              uint64_t n_vec, unsigned long long *__restrict__ packed) {
+	const uint32_t lane = threadIdx.x & 63;
+	const uint64_t wave = ((uint64_t)blockIdx.x * blockDim.x + threadIdx.x) >> 6;
+	const uint64_t n_waves = ((uint64_t)gridDim.x * blockDim.x) >> 6;
+	tscan_count<false>(lane, wave, n_waves, fs, nullptr, lip, n_rows, V, n_vec, packed);
+}
+// ... with VARCHAR comparisons
+__global__ __launch_bounds__(256) void polr_tscan_count_str_kernel(DevFilterSet fs, DevStrSet ss, DevLipSet lip, uint64_t n_rows,
+                                                                  uint32_t V, uint64_t n_vec,
+                                                                  unsigned long long *__restrict__ packed) {
+	const uint32_t lane = threadIdx.x & 63;
+	const uint64_t wave = ((uint64_t)blockIdx.x * blockDim.x + threadIdx.x) >> 6;
+	const uint64_t n_waves = ((uint64_t)gridDim.x * blockDim.x) >> 6;
+	tscan_count<true>(lane, wave, n_waves, fs, &ss, lip, n_rows, V, n_vec, packed);
 }
 
 // block sums of 1024 packed entries each
@@ -272,15 +343,11 @@ __global__ __launch_bounds__(1024) void polr_tscan_apply_kernel(unsigned long lo
 }
 
 // one wave per vector: ascending row ids of the survivors, chunk boundary of every non-empty vector
-__global__ __launch_bounds__(256) void polr_tscan_write_kernel(DevFilterSet fs, DevLipSet lip, uint64_t n_rows, uint32_t V,
-                                                              uint64_t n_vec,
-                                                              const unsigned long long *__restrict__ prefix,
-                                                              uint32_t *__restrict__ sel,
-                                                              uint64_t *__restrict__ chunk_offsets,
-                                                              const unsigned long long *__restrict__ totals) {
-	const uint32_t lane = threadIdx.x & 63;
-	const uint64_t wave = ((uint64_t)blockIdx.x * blockDim.x + threadIdx.x) >> 6;
-	const uint64_t n_waves = ((uint64_t)gridDim.x * blockDim.x) >> 6;
+template <bool STR>
+__device__ __forceinline__ void tscan_write(uint32_t lane, uint64_t wave, uint64_t n_waves, const DevFilterSet &fs, const DevStrSet *ss, const DevLipSet &lip, uint64_t n_rows,
+                                            uint32_t V, uint64_t n_vec, const unsigned long long *__restrict__ prefix,
+                                            uint32_t *__restrict__ sel, uint64_t *__restrict__ chunk_offsets,
+                                            const unsigned long long *__restrict__ totals) {
 	if (wave == 0 && lane == 0) {
 		chunk_offsets[totals[1]] = totals[0]; // the end of the last chunk
 	}
@@ -298,7 +365,7 @@ __global__ __launch_bounds__(256) void polr_tscan_write_kernel(DevFilterSet fs, 
 		const uint64_t end = begin + V < n_rows ? begin + V : n_rows;
 		for (uint64_t r0 = begin; r0 < end; r0 += 64) {
 			const uint64_t row = r0 + lane;
-			const bool pass = row < end && row_passes(fs, lip, row);
+			const bool pass = row < end && row_passes<STR>(fs, ss, lip, row);
 			const uint64_t m = __ballot(pass);
 			if (pass) {
 				sel[out + lane_rank(m)] = (uint32_t)row;
@@ -307,6 +374,50 @@ __global__ __launch_bounds__(256) void polr_tscan_write_kernel(DevFilterSet fs, 
 		}
 	}
 }
+__global__ __launch_bounds__(256) void polr_tscan_write_kernel(DevFilterSet fs, DevLipSet lip, uint64_t n_rows, uint32_t V,
+                                                              uint64_t n_vec,
+                                                              const unsigned long long *__restrict__ prefix,
+                                                              uint32_t *__restrict__ sel,
+                                                              uint64_t *__restrict__ chunk_offsets,
+                                                              const unsigned long long *__restrict__ totals) {
+	const uint32_t lane = threadIdx.x & 63;
+	const uint64_t wave = ((uint64_t)blockIdx.x * blockDim.x + threadIdx.x) >> 6;
+	const uint64_t n_waves = ((uint64_t)gridDim.x * blockDim.x) >> 6;
+	tscan_write<false>(lane, wave, n_waves, fs, nullptr, lip, n_rows, V, n_vec, prefix, sel, chunk_offsets, totals);
+}
+__global__ __launch_bounds__(256) void polr_tscan_write_str_kernel(DevFilterSet fs, DevStrSet ss, DevLipSet lip, uint64_t n_rows,
+                                                                  uint32_t V, uint64_t n_vec,
+                                                                  const unsigned long long *__restrict__ prefix,
+                                                                  uint32_t *__restrict__ sel,
+                                                                  uint64_t *__restrict__ chunk_offsets,
+                                                                  const unsigned long long *__restrict__ totals) {
+	const uint32_t lane = threadIdx.x & 63;
+	const uint64_t wave = ((uint64_t)blockIdx.x * blockDim.x + threadIdx.x) >> 6;
+	const uint64_t n_waves = ((uint64_t)gridDim.x * blockDim.x) >> 6;
+	tscan_write<true>(lane, wave, n_waves, fs, &ss, lip, n_rows, V, n_vec, prefix, sel, chunk_offsets, totals);
+}
+
+// the guard of a VARCHAR filter column whose cells were never rebased onto a device heap: its non-NULL cells longer than 12
+// bytes -- their pointers are the host's.  Reads the validity byte and the length word of a cell, nothing else.
+__global__ __launch_bounds__(256) void polr_tscan_count_long_kernel(const uint8_t *__restrict__ cells,
+                                                                   const uint8_t *__restrict__ valid, uint64_t n_rows,
+                                                                   unsigned long long *__restrict__ n_long) {
+	unsigned long long mine = 0;
+	for (uint64_t row = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; row < n_rows; row += (uint64_t)gridDim.x * blockDim.x) {
+		if (valid && !valid[row]) {
+			continue;
+		}
+		mine += *(const uint32_t *)(cells + row * 16u) > 12u ? 1u : 0u;
+	}
+	mine = wave_sum64(mine);
+	if ((threadIdx.x & 63u) == 0 && mine) {
+		atomicAdd(n_long, mine);
+	}
+}
+
+static int scan_filter_run(polr_pipeline *p, void *stream, const polr_scan_filter *filters, const polr_scan_filter_str *sfilters,
+                           uint32_t n_filters, uint32_t lip_joins, uint32_t vector_size, uint64_t *n_selected,
+                           uint64_t *n_chunks);
 
 extern "C" {
 
@@ -321,6 +432,25 @@ int polr_pipeline_scan_filter_lip(polr_pipeline *p, void *stream, const polr_sca
 	if (!p || (!filters && n_filters)) {
 		return POLR_E_INVALID;
 	}
+	return scan_filter_run(p, stream, filters, nullptr, n_filters, lip_joins, vector_size, n_selected, n_chunks);
+}
+
+int polr_pipeline_scan_filter_str(polr_pipeline *p, void *stream, const polr_scan_filter_str *filters, uint32_t n_filters,
+                                  uint32_t lip_joins, uint32_t vector_size, uint64_t *n_selected, uint64_t *n_chunks) {
+	POLR_ENTRY();
+	if (!p || (!filters && n_filters)) {
+		return POLR_E_INVALID;
+	}
+	return scan_filter_run(p, stream, nullptr, filters, n_filters, lip_joins, vector_size, n_selected, n_chunks);
+}
+
+} // extern "C"
+
+// The scan behind both entry points.  `filters`: polr_pipeline_scan_filter[_lip], every filter an integer one whatever the
+// column's width; `sfilters`: polr_pipeline_scan_filter_str, where a comparison on a 16-byte column is a VARCHAR one.
+static int scan_filter_run(polr_pipeline *p, void *stream, const polr_scan_filter *filters, const polr_scan_filter_str *sfilters,
+                           uint32_t n_filters, uint32_t lip_joins, uint32_t vector_size, uint64_t *n_selected,
+                           uint64_t *n_chunks) {
 	polr_ctx *ctx = p->ctx;
 	if (n_filters > POLR_MAX_FILTERS) {
 		POLR_FAIL(ctx, POLR_E_UNSUPPORTED, "at most %d pushed-down filters", POLR_MAX_FILTERS);
@@ -333,9 +463,20 @@ int polr_pipeline_scan_filter_lip(polr_pipeline *p, void *stream, const polr_sca
 	}
 	DevFilterSet fs;
 	memset(&fs, 0, sizeof(fs));
-	fs.n = n_filters;
+	DevStrSet ss;
+	memset(&ss, 0, sizeof(ss));
+	std::vector<uint8_t> tails; // the VARCHAR constants' bytes beyond 12
+	uint32_t str_col[POLR_MAX_FILTERS];      // probe column of ss.col[c]
+	std::vector<uint32_t> str_of[POLR_MAX_FILTERS]; // its comparisons (indices into sfilters)
 	for (uint32_t i = 0; i < n_filters; i++) {
-		const polr_scan_filter &f = filters[i];
+		polr_scan_filter f;
+		if (sfilters) {
+			f.col = sfilters[i].col;
+			f.op = sfilters[i].op;
+			f.constant = sfilters[i].constant;
+		} else {
+			f = filters[i];
+		}
 		if (f.col >= p->n_probe_cols) {
 			POLR_FAIL(ctx, POLR_E_INVALID, "filter %u: column %u out of range", i, f.col);
 		}
@@ -343,16 +484,61 @@ int polr_pipeline_scan_filter_lip(polr_pipeline *p, void *stream, const polr_sca
 			POLR_FAIL(ctx, POLR_E_INVALID, "filter %u: unknown comparison %u", i, f.op);
 		}
 		const OwnedCol &c = p->probe_cols[f.col];
+		if (sfilters) {
+			const polr_scan_filter_str &sf = sfilters[i];
+			if (!sf.str && sf.str_len) {
+				POLR_FAIL(ctx, POLR_E_INVALID, "filter %u: a string constant of %llu bytes without its bytes", i,
+				          (unsigned long long)sf.str_len);
+			}
+			if (sf.str && c.width != 16) {
+				POLR_FAIL(ctx, POLR_E_INVALID, "filter %u: a string constant against column %u, which is %u bytes wide", i, f.col, c.width);
+			}
+			if (sf.str_len > POLR_MAX_FILTER_STRING) {
+				POLR_FAIL(ctx, POLR_E_UNSUPPORTED, "filter %u: a string constant of %llu bytes (at most %d)", i,
+				          (unsigned long long)sf.str_len, POLR_MAX_FILTER_STRING);
+			}
+			if (c.width == 16 && f.op <= POLR_CMP_GE) {
+				// a VARCHAR comparison: grouped by column, so that the cell is loaded once for all its constants
+				uint32_t g = 0;
+				while (g < ss.n_cols && str_col[g] != f.col) {
+					g++;
+				}
+				if (g == ss.n_cols) {
+					str_col[ss.n_cols++] = f.col;
+				}
+				str_of[g].push_back(i);
+				continue;
+			}
+		}
+		// (IS [NOT] NULL reads the validity only, whatever the column holds)
 		const bool is_signed = (c.flags & 1u) != 0;
 		if (!is_signed && f.constant < 0 && f.op <= POLR_CMP_GE) {
 			POLR_FAIL(ctx, POLR_E_INVALID, "filter %u: negative constant against an unsigned column", i);
 		}
-		fs.f[i].data = c.data;
-		fs.f[i].valid = c.valid;
-		fs.f[i].width = c.width;
-		fs.f[i].is_signed = is_signed ? 1u : 0u;
-		fs.f[i].op = f.op;
-		fs.f[i].constant = f.constant;
+		DevFilter &d = fs.f[fs.n++];
+		d.data = c.data;
+		d.valid = c.valid;
+		d.width = c.width;
+		d.is_signed = is_signed ? 1u : 0u;
+		d.op = f.op;
+		d.constant = f.constant;
+	}
+	for (uint32_t g = 0, at = 0; g < ss.n_cols; g++) {
+		const OwnedCol &c = p->probe_cols[str_col[g]];
+		ss.col[g].data = c.data;
+		ss.col[g].valid = c.valid;
+		ss.col[g].first = at;
+		ss.col[g].n = (uint32_t)str_of[g].size();
+		for (uint32_t i : str_of[g]) {
+			const polr_scan_filter_str &sf = sfilters[i];
+			DevStrCmp &d = ss.cmp[at++];
+			d.c = polr_str_const_make((const uint8_t *)sf.str, sf.str_len);
+			d.op = sf.op;
+			d.tail_off = (uint32_t)tails.size();
+			if (sf.str_len > 12) {
+				tails.insert(tails.end(), (const uint8_t *)sf.str + 12, (const uint8_t *)sf.str + sf.str_len);
+			}
+		}
 	}
 	// LIP: the joins whose filters are applied at the source, smallest index structure first (cheapest test first)
 	DevLipSet lip;
@@ -394,6 +580,43 @@ int polr_pipeline_scan_filter_lip(polr_pipeline *p, void *stream, const polr_sca
 	}
 	HIPCHK(ctx, hipSetDevice(ctx->device));
 	hipStream_t st = polr_stream(ctx, stream);
+	// A VARCHAR filter column the library uploaded whose heap never came (polr_pipeline_set_probe_heaps) may hold inline
+	// strings only: counted from the length words before any kernel that follows a pointer is enqueued.  (A
+	// POLR_COL_DEVICE column points into HBM by contract.)
+	for (uint32_t g = 0; g < ss.n_cols; g++) {
+		const OwnedCol &c = p->probe_cols[str_col[g]];
+		if (c.strings_rebased || !c.owned || p->n_probe_rows == 0) {
+			continue;
+		}
+		unsigned long long *n_long = nullptr, h_long = 0;
+		HIPCHK(ctx, hipMalloc((void **)&n_long, 8));
+		hipError_t e = hipMemsetAsync(n_long, 0, 8, st);
+		if (e == hipSuccess) {
+			const uint32_t grid = (uint32_t)std::min<uint64_t>((p->n_probe_rows + 255) / 256, (uint64_t)ctx->n_cus * 8);
+			hipLaunchKernelGGL(polr_tscan_count_long_kernel, dim3(grid), dim3(256), 0, st, (const uint8_t *)c.data,
+			                   (const uint8_t *)c.valid, p->n_probe_rows, n_long);
+			e = hipMemcpyAsync(&h_long, n_long, 8, hipMemcpyDeviceToHost, st);
+			e = e == hipSuccess ? hipStreamSynchronize(st) : e;
+		}
+		hipFree(n_long);
+		if (e != hipSuccess) {
+			POLR_FAIL(ctx, POLR_E_HIP, "string column check failed: %s", hipGetErrorString(e));
+		}
+		if (h_long) {
+			POLR_FAIL(ctx, POLR_E_INVALID,
+			          "filter column %u: %llu rows hold strings longer than 12 bytes, but the column's heap was never put on the "
+			          "device (polr_pipeline_set_probe_heaps)",
+			          str_col[g], h_long);
+		}
+	}
+	if (!tails.empty()) {
+		if (!p->scan_str_tails) {
+			HIPCHK(ctx, hipMalloc((void **)&p->scan_str_tails, (size_t)POLR_MAX_FILTERS * POLR_MAX_FILTER_STRING));
+		}
+		// (no scan kernel is in flight: every scan call ends with a synchronisation of its stream)
+		HIPCHK(ctx, hipMemcpy(p->scan_str_tails, tails.data(), tails.size(), hipMemcpyHostToDevice));
+	}
+	ss.tails = p->scan_str_tails;
 	if (p->scan_valid) {
 		// A re-scan rewrites the selection, the chunk boundaries and the device copies of the pipeline in place, and runs
 		// of the previous scan may still be in flight on their multiplexers' streams (passes are enqueued without a
@@ -448,12 +671,22 @@ int polr_pipeline_scan_filter_lip(polr_pipeline *p, void *stream, const polr_sca
 		const uint32_t waves_per_block = 4;
 		const uint32_t grid = (uint32_t)std::min<uint64_t>((n_vec + waves_per_block - 1) / waves_per_block,
 		                                                   (uint64_t)ctx->n_cus * 8);
-		hipLaunchKernelGGL(polr_tscan_count_kernel, dim3(grid), dim3(256), 0, st, fs, lip, n_rows, vector_size, n_vec, packed);
+		if (ss.n_cols) {
+			hipLaunchKernelGGL(polr_tscan_count_str_kernel, dim3(grid), dim3(256), 0, st, fs, ss, lip, n_rows, vector_size, n_vec,
+			                   packed);
+		} else {
+			hipLaunchKernelGGL(polr_tscan_count_kernel, dim3(grid), dim3(256), 0, st, fs, lip, n_rows, vector_size, n_vec, packed);
+		}
 		hipLaunchKernelGGL(polr_tscan_block_sums_kernel, dim3((uint32_t)n_blocks), dim3(1024), 0, st, packed, n_vec, sums);
 		hipLaunchKernelGGL(polr_tscan_sums_kernel, dim3(1), dim3(1024), 0, st, sums, n_blocks, totals);
 		hipLaunchKernelGGL(polr_tscan_apply_kernel, dim3((uint32_t)n_blocks), dim3(1024), 0, st, packed, n_vec, sums);
-		hipLaunchKernelGGL(polr_tscan_write_kernel, dim3(grid), dim3(256), 0, st, fs, lip, n_rows, vector_size, n_vec, packed,
-		                   sel, offs, totals);
+		if (ss.n_cols) {
+			hipLaunchKernelGGL(polr_tscan_write_str_kernel, dim3(grid), dim3(256), 0, st, fs, ss, lip, n_rows, vector_size, n_vec,
+			                   packed, sel, offs, totals);
+		} else {
+			hipLaunchKernelGGL(polr_tscan_write_kernel, dim3(grid), dim3(256), 0, st, fs, lip, n_rows, vector_size, n_vec, packed,
+			                   sel, offs, totals);
+		}
 		e = hipMemcpyAsync(h_tot, totals, 16, hipMemcpyDeviceToHost, st);
 		e = e == hipSuccess ? hipStreamSynchronize(st) : e;
 	} else {
@@ -488,6 +721,8 @@ int polr_pipeline_scan_filter_lip(polr_pipeline *p, void *stream, const polr_sca
 	}
 	return POLR_OK;
 }
+
+extern "C" {
 
 int polr_pipeline_fetch_scan(polr_pipeline *p, uint32_t *sel, uint64_t *chunk_offsets) {
 	POLR_ENTRY();

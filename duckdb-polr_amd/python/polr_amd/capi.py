@@ -42,6 +42,7 @@ EXPORTS = [
     "polr_ht_encode_dictionary", "polr_ht_fetch_dictionary",
     "polr_out_aggregate_expr", "polr_out_aggregate_grouped_expr", "polr_out_aggregate_hashed_expr",
     "polr_mpx_run_resident_stealing", "polr_mpx_steal_stats",
+    "polr_pipeline_scan_filter_str",
 ]
 
 
@@ -81,7 +82,32 @@ class ScanFilter(C.Structure):
     _fields_ = [("col", C.c_uint32), ("op", C.c_uint32), ("constant", C.c_int64)]
 
 
+class ScanFilterStr(C.Structure):
+    """polr_scan_filter_str"""
+    _fields_ = [("col", C.c_uint32), ("op", C.c_uint32), ("constant", C.c_int64), ("str", C.c_void_p),
+                ("str_len", C.c_uint64)]
+
+
 CMP = {"=": 0, "==": 0, "!=": 1, "<>": 1, "<": 2, ">": 3, "<=": 4, ">=": 5, "is null": 6, "is not null": 7}
+MAX_FILTER_STRING = 4096  # POLR_MAX_FILTER_STRING
+
+
+def like_pushdown(pattern):
+    """What the reference pushes into the table scan for `col LIKE pattern` / prefix(col, pattern) (FilterCombiner,
+    src/optimizer/filter_combiner.cpp:450-485) -> [(op, constant)]: nothing for a pattern that begins with a wildcard;
+    equality for one without wildcards; else the range [prefix, prefix with its last byte + 1) of the bytes before the first
+    wildcard; IS NOT NULL goes with both.  The range is the whole predicate only for a pure prefix pattern ('abc%'):
+    anything else stays a filter of the engine behind the scan."""
+    p = pattern.encode() if isinstance(pattern, str) else bytes(pattern)
+    if not p or p[0] in b"%_":
+        return []
+    cut = min([i for i in (p.find(b"%"), p.find(b"_")) if i >= 0], default=-1)
+    if cut < 0:
+        return [("=", p), ("is not null", None)]
+    prefix = p[:cut]
+    if prefix[-1] == 0xFF:
+        raise ValueError("a LIKE prefix that ends in 0xFF has no upper bound one byte up (not UTF-8)")
+    return [(">=", prefix), ("<", prefix[:-1] + bytes([prefix[-1] + 1])), ("is not null", None)]
 
 
 class HeapRange(C.Structure):
@@ -264,6 +290,7 @@ def load():
     L.polr_ht_finalize_auto.argtypes = [vp, C.c_int64, C.c_int64, vp, vp]
     L.polr_pipeline_scan_filter.argtypes = [vp, vp, vp, u32, u32, vp, vp]
     L.polr_pipeline_scan_filter_lip.argtypes = [vp, vp, vp, u32, u32, u32, vp, vp]
+    L.polr_pipeline_scan_filter_str.argtypes = [vp, vp, vp, u32, u32, u32, vp, vp]
     L.polr_pipeline_fetch_scan.argtypes = [vp, vp, vp]
     L.polr_mpx_use_scan_chunks.argtypes = [vp]
     L.polr_out_aggregate.argtypes = [vp, vp, vp, u32, vp]
@@ -609,13 +636,40 @@ class Pipeline:
     def scan_filter(self, filters, vector_size=1024, stream=None, lip_joins=0):
         """polr_pipeline_scan_filter(_lip): filters = [(col, op, constant)] with op in CMP; lip_joins: bit j = also
         apply join j's filter at the source (LIP); the selection and the chunk boundaries stay on the device ->
-        (n_selected, n_chunks)"""
+        (n_selected, n_chunks).  A bytes / str constant is a VARCHAR one (polr_pipeline_scan_filter_str): any such
+        constant sends the whole call through that entry point."""
         n = len(filters)
+        ns, nc = C.c_uint64(), C.c_uint64()
+        if any(isinstance(f[2], (bytes, bytearray, str)) for f in filters):
+            raw = []
+            for col, op, const in filters:
+                if isinstance(const, (bytes, bytearray, str)):
+                    b = const.encode() if isinstance(const, str) else bytes(const)
+                    raw.append((col, op, 0, b, len(b)))
+                else:
+                    raw.append((col, op, const, None, 0))
+            return self.scan_filter_str_raw(raw, vector_size, stream, lip_joins)
         arr = (ScanFilter * max(n, 1))()
         for i, (col, op, const) in enumerate(filters):
             arr[i].col, arr[i].op, arr[i].constant = col, CMP[op] if isinstance(op, str) else op, int(const or 0)
-        ns, nc = C.c_uint64(), C.c_uint64()
         self.ctx.check(self.ctx.L.polr_pipeline_scan_filter_lip(self.h, stream, arr if n else None, n, int(lip_joins),
+                                                                vector_size, C.byref(ns), C.byref(nc)))
+        self.scan = (ns.value, nc.value)
+        return self.scan
+
+    def scan_filter_str_raw(self, filters, vector_size=1024, stream=None, lip_joins=0):
+        """polr_pipeline_scan_filter_str with the struct fields as given: filters = [(col, op code, constant, bytes or
+        None, str_len)] -- the edges of the contract (a length without bytes, bytes against an integer column)"""
+        n = len(filters)
+        arr, keep = (ScanFilterStr * max(n, 1))(), []
+        for i, (col, op, const, b, blen) in enumerate(filters):
+            arr[i].col, arr[i].op, arr[i].constant, arr[i].str_len = col, CMP[op] if isinstance(op, str) else op, int(const or 0), blen
+            if b is not None:
+                buf = C.create_string_buffer(bytes(b), max(len(b), 1))
+                keep.append(buf)
+                arr[i].str = C.addressof(buf)
+        ns, nc = C.c_uint64(), C.c_uint64()
+        self.ctx.check(self.ctx.L.polr_pipeline_scan_filter_str(self.h, stream, arr if n else None, n, int(lip_joins),
                                                                 vector_size, C.byref(ns), C.byref(nc)))
         self.scan = (ns.value, nc.value)
         return self.scan

@@ -291,6 +291,40 @@ int polr_pipeline_scan_filter(polr_pipeline *p, void *stream, const polr_scan_fi
  * value or NULL = NULL); a refused call leaves the scan result before it in place. */
 int polr_pipeline_scan_filter_lip(polr_pipeline *p, void *stream, const polr_scan_filter *filters, uint32_t n_filters,
                                   uint32_t lip_joins, uint32_t vector_size, uint64_t *n_selected, uint64_t *n_chunks);
+/* The same scan with pushed-down VARCHAR constant comparisons.  The reference pushes =, <, >, <=, >= against a VARCHAR
+ * constant into the table scan (FilterCombiner::GenerateTableScanFilters, src/optimizer/filter_combiner.cpp:391-398),
+ * rewrites prefix(col, 'x') and col LIKE 'abc%...' into col >= 'abc' AND col < 'abd' plus IS NOT NULL (:426-485), and
+ * evaluates them on string_t (ColumnSegment::FilterSelection, src/storage/table/column_segment.cpp:435-442).  An engine
+ * hands over its TableFilterSet as it is: a ConstantFilter whose Value is a VARCHAR becomes {col, op, 0, bytes, length}.
+ *  - A comparison on a column of 16-byte string cells compares the row's string with the constant as
+ *    StringComparisonOperators do (comparison_operators.hpp:157-227): memcmp over the shorter length, bytes unsigned, on a
+ *    tie the shorter string is the smaller; equal means same length and same bytes.  '\0' and 0x80-0xFF are ordinary
+ *    bytes; the padding of an inline cell and the pointer of a long one play no part.  str == NULL with str_len == 0 is
+ *    the empty string, which is not NULL.  The constant's bytes are host memory and are copied by the call.
+ *  - A NULL row passes no comparison, not even <>; its cell is never read.  IS NULL / IS NOT NULL read the validity only.
+ *  - Filters are AND-ed; several may name the same column (the LIKE range); filters on integer columns (`constant`, as
+ *    polr_scan_filter) and the LIP mask mix freely with the VARCHAR ones.  With no 16-byte column compared the call is
+ *    polr_pipeline_scan_filter_lip.  Row order, skipped empty vectors, chunk boundaries, the installation as the
+ *    pipeline's source and the settling of a re-scan are those of polr_pipeline_scan_filter.
+ *  - POLR_E_INVALID: str == NULL with str_len > 0; a non-NULL str against a column that is not 16 bytes wide;
+ *    POLR_CMP_STR_EQ or any code above POLR_CMP_IS_NOT_NULL; and everything polr_pipeline_scan_filter_lip refuses so.
+ *    POLR_E_UNSUPPORTED: a constant longer than POLR_MAX_FILTER_STRING bytes; more than 8 filters.
+ *  - The heaps: as for polr_out_aggregate_hashed_str.  A compared column the library uploaded whose heap never came
+ *    (polr_pipeline_set_probe_heaps) may hold inline strings only: the call first counts its non-NULL cells longer than 12
+ *    bytes, reading length words only, and any such cell is POLR_E_INVALID before a kernel that follows a pointer is
+ *    enqueued.  The cells of a POLR_COL_DEVICE column point into HBM by contract.
+ *  - A refused call enqueues no scan and leaves the scan result before it in place.
+ * OR-conjunctions, IN lists, LIKE beyond the pushed prefix range and collations stay with the engine's own filter. */
+#define POLR_MAX_FILTER_STRING 4096
+typedef struct polr_scan_filter_str {
+	uint32_t col;      /* probe-table column */
+	uint32_t op;       /* POLR_CMP_EQ .. POLR_CMP_IS_NOT_NULL */
+	int64_t constant;  /* integer column: as polr_scan_filter */
+	const void *str;   /* VARCHAR column (width 16): the constant's bytes (host memory, copied by the call) */
+	uint64_t str_len;  /* may be 0 (the empty string, which is not NULL) */
+} polr_scan_filter_str;
+int polr_pipeline_scan_filter_str(polr_pipeline *p, void *stream, const polr_scan_filter_str *filters, uint32_t n_filters,
+                                  uint32_t lip_joins, uint32_t vector_size, uint64_t *n_selected, uint64_t *n_chunks);
 /* read the scan result back (tests): sel[n_selected], chunk_offsets[n_chunks + 1]; either may be NULL */
 int polr_pipeline_fetch_scan(polr_pipeline *p, uint32_t *sel, uint64_t *chunk_offsets);
 /* Refresh the cells of probe column `col` in place (a new DataChunk arriving at the operator-level
