@@ -1637,6 +1637,12 @@ void polr_pipeline_destroy(polr_pipeline *p) {
 	if (p->scan_str_tails) {
 		hipFree(p->scan_str_tails);
 	}
+	if (p->scan_expr_prog) {
+		hipFree(p->scan_expr_prog);
+	}
+	if (p->scan_pass_bits) {
+		hipFree(p->scan_pass_bits);
+	}
 	if (p->dev_mat) {
 		hipFree(p->dev_mat);
 	}

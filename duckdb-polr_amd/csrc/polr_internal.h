@@ -114,6 +114,12 @@ struct polr_pipeline {
 	unsigned long long *scan_packed = nullptr, *scan_sums = nullptr, *scan_totals = nullptr;
 	uint64_t scan_cap_rows = 0, scan_cap_vec = 0;
 	uint8_t *scan_str_tails = nullptr; // polr_pipeline_scan_filter_str: the VARCHAR constants' bytes beyond 12, re-uploaded per call
+	// polr_pipeline_scan_filter_expr: the lowered program (re-uploaded per call) and one pass bit per table row, written
+	// by the counting pass and read by the writing pass; both allocated by the first such call
+	uint8_t *scan_expr_prog = nullptr;
+	size_t scan_expr_cap = 0;
+	unsigned long long *scan_pass_bits = nullptr;
+	uint64_t scan_pass_cap = 0; // words
 	bool scan_valid = false;      // a scan result is installed (selection + chunk boundaries)
 	uint64_t scan_generation = 0; // bumped by every scan: multiplexers must re-attach (polr_mpx_use_scan_chunks)
 	std::vector<polr_ht *> hts;

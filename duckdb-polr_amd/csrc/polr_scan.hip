@@ -22,6 +22,12 @@
 // time with a DevStrSet beside the integer filters, so a scan without string filters runs the code it always ran.  A row
 // costs one 16-byte cell load per distinct VARCHAR filter column (2 x 16 over the two passes); the comparison is
 // polr_strcmp.h.  The heap is read only for a cell longer than 12 bytes whose first four bytes tie with a constant's.
+//
+// Filter expressions (polr_pipeline_scan_filter_expr; what the reference evaluates in a PhysicalFilter between the scan
+// and the first join -- OR / NOT trees, IN lists, LIKE): a count kernel of its own that evaluates a postfix program once
+// per row and keeps every step's ballot, and a write kernel that reads those bits instead of evaluating again (see
+// "expression filters" below; the program is checked and lowered by polr_filter_plan.h, LIKE is polr_like.h).  Algorithmic
+// bytes: the named columns once per table row + 2 bits per row + 4 per surviving row.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <string.h>
@@ -29,7 +35,9 @@
 #include <algorithm>
 #include <vector>
 
+#include "polr_filter_plan.h"
 #include "polr_internal.h"
+#include "polr_like.h"
 #include "polr_strcmp.h"
 
 struct DevFilter {
@@ -397,6 +405,201 @@ __global__ __launch_bounds__(256) void polr_tscan_write_str_kernel(DevFilterSet 
 	tscan_write<true>(lane, wave, n_waves, fs, &ss, lip, n_rows, V, n_vec, prefix, sel, chunk_offsets, totals);
 }
 
+// ---- expression filters (polr_pipeline_scan_filter_expr): what the reference evaluates in a PhysicalFilter behind the scan
+// -- OR / NOT trees, IN lists, LIKE -- as a postfix program (lowered by polr_filter_plan.h).  The program is wave-uniform: the
+// nodes travel in the kernel argument, leaves / values / segments / constant bytes in one buffer of the pipeline read at
+// uniform addresses; only the evaluation of a leaf is per lane.  A row first evaluates the leaves column by column -- the cell
+// of a column is loaded once, a NULL row's cell never -- into one bit per leaf and one NULL bit per column, then walks the
+// nodes over an operand stack of two 32-bit words per lane (true bits, NULL bits; a NULL's true bit is 0).  The counting
+// pass stores the ballot of every 64-row step (LIP included) in the pipeline's pass-bit buffer, ceil(V / 64) words per
+// vector; the writing pass reads those words and evaluates nothing.
+struct DevFxCol {
+	const uint8_t *data;
+	const uint8_t *valid;
+	uint32_t width, is_signed;
+	uint32_t first_leaf, n_leaves;
+	uint32_t needs_cell, pad;
+};
+struct DevFxProg {
+	DevFxCol col[POLR_FX_MAX_COLS];
+	uint32_t nodes[POLR_MAX_FILTER_NODES];
+	const PolrFxLeaf *leaves;
+	const PolrFxValue *values;
+	const polr_like_seg *segs;
+	const uint8_t *bytes;
+	uint32_t n_cols, n_nodes;
+};
+
+// does the integer v compare (op) with one of the leaf's constants?  (CMP: one constant; IN: op is EQ)
+__device__ __forceinline__ bool fx_leaf_int(const DevFxProg &px, const PolrFxLeaf lf, uint64_t v, bool is_signed) {
+	bool r = false;
+	for (uint32_t i = lf.first_value; i < lf.first_value + lf.n_values; i++) {
+		const int64_t k = px.values[i].constant;
+		bool h;
+		if (is_signed) {
+			const int64_t a = (int64_t)v;
+			h = lf.op == POLR_CMP_EQ   ? a == k
+			    : lf.op == POLR_CMP_NE ? a != k
+			    : lf.op == POLR_CMP_LT ? a < k
+			    : lf.op == POLR_CMP_GT ? a > k
+			    : lf.op == POLR_CMP_LE ? a <= k
+			                           : a >= k;
+		} else {
+			const uint64_t c = (uint64_t)k; // (host: constant >= 0 for unsigned columns)
+			h = lf.op == POLR_CMP_EQ   ? v == c
+			    : lf.op == POLR_CMP_NE ? v != c
+			    : lf.op == POLR_CMP_LT ? v < c
+			    : lf.op == POLR_CMP_GT ? v > c
+			    : lf.op == POLR_CMP_LE ? v <= c
+			                           : v >= c;
+		}
+		r = r || h;
+	}
+	return r;
+}
+
+__device__ __forceinline__ bool fx_leaf_str(const DevFxProg &px, const PolrFxLeaf lf, const uint4 cell) {
+	if (lf.kind == POLR_FX_LIKE) {
+		return polr_like_match(cell.x, cell.y, cell.z, cell.w, px.values[lf.first_value].pat, px.segs, px.bytes);
+	}
+	bool r = false;
+	for (uint32_t i = lf.first_value; i < lf.first_value + lf.n_values && !r; i++) {
+		const polr_str_const c = px.values[i].c;
+		if (lf.op == POLR_CMP_EQ && c.len != cell.x) {
+			continue; // (equal strings have equal lengths: most IN members end here)
+		}
+		r = polr_str_cmp_holds(polr_str_cmp3(cell.x, cell.y, cell.z, cell.w, c, px.bytes + px.values[i].bytes_off + 12u), lf.op);
+	}
+	return r;
+}
+
+// is the root TRUE for the row?
+__device__ __forceinline__ bool fx_row_true(const DevFxProg &px, uint64_t row) {
+	unsigned long long leaf_true = 0;
+	uint32_t col_null = 0;
+	for (uint32_t c = 0; c < px.n_cols; c++) {
+		const DevFxCol &col = px.col[c];
+		const bool valid = !(col.valid && !as_global(col.valid)[row]);
+		col_null |= valid ? 0u : 1u << c;
+		uint4 cell = make_uint4(0, 0, 0, 0);
+		uint64_t v = 0;
+		if (valid && col.needs_cell) {
+			if (col.width == 16) {
+				cell = load_global_x4(as_global((const uint32_t *)col.data) + row * 4);
+			} else {
+				v = load_cell(as_global(col.data) + row * col.width, col.width, col.is_signed != 0);
+			}
+		}
+		for (uint32_t l = col.first_leaf; l < col.first_leaf + col.n_leaves; l++) {
+			const PolrFxLeaf lf = px.leaves[l];
+			bool t;
+			if (lf.kind == POLR_FX_CMP && lf.op >= POLR_CMP_IS_NULL) {
+				t = (lf.op == POLR_CMP_IS_NULL) != valid;
+			} else if (!valid) {
+				t = false; // NULL: the node takes the column's NULL bit
+			} else if (col.width == 16) {
+				t = fx_leaf_str(px, lf, cell);
+			} else {
+				t = fx_leaf_int(px, lf, v, col.is_signed != 0);
+			}
+			leaf_true |= (unsigned long long)t << l;
+		}
+	}
+	uint32_t T = 0, N = 0; // the operand stack: bit 0 is the top
+	for (uint32_t i = 0; i < px.n_nodes; i++) {
+		const uint32_t nd = px.nodes[i];
+		const uint32_t kind = nd & 0xFFu;
+		if (kind <= POLR_FX_LIKE) {
+			const uint32_t n = (nd & POLR_FX_NEVER_NULL) ? 0u : (col_null >> ((nd >> 16) & 0xFFu)) & 1u;
+			const uint32_t t = (uint32_t)(leaf_true >> ((nd >> 8) & 0xFFu)) & 1u & ~n;
+			T = (T << 1) | t;
+			N = (N << 1) | n;
+		} else if (kind == POLR_FX_NOT) {
+			T ^= ~N & 1u; // NOT NULL = NULL
+		} else {
+			const uint32_t ta = (T >> 1) & 1u, tb = T & 1u, na = (N >> 1) & 1u, nb = N & 1u;
+			uint32_t rt, rn;
+			if (kind == POLR_FX_AND) {
+				const uint32_t rf = (~(ta | na) | ~(tb | nb)) & 1u; // one side FALSE: FALSE, whatever the other is
+				rt = ta & tb;
+				rn = (na | nb) & ~rf;
+			} else {
+				rt = ta | tb; // one side TRUE: TRUE
+				rn = (na | nb) & ~rt;
+			}
+			T = ((T >> 2) << 1) | rt;
+			N = ((N >> 2) << 1) | rn;
+		}
+	}
+	return px.n_nodes == 0 || (T & 1u);
+}
+
+__global__ __launch_bounds__(256) void polr_tscan_count_expr_kernel(DevFxProg px, DevLipSet lip, uint64_t n_rows, uint32_t V,
+                                                                   uint64_t n_vec, unsigned long long *__restrict__ packed,
+                                                                   unsigned long long *__restrict__ pass_bits) {
+	const uint32_t lane = threadIdx.x & 63;
+	const uint64_t wave = ((uint64_t)blockIdx.x * blockDim.x + threadIdx.x) >> 6;
+	const uint64_t n_waves = ((uint64_t)gridDim.x * blockDim.x) >> 6;
+	const uint64_t words_per_vec = ((uint64_t)V + 63) >> 6;
+	for (uint64_t v = wave; v < n_vec; v += n_waves) {
+		const uint64_t begin = v * V;
+		const uint64_t end = begin + V < n_rows ? begin + V : n_rows;
+		uint64_t word = v * words_per_vec;
+		uint32_t cnt = 0;
+		for (uint64_t r0 = begin; r0 < end; r0 += 64, word++) {
+			const uint64_t row = r0 + lane;
+			bool pass = row < end && fx_row_true(px, row);
+			for (uint32_t i = 0; i < lip.n; i++) {
+				pass = pass && lip_contains(lip.f[i], row);
+			}
+			const uint64_t m = __ballot(pass);
+			cnt += (uint32_t)__popcll(m);
+			if (lane == 0) {
+				pass_bits[word] = m;
+			}
+		}
+		if (lane == 0) {
+			packed[v] = (unsigned long long)cnt | (cnt ? (1ull << PACK_SHIFT) : 0ull);
+		}
+	}
+}
+
+// tscan_write with the rows that pass read from the counting pass's bits
+__global__ __launch_bounds__(256) void polr_tscan_write_bits_kernel(const unsigned long long *__restrict__ pass_bits, uint64_t n_rows,
+                                                                   uint32_t V, uint64_t n_vec,
+                                                                   const unsigned long long *__restrict__ prefix,
+                                                                   uint32_t *__restrict__ sel, uint64_t *__restrict__ chunk_offsets,
+                                                                   const unsigned long long *__restrict__ totals) {
+	const uint32_t lane = threadIdx.x & 63;
+	const uint64_t wave = ((uint64_t)blockIdx.x * blockDim.x + threadIdx.x) >> 6;
+	const uint64_t n_waves = ((uint64_t)gridDim.x * blockDim.x) >> 6;
+	const uint64_t words_per_vec = ((uint64_t)V + 63) >> 6;
+	if (wave == 0 && lane == 0) {
+		chunk_offsets[totals[1]] = totals[0]; // the end of the last chunk
+	}
+	for (uint64_t v = wave; v < n_vec; v += n_waves) {
+		const unsigned long long pv = prefix[v];
+		if (!(pv >> 63)) {
+			continue; // no survivor: the scan skips the vector
+		}
+		uint64_t out = pv & PACK_MASK;
+		const uint64_t chunk = (pv & ~(1ull << 63)) >> PACK_SHIFT;
+		if (lane == 0) {
+			chunk_offsets[chunk] = out;
+		}
+		const uint64_t begin = v * V;
+		const uint64_t end = begin + V < n_rows ? begin + V : n_rows;
+		uint64_t word = v * words_per_vec;
+		for (uint64_t r0 = begin; r0 < end; r0 += 64, word++) {
+			const uint64_t m = pass_bits[word];
+			if ((m >> lane) & 1ull) {
+				sel[out + lane_rank(m)] = (uint32_t)(r0 + lane);
+			}
+			out += (uint64_t)__popcll(m);
+		}
+	}
+}
+
 // the guard of a VARCHAR filter column whose cells were never rebased onto a device heap: its non-NULL cells longer than 12
 // bytes -- their pointers are the host's.  Reads the validity byte and the length word of a cell, nothing else.
 __global__ __launch_bounds__(256) void polr_tscan_count_long_kernel(const uint8_t *__restrict__ cells,
@@ -445,6 +648,143 @@ int polr_pipeline_scan_filter_str(polr_pipeline *p, void *stream, const polr_sca
 }
 
 } // extern "C"
+
+// LIP: the joins whose filters are applied at the source, smallest index structure first (cheapest test first)
+static int scan_lip_set(polr_pipeline *p, uint32_t lip_joins, DevLipSet &lip) {
+	polr_ctx *ctx = p->ctx;
+	memset(&lip, 0, sizeof(lip));
+	{
+		std::vector<uint32_t> js;
+		for (uint32_t j = 0; j < p->k; j++) {
+			if (!((lip_joins >> j) & 1u)) {
+				continue;
+			}
+			const DevJoin &dj = p->host_count.joins[j];
+			if (dj.n_keys != 1 || dj.key_src_join[0] >= 0) {
+				POLR_FAIL(ctx, POLR_E_INVALID, "LIP: join %u is not keyed by one column of the source (physical_join.cpp:57-107)", j);
+			}
+			if (p->hts[j]->pack.packed) {
+				POLR_FAIL(ctx, POLR_E_UNSUPPORTED, "LIP: join %u compares its key by value / NULL = NULL (packed form)", j);
+			}
+			js.push_back(j);
+		}
+		if (lip_joins >> p->k) {
+			POLR_FAIL(ctx, POLR_E_INVALID, "LIP: join mask names a join beyond the %u of the pipeline", p->k);
+		}
+		std::sort(js.begin(), js.end(), [&](uint32_t a, uint32_t b) { return p->hts[a]->device_bytes < p->hts[b]->device_bytes; });
+		for (uint32_t j : js) {
+			const DevJoin &dj = p->host_count.joins[j];
+			const OwnedCol &c = p->probe_cols[dj.key_src_col[0]];
+			DevLip &f = lip.f[lip.n++];
+			f.key_data = c.data;
+			f.key_valid = c.valid;
+			f.key_width = c.width;
+			f.key_signed = dj.key_signed;
+			f.kind = dj.kind;
+			f.table = dj.table;
+			f.mask = dj.mask;
+			f.min_value = dj.min_value;
+			f.range = dj.range;
+			f.sentinel_count = dj.sentinel_count;
+		}
+	}
+	return POLR_OK;
+}
+
+// A VARCHAR filter column the library uploaded whose heap never came may hold inline strings only (see scan_filter_run)
+static int scan_check_heap(polr_pipeline *p, hipStream_t st, uint32_t col) {
+	polr_ctx *ctx = p->ctx;
+	const OwnedCol &c = p->probe_cols[col];
+	if (c.strings_rebased || !c.owned || p->n_probe_rows == 0) {
+		return POLR_OK;
+	}
+	unsigned long long *n_long = nullptr, h_long = 0;
+	HIPCHK(ctx, hipMalloc((void **)&n_long, 8));
+	hipError_t e = hipMemsetAsync(n_long, 0, 8, st);
+	if (e == hipSuccess) {
+		const uint32_t grid = (uint32_t)std::min<uint64_t>((p->n_probe_rows + 255) / 256, (uint64_t)ctx->n_cus * 8);
+		hipLaunchKernelGGL(polr_tscan_count_long_kernel, dim3(grid), dim3(256), 0, st, (const uint8_t *)c.data,
+		                   (const uint8_t *)c.valid, p->n_probe_rows, n_long);
+		e = hipMemcpyAsync(&h_long, n_long, 8, hipMemcpyDeviceToHost, st);
+		e = e == hipSuccess ? hipStreamSynchronize(st) : e;
+	}
+	hipFree(n_long);
+	if (e != hipSuccess) {
+		POLR_FAIL(ctx, POLR_E_HIP, "string column check failed: %s", hipGetErrorString(e));
+	}
+	if (h_long) {
+		POLR_FAIL(ctx, POLR_E_INVALID,
+		          "filter column %u: %llu rows hold strings longer than 12 bytes, but the column's heap was never put on the "
+		          "device (polr_pipeline_set_probe_heaps)",
+		          col, h_long);
+	}
+	return POLR_OK;
+}
+
+// the scan's scratch and result buffers, grown to the table and the vector count (see scan_filter_run)
+static int scan_buffers(polr_pipeline *p, uint64_t n_rows, uint64_t n_vec, uint64_t n_blocks) {
+	polr_ctx *ctx = p->ctx;
+	if (p->scan_cap_rows < n_rows || p->scan_cap_vec < n_vec) {
+		if (p->scan_packed) {
+			hipFree(p->scan_packed);
+			hipFree(p->scan_sums);
+			hipFree(p->scan_totals);
+			p->scan_packed = p->scan_sums = p->scan_totals = nullptr;
+		}
+		if (p->scan_sel) {
+			if (p->sel_dev == p->scan_sel) {
+				p->sel_dev = nullptr;
+			}
+			hipFree(p->scan_sel);
+			p->scan_sel = nullptr;
+		}
+		if (p->scan_offsets_dev) {
+			hipFree(p->scan_offsets_dev);
+			p->scan_offsets_dev = nullptr;
+		}
+		hipError_t ea = hipMalloc((void **)&p->scan_packed, std::max<uint64_t>(n_vec, 1) * 8);
+		ea = ea == hipSuccess ? hipMalloc((void **)&p->scan_sums, std::max<uint64_t>(n_blocks, 1) * 8) : ea;
+		ea = ea == hipSuccess ? hipMalloc((void **)&p->scan_totals, 16) : ea;
+		ea = ea == hipSuccess ? hipMalloc((void **)&p->scan_sel, std::max<uint64_t>(n_rows, 1) * 4) : ea;
+		ea = ea == hipSuccess ? hipMalloc((void **)&p->scan_offsets_dev, (n_vec + 1) * 8) : ea;
+		if (ea != hipSuccess) {
+			p->scan_cap_rows = p->scan_cap_vec = 0;
+			POLR_FAIL(ctx, POLR_E_HIP, "scan filter buffers: %s", hipGetErrorString(ea));
+		}
+		p->scan_cap_rows = n_rows;
+		p->scan_cap_vec = n_vec;
+	}
+	return POLR_OK;
+}
+
+static int scan_install(polr_pipeline *p, uint32_t vector_size, const uint64_t *h_tot, uint64_t *n_selected, uint64_t *n_chunks) {
+	polr_ctx *ctx = p->ctx;
+	uint32_t *sel = p->scan_sel;
+	// install: the selection is the pipeline's source now (the buffers stay the pipeline's scan buffers)
+	if (p->sel_dev && p->sel_owned && p->sel_dev != p->scan_sel) {
+		hipFree(p->sel_dev);
+	}
+	p->sel_dev = sel;
+	p->sel_owned = false; // (freed as scan_sel)
+	p->n_tuples = h_tot[0];
+	p->scan_valid = true;
+	p->scan_generation++;
+	p->scan_n_chunks = h_tot[1];
+	p->scan_vector_size = vector_size;
+	p->host_mat.sel = p->sel_dev;
+	p->host_mat.n_tuples = p->n_tuples;
+	p->host_count.sel = p->sel_dev;
+	p->host_count.n_tuples = p->n_tuples;
+	HIPCHK(ctx, hipMemcpy(p->dev_mat, &p->host_mat, sizeof(DevPipeline), hipMemcpyHostToDevice));
+	HIPCHK(ctx, hipMemcpy(p->dev_count, &p->host_count, sizeof(DevPipeline), hipMemcpyHostToDevice));
+	if (n_selected) {
+		*n_selected = h_tot[0];
+	}
+	if (n_chunks) {
+		*n_chunks = h_tot[1];
+	}
+	return POLR_OK;
+}
 
 // The scan behind both entry points.  `filters`: polr_pipeline_scan_filter[_lip], every filter an integer one whatever the
 // column's width; `sfilters`: polr_pipeline_scan_filter_str, where a comparison on a 16-byte column is a VARCHAR one.
@@ -540,43 +880,9 @@ static int scan_filter_run(polr_pipeline *p, void *stream, const polr_scan_filte
 			}
 		}
 	}
-	// LIP: the joins whose filters are applied at the source, smallest index structure first (cheapest test first)
 	DevLipSet lip;
-	memset(&lip, 0, sizeof(lip));
-	{
-		std::vector<uint32_t> js;
-		for (uint32_t j = 0; j < p->k; j++) {
-			if (!((lip_joins >> j) & 1u)) {
-				continue;
-			}
-			const DevJoin &dj = p->host_count.joins[j];
-			if (dj.n_keys != 1 || dj.key_src_join[0] >= 0) {
-				POLR_FAIL(ctx, POLR_E_INVALID, "LIP: join %u is not keyed by one column of the source (physical_join.cpp:57-107)", j);
-			}
-			if (p->hts[j]->pack.packed) {
-				POLR_FAIL(ctx, POLR_E_UNSUPPORTED, "LIP: join %u compares its key by value / NULL = NULL (packed form)", j);
-			}
-			js.push_back(j);
-		}
-		if (lip_joins >> p->k) {
-			POLR_FAIL(ctx, POLR_E_INVALID, "LIP: join mask names a join beyond the %u of the pipeline", p->k);
-		}
-		std::sort(js.begin(), js.end(), [&](uint32_t a, uint32_t b) { return p->hts[a]->device_bytes < p->hts[b]->device_bytes; });
-		for (uint32_t j : js) {
-			const DevJoin &dj = p->host_count.joins[j];
-			const OwnedCol &c = p->probe_cols[dj.key_src_col[0]];
-			DevLip &f = lip.f[lip.n++];
-			f.key_data = c.data;
-			f.key_valid = c.valid;
-			f.key_width = c.width;
-			f.key_signed = dj.key_signed;
-			f.kind = dj.kind;
-			f.table = dj.table;
-			f.mask = dj.mask;
-			f.min_value = dj.min_value;
-			f.range = dj.range;
-			f.sentinel_count = dj.sentinel_count;
-		}
+	if (int rc = scan_lip_set(p, lip_joins, lip)) {
+		return rc;
 	}
 	HIPCHK(ctx, hipSetDevice(ctx->device));
 	hipStream_t st = polr_stream(ctx, stream);
@@ -584,29 +890,8 @@ static int scan_filter_run(polr_pipeline *p, void *stream, const polr_scan_filte
 	// strings only: counted from the length words before any kernel that follows a pointer is enqueued.  (A
 	// POLR_COL_DEVICE column points into HBM by contract.)
 	for (uint32_t g = 0; g < ss.n_cols; g++) {
-		const OwnedCol &c = p->probe_cols[str_col[g]];
-		if (c.strings_rebased || !c.owned || p->n_probe_rows == 0) {
-			continue;
-		}
-		unsigned long long *n_long = nullptr, h_long = 0;
-		HIPCHK(ctx, hipMalloc((void **)&n_long, 8));
-		hipError_t e = hipMemsetAsync(n_long, 0, 8, st);
-		if (e == hipSuccess) {
-			const uint32_t grid = (uint32_t)std::min<uint64_t>((p->n_probe_rows + 255) / 256, (uint64_t)ctx->n_cus * 8);
-			hipLaunchKernelGGL(polr_tscan_count_long_kernel, dim3(grid), dim3(256), 0, st, (const uint8_t *)c.data,
-			                   (const uint8_t *)c.valid, p->n_probe_rows, n_long);
-			e = hipMemcpyAsync(&h_long, n_long, 8, hipMemcpyDeviceToHost, st);
-			e = e == hipSuccess ? hipStreamSynchronize(st) : e;
-		}
-		hipFree(n_long);
-		if (e != hipSuccess) {
-			POLR_FAIL(ctx, POLR_E_HIP, "string column check failed: %s", hipGetErrorString(e));
-		}
-		if (h_long) {
-			POLR_FAIL(ctx, POLR_E_INVALID,
-			          "filter column %u: %llu rows hold strings longer than 12 bytes, but the column's heap was never put on the "
-			          "device (polr_pipeline_set_probe_heaps)",
-			          str_col[g], h_long);
+		if (int rc = scan_check_heap(p, st, str_col[g])) {
+			return rc;
 		}
 	}
 	if (!tails.empty()) {
@@ -632,35 +917,8 @@ static int scan_filter_run(polr_pipeline *p, void *stream, const polr_scan_filte
 	// Scratch and result buffers belong to the pipeline and are sized for the worst case (every row survives, every
 	// vector is a chunk), so the whole scan is enqueued without a host round trip in the middle; one
 	// synchronisation at the end reads the two totals.
-	if (p->scan_cap_rows < n_rows || p->scan_cap_vec < n_vec) {
-		if (p->scan_packed) {
-			hipFree(p->scan_packed);
-			hipFree(p->scan_sums);
-			hipFree(p->scan_totals);
-			p->scan_packed = p->scan_sums = p->scan_totals = nullptr;
-		}
-		if (p->scan_sel) {
-			if (p->sel_dev == p->scan_sel) {
-				p->sel_dev = nullptr;
-			}
-			hipFree(p->scan_sel);
-			p->scan_sel = nullptr;
-		}
-		if (p->scan_offsets_dev) {
-			hipFree(p->scan_offsets_dev);
-			p->scan_offsets_dev = nullptr;
-		}
-		hipError_t ea = hipMalloc((void **)&p->scan_packed, std::max<uint64_t>(n_vec, 1) * 8);
-		ea = ea == hipSuccess ? hipMalloc((void **)&p->scan_sums, std::max<uint64_t>(n_blocks, 1) * 8) : ea;
-		ea = ea == hipSuccess ? hipMalloc((void **)&p->scan_totals, 16) : ea;
-		ea = ea == hipSuccess ? hipMalloc((void **)&p->scan_sel, std::max<uint64_t>(n_rows, 1) * 4) : ea;
-		ea = ea == hipSuccess ? hipMalloc((void **)&p->scan_offsets_dev, (n_vec + 1) * 8) : ea;
-		if (ea != hipSuccess) {
-			p->scan_cap_rows = p->scan_cap_vec = 0;
-			POLR_FAIL(ctx, POLR_E_HIP, "scan filter buffers: %s", hipGetErrorString(ea));
-		}
-		p->scan_cap_rows = n_rows;
-		p->scan_cap_vec = n_vec;
+	if (int rc = scan_buffers(p, n_rows, n_vec, n_blocks)) {
+		return rc;
 	}
 	unsigned long long *packed = p->scan_packed, *sums = p->scan_sums, *totals = p->scan_totals;
 	uint32_t *sel = p->scan_sel;
@@ -696,33 +954,152 @@ static int scan_filter_run(polr_pipeline *p, void *stream, const polr_scan_filte
 	if (e != hipSuccess) {
 		POLR_FAIL(ctx, POLR_E_HIP, "scan filter failed: %s", hipGetErrorString(e));
 	}
-	// install: the selection is the pipeline's source now (the buffers stay the pipeline's scan buffers)
-	if (p->sel_dev && p->sel_owned && p->sel_dev != p->scan_sel) {
-		hipFree(p->sel_dev);
+	return scan_install(p, vector_size, h_tot, n_selected, n_chunks);
+}
+
+// polr_pipeline_scan_filter_expr: the program checked and lowered on the host (polr_filter_plan.h), uploaded into the
+// pipeline's program buffer, one evaluating pass and one pass over its bits
+static int scan_filter_expr_run(polr_pipeline *p, void *stream, const polr_filter_node *nodes, uint32_t n_nodes,
+                                const polr_filter_value *values, uint32_t n_values, uint32_t lip_joins, uint32_t vector_size,
+                                uint64_t *n_selected, uint64_t *n_chunks) {
+	polr_ctx *ctx = p->ctx;
+	if (vector_size < 2 || vector_size > 65536) {
+		POLR_FAIL(ctx, POLR_E_INVALID, "vector size %u out of range", vector_size);
 	}
-	p->sel_dev = sel;
-	p->sel_owned = false; // (freed as scan_sel)
-	p->n_tuples = h_tot[0];
-	p->scan_valid = true;
-	p->scan_generation++;
-	p->scan_n_chunks = h_tot[1];
-	p->scan_vector_size = vector_size;
-	p->host_mat.sel = p->sel_dev;
-	p->host_mat.n_tuples = p->n_tuples;
-	p->host_count.sel = p->sel_dev;
-	p->host_count.n_tuples = p->n_tuples;
-	HIPCHK(ctx, hipMemcpy(p->dev_mat, &p->host_mat, sizeof(DevPipeline), hipMemcpyHostToDevice));
-	HIPCHK(ctx, hipMemcpy(p->dev_count, &p->host_count, sizeof(DevPipeline), hipMemcpyHostToDevice));
-	if (n_selected) {
-		*n_selected = h_tot[0];
+	if (p->n_probe_rows >= 0xFFFFFFF0ull) {
+		POLR_FAIL(ctx, POLR_E_UNSUPPORTED, "source partition too large for 32-bit row ids");
 	}
-	if (n_chunks) {
-		*n_chunks = h_tot[1];
+	std::vector<PolrFilterColumn> cols(p->n_probe_cols);
+	for (uint32_t c = 0; c < p->n_probe_cols; c++) {
+		cols[c].width = p->probe_cols[c].width;
+		cols[c].is_signed = p->probe_cols[c].flags & 1u;
 	}
-	return POLR_OK;
+	PolrFilterPlan pl;
+	if (int rc = polr_filter_plan(nodes, n_nodes, values, n_values, cols.data(), p->n_probe_cols, pl)) {
+		POLR_FAIL(ctx, rc, "filter expression: %s", pl.err);
+	}
+	DevLipSet lip;
+	if (int rc = scan_lip_set(p, lip_joins, lip)) {
+		return rc;
+	}
+	HIPCHK(ctx, hipSetDevice(ctx->device));
+	hipStream_t st = polr_stream(ctx, stream);
+	// (the heaps: as scan_filter_run -- only columns whose cells some leaf reads)
+	for (uint32_t g = 0; g < pl.n_cols; g++) {
+		if (pl.cols[g].needs_cell && cols[pl.cols[g].col].width == 16) {
+			if (int rc = scan_check_heap(p, st, pl.cols[g].col)) {
+				return rc;
+			}
+		}
+	}
+	// the program buffer: values | leaves | segments | bytes (8 spare bytes behind: never empty)
+	const size_t values_at = 0, leaves_at = values_at + pl.values.size() * sizeof(PolrFxValue);
+	const size_t segs_at = leaves_at + pl.n_leaves * sizeof(PolrFxLeaf), bytes_at = segs_at + pl.segs.size() * sizeof(polr_like_seg);
+	std::vector<uint8_t> blob(bytes_at + pl.bytes.size() + 8, 0);
+	if (!pl.values.empty()) {
+		memcpy(blob.data() + values_at, pl.values.data(), pl.values.size() * sizeof(PolrFxValue));
+	}
+	memcpy(blob.data() + leaves_at, pl.leaves, pl.n_leaves * sizeof(PolrFxLeaf));
+	if (!pl.segs.empty()) {
+		memcpy(blob.data() + segs_at, pl.segs.data(), pl.segs.size() * sizeof(polr_like_seg));
+	}
+	if (!pl.bytes.empty()) {
+		memcpy(blob.data() + bytes_at, pl.bytes.data(), pl.bytes.size());
+	}
+	if (p->scan_expr_cap < blob.size()) {
+		if (p->scan_expr_prog) {
+			hipFree(p->scan_expr_prog);
+			p->scan_expr_prog = nullptr;
+			p->scan_expr_cap = 0;
+		}
+		const size_t cap = std::max<size_t>(blob.size(), 8192);
+		HIPCHK(ctx, hipMalloc((void **)&p->scan_expr_prog, cap));
+		p->scan_expr_cap = cap;
+	}
+	// (no scan kernel is in flight: every scan call ends with a synchronisation of its stream)
+	HIPCHK(ctx, hipMemcpy(p->scan_expr_prog, blob.data(), blob.size(), hipMemcpyHostToDevice));
+	DevFxProg px;
+	memset(&px, 0, sizeof(px));
+	px.n_cols = pl.n_cols;
+	px.n_nodes = pl.n_nodes;
+	memcpy(px.nodes, pl.nodes, sizeof(uint32_t) * pl.n_nodes);
+	for (uint32_t g = 0; g < pl.n_cols; g++) {
+		const OwnedCol &c = p->probe_cols[pl.cols[g].col];
+		DevFxCol &d = px.col[g];
+		d.data = c.data;
+		d.valid = c.valid;
+		d.width = c.width;
+		d.is_signed = c.flags & 1u;
+		d.first_leaf = pl.cols[g].first_leaf;
+		d.n_leaves = pl.cols[g].n_leaves;
+		d.needs_cell = pl.cols[g].needs_cell;
+	}
+	px.values = (const PolrFxValue *)(p->scan_expr_prog + values_at);
+	px.leaves = (const PolrFxLeaf *)(p->scan_expr_prog + leaves_at);
+	px.segs = (const polr_like_seg *)(p->scan_expr_prog + segs_at);
+	px.bytes = p->scan_expr_prog + bytes_at;
+	if (p->scan_valid) {
+		HIPCHK(ctx, hipDeviceSynchronize()); // (runs of the scan before may be in flight: see scan_filter_run)
+	}
+	const uint64_t n_rows = p->n_probe_rows;
+	const uint64_t n_vec = (n_rows + vector_size - 1) / vector_size;
+	const uint64_t n_blocks = (n_vec + 1023) / 1024;
+	if (n_vec >= (1ull << 23)) {
+		POLR_FAIL(ctx, POLR_E_UNSUPPORTED, "more than 2^23 scan vectors per partition");
+	}
+	if (int rc = scan_buffers(p, n_rows, n_vec, n_blocks)) {
+		return rc;
+	}
+	// the pass bits: one word per 64-row step of a vector
+	const uint64_t n_words = n_vec * (((uint64_t)vector_size + 63) / 64);
+	if (p->scan_pass_cap < n_words) {
+		if (p->scan_pass_bits) {
+			hipFree(p->scan_pass_bits);
+			p->scan_pass_bits = nullptr;
+			p->scan_pass_cap = 0;
+		}
+		HIPCHK(ctx, hipMalloc((void **)&p->scan_pass_bits, n_words * 8));
+		p->scan_pass_cap = n_words;
+	}
+	unsigned long long *packed = p->scan_packed, *sums = p->scan_sums, *totals = p->scan_totals;
+	uint64_t h_tot[2] = {0, 0};
+	hipError_t e = hipSuccess;
+	if (n_vec) {
+		const uint32_t waves_per_block = 4;
+		const uint32_t grid = (uint32_t)std::min<uint64_t>((n_vec + waves_per_block - 1) / waves_per_block,
+		                                                   (uint64_t)ctx->n_cus * 8);
+		hipLaunchKernelGGL(polr_tscan_count_expr_kernel, dim3(grid), dim3(256), 0, st, px, lip, n_rows, vector_size, n_vec, packed,
+		                   p->scan_pass_bits);
+		hipLaunchKernelGGL(polr_tscan_block_sums_kernel, dim3((uint32_t)n_blocks), dim3(1024), 0, st, packed, n_vec, sums);
+		hipLaunchKernelGGL(polr_tscan_sums_kernel, dim3(1), dim3(1024), 0, st, sums, n_blocks, totals);
+		hipLaunchKernelGGL(polr_tscan_apply_kernel, dim3((uint32_t)n_blocks), dim3(1024), 0, st, packed, n_vec, sums);
+		hipLaunchKernelGGL(polr_tscan_write_bits_kernel, dim3(grid), dim3(256), 0, st, (const unsigned long long *)p->scan_pass_bits,
+		                   n_rows, vector_size, n_vec, (const unsigned long long *)packed, p->scan_sel, p->scan_offsets_dev,
+		                   (const unsigned long long *)totals);
+		e = hipMemcpyAsync(h_tot, totals, 16, hipMemcpyDeviceToHost, st);
+		e = e == hipSuccess ? hipStreamSynchronize(st) : e;
+	} else {
+		e = hipMemsetAsync(p->scan_offsets_dev, 0, 8, st);
+		e = e == hipSuccess ? hipStreamSynchronize(st) : e;
+	}
+	if (e != hipSuccess) {
+		POLR_FAIL(ctx, POLR_E_HIP, "scan filter failed: %s", hipGetErrorString(e));
+	}
+	return scan_install(p, vector_size, h_tot, n_selected, n_chunks);
 }
 
 extern "C" {
+
+int polr_pipeline_scan_filter_expr(polr_pipeline *p, void *stream, const polr_filter_node *nodes, uint32_t n_nodes,
+                                   const polr_filter_value *values, uint32_t n_values, uint32_t lip_joins,
+                                   uint32_t vector_size, uint64_t *n_selected, uint64_t *n_chunks) {
+	POLR_ENTRY();
+	if (!p) {
+		return POLR_E_INVALID;
+	}
+	return scan_filter_expr_run(p, stream, nodes, n_nodes, values, n_values, lip_joins, vector_size, n_selected, n_chunks);
+}
+
 
 int polr_pipeline_fetch_scan(polr_pipeline *p, uint32_t *sel, uint64_t *chunk_offsets) {
 	POLR_ENTRY();

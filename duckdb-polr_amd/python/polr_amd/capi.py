@@ -43,6 +43,7 @@ EXPORTS = [
     "polr_out_aggregate_expr", "polr_out_aggregate_grouped_expr", "polr_out_aggregate_hashed_expr",
     "polr_mpx_run_resident_stealing", "polr_mpx_steal_stats",
     "polr_pipeline_scan_filter_str",
+    "polr_pipeline_scan_filter_expr",
 ]
 
 
@@ -88,6 +89,19 @@ class ScanFilterStr(C.Structure):
                 ("str_len", C.c_uint64)]
 
 
+class FilterValue(C.Structure):
+    """polr_filter_value"""
+    _fields_ = [("constant", C.c_int64), ("str", C.c_void_p), ("str_len", C.c_uint64)]
+
+
+class FilterNode(C.Structure):
+    """polr_filter_node"""
+    _fields_ = [("kind", C.c_uint32), ("col", C.c_uint32), ("op", C.c_uint32), ("first_value", C.c_uint32),
+                ("n_values", C.c_uint32), ("pad", C.c_uint32)]
+
+
+FX = {"cmp": 0, "in": 1, "like": 2, "not": 3, "and": 4, "or": 5}  # POLR_FX_*
+MAX_FILTER_NODES, MAX_FILTER_DEPTH, MAX_FILTER_VALUES, MAX_FILTER_BYTES = 64, 32, 64, 16384
 CMP = {"=": 0, "==": 0, "!=": 1, "<>": 1, "<": 2, ">": 3, "<=": 4, ">=": 5, "is null": 6, "is not null": 7}
 MAX_FILTER_STRING = 4096  # POLR_MAX_FILTER_STRING
 
@@ -108,6 +122,55 @@ def like_pushdown(pattern):
     if prefix[-1] == 0xFF:
         raise ValueError("a LIKE prefix that ends in 0xFF has no upper bound one byte up (not UTF-8)")
     return [(">=", prefix), ("<", prefix[:-1] + bytes([prefix[-1] + 1])), ("is not null", None)]
+
+
+def flatten_filter_expr(expr):
+    """a nested filter expression (Pipeline.scan_filter_expr) -> (nodes, values) in postfix order, as
+    Pipeline.scan_filter_expr_raw takes them"""
+    nodes, values = [], []
+
+    def value(c):
+        if isinstance(c, (bytes, bytearray, str)):
+            b = c.encode() if isinstance(c, str) else bytes(c)
+            values.append((0, b, len(b)))
+        else:
+            values.append((int(c), None, 0))
+
+    def walk(e):
+        kind = e[0]
+        if kind in ("and", "or"):
+            if len(e) < 3:
+                raise ValueError("%s takes two or more operands" % kind)
+            walk(e[1])
+            for operand in e[2:]:
+                walk(operand)
+                nodes.append((kind, 0, 0, 0, 0))
+        elif kind == "not":
+            walk(e[1])
+            nodes.append(("not", 0, 0, 0, 0))
+        elif kind == "cmp":
+            col, op, const = e[1], e[2], e[3] if len(e) > 3 else None  # (IS [NOT] NULL takes no constant)
+            code = CMP[op] if isinstance(op, str) else op
+            if code >= CMP["is null"]:
+                nodes.append(("cmp", col, code, 0, 0))
+            else:
+                nodes.append(("cmp", col, code, len(values), 1))
+                value(const)
+        elif kind == "in":
+            _, col, members = e
+            nodes.append(("in", col, 0, len(values), len(members)))
+            for m in members:
+                value(m)
+        elif kind == "like":
+            _, col, pattern = e
+            nodes.append(("like", col, 0, len(values), 1))
+            value(pattern)
+        else:
+            raise ValueError("unknown filter expression node %r" % (kind,))
+
+    if expr is not None:
+        walk(expr)
+    return nodes, values
 
 
 class HeapRange(C.Structure):
@@ -291,6 +354,7 @@ def load():
     L.polr_pipeline_scan_filter.argtypes = [vp, vp, vp, u32, u32, vp, vp]
     L.polr_pipeline_scan_filter_lip.argtypes = [vp, vp, vp, u32, u32, u32, vp, vp]
     L.polr_pipeline_scan_filter_str.argtypes = [vp, vp, vp, u32, u32, u32, vp, vp]
+    L.polr_pipeline_scan_filter_expr.argtypes = [vp, vp, vp, u32, vp, u32, u32, u32, vp, vp]
     L.polr_pipeline_fetch_scan.argtypes = [vp, vp, vp]
     L.polr_mpx_use_scan_chunks.argtypes = [vp]
     L.polr_out_aggregate.argtypes = [vp, vp, vp, u32, vp]
@@ -671,6 +735,35 @@ class Pipeline:
         ns, nc = C.c_uint64(), C.c_uint64()
         self.ctx.check(self.ctx.L.polr_pipeline_scan_filter_str(self.h, stream, arr if n else None, n, int(lip_joins),
                                                                 vector_size, C.byref(ns), C.byref(nc)))
+        self.scan = (ns.value, nc.value)
+        return self.scan
+
+    def scan_filter_expr(self, expr, vector_size=1024, stream=None, lip_joins=0):
+        """polr_pipeline_scan_filter_expr: expr is a nested tuple -- ("and" | "or", a, b, ...), ("not", a), and the leaves
+        ("cmp", col, op, constant), ("in", col, [members]), ("like", col, pattern); a bytes / str constant is a VARCHAR
+        one; None: every row passes.  Flattened to postfix (an "and" / "or" of more than two operands left to right);
+        sets self.scan and returns it."""
+        nodes, values = flatten_filter_expr(expr)
+        return self.scan_filter_expr_raw(nodes, values, vector_size, stream, lip_joins)
+
+    def scan_filter_expr_raw(self, nodes, values, vector_size=1024, stream=None, lip_joins=0, n_nodes=None, n_values=None):
+        """polr_pipeline_scan_filter_expr with the struct fields as given: nodes = [(kind, col, op, first_value,
+        n_values)], values = [(constant, bytes or None, str_len)]; n_nodes / n_values: the counts to pass, when they are
+        not the lists' lengths -- the edges of the contract"""
+        na, va, keep = (FilterNode * max(len(nodes), 1))(), (FilterValue * max(len(values), 1))(), []
+        for i, (kind, col, op, first, n) in enumerate(nodes):
+            na[i].kind, na[i].col, na[i].op = FX[kind] if isinstance(kind, str) else kind, col, CMP[op] if isinstance(op, str) else op
+            na[i].first_value, na[i].n_values = first, n
+        for i, (const, b, blen) in enumerate(values):
+            va[i].constant, va[i].str_len = int(const or 0), blen
+            if b is not None:
+                buf = C.create_string_buffer(bytes(b), max(len(b), 1))
+                keep.append(buf)
+                va[i].str = C.addressof(buf)
+        ns, nc = C.c_uint64(), C.c_uint64()
+        self.ctx.check(self.ctx.L.polr_pipeline_scan_filter_expr(
+            self.h, stream, na if nodes else None, len(nodes) if n_nodes is None else n_nodes, va if values else None,
+            len(values) if n_values is None else n_values, int(lip_joins), vector_size, C.byref(ns), C.byref(nc)))
         self.scan = (ns.value, nc.value)
         return self.scan
 

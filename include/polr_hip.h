@@ -314,7 +314,8 @@ int polr_pipeline_scan_filter_lip(polr_pipeline *p, void *stream, const polr_sca
  *    bytes, reading length words only, and any such cell is POLR_E_INVALID before a kernel that follows a pointer is
  *    enqueued.  The cells of a POLR_COL_DEVICE column point into HBM by contract.
  *  - A refused call enqueues no scan and leaves the scan result before it in place.
- * OR-conjunctions, IN lists, LIKE beyond the pushed prefix range and collations stay with the engine's own filter. */
+ * OR-conjunctions, IN lists and LIKE beyond the pushed prefix range: polr_pipeline_scan_filter_expr below; collations
+ * stay with the engine's own filter. */
 #define POLR_MAX_FILTER_STRING 4096
 typedef struct polr_scan_filter_str {
 	uint32_t col;      /* probe-table column */
@@ -325,6 +326,64 @@ typedef struct polr_scan_filter_str {
 } polr_scan_filter_str;
 int polr_pipeline_scan_filter_str(polr_pipeline *p, void *stream, const polr_scan_filter_str *filters, uint32_t n_filters,
                                   uint32_t lip_joins, uint32_t vector_size, uint64_t *n_selected, uint64_t *n_chunks);
+/* The same scan with a whole boolean expression over the probe table's columns: what the reference evaluates in a
+ * PhysicalFilter between the table scan and the first multiplexed join (OR-conjunctions, NOT, IN lists, LIKE beyond the
+ * pushed prefix range).  The expression arrives in postfix order: a leaf (POLR_FX_CMP, _IN, _LIKE) pushes one value,
+ * POLR_FX_NOT replaces the top, POLR_FX_AND / _OR pop two and push one; it must leave exactly one value.  n_nodes == 0:
+ * every row passes.
+ *  - SQL three-valued logic, as the reference's ExpressionExecutor evaluates a WHERE: NOT NULL = NULL; NULL AND FALSE =
+ *    FALSE, NULL AND TRUE = NULL; NULL OR TRUE = TRUE, NULL OR FALSE = NULL.  A row passes when the root is TRUE, not when
+ *    it is NULL.  A CMP, IN or LIKE leaf on a NULL row is NULL and the row's cell is never read; IS NULL / IS NOT NULL read
+ *    the validity only and are never NULL.
+ *  - POLR_FX_CMP is exactly one filter of polr_pipeline_scan_filter_str: an integer column compares `constant`, a column of
+ *    16-byte string cells compares the string (csrc/polr_strcmp.h).  n_values 1; 0 for IS [NOT] NULL.
+ *  - POLR_FX_IN is true when the row's value equals one of its n_values >= 1 members: integer members as CMP EQ compares,
+ *    VARCHAR members in length and every byte.  A NULL member is not offered; NOT IN is POLR_FX_NOT over it.  (The
+ *    reference turns an IN list of fewer than 6 members into an OR of equalities and a longer constant list into a MARK
+ *    join in front of the filter, src/optimizer/in_clause_rewriter.cpp:42-106: this leaf stands for both.)
+ *  - POLR_FX_LIKE (16-byte string cells only) matches the row's string against the pattern values[first_value], in bytes:
+ *    '%' matches any run of bytes, none included; '_' exactly one BYTE (TemplatedLikeOperator advances one byte,
+ *    src/function/scalar/string/like.cpp:22-65); every other byte matches itself.  There is no ESCAPE clause: a backslash
+ *    is an ordinary byte, and a pattern that holds a '\0' byte -- the escape character the reference binds a LIKE without
+ *    ESCAPE with -- is POLR_E_UNSUPPORTED.  NOT LIKE is POLR_FX_NOT over it.  This covers what the reference's optimizer
+ *    turns into contains, suffix, prefix and =; ILIKE, ESCAPE, SIMILAR TO and regular expressions stay with the engine.
+ *  - lip_joins, vector_size, stream, n_selected, n_chunks, row order, skipped empty vectors, chunk boundaries, the
+ *    installation as the pipeline's source, polr_pipeline_fetch_scan and the settling against the scan before or after are
+ *    those of polr_pipeline_scan_filter_str; so are the heaps: a column the library uploaded whose heap never came and that
+ *    holds a non-NULL cell longer than 12 bytes is POLR_E_INVALID from the pass over the length words, before a kernel that
+ *    follows a pointer is enqueued (only columns some CMP, IN or LIKE leaf reads are looked at).
+ *  - POLR_E_INVALID: stack underflow, more or fewer than one value left, an unknown kind or op; a value range outside
+ *    `values`; col beyond the probe columns; str != NULL against an integer column, str == NULL with str_len > 0; LIKE on
+ *    an integer column or with n_values != 1; IN with n_values == 0; CMP with another n_values than above; a negative
+ *    constant against an unsigned column; and everything polr_pipeline_scan_filter_lip refuses so.
+ *    POLR_E_UNSUPPORTED: more than POLR_MAX_FILTER_NODES nodes, an operand stack deeper than POLR_MAX_FILTER_DEPTH, more
+ *    than POLR_MAX_FILTER_VALUES values, more than POLR_MAX_FILTER_BYTES bytes of VARCHAR constants and patterns together,
+ *    one constant longer than POLR_MAX_FILTER_STRING, more than 8 distinct columns, a NUL byte in a pattern.
+ *  - A refused call enqueues nothing and leaves the scan result before it in place.  nodes, values and the values' bytes
+ *    are host memory and are copied by the call.
+ * Every row's expression is evaluated once: the counting pass keeps one bit per table row in a buffer of the pipeline
+ * (allocated by the first such call), the writing pass reads those bits. */
+#define POLR_MAX_FILTER_NODES 64    /* nodes of one expression */
+#define POLR_MAX_FILTER_DEPTH 32    /* operand stack depth the postfix order may reach */
+#define POLR_MAX_FILTER_VALUES 64   /* constants of one call (comparison constants, IN members, patterns) */
+#define POLR_MAX_FILTER_BYTES 16384 /* bytes of all VARCHAR constants and patterns of one call together */
+enum { POLR_FX_CMP = 0, POLR_FX_IN = 1, POLR_FX_LIKE = 2, POLR_FX_NOT = 3, POLR_FX_AND = 4, POLR_FX_OR = 5 };
+typedef struct polr_filter_value {
+	int64_t constant; /* integer column: as polr_scan_filter */
+	const void *str;  /* VARCHAR column (width 16): the constant's / member's / pattern's bytes, as polr_scan_filter_str */
+	uint64_t str_len;
+} polr_filter_value;
+typedef struct polr_filter_node {
+	uint32_t kind;        /* POLR_FX_* */
+	uint32_t col;         /* leaves: probe-table column */
+	uint32_t op;          /* POLR_FX_CMP: POLR_CMP_EQ .. POLR_CMP_IS_NOT_NULL */
+	uint32_t first_value; /* leaves: values[first_value .. first_value + n_values) */
+	uint32_t n_values;    /* CMP: 1 (0 for IS [NOT] NULL); IN: 1 or more; LIKE: 1, the pattern */
+	uint32_t pad;
+} polr_filter_node;
+int polr_pipeline_scan_filter_expr(polr_pipeline *p, void *stream, const polr_filter_node *nodes, uint32_t n_nodes,
+                                   const polr_filter_value *values, uint32_t n_values, uint32_t lip_joins,
+                                   uint32_t vector_size, uint64_t *n_selected, uint64_t *n_chunks);
 /* read the scan result back (tests): sel[n_selected], chunk_offsets[n_chunks + 1]; either may be NULL */
 int polr_pipeline_fetch_scan(polr_pipeline *p, uint32_t *sel, uint64_t *chunk_offsets);
 /* Refresh the cells of probe column `col` in place (a new DataChunk arriving at the operator-level
