@@ -464,22 +464,17 @@ static int aggregate_ungrouped(polr_out *o, void *stream, SinkAggs &aggs, polr_a
 	std::vector<AggPartial> host((size_t)n_blocks * n_aggs);
 	SinkCounters cnt(aggs, 0);
 	if (o->n_chunks) {
-		AggPartial *part = nullptr;
-		HIPCHK(ctx, hipMalloc((void **)&part, host.size() * sizeof(AggPartial) + cnt.bytes())); // (the counters behind the partials)
+		DevBuf<uint8_t> mem; // the partials, and the counters behind them
+		HIPCHK(ctx, mem.alloc(host.size() * sizeof(AggPartial) + cnt.bytes()));
+		AggPartial *part = (AggPartial *)mem.get();
 		cnt.place((unsigned long long *)(part + host.size()), &aggs);
-		hipError_t e = cnt.zero(st);
-		if (e == hipSuccess) {
-			with_set(aggs, [&](const auto &set) {
-				hipLaunchKernelGGL(polr_agg_kernel, dim3(n_blocks), dim3(256), 0, st, o->dev, o->n_chunks, set, part);
-			});
-			e = cnt.fetch(st);
-		}
-		e = e == hipSuccess ? hipMemcpyAsync(host.data(), part, host.size() * sizeof(AggPartial), hipMemcpyDeviceToHost, st) : e;
-		e = e == hipSuccess ? hipStreamSynchronize(st) : e;
-		hipFree(part);
-		if (e != hipSuccess) {
-			POLR_FAIL(ctx, POLR_E_HIP, "aggregate failed: %s", hipGetErrorString(e));
-		}
+		HIPCHK(ctx, cnt.zero(st));
+		with_set(aggs, [&](const auto &set) {
+			hipLaunchKernelGGL(polr_agg_kernel, dim3(n_blocks), dim3(256), 0, st, o->dev, o->n_chunks, set, part);
+		});
+		HIPCHK(ctx, cnt.fetch(st));
+		HIPCHK(ctx, hipMemcpyAsync(host.data(), part, host.size() * sizeof(AggPartial), hipMemcpyDeviceToHost, st));
+		HIPCHK(ctx, hipStreamSynchronize(st));
 	}
 	rc = cnt.check_range(ctx, n_out_of_range);
 	if (rc) {
@@ -689,36 +684,27 @@ static int aggregate_grouped(polr_out *o, void *stream, const polr_group_key *ke
 	const uint32_t n_cells = (uint32_t)groups * n_aggs;
 	std::vector<GroupCell> host(n_cells);
 	SinkCounters cnt(aggs, 1); // [0] dropped rows
-	GroupCell *table = nullptr;
-	unsigned long long *dropped = nullptr;
-	hipError_t e = hipMalloc((void **)&table, (size_t)n_cells * sizeof(GroupCell));
-	e = e == hipSuccess ? hipMalloc((void **)&dropped, cnt.bytes()) : e;
+	DevBuf<GroupCell> table_mem;
+	DevBuf<uint8_t> dropped_mem;
+	HIPCHK(ctx, table_mem.alloc(n_cells));
+	HIPCHK(ctx, dropped_mem.alloc(cnt.bytes()));
+	GroupCell *table = table_mem;
+	unsigned long long *dropped = (unsigned long long *)dropped_mem.get();
 	cnt.place(dropped, &aggs);
-	e = e == hipSuccess ? cnt.zero(st) : e;
-	if (e == hipSuccess) {
-		hipLaunchKernelGGL(polr_group_init_kernel, dim3((n_cells + 255) / 256), dim3(256), 0, st, table, (uint64_t)n_cells);
-		if (o->n_chunks) {
-			const int use_lds = n_cells <= POLR_GROUP_LDS_CELLS;
-			const uint32_t n_blocks = std::max<uint32_t>(1, std::min<uint32_t>(o->n_chunks, (uint32_t)ctx->n_cus * 4));
-			const size_t lds = use_lds ? (size_t)n_cells * sizeof(GroupCell) : 0;
-			with_set(aggs, [&](const auto &set) {
-				hipLaunchKernelGGL(polr_group_agg_kernel, dim3(n_blocks), dim3(256), lds, st, o->dev, o->n_chunks, gs, set, table, dropped,
-				                   use_lds);
-			});
-		}
-		e = hipMemcpyAsync(host.data(), table, (size_t)n_cells * sizeof(GroupCell), hipMemcpyDeviceToHost, st);
-		e = e == hipSuccess ? cnt.fetch(st) : e;
-		e = e == hipSuccess ? hipStreamSynchronize(st) : e;
+	HIPCHK(ctx, cnt.zero(st));
+	hipLaunchKernelGGL(polr_group_init_kernel, dim3((n_cells + 255) / 256), dim3(256), 0, st, table, (uint64_t)n_cells);
+	if (o->n_chunks) {
+		const int use_lds = n_cells <= POLR_GROUP_LDS_CELLS;
+		const uint32_t n_blocks = std::max<uint32_t>(1, std::min<uint32_t>(o->n_chunks, (uint32_t)ctx->n_cus * 4));
+		const size_t lds = use_lds ? (size_t)n_cells * sizeof(GroupCell) : 0;
+		with_set(aggs, [&](const auto &set) {
+			hipLaunchKernelGGL(polr_group_agg_kernel, dim3(n_blocks), dim3(256), lds, st, o->dev, o->n_chunks, gs, set, table, dropped,
+			                   use_lds);
+		});
 	}
-	if (table) {
-		hipFree(table);
-	}
-	if (dropped) {
-		hipFree(dropped);
-	}
-	if (e != hipSuccess) {
-		POLR_FAIL(ctx, POLR_E_HIP, "grouped aggregate failed: %s", hipGetErrorString(e));
-	}
+	HIPCHK(ctx, hipMemcpyAsync(host.data(), table, (size_t)n_cells * sizeof(GroupCell), hipMemcpyDeviceToHost, st));
+	HIPCHK(ctx, cnt.fetch(st));
+	HIPCHK(ctx, hipStreamSynchronize(st));
 	rc = cnt.check_range(ctx, n_out_of_range);
 	if (rc) {
 		return rc;
@@ -784,11 +770,9 @@ extern "C" int polr_out_fuse_grouped(polr_out *o, const polr_group_key *keys, ui
 	if (!keys || n_keys == 0) { // un-fuse: the output object collects row ids again
 		if (o->fused_dev) {
 			HIPCHK(ctx, hipDeviceSynchronize());
-			hipFree(o->fused_dev);
-			hipFree(o->fused_cells);
-			hipFree(o->fused_dropped);
-			o->fused_dev = nullptr;
-			o->fused_cells = o->fused_dropped = nullptr;
+			o->fused_dev.reset();
+			o->fused_cells.reset();
+			o->fused_dropped.reset();
 			o->dev.fused = nullptr;
 		}
 		return POLR_OK;
@@ -842,23 +826,21 @@ extern "C" int polr_out_fuse_grouped(polr_out *o, const polr_group_key *keys, ui
 	fs.n_tables = POLR_FUSED_TABLES;
 	fs.words_per_table = words;
 	const size_t bytes = (size_t)(POLR_FUSED_TABLES + 1u) * words * 8u; // (+ 1: where the read-out sums the tables)
-	hipError_t e = hipMalloc((void **)&o->fused_cells, bytes);
-	e = e == hipSuccess ? hipMalloc((void **)&o->fused_dropped, 8) : e;
-	e = e == hipSuccess ? hipMalloc((void **)&o->fused_dev, sizeof(FusedSink)) : e;
-	fs.cells = o->fused_cells;
-	fs.dropped = o->fused_dropped;
-	e = e == hipSuccess ? hipMemsetAsync(o->fused_cells, 0, bytes, ctx->stream) : e;
-	e = e == hipSuccess ? hipMemsetAsync(o->fused_dropped, 0, 8, ctx->stream) : e;
-	e = e == hipSuccess ? hipMemcpyAsync(o->fused_dev, &fs, sizeof(fs), hipMemcpyHostToDevice, ctx->stream) : e;
-	e = e == hipSuccess ? hipStreamSynchronize(ctx->stream) : e;
-	if (e != hipSuccess) { // (nothing half-made stays behind)
-		hipFree(o->fused_cells);
-		hipFree(o->fused_dropped);
-		hipFree(o->fused_dev);
-		o->fused_cells = o->fused_dropped = nullptr;
-		o->fused_dev = nullptr;
-		POLR_FAIL(ctx, POLR_E_HIP, "fused sink: %s", hipGetErrorString(e));
-	}
+	// built in locals and moved into the output at the point of success: nothing half-made stays behind
+	DevBuf<unsigned long long> cells, dropped;
+	DevBuf<FusedSink> dev;
+	HIPCHK(ctx, cells.alloc(bytes / 8));
+	HIPCHK(ctx, dropped.alloc(1));
+	HIPCHK(ctx, dev.alloc(1));
+	fs.cells = cells;
+	fs.dropped = dropped;
+	HIPCHK(ctx, hipMemsetAsync(cells, 0, bytes, ctx->stream));
+	HIPCHK(ctx, hipMemsetAsync(dropped, 0, 8, ctx->stream));
+	HIPCHK(ctx, hipMemcpyAsync(dev, &fs, sizeof(fs), hipMemcpyHostToDevice, ctx->stream));
+	HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+	o->fused_cells = std::move(cells);
+	o->fused_dropped = std::move(dropped);
+	o->fused_dev = std::move(dev);
 	o->fused_tables = POLR_FUSED_TABLES;
 	o->fused_groups = (uint32_t)groups;
 	o->fused_aggs = n_aggs;
@@ -1090,22 +1072,17 @@ __global__ __launch_bounds__(256) void polr_count_long_cells_kernel(DevOut out, 
 // POLR_OK when the column may be read by a kernel that follows string pointers
 static int check_string_col_on_device(polr_out *o, hipStream_t st, const OutCol &c, const char *what, uint32_t idx) {
 	polr_ctx *ctx = o->pipe->ctx;
-	if (c.col->strings_rebased || !c.col->owned || o->n_chunks == 0) {
+	if (c.col->strings_rebased || !c.col->owned() || o->n_chunks == 0) {
 		return POLR_OK; // (rebased here; or the caller's own device memory, whose cells point into HBM by contract)
 	}
-	unsigned long long *n_long = nullptr, h_long = 0;
-	HIPCHK(ctx, hipMalloc((void **)&n_long, 8));
-	hipError_t e = hipMemsetAsync(n_long, 0, 8, st);
-	if (e == hipSuccess) {
-		const uint32_t n_blocks = std::max<uint32_t>(1, std::min<uint32_t>(o->n_chunks, (uint32_t)ctx->n_cus * 4));
-		hipLaunchKernelGGL(polr_count_long_cells_kernel, dim3(n_blocks), dim3(256), 0, st, o->dev, o->n_chunks, c.dev, c.slot, n_long);
-		e = hipMemcpyAsync(&h_long, n_long, 8, hipMemcpyDeviceToHost, st);
-		e = e == hipSuccess ? hipStreamSynchronize(st) : e;
-	}
-	hipFree(n_long);
-	if (e != hipSuccess) {
-		POLR_FAIL(ctx, POLR_E_HIP, "string column check failed: %s", hipGetErrorString(e));
-	}
+	DevBuf<unsigned long long> n_long;
+	unsigned long long h_long = 0;
+	HIPCHK(ctx, n_long.alloc(1));
+	HIPCHK(ctx, hipMemsetAsync(n_long, 0, 8, st));
+	const uint32_t n_blocks = std::max<uint32_t>(1, std::min<uint32_t>(o->n_chunks, (uint32_t)ctx->n_cus * 4));
+	hipLaunchKernelGGL(polr_count_long_cells_kernel, dim3(n_blocks), dim3(256), 0, st, o->dev, o->n_chunks, c.dev, c.slot, n_long.get());
+	HIPCHK(ctx, hipMemcpyAsync(&h_long, n_long, 8, hipMemcpyDeviceToHost, st));
+	HIPCHK(ctx, hipStreamSynchronize(st));
 	if (h_long) {
 		POLR_FAIL(ctx, POLR_E_INVALID,
 		          "%s %u: %llu output rows hold strings longer than 12 bytes, but the column's heap was never put on the device "
@@ -1118,7 +1095,7 @@ static int check_string_col_on_device(polr_out *o, hipStream_t st, const OutCol 
 // all or nothing: the ranges are checked, copied and every cell validated before any cell is rewritten; on an error the
 // column is as it was and no device memory is kept
 static int set_string_heaps(polr_ctx *ctx, OwnedCol *c, uint64_t n_rows, const polr_heap_range *ranges, uint32_t n_ranges,
-                            std::vector<void *> &owner) {
+                            std::vector<DevBuf<uint8_t>> &owner) {
 	if (!ranges || n_ranges == 0) {
 		POLR_FAIL(ctx, POLR_E_INVALID, "a string heap needs at least one range");
 	}
@@ -1153,47 +1130,35 @@ static int set_string_heaps(polr_ctx *ctx, OwnedCol *c, uint64_t n_rows, const p
 		at += x.bytes;
 	}
 	HIPCHK(ctx, hipSetDevice(ctx->device));
-	uint8_t *heap = nullptr;
-	HeapRange *d_ranges = nullptr;
-	unsigned long long *outside = nullptr;
-	hipError_t e = hipMalloc((void **)&heap, total);
-	e = e == hipSuccess ? hipMalloc((void **)&d_ranges, n_ranges * sizeof(HeapRange)) : e;
-	e = e == hipSuccess ? hipMalloc((void **)&outside, 8) : e;
-	for (uint32_t r = 0; r < n_ranges && e == hipSuccess; r++) {
-		e = hipMemcpyAsync(heap + hr[r].dev_base, (const void *)hr[r].host_base, hr[r].bytes, hipMemcpyHostToDevice, ctx->stream);
-		hr[r].dev_base += (uint64_t)heap;
+	DevBuf<uint8_t> heap;
+	DevBuf<HeapRange> d_ranges;
+	DevBuf<unsigned long long> outside;
+	HIPCHK(ctx, heap.alloc(total));
+	HIPCHK(ctx, d_ranges.alloc(n_ranges));
+	HIPCHK(ctx, outside.alloc(1));
+	for (uint32_t r = 0; r < n_ranges; r++) {
+		HIPCHK(ctx, hipMemcpyAsync(heap + hr[r].dev_base, (const void *)hr[r].host_base, hr[r].bytes, hipMemcpyHostToDevice, ctx->stream));
+		hr[r].dev_base += (uint64_t)heap.get();
 	}
-	e = e == hipSuccess ? hipMemcpyAsync(d_ranges, hr.data(), n_ranges * sizeof(HeapRange), hipMemcpyHostToDevice, ctx->stream) : e;
-	e = e == hipSuccess ? hipMemsetAsync(outside, 0, 8, ctx->stream) : e;
+	HIPCHK(ctx, hipMemcpyAsync(d_ranges, hr.data(), n_ranges * sizeof(HeapRange), hipMemcpyHostToDevice, ctx->stream));
+	HIPCHK(ctx, hipMemsetAsync(outside, 0, 8, ctx->stream));
 	const dim3 grid((unsigned)((n_rows + 255) / 256));
-	if (e == hipSuccess && n_rows) {
-		hipLaunchKernelGGL(polr_rebase_strings_kernel, grid, dim3(256), 0, ctx->stream, (uint4 *)c->data, c->valid, n_rows, d_ranges,
-		                   n_ranges, 0, outside);
+	if (n_rows) {
+		hipLaunchKernelGGL(polr_rebase_strings_kernel, grid, dim3(256), 0, ctx->stream, (uint4 *)c->data, c->valid, n_rows,
+		                   d_ranges.get(), n_ranges, 0, outside.get());
 	}
 	unsigned long long bad = 0;
-	e = e == hipSuccess ? hipMemcpyAsync(&bad, outside, 8, hipMemcpyDeviceToHost, ctx->stream) : e;
-	e = e == hipSuccess ? hipStreamSynchronize(ctx->stream) : e;
-	if (e == hipSuccess && !bad && n_rows) {
-		hipLaunchKernelGGL(polr_rebase_strings_kernel, grid, dim3(256), 0, ctx->stream, (uint4 *)c->data, c->valid, n_rows, d_ranges,
-		                   n_ranges, 1, outside);
-		e = hipStreamSynchronize(ctx->stream);
-	}
-	if (d_ranges) {
-		hipFree(d_ranges);
-	}
-	if (outside) {
-		hipFree(outside);
-	}
-	if (e != hipSuccess || bad) {
-		if (heap) {
-			hipFree(heap);
-		}
-		if (e != hipSuccess) {
-			POLR_FAIL(ctx, POLR_E_HIP, "string heap upload failed: %s", hipGetErrorString(e));
-		}
+	HIPCHK(ctx, hipMemcpyAsync(&bad, outside, 8, hipMemcpyDeviceToHost, ctx->stream));
+	HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+	if (bad) {
 		POLR_FAIL(ctx, POLR_E_INVALID, "%llu non-NULL string cells point outside the heap ranges given for their column", bad);
 	}
-	owner.push_back(heap);
+	if (n_rows) {
+		hipLaunchKernelGGL(polr_rebase_strings_kernel, grid, dim3(256), 0, ctx->stream, (uint4 *)c->data, c->valid, n_rows,
+		                   d_ranges.get(), n_ranges, 1, outside.get());
+		HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+	}
+	owner.push_back(std::move(heap)); // (only now: a refused call keeps nothing)
 	c->strings_rebased = true;
 	return POLR_OK;
 }
@@ -1222,7 +1187,7 @@ int polr_pipeline_set_probe_heaps(polr_pipeline *p, uint32_t probe_col, const po
 	if (!p || probe_col >= p->n_probe_cols) {
 		return POLR_E_INVALID;
 	}
-	if (!p->probe_cols[probe_col].owned) {
+	if (!p->probe_cols[probe_col].owned()) {
 		POLR_FAIL(p->ctx, POLR_E_INVALID, "probe column %u lives in the caller's device memory: its cells must point into HBM already",
 		          probe_col);
 	}
@@ -1270,8 +1235,9 @@ int polr_out_aggregate_string(polr_out *o, void *stream, uint32_t fn, int32_t sr
 		return rc;
 	}
 	const uint32_t n_blocks = std::max<uint32_t>(1, std::min<uint32_t>(o->n_chunks, (uint32_t)ctx->n_cus * 4));
-	StrPartial *part = nullptr;
-	HIPCHK(ctx, hipMalloc((void **)&part, ((size_t)n_blocks + 1) * sizeof(StrPartial)));
+	DevBuf<StrPartial> part_mem;
+	HIPCHK(ctx, part_mem.alloc((size_t)n_blocks + 1));
+	StrPartial *part = part_mem;
 	hipLaunchKernelGGL(polr_agg_string_kernel, dim3(n_blocks), dim3(256), 0, st, o->dev, o->n_chunks, c.dev, c.slot,
 	                   fn == POLR_AGG_MAX ? 1 : 0, (const StrPartial *)nullptr, 0u, part);
 	hipLaunchKernelGGL(polr_agg_string_kernel, dim3(1), dim3(256), 0, st, o->dev, 0u, c.dev, c.slot, fn == POLR_AGG_MAX ? 1 : 0,
@@ -1290,7 +1256,6 @@ int polr_out_aggregate_string(polr_out *o, void *stream, uint32_t fn, int32_t sr
 			e = hipMemcpy(dst, (const void *)(((uint64_t)win.cell.w << 32) | win.cell.z), take, hipMemcpyDeviceToHost);
 		}
 	}
-	hipFree(part);
 	if (e != hipSuccess) {
 		POLR_FAIL(ctx, POLR_E_HIP, "string aggregate failed: %s", hipGetErrorString(e));
 	}
@@ -1645,8 +1610,8 @@ static int aggregate_hashed(polr_out *o, void *stream, const polr_group_key *col
 	             b_okeys = (max_groups * n_cols * 8 + 15) & ~(size_t)15, // (the uint4 cells behind it stay 16-byte aligned)
 	             b_oreps = max_groups * n_cols * rep_bytes, b_onulls = (max_groups * 4 + 15) & ~(size_t)15,
 	             b_ocells = max_groups * n_aggs * sizeof(GroupCell);
-	uint8_t *base = nullptr;
-	HIPCHK(ctx, hipMalloc((void **)&base, b_state + b_nulls + b_cnt + b_keys + b_reps + b_cells + b_okeys + b_oreps + b_onulls + b_ocells));
+	DevBuf<uint8_t> base;
+	HIPCHK(ctx, base.alloc(b_state + b_nulls + b_cnt + b_keys + b_reps + b_cells + b_okeys + b_oreps + b_onulls + b_ocells));
 	uint8_t *at = base;
 	t.state = (uint32_t *)at;
 	at += b_state;
@@ -1722,22 +1687,18 @@ static int aggregate_hashed(polr_out *o, void *stream, const polr_group_key *col
 			}
 		}
 	}
-	uint8_t *arena = nullptr;
+	DevBuf<uint8_t> arena;
 	if (e == hipSuccess && g_n && used && used <= str_cap) {
-		e = hipMalloc((void **)&arena, used);
+		e = arena.alloc(used);
 		e = e == hipSuccess ? hipMemcpyAsync(okeys, hkeys, g_n * n_cols * 8, hipMemcpyHostToDevice, st) : e;
 		if (e == hipSuccess) {
 			const uint64_t n_rec = g_n * n_cols;
 			hipLaunchKernelGGL(polr_group_strings_kernel, dim3((unsigned)((n_rec + 255) / 256)), dim3(256), 0, st, (const uint4 *)oreps,
-			                   (const uint32_t *)onulls, (const long long *)okeys, g_n, n_cols, str_mask, arena, used);
+			                   (const uint32_t *)onulls, (const long long *)okeys, g_n, n_cols, str_mask, arena.get(), used);
 			e = hipMemcpyAsync(str_bytes, arena, used, hipMemcpyDeviceToHost, st);
 			e = e == hipSuccess ? hipStreamSynchronize(st) : e;
 		}
 	}
-	if (arena) {
-		hipFree(arena);
-	}
-	hipFree(base);
 	if (e != hipSuccess) {
 		POLR_FAIL(ctx, POLR_E_HIP, "hash aggregate failed: %s", hipGetErrorString(e));
 	}

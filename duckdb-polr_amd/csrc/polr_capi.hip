@@ -5,6 +5,7 @@
 #include <string.h>
 
 #include <algorithm>
+#include <memory>
 
 #include <stdlib.h>
 
@@ -30,6 +31,10 @@ extern "C" {
 
 int polr_abi_version(void) {
 	return POLR_ABI_VERSION;
+}
+
+uint64_t polr_device_bytes_live(void) {
+	return polr_devbuf_live_bytes.load(std::memory_order_relaxed);
 }
 
 int polr_ctx_create(int device_id, polr_ctx **out) {
@@ -152,19 +157,23 @@ static bool valid_width(uint32_t w) {
 	return w == 1 || w == 2 || w == 4 || w == 8 || w == 16;
 }
 
-static int dev_alloc(polr_ctx *ctx, void **p, uint64_t bytes, uint64_t *acct) {
-	*p = nullptr;
-	if (bytes == 0) {
-		bytes = 16;
+// what polr_ht_upload_* and the other functions that build a handle hold it in: POLR_FAIL / HIPCHK inside them then
+// destroy the half-built handle, and success hands it out with release()
+struct HandleDeleter {
+	void operator()(polr_ht *ht) const {
+		polr_ht_destroy(ht);
 	}
-	HIPCHK(ctx, hipMalloc(p, bytes));
-	if (acct) {
-		*acct += bytes;
+	void operator()(polr_pipeline *p) const {
+		polr_pipeline_destroy(p);
 	}
-	return POLR_OK;
-}
+	void operator()(polr_out *o) const {
+		polr_out_destroy(o);
+	}
+};
+template <class T>
+using HandleGuard = std::unique_ptr<T, HandleDeleter>;
 
-// copy (or alias) a caller column to the device
+// copy (or alias) a caller column to the device; acct: gains the bytes allocated
 static int ingest_col(polr_ctx *ctx, const polr_col *src, uint64_t n_rows, OwnedCol *dst, uint64_t *acct,
                       hipStream_t st) {
 	if (!valid_width(src->width)) {
@@ -178,22 +187,16 @@ static int ingest_col(polr_ctx *ctx, const polr_col *src, uint64_t n_rows, Owned
 	if (src->flags & POLR_COL_DEVICE) {
 		dst->data = (uint8_t *)src->data;
 		dst->valid = (uint8_t *)src->valid;
-		dst->owned = false;
 		return POLR_OK;
 	}
-	dst->owned = true;
-	int rc = dev_alloc(ctx, (void **)&dst->data, n_rows * src->width, acct);
-	if (rc) {
-		return rc;
-	}
+	HIPCHK(ctx, dst->alloc_data(n_rows * src->width));
+	*acct += dst->own_data.bytes();
 	if (n_rows) {
 		HIPCHK(ctx, hipMemcpyAsync(dst->data, src->data, n_rows * src->width, hipMemcpyHostToDevice, st));
 	}
 	if (src->valid) {
-		rc = dev_alloc(ctx, (void **)&dst->valid, n_rows, acct);
-		if (rc) {
-			return rc;
-		}
+		HIPCHK(ctx, dst->alloc_valid(n_rows));
+		*acct += dst->own_valid.bytes();
 		if (n_rows) {
 			HIPCHK(ctx, hipMemcpyAsync(dst->valid, src->valid, n_rows, hipMemcpyHostToDevice, st));
 		}
@@ -201,19 +204,7 @@ static int ingest_col(polr_ctx *ctx, const polr_col *src, uint64_t n_rows, Owned
 	return POLR_OK;
 }
 
-static void free_col(OwnedCol &c) {
-	if (c.owned) {
-		if (c.data) {
-			hipFree(c.data);
-		}
-		if (c.valid) {
-			hipFree(c.valid);
-		}
-	}
-	c.data = c.valid = nullptr;
-}
-
-static int upload_devcols(polr_ctx *ctx, const std::vector<OwnedCol> &cols, DevCol **dst, hipStream_t st) {
+static int upload_devcols(polr_ctx *ctx, const std::vector<OwnedCol> &cols, DevBuf<DevCol> *dst, hipStream_t st) {
 	std::vector<DevCol> h(cols.size() ? cols.size() : 1);
 	for (size_t i = 0; i < cols.size(); i++) {
 		h[i].data = cols[i].data;
@@ -221,10 +212,8 @@ static int upload_devcols(polr_ctx *ctx, const std::vector<OwnedCol> &cols, DevC
 		h[i].width = cols[i].width;
 		h[i].flags = cols[i].flags;
 	}
-	if (!*dst) {
-		HIPCHK(ctx, hipMalloc((void **)dst, h.size() * sizeof(DevCol)));
-	}
-	HIPCHK(ctx, hipMemcpyAsync(*dst, h.data(), h.size() * sizeof(DevCol), hipMemcpyHostToDevice, st));
+	HIPCHK(ctx, dst->ensure(h.size()));
+	HIPCHK(ctx, hipMemcpyAsync(dst->get(), h.data(), h.size() * sizeof(DevCol), hipMemcpyHostToDevice, st));
 	HIPCHK(ctx, hipStreamSynchronize(st)); // h is a stack-lifetime staging buffer
 	return POLR_OK;
 }
@@ -283,32 +272,23 @@ int polr_ht_upload_columns(polr_ctx *ctx, const polr_col *keys, uint32_t n_keys,
 		          (unsigned long long)n_rows);
 	}
 	HIPCHK(ctx, hipSetDevice(ctx->device));
-	polr_ht *ht = new polr_ht();
+	HandleGuard<polr_ht> ht(new polr_ht());
 	ht->ctx = polr_ctx_retain(ctx);
 	ht->n_keys = n_keys;
 	ht->n_payload = n_payload;
 	ht->n_rows_in = n_rows;
 	ht->keys.resize(n_keys);
 	ht->payload.resize(n_payload);
-	int rc = POLR_OK;
-	for (uint32_t i = 0; i < n_keys && !rc; i++) {
-		rc = ingest_col(ctx, &keys[i], n_rows, &ht->keys[i], &ht->device_bytes, ctx->stream);
+	for (uint32_t i = 0; i < n_keys; i++) {
+		POLR_TRY(ingest_col(ctx, &keys[i], n_rows, &ht->keys[i], &ht->device_bytes, ctx->stream));
 	}
-	for (uint32_t i = 0; i < n_payload && !rc; i++) {
-		rc = ingest_col(ctx, &payload[i], n_rows, &ht->payload[i], &ht->device_bytes, ctx->stream);
+	for (uint32_t i = 0; i < n_payload; i++) {
+		POLR_TRY(ingest_col(ctx, &payload[i], n_rows, &ht->payload[i], &ht->device_bytes, ctx->stream));
 	}
-	if (!rc) {
-		rc = check_key_shape(ctx, ht->keys);
-	}
-	if (!rc) {
-		ht->key_signed = ht->keys[0].flags & POLR_COL_SIGNED;
-		rc = upload_devcols(ctx, ht->keys, &ht->keys_dev, ctx->stream);
-	}
-	if (rc) {
-		polr_ht_destroy(ht);
-		return rc;
-	}
-	*out = ht;
+	POLR_TRY(check_key_shape(ctx, ht->keys));
+	ht->key_signed = ht->keys[0].flags & POLR_COL_SIGNED;
+	POLR_TRY(upload_devcols(ctx, ht->keys, &ht->keys_dev, ctx->stream));
+	*out = ht.release();
 	return POLR_OK;
 }
 
@@ -335,59 +315,34 @@ int polr_ht_upload_rows(polr_ctx *ctx, const void *rows, uint64_t n_rows, uint32
 		POLR_FAIL(ctx, POLR_E_INVALID, "row layout: validity bytes exceed row width");
 	}
 	HIPCHK(ctx, hipSetDevice(ctx->device));
-	polr_ht *ht = new polr_ht();
+	HandleGuard<polr_ht> ht(new polr_ht());
 	ht->ctx = polr_ctx_retain(ctx);
 	ht->n_keys = n_keys;
 	ht->n_payload = n_payload;
 	ht->n_rows_in = n_rows;
 	ht->keys.resize(n_keys);
 	ht->payload.resize(n_payload);
-	uint8_t *blob = nullptr;
-	int rc = dev_alloc(ctx, (void **)&blob, n_rows * row_width, nullptr);
-	if (!rc && n_rows) {
-		hipError_t e = hipMemcpyAsync(blob, rows, n_rows * row_width, hipMemcpyHostToDevice, ctx->stream);
-		if (e != hipSuccess) {
-			ctx->err = std::string("hipMemcpyAsync(rows) failed: ") + hipGetErrorString(e);
-			rc = POLR_E_HIP;
-		}
+	DevBuf<uint8_t> blob;
+	HIPCHK(ctx, blob.alloc(n_rows * row_width));
+	if (n_rows) {
+		HIPCHK(ctx, hipMemcpyAsync(blob, rows, n_rows * row_width, hipMemcpyHostToDevice, ctx->stream));
 	}
-	for (uint32_t c = 0; c < ncols && !rc; c++) {
+	for (uint32_t c = 0; c < ncols; c++) {
 		OwnedCol &col = c < n_keys ? ht->keys[c] : ht->payload[c - n_keys];
 		col.width = col_width[c];
 		col.flags = col_flags ? (col_flags[c] & POLR_COL_SIGNED) : 0;
-		col.owned = true;
-		rc = dev_alloc(ctx, (void **)&col.data, n_rows * col.width, &ht->device_bytes);
-		if (!rc) {
-			// (key columns too: a table whose condition is IS NOT DISTINCT FROM keeps its NULL-key rows, join_hashtable.cpp:182)
-			rc = dev_alloc(ctx, (void **)&col.valid, n_rows, &ht->device_bytes);
-		}
-		if (!rc) {
-			polr_launch_deserialize_col(ctx->stream, blob, n_rows, row_width, c, col_offset[c], col.width, col.data,
-			                            col.valid);
-		}
+		HIPCHK(ctx, col.alloc_data(n_rows * col.width));
+		// (key columns too: a table whose condition is IS NOT DISTINCT FROM keeps its NULL-key rows, join_hashtable.cpp:182)
+		HIPCHK(ctx, col.alloc_valid(n_rows));
+		ht->device_bytes += col.own_data.bytes() + col.own_valid.bytes();
+		polr_launch_deserialize_col(ctx->stream, blob, n_rows, row_width, c, col_offset[c], col.width, col.data,
+		                            col.valid);
 	}
-	if (!rc) {
-		hipError_t e = hipStreamSynchronize(ctx->stream);
-		if (e != hipSuccess) {
-			ctx->err = std::string("row de-serialisation failed: ") + hipGetErrorString(e);
-			rc = POLR_E_HIP;
-		}
-	}
-	if (blob) {
-		hipFree(blob);
-	}
-	if (!rc) {
-		rc = check_key_shape(ctx, ht->keys);
-	}
-	if (!rc) {
-		ht->key_signed = ht->keys[0].flags & POLR_COL_SIGNED;
-		rc = upload_devcols(ctx, ht->keys, &ht->keys_dev, ctx->stream);
-	}
-	if (rc) {
-		polr_ht_destroy(ht);
-		return rc;
-	}
-	*out = ht;
+	HIPCHK(ctx, hipStreamSynchronize(ctx->stream)); // (the row de-serialisation; blob is a local)
+	POLR_TRY(check_key_shape(ctx, ht->keys));
+	ht->key_signed = ht->keys[0].flags & POLR_COL_SIGNED;
+	POLR_TRY(upload_devcols(ctx, ht->keys, &ht->keys_dev, ctx->stream));
+	*out = ht.release();
 	return POLR_OK;
 }
 
@@ -419,7 +374,7 @@ int polr_ht_finalize_hash(polr_ht *ht, void *stream) {
 	HIPCHK(ctx, hipSetDevice(ctx->device));
 	hipStream_t st = polr_stream(ctx, stream);
 	const uint64_t n = ht->n_rows_in;
-	ht->pack = KeyPack();
+	KeyPack pack = KeyPack(); // (built here, stored with everything else once the build has succeeded)
 	if (needs_key_pack(ht)) {
 		// per-column [min, max] of the build keys (rows with a NULL key never match and do not count)
 		long long h_mm[2 * POLR_NKEYS];
@@ -427,50 +382,39 @@ int polr_ht_finalize_hash(polr_ht *ht, void *stream) {
 			h_mm[2 * c] = 0x7FFFFFFFFFFFFFFFll;
 			h_mm[2 * c + 1] = -0x7FFFFFFFFFFFFFFFll - 1;
 		}
-		long long *mm = nullptr;
-		int rc0 = dev_alloc(ctx, (void **)&mm, sizeof(h_mm), nullptr);
-		if (rc0) {
-			return rc0;
+		DevBuf<long long> mm;
+		HIPCHK(ctx, mm.alloc(2 * POLR_NKEYS));
+		HIPCHK(ctx, hipMemcpyAsync(mm, h_mm, sizeof(h_mm), hipMemcpyHostToDevice, st));
+		uint32_t null_eq = 0;
+		for (uint32_t c = 0; c < ht->n_keys; c++) {
+			null_eq |= (ht->key_flags[c] & POLR_KEY_NULL_EQUAL) ? (1u << c) : 0u;
 		}
-		hipError_t e = hipMemcpyAsync(mm, h_mm, sizeof(h_mm), hipMemcpyHostToDevice, st);
-		if (e == hipSuccess) {
-			uint32_t null_eq = 0;
-			for (uint32_t c = 0; c < ht->n_keys; c++) {
-				null_eq |= (ht->key_flags[c] & POLR_KEY_NULL_EQUAL) ? (1u << c) : 0u;
-			}
-			ht->pack.null_eq = null_eq;
-			polr_launch_key_minmax(st, ht->keys_dev, ht->n_keys, n, null_eq, mm);
-			e = hipMemcpyAsync(h_mm, mm, sizeof(h_mm), hipMemcpyDeviceToHost, st);
-		}
-		e = e == hipSuccess ? hipStreamSynchronize(st) : e;
-		hipFree(mm);
-		if (e != hipSuccess) {
-			POLR_FAIL(ctx, POLR_E_HIP, "key range scan failed: %s", hipGetErrorString(e));
-		}
+		pack.null_eq = null_eq;
+		polr_launch_key_minmax(st, ht->keys_dev, ht->n_keys, n, null_eq, mm);
+		HIPCHK(ctx, hipMemcpyAsync(h_mm, mm, sizeof(h_mm), hipMemcpyDeviceToHost, st));
+		HIPCHK(ctx, hipStreamSynchronize(st));
 		uint32_t shift = 0;
-		const uint32_t null_eq_mask = ht->pack.null_eq;
-		ht->pack.packed = 1;
+		pack.packed = 1;
 		for (uint32_t c = 0; c < ht->n_keys; c++) {
 			const bool empty = h_mm[2 * c] > h_mm[2 * c + 1]; // no row with valid keys at all
 			const int64_t lo = empty ? 0 : h_mm[2 * c], hi = empty ? 0 : h_mm[2 * c + 1];
 			const uint64_t range = (uint64_t)hi - (uint64_t)lo;
 			// (a NULL = NULL column has one more code, range + 1: NULL)
-			const bool null_eq_col = ((null_eq_mask >> c) & 1u) != 0;
+			const bool null_eq_col = ((null_eq >> c) & 1u) != 0;
 			const uint64_t top = range + (null_eq_col ? 1u : 0u);
 			uint32_t bits = 0;
 			while (bits < 64 && (top >> bits) != 0) {
 				bits++;
 			}
 			if (shift + bits > 64 || (null_eq_col && top == 0)) {
-				ht->pack = KeyPack();
 				POLR_FAIL(ctx, POLR_E_UNSUPPORTED,
 				          "composite key of %u columns needs more than 64 bits (column %u: range %llu after %u bits)",
 				          ht->n_keys, c, (unsigned long long)range, shift);
 			}
-			ht->pack.shift[c] = shift;
-			ht->pack.sx[c] = (ht->keys[c].flags & 1u) ? 1u : 0u;
-			ht->pack.min[c] = lo;
-			ht->pack.range[c] = range;
+			pack.shift[c] = shift;
+			pack.sx[c] = (ht->keys[c].flags & 1u) ? 1u : 0u;
+			pack.min[c] = lo;
+			pack.range[c] = range;
 			shift += bits;
 		}
 	}
@@ -480,128 +424,76 @@ int polr_ht_finalize_hash(polr_ht *ht, void *stream) {
 		POLR_FAIL(ctx, POLR_E_UNSUPPORTED, "hash table of %llu slots exceeds the 32-bit slot space",
 		          (unsigned long long)capacity);
 	}
-	uint4 *slots = nullptr;
-	uint32_t *slot_of_row = nullptr, *cursor = nullptr, *rowids = nullptr, *block_sums = nullptr, *scalars = nullptr;
-	unsigned long long *n_valid = nullptr;
-	uint64_t acct = 0;
-	int rc = dev_alloc(ctx, (void **)&slots, capacity * sizeof(uint4), &acct);
-	if (!rc) {
-		rc = dev_alloc(ctx, (void **)&slot_of_row, n * 4, nullptr);
-	}
-	if (!rc) {
-		rc = dev_alloc(ctx, (void **)&cursor, capacity * 4, nullptr);
-	}
-	if (!rc) {
-		rc = dev_alloc(ctx, (void **)&rowids, n * 4, &acct);
-	}
 	const uint64_t n_blocks = (capacity + 1023) / 1024;
-	if (!rc) {
-		rc = dev_alloc(ctx, (void **)&block_sums, n_blocks * 4, nullptr);
-	}
-	if (!rc) {
-		rc = dev_alloc(ctx, (void **)&scalars, 4 * 4, nullptr);
-	}
-	if (!rc) {
-		rc = dev_alloc(ctx, (void **)&n_valid, 8, nullptr);
-	}
+	DevBuf<uint8_t> slots_mem; // [capacity] uint4: the table itself unless it is converted to 8-byte slots
+	DevBuf<uint32_t> slot_of_row, cursor, rowids, block_sums, scalars;
+	DevBuf<unsigned long long> n_valid;
+	HIPCHK(ctx, slots_mem.alloc(capacity * sizeof(uint4)));
+	HIPCHK(ctx, slot_of_row.alloc(n));
+	HIPCHK(ctx, cursor.alloc(capacity));
+	HIPCHK(ctx, rowids.alloc(n));
+	HIPCHK(ctx, block_sums.alloc(n_blocks));
+	HIPCHK(ctx, scalars.alloc(4));
+	HIPCHK(ctx, n_valid.alloc(1));
+	uint4 *slots = (uint4 *)slots_mem.get();
 	uint32_t h_scalars[4] = {0, 0, 0, 0};
 	unsigned long long h_valid = 0;
-	if (!rc) {
-		hipError_t e = hipMemsetAsync(cursor, 0, capacity * 4, st);
-		e = e == hipSuccess ? hipMemsetAsync(scalars, 0, 16, st) : e;
-		e = e == hipSuccess ? hipMemsetAsync(n_valid, 0, 8, st) : e;
-		if (e == hipSuccess) {
-			polr_launch_s16_build(st, ht->keys_dev, ht->n_keys, ht->pack, n, slots, capacity, slot_of_row, cursor, rowids,
-			                      block_sums, scalars, n_valid);
-			e = hipMemcpyAsync(h_scalars, scalars, 16, hipMemcpyDeviceToHost, st);
-			e = e == hipSuccess ? hipMemcpyAsync(&h_valid, n_valid, 8, hipMemcpyDeviceToHost, st) : e;
-			e = e == hipSuccess ? hipStreamSynchronize(st) : e;
-		}
-		if (e == hipSuccess) {
-			// h_scalars: [0] sentinel rows, [1] longest run, [2] rows with a regular key
-			polr_launch_s16_scatter(st, n, slots, slot_of_row, cursor, rowids, h_scalars[2], &scalars[3]);
-			e = hipStreamSynchronize(st);
-		}
-		if (e != hipSuccess) {
-			ctx->err = std::string("hash table build failed: ") + hipGetErrorString(e);
-			rc = POLR_E_HIP;
-		}
+	HIPCHK(ctx, hipMemsetAsync(cursor, 0, capacity * 4, st));
+	HIPCHK(ctx, hipMemsetAsync(scalars, 0, 16, st));
+	HIPCHK(ctx, hipMemsetAsync(n_valid, 0, 8, st));
+	polr_launch_s16_build(st, ht->keys_dev, ht->n_keys, pack, n, slots, capacity, slot_of_row, cursor, rowids, block_sums,
+	                      scalars, n_valid);
+	HIPCHK(ctx, hipMemcpyAsync(h_scalars, scalars, 16, hipMemcpyDeviceToHost, st));
+	HIPCHK(ctx, hipMemcpyAsync(&h_valid, n_valid, 8, hipMemcpyDeviceToHost, st));
+	HIPCHK(ctx, hipStreamSynchronize(st));
+	// h_scalars: [0] sentinel rows, [1] longest run, [2] rows with a regular key
+	polr_launch_s16_scatter(st, n, slots, slot_of_row, cursor, rowids, h_scalars[2], scalars + 3);
+	HIPCHK(ctx, hipStreamSynchronize(st));
+	const uint64_t max_run = std::max<uint64_t>(h_scalars[1], h_scalars[0]);
+	if (max_run >= (1ull << 25)) {
+		POLR_FAIL(ctx, POLR_E_UNSUPPORTED, "a build key repeats more than 2^25 times: outside the expansion counter range");
 	}
-	if (!rc) {
-		ht->n_rows = h_valid;
-		ht->has_null = h_valid < n;
-		ht->capacity = capacity;
-		ht->sentinel_start = h_scalars[2];
-		ht->sentinel_count = h_scalars[0];
-		ht->max_run = std::max<uint64_t>(h_scalars[1], h_scalars[0]);
-		if (ht->max_run >= (1ull << 25)) {
-			ctx->err = "a build key repeats more than 2^25 times: outside the expansion counter range";
-			rc = POLR_E_UNSUPPORTED;
-		}
+	const bool unique32 = max_run <= 1 && ht->n_keys == 1 && ht->keys[0].width == 4 && !pack.packed;
+	DevBuf<uint8_t> s8_mem; // [capacity] uint2
+	if (unique32) {
+		HIPCHK(ctx, s8_mem.alloc(capacity * sizeof(uint2)));
+		polr_launch_s16_to_s8(st, slots, capacity, rowids, (uint2 *)s8_mem.get());
+		HIPCHK(ctx, hipStreamSynchronize(st));
 	}
-	if (!rc) {
-		const bool unique32 = ht->max_run <= 1 && ht->n_keys == 1 && ht->keys[0].width == 4 && !ht->pack.packed;
-		if (unique32) {
-			uint2 *s8 = nullptr;
-			rc = dev_alloc(ctx, (void **)&s8, capacity * sizeof(uint2), &ht->device_bytes);
-			if (!rc) {
-				polr_launch_s16_to_s8(st, slots, capacity, rowids, s8);
-				hipError_t e = hipStreamSynchronize(st);
-				if (e != hipSuccess) {
-					ctx->err = std::string("s8 conversion failed: ") + hipGetErrorString(e);
-					rc = POLR_E_HIP;
-				}
-			}
-			if (!rc) {
-				ht->table = s8;
-				ht->kind = KIND_S8;
-				hipFree(slots);
-				hipFree(rowids);
-				slots = nullptr;
-				rowids = nullptr;
-			}
-		} else {
-			ht->table = slots;
-			ht->rowids = rowids;
-			ht->kind = KIND_S16;
-			ht->device_bytes += acct;
-			slots = nullptr;
-			rowids = nullptr;
-		}
+	POLR_TRY(upload_devcols(ctx, ht->payload, &ht->payload_dev, st));
+	// nothing can fail from here on: the table takes what was built
+	ht->pack = pack;
+	ht->n_rows = h_valid;
+	ht->has_null = h_valid < n;
+	ht->capacity = capacity;
+	ht->sentinel_start = h_scalars[2];
+	ht->sentinel_count = h_scalars[0];
+	ht->max_run = max_run;
+	if (unique32) {
+		ht->table_mem = std::move(s8_mem);
+	} else {
+		ht->table_mem = std::move(slots_mem);
+		ht->rowids = std::move(rowids);
+		ht->device_bytes += ht->rowids.bytes();
 	}
-	if (!rc) {
-		rc = upload_devcols(ctx, ht->payload, &ht->payload_dev, st);
-	}
-	if (slots) {
-		hipFree(slots);
-	}
-	if (rowids) {
-		hipFree(rowids);
-	}
-	hipFree(slot_of_row);
-	hipFree(cursor);
-	hipFree(block_sums);
-	hipFree(scalars);
-	hipFree(n_valid);
-	return rc;
+	ht->device_bytes += ht->table_mem.bytes();
+	ht->table = ht->table_mem;
+	ht->kind = unique32 ? KIND_S8 : KIND_S16;
+	return POLR_OK;
 }
 
-static int alloc_perfect_cols(polr_ht *ht, uint64_t size) {
+// the re-ordered copies of the payload columns a perfect table of `size` slots reads; acct: gains the bytes allocated
+static int alloc_perfect_cols(const polr_ht *ht, uint64_t size, std::vector<OwnedCol> &pcols, uint64_t *acct) {
 	polr_ctx *ctx = ht->ctx;
-	ht->pcols.resize(ht->n_payload);
+	pcols.resize(ht->n_payload);
 	for (uint32_t i = 0; i < ht->n_payload; i++) {
-		OwnedCol &c = ht->pcols[i];
+		OwnedCol &c = pcols[i];
 		c.width = ht->payload[i].width;
 		c.flags = ht->payload[i].flags;
-		c.owned = true;
 		c.strings_rebased = ht->payload[i].strings_rebased; // (the re-ordered copy holds the same cells)
-		int rc = dev_alloc(ctx, (void **)&c.data, size * c.width, &ht->device_bytes);
-		if (!rc) {
-			rc = dev_alloc(ctx, (void **)&c.valid, size, &ht->device_bytes);
-		}
-		if (rc) {
-			return rc;
-		}
+		HIPCHK(ctx, c.alloc_data(size * c.width));
+		HIPCHK(ctx, c.alloc_valid(size));
+		*acct += c.own_data.bytes() + c.own_valid.bytes();
 	}
 	return POLR_OK;
 }
@@ -633,82 +525,52 @@ int polr_ht_finalize_perfect(polr_ht *ht, int64_t min_value, int64_t max_value, 
 	hipStream_t st = polr_stream(ctx, stream);
 	const uint64_t size = range + 1;
 	const uint64_t words = (size + 31) / 32;
-	uint32_t *bits = nullptr, *idx_row = nullptr, *flags = nullptr;
-	unsigned long long *unique = nullptr;
-	uint64_t acct = 0;
-	int rc = dev_alloc(ctx, (void **)&bits, words * 4, &acct);
-	if (!rc) {
-		rc = dev_alloc(ctx, (void **)&idx_row, size * 4, &acct);
-	}
-	if (!rc) {
-		rc = dev_alloc(ctx, (void **)&flags, 8, nullptr);
-	}
-	if (!rc) {
-		rc = dev_alloc(ctx, (void **)&unique, 8, nullptr);
-	}
+	DevBuf<uint8_t> bits_mem; // [words] uint32_t
+	DevBuf<uint32_t> idx_row, flags;
+	DevBuf<unsigned long long> unique;
+	HIPCHK(ctx, bits_mem.alloc(words * 4));
+	HIPCHK(ctx, idx_row.alloc(size));
+	HIPCHK(ctx, flags.alloc(2));
+	HIPCHK(ctx, unique.alloc(1));
+	uint32_t *bits = (uint32_t *)bits_mem.get();
 	uint32_t h_flags[2] = {0, 0};
 	unsigned long long h_unique = 0;
-	if (!rc) {
-		hipError_t e = hipMemsetAsync(bits, 0, words * 4, st);
-		e = e == hipSuccess ? hipMemsetAsync(idx_row, 0xFF, size * 4, st) : e;
-		e = e == hipSuccess ? hipMemsetAsync(flags, 0, 8, st) : e;
-		e = e == hipSuccess ? hipMemsetAsync(unique, 0, 8, st) : e;
-		if (e == hipSuccess) {
-			polr_launch_pht_mark(st, ht->keys_dev, ht->n_rows_in, min_value, range, is_signed ? 1 : 0, bits, idx_row,
-			                     flags, unique);
-			e = hipMemcpyAsync(h_flags, flags, 8, hipMemcpyDeviceToHost, st);
-			e = e == hipSuccess ? hipMemcpyAsync(&h_unique, unique, 8, hipMemcpyDeviceToHost, st) : e;
-			e = e == hipSuccess ? hipStreamSynchronize(st) : e;
-		}
-		if (e != hipSuccess) {
-			ctx->err = std::string("perfect table build failed: ") + hipGetErrorString(e);
-			rc = POLR_E_HIP;
-		}
+	HIPCHK(ctx, hipMemsetAsync(bits, 0, words * 4, st));
+	HIPCHK(ctx, hipMemsetAsync(idx_row, 0xFF, size * 4, st));
+	HIPCHK(ctx, hipMemsetAsync(flags, 0, 8, st));
+	HIPCHK(ctx, hipMemsetAsync(unique, 0, 8, st));
+	polr_launch_pht_mark(st, ht->keys_dev, ht->n_rows_in, min_value, range, is_signed ? 1 : 0, bits, idx_row, flags,
+	                     unique);
+	HIPCHK(ctx, hipMemcpyAsync(h_flags, flags, 8, hipMemcpyDeviceToHost, st));
+	HIPCHK(ctx, hipMemcpyAsync(&h_unique, unique, 8, hipMemcpyDeviceToHost, st));
+	HIPCHK(ctx, hipStreamSynchronize(st));
+	if (h_flags[0]) {
+		POLR_FAIL(ctx, POLR_E_DUPLICATE, "duplicate build key inside the perfect-hash range");
 	}
-	if (!rc && h_flags[0]) {
-		ctx->err = "duplicate build key inside the perfect-hash range";
-		rc = POLR_E_DUPLICATE;
+	std::vector<OwnedCol> pcols;
+	uint64_t acct = bits_mem.bytes() + idx_row.bytes();
+	POLR_TRY(alloc_perfect_cols(ht, size, pcols, &acct));
+	for (uint32_t i = 0; i < ht->n_payload; i++) {
+		polr_launch_pht_gather(st, bits, idx_row, size, dev_col(ht->payload[i]), pcols[i].data, pcols[i].valid);
 	}
-	if (!rc) {
-		ht->bits = bits;
-		ht->idx_row = idx_row;
-		ht->device_bytes += acct;
-		bits = nullptr;
-		idx_row = nullptr;
-		ht->min_value = min_value;
-		ht->max_value = max_value;
-		ht->range = range;
-		ht->has_null = h_flags[1];
-		ht->n_rows = h_unique;
-		ht->capacity = size;
-		ht->max_run = h_unique ? 1 : 0;
-		ht->is_dense = (h_unique == size && !h_flags[1]) ? 1 : 0;
-		rc = alloc_perfect_cols(ht, size);
-	}
-	if (!rc) {
-		for (uint32_t i = 0; i < ht->n_payload; i++) {
-			polr_launch_pht_gather(st, ht->bits, ht->idx_row, size, dev_col(ht->payload[i]), ht->pcols[i].data, ht->pcols[i].valid);
-		}
-		hipError_t e = hipStreamSynchronize(st);
-		if (e != hipSuccess) {
-			ctx->err = std::string("perfect column gather failed: ") + hipGetErrorString(e);
-			rc = POLR_E_HIP;
-		}
-	}
-	if (!rc) {
-		ht->table = ht->bits;
-		ht->kind = KIND_PERFECT;
-		rc = upload_devcols(ctx, ht->pcols, &ht->payload_dev, st);
-	}
-	if (bits) {
-		hipFree(bits);
-	}
-	if (idx_row) {
-		hipFree(idx_row);
-	}
-	hipFree(flags);
-	hipFree(unique);
-	return rc;
+	HIPCHK(ctx, hipStreamSynchronize(st));
+	POLR_TRY(upload_devcols(ctx, pcols, &ht->payload_dev, st));
+	// nothing can fail from here on: the table takes what was built
+	ht->table_mem = std::move(bits_mem);
+	ht->idx_row = std::move(idx_row);
+	ht->pcols = std::move(pcols);
+	ht->device_bytes += acct;
+	ht->min_value = min_value;
+	ht->max_value = max_value;
+	ht->range = range;
+	ht->has_null = h_flags[1];
+	ht->n_rows = h_unique;
+	ht->capacity = size;
+	ht->max_run = h_unique ? 1 : 0;
+	ht->is_dense = (h_unique == size && !h_flags[1]) ? 1 : 0;
+	ht->table = ht->bits = bits;
+	ht->kind = KIND_PERFECT;
+	return POLR_OK;
 }
 
 int polr_ht_finalize_auto(polr_ht *ht, int64_t min_value, int64_t max_value, void *stream, uint32_t *kind_out) {
@@ -753,7 +615,7 @@ int polr_pht_upload(polr_ctx *ctx, uint32_t key_width, uint32_t key_flags, int64
 	}
 	HIPCHK(ctx, hipSetDevice(ctx->device));
 	const uint64_t size = range + 1;
-	polr_ht *ht = new polr_ht();
+	HandleGuard<polr_ht> ht(new polr_ht());
 	ht->ctx = polr_ctx_retain(ctx);
 	ht->n_keys = 1;
 	ht->n_payload = n_payload;
@@ -761,57 +623,35 @@ int polr_pht_upload(polr_ctx *ctx, uint32_t key_width, uint32_t key_flags, int64
 	ht->keys.resize(1);
 	ht->keys[0].width = key_width;
 	ht->keys[0].flags = ht->key_signed;
-	ht->keys[0].owned = false;
 	ht->pcols.resize(n_payload);
 	ht->payload.resize(n_payload);
-	int rc = POLR_OK;
-	for (uint32_t i = 0; i < n_payload && !rc; i++) {
-		rc = ingest_col(ctx, &payload[i], size, &ht->pcols[i], &ht->device_bytes, ctx->stream);
+	for (uint32_t i = 0; i < n_payload; i++) {
+		POLR_TRY(ingest_col(ctx, &payload[i], size, &ht->pcols[i], &ht->device_bytes, ctx->stream));
 		ht->payload[i].width = ht->pcols[i].width;
-		ht->payload[i].owned = false;
 	}
-	uint8_t *bytes = nullptr;
-	if (!rc) {
-		rc = dev_alloc(ctx, (void **)&bytes, size, nullptr);
+	DevBuf<uint8_t> bytes;
+	HIPCHK(ctx, bytes.alloc(size));
+	HIPCHK(ctx, ht->table_mem.alloc(((size + 31) / 32) * 4));
+	ht->device_bytes += ht->table_mem.bytes();
+	ht->bits = (uint32_t *)ht->table_mem.get();
+	HIPCHK(ctx, hipMemcpyAsync(bytes, bitmap, size, hipMemcpyHostToDevice, ctx->stream));
+	polr_launch_pack_bitmap(ctx->stream, bytes, size, ht->bits);
+	HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+	uint64_t set = 0;
+	for (uint64_t i = 0; i < size; i++) {
+		set += bitmap[i] ? 1 : 0;
 	}
-	if (!rc) {
-		rc = dev_alloc(ctx, (void **)&ht->bits, ((size + 31) / 32) * 4, &ht->device_bytes);
-	}
-	if (!rc) {
-		hipError_t e = hipMemcpyAsync(bytes, bitmap, size, hipMemcpyHostToDevice, ctx->stream);
-		if (e == hipSuccess) {
-			polr_launch_pack_bitmap(ctx->stream, bytes, size, ht->bits);
-			e = hipStreamSynchronize(ctx->stream);
-		}
-		if (e != hipSuccess) {
-			ctx->err = std::string("bitmap upload failed: ") + hipGetErrorString(e);
-			rc = POLR_E_HIP;
-		}
-	}
-	if (bytes) {
-		hipFree(bytes);
-	}
-	if (!rc) {
-		uint64_t set = 0;
-		for (uint64_t i = 0; i < size; i++) {
-			set += bitmap[i] ? 1 : 0;
-		}
-		ht->n_rows = ht->n_rows_in = set;
-		ht->min_value = min_value;
-		ht->max_value = max_value;
-		ht->range = range;
-		ht->capacity = size;
-		ht->max_run = set ? 1 : 0;
-		ht->is_dense = set == size;
-		ht->table = ht->bits;
-		ht->kind = KIND_PERFECT;
-		rc = upload_devcols(ctx, ht->pcols, &ht->payload_dev, ctx->stream);
-	}
-	if (rc) {
-		polr_ht_destroy(ht);
-		return rc;
-	}
-	*out = ht;
+	ht->n_rows = ht->n_rows_in = set;
+	ht->min_value = min_value;
+	ht->max_value = max_value;
+	ht->range = range;
+	ht->capacity = size;
+	ht->max_run = set ? 1 : 0;
+	ht->is_dense = set == size;
+	ht->table = ht->bits;
+	ht->kind = KIND_PERFECT;
+	POLR_TRY(upload_devcols(ctx, ht->pcols, &ht->payload_dev, ctx->stream));
+	*out = ht.release();
 	return POLR_OK;
 }
 
@@ -821,42 +661,6 @@ void polr_ht_destroy(polr_ht *ht) {
 		return;
 	}
 	hipSetDevice(ht->ctx->device);
-	for (auto &c : ht->keys) {
-		free_col(c);
-	}
-	for (auto &c : ht->payload) {
-		free_col(c);
-	}
-	for (auto &c : ht->pcols) {
-		free_col(c);
-	}
-	for (void *h : ht->heaps) {
-		hipFree(h);
-	}
-	for (DictCol &d : ht->dicts) {
-		if (d.cells) {
-			hipFree(d.cells);
-		}
-	}
-	if (ht->kind == KIND_PERFECT) {
-		if (ht->bits) {
-			hipFree(ht->bits);
-		}
-	} else if (ht->table) {
-		hipFree(ht->table);
-	}
-	if (ht->rowids) {
-		hipFree(ht->rowids);
-	}
-	if (ht->idx_row) {
-		hipFree(ht->idx_row);
-	}
-	if (ht->keys_dev) {
-		hipFree(ht->keys_dev);
-	}
-	if (ht->payload_dev) {
-		hipFree(ht->payload_dev);
-	}
 	polr_ctx *ctx_ = ht->ctx;
 	delete ht;
 	polr_ctx_release(ctx_);
@@ -992,8 +796,11 @@ int polr_ht_alloc_like(polr_ctx *ctx, const void *meta, uint64_t meta_bytes, pol
 	if (m.magic != 0x504F4C52u || m.n_payload > 62 || m.n_keys > POLR_MAX_KEYS) {
 		POLR_FAIL(ctx, POLR_E_INVALID, "bad table metadata");
 	}
+	if (m.kind != KIND_PERFECT && m.kind != KIND_S8 && m.kind != KIND_S16) {
+		POLR_FAIL(ctx, POLR_E_INVALID, "bad table kind in metadata");
+	}
 	HIPCHK(ctx, hipSetDevice(ctx->device));
-	polr_ht *ht = new polr_ht();
+	HandleGuard<polr_ht> ht(new polr_ht());
 	ht->ctx = polr_ctx_retain(ctx);
 	ht->kind = m.kind;
 	ht->n_keys = m.n_keys;
@@ -1014,52 +821,42 @@ int polr_ht_alloc_like(polr_ctx *ctx, const void *meta, uint64_t meta_bytes, pol
 	for (uint32_t i = 0; i < m.n_keys; i++) {
 		ht->keys[i].width = m.key_width[i];
 		ht->keys[i].flags = m.n_keys == 1 ? m.key_signed : m.key_flags[i];
-		ht->keys[i].owned = false;
 		ht->key_flags[i] = m.key_sem[i];
 	}
 	ht->pack = m.pack;
-	int rc = POLR_OK;
 	const uint64_t rows = m.kind == KIND_PERFECT ? m.capacity : m.n_rows_in;
 	if (m.kind == KIND_PERFECT) {
-		rc = dev_alloc(ctx, (void **)&ht->bits, ((m.capacity + 31) / 32) * 4, &ht->device_bytes);
-		ht->table = ht->bits;
-	} else if (m.kind == KIND_S8) {
-		rc = dev_alloc(ctx, &ht->table, m.capacity * sizeof(uint2), &ht->device_bytes);
-	} else if (m.kind == KIND_S16) {
-		rc = dev_alloc(ctx, &ht->table, m.capacity * sizeof(uint4), &ht->device_bytes);
-		if (!rc) {
-			rc = dev_alloc(ctx, (void **)&ht->rowids, std::max<uint64_t>(m.n_rows_in * 4, 16), &ht->device_bytes);
-		}
+		HIPCHK(ctx, ht->table_mem.alloc(((m.capacity + 31) / 32) * 4));
+		ht->bits = (uint32_t *)ht->table_mem.get();
 	} else {
-		ctx->err = "bad table kind in metadata";
-		rc = POLR_E_INVALID;
+		HIPCHK(ctx, ht->table_mem.alloc(m.capacity * (m.kind == KIND_S8 ? sizeof(uint2) : sizeof(uint4))));
+	}
+	ht->table = ht->table_mem;
+	ht->device_bytes += ht->table_mem.bytes();
+	if (m.kind == KIND_S16) {
+		HIPCHK(ctx, ht->rowids.alloc(std::max<uint64_t>(m.n_rows_in, 4)));
+		ht->device_bytes += ht->rowids.bytes();
 	}
 	std::vector<OwnedCol> &cols = m.kind == KIND_PERFECT ? ht->pcols : ht->payload;
 	cols.resize(m.n_payload);
 	if (m.kind == KIND_PERFECT) {
 		ht->payload.resize(m.n_payload);
 	}
-	for (uint32_t i = 0; i < m.n_payload && !rc; i++) {
+	for (uint32_t i = 0; i < m.n_payload; i++) {
 		cols[i].width = m.payload_width[i];
 		cols[i].flags = m.payload_flags[i];
-		cols[i].owned = true;
-		rc = dev_alloc(ctx, (void **)&cols[i].data, std::max<uint64_t>(rows * cols[i].width, 16), &ht->device_bytes);
-		if (!rc && m.payload_has_valid[i]) {
-			rc = dev_alloc(ctx, (void **)&cols[i].valid, std::max<uint64_t>(rows, 16), &ht->device_bytes);
+		HIPCHK(ctx, cols[i].alloc_data(std::max<uint64_t>(rows * cols[i].width, 16)));
+		ht->device_bytes += cols[i].own_data.bytes();
+		if (m.payload_has_valid[i]) {
+			HIPCHK(ctx, cols[i].alloc_valid(std::max<uint64_t>(rows, 16)));
+			ht->device_bytes += cols[i].own_valid.bytes();
 		}
 		if (m.kind == KIND_PERFECT) {
 			ht->payload[i].width = cols[i].width;
-			ht->payload[i].owned = false;
 		}
 	}
-	if (!rc) {
-		rc = upload_devcols(ctx, cols, &ht->payload_dev, ctx->stream);
-	}
-	if (rc) {
-		polr_ht_destroy(ht);
-		return rc;
-	}
-	*out = ht;
+	POLR_TRY(upload_devcols(ctx, cols, &ht->payload_dev, ctx->stream));
+	*out = ht.release();
 	return POLR_OK;
 }
 
@@ -1407,7 +1204,8 @@ int polr_pipeline_create(polr_ctx *ctx, const polr_col *probe_cols, uint32_t n_p
 		}
 	}
 	HIPCHK(ctx, hipSetDevice(ctx->device));
-	polr_pipeline *p = new polr_pipeline();
+	HandleGuard<polr_pipeline> guard(new polr_pipeline());
+	polr_pipeline *p = guard.get();
 	p->ctx = polr_ctx_retain(ctx);
 	p->k = k;
 	p->n_paths = n_paths;
@@ -1415,115 +1213,96 @@ int polr_pipeline_create(polr_ctx *ctx, const polr_col *probe_cols, uint32_t n_p
 	p->n_probe_rows = n_probe_rows;
 	p->n_tuples = n_probe_rows;
 	p->probe_cols.resize(n_probe_cols);
-	int rc = POLR_OK;
 	uint64_t acct = 0;
-	for (uint32_t i = 0; i < n_probe_cols && !rc; i++) {
-		rc = ingest_col(ctx, &probe_cols[i], n_probe_rows, &p->probe_cols[i], &acct, ctx->stream);
+	for (uint32_t i = 0; i < n_probe_cols; i++) {
+		POLR_TRY(ingest_col(ctx, &probe_cols[i], n_probe_rows, &p->probe_cols[i], &acct, ctx->stream));
 	}
-	if (!rc) {
-		rc = upload_devcols(ctx, p->probe_cols, &p->probe_cols_dev, ctx->stream);
+	POLR_TRY(upload_devcols(ctx, p->probe_cols, &p->probe_cols_dev, ctx->stream));
+	DevPipeline &m = p->host_mat;
+	memset(&m, 0, sizeof(m));
+	m.k = k;
+	m.n_paths = n_paths;
+	m.n_probe_cols = n_probe_cols;
+	m.probe_cols = p->probe_cols_dev;
+	m.sel = nullptr;
+	m.n_tuples = n_probe_rows;
+	for (uint32_t j = 0; j < k; j++) {
+		p->hts.push_back(joins[j].ht);
+		fill_dev_join(&m.joins[j], &joins[j], joins[j].ht);
 	}
-	if (!rc) {
-		DevPipeline &m = p->host_mat;
-		memset(&m, 0, sizeof(m));
-		m.k = k;
-		m.n_paths = n_paths;
-		m.n_probe_cols = n_probe_cols;
-		m.probe_cols = p->probe_cols_dev;
-		m.sel = nullptr;
-		m.n_tuples = n_probe_rows;
+	for (uint32_t q = 0; q < n_paths; q++) {
 		for (uint32_t j = 0; j < k; j++) {
-			p->hts.push_back(joins[j].ht);
-			fill_dev_join(&m.joins[j], &joins[j], joins[j].ht);
+			m.paths[q].order[j] = (uint32_t)paths[q * k + j];
 		}
-		for (uint32_t q = 0; q < n_paths; q++) {
-			for (uint32_t j = 0; j < k; j++) {
-				m.paths[q].order[j] = (uint32_t)paths[q * k + j];
+	}
+	p->host_count = m;
+	// materialising variant: slot 1+j = join j (the adaptive union's column order)
+	m.materialize = 1;
+	m.W = 1 + k;
+	for (uint32_t j = 0; j < POLR_KMAX; j++) {
+		m.slot_of_join[j] = j < k ? (int32_t)(1 + j) : -1;
+	}
+	// counting variant: carry only the build ids some later join reads its key through
+	DevPipeline &c = p->host_count;
+	c.materialize = 0;
+	uint32_t w = 1;
+	for (uint32_t j = 0; j < POLR_KMAX; j++) {
+		c.slot_of_join[j] = -1;
+	}
+	for (uint32_t j = 0; j < k; j++) {
+		for (uint32_t cc = 0; cc < joins[j].n_keys; cc++) {
+			const int32_t sj = joins[j].key_src_join[cc];
+			if (sj >= 0 && c.slot_of_join[sj] < 0) {
+				c.slot_of_join[sj] = (int32_t)w++;
 			}
 		}
-		p->host_count = m;
-		// materialising variant: slot 1+j = join j (the adaptive union's column order)
-		m.materialize = 1;
-		m.W = 1 + k;
-		for (uint32_t j = 0; j < POLR_KMAX; j++) {
-			m.slot_of_join[j] = j < k ? (int32_t)(1 + j) : -1;
-		}
-		// counting variant: carry only the build ids some later join reads its key through
-		DevPipeline &c = p->host_count;
-		c.materialize = 0;
-		uint32_t w = 1;
-		for (uint32_t j = 0; j < POLR_KMAX; j++) {
-			c.slot_of_join[j] = -1;
-		}
-		for (uint32_t j = 0; j < k; j++) {
-			for (uint32_t cc = 0; cc < joins[j].n_keys; cc++) {
-				const int32_t sj = joins[j].key_src_join[cc];
-				if (sj >= 0 && c.slot_of_join[sj] < 0) {
-					c.slot_of_join[sj] = (int32_t)w++;
-				}
-			}
-			for (uint32_t cc = 0; cc < joins[j].n_preds; cc++) {
-				const int32_t sj = joins[j].pred_src_join[cc];
-				if (sj >= 0 && c.slot_of_join[sj] < 0) {
-					c.slot_of_join[sj] = (int32_t)w++;
-				}
+		for (uint32_t cc = 0; cc < joins[j].n_preds; cc++) {
+			const int32_t sj = joins[j].pred_src_join[cc];
+			if (sj >= 0 && c.slot_of_join[sj] < 0) {
+				c.slot_of_join[sj] = (int32_t)w++;
 			}
 		}
-		c.W = w;
-		// multiplicities (polr_gen_device.h): worth a tuple slot when some join's matches can be folded into them -- its
-		// build key may repeat, nobody reads its build rows downstream, it has no non-equality condition
-		c.mult = 0;
-		for (uint32_t j = 0; j < k; j++) {
-			const polr_ht *ht = joins[j].ht;
-			const bool repeats = !(ht->kind == KIND_PERFECT || ht->kind == KIND_S8 || ht->max_run <= 1);
-			if (repeats && c.slot_of_join[j] < 0 && joins[j].n_preds == 0) {
-				c.mult = 1;
-			}
+	}
+	c.W = w;
+	// multiplicities (polr_gen_device.h): worth a tuple slot when some join's matches can be folded into them -- its
+	// build key may repeat, nobody reads its build rows downstream, it has no non-equality condition
+	c.mult = 0;
+	for (uint32_t j = 0; j < k; j++) {
+		const polr_ht *ht = joins[j].ht;
+		const bool repeats = !(ht->kind == KIND_PERFECT || ht->kind == KIND_S8 || ht->max_run <= 1);
+		if (repeats && c.slot_of_join[j] < 0 && joins[j].n_preds == 0) {
+			c.mult = 1;
 		}
-		p->host_mat.mult = 0;
-		std::vector<StageDesc> sd_mat, sd_count;
-		std::vector<StageExt> sd_ext;
-		build_stage_descs(p, p->host_mat, sd_mat, sd_ext);
-		build_stage_descs(p, p->host_count, sd_count, sd_ext);
-		plan_flat(p, sd_count);
-		p->host_mat.ext = p->host_count.ext = sd_ext.empty() ? 0u : 1u;
-		hipError_t e = hipSuccess;
-		if (!sd_ext.empty()) {
-			e = hipMalloc((void **)&p->stage_ext, sd_ext.size() * sizeof(StageExt));
-			e = e == hipSuccess ? hipMemcpy(p->stage_ext, sd_ext.data(), sd_ext.size() * sizeof(StageExt), hipMemcpyHostToDevice)
-			                    : e;
-			for (auto *sd : {&sd_mat, &sd_count}) {
-				for (auto &d : *sd) {
-					if (d.ext) {
-						d.ext = p->stage_ext + ((uintptr_t)d.ext - 1);
-					}
+	}
+	p->host_mat.mult = 0;
+	std::vector<StageDesc> sd_mat, sd_count;
+	std::vector<StageExt> sd_ext;
+	build_stage_descs(p, p->host_mat, sd_mat, sd_ext);
+	build_stage_descs(p, p->host_count, sd_count, sd_ext);
+	plan_flat(p, sd_count);
+	p->host_mat.ext = p->host_count.ext = sd_ext.empty() ? 0u : 1u;
+	if (!sd_ext.empty()) {
+		HIPCHK(ctx, p->stage_ext.alloc(sd_ext.size()));
+		HIPCHK(ctx, hipMemcpy(p->stage_ext, sd_ext.data(), sd_ext.size() * sizeof(StageExt), hipMemcpyHostToDevice));
+		for (auto *sd : {&sd_mat, &sd_count}) {
+			for (auto &d : *sd) {
+				if (d.ext) {
+					d.ext = p->stage_ext + ((uintptr_t)d.ext - 1);
 				}
 			}
 		}
-		e = e == hipSuccess ? hipMalloc((void **)&p->stages_mat, sd_mat.size() * sizeof(StageDesc)) : e;
-		e = e == hipSuccess ? hipMalloc((void **)&p->stages_count, sd_count.size() * sizeof(StageDesc)) : e;
-		e = e == hipSuccess ? hipMemcpy(p->stages_mat, sd_mat.data(), sd_mat.size() * sizeof(StageDesc),
-		                                hipMemcpyHostToDevice)
-		                    : e;
-		e = e == hipSuccess ? hipMemcpy(p->stages_count, sd_count.data(), sd_count.size() * sizeof(StageDesc),
-		                                hipMemcpyHostToDevice)
-		                    : e;
-		p->host_mat.stages = p->stages_mat;
-		p->host_count.stages = p->stages_count;
-		e = e == hipSuccess ? hipMalloc((void **)&p->dev_mat, sizeof(DevPipeline)) : e;
-		e = e == hipSuccess ? hipMalloc((void **)&p->dev_count, sizeof(DevPipeline)) : e;
-		e = e == hipSuccess ? hipMemcpy(p->dev_mat, &p->host_mat, sizeof(DevPipeline), hipMemcpyHostToDevice) : e;
-		e = e == hipSuccess ? hipMemcpy(p->dev_count, &p->host_count, sizeof(DevPipeline), hipMemcpyHostToDevice) : e;
-		if (e != hipSuccess) {
-			ctx->err = std::string("pipeline upload failed: ") + hipGetErrorString(e);
-			rc = POLR_E_HIP;
-		}
 	}
-	if (rc) {
-		polr_pipeline_destroy(p);
-		return rc;
-	}
-	*out = p;
+	HIPCHK(ctx, p->stages_mat.alloc(sd_mat.size()));
+	HIPCHK(ctx, p->stages_count.alloc(sd_count.size()));
+	HIPCHK(ctx, hipMemcpy(p->stages_mat, sd_mat.data(), sd_mat.size() * sizeof(StageDesc), hipMemcpyHostToDevice));
+	HIPCHK(ctx, hipMemcpy(p->stages_count, sd_count.data(), sd_count.size() * sizeof(StageDesc), hipMemcpyHostToDevice));
+	p->host_mat.stages = p->stages_mat;
+	p->host_count.stages = p->stages_count;
+	HIPCHK(ctx, p->dev_mat.alloc(1));
+	HIPCHK(ctx, p->dev_count.alloc(1));
+	HIPCHK(ctx, hipMemcpy(p->dev_mat, &p->host_mat, sizeof(DevPipeline), hipMemcpyHostToDevice));
+	HIPCHK(ctx, hipMemcpy(p->dev_count, &p->host_count, sizeof(DevPipeline), hipMemcpyHostToDevice));
+	*out = guard.release();
 	return POLR_OK;
 }
 
@@ -1534,11 +1313,8 @@ int polr_pipeline_set_selection(polr_pipeline *p, const uint32_t *sel, uint64_t 
 	}
 	polr_ctx *ctx = p->ctx;
 	HIPCHK(ctx, hipSetDevice(ctx->device));
-	if (p->sel_dev && p->sel_owned) {
-		hipFree(p->sel_dev);
-	}
+	p->sel_upload.reset();
 	p->sel_dev = nullptr;
-	p->sel_owned = false;
 	p->scan_n_chunks = 0; // a caller-given selection replaces a scan result (its buffers stay for the next scan)
 	p->scan_valid = false;
 	if (!sel) {
@@ -1547,11 +1323,8 @@ int polr_pipeline_set_selection(polr_pipeline *p, const uint32_t *sel, uint64_t 
 		if (flags & POLR_COL_DEVICE) {
 			p->sel_dev = (uint32_t *)sel;
 		} else {
-			int rc = dev_alloc(ctx, (void **)&p->sel_dev, n_sel * 4, nullptr);
-			if (rc) {
-				return rc;
-			}
-			p->sel_owned = true;
+			HIPCHK(ctx, p->sel_upload.alloc(n_sel));
+			p->sel_dev = p->sel_upload;
 			if (n_sel) {
 				HIPCHK(ctx, hipMemcpy(p->sel_dev, sel, n_sel * 4, hipMemcpyHostToDevice));
 			}
@@ -1579,7 +1352,7 @@ int polr_pipeline_update_probe(polr_pipeline *p, uint32_t col, const void *data,
 		          col, (unsigned long long)n_rows, p->n_probe_cols, (unsigned long long)p->n_probe_rows);
 	}
 	OwnedCol &c = p->probe_cols[col];
-	if (!c.owned) {
+	if (!c.owned()) {
 		POLR_FAIL(ctx, POLR_E_INVALID, "probe column %u is caller-owned device memory", col);
 	}
 	if (valid && !c.valid) {
@@ -1611,68 +1384,6 @@ void polr_pipeline_destroy(polr_pipeline *p) {
 		return;
 	}
 	hipSetDevice(p->ctx->device);
-	for (auto &c : p->probe_cols) {
-		free_col(c);
-	}
-	for (void *h : p->heaps) {
-		hipFree(h);
-	}
-	if (p->probe_cols_dev) {
-		hipFree(p->probe_cols_dev);
-	}
-	if (p->sel_dev && p->sel_owned) {
-		hipFree(p->sel_dev);
-	}
-	if (p->scan_offsets_dev) {
-		hipFree(p->scan_offsets_dev);
-	}
-	if (p->scan_sel) {
-		hipFree(p->scan_sel);
-	}
-	if (p->scan_packed) {
-		hipFree(p->scan_packed);
-		hipFree(p->scan_sums);
-		hipFree(p->scan_totals);
-	}
-	if (p->scan_str_tails) {
-		hipFree(p->scan_str_tails);
-	}
-	if (p->scan_expr_prog) {
-		hipFree(p->scan_expr_prog);
-	}
-	if (p->scan_pass_bits) {
-		hipFree(p->scan_pass_bits);
-	}
-	if (p->dev_mat) {
-		hipFree(p->dev_mat);
-	}
-	if (p->dev_count) {
-		hipFree(p->dev_count);
-	}
-	if (p->stage_ext) {
-		hipFree(p->stage_ext);
-	}
-	if (p->stages_mat) {
-		hipFree(p->stages_mat);
-	}
-	if (p->stages_count) {
-		hipFree(p->stages_count);
-	}
-	if (p->rounds_dev) {
-		hipFree(p->rounds_dev);
-	}
-	if (p->prefix_dev) {
-		hipFree(p->prefix_dev);
-	}
-	if (p->unit_sizes_dev) {
-		hipFree(p->unit_sizes_dev);
-	}
-	if (p->counts_dev) {
-		hipFree(p->counts_dev);
-	}
-	if (p->shards_dev) {
-		hipFree(p->shards_dev);
-	}
 	polr_ctx *ctx_ = p->ctx;
 	delete p;
 	polr_ctx_release(ctx_);
@@ -1693,7 +1404,7 @@ int polr_out_create(polr_pipeline *p, uint32_t chunk_capacity, uint64_t max_chun
 		          (unsigned long long)max_chunks);
 	}
 	HIPCHK(ctx, hipSetDevice(ctx->device));
-	polr_out *o = new polr_out();
+	HandleGuard<polr_out> o(new polr_out());
 	o->pipe = p;
 	o->ctx = polr_ctx_retain(p->ctx);
 	memset(&o->dev, 0, sizeof(o->dev));
@@ -1701,32 +1412,17 @@ int polr_out_create(polr_pipeline *p, uint32_t chunk_capacity, uint64_t max_chun
 	o->dev.max_chunks = (uint32_t)max_chunks;
 	o->dev.W_out = 1 + p->k;
 	o->dev.slot_stride = max_chunks * chunk_capacity;
-	int rc = dev_alloc(ctx, (void **)&o->dev.ids, o->dev.slot_stride * o->dev.W_out * 4, nullptr);
-	if (!rc) {
-		rc = dev_alloc(ctx, (void **)&o->dev.chunk_count, max_chunks * 4, nullptr);
-	}
-	if (!rc) {
-		rc = dev_alloc(ctx, (void **)&o->dev.cursor, 8, nullptr);
-	}
-	if (!rc) {
-		rc = dev_alloc(ctx, (void **)&o->chunk_base, max_chunks * 8, nullptr);
-	}
-	if (!rc) {
-		rc = dev_alloc(ctx, (void **)&o->total_dev, 8, nullptr);
-	}
-	if (!rc) {
-		hipError_t e = hipMemset(o->dev.chunk_count, 0, max_chunks * 4);
-		e = e == hipSuccess ? hipMemset(o->dev.cursor, 0, 8) : e;
-		if (e != hipSuccess) {
-			ctx->err = std::string("output reset failed: ") + hipGetErrorString(e);
-			rc = POLR_E_HIP;
-		}
-	}
-	if (rc) {
-		polr_out_destroy(o);
-		return rc;
-	}
-	*out = o;
+	HIPCHK(ctx, o->ids.alloc(o->dev.slot_stride * o->dev.W_out));
+	HIPCHK(ctx, o->chunk_count.alloc(max_chunks));
+	HIPCHK(ctx, o->cursor.alloc(2));
+	HIPCHK(ctx, o->chunk_base.alloc(max_chunks));
+	HIPCHK(ctx, o->total_dev.alloc(1));
+	o->dev.ids = o->ids;
+	o->dev.chunk_count = o->chunk_count;
+	o->dev.cursor = o->cursor;
+	HIPCHK(ctx, hipMemset(o->dev.chunk_count, 0, max_chunks * 4));
+	HIPCHK(ctx, hipMemset(o->dev.cursor, 0, 8));
+	*out = o.release();
 	return POLR_OK;
 }
 
@@ -1798,16 +1494,11 @@ int polr_out_fetch_ids(polr_out *o, void *stream, uint32_t *dst, uint64_t dst_ro
 	if (o->n_rows == 0) {
 		return POLR_OK;
 	}
-	uint32_t *tmp = nullptr;
-	const uint64_t bytes = o->n_rows * o->dev.W_out * 4;
-	HIPCHK(ctx, hipMalloc((void **)&tmp, bytes));
+	DevBuf<uint32_t> tmp;
+	HIPCHK(ctx, tmp.alloc(o->n_rows * o->dev.W_out));
 	polr_launch_compact_ids(st, o->dev, o->chunk_base, o->n_chunks, tmp);
-	hipError_t e = hipMemcpyAsync(dst, tmp, bytes, hipMemcpyDeviceToHost, st);
-	e = e == hipSuccess ? hipStreamSynchronize(st) : e;
-	hipFree(tmp);
-	if (e != hipSuccess) {
-		POLR_FAIL(ctx, POLR_E_HIP, "fetch ids failed: %s", hipGetErrorString(e));
-	}
+	HIPCHK(ctx, hipMemcpyAsync(dst, tmp, o->n_rows * o->dev.W_out * 4, hipMemcpyDeviceToHost, st));
+	HIPCHK(ctx, hipStreamSynchronize(st));
 	return POLR_OK;
 }
 
@@ -1840,34 +1531,22 @@ int polr_out_materialize(polr_out *o, void *stream, int32_t src_join, uint32_t s
 	}
 	const bool to_device = (dst_flags & POLR_COL_DEVICE) != 0;
 	uint8_t *d_data = (uint8_t *)dst_data, *d_valid = dst_valid;
-	uint8_t *tmp_data = nullptr, *tmp_valid = nullptr;
+	DevBuf<uint8_t> tmp_data, tmp_valid;
 	if (!to_device) {
-		HIPCHK(ctx, hipMalloc((void **)&tmp_data, o->n_rows * src.width));
+		HIPCHK(ctx, tmp_data.alloc(o->n_rows * src.width));
 		d_data = tmp_data;
 		if (dst_valid) {
-			hipError_t e = hipMalloc((void **)&tmp_valid, o->n_rows);
-			if (e != hipSuccess) {
-				hipFree(tmp_data);
-				POLR_FAIL(ctx, POLR_E_HIP, "hipMalloc failed: %s", hipGetErrorString(e));
-			}
+			HIPCHK(ctx, tmp_valid.alloc(o->n_rows));
 			d_valid = tmp_valid;
 		}
 	}
 	polr_launch_gather(st, o->dev, o->chunk_base, o->n_chunks, slot, src, d_data, d_valid);
-	hipError_t e = hipSuccess;
 	if (!to_device) {
-		e = hipMemcpyAsync(dst_data, tmp_data, o->n_rows * src.width, hipMemcpyDeviceToHost, st);
-		if (e == hipSuccess && dst_valid) {
-			e = hipMemcpyAsync(dst_valid, tmp_valid, o->n_rows, hipMemcpyDeviceToHost, st);
+		HIPCHK(ctx, hipMemcpyAsync(dst_data, tmp_data, o->n_rows * src.width, hipMemcpyDeviceToHost, st));
+		if (dst_valid) {
+			HIPCHK(ctx, hipMemcpyAsync(dst_valid, tmp_valid, o->n_rows, hipMemcpyDeviceToHost, st));
 		}
-		e = e == hipSuccess ? hipStreamSynchronize(st) : e;
-		hipFree(tmp_data);
-		if (tmp_valid) {
-			hipFree(tmp_valid);
-		}
-	}
-	if (e != hipSuccess) {
-		POLR_FAIL(ctx, POLR_E_HIP, "materialize failed: %s", hipGetErrorString(e));
+		HIPCHK(ctx, hipStreamSynchronize(st)); // (the temporaries are locals)
 	}
 	return POLR_OK;
 }
@@ -1878,30 +1557,6 @@ void polr_out_destroy(polr_out *o) {
 		return;
 	}
 	hipSetDevice(o->ctx->device);
-	if (o->dev.ids) {
-		hipFree(o->dev.ids);
-	}
-	if (o->dev.chunk_count) {
-		hipFree(o->dev.chunk_count);
-	}
-	if (o->dev.cursor) {
-		hipFree(o->dev.cursor);
-	}
-	if (o->chunk_base) {
-		hipFree(o->chunk_base);
-	}
-	if (o->total_dev) {
-		hipFree(o->total_dev);
-	}
-	if (o->fused_dev) {
-		hipFree(o->fused_dev);
-	}
-	if (o->fused_cells) {
-		hipFree(o->fused_cells);
-	}
-	if (o->fused_dropped) {
-		hipFree(o->fused_dropped);
-	}
 	polr_ctx *ctx_ = o->ctx;
 	delete o;
 	polr_ctx_release(ctx_);
@@ -1992,15 +1647,11 @@ int polr_probe_rounds_async(polr_pipeline *p, void *stream, const polr_round *ro
 		return POLR_OK;
 	}
 	const uint64_t need_shards = (uint64_t)n_rounds * POLR_NSHARD * p->k;
-	if (need_shards > p->shards_cap) {
+	if (need_shards > p->shards_dev.size()) {
 		if (p->shards_dev) {
-			HIPCHK(ctx, hipStreamSynchronize(st));
-			hipFree(p->shards_dev);
-			p->shards_dev = nullptr;
+			HIPCHK(ctx, hipStreamSynchronize(st)); // (the stream may still read what ensure frees)
 		}
-		const uint64_t cap = std::max<uint64_t>(need_shards, 64 * POLR_NSHARD * POLR_KMAX);
-		HIPCHK(ctx, hipMalloc((void **)&p->shards_dev, cap * 8));
-		p->shards_cap = cap;
+		HIPCHK(ctx, p->shards_dev.ensure(std::max<uint64_t>(need_shards, 64 * POLR_NSHARD * POLR_KMAX)));
 	}
 	HIPCHK(ctx, hipMemsetAsync(p->shards_dev, 0, need_shards * 8, st));
 	const bool materialize = out != nullptr;
@@ -2009,21 +1660,15 @@ int polr_probe_rounds_async(polr_pipeline *p, void *stream, const polr_round *ro
 	if (rc) {
 		return rc;
 	}
-	if (n_rounds > p->rounds_cap) {
-		if (p->rounds_dev) {
+	// (three buffers, each with its own capacity: a failed allocation leaves that one empty, and the next call grows it)
+	if (n_rounds > p->rounds_dev.size() || n_rounds + 1 > p->prefix_dev.size() || n_rounds > p->unit_sizes_dev.size()) {
+		if (p->rounds_dev || p->prefix_dev || p->unit_sizes_dev) {
 			HIPCHK(ctx, hipStreamSynchronize(st));
-			hipFree(p->rounds_dev);
-			hipFree(p->prefix_dev);
-			hipFree(p->unit_sizes_dev);
-			p->rounds_dev = nullptr;
-			p->prefix_dev = nullptr;
-			p->unit_sizes_dev = nullptr;
 		}
-		const uint32_t cap = std::max<uint32_t>(n_rounds, 64);
-		HIPCHK(ctx, hipMalloc((void **)&p->rounds_dev, (uint64_t)cap * sizeof(DevRound)));
-		HIPCHK(ctx, hipMalloc((void **)&p->prefix_dev, ((uint64_t)cap + 1) * 8));
-		HIPCHK(ctx, hipMalloc((void **)&p->unit_sizes_dev, (uint64_t)cap * 4));
-		p->rounds_cap = cap;
+		const uint64_t cap = std::max<uint32_t>(n_rounds, 64);
+		HIPCHK(ctx, p->rounds_dev.ensure(cap));
+		HIPCHK(ctx, p->prefix_dev.ensure(cap + 1));
+		HIPCHK(ctx, p->unit_sizes_dev.ensure(cap));
 	}
 	std::vector<uint64_t> prefix(n_rounds + 1);
 	std::vector<uint32_t> usizes(n_rounds, unit_size);
@@ -2068,16 +1713,10 @@ int polr_probe_rounds(polr_pipeline *p, void *stream, const polr_round *rounds, 
 	HIPCHK(ctx, hipSetDevice(ctx->device));
 	hipStream_t st = polr_stream(ctx, stream);
 	const uint64_t need = (uint64_t)n_rounds * p->k;
-	if (need > p->counts_cap) {
-		if (p->counts_dev) {
-			hipFree(p->counts_dev);
-			p->counts_dev = nullptr;
-		}
-		const uint64_t cap = std::max<uint64_t>(need, 256);
-		HIPCHK(ctx, hipMalloc((void **)&p->counts_dev, cap * 8));
-		p->counts_cap = cap;
+	if (need > p->counts_dev.size()) {
+		HIPCHK(ctx, p->counts_dev.ensure(std::max<uint64_t>(need, 256)));
 	}
-	int rc = polr_probe_rounds_async(p, stream, rounds, n_rounds, out, (uint64_t *)p->counts_dev);
+	int rc = polr_probe_rounds_async(p, stream, rounds, n_rounds, out, (uint64_t *)p->counts_dev.get());
 	if (rc) {
 		return rc;
 	}

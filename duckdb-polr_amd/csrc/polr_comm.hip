@@ -84,7 +84,7 @@ struct polr_comm {
 	polr_ctx *ctx = nullptr;
 	rccl_comm_t comm = nullptr;
 	int world = 1, rank = 0;
-	unsigned long long *scratch = nullptr; // device: [0] = size of the metadata blob; then the blob; behind it a status word
+	DevBuf<unsigned long long> scratch; // device: [0] = size of the metadata blob; then the blob; behind it a status word
 	uint64_t bytes_broadcast = 0;
 };
 #define POLR_COMM_SCRATCH 8192
@@ -138,7 +138,7 @@ int polr_comm_create(polr_ctx *ctx, const void *id, int world_size, int rank, po
 		delete c;
 		POLR_FAIL(ctx, POLR_E_HIP, "ncclCommInitRank failed: %s", r.get_error_string(rc));
 	}
-	hipError_t e = hipMalloc((void **)&c->scratch, POLR_COMM_SCRATCH + 64); // (+ the status word of polr_bcast_build)
+	hipError_t e = c->scratch.alloc((POLR_COMM_SCRATCH + 64) / 8); // (+ the status word of polr_bcast_build)
 	if (e != hipSuccess) {
 		r.comm_destroy(c->comm);
 		polr_ctx_release(c->ctx);
@@ -256,7 +256,7 @@ int polr_bcast_build(polr_comm *comm, polr_ht **ht, int root, void *stream) {
 	}
 	// (2) agree: 1 only if every rank is ready for the buffers
 	int status = local_rc == POLR_OK ? 1 : 0;
-	int *status_dev = (int *)((uint8_t *)comm->scratch + POLR_COMM_SCRATCH);
+	int *status_dev = (int *)((uint8_t *)comm->scratch.get() + POLR_COMM_SCRATCH);
 	HIPCHK(ctx, hipMemcpyAsync(status_dev, &status, sizeof(int), hipMemcpyHostToDevice, st));
 	RCCLCHK(ctx, r.all_reduce(status_dev, status_dev, 1, RCCL_INT32, RCCL_MIN, comm->comm, st));
 	int agreed = 0;
@@ -302,9 +302,6 @@ void polr_comm_destroy(polr_comm *comm) {
 	hipSetDevice(comm->ctx->device);
 	if (comm->comm) {
 		rccl().comm_destroy(comm->comm);
-	}
-	if (comm->scratch) {
-		hipFree(comm->scratch);
 	}
 	polr_ctx *ctx_ = comm->ctx;
 	delete comm;

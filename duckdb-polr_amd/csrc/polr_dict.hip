@@ -269,7 +269,7 @@ extern "C" int polr_ht_encode_dictionary(polr_ht *ht, uint32_t payload_col, void
 	if (payload_col >= ht->n_payload) {
 		POLR_FAIL(ctx, POLR_E_INVALID, "payload column %u of %u", payload_col, ht->n_payload);
 	}
-	const OwnedCol src = ht->payload[payload_col];
+	const OwnedCol &src = ht->payload[payload_col]; // (not read after the code column is appended)
 	if (src.width != 16) {
 		POLR_FAIL(ctx, POLR_E_INVALID, "a dictionary is made of a column of 16-byte string cells (this one: %u bytes)", src.width);
 	}
@@ -306,14 +306,13 @@ extern "C" int polr_ht_encode_dictionary(polr_ht *ht, uint32_t payload_col, void
 	const size_t b_rep = capacity * 16, b_hash = capacity * 8, b_state = capacity * 4, b_first = capacity * 4, b_code = capacity * 4,
 	             b_slot = (n * 4 + 15) & ~(size_t)15, b_roc = (n * 4 + 15) & ~(size_t)15, b_sums = ((size_t)n_blocks * 4 + 15) & ~(size_t)15,
 	             b_scalars = 64;
-	uint8_t *base = nullptr;
+	DevBuf<uint8_t> base;
 	OwnedCol codes;
 	codes.width = 4;
 	codes.flags = 0;
-	codes.owned = true;
 	const uint64_t acct = std::max<uint64_t>(n * 4, 16); // (what polr_ht_export reports for a column)
-	HIPCHK(ctx, hipMalloc((void **)&codes.data, acct));
-	hipError_t e = hipMalloc((void **)&base, b_rep + b_hash + b_state + b_first + b_code + b_slot + b_roc + b_sums + b_scalars);
+	HIPCHK(ctx, codes.alloc_data(acct));
+	hipError_t e = base.alloc(b_rep + b_hash + b_state + b_first + b_code + b_slot + b_roc + b_sums + b_scalars);
 	DictTable t;
 	memset(&t, 0, sizeof(t));
 	uint8_t *at = base;
@@ -337,7 +336,7 @@ extern "C" int polr_ht_encode_dictionary(polr_ht *ht, uint32_t payload_col, void
 	t.mask = capacity - 1;
 	uint32_t h_scalars[DICT_SCALARS] = {0, 0, 0, 0};
 	unsigned long long h_long = 0;
-	if (e == hipSuccess && n && src.owned && !src.strings_rebased) {
+	if (e == hipSuccess && n && src.owned() && !src.strings_rebased) {
 		// the library uploaded the column and its heap never came: inline strings only, checked before a pointer is followed
 		unsigned long long *n_long = (unsigned long long *)(scalars + 8);
 		e = hipMemsetAsync(n_long, 0, 8, st);
@@ -374,21 +373,14 @@ extern "C" int polr_ht_encode_dictionary(polr_ht *ht, uint32_t payload_col, void
 	d.has_null = h_scalars[DICT_HAS_NULL];
 	const bool ok = e == hipSuccess && !h_long && !h_scalars[DICT_FULL];
 	if (ok && d.n_codes) {
-		e = hipMalloc((void **)&d.cells, (size_t)d.n_codes * 16);
+		e = d.cells.alloc(d.n_codes);
 		if (e == hipSuccess) {
 			hipLaunchKernelGGL(polr_dict_reps_kernel, dim3((d.n_codes + 255) / 256), dim3(256), 0, st, cells, (const uint32_t *)row_of_code,
-			                   d.n_codes, d.cells);
+			                   d.n_codes, d.cells.get());
 			e = hipStreamSynchronize(st);
 		}
 	}
-	if (base) {
-		hipFree(base);
-	}
-	if (!ok || e != hipSuccess) { // the table is exactly as it was
-		hipFree(codes.data);
-		if (d.cells) {
-			hipFree(d.cells);
-		}
+	if (!ok || e != hipSuccess) { // the table is exactly as it was: codes, d.cells and the scratch go with this scope
 		if (e != hipSuccess) {
 			POLR_FAIL(ctx, POLR_E_HIP, "dictionary encoding failed: %s", hipGetErrorString(e));
 		}
@@ -401,10 +393,10 @@ extern "C" int polr_ht_encode_dictionary(polr_ht *ht, uint32_t payload_col, void
 		POLR_FAIL(ctx, POLR_E_HIP, "dictionary encoding failed: the string table filled up");
 	}
 	// from here on an ordinary payload column: 4 bytes, unsigned, no validity array
-	ht->payload.push_back(codes);
+	ht->payload.push_back(std::move(codes));
 	ht->n_payload++;
 	ht->device_bytes += acct + (uint64_t)d.n_codes * 16;
-	ht->dicts.push_back(d);
+	ht->dicts.push_back(std::move(d));
 	*code_col = d.code_col;
 	*n_codes = d.n_codes;
 	*has_null = d.has_null;
@@ -448,26 +440,15 @@ extern "C" int polr_ht_fetch_dictionary(polr_ht *ht, uint32_t code_col, void *st
 		POLR_FAIL(ctx, POLR_E_OVERFLOW, "the dictionary has %u strings in %llu bytes, the caller made room for %llu and %llu", d->n_codes,
 		          (unsigned long long)used, (unsigned long long)n_offsets, (unsigned long long)str_cap);
 	}
-	uint8_t *arena = nullptr;
-	uint64_t *d_offs = nullptr;
-	hipError_t e = hipMalloc((void **)&arena, used);
-	e = e == hipSuccess ? hipMalloc((void **)&d_offs, (size_t)d->n_codes * 8) : e;
-	e = e == hipSuccess ? hipMemcpyAsync(d_offs, offs.data(), (size_t)d->n_codes * 8, hipMemcpyHostToDevice, st) : e;
-	if (e == hipSuccess) {
-		hipLaunchKernelGGL(polr_dict_records_kernel, dim3((d->n_codes + 255) / 256), dim3(256), 0, st, (const uint4 *)d->cells,
-		                   (const uint64_t *)d_offs, d->n_codes, arena, used);
-		e = hipMemcpyAsync(str_bytes, arena, used, hipMemcpyDeviceToHost, st);
-		e = e == hipSuccess ? hipStreamSynchronize(st) : e;
-	}
-	if (arena) {
-		hipFree(arena);
-	}
-	if (d_offs) {
-		hipFree(d_offs);
-	}
-	if (e != hipSuccess) {
-		POLR_FAIL(ctx, POLR_E_HIP, "dictionary fetch failed: %s", hipGetErrorString(e));
-	}
+	DevBuf<uint8_t> arena;
+	DevBuf<uint64_t> d_offs;
+	HIPCHK(ctx, arena.alloc(used));
+	HIPCHK(ctx, d_offs.alloc(d->n_codes));
+	HIPCHK(ctx, hipMemcpyAsync(d_offs, offs.data(), (size_t)d->n_codes * 8, hipMemcpyHostToDevice, st));
+	hipLaunchKernelGGL(polr_dict_records_kernel, dim3((d->n_codes + 255) / 256), dim3(256), 0, st, (const uint4 *)d->cells.get(),
+	                   (const uint64_t *)d_offs.get(), d->n_codes, arena.get(), used);
+	HIPCHK(ctx, hipMemcpyAsync(str_bytes, arena, used, hipMemcpyDeviceToHost, st));
+	HIPCHK(ctx, hipStreamSynchronize(st));
 	memcpy(offsets, offs.data(), (size_t)d->n_codes * 8);
 	return POLR_OK;
 }

@@ -11,6 +11,7 @@
 
 #include "../../include/polr_hip.h"
 #include "polr_device.h"
+#include "polr_devbuf.h"
 #include "polr_mpx_device.h"
 
 // Shared ownership: every object created on a context (build sides, pipelines, outputs, multiplexers) holds a
@@ -48,13 +49,28 @@ static inline void polr_ctx_release(polr_ctx *ctx) {
 	}
 }
 
+// A column on the device.  data / valid are what the kernels read; the library's own copies are held by own_data /
+// own_valid, and a caller's device memory (POLR_COL_DEVICE) is a column whose owners are empty.
 struct OwnedCol {
 	uint8_t *data = nullptr;
 	uint8_t *valid = nullptr;
 	uint32_t width = 0;
 	uint32_t flags = 0;
-	bool owned = true;
 	bool strings_rebased = false; // string cells point into a device heap (set_string_heaps): a second upload is refused
+	DevBuf<uint8_t> own_data, own_valid;
+	bool owned() const {
+		return own_data.get() != nullptr;
+	}
+	hipError_t alloc_data(uint64_t bytes) {
+		const hipError_t e = own_data.alloc(bytes);
+		data = own_data;
+		return e;
+	}
+	hipError_t alloc_valid(uint64_t bytes) {
+		const hipError_t e = own_valid.alloc(bytes);
+		valid = own_valid;
+		return e;
+	}
 };
 
 // the dictionary of a code column (polr_ht_encode_dictionary, polr_dict.hip): one representative string_t cell per code,
@@ -62,7 +78,7 @@ struct OwnedCol {
 struct DictCol {
 	uint32_t code_col = 0, src_col = 0; // payload columns: the codes, and the VARCHAR column they encode
 	uint32_t n_codes = 0, has_null = 0;
-	uint4 *cells = nullptr;             // device, [n_codes]
+	DevBuf<uint4> cells;                // device, [n_codes]
 };
 
 struct polr_ht {
@@ -73,23 +89,25 @@ struct polr_ht {
 	uint64_t n_rows_in = 0; // rows as uploaded (build row ids index these)
 	uint64_t n_rows = 0;    // rows kept (NULL keys dropped)
 	std::vector<OwnedCol> keys, payload;
-	DevCol *keys_dev = nullptr;    // device array [n_keys]
-	DevCol *payload_dev = nullptr; // device array [n_payload] the probe kernel reads (by build id)
+	DevBuf<DevCol> keys_dev;    // device array [n_keys]
+	DevBuf<DevCol> payload_dev; // device array [n_payload] the probe kernel reads (by build id)
 	uint32_t kind = KIND_NONE;
 	uint32_t key_signed = 0;
+	// the slots of a hash table or the bits of a perfect one: one allocation, table and bits (below) are views of it
+	DevBuf<uint8_t> table_mem;
 	// hash
 	void *table = nullptr;
 	uint64_t capacity = 0;
-	uint32_t *rowids = nullptr;
+	DevBuf<uint32_t> rowids;
 	uint32_t sentinel_start = 0, sentinel_count = 0;
 	uint64_t max_run = 0;
 	// perfect
 	int64_t min_value = 0, max_value = 0;
 	uint64_t range = 0;
 	uint32_t *bits = nullptr;
-	uint32_t *idx_row = nullptr;
+	DevBuf<uint32_t> idx_row;
 	std::vector<OwnedCol> pcols;
-	std::vector<void *> heaps; // string heaps of VARCHAR payload columns (polr_ht_set_payload_heap), owned
+	std::vector<DevBuf<uint8_t>> heaps; // string heaps of VARCHAR payload columns (polr_ht_set_payload_heap), owned
 	std::vector<DictCol> dicts; // dictionaries of the code columns (polr_ht_encode_dictionary), cells owned
 	uint32_t is_dense = 0, has_null = 0;
 	uint64_t device_bytes = 0;
@@ -101,59 +119,54 @@ struct polr_pipeline {
 	uint64_t n_probe_rows = 0;
 	uint64_t n_tuples = 0;
 	std::vector<OwnedCol> probe_cols;
-	std::vector<void *> heaps; // string heaps of VARCHAR probe columns (polr_pipeline_set_probe_heap), owned
-	DevCol *probe_cols_dev = nullptr;
-	uint32_t *sel_dev = nullptr;
-	bool sel_owned = false;
+	std::vector<DevBuf<uint8_t>> heaps; // string heaps of VARCHAR probe columns (polr_pipeline_set_probe_heap), owned
+	DevBuf<DevCol> probe_cols_dev;
+	uint32_t *sel_dev = nullptr; // the selection in use: a view of sel_upload, of scan_sel, or of the caller's device memory
+	DevBuf<uint32_t> sel_upload; // a selection uploaded from the host (polr_pipeline_set_selection)
 	// result of polr_pipeline_scan_filter: boundaries of the (non-empty) source chunks in selection positions
-	uint64_t *scan_offsets_dev = nullptr;
+	DevBuf<uint64_t> scan_offsets_dev;
 	uint64_t scan_n_chunks = 0;
 	uint32_t scan_vector_size = 0;
 	// scan buffers, sized for the worst case and reused by every polr_pipeline_scan_filter call
-	uint32_t *scan_sel = nullptr;
-	unsigned long long *scan_packed = nullptr, *scan_sums = nullptr, *scan_totals = nullptr;
-	uint64_t scan_cap_rows = 0, scan_cap_vec = 0;
-	uint8_t *scan_str_tails = nullptr; // polr_pipeline_scan_filter_str: the VARCHAR constants' bytes beyond 12, re-uploaded per call
+	DevBuf<uint32_t> scan_sel;
+	DevBuf<unsigned long long> scan_packed, scan_sums, scan_totals;
+	DevBuf<uint8_t> scan_str_tails; // polr_pipeline_scan_filter_str: the VARCHAR constants' bytes beyond 12, re-uploaded per call
 	// polr_pipeline_scan_filter_expr: the lowered program (re-uploaded per call) and one pass bit per table row, written
 	// by the counting pass and read by the writing pass; both allocated by the first such call
-	uint8_t *scan_expr_prog = nullptr;
-	size_t scan_expr_cap = 0;
-	unsigned long long *scan_pass_bits = nullptr;
-	uint64_t scan_pass_cap = 0; // words
+	DevBuf<uint8_t> scan_expr_prog;
+	DevBuf<unsigned long long> scan_pass_bits; // words
 	bool scan_valid = false;      // a scan result is installed (selection + chunk boundaries)
 	uint64_t scan_generation = 0; // bumped by every scan: multiplexers must re-attach (polr_mpx_use_scan_chunks)
 	std::vector<polr_ht *> hts;
 	DevPipeline host_count, host_mat; // count-only (narrow tuples) and materialising (all ids) variants
-	DevPipeline *dev_count = nullptr, *dev_mat = nullptr;
-	StageDesc *stages_count = nullptr, *stages_mat = nullptr; // [n_paths][POLR_KMAX] each
-	StageExt *stage_ext = nullptr; // extension records of both variants (those stages that have one)
+	DevBuf<DevPipeline> dev_count, dev_mat;
+	DevBuf<StageDesc> stages_count, stages_mat; // [n_paths][POLR_KMAX] each
+	DevBuf<StageExt> stage_ext; // extension records of both variants (those stages that have one)
 	int blocks_per_cu_count = 0, blocks_per_cu_mat = 0;       // measured residency of the path kernel
 	uint32_t wpb_count = 0, wpb_mat = 0;                      // waves per workgroup (4, or fewer when the LDS queues are wide)
 	uint32_t flat_wpb = 0;                                    // flat pipelines: waves per workgroup of the flat pool kernel
 	bool flat_emit = false;                                   // ... and every join is a perfect table: emitting runs take it too
 	// launch scratch (grown on demand)
-	DevRound *rounds_dev = nullptr;
-	uint64_t *prefix_dev = nullptr;
-	uint32_t *unit_sizes_dev = nullptr;
-	uint32_t rounds_cap = 0;
-	unsigned long long *counts_dev = nullptr;
-	uint64_t counts_cap = 0;
-	unsigned long long *shards_dev = nullptr; // [rounds][POLR_NSHARD][k] scratch of the path kernel
-	uint64_t shards_cap = 0;
+	DevBuf<DevRound> rounds_dev;
+	DevBuf<uint64_t> prefix_dev;
+	DevBuf<uint32_t> unit_sizes_dev;
+	DevBuf<unsigned long long> counts_dev;
+	DevBuf<unsigned long long> shards_dev; // [rounds][POLR_NSHARD][k] scratch of the path kernel
 };
 
 struct polr_out {
 	polr_pipeline *pipe = nullptr;
 	polr_ctx *ctx = nullptr; // (kept so that destroying the object never has to go through the pipeline)
-	DevOut dev;
-	uint64_t *chunk_base = nullptr; // [max_chunks] exclusive prefix, refreshed by stats
-	uint64_t *total_dev = nullptr;
+	DevOut dev; // (ids, chunk_count and cursor are views of the three buffers below)
+	DevBuf<uint32_t> ids, chunk_count, cursor;
+	DevBuf<uint64_t> chunk_base; // [max_chunks] exclusive prefix, refreshed by stats
+	DevBuf<uint64_t> total_dev;
 	uint64_t n_rows = 0;
 	uint32_t n_chunks = 0;
 	bool stats_valid = false;
 	// a fused GROUP BY sink (polr_out_fuse_grouped): the device descriptor, its cell tables, and what the result needs
-	FusedSink *fused_dev = nullptr;
-	unsigned long long *fused_cells = nullptr, *fused_dropped = nullptr;
+	DevBuf<FusedSink> fused_dev;
+	DevBuf<unsigned long long> fused_cells, fused_dropped;
 	uint32_t fused_tables = 0, fused_groups = 0, fused_aggs = 0;
 	uint32_t fused_fn[8] = {};
 	bool fused_has_valid[8] = {};
@@ -172,6 +185,15 @@ struct polr_out {
 		hipError_t e_ = (call_);                                                                                       \
 		if (e_ != hipSuccess) {                                                                                        \
 			POLR_FAIL(ctx_, POLR_E_HIP, "%s failed: %s (%s:%d)", #call_, hipGetErrorString(e_), __FILE__, __LINE__);   \
+		}                                                                                                              \
+	} while (0)
+
+// return a POLR_E_* code as it is (the callee has set the context's error)
+#define POLR_TRY(call_)                                                                                                \
+	do {                                                                                                               \
+		const int rc_ = (call_);                                                                                       \
+		if (rc_) {                                                                                                     \
+			return rc_;                                                                                                \
 		}                                                                                                              \
 	} while (0)
 

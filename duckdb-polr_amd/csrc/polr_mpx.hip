@@ -30,20 +30,23 @@ struct polr_mpx {
 	polr_pipeline *pipe = nullptr;
 	polr_ctx *ctx = nullptr; // (kept so that destroying the object never has to go through the pipeline)
 	polr_mpx_config cfg;
-	DevMpx *dev = nullptr;
-	DevRound *round_dev = nullptr;
-	uint64_t *prefix_dev = nullptr;
-	uint32_t *unit_size_dev = nullptr;
-	uint32_t *ticket_dev = nullptr;
-	polr_mpx_stats *stats_dev = nullptr;
-	unsigned long long *stamps_dev = nullptr; // diagnostic builds only
+	DevBuf<DevMpx> dev;
+	DevBuf<DevRound> round_dev;
+	DevBuf<uint64_t> prefix_dev;
+	DevBuf<uint32_t> unit_size_dev;
+	DevBuf<uint32_t> ticket_dev;
+	DevBuf<polr_mpx_stats> stats_dev;
+	DevBuf<unsigned long long> stamps_dev; // diagnostic builds only
 	uint32_t iter = 0; // launches of the path kernel so far (descriptor slot = iter & 1)
-	unsigned long long *counts_dev = nullptr;
+	DevBuf<unsigned long long> counts_dev;
+	// the chunk boundaries in use: a view of chunk_offsets_own (polr_mpx_set_chunk_offsets), or of the pipeline's scan
+	// result (polr_mpx_use_scan_chunks: from_scan, of the scan scan_generation); nullptr: chunks of cfg.chunk_size tuples
 	uint64_t *chunk_offsets_dev = nullptr;
-	bool chunk_offsets_owned = true; // false: the pipeline's scan result ...
-	uint64_t scan_generation = 0;    // ... of this scan
-	uint32_t *log_path = nullptr;
-	uint64_t *log_tuples = nullptr, *log_inter = nullptr;
+	DevBuf<uint64_t> chunk_offsets_own;
+	bool from_scan = false;
+	uint64_t scan_generation = 0;
+	DevBuf<uint32_t> log_path;
+	DevBuf<uint64_t> log_tuples, log_inter;
 	volatile uint32_t *done_host = nullptr;    // pinned, mapped: the words the device reports in (PolrHostWord)
 	volatile uint32_t *progress_dev = nullptr; // the device's view of done_host
 	uint32_t steps_base = 0;
@@ -54,14 +57,13 @@ struct polr_mpx {
 	uint32_t wide0_mask = 0;
 	uint64_t n_chunks = 0;
 	// resident launches
-	ResidentSync *sync_dev = nullptr;  // arrival counters of this executor
-	char *execs_dev = nullptr;         // run header + executor descriptors + morsel cursor (owned by the first multiplexer of a run)
-	uint32_t execs_cap = 0;
+	DevBuf<ResidentSync> sync_dev;     // arrival counters of this executor
+	DevBuf<char> execs_dev;            // run header + executor descriptors + morsel cursor (owned by the first multiplexer of a run)
+	uint32_t execs_cap = 0;            // executor descriptors execs_dev is laid out for
 	std::vector<char> execs_host;      // what execs_dev holds (a pass that repeats the last one re-sends nothing)
-	PoolSync *pool_dev = nullptr;      // unit rings of the runs this multiplexer leads
-	uint32_t *share_dev = nullptr;     // work sharing of the generic pipeline: one record per probe wave + its flag
-	size_t share_bytes = 0;
-	uint32_t pool_lo_cap = 0, pool_hi_cap = 0;
+	DevBuf<uint8_t> pool_dev;          // unit rings of the runs this multiplexer leads: a PoolSync and the rings behind it
+	DevBuf<uint32_t> share_dev;        // work sharing of the generic pipeline: one record per probe wave + its flag
+	uint32_t pool_lo_cap = 0, pool_hi_cap = 0; // ring capacities pool_dev is laid out for
 	bool pool_dirty = false;           // a run was given up: rings and tickets are re-initialised before the next one
 	polr_mpx *leader = nullptr;        // the first multiplexer of the last pool run this one took part in (owns the rings)
 	uint32_t res_epoch = 0;
@@ -70,8 +72,7 @@ struct polr_mpx {
 	bool stats_in_host = false;
 	// range stealing (polr_mpx_run_resident_stealing): the claim words of the runs this multiplexer leads + the
 	// executors' counters behind them, and what they are initialised from with every launch
-	unsigned long long *steal_dev = nullptr;
-	uint32_t steal_cap = 0;
+	DevBuf<unsigned long long> steal_dev; // [5 per executor]
 	std::vector<unsigned long long> steal_host;
 	bool steal_run = false;            // the last run of this multiplexer was a stealing run (its counters are in done_host)
 	polr_steal_stats steal_stats = {}; // picked up by polr_mpx_finish(_many)
@@ -99,21 +100,6 @@ static hipError_t adopt_stream(polr_mpx *m, hipStream_t st) {
 	}
 	m->last_stream = st;
 	return e;
-}
-
-// Replace the device buffer *buf (capacity *cap, in the caller's units) by one of `bytes` bytes and capacity new_cap, for
-// work about to be enqueued on `st`.  What is queued on `st` may still use the old one: synchronise before freeing it.
-template <typename T, typename Cap>
-static int grow_buffer(polr_ctx *ctx, hipStream_t st, T **buf, Cap *cap, Cap new_cap, size_t bytes) {
-	if (*buf) {
-		HIPCHK(ctx, hipStreamSynchronize(st));
-		hipFree(*buf);
-		*buf = nullptr;
-		*cap = 0;
-	}
-	HIPCHK(ctx, hipMalloc((void **)buf, bytes));
-	*cap = new_cap;
-	return POLR_OK;
 }
 
 // after the stream of a run has been synchronised: the stealing counters its router left in the pinned words
@@ -268,25 +254,25 @@ int polr_mpx_create(polr_pipeline *p, const polr_mpx_config *cfg, polr_mpx **out
 	m->cfg = *cfg;
 	m->n_chunks = (p->n_tuples + cfg->chunk_size - 1) / cfg->chunk_size;
 	const uint64_t max_log = cfg->log_rounds ? std::max<uint64_t>(cfg->max_log_rounds, 1) : 1;
-	hipError_t e = hipMalloc((void **)&m->dev, sizeof(DevMpx));
-	e = e == hipSuccess ? hipMalloc((void **)&m->round_dev, 2 * sizeof(DevRound)) : e;
-	e = e == hipSuccess ? hipMalloc((void **)&m->prefix_dev, 4 * 8) : e;
-	e = e == hipSuccess ? hipMalloc((void **)&m->unit_size_dev, 2 * 4) : e;
-	e = e == hipSuccess ? hipMalloc((void **)&m->ticket_dev, 64) : e;
+	hipError_t e = m->dev.alloc(1);
+	e = e == hipSuccess ? m->round_dev.alloc(2) : e;
+	e = e == hipSuccess ? m->prefix_dev.alloc(4) : e;
+	e = e == hipSuccess ? m->unit_size_dev.alloc(2) : e;
+	e = e == hipSuccess ? m->ticket_dev.alloc(16) : e;
 	e = e == hipSuccess ? hipStreamCreateWithFlags(&m->own_stream, hipStreamNonBlocking) : e;
 	e = e == hipSuccess ? hipMemset(m->ticket_dev, 0, 64) : e;
 	// two counter banks (a resident run keeps up to two rounds in flight; everything else uses the first)
-	e = e == hipSuccess ? hipMalloc((void **)&m->counts_dev, POLR_SLOTS * POLR_NSHARD * POLR_KMAX * 8) : e;
-	e = e == hipSuccess ? hipMalloc((void **)&m->log_path, max_log * 4) : e;
-	e = e == hipSuccess ? hipMalloc((void **)&m->log_tuples, max_log * 8) : e;
-	e = e == hipSuccess ? hipMalloc((void **)&m->log_inter, max_log * 8) : e;
+	e = e == hipSuccess ? m->counts_dev.alloc(POLR_SLOTS * POLR_NSHARD * POLR_KMAX) : e;
+	e = e == hipSuccess ? m->log_path.alloc(max_log) : e;
+	e = e == hipSuccess ? m->log_tuples.alloc(max_log) : e;
+	e = e == hipSuccess ? m->log_inter.alloc(max_log) : e;
 	e = e == hipSuccess ? hipHostMalloc((void **)&m->done_host, POLR_HOST_WORDS_BYTES, hipHostMallocMapped) : e;
 	if (e == hipSuccess) {
 		memset((void *)m->done_host, 0, POLR_HOST_WORDS_BYTES);
 		e = hipHostGetDevicePointer((void **)&m->progress_dev, (void *)m->done_host, 0);
 	}
 	e = e == hipSuccess ? hipMemset(m->counts_dev, 0, POLR_SLOTS * POLR_NSHARD * POLR_KMAX * 8) : e;
-	e = e == hipSuccess ? hipMalloc((void **)&m->sync_dev, sizeof(ResidentSync)) : e;
+	e = e == hipSuccess ? m->sync_dev.alloc(1) : e;
 	e = e == hipSuccess ? hipHostMalloc((void **)&m->stats_host, sizeof(polr_mpx_stats), hipHostMallocMapped) : e;
 	e = e == hipSuccess ? hipHostGetDevicePointer((void **)&m->stats_host_dev, m->stats_host, 0) : e;
 	e = e == hipSuccess ? hipMemset(m->sync_dev, 0, sizeof(ResidentSync)) : e;
@@ -322,11 +308,9 @@ int polr_mpx_set_chunk_offsets(polr_mpx *m, const uint64_t *offsets, uint64_t n_
 	}
 	polr_ctx *ctx = m->pipe->ctx;
 	HIPCHK(ctx, hipSetDevice(ctx->device));
-	if (m->chunk_offsets_dev && m->chunk_offsets_owned) {
-		hipFree(m->chunk_offsets_dev);
-	}
+	m->chunk_offsets_own.reset();
 	m->chunk_offsets_dev = nullptr;
-	m->chunk_offsets_owned = true;
+	m->from_scan = false;
 	if (!offsets) {
 		m->n_chunks = (m->pipe->n_tuples + m->cfg.chunk_size - 1) / m->cfg.chunk_size;
 		return POLR_OK;
@@ -337,7 +321,8 @@ int polr_mpx_set_chunk_offsets(polr_mpx *m, const uint64_t *offsets, uint64_t n_
 			          (unsigned long long)m->pipe->n_tuples);
 		}
 	}
-	HIPCHK(ctx, hipMalloc((void **)&m->chunk_offsets_dev, (n_chunks + 1) * 8));
+	HIPCHK(ctx, m->chunk_offsets_own.alloc(n_chunks + 1));
+	m->chunk_offsets_dev = m->chunk_offsets_own;
 	HIPCHK(ctx, hipMemcpy(m->chunk_offsets_dev, offsets, (n_chunks + 1) * 8, hipMemcpyHostToDevice));
 	m->n_chunks = n_chunks;
 	return POLR_OK;
@@ -455,12 +440,12 @@ int polr_mpx_use_scan_chunks(polr_mpx *m) {
 	if (!p->scan_valid) {
 		POLR_FAIL(ctx, POLR_E_INVALID, "no scan result: call polr_pipeline_scan_filter first");
 	}
-	if (m->chunk_offsets_dev && m->chunk_offsets_owned) {
+	if (m->chunk_offsets_own) {
 		HIPCHK(ctx, hipSetDevice(ctx->device));
-		hipFree(m->chunk_offsets_dev);
+		m->chunk_offsets_own.reset();
 	}
 	m->chunk_offsets_dev = p->scan_offsets_dev;
-	m->chunk_offsets_owned = false;
+	m->from_scan = true;
 	m->scan_generation = p->scan_generation;
 	m->n_chunks = p->scan_n_chunks;
 	return POLR_OK;
@@ -483,7 +468,7 @@ static int run_begin(RunState &rs, polr_mpx *m, void *stream, uint64_t chunk_beg
                      polr_out *out, uint32_t share) {
 	polr_pipeline *p = m->pipe;
 	polr_ctx *ctx = p->ctx;
-	if (!m->chunk_offsets_owned && (!p->scan_valid || m->scan_generation != p->scan_generation)) {
+	if (m->from_scan && (!p->scan_valid || m->scan_generation != p->scan_generation)) {
 		POLR_FAIL(ctx, POLR_E_INVALID, "the pipeline was scanned again: call polr_mpx_use_scan_chunks");
 	}
 	if (chunk_begin > chunk_end || chunk_end > m->n_chunks) {
@@ -504,7 +489,7 @@ static int run_begin(RunState &rs, polr_mpx *m, void *stream, uint64_t chunk_beg
 	}
 #ifdef POLR_DIAG_STAMPS
 	if (!m->stamps_dev) {
-		HIPCHK(ctx, hipMalloc((void **)&m->stamps_dev, 4096 * 8 * 8));
+		HIPCHK(ctx, m->stamps_dev.alloc(4096 * 8));
 		HIPCHK(ctx, hipMemset(m->stamps_dev, 0, 4096 * 8 * 8));
 	}
 #endif
@@ -700,7 +685,7 @@ static int validate_request(polr_mpx **ms, uint32_t n, const ResidentRequest &rq
 		if (!ms[i] || ms[i]->pipe != p) {
 			return POLR_E_INVALID;
 		}
-		if (!ms[i]->chunk_offsets_owned && (!p->scan_valid || ms[i]->scan_generation != p->scan_generation)) {
+		if (ms[i]->from_scan && (!p->scan_valid || ms[i]->scan_generation != p->scan_generation)) {
 			POLR_FAIL(ctx, POLR_E_INVALID, "the pipeline was scanned again: call polr_mpx_use_scan_chunks");
 		}
 		for (uint32_t r = 0; r < (rq.morsel_chunks ? 1u : rq.ranges_per_exec); r++) {
@@ -762,14 +747,15 @@ static int plan_run(polr_ctx *ctx, const PoolShape &sh, uint32_t n, uint64_t n_t
 // the buffers of the runs `m0` leads, large enough for this one: descriptors, work-sharing records, unit rings, claim words
 static int ensure_run_buffers(polr_mpx *m0, hipStream_t st, uint32_t n, const PoolPlan &pl, bool stealing) {
 	polr_ctx *ctx = m0->pipe->ctx;
-	if (m0->execs_cap < n) {
+	// (growing: what is queued on st may still use the old buffer, so the stream is synchronised before ensure frees it)
+	if (!m0->execs_dev || m0->execs_cap < n) {
 		const uint32_t cap = std::max<uint32_t>(n, 8);
 		m0->execs_host.clear();
-		int rc = grow_buffer(ctx, st, &m0->execs_dev, &m0->execs_cap, cap,
-		                     POOL_HEADER_BYTES + (size_t)cap * sizeof(ResidentExec) + 64);
-		if (rc) {
-			return rc;
+		if (m0->execs_dev) {
+			HIPCHK(ctx, hipStreamSynchronize(st));
 		}
+		HIPCHK(ctx, m0->execs_dev.ensure(POOL_HEADER_BYTES + (size_t)cap * sizeof(ResidentExec) + 64));
+		m0->execs_cap = cap;
 	}
 	if (m0->done_host[POLR_HW_GIVEN_UP]) {
 		// an earlier run on these rings was given up (whoever finished it): probe waves left holding tickets
@@ -782,14 +768,14 @@ static int ensure_run_buffers(polr_mpx *m0, hipStream_t st, uint32_t n, const Po
 	// wave that took it) unless a run was given up
 	if (pl.share_after != 0xFFFFFFFFu) {
 		const size_t need = ((size_t)pl.pool_waves * pl.share_stride + pl.pool_waves) * sizeof(uint32_t);
-		if (m0->share_bytes < need) {
-			int rc = grow_buffer(ctx, st, &m0->share_dev, &m0->share_bytes, need, need);
-			if (rc) {
-				return rc;
+		if (!m0->share_dev || m0->share_dev.bytes() < need) {
+			if (m0->share_dev) {
+				HIPCHK(ctx, hipStreamSynchronize(st));
 			}
+			HIPCHK(ctx, m0->share_dev.ensure(need / sizeof(uint32_t)));
 			HIPCHK(ctx, hipMemsetAsync(m0->share_dev, 0, need, st));
 		} else if (m0->pool_dirty) {
-			HIPCHK(ctx, hipMemsetAsync(m0->share_dev, 0, m0->share_bytes, st));
+			HIPCHK(ctx, hipMemsetAsync(m0->share_dev, 0, m0->share_dev.bytes(), st));
 		}
 	}
 	// unit rings: never smaller than before; zeroed when new or when a run on them was given up
@@ -798,19 +784,21 @@ static int ensure_run_buffers(polr_mpx *m0, hipStream_t st, uint32_t n, const Po
 		const uint32_t lc = std::max(pl.lo_cap, m0->pool_lo_cap), hc = std::max(pl.hi_cap, m0->pool_hi_cap);
 		const size_t bytes = sizeof(PoolSync) + (size_t)POLR_POOL_RINGS * (2 * (size_t)lc + hc) * sizeof(PoolEntry);
 		if (!m0->pool_dev || too_small) {
-			int rc = grow_buffer(ctx, st, &m0->pool_dev, &m0->pool_lo_cap, lc, bytes);
-			if (rc) {
-				return rc;
+			if (m0->pool_dev) {
+				HIPCHK(ctx, hipStreamSynchronize(st));
 			}
+			HIPCHK(ctx, m0->pool_dev.ensure(bytes));
 		}
 		HIPCHK(ctx, hipMemsetAsync(m0->pool_dev, 0, bytes, st));
 		m0->pool_lo_cap = lc;
 		m0->pool_hi_cap = hc;
 		m0->pool_dirty = false;
 	}
-	if (stealing && m0->steal_cap < n) {
-		const uint32_t cap = std::max<uint32_t>(n, 8);
-		return grow_buffer(ctx, st, &m0->steal_dev, &m0->steal_cap, cap, (size_t)cap * 5 * sizeof(unsigned long long));
+	if (stealing && m0->steal_dev.size() < (uint64_t)n * 5) {
+		if (m0->steal_dev) {
+			HIPCHK(ctx, hipStreamSynchronize(st));
+		}
+		HIPCHK(ctx, m0->steal_dev.ensure((uint64_t)std::max<uint32_t>(n, 8) * 5));
 	}
 	return POLR_OK;
 }
@@ -828,7 +816,7 @@ static std::vector<char> fill_descriptors(polr_mpx **ms, uint32_t n, const Resid
 	PoolRun *hr = (PoolRun *)host.data();
 	ResidentExec *ex = (ResidentExec *)(host.data() + POOL_HEADER_BYTES);
 	const bool sharing = pl.share_after != 0xFFFFFFFFu;
-	hr->sync = m0->pool_dev;
+	hr->sync = (PoolSync *)m0->pool_dev.get();
 	hr->n_exec = n;
 	hr->n_router_blocks = pl.n_router_blocks;
 	hr->routers_per_block = pl.routers_per_block;
@@ -936,9 +924,9 @@ static int enqueue_run(polr_mpx **ms, hipStream_t st, uint32_t n, const Resident
 	const ResidentExec *execs_dev = (const ResidentExec *)(m0->execs_dev + POOL_HEADER_BYTES);
 	hipError_t e =
 	    sh.flat ? polr_launch_pool_flat_kernel(dp.k, pl.n_blocks, sh.wpb, dp.lds_table_dwords, st, p->dev_count, execs_dev,
-	                                           (PoolRun *)m0->execs_dev, dout, materialize, sh.fused_words)
+	                                           (PoolRun *)m0->execs_dev.get(), dout, materialize, sh.fused_words)
 	            : polr_launch_pool_kernel(sh.wq, dp.k, pl.n_blocks, st, materialize ? p->dev_mat : p->dev_count, execs_dev,
-	                                      (PoolRun *)m0->execs_dev, dout, dp.ext != 0);
+	                                      (PoolRun *)m0->execs_dev.get(), dout, dp.ext != 0);
 	if (e != hipSuccess) {
 		POLR_FAIL(ctx, POLR_E_HIP, "pool kernel launch failed: %s", hipGetErrorString(e));
 	}
@@ -1119,11 +1107,8 @@ static hipError_t enqueue_close(polr_mpx *m, hipStream_t st, polr_mpx_stats *sta
 	if (m->stats_in_host) {
 		return hipSuccess;
 	}
-	if (!m->stats_dev) {
-		hipError_t e = hipMalloc((void **)&m->stats_dev, sizeof(polr_mpx_stats));
-		if (e != hipSuccess) {
-			return e;
-		}
+	if (hipError_t e = m->stats_dev.ensure(1)) {
+		return e;
 	}
 	hipLaunchKernelGGL(polr_mpx_finish_kernel, dim3(1), dim3(64), 0, st, m->dev, m->counts_dev, m->pipe->k, m->stats_dev);
 	return hipMemcpyAsync(stats, m->stats_dev, sizeof(polr_mpx_stats), hipMemcpyDeviceToHost, st);
@@ -1262,63 +1247,15 @@ void polr_mpx_destroy(polr_mpx *m) {
 		return;
 	}
 	hipSetDevice(m->ctx->device);
-	if (m->dev) {
-		hipFree(m->dev);
-	}
-	if (m->round_dev) {
-		hipFree(m->round_dev);
-	}
-	if (m->prefix_dev) {
-		hipFree(m->prefix_dev);
-	}
-	if (m->unit_size_dev) {
-		hipFree(m->unit_size_dev);
-	}
-	if (m->ticket_dev) {
-		hipFree(m->ticket_dev);
-	}
 	if (m->own_stream) {
 		hipStreamSynchronize(m->own_stream);
 		hipStreamDestroy(m->own_stream);
 	}
-	if (m->stats_dev) {
-		hipFree(m->stats_dev);
-	}
-	if (m->counts_dev) {
-		hipFree(m->counts_dev);
-	}
-	if (m->chunk_offsets_dev && m->chunk_offsets_owned) {
-		hipFree(m->chunk_offsets_dev);
-	}
-	if (m->log_path) {
-		hipFree(m->log_path);
-	}
-	if (m->log_tuples) {
-		hipFree(m->log_tuples);
-	}
-	if (m->log_inter) {
-		hipFree(m->log_inter);
-	}
 	if (m->done_host) {
 		hipHostFree((void *)m->done_host);
 	}
-	if (m->sync_dev) {
-		hipFree(m->sync_dev);
-	}
 	if (m->stats_host) {
 		hipHostFree(m->stats_host);
-	}
-	if (m->execs_dev) {
-		hipFree(m->execs_dev);
-	}
-	if (m->share_dev) {
-		hipFree(m->share_dev);
-	}
-	if (m->steal_dev) {
-		hipFree(m->steal_dev);
-	}
-	if (m->pool_dev) {
-		hipFree(m->pool_dev);
 	}
 	for (auto e : m->ev_start) {
 		hipEventDestroy(e);

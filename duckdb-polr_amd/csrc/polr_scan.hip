@@ -695,23 +695,18 @@ static int scan_lip_set(polr_pipeline *p, uint32_t lip_joins, DevLipSet &lip) {
 static int scan_check_heap(polr_pipeline *p, hipStream_t st, uint32_t col) {
 	polr_ctx *ctx = p->ctx;
 	const OwnedCol &c = p->probe_cols[col];
-	if (c.strings_rebased || !c.owned || p->n_probe_rows == 0) {
+	if (c.strings_rebased || !c.owned() || p->n_probe_rows == 0) {
 		return POLR_OK;
 	}
-	unsigned long long *n_long = nullptr, h_long = 0;
-	HIPCHK(ctx, hipMalloc((void **)&n_long, 8));
-	hipError_t e = hipMemsetAsync(n_long, 0, 8, st);
-	if (e == hipSuccess) {
-		const uint32_t grid = (uint32_t)std::min<uint64_t>((p->n_probe_rows + 255) / 256, (uint64_t)ctx->n_cus * 8);
-		hipLaunchKernelGGL(polr_tscan_count_long_kernel, dim3(grid), dim3(256), 0, st, (const uint8_t *)c.data,
-		                   (const uint8_t *)c.valid, p->n_probe_rows, n_long);
-		e = hipMemcpyAsync(&h_long, n_long, 8, hipMemcpyDeviceToHost, st);
-		e = e == hipSuccess ? hipStreamSynchronize(st) : e;
-	}
-	hipFree(n_long);
-	if (e != hipSuccess) {
-		POLR_FAIL(ctx, POLR_E_HIP, "string column check failed: %s", hipGetErrorString(e));
-	}
+	DevBuf<unsigned long long> n_long;
+	unsigned long long h_long = 0;
+	HIPCHK(ctx, n_long.alloc(1));
+	HIPCHK(ctx, hipMemsetAsync(n_long, 0, 8, st));
+	const uint32_t grid = (uint32_t)std::min<uint64_t>((p->n_probe_rows + 255) / 256, (uint64_t)ctx->n_cus * 8);
+	hipLaunchKernelGGL(polr_tscan_count_long_kernel, dim3(grid), dim3(256), 0, st, (const uint8_t *)c.data,
+	                   (const uint8_t *)c.valid, p->n_probe_rows, n_long.get());
+	HIPCHK(ctx, hipMemcpyAsync(&h_long, n_long, 8, hipMemcpyDeviceToHost, st));
+	HIPCHK(ctx, hipStreamSynchronize(st));
 	if (h_long) {
 		POLR_FAIL(ctx, POLR_E_INVALID,
 		          "filter column %u: %llu rows hold strings longer than 12 bytes, but the column's heap was never put on the "
@@ -724,35 +719,17 @@ static int scan_check_heap(polr_pipeline *p, hipStream_t st, uint32_t col) {
 // the scan's scratch and result buffers, grown to the table and the vector count (see scan_filter_run)
 static int scan_buffers(polr_pipeline *p, uint64_t n_rows, uint64_t n_vec, uint64_t n_blocks) {
 	polr_ctx *ctx = p->ctx;
-	if (p->scan_cap_rows < n_rows || p->scan_cap_vec < n_vec) {
-		if (p->scan_packed) {
-			hipFree(p->scan_packed);
-			hipFree(p->scan_sums);
-			hipFree(p->scan_totals);
-			p->scan_packed = p->scan_sums = p->scan_totals = nullptr;
-		}
-		if (p->scan_sel) {
-			if (p->sel_dev == p->scan_sel) {
-				p->sel_dev = nullptr;
-			}
-			hipFree(p->scan_sel);
-			p->scan_sel = nullptr;
-		}
-		if (p->scan_offsets_dev) {
-			hipFree(p->scan_offsets_dev);
-			p->scan_offsets_dev = nullptr;
-		}
-		hipError_t ea = hipMalloc((void **)&p->scan_packed, std::max<uint64_t>(n_vec, 1) * 8);
-		ea = ea == hipSuccess ? hipMalloc((void **)&p->scan_sums, std::max<uint64_t>(n_blocks, 1) * 8) : ea;
-		ea = ea == hipSuccess ? hipMalloc((void **)&p->scan_totals, 16) : ea;
-		ea = ea == hipSuccess ? hipMalloc((void **)&p->scan_sel, std::max<uint64_t>(n_rows, 1) * 4) : ea;
-		ea = ea == hipSuccess ? hipMalloc((void **)&p->scan_offsets_dev, (n_vec + 1) * 8) : ea;
-		if (ea != hipSuccess) {
-			p->scan_cap_rows = p->scan_cap_vec = 0;
-			POLR_FAIL(ctx, POLR_E_HIP, "scan filter buffers: %s", hipGetErrorString(ea));
-		}
-		p->scan_cap_rows = n_rows;
-		p->scan_cap_vec = n_vec;
+	const uint32_t *old_sel = p->scan_sel;
+	hipError_t e = p->scan_packed.ensure(std::max<uint64_t>(n_vec, 1));
+	e = e == hipSuccess ? p->scan_sums.ensure(std::max<uint64_t>(n_blocks, 1)) : e;
+	e = e == hipSuccess ? p->scan_totals.ensure(2) : e;
+	e = e == hipSuccess ? p->scan_sel.ensure(std::max<uint64_t>(n_rows, 1)) : e;
+	e = e == hipSuccess ? p->scan_offsets_dev.ensure(n_vec + 1) : e;
+	if (p->sel_dev && p->sel_dev == old_sel && old_sel != p->scan_sel) {
+		p->sel_dev = nullptr; // (the selection in use was the scan result that just went)
+	}
+	if (e != hipSuccess) {
+		POLR_FAIL(ctx, POLR_E_HIP, "scan filter buffers: %s", hipGetErrorString(e));
 	}
 	return POLR_OK;
 }
@@ -761,11 +738,8 @@ static int scan_install(polr_pipeline *p, uint32_t vector_size, const uint64_t *
 	polr_ctx *ctx = p->ctx;
 	uint32_t *sel = p->scan_sel;
 	// install: the selection is the pipeline's source now (the buffers stay the pipeline's scan buffers)
-	if (p->sel_dev && p->sel_owned && p->sel_dev != p->scan_sel) {
-		hipFree(p->sel_dev);
-	}
+	p->sel_upload.reset();
 	p->sel_dev = sel;
-	p->sel_owned = false; // (freed as scan_sel)
 	p->n_tuples = h_tot[0];
 	p->scan_valid = true;
 	p->scan_generation++;
@@ -895,9 +869,7 @@ static int scan_filter_run(polr_pipeline *p, void *stream, const polr_scan_filte
 		}
 	}
 	if (!tails.empty()) {
-		if (!p->scan_str_tails) {
-			HIPCHK(ctx, hipMalloc((void **)&p->scan_str_tails, (size_t)POLR_MAX_FILTERS * POLR_MAX_FILTER_STRING));
-		}
+		HIPCHK(ctx, p->scan_str_tails.ensure((size_t)POLR_MAX_FILTERS * POLR_MAX_FILTER_STRING));
 		// (no scan kernel is in flight: every scan call ends with a synchronisation of its stream)
 		HIPCHK(ctx, hipMemcpy(p->scan_str_tails, tails.data(), tails.size(), hipMemcpyHostToDevice));
 	}
@@ -1006,16 +978,7 @@ static int scan_filter_expr_run(polr_pipeline *p, void *stream, const polr_filte
 	if (!pl.bytes.empty()) {
 		memcpy(blob.data() + bytes_at, pl.bytes.data(), pl.bytes.size());
 	}
-	if (p->scan_expr_cap < blob.size()) {
-		if (p->scan_expr_prog) {
-			hipFree(p->scan_expr_prog);
-			p->scan_expr_prog = nullptr;
-			p->scan_expr_cap = 0;
-		}
-		const size_t cap = std::max<size_t>(blob.size(), 8192);
-		HIPCHK(ctx, hipMalloc((void **)&p->scan_expr_prog, cap));
-		p->scan_expr_cap = cap;
-	}
+	HIPCHK(ctx, p->scan_expr_prog.ensure(std::max<size_t>(blob.size(), 8192)));
 	// (no scan kernel is in flight: every scan call ends with a synchronisation of its stream)
 	HIPCHK(ctx, hipMemcpy(p->scan_expr_prog, blob.data(), blob.size(), hipMemcpyHostToDevice));
 	DevFxProg px;
@@ -1052,15 +1015,7 @@ static int scan_filter_expr_run(polr_pipeline *p, void *stream, const polr_filte
 	}
 	// the pass bits: one word per 64-row step of a vector
 	const uint64_t n_words = n_vec * (((uint64_t)vector_size + 63) / 64);
-	if (p->scan_pass_cap < n_words) {
-		if (p->scan_pass_bits) {
-			hipFree(p->scan_pass_bits);
-			p->scan_pass_bits = nullptr;
-			p->scan_pass_cap = 0;
-		}
-		HIPCHK(ctx, hipMalloc((void **)&p->scan_pass_bits, n_words * 8));
-		p->scan_pass_cap = n_words;
-	}
+	HIPCHK(ctx, p->scan_pass_bits.ensure(n_words));
 	unsigned long long *packed = p->scan_packed, *sums = p->scan_sums, *totals = p->scan_totals;
 	uint64_t h_tot[2] = {0, 0};
 	hipError_t e = hipSuccess;
@@ -1069,12 +1024,12 @@ static int scan_filter_expr_run(polr_pipeline *p, void *stream, const polr_filte
 		const uint32_t grid = (uint32_t)std::min<uint64_t>((n_vec + waves_per_block - 1) / waves_per_block,
 		                                                   (uint64_t)ctx->n_cus * 8);
 		hipLaunchKernelGGL(polr_tscan_count_expr_kernel, dim3(grid), dim3(256), 0, st, px, lip, n_rows, vector_size, n_vec, packed,
-		                   p->scan_pass_bits);
+		                   p->scan_pass_bits.get());
 		hipLaunchKernelGGL(polr_tscan_block_sums_kernel, dim3((uint32_t)n_blocks), dim3(1024), 0, st, packed, n_vec, sums);
 		hipLaunchKernelGGL(polr_tscan_sums_kernel, dim3(1), dim3(1024), 0, st, sums, n_blocks, totals);
 		hipLaunchKernelGGL(polr_tscan_apply_kernel, dim3((uint32_t)n_blocks), dim3(1024), 0, st, packed, n_vec, sums);
-		hipLaunchKernelGGL(polr_tscan_write_bits_kernel, dim3(grid), dim3(256), 0, st, (const unsigned long long *)p->scan_pass_bits,
-		                   n_rows, vector_size, n_vec, (const unsigned long long *)packed, p->scan_sel, p->scan_offsets_dev,
+		hipLaunchKernelGGL(polr_tscan_write_bits_kernel, dim3(grid), dim3(256), 0, st, (const unsigned long long *)p->scan_pass_bits.get(),
+		                   n_rows, vector_size, n_vec, (const unsigned long long *)packed, p->scan_sel.get(), p->scan_offsets_dev.get(),
 		                   (const unsigned long long *)totals);
 		e = hipMemcpyAsync(h_tot, totals, 16, hipMemcpyDeviceToHost, st);
 		e = e == hipSuccess ? hipStreamSynchronize(st) : e;

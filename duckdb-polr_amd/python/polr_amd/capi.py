@@ -44,6 +44,7 @@ EXPORTS = [
     "polr_mpx_run_resident_stealing", "polr_mpx_steal_stats",
     "polr_pipeline_scan_filter_str",
     "polr_pipeline_scan_filter_expr",
+    "polr_device_bytes_live",
 ]
 
 
@@ -302,6 +303,8 @@ def load():
     vp, u32, u64, i32, i64 = C.c_void_p, C.c_uint32, C.c_uint64, C.c_int32, C.c_int64
     P = C.POINTER
     L.polr_abi_version.restype = C.c_int
+    L.polr_device_bytes_live.argtypes = []
+    L.polr_device_bytes_live.restype = u64
     L.polr_ctx_create.argtypes = [C.c_int, P(vp)]
     L.polr_ctx_destroy.argtypes = [vp]
     L.polr_ctx_destroy.restype = None
@@ -385,6 +388,11 @@ def load():
     L.polr_comm_destroy.restype = None
     _lib = L
     return L
+
+
+def device_bytes_live():
+    """polr_device_bytes_live: bytes of device memory the library owns right now, over all contexts and handles"""
+    return int(load().polr_device_bytes_live())
 
 
 def _np_col(arr, valid=None):

@@ -109,6 +109,10 @@ typedef struct polr_pool_tuning {
 	                          pipelines); 0xFFFFFFFF: never */
 } polr_pool_tuning;
 int polr_ctx_set_pool_tuning(polr_ctx *ctx, const polr_pool_tuning *tuning);
+/* Diagnostic: bytes of device memory the library owns right now, over every context and handle of the process -- what
+ * a leak test compares before and after (exact, where the device's free memory also moves with other tenants).  Not
+ * counted: pinned host memory, streams, events, RCCL's own buffers. */
+uint64_t polr_device_bytes_live(void);
 
 /* ---------------------------------------------------------------------------------------------
  * Build sides.  Replaces what JoinHashTable::Finalize leaves in host memory

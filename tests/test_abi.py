@@ -60,3 +60,19 @@ def test_library_reads_no_tuning_from_the_environment():
     assert not bad, bad
     lib = capi.load()
     assert lib.polr_ctx_set_pool_tuning(None, None) == capi.E_INVALID
+
+
+def test_device_memory_has_one_owner():
+    """device memory is allocated and freed by DevBuf (csrc/polr_devbuf.h) and nowhere else: no other file of the device
+    library calls the allocator, and the helpers that did so by hand are gone"""
+    pkg = os.path.join(common.ROOT, "duckdb-polr_amd", "csrc")
+    assert os.path.isfile(os.path.join(pkg, "polr_devbuf.h"))
+    bad = []
+    for f in sorted(os.listdir(pkg)):
+        if f.endswith((".hip", ".h")):
+            text = open(os.path.join(pkg, f)).read()
+            words = ["dev_alloc(", "free_col(", "grow_buffer("] + (["hipMalloc(", "hipFree("] if f != "polr_devbuf.h" else [])
+            bad += [(f, w) for w in words if w in text]
+    assert not bad, bad
+    text = open(os.path.join(pkg, "polr_devbuf.h")).read()
+    assert text.count("hipMalloc(") == 1 and text.count("hipFree(") == 1
