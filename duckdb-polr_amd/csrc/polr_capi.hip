@@ -874,7 +874,7 @@ static void fill_dev_join(DevJoin *dj, const polr_join_desc *jd, const polr_ht *
 	}
 	dj->key_signed = ht->key_signed ? 1 : 0;
 	dj->n_payload = ht->n_payload;
-	dj->mask = ht->capacity ? ht->capacity - 1 : 0;
+	dj->mask = ht_mask(ht);
 	dj->min_value = ht->min_value;
 	dj->range = ht->range;
 	dj->table = ht->table;
@@ -891,169 +891,117 @@ static void fill_dev_join(DevJoin *dj, const polr_join_desc *jd, const polr_ht *
 	}
 }
 
+// one join as the plan sees it (polr_pipeline_plan.h): the caller's descriptor and what its build side is like
+static PipePlanJoin plan_join(const polr_join_desc &jd) {
+	PipePlanJoin t = PipePlanJoin();
+	t.desc = jd;
+	const polr_ht *ht = jd.ht;
+	if (!ht || ht->kind == KIND_NONE) {
+		return t; // (KIND_NONE: refused as not finalized)
+	}
+	t.kind = ht->kind;
+	t.n_keys = ht->n_keys;
+	for (uint32_t c = 0; c < ht->n_keys && c < POLR_NKEYS; c++) {
+		t.key_width[c] = ht->keys[c].width;
+		t.key_flags[c] = ht->key_flags[c];
+	}
+	t.key_signed = ht->key_signed ? 1 : 0;
+	t.cols.reserve(ht->n_payload);
+	for (uint32_t i = 0; i < ht->n_payload; i++) {
+		const OwnedCol &col = build_col(ht, i);
+		t.cols.push_back(PipeCol {col.width, col.flags & 1u});
+	}
+	t.capacity = ht->capacity;
+	t.max_run = ht->max_run;
+	t.min_value = ht->min_value;
+	t.max_value = ht->max_value;
+	t.range = ht->range;
+	t.packed = ht->pack.packed;
+	t.device = ht->ctx->device;
+	t.table = ht->table;
+	return t;
+}
+
 // resolve every (join order, position) of a pipeline variant into a StageDesc (see polr_device.h)
 // ext: extension records of the stages that need one (appended; StageDesc::ext holds the INDEX + 1 until the records
 // have their device address, see polr_pipeline_create)
-static void build_stage_descs(const polr_pipeline *p, const DevPipeline &dp, std::vector<StageDesc> &out,
-                              std::vector<StageExt> &ext) {
-	out.assign((size_t)dp.n_paths * POLR_KMAX, StageDesc());
-	auto source = [&](int32_t sj, int32_t sc, int32_t &slot, const uint8_t *&data, const uint8_t *&valid) {
-		if (sj < 0) {
-			slot = 0;
-			data = p->probe_cols[sc].data;
-			valid = p->probe_cols[sc].valid;
-		} else {
-			const OwnedCol &col = build_col(p->hts[sj], sc);
-			slot = dp.slot_of_join[sj];
-			data = col.data;
-			valid = col.valid;
-		}
+static void build_stage_descs(const polr_pipeline *p, const PipePlanInput &in, const PipePlan &plan, bool counting,
+                              std::vector<StageDesc> &out, std::vector<StageExt> &ext) {
+	const PipeSlots &slots = counting ? plan.count : plan.mat;
+	out.assign((size_t)in.n_paths * POLR_KMAX, StageDesc());
+	// the column a key or the left side of a condition is read from, and the tuple slot that holds its row
+	auto source = [&](const PipeSource &s, int32_t &slot, const uint8_t *&data, const uint8_t *&valid) {
+		const OwnedCol &col = s.join < 0 ? p->probe_cols[s.col] : build_col(p->hts[s.join], s.col);
+		slot = s.join < 0 ? 0 : slots.slot_of_join[s.join];
+		data = col.data;
+		valid = col.valid;
 	};
-	// width and signedness of the column a key is READ from (a key compared by value may differ from the build column)
-	auto source_type = [&](int32_t sj, int32_t sc, uint32_t &width, uint32_t &sx) {
-		const OwnedCol &col = sj < 0 ? p->probe_cols[sc] : build_col(p->hts[sj], sc);
-		width = col.width;
-		sx = (col.flags & 1u) ? 1u : 0u;
-	};
-	for (uint32_t q = 0; q < dp.n_paths; q++) {
-		for (uint32_t pos = 0; pos < dp.k; pos++) {
-			const uint32_t j = dp.paths[q].order[pos];
-			const DevJoin &dj = dp.joins[j];
+	for (uint32_t q = 0; q < in.n_paths; q++) {
+		for (uint32_t pos = 0; pos < in.k; pos++) {
+			const uint32_t j = (uint32_t)in.paths[q * in.k + pos];
 			const polr_ht *ht = p->hts[j];
+			const polr_join_desc &jd = in.joins[j].desc;
+			const PipePlan::Join &pj = plan.joins[j];
 			StageDesc &d = out[(size_t)q * POLR_KMAX + pos];
 			memset(&d, 0, sizeof(d));
-			d.kind = dj.kind;
-			d.n_keys = dj.n_keys;
-			d.key_signed = dj.key_signed;
-			d.out_slot = dp.slot_of_join[j];
-			for (uint32_t c = 0; c < dj.n_keys && c < 2; c++) {
-				d.key_width[c] = dj.key_width[c];
-				source(dj.key_src_join[c], dj.key_src_col[c], d.key_slot[c], d.key_data[c], d.key_valid[c]);
+			d.kind = ht->kind;
+			d.n_keys = ht->n_keys;
+			d.key_signed = ht->key_signed ? 1 : 0;
+			d.out_slot = slots.slot_of_join[j];
+			for (uint32_t c = 0; c < ht->n_keys && c < 2; c++) {
+				d.key_width[c] = ht->keys[c].width;
+				source(pj.key[c], d.key_slot[c], d.key_data[c], d.key_valid[c]);
 			}
 			d.packed = ht->pack.packed;
-			d.n_preds = dj.n_preds;
-			if (d.packed || d.n_preds) {
+			d.n_preds = jd.n_preds;
+			if (pj.ext) {
 				StageExt x;
 				memset(&x, 0, sizeof(x));
-				for (uint32_t c = 0; c < dj.n_keys; c++) {
-					source_type(dj.key_src_join[c], dj.key_src_col[c], x.key_width[c], x.key_sx[c]);
-					source(dj.key_src_join[c], dj.key_src_col[c], x.key_slot[c], x.key_data[c], x.key_valid[c]);
+				for (uint32_t c = 0; c < ht->n_keys; c++) {
+					// width and signedness of the column a key is READ from (a key compared by value may differ from the build column)
+					x.key_width[c] = pj.key[c].width;
+					x.key_sx[c] = pj.key[c].sx;
+					source(pj.key[c], x.key_slot[c], x.key_data[c], x.key_valid[c]);
 				}
 				x.pack = ht->pack;
-				x.n_preds = dj.n_preds;
-				for (uint32_t c = 0; c < dj.n_preds; c++) {
-					const OwnedCol &bcol = build_col(ht, dj.pred_build_col[c]);
-					x.pred_op[c] = dj.pred_op[c];
+				x.n_preds = jd.n_preds;
+				for (uint32_t c = 0; c < jd.n_preds; c++) {
+					const OwnedCol &bcol = build_col(ht, jd.pred_build_col[c]);
+					x.pred_op[c] = jd.pred_op[c];
 					x.pred_width[c] = bcol.width;
 					x.pred_sx[c] = (bcol.flags & 1u) ? 1u : 0u;
 					x.pred_bdata[c] = bcol.data;
 					x.pred_bvalid[c] = bcol.valid;
-					source(dj.pred_src_join[c], dj.pred_src_col[c], x.pred_slot[c], x.pred_data[c], x.pred_valid[c]);
+					source(pj.pred[c], x.pred_slot[c], x.pred_data[c], x.pred_valid[c]);
 				}
 				ext.push_back(x);
 				d.ext = (const StageExt *)(uintptr_t)ext.size(); // index + 1, patched to the device address later
 			}
 			d.table = ht->table;
 			d.rowids = ht->rowids;
-			d.mask = dj.mask;
-			d.min_value = dj.min_value;
-			d.range = dj.range;
-			d.sentinel_start = dj.sentinel_start;
-			d.sentinel_count = dj.sentinel_count;
-			// 1: at most one match per tuple; 2: keys may repeat (wide steps fall back to a narrow one where they do)
-			d.unique = (ht->kind == KIND_PERFECT || ht->kind == KIND_S8 || ht->max_run <= 1) ? 1u : 2u;
+			d.mask = ht_mask(ht);
+			d.min_value = ht->min_value;
+			d.range = ht->range;
+			d.sentinel_start = ht->sentinel_start;
+			d.sentinel_count = ht->sentinel_count;
+			d.unique = pj.unique;
+			d.lds_off1 = counting ? pj.lds_off1 : 0u; // (only the counting variant runs on the flat kernel)
 		}
 	}
 }
 
-// Flat pipelines (polr_flat_device.h): every join keyed by ONE 4-byte probe column, at most one build row per key
-// (perfect bit table or unique-key hash table).  Decides the workgroup shape of the flat pool kernel and which bit
-// tables stay in LDS for the whole run (smallest first, while they fit beside the per-wave queues).
-static void plan_flat(polr_pipeline *p, std::vector<StageDesc> &sd_count) {
-	DevPipeline &c = p->host_count;
-	c.flat = 0;
-	c.n_lds_tables = 0;
-	c.lds_table_dwords = 0;
-	if (c.W != 1 || c.k > 6) {
-		return; // some join reads its key through a build column / more joins than the sweep holds in registers
-	}
-	for (uint32_t j = 0; j < c.k; j++) {
-		const polr_ht *ht = p->hts[j];
-		const DevJoin &dj = c.joins[j];
-		if (dj.n_keys != 1 || dj.key_src_join[0] >= 0 || dj.key_width[0] != 4 || dj.n_preds != 0) {
-			return;
-		}
-		if (ht->kind == KIND_PERFECT) {
-			// the flat lookup works in 32-bit modular arithmetic: [min, max] must lie inside the key type's domain
-			const int64_t lo = dj.key_signed ? -2147483648ll : 0ll;
-			const int64_t hi = dj.key_signed ? 2147483647ll : 4294967295ll;
-			if (ht->min_value < lo || ht->max_value > hi || ht->range > 0xFFFFFFFFull) {
-				return;
-			}
-		} else if (ht->kind != KIND_S8 || ht->capacity > (1ull << 31)) {
-			return;
-		}
-	}
-	const size_t per_wave = polr_pool_flat_wave_bytes(c.k);
-	uint32_t wpb = 4;
-	for (uint32_t w : {16u, 8u}) {
-		if (per_wave * w <= 120u * 1024) {
-			wpb = w;
-			break;
-		}
-	}
-	p->flat_wpb = wpb;
-	// one workgroup of 16 waves per CU leaves the rest of the 160 KB to the tables; smaller workgroups share a CU
-	const size_t budget = wpb == 16 ? std::min<size_t>(64u * 1024, 156u * 1024 - per_wave * wpb) : 16u * 1024;
-	std::vector<uint32_t> order;
-	for (uint32_t j = 0; j < c.k; j++) {
-		if (p->hts[j]->kind == KIND_PERFECT) {
-			order.push_back(j);
-		}
-	}
-	std::sort(order.begin(), order.end(), [&](uint32_t a, uint32_t b) { return p->hts[a]->range < p->hts[b]->range; });
-	uint32_t off_of_join[POLR_KMAX];
+// one variant's header: which slot of a tuple carries which join's build id
+static void set_slots(DevPipeline &dp, const PipeSlots &slots, uint32_t materialize, uint32_t mult) {
+	dp.materialize = materialize;
+	dp.W = slots.W;
+	dp.mult = mult;
 	for (uint32_t j = 0; j < POLR_KMAX; j++) {
-		off_of_join[j] = 0;
+		dp.slot_of_join[j] = slots.slot_of_join[j];
 	}
-	uint32_t used = 0;
-	for (uint32_t j : order) {
-		const polr_ht *ht = p->hts[j];
-		const uint32_t words = (uint32_t)((ht->range + 1 + 31) / 32);
-		// the same build side joined twice shares one LDS copy
-		bool shared = false;
-		for (uint32_t t = 0; t < c.n_lds_tables; t++) {
-			if (c.lds_table_src[t] == (const uint32_t *)ht->table) {
-				off_of_join[j] = c.lds_table_off[t] + 1;
-				shared = true;
-			}
-		}
-		if (shared) {
-			continue;
-		}
-		const uint32_t padded = (words + 3u) & ~3u;
-		if (((size_t)used + padded) * 4 > budget || c.n_lds_tables >= POLR_KMAX) {
-			break;
-		}
-		c.lds_table_src[c.n_lds_tables] = (const uint32_t *)ht->table;
-		c.lds_table_off[c.n_lds_tables] = used;
-		c.lds_table_len[c.n_lds_tables] = words;
-		c.n_lds_tables++;
-		off_of_join[j] = used + 1;
-		used += padded;
-	}
-	c.lds_table_dwords = used;
-	// (an emitting run needs every join's build id: a perfect table's is the key's offset, a hash table's would take a
-	// second probe -- such banks emit through the generic pipeline)
-	p->flat_emit = order.size() == c.k;
-	for (uint32_t q = 0; q < c.n_paths; q++) {
-		for (uint32_t pos = 0; pos < c.k; pos++) {
-			sd_count[(size_t)q * POLR_KMAX + pos].lds_off1 = off_of_join[c.paths[q].order[pos]];
-		}
-	}
-	c.flat = 1;
 }
 
+// The rules -- what is refused, tuple slots, multiplicities, the flat kernel and its LDS tables -- are
+// polr_pipeline_plan(); here the handles are described to it and its answer is written into the device structs.
 int polr_pipeline_create(polr_ctx *ctx, const polr_col *probe_cols, uint32_t n_probe_cols, uint64_t n_probe_rows,
                          const polr_join_desc *joins, uint32_t k, const int32_t *paths, uint32_t n_paths,
                          polr_pipeline **out) {
@@ -1062,146 +1010,24 @@ int polr_pipeline_create(polr_ctx *ctx, const polr_col *probe_cols, uint32_t n_p
 		return POLR_E_INVALID;
 	}
 	*out = nullptr;
-	if (k < 1 || k > POLR_MAX_JOINS) {
-		POLR_FAIL(ctx, POLR_E_UNSUPPORTED, "%u multiplexed joins not supported (1..%d)", k, POLR_MAX_JOINS);
+	PipePlanInput in;
+	in.probe_cols.reserve(n_probe_cols);
+	in.joins.reserve(k <= POLR_MAX_JOINS ? k : 0);
+	for (uint32_t i = 0; i < n_probe_cols; i++) {
+		in.probe_cols.push_back(PipeCol {probe_cols[i].width, probe_cols[i].flags & POLR_COL_SIGNED});
 	}
-	if (n_paths < 1 || n_paths > POLR_MAX_PATHS) {
-		POLR_FAIL(ctx, POLR_E_UNSUPPORTED, "%u join orders not supported (1..%d)", n_paths, POLR_MAX_PATHS);
+	in.n_probe_rows = n_probe_rows;
+	in.device = ctx->device;
+	in.k = k;
+	in.n_paths = n_paths;
+	for (uint32_t j = 0; j < k && k <= POLR_MAX_JOINS; j++) { // (any other k is refused before a join is looked at)
+		in.joins.push_back(plan_join(joins[j]));
 	}
-	if (n_probe_rows >= 0xFFFFFFF0ull) {
-		POLR_FAIL(ctx, POLR_E_UNSUPPORTED, "probe side of %llu rows exceeds the 32-bit row-id space per shard",
-		          (unsigned long long)n_probe_rows);
-	}
-	// the descriptors first: the dependency walk below reads n_keys / n_preds entries of every join and shifts by the
-	// join index a key or a condition names
-	for (uint32_t j = 0; j < k; j++) {
-		const polr_ht *ht = joins[j].ht;
-		if (!ht || ht->kind == KIND_NONE) {
-			POLR_FAIL(ctx, POLR_E_INVALID, "join %u: build side not finalized", j);
-		}
-		if (joins[j].n_keys != ht->n_keys || joins[j].n_keys < 1 || joins[j].n_keys > POLR_MAX_KEYS) {
-			POLR_FAIL(ctx, POLR_E_INVALID, "join %u: %u probe keys for a %u-key table", j, joins[j].n_keys, ht->n_keys);
-		}
-		if (joins[j].n_preds > POLR_MAX_PREDS) {
-			POLR_FAIL(ctx, POLR_E_UNSUPPORTED, "join %u: %u non-equality conditions (at most %d)", j, joins[j].n_preds,
-			          POLR_MAX_PREDS);
-		}
-		for (uint32_t c = 0; c < joins[j].n_keys; c++) {
-			const int32_t sj = joins[j].key_src_join[c];
-			if (sj >= 0 && ((uint32_t)sj >= k || (uint32_t)sj == j)) {
-				POLR_FAIL(ctx, POLR_E_INVALID, "join %u key %u: reads a build column of join %d", j, c, sj);
-			}
-		}
-		for (uint32_t c = 0; c < joins[j].n_preds; c++) {
-			const int32_t sj = joins[j].pred_src_join[c];
-			if (sj >= 0 && ((uint32_t)sj >= k || (uint32_t)sj == j)) {
-				POLR_FAIL(ctx, POLR_E_INVALID, "join %u condition %u: reads a build column of join %d", j, c, sj);
-			}
-		}
-	}
-	// every path must be a permutation of 0..k-1 that respects the key dependencies
-	// (POLARConfig join_prerequisites, polar_config.cpp:72-95)
-	for (uint32_t p = 0; p < n_paths; p++) {
-		uint32_t seen = 0;
-		for (uint32_t j = 0; j < k; j++) {
-			const int32_t x = paths[p * k + j];
-			if (x < 0 || (uint32_t)x >= k || (seen >> x) & 1) {
-				POLR_FAIL(ctx, POLR_E_INVALID, "path %u is not a permutation of the %u joins", p, k);
-			}
-			for (uint32_t c = 0; c < joins[x].n_keys; c++) {
-				const int32_t sj = joins[x].key_src_join[c];
-				if (sj >= 0 && !((seen >> sj) & 1)) {
-					POLR_FAIL(ctx, POLR_E_INVALID, "path %u probes join %d before join %d that provides its key", p, x,
-					          sj);
-				}
-			}
-			for (uint32_t c = 0; c < joins[x].n_preds; c++) {
-				const int32_t sj = joins[x].pred_src_join[c];
-				if (sj >= 0 && !((seen >> sj) & 1)) {
-					POLR_FAIL(ctx, POLR_E_INVALID, "path %u probes join %d before join %d that a condition of it reads", p, x,
-					          sj);
-				}
-			}
-			seen |= 1u << x;
-		}
-	}
-	for (uint32_t j = 0; j < k; j++) {
-		const polr_ht *ht = joins[j].ht;
-		if (!ht || ht->kind == KIND_NONE) {
-			POLR_FAIL(ctx, POLR_E_INVALID, "join %u: build side not finalized", j);
-		}
-		if (ht->ctx->device != ctx->device) {
-			POLR_FAIL(ctx, POLR_E_INVALID, "join %u: build side lives on another device", j);
-		}
-		if (joins[j].n_keys != ht->n_keys) {
-			POLR_FAIL(ctx, POLR_E_INVALID, "join %u: %u probe keys for a %u-key table", j, joins[j].n_keys, ht->n_keys);
-		}
-		for (uint32_t c = 0; c < ht->n_keys; c++) {
-			const int32_t sj = joins[j].key_src_join[c];
-			const int32_t sc = joins[j].key_src_col[c];
-			uint32_t width;
-			if (sj < 0) {
-				if (sc < 0 || (uint32_t)sc >= n_probe_cols) {
-					POLR_FAIL(ctx, POLR_E_INVALID, "join %u key %u: probe column %d out of range", j, c, sc);
-				}
-				width = probe_cols[sc].width;
-			} else {
-				if ((uint32_t)sj >= k || (uint32_t)sj == j || sc < 0 || (uint32_t)sc >= joins[sj].ht->n_payload) {
-					POLR_FAIL(ctx, POLR_E_INVALID, "join %u key %u: build column (%d,%d) out of range", j, c, sj, sc);
-				}
-				width = joins[sj].ht->payload[sc].width;
-			}
-			// JoinHashTable asserts left/right key types equal (join_hashtable.cpp:24): the reference's left side is then
-			// CAST(column) (polar_config.cpp:75-82).  An integer cast is a comparison by VALUE, which a table whose key
-			// column carries POLR_KEY_BY_VALUE does on the device -- no materialised copy of the probe column
-			if (width != ht->keys[c].width && !(ht->key_flags[c] & POLR_KEY_BY_VALUE)) {
-				POLR_FAIL(ctx, POLR_E_INVALID,
-				          "join %u key %u: probe key is %u bytes, build key %u bytes (a CAST'ed key: polr_ht_set_key_flags(..., "
-				          "POLR_KEY_BY_VALUE) before the table is finalized)",
-				          j, c, width, ht->keys[c].width);
-			}
-			if (width != 1 && width != 2 && width != 4 && width != 8) {
-				POLR_FAIL(ctx, POLR_E_UNSUPPORTED, "join %u key %u: probe key of %u bytes", j, c, width);
-			}
-		}
-		if (joins[j].n_preds > POLR_MAX_PREDS) {
-			POLR_FAIL(ctx, POLR_E_UNSUPPORTED, "join %u: %u non-equality conditions (at most %d)", j, joins[j].n_preds,
-			          POLR_MAX_PREDS);
-		}
-		for (uint32_t c = 0; c < joins[j].n_preds; c++) {
-			const int32_t sj = joins[j].pred_src_join[c];
-			const int32_t sc = joins[j].pred_src_col[c];
-			const uint32_t bc = joins[j].pred_build_col[c];
-			const uint32_t op = joins[j].pred_op[c];
-			if (op > POLR_CMP_GE && op != POLR_CMP_STR_EQ) {
-				POLR_FAIL(ctx, POLR_E_UNSUPPORTED, "join %u condition %u: comparison %u (EQ, NE, LT, GT, LE, GE, STR_EQ)", j, c, op);
-			}
-			if (bc >= ht->n_payload) {
-				POLR_FAIL(ctx, POLR_E_INVALID, "join %u condition %u: build column %u out of range", j, c, bc);
-			}
-			uint32_t width;
-			if (sj < 0) {
-				if (sc < 0 || (uint32_t)sc >= n_probe_cols) {
-					POLR_FAIL(ctx, POLR_E_INVALID, "join %u condition %u: probe column %d out of range", j, c, sc);
-				}
-				width = probe_cols[sc].width;
-			} else {
-				if ((uint32_t)sj >= k || (uint32_t)sj == j || sc < 0 || (uint32_t)sc >= joins[sj].ht->n_payload) {
-					POLR_FAIL(ctx, POLR_E_INVALID, "join %u condition %u: build column (%d,%d) out of range", j, c, sj, sc);
-				}
-				width = joins[sj].ht->payload[sc].width;
-			}
-			const OwnedCol &bcol = build_col(ht, bc);
-			if (op == POLR_CMP_STR_EQ) {
-				if (width != 16 || bcol.width != 16) {
-					POLR_FAIL(ctx, POLR_E_INVALID, "join %u condition %u: STR_EQ compares two columns of 16-byte string cells "
-					                               "(left %u bytes, right %u bytes)", j, c, width, bcol.width);
-				}
-			} else if (width != bcol.width || (width != 1 && width != 2 && width != 4 && width != 8)) {
-				POLR_FAIL(ctx, POLR_E_INVALID, "join %u condition %u: left side is %u bytes, right side %u bytes", j, c, width,
-				          bcol.width);
-			}
-		}
+	in.paths = paths;
+	in.flat_wave_bytes = polr_pool_flat_wave_bytes(k);
+	PipePlan plan;
+	if (polr_pipeline_plan(in, plan)) {
+		POLR_FAIL(ctx, plan.code, "%s", plan.msg);
 	}
 	HIPCHK(ctx, hipSetDevice(ctx->device));
 	HandleGuard<polr_pipeline> guard(new polr_pipeline());
@@ -1218,7 +1044,7 @@ int polr_pipeline_create(polr_ctx *ctx, const polr_col *probe_cols, uint32_t n_p
 		POLR_TRY(ingest_col(ctx, &probe_cols[i], n_probe_rows, &p->probe_cols[i], &acct, ctx->stream));
 	}
 	POLR_TRY(upload_devcols(ctx, p->probe_cols, &p->probe_cols_dev, ctx->stream));
-	DevPipeline &m = p->host_mat;
+	DevPipeline &m = p->host_mat, &c = p->host_count;
 	memset(&m, 0, sizeof(m));
 	m.k = k;
 	m.n_paths = n_paths;
@@ -1235,52 +1061,24 @@ int polr_pipeline_create(polr_ctx *ctx, const polr_col *probe_cols, uint32_t n_p
 			m.paths[q].order[j] = (uint32_t)paths[q * k + j];
 		}
 	}
-	p->host_count = m;
-	// materialising variant: slot 1+j = join j (the adaptive union's column order)
-	m.materialize = 1;
-	m.W = 1 + k;
-	for (uint32_t j = 0; j < POLR_KMAX; j++) {
-		m.slot_of_join[j] = j < k ? (int32_t)(1 + j) : -1;
+	c = m;
+	set_slots(m, plan.mat, 1, 0);
+	set_slots(c, plan.count, 0, plan.mult);
+	c.flat = plan.flat;
+	c.n_lds_tables = plan.n_lds_tables;
+	c.lds_table_dwords = plan.lds_table_dwords;
+	for (uint32_t t = 0; t < plan.n_lds_tables; t++) {
+		c.lds_table_src[t] = (const uint32_t *)p->hts[plan.lds_table_join[t]]->table;
+		c.lds_table_off[t] = plan.lds_table_off[t];
+		c.lds_table_len[t] = plan.lds_table_len[t];
 	}
-	// counting variant: carry only the build ids some later join reads its key through
-	DevPipeline &c = p->host_count;
-	c.materialize = 0;
-	uint32_t w = 1;
-	for (uint32_t j = 0; j < POLR_KMAX; j++) {
-		c.slot_of_join[j] = -1;
-	}
-	for (uint32_t j = 0; j < k; j++) {
-		for (uint32_t cc = 0; cc < joins[j].n_keys; cc++) {
-			const int32_t sj = joins[j].key_src_join[cc];
-			if (sj >= 0 && c.slot_of_join[sj] < 0) {
-				c.slot_of_join[sj] = (int32_t)w++;
-			}
-		}
-		for (uint32_t cc = 0; cc < joins[j].n_preds; cc++) {
-			const int32_t sj = joins[j].pred_src_join[cc];
-			if (sj >= 0 && c.slot_of_join[sj] < 0) {
-				c.slot_of_join[sj] = (int32_t)w++;
-			}
-		}
-	}
-	c.W = w;
-	// multiplicities (polr_gen_device.h): worth a tuple slot when some join's matches can be folded into them -- its
-	// build key may repeat, nobody reads its build rows downstream, it has no non-equality condition
-	c.mult = 0;
-	for (uint32_t j = 0; j < k; j++) {
-		const polr_ht *ht = joins[j].ht;
-		const bool repeats = !(ht->kind == KIND_PERFECT || ht->kind == KIND_S8 || ht->max_run <= 1);
-		if (repeats && c.slot_of_join[j] < 0 && joins[j].n_preds == 0) {
-			c.mult = 1;
-		}
-	}
-	p->host_mat.mult = 0;
+	p->flat_wpb = plan.flat_wpb;
+	p->flat_emit = plan.flat_emit != 0;
 	std::vector<StageDesc> sd_mat, sd_count;
 	std::vector<StageExt> sd_ext;
-	build_stage_descs(p, p->host_mat, sd_mat, sd_ext);
-	build_stage_descs(p, p->host_count, sd_count, sd_ext);
-	plan_flat(p, sd_count);
-	p->host_mat.ext = p->host_count.ext = sd_ext.empty() ? 0u : 1u;
+	build_stage_descs(p, in, plan, false, sd_mat, sd_ext);
+	build_stage_descs(p, in, plan, true, sd_count, sd_ext);
+	m.ext = c.ext = sd_ext.empty() ? 0u : 1u;
 	if (!sd_ext.empty()) {
 		HIPCHK(ctx, p->stage_ext.alloc(sd_ext.size()));
 		HIPCHK(ctx, hipMemcpy(p->stage_ext, sd_ext.data(), sd_ext.size() * sizeof(StageExt), hipMemcpyHostToDevice));
@@ -1296,12 +1094,12 @@ int polr_pipeline_create(polr_ctx *ctx, const polr_col *probe_cols, uint32_t n_p
 	HIPCHK(ctx, p->stages_count.alloc(sd_count.size()));
 	HIPCHK(ctx, hipMemcpy(p->stages_mat, sd_mat.data(), sd_mat.size() * sizeof(StageDesc), hipMemcpyHostToDevice));
 	HIPCHK(ctx, hipMemcpy(p->stages_count, sd_count.data(), sd_count.size() * sizeof(StageDesc), hipMemcpyHostToDevice));
-	p->host_mat.stages = p->stages_mat;
-	p->host_count.stages = p->stages_count;
+	m.stages = p->stages_mat;
+	c.stages = p->stages_count;
 	HIPCHK(ctx, p->dev_mat.alloc(1));
 	HIPCHK(ctx, p->dev_count.alloc(1));
-	HIPCHK(ctx, hipMemcpy(p->dev_mat, &p->host_mat, sizeof(DevPipeline), hipMemcpyHostToDevice));
-	HIPCHK(ctx, hipMemcpy(p->dev_count, &p->host_count, sizeof(DevPipeline), hipMemcpyHostToDevice));
+	HIPCHK(ctx, hipMemcpy(p->dev_mat, &m, sizeof(DevPipeline), hipMemcpyHostToDevice));
+	HIPCHK(ctx, hipMemcpy(p->dev_count, &c, sizeof(DevPipeline), hipMemcpyHostToDevice));
 	*out = guard.release();
 	return POLR_OK;
 }

@@ -17,6 +17,8 @@
 
 #include <stdint.h>
 
+#include "polr_pipeline_plan.h" // POLR_KMAX, POLR_PMAX, POLR_NKEYS, POLR_NPREDS, KIND_*: shared with the host's plan
+
 // Device code names the address space of what it loads from: a pointer rebuilt from an integer (descriptors travel as
 // 64-bit words through LDS and scalar registers) is a GENERIC pointer to the compiler, and a generic access is a FLAT
 // instruction -- it counts against the LDS counter (lgkmcnt) as well as the memory counter, so every wait for an LDS
@@ -40,20 +42,13 @@ __device__ __forceinline__ uint4 load_global_x4(const POLR_GLOBAL uint32_t *p) {
 }
 #endif
 
-#define POLR_KMAX 8
-#define POLR_PMAX 32
 #define POLR_WMAX (1 + POLR_KMAX)
 // per-round counters are sharded by workgroup so a table-sized round does not serialise thousands of
 // atomics on k words; readers sum the shards
 #define POLR_NSHARD 32 // (the router sums the shards with one half-wave per counter: keep it 32)
 
-enum { KIND_NONE = 0, KIND_PERFECT = 1, KIND_S8 = 2, KIND_S16 = 3 };
-
 #define S8_EMPTY_ROW 0xFFFFFFFFu
 #define S16_EMPTY_KEY 0xFFFFFFFFFFFFFFFFull
-
-#define POLR_NKEYS 4 // = POLR_MAX_KEYS of the ABI
-#define POLR_NPREDS 4 // = POLR_MAX_PREDS
 
 // Composite keys that do not fit the plain {key0 | key1 << 32} form: column c contributes (value - min[c]) << shift[c],
 // value sign- or zero-extended by the BUILD column's type; a probe value outside [min, min + range] cannot match.

@@ -212,6 +212,11 @@ static inline const OwnedCol &build_col(const polr_ht *ht, uint32_t i) {
 	return ht->kind == KIND_PERFECT ? ht->pcols[i] : ht->payload[i];
 }
 
+// slot index mask of a hash table (capacity is a power of two; 0 for a perfect table)
+static inline uint64_t ht_mask(const polr_ht *ht) {
+	return ht->capacity ? ht->capacity - 1 : 0;
+}
+
 static inline DevCol dev_col(const OwnedCol &c) {
 	DevCol d;
 	d.data = c.data;

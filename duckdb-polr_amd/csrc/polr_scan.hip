@@ -659,8 +659,7 @@ static int scan_lip_set(polr_pipeline *p, uint32_t lip_joins, DevLipSet &lip) {
 			if (!((lip_joins >> j) & 1u)) {
 				continue;
 			}
-			const DevJoin &dj = p->host_count.joins[j];
-			if (dj.n_keys != 1 || dj.key_src_join[0] >= 0) {
+			if (p->hts[j]->n_keys != 1 || p->host_count.joins[j].key_src_join[0] >= 0) {
 				POLR_FAIL(ctx, POLR_E_INVALID, "LIP: join %u is not keyed by one column of the source (physical_join.cpp:57-107)", j);
 			}
 			if (p->hts[j]->pack.packed) {
@@ -673,19 +672,20 @@ static int scan_lip_set(polr_pipeline *p, uint32_t lip_joins, DevLipSet &lip) {
 		}
 		std::sort(js.begin(), js.end(), [&](uint32_t a, uint32_t b) { return p->hts[a]->device_bytes < p->hts[b]->device_bytes; });
 		for (uint32_t j : js) {
-			const DevJoin &dj = p->host_count.joins[j];
-			const OwnedCol &c = p->probe_cols[dj.key_src_col[0]];
+			// (the build side itself says what its index is like; DevJoin keeps where the caller's descriptor reads the key)
+			const polr_ht *ht = p->hts[j];
+			const OwnedCol &c = p->probe_cols[p->host_count.joins[j].key_src_col[0]];
 			DevLip &f = lip.f[lip.n++];
 			f.key_data = c.data;
 			f.key_valid = c.valid;
 			f.key_width = c.width;
-			f.key_signed = dj.key_signed;
-			f.kind = dj.kind;
-			f.table = dj.table;
-			f.mask = dj.mask;
-			f.min_value = dj.min_value;
-			f.range = dj.range;
-			f.sentinel_count = dj.sentinel_count;
+			f.key_signed = ht->key_signed ? 1 : 0;
+			f.kind = ht->kind;
+			f.table = ht->table;
+			f.mask = ht_mask(ht);
+			f.min_value = ht->min_value;
+			f.range = ht->range;
+			f.sentinel_count = ht->sentinel_count;
 		}
 	}
 	return POLR_OK;
