@@ -127,14 +127,14 @@ struct polr_pipeline {
 	DevBuf<uint64_t> scan_offsets_dev;
 	uint64_t scan_n_chunks = 0;
 	uint32_t scan_vector_size = 0;
-	// scan buffers, sized for the worst case and reused by every polr_pipeline_scan_filter call
+	// scan buffers, sized for the worst case and reused by every scan call, whichever entry point it came through
 	DevBuf<uint32_t> scan_sel;
 	DevBuf<unsigned long long> scan_packed, scan_sums, scan_totals;
 	DevBuf<uint8_t> scan_str_tails; // polr_pipeline_scan_filter_str: the VARCHAR constants' bytes beyond 12, re-uploaded per call
-	// polr_pipeline_scan_filter_expr: the lowered program (re-uploaded per call) and one pass bit per table row, written
-	// by the counting pass and read by the writing pass; both allocated by the first such call
-	DevBuf<uint8_t> scan_expr_prog;
-	DevBuf<unsigned long long> scan_pass_bits; // words
+	DevBuf<uint8_t> scan_expr_prog; // polr_pipeline_scan_filter_expr: the lowered program, re-uploaded per call
+	// one pass bit per table row, ceil(vector size / 64) words per vector: written by the counting pass, read by the
+	// writing pass
+	DevBuf<unsigned long long> scan_pass_bits;
 	bool scan_valid = false;      // a scan result is installed (selection + chunk boundaries)
 	uint64_t scan_generation = 0; // bumped by every scan: multiplexers must re-attach (polr_mpx_use_scan_chunks)
 	std::vector<polr_ht *> hts;

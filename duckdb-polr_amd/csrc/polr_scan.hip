@@ -7,27 +7,31 @@
 // to the rows that pass, in row order; a vector with no survivor is skipped (row_group.cpp:399-416), a NULL
 // never passes a comparison (column_segment.cpp:200).  The multiplexer therefore sees chunks of 1..V tuples.
 //
-// Here: three HBM-streaming kernels over the filter columns (already resident in HBM)
-//   1. count   : one wave per vector, 64 rows per step, survivors counted with a ballot
+// Here: three HBM-streaming passes; only the first reads the filter columns (already resident in HBM)
+//   1. count   : one wave per vector, 64 rows per step: the row predicate and the LIP tests are evaluated, the survivors
+//                counted with a ballot, and every step's ballot kept in the pipeline's pass-bit buffer (tscan_count).
+//                One kernel per row predicate, so that an integer scan carries neither string nor program code:
+//                  polr_tscan_count_kernel       DevFilterSet               polr_pipeline_scan_filter[_lip]
+//                  polr_tscan_count_str_kernel   DevFilterSet + DevStrSet   polr_pipeline_scan_filter_str
+//                  polr_tscan_count_expr_kernel  DevFxProg                  polr_pipeline_scan_filter_expr
 //   2. scan    : exclusive prefix over the vectors of (tuples, non-empty vectors) packed in one u64
 //                (per-1024-vector block sums -> one block scans the sums -> apply)
-//   3. write   : one wave per vector again: ascending row ids to sel[], chunk boundary of every non-empty vector
+//   3. write   : polr_tscan_write_bits_kernel, one wave per vector again: ascending row ids to sel[] from the pass
+//                bits, chunk boundary of every non-empty vector; evaluates nothing
 // and the result -- selection + chunk boundaries -- stays on the device, installed in the pipeline; a
-// multiplexer takes the boundaries with polr_mpx_use_scan_chunks.  Algorithmic bytes: 2 x (sum of filter column
-// widths [+ validity bytes]) per table row + 4 per surviving row.
+// multiplexer takes the boundaries with polr_mpx_use_scan_chunks.  Algorithmic bytes: the sum of the filter column
+// widths [+ validity bytes, + LIP key widths] per table row, once, + 2 bits per row (the pass bit, written and read)
+// + 4 per surviving row.
 //
 // VARCHAR constant comparisons (polr_pipeline_scan_filter_str; the reference pushes =, <, >, <=, >= against a VARCHAR
 // constant and the prefix range of LIKE 'abc%' into the scan: filter_combiner.cpp:391-398, :426-485, evaluated on
-// string_t by ColumnSegment::FilterSelection column_segment.cpp:435-442): the count and write kernels exist a second
-// time with a DevStrSet beside the integer filters, so a scan without string filters runs the code it always ran.  A row
-// costs one 16-byte cell load per distinct VARCHAR filter column (2 x 16 over the two passes); the comparison is
-// polr_strcmp.h.  The heap is read only for a cell longer than 12 bytes whose first four bytes tie with a constant's.
+// string_t by ColumnSegment::FilterSelection column_segment.cpp:435-442): a DevStrSet beside the integer filters.  A row
+// costs one 16-byte cell load per distinct VARCHAR filter column; the comparison is polr_strcmp.h.  The heap is read only
+// for a cell longer than 12 bytes whose first four bytes tie with a constant's.
 //
 // Filter expressions (polr_pipeline_scan_filter_expr; what the reference evaluates in a PhysicalFilter between the scan
-// and the first join -- OR / NOT trees, IN lists, LIKE): a count kernel of its own that evaluates a postfix program once
-// per row and keeps every step's ballot, and a write kernel that reads those bits instead of evaluating again (see
-// "expression filters" below; the program is checked and lowered by polr_filter_plan.h, LIKE is polr_like.h).  Algorithmic
-// bytes: the named columns once per table row + 2 bits per row + 4 per surviving row.
+// and the first join -- OR / NOT trees, IN lists, LIKE): a postfix program evaluated per row (see "expression filters"
+// below; the program is checked and lowered by polr_filter_plan.h, LIKE is polr_like.h).
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <string.h>
@@ -149,7 +153,44 @@ __device__ __forceinline__ bool lip_contains(const DevLip &f, uint64_t row) {
 #define PACK_SHIFT 40 // low 40 bits: tuples, high 24: non-empty vectors
 #define PACK_MASK ((1ull << PACK_SHIFT) - 1)
 
-__device__ __forceinline__ bool row_passes_filters(const DevFilterSet &fs, uint64_t row);
+// value OP constant on integers: the six comparisons of a ConstantFilter, in the column's signedness
+__device__ __forceinline__ bool int_cmp_holds(uint64_t v, int64_t constant, uint32_t op, bool is_signed) {
+	if (is_signed) {
+		const int64_t a = (int64_t)v, c = constant;
+		return op == POLR_CMP_EQ   ? a == c
+		       : op == POLR_CMP_NE ? a != c
+		       : op == POLR_CMP_LT ? a < c
+		       : op == POLR_CMP_GT ? a > c
+		       : op == POLR_CMP_LE ? a <= c
+		                           : a >= c;
+	}
+	const uint64_t c = (uint64_t)constant; // (host: constant >= 0 for unsigned columns)
+	return op == POLR_CMP_EQ   ? v == c
+	       : op == POLR_CMP_NE ? v != c
+	       : op == POLR_CMP_LT ? v < c
+	       : op == POLR_CMP_GT ? v > c
+	       : op == POLR_CMP_LE ? v <= c
+	                           : v >= c;
+}
+
+__device__ __forceinline__ bool row_passes_filters(const DevFilterSet &fs, uint64_t row) {
+	bool ok = true;
+	for (uint32_t i = 0; i < fs.n; i++) {
+		const DevFilter &f = fs.f[i];
+		const bool valid = !(f.valid && !f.valid[row]);
+		if (f.op == POLR_CMP_IS_NULL) {
+			ok = ok && !valid;
+			continue;
+		}
+		if (f.op == POLR_CMP_IS_NOT_NULL) {
+			ok = ok && valid;
+			continue;
+		}
+		const uint64_t v = load_cell(as_global(f.data) + row * f.width, f.width, f.is_signed != 0);
+		ok = ok && valid && int_cmp_holds(v, f.constant, f.op, f.is_signed != 0);
+	}
+	return ok;
+}
 
 // every comparison of every VARCHAR filter column holds for the row.  The validity byte comes first: the cell of a NULL
 // row is never loaded, let alone its pointer followed (the reference leaves such cells as they were).
@@ -171,70 +212,32 @@ __device__ __forceinline__ bool row_passes_str(const DevStrSet &ss, uint64_t row
 	return ok;
 }
 
-// STR: the kernel has VARCHAR comparisons (ss != nullptr); they are evaluated for the rows the integer filters keep,
-// LIP for the rows both keep
-template <bool STR>
-__device__ __forceinline__ bool row_passes(const DevFilterSet &fs, const DevStrSet *ss, const DevLipSet &lip, uint64_t row) {
-	bool ok = row_passes_filters(fs, row);
-	if constexpr (STR) {
-		ok = ok && row_passes_str(*ss, row);
-	}
-	for (uint32_t i = 0; i < lip.n; i++) {
-		ok = ok && lip_contains(lip.f[i], row);
-	}
-	return ok;
-}
-
-__device__ __forceinline__ bool row_passes_filters(const DevFilterSet &fs, uint64_t row) {
-	bool ok = true;
-	for (uint32_t i = 0; i < fs.n; i++) {
-		const DevFilter &f = fs.f[i];
-		const bool valid = !(f.valid && !f.valid[row]);
-		if (f.op == POLR_CMP_IS_NULL) {
-			ok = ok && !valid;
-			continue;
-		}
-		if (f.op == POLR_CMP_IS_NOT_NULL) {
-			ok = ok && valid;
-			continue;
-		}
-		const uint64_t v = load_cell(as_global(f.data) + row * f.width, f.width, f.is_signed != 0);
-		bool r;
-		if (f.is_signed) {
-			const int64_t a = (int64_t)v, c = f.constant;
-			r = f.op == POLR_CMP_EQ   ? a == c
-			    : f.op == POLR_CMP_NE ? a != c
-			    : f.op == POLR_CMP_LT ? a < c
-			    : f.op == POLR_CMP_GT ? a > c
-			    : f.op == POLR_CMP_LE ? a <= c
-			                          : a >= c;
-		} else {
-			const uint64_t c = (uint64_t)f.constant; // (host: constant >= 0 for unsigned columns)
-			r = f.op == POLR_CMP_EQ   ? v == c
-			    : f.op == POLR_CMP_NE ? v != c
-			    : f.op == POLR_CMP_LT ? v < c
-			    : f.op == POLR_CMP_GT ? v > c
-			    : f.op == POLR_CMP_LE ? v <= c
-			                          : v >= c;
-		}
-		ok = ok && valid && r;
-	}
-	return ok;
-}
-
-// one wave per vector (grid-stride); counts[v] = survivors of vector v, packed with its non-empty flag.  (The kernels
-// compute the wave ids: blockDim is read cheapest in the kernel function itself.)
-template <bool STR>
-__device__ __forceinline__ void tscan_count(uint32_t lane, uint64_t wave, uint64_t n_waves, const DevFilterSet &fs, const DevStrSet *ss, const DevLipSet &lip, uint64_t n_rows,
-                                            uint32_t V, uint64_t n_vec, unsigned long long *__restrict__ packed) {
+// The counting pass of every scan: one wave per vector (grid-stride), 64 rows per step.  `passes(row)` is the scan's row
+// predicate; LIP is tested for the rows it keeps.  packed[v] = survivors of vector v with its non-empty flag; the ballot
+// of every step goes to pass_bits, ceil(V / 64) words per vector, which the writing pass reads instead of evaluating again.
+// All words of a vector are written, those beyond the table's last row as 0, so no word of an earlier scan is left in the
+// range a scan uses.  (The kernels compute the wave ids: blockDim is read cheapest in the kernel function itself.)
+template <class Pred>
+__device__ __forceinline__ void tscan_count(uint32_t lane, uint64_t wave, uint64_t n_waves, const DevLipSet &lip, uint64_t n_rows,
+                                            uint32_t V, uint64_t n_vec, unsigned long long *__restrict__ packed,
+                                            unsigned long long *__restrict__ pass_bits, Pred passes) {
+	const uint64_t words_per_vec = ((uint64_t)V + 63) >> 6;
 	for (uint64_t v = wave; v < n_vec; v += n_waves) {
 		const uint64_t begin = v * V;
 		const uint64_t end = begin + V < n_rows ? begin + V : n_rows;
+		uint64_t word = v * words_per_vec;
 		uint32_t cnt = 0;
-		for (uint64_t r0 = begin; r0 < end; r0 += 64) {
+		for (uint64_t r0 = begin; r0 < begin + V; r0 += 64, word++) {
 			const uint64_t row = r0 + lane;
-			const bool pass = row < end && row_passes<STR>(fs, ss, lip, row);
-			cnt += (uint32_t)__popcll(__ballot(pass));
+			bool pass = row < end && passes(row);
+			for (uint32_t i = 0; i < lip.n; i++) {
+				pass = pass && lip_contains(lip.f[i], row);
+			}
+			const uint64_t m = __ballot(pass);
+			cnt += (uint32_t)__popcll(m);
+			if (lane == 0) {
+				pass_bits[word] = m;
+			}
 		}
 		if (lane == 0) {
 			packed[v] = (unsigned long long)cnt | (cnt ? (1ull << PACK_SHIFT) : 0ull);
@@ -242,20 +245,24 @@ __device__ __forceinline__ void tscan_count(uint32_t lane, uint64_t wave, uint64
 	}
 }
 __global__ __launch_bounds__(256) void polr_tscan_count_kernel(DevFilterSet fs, DevLipSet lip, uint64_t n_rows, uint32_t V,
-                                                              uint64_t n_vec, unsigned long long *__restrict__ packed) {
+                                                              uint64_t n_vec, unsigned long long *__restrict__ packed,
+                                                              unsigned long long *__restrict__ pass_bits) {
 	const uint32_t lane = threadIdx.x & 63;
 	const uint64_t wave = ((uint64_t)blockIdx.x * blockDim.x + threadIdx.x) >> 6;
 	const uint64_t n_waves = ((uint64_t)gridDim.x * blockDim.x) >> 6;
-	tscan_count<false>(lane, wave, n_waves, fs, nullptr, lip, n_rows, V, n_vec, packed);
+	tscan_count(lane, wave, n_waves, lip, n_rows, V, n_vec, packed, pass_bits,
+	            [&](uint64_t row) { return row_passes_filters(fs, row); });
 }
-// ... with VARCHAR comparisons
+// ... with VARCHAR comparisons, evaluated for the rows the integer filters keep
 __global__ __launch_bounds__(256) void polr_tscan_count_str_kernel(DevFilterSet fs, DevStrSet ss, DevLipSet lip, uint64_t n_rows,
                                                                   uint32_t V, uint64_t n_vec,
-                                                                  unsigned long long *__restrict__ packed) {
+                                                                  unsigned long long *__restrict__ packed,
+                                                                  unsigned long long *__restrict__ pass_bits) {
 	const uint32_t lane = threadIdx.x & 63;
 	const uint64_t wave = ((uint64_t)blockIdx.x * blockDim.x + threadIdx.x) >> 6;
 	const uint64_t n_waves = ((uint64_t)gridDim.x * blockDim.x) >> 6;
-	tscan_count<true>(lane, wave, n_waves, fs, &ss, lip, n_rows, V, n_vec, packed);
+	tscan_count(lane, wave, n_waves, lip, n_rows, V, n_vec, packed, pass_bits,
+	            [&](uint64_t row) { return row_passes_filters(fs, row) && row_passes_str(ss, row); });
 }
 
 // block sums of 1024 packed entries each
@@ -350,69 +357,12 @@ __global__ __launch_bounds__(1024) void polr_tscan_apply_kernel(unsigned long lo
 	}
 }
 
-// one wave per vector: ascending row ids of the survivors, chunk boundary of every non-empty vector
-template <bool STR>
-__device__ __forceinline__ void tscan_write(uint32_t lane, uint64_t wave, uint64_t n_waves, const DevFilterSet &fs, const DevStrSet *ss, const DevLipSet &lip, uint64_t n_rows,
-                                            uint32_t V, uint64_t n_vec, const unsigned long long *__restrict__ prefix,
-                                            uint32_t *__restrict__ sel, uint64_t *__restrict__ chunk_offsets,
-                                            const unsigned long long *__restrict__ totals) {
-	if (wave == 0 && lane == 0) {
-		chunk_offsets[totals[1]] = totals[0]; // the end of the last chunk
-	}
-	for (uint64_t v = wave; v < n_vec; v += n_waves) {
-		const unsigned long long pv = prefix[v];
-		if (!(pv >> 63)) {
-			continue; // no survivor: the scan skips the vector
-		}
-		uint64_t out = pv & PACK_MASK;
-		const uint64_t chunk = (pv & ~(1ull << 63)) >> PACK_SHIFT;
-		if (lane == 0) {
-			chunk_offsets[chunk] = out;
-		}
-		const uint64_t begin = v * V;
-		const uint64_t end = begin + V < n_rows ? begin + V : n_rows;
-		for (uint64_t r0 = begin; r0 < end; r0 += 64) {
-			const uint64_t row = r0 + lane;
-			const bool pass = row < end && row_passes<STR>(fs, ss, lip, row);
-			const uint64_t m = __ballot(pass);
-			if (pass) {
-				sel[out + lane_rank(m)] = (uint32_t)row;
-			}
-			out += (uint64_t)__popcll(m);
-		}
-	}
-}
-__global__ __launch_bounds__(256) void polr_tscan_write_kernel(DevFilterSet fs, DevLipSet lip, uint64_t n_rows, uint32_t V,
-                                                              uint64_t n_vec,
-                                                              const unsigned long long *__restrict__ prefix,
-                                                              uint32_t *__restrict__ sel,
-                                                              uint64_t *__restrict__ chunk_offsets,
-                                                              const unsigned long long *__restrict__ totals) {
-	const uint32_t lane = threadIdx.x & 63;
-	const uint64_t wave = ((uint64_t)blockIdx.x * blockDim.x + threadIdx.x) >> 6;
-	const uint64_t n_waves = ((uint64_t)gridDim.x * blockDim.x) >> 6;
-	tscan_write<false>(lane, wave, n_waves, fs, nullptr, lip, n_rows, V, n_vec, prefix, sel, chunk_offsets, totals);
-}
-__global__ __launch_bounds__(256) void polr_tscan_write_str_kernel(DevFilterSet fs, DevStrSet ss, DevLipSet lip, uint64_t n_rows,
-                                                                  uint32_t V, uint64_t n_vec,
-                                                                  const unsigned long long *__restrict__ prefix,
-                                                                  uint32_t *__restrict__ sel,
-                                                                  uint64_t *__restrict__ chunk_offsets,
-                                                                  const unsigned long long *__restrict__ totals) {
-	const uint32_t lane = threadIdx.x & 63;
-	const uint64_t wave = ((uint64_t)blockIdx.x * blockDim.x + threadIdx.x) >> 6;
-	const uint64_t n_waves = ((uint64_t)gridDim.x * blockDim.x) >> 6;
-	tscan_write<true>(lane, wave, n_waves, fs, &ss, lip, n_rows, V, n_vec, prefix, sel, chunk_offsets, totals);
-}
-
 // ---- expression filters (polr_pipeline_scan_filter_expr): what the reference evaluates in a PhysicalFilter behind the scan
 // -- OR / NOT trees, IN lists, LIKE -- as a postfix program (lowered by polr_filter_plan.h).  The program is wave-uniform: the
 // nodes travel in the kernel argument, leaves / values / segments / constant bytes in one buffer of the pipeline read at
 // uniform addresses; only the evaluation of a leaf is per lane.  A row first evaluates the leaves column by column -- the cell
 // of a column is loaded once, a NULL row's cell never -- into one bit per leaf and one NULL bit per column, then walks the
-// nodes over an operand stack of two 32-bit words per lane (true bits, NULL bits; a NULL's true bit is 0).  The counting
-// pass stores the ballot of every 64-row step (LIP included) in the pipeline's pass-bit buffer, ceil(V / 64) words per
-// vector; the writing pass reads those words and evaluates nothing.
+// nodes over an operand stack of two 32-bit words per lane (true bits, NULL bits; a NULL's true bit is 0).
 struct DevFxCol {
 	const uint8_t *data;
 	const uint8_t *valid;
@@ -434,26 +384,7 @@ struct DevFxProg {
 __device__ __forceinline__ bool fx_leaf_int(const DevFxProg &px, const PolrFxLeaf lf, uint64_t v, bool is_signed) {
 	bool r = false;
 	for (uint32_t i = lf.first_value; i < lf.first_value + lf.n_values; i++) {
-		const int64_t k = px.values[i].constant;
-		bool h;
-		if (is_signed) {
-			const int64_t a = (int64_t)v;
-			h = lf.op == POLR_CMP_EQ   ? a == k
-			    : lf.op == POLR_CMP_NE ? a != k
-			    : lf.op == POLR_CMP_LT ? a < k
-			    : lf.op == POLR_CMP_GT ? a > k
-			    : lf.op == POLR_CMP_LE ? a <= k
-			                           : a >= k;
-		} else {
-			const uint64_t c = (uint64_t)k; // (host: constant >= 0 for unsigned columns)
-			h = lf.op == POLR_CMP_EQ   ? v == c
-			    : lf.op == POLR_CMP_NE ? v != c
-			    : lf.op == POLR_CMP_LT ? v < c
-			    : lf.op == POLR_CMP_GT ? v > c
-			    : lf.op == POLR_CMP_LE ? v <= c
-			                           : v >= c;
-		}
-		r = r || h;
+		r = r || int_cmp_holds(v, px.values[i].constant, lf.op, is_signed);
 	}
 	return r;
 }
@@ -540,31 +471,11 @@ __global__ __launch_bounds__(256) void polr_tscan_count_expr_kernel(DevFxProg px
 	const uint32_t lane = threadIdx.x & 63;
 	const uint64_t wave = ((uint64_t)blockIdx.x * blockDim.x + threadIdx.x) >> 6;
 	const uint64_t n_waves = ((uint64_t)gridDim.x * blockDim.x) >> 6;
-	const uint64_t words_per_vec = ((uint64_t)V + 63) >> 6;
-	for (uint64_t v = wave; v < n_vec; v += n_waves) {
-		const uint64_t begin = v * V;
-		const uint64_t end = begin + V < n_rows ? begin + V : n_rows;
-		uint64_t word = v * words_per_vec;
-		uint32_t cnt = 0;
-		for (uint64_t r0 = begin; r0 < end; r0 += 64, word++) {
-			const uint64_t row = r0 + lane;
-			bool pass = row < end && fx_row_true(px, row);
-			for (uint32_t i = 0; i < lip.n; i++) {
-				pass = pass && lip_contains(lip.f[i], row);
-			}
-			const uint64_t m = __ballot(pass);
-			cnt += (uint32_t)__popcll(m);
-			if (lane == 0) {
-				pass_bits[word] = m;
-			}
-		}
-		if (lane == 0) {
-			packed[v] = (unsigned long long)cnt | (cnt ? (1ull << PACK_SHIFT) : 0ull);
-		}
-	}
+	tscan_count(lane, wave, n_waves, lip, n_rows, V, n_vec, packed, pass_bits, [&](uint64_t row) { return fx_row_true(px, row); });
 }
 
-// tscan_write with the rows that pass read from the counting pass's bits
+// the writing pass of every scan, one wave per vector: ascending row ids of the survivors, read from the counting pass's
+// bits, and the chunk boundary of every non-empty vector
 __global__ __launch_bounds__(256) void polr_tscan_write_bits_kernel(const unsigned long long *__restrict__ pass_bits, uint64_t n_rows,
                                                                    uint32_t V, uint64_t n_vec,
                                                                    const unsigned long long *__restrict__ prefix,
@@ -716,13 +627,26 @@ static int scan_check_heap(polr_pipeline *p, hipStream_t st, uint32_t col) {
 	return POLR_OK;
 }
 
-// the scan's scratch and result buffers, grown to the table and the vector count (see scan_filter_run)
-static int scan_buffers(polr_pipeline *p, uint64_t n_rows, uint64_t n_vec, uint64_t n_blocks) {
+// the vector size and the table fit the scan: what every entry point checks before it looks at its filters
+static int scan_check_shape(polr_pipeline *p, uint32_t vector_size) {
+	polr_ctx *ctx = p->ctx;
+	if (vector_size < 2 || vector_size > 65536) {
+		POLR_FAIL(ctx, POLR_E_INVALID, "vector size %u out of range", vector_size);
+	}
+	if (p->n_probe_rows >= 0xFFFFFFF0ull) {
+		POLR_FAIL(ctx, POLR_E_UNSUPPORTED, "source partition too large for 32-bit row ids");
+	}
+	return POLR_OK;
+}
+
+// the scan's scratch and result buffers, grown to the table, the vector count and the pass-bit words (see scan_run)
+static int scan_buffers(polr_pipeline *p, uint64_t n_rows, uint64_t n_vec, uint64_t n_blocks, uint64_t n_words) {
 	polr_ctx *ctx = p->ctx;
 	const uint32_t *old_sel = p->scan_sel;
 	hipError_t e = p->scan_packed.ensure(std::max<uint64_t>(n_vec, 1));
 	e = e == hipSuccess ? p->scan_sums.ensure(std::max<uint64_t>(n_blocks, 1)) : e;
 	e = e == hipSuccess ? p->scan_totals.ensure(2) : e;
+	e = e == hipSuccess ? p->scan_pass_bits.ensure(std::max<uint64_t>(n_words, 1)) : e;
 	e = e == hipSuccess ? p->scan_sel.ensure(std::max<uint64_t>(n_rows, 1)) : e;
 	e = e == hipSuccess ? p->scan_offsets_dev.ensure(n_vec + 1) : e;
 	if (p->sel_dev && p->sel_dev == old_sel && old_sel != p->scan_sel) {
@@ -760,8 +684,61 @@ static int scan_install(polr_pipeline *p, uint32_t vector_size, const uint64_t *
 	return POLR_OK;
 }
 
-// The scan behind both entry points.  `filters`: polr_pipeline_scan_filter[_lip], every filter an integer one whatever the
-// column's width; `sfilters`: polr_pipeline_scan_filter_str, where a comparison on a 16-byte column is a VARCHAR one.
+// The scan behind all four entry points, from the settling of a re-scan to the installed result.  The caller has checked
+// and lowered its filters (and uploaded what they need); `enqueue_count(grid, lip, n_rows, n_vec, packed, pass_bits)` enqueues
+// its counting kernel on `st`.
+template <class EnqueueCount>
+static int scan_run(polr_pipeline *p, hipStream_t st, uint32_t vector_size, const DevLipSet &lip, uint64_t *n_selected,
+                    uint64_t *n_chunks, EnqueueCount enqueue_count) {
+	polr_ctx *ctx = p->ctx;
+	if (p->scan_valid) {
+		// A re-scan rewrites the selection, the chunk boundaries and the device copies of the pipeline in place, and runs
+		// of the previous scan may still be in flight on their multiplexers' streams (passes are enqueued without a
+		// host synchronisation): settle the device first.  (The first scan of a pipeline has nothing to wait for.)
+		HIPCHK(ctx, hipDeviceSynchronize());
+	}
+	const uint64_t n_rows = p->n_probe_rows;
+	const uint64_t n_vec = (n_rows + vector_size - 1) / vector_size;
+	const uint64_t n_blocks = (n_vec + 1023) / 1024;
+	if (n_vec >= (1ull << 23)) {
+		POLR_FAIL(ctx, POLR_E_UNSUPPORTED, "more than 2^23 scan vectors per partition");
+	}
+	// Scratch and result buffers belong to the pipeline and are sized for the worst case (every row survives, every
+	// vector is a chunk; one pass-bit word per 64-row step of a vector), so the whole scan is enqueued without a host
+	// round trip in the middle; one synchronisation at the end reads the two totals.
+	if (int rc = scan_buffers(p, n_rows, n_vec, n_blocks, n_vec * (((uint64_t)vector_size + 63) / 64))) {
+		return rc;
+	}
+	unsigned long long *packed = p->scan_packed, *sums = p->scan_sums, *totals = p->scan_totals, *bits = p->scan_pass_bits;
+	uint32_t *sel = p->scan_sel;
+	uint64_t *offs = p->scan_offsets_dev;
+	uint64_t h_tot[2] = {0, 0};
+	hipError_t e = hipSuccess;
+	if (n_vec) {
+		const uint32_t waves_per_block = 4;
+		const uint32_t grid = (uint32_t)std::min<uint64_t>((n_vec + waves_per_block - 1) / waves_per_block,
+		                                                   (uint64_t)ctx->n_cus * 8);
+		enqueue_count(grid, lip, n_rows, n_vec, packed, bits);
+		hipLaunchKernelGGL(polr_tscan_block_sums_kernel, dim3((uint32_t)n_blocks), dim3(1024), 0, st, packed, n_vec, sums);
+		hipLaunchKernelGGL(polr_tscan_sums_kernel, dim3(1), dim3(1024), 0, st, sums, n_blocks, totals);
+		hipLaunchKernelGGL(polr_tscan_apply_kernel, dim3((uint32_t)n_blocks), dim3(1024), 0, st, packed, n_vec, sums);
+		hipLaunchKernelGGL(polr_tscan_write_bits_kernel, dim3(grid), dim3(256), 0, st, (const unsigned long long *)bits, n_rows,
+		                   vector_size, n_vec, (const unsigned long long *)packed, sel, offs, (const unsigned long long *)totals);
+		e = hipMemcpyAsync(h_tot, totals, 16, hipMemcpyDeviceToHost, st);
+		e = e == hipSuccess ? hipStreamSynchronize(st) : e;
+	} else {
+		e = hipMemsetAsync(offs, 0, 8, st);
+		e = e == hipSuccess ? hipStreamSynchronize(st) : e;
+	}
+	if (e != hipSuccess) {
+		POLR_FAIL(ctx, POLR_E_HIP, "scan filter failed: %s", hipGetErrorString(e));
+	}
+	return scan_install(p, vector_size, h_tot, n_selected, n_chunks);
+}
+
+// The integer and VARCHAR entry points: filters checked and lowered, then scan_run.  `filters`:
+// polr_pipeline_scan_filter[_lip], every filter an integer one whatever the column's width; `sfilters`:
+// polr_pipeline_scan_filter_str, where a comparison on a 16-byte column is a VARCHAR one.
 static int scan_filter_run(polr_pipeline *p, void *stream, const polr_scan_filter *filters, const polr_scan_filter_str *sfilters,
                            uint32_t n_filters, uint32_t lip_joins, uint32_t vector_size, uint64_t *n_selected,
                            uint64_t *n_chunks) {
@@ -769,11 +746,8 @@ static int scan_filter_run(polr_pipeline *p, void *stream, const polr_scan_filte
 	if (n_filters > POLR_MAX_FILTERS) {
 		POLR_FAIL(ctx, POLR_E_UNSUPPORTED, "at most %d pushed-down filters", POLR_MAX_FILTERS);
 	}
-	if (vector_size < 2 || vector_size > 65536) {
-		POLR_FAIL(ctx, POLR_E_INVALID, "vector size %u out of range", vector_size);
-	}
-	if (p->n_probe_rows >= 0xFFFFFFF0ull) {
-		POLR_FAIL(ctx, POLR_E_UNSUPPORTED, "source partition too large for 32-bit row ids");
+	if (int rc = scan_check_shape(p, vector_size)) {
+		return rc;
 	}
 	DevFilterSet fs;
 	memset(&fs, 0, sizeof(fs));
@@ -874,72 +848,26 @@ static int scan_filter_run(polr_pipeline *p, void *stream, const polr_scan_filte
 		HIPCHK(ctx, hipMemcpy(p->scan_str_tails, tails.data(), tails.size(), hipMemcpyHostToDevice));
 	}
 	ss.tails = p->scan_str_tails;
-	if (p->scan_valid) {
-		// A re-scan rewrites the selection, the chunk boundaries and the device copies of the pipeline in place, and runs
-		// of the previous scan may still be in flight on their multiplexers' streams (passes are enqueued without a
-		// host synchronisation): settle the device first.  (The first scan of a pipeline has nothing to wait for.)
-		HIPCHK(ctx, hipDeviceSynchronize());
-	}
-	const uint64_t n_rows = p->n_probe_rows;
-	const uint64_t n_vec = (n_rows + vector_size - 1) / vector_size;
-	const uint64_t n_blocks = (n_vec + 1023) / 1024;
-	if (n_vec >= (1ull << 23)) {
-		POLR_FAIL(ctx, POLR_E_UNSUPPORTED, "more than 2^23 scan vectors per partition");
-	}
-	// Scratch and result buffers belong to the pipeline and are sized for the worst case (every row survives, every
-	// vector is a chunk), so the whole scan is enqueued without a host round trip in the middle; one
-	// synchronisation at the end reads the two totals.
-	if (int rc = scan_buffers(p, n_rows, n_vec, n_blocks)) {
-		return rc;
-	}
-	unsigned long long *packed = p->scan_packed, *sums = p->scan_sums, *totals = p->scan_totals;
-	uint32_t *sel = p->scan_sel;
-	uint64_t *offs = p->scan_offsets_dev;
-	uint64_t h_tot[2] = {0, 0};
-	hipError_t e = hipSuccess;
-	if (n_vec) {
-		const uint32_t waves_per_block = 4;
-		const uint32_t grid = (uint32_t)std::min<uint64_t>((n_vec + waves_per_block - 1) / waves_per_block,
-		                                                   (uint64_t)ctx->n_cus * 8);
-		if (ss.n_cols) {
-			hipLaunchKernelGGL(polr_tscan_count_str_kernel, dim3(grid), dim3(256), 0, st, fs, ss, lip, n_rows, vector_size, n_vec,
-			                   packed);
-		} else {
-			hipLaunchKernelGGL(polr_tscan_count_kernel, dim3(grid), dim3(256), 0, st, fs, lip, n_rows, vector_size, n_vec, packed);
-		}
-		hipLaunchKernelGGL(polr_tscan_block_sums_kernel, dim3((uint32_t)n_blocks), dim3(1024), 0, st, packed, n_vec, sums);
-		hipLaunchKernelGGL(polr_tscan_sums_kernel, dim3(1), dim3(1024), 0, st, sums, n_blocks, totals);
-		hipLaunchKernelGGL(polr_tscan_apply_kernel, dim3((uint32_t)n_blocks), dim3(1024), 0, st, packed, n_vec, sums);
-		if (ss.n_cols) {
-			hipLaunchKernelGGL(polr_tscan_write_str_kernel, dim3(grid), dim3(256), 0, st, fs, ss, lip, n_rows, vector_size, n_vec,
-			                   packed, sel, offs, totals);
-		} else {
-			hipLaunchKernelGGL(polr_tscan_write_kernel, dim3(grid), dim3(256), 0, st, fs, lip, n_rows, vector_size, n_vec, packed,
-			                   sel, offs, totals);
-		}
-		e = hipMemcpyAsync(h_tot, totals, 16, hipMemcpyDeviceToHost, st);
-		e = e == hipSuccess ? hipStreamSynchronize(st) : e;
-	} else {
-		e = hipMemsetAsync(offs, 0, 8, st);
-		e = e == hipSuccess ? hipStreamSynchronize(st) : e;
-	}
-	if (e != hipSuccess) {
-		POLR_FAIL(ctx, POLR_E_HIP, "scan filter failed: %s", hipGetErrorString(e));
-	}
-	return scan_install(p, vector_size, h_tot, n_selected, n_chunks);
+	return scan_run(p, st, vector_size, lip, n_selected, n_chunks,
+	                [&](uint32_t grid, const DevLipSet &l, uint64_t n_rows, uint64_t n_vec, unsigned long long *packed, unsigned long long *bits) {
+		                if (ss.n_cols) {
+			                hipLaunchKernelGGL(polr_tscan_count_str_kernel, dim3(grid), dim3(256), 0, st, fs, ss, l, n_rows, vector_size,
+			                                   n_vec, packed, bits);
+		                } else {
+			                hipLaunchKernelGGL(polr_tscan_count_kernel, dim3(grid), dim3(256), 0, st, fs, l, n_rows, vector_size, n_vec,
+			                                   packed, bits);
+		                }
+	                });
 }
 
 // polr_pipeline_scan_filter_expr: the program checked and lowered on the host (polr_filter_plan.h), uploaded into the
-// pipeline's program buffer, one evaluating pass and one pass over its bits
+// pipeline's program buffer, then scan_run
 static int scan_filter_expr_run(polr_pipeline *p, void *stream, const polr_filter_node *nodes, uint32_t n_nodes,
                                 const polr_filter_value *values, uint32_t n_values, uint32_t lip_joins, uint32_t vector_size,
                                 uint64_t *n_selected, uint64_t *n_chunks) {
 	polr_ctx *ctx = p->ctx;
-	if (vector_size < 2 || vector_size > 65536) {
-		POLR_FAIL(ctx, POLR_E_INVALID, "vector size %u out of range", vector_size);
-	}
-	if (p->n_probe_rows >= 0xFFFFFFF0ull) {
-		POLR_FAIL(ctx, POLR_E_UNSUPPORTED, "source partition too large for 32-bit row ids");
+	if (int rc = scan_check_shape(p, vector_size)) {
+		return rc;
 	}
 	std::vector<PolrFilterColumn> cols(p->n_probe_cols);
 	for (uint32_t c = 0; c < p->n_probe_cols; c++) {
@@ -1001,46 +929,11 @@ static int scan_filter_expr_run(polr_pipeline *p, void *stream, const polr_filte
 	px.leaves = (const PolrFxLeaf *)(p->scan_expr_prog + leaves_at);
 	px.segs = (const polr_like_seg *)(p->scan_expr_prog + segs_at);
 	px.bytes = p->scan_expr_prog + bytes_at;
-	if (p->scan_valid) {
-		HIPCHK(ctx, hipDeviceSynchronize()); // (runs of the scan before may be in flight: see scan_filter_run)
-	}
-	const uint64_t n_rows = p->n_probe_rows;
-	const uint64_t n_vec = (n_rows + vector_size - 1) / vector_size;
-	const uint64_t n_blocks = (n_vec + 1023) / 1024;
-	if (n_vec >= (1ull << 23)) {
-		POLR_FAIL(ctx, POLR_E_UNSUPPORTED, "more than 2^23 scan vectors per partition");
-	}
-	if (int rc = scan_buffers(p, n_rows, n_vec, n_blocks)) {
-		return rc;
-	}
-	// the pass bits: one word per 64-row step of a vector
-	const uint64_t n_words = n_vec * (((uint64_t)vector_size + 63) / 64);
-	HIPCHK(ctx, p->scan_pass_bits.ensure(n_words));
-	unsigned long long *packed = p->scan_packed, *sums = p->scan_sums, *totals = p->scan_totals;
-	uint64_t h_tot[2] = {0, 0};
-	hipError_t e = hipSuccess;
-	if (n_vec) {
-		const uint32_t waves_per_block = 4;
-		const uint32_t grid = (uint32_t)std::min<uint64_t>((n_vec + waves_per_block - 1) / waves_per_block,
-		                                                   (uint64_t)ctx->n_cus * 8);
-		hipLaunchKernelGGL(polr_tscan_count_expr_kernel, dim3(grid), dim3(256), 0, st, px, lip, n_rows, vector_size, n_vec, packed,
-		                   p->scan_pass_bits.get());
-		hipLaunchKernelGGL(polr_tscan_block_sums_kernel, dim3((uint32_t)n_blocks), dim3(1024), 0, st, packed, n_vec, sums);
-		hipLaunchKernelGGL(polr_tscan_sums_kernel, dim3(1), dim3(1024), 0, st, sums, n_blocks, totals);
-		hipLaunchKernelGGL(polr_tscan_apply_kernel, dim3((uint32_t)n_blocks), dim3(1024), 0, st, packed, n_vec, sums);
-		hipLaunchKernelGGL(polr_tscan_write_bits_kernel, dim3(grid), dim3(256), 0, st, (const unsigned long long *)p->scan_pass_bits.get(),
-		                   n_rows, vector_size, n_vec, (const unsigned long long *)packed, p->scan_sel.get(), p->scan_offsets_dev.get(),
-		                   (const unsigned long long *)totals);
-		e = hipMemcpyAsync(h_tot, totals, 16, hipMemcpyDeviceToHost, st);
-		e = e == hipSuccess ? hipStreamSynchronize(st) : e;
-	} else {
-		e = hipMemsetAsync(p->scan_offsets_dev, 0, 8, st);
-		e = e == hipSuccess ? hipStreamSynchronize(st) : e;
-	}
-	if (e != hipSuccess) {
-		POLR_FAIL(ctx, POLR_E_HIP, "scan filter failed: %s", hipGetErrorString(e));
-	}
-	return scan_install(p, vector_size, h_tot, n_selected, n_chunks);
+	return scan_run(p, st, vector_size, lip, n_selected, n_chunks,
+	                [&](uint32_t grid, const DevLipSet &l, uint64_t n_rows, uint64_t n_vec, unsigned long long *packed, unsigned long long *bits) {
+		                hipLaunchKernelGGL(polr_tscan_count_expr_kernel, dim3(grid), dim3(256), 0, st, px, l, n_rows, vector_size, n_vec,
+		                                   packed, bits);
+	                });
 }
 
 extern "C" {

@@ -264,7 +264,9 @@ int polr_pipeline_launch_info(polr_pipeline *p, int materialize, polr_launch_inf
  * stays in HBM and becomes the pipeline's source (as polr_pipeline_set_selection would install it);
  * multiplexers take the boundaries with polr_mpx_use_scan_chunks.  n_filters == 0: every row passes.
  * A negative constant against an unsigned column is POLR_E_INVALID; OR-conjunctions are not pushed
- * down on this path (POLR_E_UNSUPPORTED would be the caller's: keep them in a host filter). */
+ * down on this path (POLR_E_UNSUPPORTED would be the caller's: keep them in a host filter).
+ * Whichever of the four scan entry points is called, every row's filters are evaluated once: the counting pass keeps
+ * one bit per table row in a buffer of the pipeline, the writing pass reads those bits. */
 enum {
 	POLR_CMP_EQ = 0, POLR_CMP_NE = 1, POLR_CMP_LT = 2, POLR_CMP_GT = 3, POLR_CMP_LE = 4, POLR_CMP_GE = 5,
 	POLR_CMP_IS_NULL = 6, POLR_CMP_IS_NOT_NULL = 7,
@@ -364,9 +366,7 @@ int polr_pipeline_scan_filter_str(polr_pipeline *p, void *stream, const polr_sca
  *    than POLR_MAX_FILTER_VALUES values, more than POLR_MAX_FILTER_BYTES bytes of VARCHAR constants and patterns together,
  *    one constant longer than POLR_MAX_FILTER_STRING, more than 8 distinct columns, a NUL byte in a pattern.
  *  - A refused call enqueues nothing and leaves the scan result before it in place.  nodes, values and the values' bytes
- *    are host memory and are copied by the call.
- * Every row's expression is evaluated once: the counting pass keeps one bit per table row in a buffer of the pipeline
- * (allocated by the first such call), the writing pass reads those bits. */
+ *    are host memory and are copied by the call. */
 #define POLR_MAX_FILTER_NODES 64    /* nodes of one expression */
 #define POLR_MAX_FILTER_DEPTH 32    /* operand stack depth the postfix order may reach */
 #define POLR_MAX_FILTER_VALUES 64   /* constants of one call (comparison constants, IN members, patterns) */

@@ -4,7 +4,9 @@ same process.
 usage: python tools/bench_scan_expr.py <duckdb-polr_amd tree> <tag> [log2 rows, default 26]   -> one JSON line per case
 (host clock around the C call, which ends in a synchronise: 3 warm-up calls, then 9 timed ones; median, min, max; bytes/s =
 the algorithmic bytes of DESIGN section 4 over the median).  The tree is where the library AND its binding are taken from,
-so that the yardstick cases also run on a build from before the expression scan, which skips the rest.  To compare two
+so that the yardstick cases also run on a build from before the expression scan, which skips the rest.  (alg_bytes and
+GBps are those of this tree's scan -- every column once, plus the pass bits --, also when the tree named is an older one
+whose yardstick entry points read their columns twice: compare the times.)  To compare two
 builds, run it on each, alternating, one process each.  Cases:
   inline_eq/str, like_heap/str   the cases of tools/bench_scan_varchar.py through scan_filter_str (the yardstick)
   inline_eq/expr, like_heap/expr the same filters as AND-only programs
@@ -122,15 +124,16 @@ def main():
     f = capi.like_pushdown(b"Japan%")
     lo, hi = f[0][1], f[1][1]
     want_like = sum(int(c) for w, c in zip(words + longs, np.bincount(hpick, minlength=164)) if lo <= w < hi)
+    bits = 2 * n // 8  # the pass bits: written once, read once
     t = timed(lambda: pipe.scan_filter([(1, "=", word)]))
     assert pipe.scan[0] == want_eq, (pipe.scan, want_eq)
-    report("inline_eq/str", n, want_eq, 2 * 16 * n + 4 * want_eq, t, constant=word.decode())
+    report("inline_eq/str", n, want_eq, 16 * n + bits + 4 * want_eq, t, constant=word.decode())
     t = timed(lambda: pipe.scan_filter([(2, op, c) for op, c in f]))
     assert pipe.scan[0] == want_like, (pipe.scan, want_like)
-    report("like_heap/str", n, want_like, 2 * 16 * n + 2 * 2 * n_long + 4 * want_like, t, pattern="Japan%", heap_rows=n_long)
+    report("like_heap/str", n, want_like, 16 * n + 2 * n_long + bits + 4 * want_like, t, pattern="Japan%",
+           heap_rows=n_long)
     if not HAS_EXPR:
         return
-    bits = 2 * n // 8  # the pass bits: written once, read once
     t = timed(lambda: pipe.scan_filter_expr(("cmp", 1, "=", word)))
     assert pipe.scan[0] == want_eq, (pipe.scan, want_eq)
     report("inline_eq/expr", n, want_eq, 16 * n + bits + 4 * want_eq, t, constant=word.decode())

@@ -4,7 +4,8 @@ usage: python tools/bench_scan_varchar.py <duckdb-polr_amd tree> <tag> [log2 row
 (host clock around the C call, which ends in a synchronise: 3 warm-up calls, then 9 timed ones; median, min, max; bytes/s =
 the algorithmic bytes of DESIGN section 4 over the median).  The tree is where the library AND its binding are taken from,
 so that the integer case -- the yardstick -- also runs on a build from before the VARCHAR filters, which skips the
-string cases.  To compare two builds, run it on each, alternating, one process each.  Cases:
+string cases.  (alg_bytes and GBps are those of this tree's scan -- every column once, plus the pass bits --, also
+when the tree named is an older one that reads its columns twice: compare the times.)  To compare two builds, run it on each, alternating, one process each.  Cases:
   int8_lt        one filter on an 8-byte integer column (the yardstick)
   inline_eq      = on an inline-only VARCHAR column, about 1 % of the rows pass (first without a heap handed over: the call
                  then counts the column's long cells before it scans; then with one)
@@ -91,7 +92,8 @@ def main():
     want = int((i8 < cut).sum())
     t = timed(lambda: pipe.scan_filter([(1, "<", cut)]))
     assert pipe.scan[0] == want, (pipe.scan, want)
-    report("int8_lt", n, want, 2 * 8 * n + 4 * want, t)
+    bits = 2 * n // 8  # the pass bits: written once, read once
+    report("int8_lt", n, want, 8 * n + bits + 4 * want, t)
     if not HAS_STR:
         return
     word = words[37]
@@ -102,7 +104,7 @@ def main():
         t = timed(lambda: pipe.scan_filter([(2, "=", word)]))
         assert pipe.scan[0] == want, (pipe.scan, want)
         guard = 4 * n if case != "inline_eq" else 0  # (the length words of the guard pass)
-        report(case, n, want, 2 * 16 * n + guard + 4 * want, t, constant=word.decode())
+        report(case, n, want, 16 * n + bits + guard + 4 * want, t, constant=word.decode())
     f = capi.like_pushdown(b"Japan%")
     lo, hi = f[0][1], f[1][1]
     per_long = np.bincount(lpick, minlength=64)
@@ -111,8 +113,8 @@ def main():
     t = timed(lambda: pipe.scan_filter([(3, op, c) for op, c in f]))
     assert pipe.scan[0] == want, (pipe.scan, want)
     # heap bytes: both constants are 5 bytes long and tie with every long cell's prefix, so byte 4 decides: one byte per
-    # constant, per pass (what the memory system moves for it is a whole sector of a row's own heap copy)
-    report("like_heap", n, want, 2 * 16 * n + 2 * 2 * n_long + 4 * want, t, pattern="Japan%", heap_rows=n_long)
+    # constant (what the memory system moves for it is a whole sector of a row's own heap copy)
+    report("like_heap", n, want, 16 * n + 2 * n_long + bits + 4 * want, t, pattern="Japan%", heap_rows=n_long)
 
 
 if __name__ == "__main__":
