@@ -1084,10 +1084,7 @@ static int check_string_col_on_device(polr_out *o, hipStream_t st, const OutCol 
 	HIPCHK(ctx, hipMemcpyAsync(&h_long, n_long, 8, hipMemcpyDeviceToHost, st));
 	HIPCHK(ctx, hipStreamSynchronize(st));
 	if (h_long) {
-		POLR_FAIL(ctx, POLR_E_INVALID,
-		          "%s %u: %llu output rows hold strings longer than 12 bytes, but the column's heap was never put on the device "
-		          "(polr_ht_set_payload_heaps / polr_pipeline_set_probe_heaps)",
-		          what, idx, h_long);
+		POLR_FAIL_HEAP_NEVER_CAME(ctx, what, idx, h_long);
 	}
 	return POLR_OK;
 }

@@ -332,8 +332,10 @@ __global__ void polr_pack_bitmap_kernel(const uint8_t *__restrict__ bytes, uint6
 	bits[wd] = v;
 }
 
-// exclusive prefix of chunk_count -> chunk_base (single block; output chunk lists are short)
-__global__ void polr_chunk_prefix_kernel(const uint32_t *__restrict__ chunk_count, uint32_t n_chunks,
+// exclusive prefix of chunk_count -> chunk_base (single block; output chunk lists are short).  Sums are 64-bit whatever
+// the counts' type: T = uint32_t for the chunks' row counts, uint64_t for their byte totals (polr_strout.hip)
+template <class T>
+__global__ void polr_chunk_prefix_kernel(const T *__restrict__ chunk_count, uint32_t n_chunks,
                                          uint64_t *__restrict__ chunk_base, uint64_t *total) {
 	__shared__ uint64_t sh[1024];
 	__shared__ uint64_t carry;
@@ -456,5 +458,10 @@ extern "C++" void polr_launch_pack_bitmap(hipStream_t st, const uint8_t *bytes, 
 
 extern "C++" void polr_launch_chunk_prefix(hipStream_t st, const uint32_t *chunk_count, uint32_t n_chunks,
                                            uint64_t *chunk_base, uint64_t *total) {
-	hipLaunchKernelGGL(polr_chunk_prefix_kernel, dim3(1), dim3(1024), 0, st, chunk_count, n_chunks, chunk_base, total);
+	hipLaunchKernelGGL(polr_chunk_prefix_kernel<uint32_t>, dim3(1), dim3(1024), 0, st, chunk_count, n_chunks, chunk_base, total);
+}
+
+extern "C++" void polr_launch_chunk_prefix(hipStream_t st, const uint64_t *chunk_bytes, uint32_t n_chunks,
+                                           uint64_t *chunk_base, uint64_t *total) {
+	hipLaunchKernelGGL(polr_chunk_prefix_kernel<uint64_t>, dim3(1), dim3(1024), 0, st, chunk_bytes, n_chunks, chunk_base, total);
 }

@@ -242,6 +242,15 @@ int polr_out_col(polr_pipeline *p, int32_t src_join, uint32_t src_col, OutCol *c
 // ... and POLR_E_UNSUPPORTED for anything but an integer column of up to 8 bytes (signed if 8): what cell-valued sinks read
 int polr_out_int_col(polr_pipeline *p, int32_t src_join, uint32_t src_col, OutCol *c, const char *what, uint32_t idx);
 
+// The refusal of a VARCHAR column the library uploaded whose heap never came, once a non-NULL cell longer than 12 bytes
+// turns up among the output rows (check_string_col_on_device of polr_agg.hip; polr_out_materialize_strings counts such
+// cells in its measuring pass): one message for every sink.
+#define POLR_FAIL_HEAP_NEVER_CAME(ctx_, what_, idx_, n_long_)                                                          \
+	POLR_FAIL(ctx_, POLR_E_INVALID,                                                                                    \
+	          "%s %u: %llu output rows hold strings longer than 12 bytes, but the column's heap was never put on the "   \
+	          "device (polr_ht_set_payload_heaps / polr_pipeline_set_probe_heaps)",                                      \
+	          what_, idx_, (unsigned long long)(n_long_))
+
 // Only the flat pool kernel folds tuples into a fused GROUP BY sink (DevOut::fused).  The entry points that launch the
 // per-round path kernel refuse such an output before they enqueue anything: that kernel would write row ids instead and
 // leave the group cells empty.
@@ -303,6 +312,9 @@ void polr_launch_pht_gather(hipStream_t st, const uint32_t *bits, const uint32_t
                             uint8_t *dst, uint8_t *dst_valid);
 void polr_launch_pack_bitmap(hipStream_t st, const uint8_t *bytes, uint64_t size, uint32_t *bits);
 void polr_launch_chunk_prefix(hipStream_t st, const uint32_t *chunk_count, uint32_t n_chunks, uint64_t *chunk_base,
+                              uint64_t *total);
+// ... of 64-bit counts (the chunks' heap bytes, polr_strout.hip): the same kernel, nothing truncated
+void polr_launch_chunk_prefix(hipStream_t st, const uint64_t *chunk_bytes, uint32_t n_chunks, uint64_t *chunk_base,
                               uint64_t *total);
 
 // shared between capi and mpx

@@ -45,6 +45,7 @@ EXPORTS = [
     "polr_pipeline_scan_filter_str",
     "polr_pipeline_scan_filter_expr",
     "polr_device_bytes_live",
+    "polr_out_materialize_strings",
 ]
 
 
@@ -338,6 +339,7 @@ def load():
     L.polr_out_stats.argtypes = [vp, vp, P(u64), P(u64), P(u32)]
     L.polr_out_fetch_ids.argtypes = [vp, vp, vp, u64]
     L.polr_out_materialize.argtypes = [vp, vp, i32, u32, vp, vp, u64, u32]
+    L.polr_out_materialize_strings.argtypes = [vp, vp, i32, u32, vp, vp, u64, vp, u64, P(u64), u32]
     L.polr_out_destroy.argtypes = [vp]
     L.polr_out_destroy.restype = None
     L.polr_probe_rounds.argtypes = [vp, vp, P(Round), u32, vp, vp]
@@ -980,6 +982,64 @@ class Output:
         self.ctx.check(self.ctx.L.polr_out_materialize(self.h, stream, src_join, src_col, data.ctypes.data,
                                                        valid.ctypes.data, n, 0))
         return data, valid
+
+    def materialize_strings_raw(self, src_join, src_col, stream=None, heap_cap=None, device=False):
+        """polr_out_materialize_strings -> (cells, valid, heap, heap_used): one string_t cell per output row (a V16 array),
+        the validity bytes, and the packed heap the long cells point into.  heap_cap=None: the sizing call first, then one
+        retry with the exact size; a heap_cap that is too small raises PolrError(E_OVERFLOW).  device=True: the three
+        arrays are uint8 torch tensors on the context's device (cells [n, 16]) and the cells' pointers are device
+        addresses inside `heap`; otherwise numpy arrays, the pointers host addresses inside `heap`."""
+        n, _, _ = self.stats(stream)
+        used = C.c_uint64()
+        if device:
+            import torch
+            dev = torch.device("cuda", torch.cuda.current_device())
+
+            def alloc(shape, fill=0):
+                t = torch.full(shape, fill, dtype=torch.uint8, device=dev)
+                torch.cuda.synchronize()
+                return t, t.data_ptr()
+        else:
+            def alloc(shape, fill=0):
+                a = np.full(shape, fill, dtype=np.uint8)
+                return a, a.ctypes.data
+        cells, p_cells = alloc((n, 16))
+        valid, p_valid = alloc((n,), 1)
+        sizing = heap_cap is None
+        for cap in (0, None) if sizing else (int(heap_cap),):
+            if cap is None:
+                cap = used.value
+            heap, p_heap = alloc((cap,))
+            rc = self.ctx.L.polr_out_materialize_strings(self.h, stream, src_join, src_col, p_cells, p_valid, n,
+                                                         p_heap if cap else None, cap, C.byref(used),
+                                                         COL_DEVICE if device else 0)
+            if not (sizing and cap == 0 and rc == E_OVERFLOW):  # (the sizing call said how much: once more, with that)
+                break
+        self.ctx.check(rc)
+        return (cells if device else cells.reshape(-1).view("V16")), valid, heap, used.value
+
+    def materialize_strings(self, src_join, src_col, stream=None):
+        """a VARCHAR column over the output rows -> [bytes or None (NULL)], decoded from the cells: inline strings from the
+        cell, long ones through the pointer relative to the heap's address"""
+        cells, valid, heap, used = self.materialize_strings_raw(src_join, src_col, stream)
+        raw = cells.view(np.uint8).reshape(-1, 16)
+        words = raw.view(np.uint32).reshape(-1, 4)
+        ptr = raw.view(np.uint64).reshape(-1, 2)[:, 1]
+        base, blob = heap.ctypes.data, heap.tobytes()
+        out = []
+        for i in range(len(raw)):
+            if not valid[i]:
+                out.append(None)
+                continue
+            ln = int(words[i, 0])
+            if ln <= 12:
+                out.append(raw[i, 4:4 + ln].tobytes())
+            else:
+                at = int(ptr[i]) - base
+                if at < 0 or at + ln > used:
+                    raise PolrError(E_INVALID, "row %d: cell points outside the heap" % i)
+                out.append(blob[at:at + ln])
+        return out
 
     def close(self):
         if self.h:

@@ -415,6 +415,39 @@ int polr_out_fetch_ids(polr_out *o, void *stream, uint32_t *dst, uint64_t dst_ro
  * src_col of join src_join.  dst_data/dst_valid are host or device pointers (dst_flags). */
 int polr_out_materialize(polr_out *o, void *stream, int32_t src_join, uint32_t src_col, void *dst_data,
                          uint8_t *dst_valid, uint64_t dst_rows, uint32_t dst_flags);
+/* A VARCHAR column of the output as strings the caller can read: complete string_t cells plus a packed heap of the long
+ * strings' bytes, both in the DESTINATION's address space (RowOperations::Gather for string_t, row_gather.cpp:47-86).
+ * polr_out_materialize copies a 16-byte cell as it is, so once the column's heap lives on the device (polr_ht_set_payload_heaps
+ * / polr_pipeline_set_probe_heaps, a POLR_COL_DEVICE column, a table received over polr_bcast_build) its long cells carry
+ * device pointers; this call is the one that hands such a column back.
+ *  - Rows and their order are those of polr_out_fetch_ids and polr_out_materialize (chunk-major); src_join / src_col as for
+ *    polr_out_materialize.  dst_flags & POLR_COL_DEVICE: dst_cells, dst_valid and dst_heap are device memory, otherwise host
+ *    memory.  dst_valid may be NULL.
+ *  - Cells: dst_cells[i] is a complete string_t.  A non-NULL string of at most 12 bytes: its length, its bytes, then ZERO
+ *    padding whatever the source cell's padding held (the reference compares inline cells as words).  A longer one: its
+ *    length, its first four bytes, and the pointer (uint64_t)dst_heap + offset.  A NULL row: validity 0 and an all-zero
+ *    cell; it takes no heap bytes and its source cell is never read.
+ *  - Heap: packed.  The offset of row i is the sum of the lengths of the non-NULL rows before i that are longer than 12
+ *    bytes: no gaps, no terminators, no sharing -- two output rows that name the same build row get a copy each.
+ *    *heap_used is the exact total, 64-bit throughout (a chunk's total may exceed 2^32), and is always set (0 by a call
+ *    that is refused with POLR_E_INVALID).
+ *  - heap_cap < *heap_used: POLR_E_OVERFLOW with *heap_used exact and dst_cells, dst_valid, dst_heap untouched -- one retry
+ *    with heap_cap = *heap_used succeeds.  dst_heap == NULL with heap_cap == 0 is the sizing call; it succeeds outright
+ *    when no output row is long (all inline, all NULL, or no rows -- also an output that no materialising run has filled).
+ *  - POLR_E_INVALID, nothing written: a column that is not 16 bytes wide; dst_rows below the output's rows; NULL dst_cells
+ *    with rows to write; dst_heap == NULL with heap_cap > 0; an output with a fused sink (it holds no row ids).  A column
+ *    the library uploaded whose heap never came and that has a non-NULL cell longer than 12 bytes among the output rows:
+ *    POLR_E_INVALID as for polr_out_aggregate_string, found by the measuring pass, which reads length words only and never
+ *    follows a pointer; such a column holding only inline strings works without a heap.
+ *  - Two passes over the output chunks: one measures (row id, validity and length word per row; one read-back of the
+ *    total decides overflow before anything is written), one writes.  The call returns after the destination is complete.
+ *    While it runs it holds scratch of 8 bytes per output row plus 16 bytes per output chunk and, for a host destination,
+ *    the staged cells (16 bytes per row), validity (1) and heap (*heap_used); all freed before it returns.
+ * Not provided: one heap copy shared by the output rows of one source row; compressed or dictionary output (the code
+ * column through polr_out_materialize plus polr_ht_fetch_dictionary already serves that). */
+int polr_out_materialize_strings(polr_out *o, void *stream, int32_t src_join, uint32_t src_col, void *dst_cells,
+                                 uint8_t *dst_valid, uint64_t dst_rows, void *dst_heap, uint64_t heap_cap,
+                                 uint64_t *heap_used, uint32_t dst_flags);
 
 /* ---- sink side on the device -------------------------------------------
  * PhysicalUngroupedAggregate over the pipeline's output (src/execution/operator/aggregate/
