@@ -696,6 +696,12 @@ struct HtMeta {
 	uint8_t payload_has_valid[62];
 };
 
+// bytes of a buffer of n bytes as polr_ht_export lists it and polr_ht_alloc_like allocates it: what the table that is
+// exported holds (DevBuf::alloc(n): n bytes, 16 for an empty buffer) -- never more, the receiving side copies that many
+static uint64_t export_bytes(uint64_t n) {
+	return n ? n : 16;
+}
+
 static void ht_buffers(const polr_ht *ht, std::vector<void *> &ptrs, std::vector<uint64_t> &bytes) {
 	const uint64_t rows = ht->kind == KIND_PERFECT ? ht->capacity : ht->n_rows_in;
 	if (ht->kind == KIND_PERFECT) {
@@ -708,15 +714,15 @@ static void ht_buffers(const polr_ht *ht, std::vector<void *> &ptrs, std::vector
 		ptrs.push_back(ht->table);
 		bytes.push_back(ht->capacity * sizeof(uint4));
 		ptrs.push_back(ht->rowids);
-		bytes.push_back(std::max<uint64_t>(ht->n_rows_in * 4, 16));
+		bytes.push_back(export_bytes(ht->n_rows_in * 4));
 	}
 	for (uint32_t i = 0; i < ht->n_payload; i++) {
 		const OwnedCol &c = build_col(ht, i);
 		ptrs.push_back(c.data);
-		bytes.push_back(std::max<uint64_t>(rows * c.width, 16));
+		bytes.push_back(export_bytes(rows * c.width));
 		if (c.valid) {
 			ptrs.push_back(c.valid);
-			bytes.push_back(std::max<uint64_t>(rows, 16));
+			bytes.push_back(export_bytes(rows));
 		}
 	}
 }
@@ -834,7 +840,7 @@ int polr_ht_alloc_like(polr_ctx *ctx, const void *meta, uint64_t meta_bytes, pol
 	ht->table = ht->table_mem;
 	ht->device_bytes += ht->table_mem.bytes();
 	if (m.kind == KIND_S16) {
-		HIPCHK(ctx, ht->rowids.alloc(std::max<uint64_t>(m.n_rows_in, 4)));
+		HIPCHK(ctx, ht->rowids.alloc(m.n_rows_in));
 		ht->device_bytes += ht->rowids.bytes();
 	}
 	std::vector<OwnedCol> &cols = m.kind == KIND_PERFECT ? ht->pcols : ht->payload;
@@ -845,10 +851,10 @@ int polr_ht_alloc_like(polr_ctx *ctx, const void *meta, uint64_t meta_bytes, pol
 	for (uint32_t i = 0; i < m.n_payload; i++) {
 		cols[i].width = m.payload_width[i];
 		cols[i].flags = m.payload_flags[i];
-		HIPCHK(ctx, cols[i].alloc_data(std::max<uint64_t>(rows * cols[i].width, 16)));
+		HIPCHK(ctx, cols[i].alloc_data(rows * cols[i].width));
 		ht->device_bytes += cols[i].own_data.bytes();
 		if (m.payload_has_valid[i]) {
-			HIPCHK(ctx, cols[i].alloc_valid(std::max<uint64_t>(rows, 16)));
+			HIPCHK(ctx, cols[i].alloc_valid(rows));
 			ht->device_bytes += cols[i].own_valid.bytes();
 		}
 		if (m.kind == KIND_PERFECT) {

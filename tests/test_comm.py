@@ -1,10 +1,12 @@
 """polr_bcast_build -- the path's one exchange step (RCCL inside the product library) -- on the one GPU of the test box:
 a communicator of world size 1 exercises id creation, ncclCommInitRank, the metadata / buffer walk and ncclBroadcast
 calls end to end; the receiving side (polr_ht_alloc_like + in-place buffer broadcast) is the same code the N > 1 run
-uses and is covered structurally by tests/test_gpu_edge_cases.py (export -> alloc_like -> identical probes)."""
+uses and is covered by tests/test_gpu_build_routes.py::test_clone (export -> alloc_like -> buffer copies, the source closed,
+every table kind against the numpy reference)."""
 import numpy as np
 import pytest
 
+from buildside import _d2d
 from polr_amd import capi, workloads
 
 
@@ -140,13 +142,6 @@ def test_bcast_build_two_ranks_over_rccl(tmp_path):
         outs.append(json.loads(o.strip().splitlines()[-1]))
     assert outs[0]["counts"] == outs[1]["counts"] and outs[0]["failed"] and outs[1]["failed"]
     assert outs[0]["bytes"] == outs[1]["bytes"] > 0
-
-
-def _d2d(dst, src, n):
-    import ctypes as C
-    hip = C.CDLL("libamdhip64.so")
-    hip.hipMemcpy.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int]
-    assert hip.hipMemcpy(dst, src, n, 3) == 0
 
 
 def test_comm_api_rejects_null_arguments():
