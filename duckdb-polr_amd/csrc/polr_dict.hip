@@ -1,5 +1,5 @@
 // duckdb-polr_amd/csrc/polr_dict.hip -- dictionary encoding of a VARCHAR payload column of a build side
-// (polr_ht_encode_dictionary / polr_ht_fetch_dictionary of include/polr_hip.h).
+// (polr_ht_encode_dictionary[_ex] / polr_ht_fetch_dictionary[_codes] of include/polr_hip.h).
 //
 // A group column that is a payload column of a build side has at most as many distinct values as the build side has rows,
 // and the build side is uploaded once: the strings are hashed and compared ONCE PER BUILD ROW here, at build time, and the
@@ -14,10 +14,27 @@
 //   rank    row r is a first occurrence iff first_row[slot_of_row[r]] == r; an exclusive prefix sum of that flag over the
 //           rows is the first occurrence's code, the total is n_codes;
 //   assign  code[r] = the code of r's slot, NULL rows n_codes.
+//
+// POLR_DICT_SORTED (polr_ht_encode_dictionary_ex): the codes rise with the strings, in the order of polr_strcmp.h.  Once
+// n_codes is known the representative cells are sorted on the device and the first-appearance codes renumbered before the
+// assign step:
+//   keys      per code a 16-byte record {first 8 bytes of the string as a big-endian number, zero-padded; code; length} and
+//             a copy of its cell.  Two records whose keys differ are ordered by the keys (masked big-endian words,
+//             polr_strcmp.h); equal keys with a string of at most 8 bytes among them are ordered by length (the shorter is
+//             a prefix of the other); only then are the cells compared (polr_str_cell_cmp3).
+//   tile sort a workgroup sorts POLR_DICT_SORT_TILE records in LDS with a bitonic network (a last, short tile: the network
+//             of the next power of two).  n_codes <= one tile: this is the whole sort.
+//   merge     ping-pong buffers, every pass doubles the run length.  A workgroup produces one tile of output: it finds its
+//             split of the two input runs by a binary search on the merge diagonal, loads that many records into LDS, and
+//             every thread merges POLR_DICT_SORT_TILE / 256 of them from its own diagonal.  An unpaired last run is copied.
+//   renumber  rank[old code] = sorted position, the representative cells in sorted order; assign writes rank[...].
+// Workgroups meet at kernel boundaries only; every loop is bounded by the tile size, log2(n_codes) or a string's length.
+// Distinct values never compare equal, so the result is unique whatever the network does with the padding records.
 #include <algorithm>
 #include <cstring>
 
 #include "polr_internal.h"
+#include "polr_strcmp.h"
 
 #define POLR_DICT_NO_SLOT 0xFFFFFFFFu
 #define POLR_DICT_BLOCK 256u
@@ -203,13 +220,14 @@ __global__ __launch_bounds__(256) void polr_dict_rank_apply_kernel(DictTable t, 
 	}
 }
 
-// assign: the code column
+// assign: the code column.  rank (sorted codes; NULL: none): the sorted position of every first-appearance code
 __global__ __launch_bounds__(256) void polr_dict_assign_kernel(DictTable t, const uint32_t *__restrict__ slot_of_row, uint64_t n,
-                                                               const uint32_t *__restrict__ scalars, uint32_t *__restrict__ codes) {
+                                                               const uint32_t *__restrict__ scalars, const uint32_t *__restrict__ rank,
+                                                               uint32_t *__restrict__ codes) {
 	const uint32_t n_codes = scalars[DICT_N_CODES];
 	for (uint64_t r = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; r < n; r += (uint64_t)gridDim.x * blockDim.x) {
 		const uint32_t s = slot_of_row[r];
-		codes[r] = s == POLR_DICT_NO_SLOT ? n_codes : t.code[s];
+		codes[r] = s == POLR_DICT_NO_SLOT ? n_codes : (rank ? rank[t.code[s]] : t.code[s]);
 	}
 }
 
@@ -222,14 +240,186 @@ __global__ __launch_bounds__(256) void polr_dict_reps_kernel(const uint4 *__rest
 	}
 }
 
-// the dictionary's strings as records {u32 length, bytes} at the offsets the host laid out
-__global__ __launch_bounds__(256) void polr_dict_records_kernel(const uint4 *__restrict__ reps, const uint64_t *__restrict__ offsets,
-                                                                uint32_t n_codes, uint8_t *__restrict__ arena, uint64_t arena_bytes) {
+// ---- POLR_DICT_SORTED: the sort of the representative cells -----------------------------------------------------------------
+#define POLR_DICT_SORT_TILE 1024u // records a workgroup sorts or merges in LDS: 16 KB of the CU's 160
+#define POLR_DICT_SORT_ITEMS (POLR_DICT_SORT_TILE / POLR_DICT_BLOCK) // records a thread merges
+#define POLR_DICT_PAD 0xFFFFFFFFu // the code of a padding record: behind every string
+static_assert(POLR_DICT_SORT_TILE * 16u <= 32u * 1024u, "a tile is at most 32 KB of LDS");
+static_assert((POLR_DICT_SORT_TILE & (POLR_DICT_SORT_TILE - 1u)) == 0 && POLR_DICT_SORT_TILE % POLR_DICT_BLOCK == 0,
+              "a tile is a power of two and a whole number of records per thread");
+
+struct alignas(16) DictRec {
+	uint64_t key;  // bytes 0-7 of the string as a big-endian number, zero beyond its length
+	uint32_t code; // first-appearance code
+	uint32_t len;
+};
+
+// a < b in the order of polr_strcmp.h.  rep_old: the cell of every first-appearance code
+__device__ __forceinline__ bool dict_rec_less(const DictRec &a, const DictRec &b, const uint4 *__restrict__ rep_old) {
+	if (a.code == POLR_DICT_PAD || b.code == POLR_DICT_PAD) {
+		return a.code != POLR_DICT_PAD;
+	}
+	if (a.key != b.key) {
+		return a.key < b.key;
+	}
+	if (a.len <= 8u || b.len <= 8u) {
+		return a.len < b.len; // (equal keys: the string that ends inside them is a prefix of the other)
+	}
+	const uint4 x = rep_old[a.code], y = rep_old[b.code];
+	return polr_str_cell_cmp3(x.x, x.y, x.z, x.w, y.x, y.y, y.z, y.w) < 0;
+}
+
+// keys: the record and the cell of every first-appearance code.  The one place that reads bytes 4-7 of a long string.
+__global__ __launch_bounds__(256) void polr_dict_sort_keys_kernel(const uint4 *__restrict__ cells, const uint32_t *__restrict__ row_of_code,
+                                                                  uint32_t n_codes, uint4 *__restrict__ rep_old, DictRec *__restrict__ recs) {
 	const uint32_t c = blockIdx.x * blockDim.x + threadIdx.x;
 	if (c >= n_codes) {
 		return;
 	}
-	const uint4 cell = reps[c];
+	const uint4 cell = cells[row_of_code[c]];
+	rep_old[c] = cell;
+	const uint32_t hi = polr_str_bswap(cell.y & polr_str_word_mask(cell.x, 0));
+	uint32_t lo;
+	if (cell.x <= 12u) {
+		lo = polr_str_bswap(cell.z & polr_str_word_mask(cell.x, 1));
+	} else {
+		const POLR_STRCMP_MEM uint8_t *p = (const POLR_STRCMP_MEM uint8_t *)(((uint64_t)cell.w << 32) | cell.z);
+		lo = ((uint32_t)p[4] << 24) | ((uint32_t)p[5] << 16) | ((uint32_t)p[6] << 8) | (uint32_t)p[7];
+	}
+	DictRec r;
+	r.key = ((uint64_t)hi << 32) | lo;
+	r.code = c;
+	r.len = cell.x;
+	recs[c] = r;
+}
+
+// tile sort: records [blockIdx.x * TILE, + TILE) of recs, in place.  A short last tile is padded to the next power of two
+// with records that sort behind every string, and only its own records are written back.
+__global__ __launch_bounds__(256) void polr_dict_sort_tile_kernel(DictRec *recs, uint32_t n_codes, const uint4 *__restrict__ rep_old) {
+	__shared__ DictRec tile[POLR_DICT_SORT_TILE];
+	const uint32_t base = blockIdx.x * POLR_DICT_SORT_TILE;
+	const uint32_t count = min(POLR_DICT_SORT_TILE, n_codes - base);
+	uint32_t m = 2;
+	while (m < count) {
+		m <<= 1;
+	}
+	for (uint32_t i = threadIdx.x; i < m; i += POLR_DICT_BLOCK) {
+		DictRec r;
+		if (i < count) {
+			r = recs[base + i];
+		} else {
+			r.key = ~0ull;
+			r.code = POLR_DICT_PAD;
+			r.len = 0;
+		}
+		tile[i] = r;
+	}
+	__syncthreads();
+	for (uint32_t k = 2; k <= m; k <<= 1) {
+		for (uint32_t j = k >> 1; j; j >>= 1) {
+			for (uint32_t t = threadIdx.x; t < m / 2; t += POLR_DICT_BLOCK) {
+				const uint32_t lo = ((t & ~(j - 1u)) << 1) | (t & (j - 1u)), hi = lo | j;
+				const bool up = (lo & k) == 0;
+				const DictRec a = tile[lo], b = tile[hi];
+				if (dict_rec_less(b, a, rep_old) == up) { // (up: b < a is out of order; down: a <= b is)
+					tile[lo] = b;
+					tile[hi] = a;
+				}
+			}
+			__syncthreads();
+		}
+	}
+	for (uint32_t i = threadIdx.x; i < count; i += POLR_DICT_BLOCK) {
+		recs[base + i] = tile[i];
+	}
+}
+
+// how many of the first d records of the merge of A and B come from A (on a tie A goes first; strings never tie)
+template <class Recs>
+__device__ __forceinline__ uint32_t dict_merge_split(Recs A, uint32_t len_a, Recs B, uint32_t len_b, uint32_t d,
+                                                     const uint4 *__restrict__ rep_old) {
+	uint32_t lo = d > len_b ? d - len_b : 0u, hi = min(d, len_a);
+	while (lo < hi) {
+		const uint32_t mid = (lo + hi) >> 1;
+		if (dict_rec_less(B[d - 1u - mid], A[mid], rep_old)) {
+			hi = mid;
+		} else {
+			lo = mid + 1u;
+		}
+	}
+	return lo;
+}
+
+// merge pass: `in` is sorted in runs of `run` records (a multiple of the tile; the last run may be short), `out` gets runs
+// of 2 x run.  Workgroup b writes out[b * TILE, + TILE): one pair of runs holds it, since 2 x run is a multiple of the tile.
+__global__ __launch_bounds__(256) void polr_dict_sort_merge_kernel(const DictRec *__restrict__ in, DictRec *__restrict__ out, uint32_t n_codes,
+                                                                   uint32_t run, const uint4 *__restrict__ rep_old) {
+	__shared__ DictRec tile[POLR_DICT_SORT_TILE];
+	__shared__ uint32_t split[2];
+	const uint32_t o0 = blockIdx.x * POLR_DICT_SORT_TILE;
+	const uint32_t a_start = o0 - o0 % (2u * run);
+	const uint32_t len_a = min(run, n_codes - a_start);
+	const uint32_t b_start = a_start + len_a;
+	const uint32_t len_b = min(run, n_codes - b_start);
+	const uint32_t d0 = o0 - a_start, d1 = min(d0 + POLR_DICT_SORT_TILE, len_a + len_b);
+	const DictRec *A = in + a_start, *B = in + b_start;
+	if (len_b == 0) { // an unpaired last run
+		for (uint32_t i = d0 + threadIdx.x; i < d1; i += POLR_DICT_BLOCK) {
+			out[a_start + i] = A[i];
+		}
+		return;
+	}
+	if (threadIdx.x == 0 || threadIdx.x == 64) { // (two waves, one diagonal each)
+		split[threadIdx.x >> 6] = dict_merge_split(A, len_a, B, len_b, threadIdx.x ? d1 : d0, rep_old);
+	}
+	__syncthreads();
+	const uint32_t a0 = split[0], b0 = d0 - a0, na = split[1] - a0, count = d1 - d0, nb = count - na;
+	for (uint32_t i = threadIdx.x; i < count; i += POLR_DICT_BLOCK) {
+		tile[i] = i < na ? A[a0 + i] : B[b0 + (i - na)];
+	}
+	__syncthreads();
+	const DictRec *ta = tile, *tb = tile + na;
+	const uint32_t d = min(threadIdx.x * POLR_DICT_SORT_ITEMS, count), dn = min(d + POLR_DICT_SORT_ITEMS, count);
+	uint32_t ai = dict_merge_split(ta, na, tb, nb, d, rep_old), bi = d - ai;
+	for (uint32_t o = d; o < dn; o++) {
+		const bool from_a = bi >= nb || (ai < na && !dict_rec_less(tb[bi], ta[ai], rep_old));
+		out[o0 + o] = from_a ? ta[ai++] : tb[bi++];
+	}
+}
+
+// renumber: the representative cells in sorted order, and the sorted position of every first-appearance code
+__global__ __launch_bounds__(256) void polr_dict_renumber_kernel(const DictRec *__restrict__ sorted, const uint4 *__restrict__ rep_old,
+                                                                 uint32_t n_codes, uint4 *__restrict__ reps, uint32_t *__restrict__ rank) {
+	const uint32_t p = blockIdx.x * blockDim.x + threadIdx.x;
+	if (p >= n_codes) {
+		return;
+	}
+	const uint32_t c = sorted[p].code;
+	if (c < n_codes) { // (a permutation of the codes: always)
+		reps[p] = rep_old[c];
+		rank[c] = p;
+	}
+}
+
+// the length of the string of every listed code (each below n_codes: the host checked)
+__global__ __launch_bounds__(256) void polr_dict_lens_kernel(const uint4 *__restrict__ reps, const uint32_t *__restrict__ codes, uint32_t n,
+                                                             uint32_t *__restrict__ lens) {
+	const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+	if (i < n) {
+		lens[i] = reps[codes[i]].x;
+	}
+}
+
+// the dictionary's strings as records {u32 length, bytes} at the offsets the host laid out: record c is the string of code
+// codes[c] (each below the dictionary's size: the host checked), or of code c where there is no list
+__global__ __launch_bounds__(256) void polr_dict_records_kernel(const uint4 *__restrict__ reps, const uint32_t *__restrict__ codes,
+                                                                const uint64_t *__restrict__ offsets, uint32_t n_records,
+                                                                uint8_t *__restrict__ arena, uint64_t arena_bytes) {
+	const uint32_t c = blockIdx.x * blockDim.x + threadIdx.x;
+	if (c >= n_records) {
+		return;
+	}
+	const uint4 cell = reps[codes ? codes[c] : c];
 	const uint64_t off = offsets[c];
 	if (off > arena_bytes || arena_bytes - off < 4ull + cell.x) {
 		return; // (never past the arena, whatever the offsets say)
@@ -257,11 +447,20 @@ static uint32_t dict_grid(uint64_t n, int n_cus) {
 
 extern "C" int polr_ht_encode_dictionary(polr_ht *ht, uint32_t payload_col, void *stream, uint32_t *code_col, uint32_t *n_codes,
                                          uint32_t *has_null) {
+	return polr_ht_encode_dictionary_ex(ht, payload_col, 0u, stream, code_col, n_codes, has_null);
+}
+
+extern "C" int polr_ht_encode_dictionary_ex(polr_ht *ht, uint32_t payload_col, uint32_t flags, void *stream, uint32_t *code_col,
+                                            uint32_t *n_codes, uint32_t *has_null) {
 	POLR_ENTRY();
 	if (!ht || !code_col || !n_codes || !has_null) {
 		return POLR_E_INVALID;
 	}
 	polr_ctx *ctx = ht->ctx;
+	if (flags & ~(POLR_DICT_SORTED | POLR_DICT_NULL_INVALID)) {
+		POLR_FAIL(ctx, POLR_E_INVALID, "dictionary flags 0x%x: only POLR_DICT_SORTED and POLR_DICT_NULL_INVALID are defined", flags);
+	}
+	const bool sorted = (flags & POLR_DICT_SORTED) != 0;
 	if (ht->kind != KIND_NONE) {
 		// (a finalized perfect table keeps a re-ordered copy of every payload column, and the engines hold the column array)
 		POLR_FAIL(ctx, POLR_E_INVALID, "a payload column is dictionary-encoded before the table is finalized");
@@ -312,6 +511,12 @@ extern "C" int polr_ht_encode_dictionary(polr_ht *ht, uint32_t payload_col, void
 	codes.flags = 0;
 	const uint64_t acct = std::max<uint64_t>(n * 4, 16); // (what polr_ht_export reports for a column)
 	HIPCHK(ctx, codes.alloc_data(acct));
+	if ((flags & POLR_DICT_NULL_INVALID) && src.valid) { // the code column's own copy of the validity array
+		HIPCHK(ctx, codes.alloc_valid(n));
+		if (n) {
+			HIPCHK(ctx, hipMemcpyAsync(codes.valid, src.valid, n, hipMemcpyDeviceToDevice, st));
+		}
+	}
 	hipError_t e = base.alloc(b_rep + b_hash + b_state + b_first + b_code + b_slot + b_roc + b_sums + b_scalars);
 	DictTable t;
 	memset(&t, 0, sizeof(t));
@@ -359,8 +564,10 @@ extern "C" int polr_ht_encode_dictionary(polr_ht *ht, uint32_t payload_col, void
 		polr_launch_scan_blocksums(st, block_sums, n_blocks, &scalars[DICT_N_CODES]);
 		hipLaunchKernelGGL(polr_dict_rank_apply_kernel, dim3(n_blocks), dim3(POLR_DICT_BLOCK), 0, st, t, (const uint32_t *)slot_of_row, n,
 		                   (const uint32_t *)block_sums, row_of_code);
-		hipLaunchKernelGGL(polr_dict_assign_kernel, dim3(dict_grid(n, ctx->n_cus)), dim3(256), 0, st, t, (const uint32_t *)slot_of_row, n,
-		                   (const uint32_t *)scalars, (uint32_t *)codes.data);
+		if (!sorted) {
+			hipLaunchKernelGGL(polr_dict_assign_kernel, dim3(dict_grid(n, ctx->n_cus)), dim3(256), 0, st, t, (const uint32_t *)slot_of_row, n,
+			                   (const uint32_t *)scalars, (const uint32_t *)nullptr, (uint32_t *)codes.data);
+		}
 	}
 	if (e == hipSuccess && !h_long) { // the final count
 		e = hipMemcpyAsync(h_scalars, scalars, sizeof(h_scalars), hipMemcpyDeviceToHost, st);
@@ -372,13 +579,44 @@ extern "C" int polr_ht_encode_dictionary(polr_ht *ht, uint32_t payload_col, void
 	d.n_codes = h_scalars[DICT_N_CODES];
 	d.has_null = h_scalars[DICT_HAS_NULL];
 	const bool ok = e == hipSuccess && !h_long && !h_scalars[DICT_FULL];
+	// sorted codes, two values or more: per distinct value two records (ping and pong), a copy of its cell, its rank
+	const bool sort = ok && sorted && d.n_codes > 1;
+	const uint64_t nc = d.n_codes;
+	DevBuf<uint8_t> sort_mem;
+	const uint32_t *rank = nullptr;
 	if (ok && d.n_codes) {
 		e = d.cells.alloc(d.n_codes);
-		if (e == hipSuccess) {
+		if (e == hipSuccess && sort) {
+			e = sort_mem.alloc(nc * (2 * sizeof(DictRec) + 16 + 4));
+		}
+		if (e == hipSuccess && sort) {
+			DictRec *from = (DictRec *)sort_mem.get(), *to = from + nc;
+			uint4 *rep_old = (uint4 *)(to + nc);
+			uint32_t *rank_of = (uint32_t *)(rep_old + nc);
+			const uint32_t n_tiles = (uint32_t)((nc + POLR_DICT_SORT_TILE - 1) / POLR_DICT_SORT_TILE);
+			hipLaunchKernelGGL(polr_dict_sort_keys_kernel, dim3((d.n_codes + 255) / 256), dim3(256), 0, st, cells,
+			                   (const uint32_t *)row_of_code, d.n_codes, rep_old, from);
+			hipLaunchKernelGGL(polr_dict_sort_tile_kernel, dim3(n_tiles), dim3(POLR_DICT_BLOCK), 0, st, from, d.n_codes,
+			                   (const uint4 *)rep_old);
+			for (uint64_t run = POLR_DICT_SORT_TILE; run < nc; run <<= 1) {
+				hipLaunchKernelGGL(polr_dict_sort_merge_kernel, dim3(n_tiles), dim3(POLR_DICT_BLOCK), 0, st, (const DictRec *)from, to,
+				                   d.n_codes, (uint32_t)run, (const uint4 *)rep_old);
+				std::swap(from, to);
+			}
+			hipLaunchKernelGGL(polr_dict_renumber_kernel, dim3((d.n_codes + 255) / 256), dim3(256), 0, st, (const DictRec *)from,
+			                   (const uint4 *)rep_old, d.n_codes, d.cells.get(), rank_of);
+			rank = rank_of;
+		} else if (e == hipSuccess) {
 			hipLaunchKernelGGL(polr_dict_reps_kernel, dim3((d.n_codes + 255) / 256), dim3(256), 0, st, cells, (const uint32_t *)row_of_code,
 			                   d.n_codes, d.cells.get());
-			e = hipStreamSynchronize(st);
 		}
+	}
+	if (ok && e == hipSuccess && sorted && n) { // (sorted codes are assigned once their ranks are known)
+		hipLaunchKernelGGL(polr_dict_assign_kernel, dim3(dict_grid(n, ctx->n_cus)), dim3(256), 0, st, t, (const uint32_t *)slot_of_row, n,
+		                   (const uint32_t *)scalars, rank, (uint32_t *)codes.data);
+	}
+	if (ok && e == hipSuccess && (d.n_codes || sorted)) {
+		e = hipStreamSynchronize(st);
 	}
 	if (!ok || e != hipSuccess) { // the table is exactly as it was: codes, d.cells and the scratch go with this scope
 		if (e != hipSuccess) {
@@ -392,10 +630,11 @@ extern "C" int polr_ht_encode_dictionary(polr_ht *ht, uint32_t payload_col, void
 		}
 		POLR_FAIL(ctx, POLR_E_HIP, "dictionary encoding failed: the string table filled up");
 	}
-	// from here on an ordinary payload column: 4 bytes, unsigned, no validity array
+	// from here on an ordinary payload column: 4 bytes, unsigned, no validity array but the one POLR_DICT_NULL_INVALID copied
+	const uint64_t valid_bytes = codes.own_valid.bytes();
 	ht->payload.push_back(std::move(codes));
 	ht->n_payload++;
-	ht->device_bytes += acct + (uint64_t)d.n_codes * 16;
+	ht->device_bytes += acct + valid_bytes + (uint64_t)d.n_codes * 16;
 	ht->dicts.push_back(std::move(d));
 	*code_col = d.code_col;
 	*n_codes = d.n_codes;
@@ -446,9 +685,74 @@ extern "C" int polr_ht_fetch_dictionary(polr_ht *ht, uint32_t code_col, void *st
 	HIPCHK(ctx, d_offs.alloc(d->n_codes));
 	HIPCHK(ctx, hipMemcpyAsync(d_offs, offs.data(), (size_t)d->n_codes * 8, hipMemcpyHostToDevice, st));
 	hipLaunchKernelGGL(polr_dict_records_kernel, dim3((d->n_codes + 255) / 256), dim3(256), 0, st, (const uint4 *)d->cells.get(),
-	                   (const uint64_t *)d_offs.get(), d->n_codes, arena.get(), used);
+	                   (const uint32_t *)nullptr, (const uint64_t *)d_offs.get(), d->n_codes, arena.get(), used);
 	HIPCHK(ctx, hipMemcpyAsync(str_bytes, arena, used, hipMemcpyDeviceToHost, st));
 	HIPCHK(ctx, hipStreamSynchronize(st));
 	memcpy(offsets, offs.data(), (size_t)d->n_codes * 8);
+	return POLR_OK;
+}
+
+extern "C" int polr_ht_fetch_dictionary_codes(polr_ht *ht, uint32_t code_col, void *stream, const uint32_t *codes, uint64_t n,
+                                              uint64_t *offsets, uint8_t *str_bytes, uint64_t str_cap, uint64_t *str_used) {
+	POLR_ENTRY();
+	if (!ht || !str_used || (n && (!codes || !offsets)) || (!str_bytes && str_cap)) {
+		return POLR_E_INVALID;
+	}
+	polr_ctx *ctx = ht->ctx;
+	const DictCol *d = nullptr;
+	for (const DictCol &x : ht->dicts) {
+		if (x.code_col == code_col) {
+			d = &x;
+		}
+	}
+	if (!d) {
+		POLR_FAIL(ctx, POLR_E_INVALID, "payload column %u is not a code column whose dictionary this table holds", code_col);
+	}
+	if (n > (1ull << 30)) {
+		POLR_FAIL(ctx, POLR_E_UNSUPPORTED, "a list of %llu codes: at most 2^30 strings are fetched by one call", (unsigned long long)n);
+	}
+	for (uint64_t i = 0; i < n; i++) {
+		if (codes[i] >= d->n_codes) { // (nothing was written, *str_used included)
+			POLR_FAIL(ctx, POLR_E_INVALID, "code %u at position %llu of the list: the dictionary has %u strings (the NULL code is none)",
+			          codes[i], (unsigned long long)i, d->n_codes);
+		}
+	}
+	*str_used = 0;
+	if (n == 0) {
+		return POLR_OK;
+	}
+	HIPCHK(ctx, hipSetDevice(ctx->device));
+	hipStream_t st = polr_stream(ctx, stream);
+	const uint32_t n32 = (uint32_t)n;
+	DevBuf<uint32_t> d_codes, d_lens;
+	HIPCHK(ctx, d_codes.alloc(n));
+	HIPCHK(ctx, d_lens.alloc(n));
+	HIPCHK(ctx, hipMemcpyAsync(d_codes, codes, (size_t)n * 4, hipMemcpyHostToDevice, st));
+	hipLaunchKernelGGL(polr_dict_lens_kernel, dim3((n32 + 255) / 256), dim3(256), 0, st, (const uint4 *)d->cells.get(),
+	                   (const uint32_t *)d_codes.get(), n32, d_lens.get());
+	std::vector<uint32_t> lens(n);
+	HIPCHK(ctx, hipMemcpyAsync(lens.data(), d_lens, (size_t)n * 4, hipMemcpyDeviceToHost, st));
+	HIPCHK(ctx, hipStreamSynchronize(st));
+	std::vector<uint64_t> offs(n);
+	uint64_t used = 0;
+	for (uint64_t i = 0; i < n; i++) {
+		offs[i] = used;
+		used += 4ull + lens[i];
+	}
+	*str_used = used;
+	if (used > str_cap) { // (nothing was written: offsets and str_bytes are as they were)
+		POLR_FAIL(ctx, POLR_E_OVERFLOW, "the %llu listed strings take %llu bytes, the caller made room for %llu", (unsigned long long)n,
+		          (unsigned long long)used, (unsigned long long)str_cap);
+	}
+	DevBuf<uint8_t> arena;
+	DevBuf<uint64_t> d_offs;
+	HIPCHK(ctx, arena.alloc(used));
+	HIPCHK(ctx, d_offs.alloc(n));
+	HIPCHK(ctx, hipMemcpyAsync(d_offs, offs.data(), (size_t)n * 8, hipMemcpyHostToDevice, st));
+	hipLaunchKernelGGL(polr_dict_records_kernel, dim3((n32 + 255) / 256), dim3(256), 0, st, (const uint4 *)d->cells.get(),
+	                   (const uint32_t *)d_codes.get(), (const uint64_t *)d_offs.get(), n32, arena.get(), used);
+	HIPCHK(ctx, hipMemcpyAsync(str_bytes, arena, used, hipMemcpyDeviceToHost, st));
+	HIPCHK(ctx, hipStreamSynchronize(st));
+	memcpy(offsets, offs.data(), (size_t)n * 8);
 	return POLR_OK;
 }

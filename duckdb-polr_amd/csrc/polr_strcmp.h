@@ -1,4 +1,5 @@
-// duckdb-polr_amd/csrc/polr_strcmp.h -- the order of a string_t cell against a constant, defined once for host and device.
+// duckdb-polr_amd/csrc/polr_strcmp.h -- the order of a string_t cell against a constant, and of two cells (polr_str_cell_cmp3,
+// below), defined once for host and device.
 //
 // Reference: StringComparisonOperators / templated_string_compare_op (src/include/duckdb/common/operator/
 // comparison_operators.hpp:157-227): memcmp over the shorter of the two lengths, bytes unsigned; on a tie the shorter
@@ -100,6 +101,49 @@ POLR_STRCMP_HD int polr_str_cmp3(uint32_t len, uint32_t w0, uint32_t w1, uint32_
 	for (uint32_t i = 4; i < n; i++) {
 		const uint32_t x = s[i];
 		const uint32_t y = i < 12u ? (c.w[i >> 2] >> (8u * (i & 3u))) & 0xFFu : (uint32_t)t[i - 12u];
+		if (x != y) {
+			return x < y ? -1 : 1;
+		}
+	}
+	return by_length;
+}
+
+// byte i (4 <= i < len) of a cell's string: an inline cell holds it in w1 / w2, a long one behind its pointer
+POLR_STRCMP_HD uint32_t polr_str_cell_byte(uint32_t len, uint32_t w1, uint32_t w2, uint32_t i) {
+	if (len <= 12u) {
+		return ((i < 8u ? w1 : w2) >> (8u * (i & 3u))) & 0xFFu;
+	}
+	const POLR_STRCMP_MEM uint8_t *s = (const POLR_STRCMP_MEM uint8_t *)(((uint64_t)w2 << 32) | w1);
+	return s[i];
+}
+
+// < 0, 0, > 0: the string of cell a is smaller than, equal to, greater than the string of cell b -- the same order between
+// two cells (the order of the sorted dictionary codes, polr_dict.hip).  A cell = len, w0, w1, w2 as above.  Two inline
+// cells are three masked big-endian words and the lengths, by the argument at the top.  Otherwise word 0 decides where it
+// differs (an inline cell's masked to its own bytes, a long cell's four characters); where it ties, the bytes from 4 up to
+// the shorter length are compared one by one -- from the words of an inline cell, through the pointer of a long one, never
+// past either string -- and then the lengths.
+POLR_STRCMP_HD int polr_str_cell_cmp3(uint32_t alen, uint32_t a0, uint32_t a1, uint32_t a2, uint32_t blen, uint32_t b0,
+                                      uint32_t b1, uint32_t b2) {
+	const int by_length = alen < blen ? -1 : (alen > blen ? 1 : 0);
+	const uint32_t x0 = polr_str_bswap(a0 & polr_str_word_mask(alen, 0)), y0 = polr_str_bswap(b0 & polr_str_word_mask(blen, 0));
+	if (x0 != y0) {
+		return x0 < y0 ? -1 : 1;
+	}
+	if (alen <= 12u && blen <= 12u) {
+		const uint32_t x1 = polr_str_bswap(a1 & polr_str_word_mask(alen, 1)), y1 = polr_str_bswap(b1 & polr_str_word_mask(blen, 1));
+		if (x1 != y1) {
+			return x1 < y1 ? -1 : 1;
+		}
+		const uint32_t x2 = polr_str_bswap(a2 & polr_str_word_mask(alen, 2)), y2 = polr_str_bswap(b2 & polr_str_word_mask(blen, 2));
+		if (x2 != y2) {
+			return x2 < y2 ? -1 : 1;
+		}
+		return by_length;
+	}
+	const uint32_t n = alen < blen ? alen : blen;
+	for (uint32_t i = 4; i < n; i++) {
+		const uint32_t x = polr_str_cell_byte(alen, a1, a2, i), y = polr_str_cell_byte(blen, b1, b2, i);
 		if (x != y) {
 			return x < y ? -1 : 1;
 		}

@@ -40,6 +40,7 @@ EXPORTS = [
     "polr_out_fuse_grouped", "polr_out_fused_result", "polr_out_aggregate_hashed",
     "polr_ht_set_payload_heaps", "polr_pipeline_set_probe_heaps", "polr_out_aggregate_hashed_str", "polr_out_column_width",
     "polr_ht_encode_dictionary", "polr_ht_fetch_dictionary",
+    "polr_ht_encode_dictionary_ex", "polr_ht_fetch_dictionary_codes",
     "polr_out_aggregate_expr", "polr_out_aggregate_grouped_expr", "polr_out_aggregate_hashed_expr",
     "polr_mpx_run_resident_stealing", "polr_mpx_steal_stats",
     "polr_pipeline_scan_filter_str",
@@ -61,6 +62,7 @@ class Col(C.Structure):
 
 
 KEY_BY_VALUE, KEY_NULL_EQUAL = 1, 2  # polr_ht_set_key_flags
+DICT_SORTED, DICT_NULL_INVALID = 1, 2  # polr_ht_encode_dictionary_ex
 
 
 class PoolTuning(C.Structure):
@@ -373,6 +375,8 @@ def load():
     L.polr_out_aggregate_hashed_expr.argtypes = [vp, vp, vp, u32, vp, u32, C.c_uint64, vp, vp, vp, vp, vp, C.c_uint64, vp, vp]
     L.polr_ht_encode_dictionary.argtypes = [vp, u32, vp, P(u32), P(u32), P(u32)]
     L.polr_ht_fetch_dictionary.argtypes = [vp, u32, vp, vp, u64, vp, u64, P(u64)]
+    L.polr_ht_encode_dictionary_ex.argtypes = [vp, u32, u32, vp, P(u32), P(u32), P(u32)]
+    L.polr_ht_fetch_dictionary_codes.argtypes = [vp, u32, vp, vp, u64, vp, vp, u64, P(u64)]
     L.polr_out_fused_result.argtypes = [vp, vp, vp, C.c_uint64, vp]
     L.polr_mpx_run_resident.argtypes = [vp, vp, vp, vp, u32, vp, u32]
     L.polr_mpx_run_resident_ranges.argtypes = [vp, vp, vp, vp, u32, u32, vp, u32]
@@ -544,12 +548,20 @@ class HashTable:
         self.ctx.check(L.polr_ht_set_payload_heaps(self.h, payload_col, _heap_ranges(blocks), len(blocks)))
         return self
 
-    def encode_dictionary(self, payload_col, stream=None):
+    def encode_dictionary(self, payload_col, stream=None, sorted=False, null_invalid=False, flags=None):
         """polr_ht_encode_dictionary (before finalize): VARCHAR payload column `payload_col` -> one more payload column of
-        4-byte codes, 0 .. n_codes - 1 in order of first appearance, NULL rows n_codes -> (code_col, n_codes, has_null)"""
+        4-byte codes, 0 .. n_codes - 1 in order of first appearance, NULL rows n_codes -> (code_col, n_codes, has_null).
+        sorted / null_invalid (polr_ht_encode_dictionary_ex: DICT_SORTED, DICT_NULL_INVALID; `flags`: the word itself): codes
+        that rise with the strings; a validity array for the code column, copied from the source column's"""
         col, n, null = C.c_uint32(), C.c_uint32(), C.c_uint32()
-        self.ctx.check(self.ctx.L.polr_ht_encode_dictionary(self.h, payload_col, stream, C.byref(col), C.byref(n),
-                                                            C.byref(null)))
+        if flags is None:
+            flags = (DICT_SORTED if sorted else 0) | (DICT_NULL_INVALID if null_invalid else 0)
+        if flags:
+            self.ctx.check(self.ctx.L.polr_ht_encode_dictionary_ex(self.h, payload_col, flags, stream, C.byref(col), C.byref(n),
+                                                                   C.byref(null)))
+        else:
+            self.ctx.check(self.ctx.L.polr_ht_encode_dictionary(self.h, payload_col, stream, C.byref(col), C.byref(n),
+                                                                C.byref(null)))
         self.__dict__.setdefault("_n_codes", {})[col.value] = n.value  # (dictionary() sizes its offsets by it)
         return col.value, n.value, null.value
 
@@ -572,6 +584,29 @@ class HashTable:
         raw = arena.tobytes()
         out = []
         for at in offs[:n_codes].tolist():
+            ln = int.from_bytes(raw[at:at + 4], "little")
+            out.append(raw[at + 4:at + 4 + ln])
+        return out
+
+    def dictionary_strings(self, code_col, codes, str_cap=4096, stream=None):
+        """polr_ht_fetch_dictionary_codes: the strings of the listed codes of code column `code_col`, [bytes] in list order
+        (duplicates included); one retry with the exact size when str_cap was too small"""
+        codes = np.ascontiguousarray(codes, dtype=np.uint32)
+        n = len(codes)
+        used = C.c_uint64()
+        for attempt in (0, 1):
+            offs = np.zeros((max(n, 1),), dtype=np.uint64)
+            arena = np.zeros((max(str_cap, 1),), dtype=np.uint8)
+            rc = self.ctx.L.polr_ht_fetch_dictionary_codes(self.h, code_col, stream, codes.ctypes.data, n, offs.ctypes.data,
+                                                           arena.ctypes.data, str_cap, C.byref(used))
+            if rc == E_OVERFLOW and attempt == 0 and used.value > str_cap:
+                str_cap = used.value
+                continue
+            self.ctx.check(rc)
+            break
+        raw = arena.tobytes()
+        out = []
+        for at in offs[:n].tolist():
             ln = int.from_bytes(raw[at:at + 4], "little")
             out.append(raw[at + 4:at + 4 + ln])
         return out
@@ -1312,8 +1347,13 @@ def build_joins(ctx, wl, auto=False):
         # each, behind all the others; dictionary_payload_index gives its column number and (n_codes, has_null))
         if j.get("dictionary"):
             j["dictionary_cols"] = {}
+            # j["dictionary_flags"] = {name: DICT_SORTED | DICT_NULL_INVALID}: the flags of polr_ht_encode_dictionary_ex
             for col in j["dictionary"]:
-                code_col, n_codes, has_null = ht.encode_dictionary(string_payload_index(j, col))
+                flags = (j.get("dictionary_flags") or {}).get(col, 0)
+                if flags:
+                    code_col, n_codes, has_null = ht.encode_dictionary(string_payload_index(j, col), flags=flags)
+                else:
+                    code_col, n_codes, has_null = ht.encode_dictionary(string_payload_index(j, col))
                 j["dictionary_cols"][col] = (code_col, (n_codes, has_null))
         # j["key_flags"]: per key column KEY_BY_VALUE (the probe side reads another integer type: a CAST'ed key) and / or
         # KEY_NULL_EQUAL (IS NOT DISTINCT FROM)

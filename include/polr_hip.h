@@ -645,11 +645,44 @@ int polr_pipeline_set_probe_heap(polr_pipeline *p, uint32_t probe_col, const voi
  * *str_used exact and offsets / str_bytes untouched -- one retry with *str_used succeeds.  POLR_E_INVALID for a column that
  * is not a code column of this table, a table that was never encoded, and a table made by polr_ht_alloc_like / received
  * by polr_bcast_build (they carry the codes, not the strings: the rank that built the table holds the dictionary).
- * Not provided: sorted (lexicographic) codes; dictionaries of probe-side columns. */
+ *
+ * polr_ht_encode_dictionary_ex is the same call with `flags`; flags = 0 IS polr_ht_encode_dictionary, bit for bit, and a
+ * column encoded by either call is "encoded already" for both.  A bit other than the two below: POLR_E_INVALID, table
+ * untouched.  Refusals, atomicity and the stream rule are those above.
+ *  - POLR_DICT_SORTED: the code of a value is the number of distinct non-NULL values of the column that are SMALLER than it
+ *    (bytes compared as unsigned, a proper prefix first: the order of polr_out_aggregate_string and of the reference's
+ *    string comparison) -- 0 .. *n_codes - 1 ascending with the strings, whatever the order of the build rows, the padding
+ *    of inline cells or the heap addresses.  NULL rows still get *n_codes, the largest code.  polr_ht_fetch_dictionary then
+ *    returns the strings in ascending order.  What it buys: a result of polr_out_aggregate_grouped / polr_out_fuse_grouped
+ *    read in index order is in ORDER BY order of the group columns (NULL last), and MIN / MAX of the column -- per group or
+ *    over all rows -- is the integer MIN / MAX of its code column in any sink, one 4-byte read per tuple, and one look-up
+ *    per result (polr_ht_fetch_dictionary_codes).  The representative cells are sorted on the device (LDS bitonic tiles of
+ *    1024 values, then merge passes; nothing but the counts goes to the host); while the call runs the sort holds 52 more
+ *    bytes of scratch per DISTINCT value (two 16-byte records, a copy of the cell, the rank), freed before it returns.
+ *    *n_codes <= 1 sorts nothing.
+ *  - POLR_DICT_NULL_INVALID: when the source column has a validity array the code column gets a device copy of it (counted
+ *    in device_bytes), which travels through finalize, polr_ht_export / polr_ht_alloc_like and polr_bcast_build like any
+ *    payload validity.  The cell of a NULL row is still *n_codes (polr_out_materialize reports it as it reports every NULL
+ *    cell: validity 0, data 0), but COUNT(col) / MIN / MAX over the code column follow
+ *    SQL (NULLs take no part), the perfect-hash sink counts NULL-key rows in *n_dropped as for any NULL group key, and the
+ *    hashed sink makes NULL a group of its own.  Without the flag, or for a source column without validity: no validity
+ *    array, as above.
+ * polr_ht_fetch_dictionary_codes returns the records {uint32 length, bytes} of the `n` listed codes, in list order, instead
+ * of the whole dictionary: offsets[i] = byte offset of the record of codes[i], duplicates get a record each, *str_used =
+ * the bytes the records take.  n = 0: POLR_OK, *str_used = 0.  A listed code >= n_codes (the NULL code is not a string):
+ * POLR_E_INVALID, nothing written.  str_cap < *str_used: POLR_E_OVERFLOW with *str_used exact and offsets / str_bytes
+ * untouched -- one retry succeeds.  POLR_E_INVALID for the same tables as polr_ht_fetch_dictionary.
+ * Not provided: dictionaries of probe-side columns. */
+#define POLR_DICT_SORTED       1u
+#define POLR_DICT_NULL_INVALID 2u
 int polr_ht_encode_dictionary(polr_ht *ht, uint32_t payload_col, void *stream, uint32_t *code_col, uint32_t *n_codes,
                               uint32_t *has_null);
+int polr_ht_encode_dictionary_ex(polr_ht *ht, uint32_t payload_col, uint32_t flags, void *stream, uint32_t *code_col,
+                                 uint32_t *n_codes, uint32_t *has_null);
 int polr_ht_fetch_dictionary(polr_ht *ht, uint32_t code_col, void *stream, uint64_t *offsets, uint64_t n_offsets,
                              uint8_t *str_bytes, uint64_t str_cap, uint64_t *str_used);
+int polr_ht_fetch_dictionary_codes(polr_ht *ht, uint32_t code_col, void *stream, const uint32_t *codes, uint64_t n,
+                                   uint64_t *offsets, uint8_t *str_bytes, uint64_t str_cap, uint64_t *str_used);
 /* MIN / MAX (fn = POLR_AGG_MIN / POLR_AGG_MAX) of a VARCHAR column over the pipeline's output rows, reduced on the
  * device (src/function/aggregate/distributive/minmax.cpp over string_t: bytes compared as unsigned, a proper prefix
  * sorts first; NULLs take no part).  The winning string's bytes go to dst (at most dst_cap of them), *len = its whole
