@@ -1244,6 +1244,12 @@ int polr_out_reset(polr_out *o, void *stream) {
 		                           (size_t)o->fused_tables * o->fused_groups * (1u + 2u * o->fused_aggs) * 8u, st));
 		HIPCHK(ctx, hipMemsetAsync(o->fused_dropped, 0, 8, st));
 	}
+	// (runs that write this output on another stream wait for these memsets: out_order_behind_reset)
+	if (!o->reset_event) {
+		HIPCHK(ctx, hipEventCreateWithFlags(&o->reset_event, hipEventDisableTiming));
+	}
+	HIPCHK(ctx, hipEventRecord(o->reset_event, st));
+	o->reset_stream = st;
 	o->stats_valid = false;
 	return POLR_OK;
 }
@@ -1362,6 +1368,9 @@ void polr_out_destroy(polr_out *o) {
 	}
 	hipSetDevice(o->ctx->device);
 	polr_ctx *ctx_ = o->ctx;
+	if (o->reset_event) {
+		hipEventDestroy(o->reset_event);
+	}
 	delete o;
 	polr_ctx_release(ctx_);
 }
@@ -1494,6 +1503,7 @@ int polr_probe_rounds_async(polr_pipeline *p, void *stream, const polr_round *ro
 	if (out) {
 		dout = out->dev;
 		out->stats_valid = false;
+		HIPCHK(ctx, out_order_behind_reset(out, st));
 	}
 	const DevPipeline &dp = materialize ? p->host_mat : p->host_count;
 	hipError_t e = polr_launch_path_kernel(dp.W, dp.k, n_blocks, wpb, st, materialize ? p->dev_mat : p->dev_count,

@@ -164,6 +164,10 @@ struct polr_out {
 	uint64_t n_rows = 0;
 	uint32_t n_chunks = 0;
 	bool stats_valid = false;
+	// polr_out_reset only enqueues its memsets: a run that writes this output on ANOTHER stream is ordered behind them
+	// by this event (out_order_behind_reset); reset_stream: where the last reset was enqueued
+	hipEvent_t reset_event = nullptr;
+	hipStream_t reset_stream = nullptr;
 	// a fused GROUP BY sink (polr_out_fuse_grouped): the device descriptor, its cell tables, and what the result needs
 	DevBuf<FusedSink> fused_dev;
 	DevBuf<unsigned long long> fused_cells, fused_dropped;
@@ -224,6 +228,15 @@ static inline DevCol dev_col(const OwnedCol &c) {
 	d.width = c.width;
 	d.flags = c.flags;
 	return d;
+}
+
+// a run on stream `st` is about to write output `o`: the last polr_out_reset, if it was enqueued on another stream, comes
+// first (without this the reset could land behind the run and wipe the cursor: counters right, no rows)
+static inline hipError_t out_order_behind_reset(polr_out *o, hipStream_t st) {
+	if (!o || !o->reset_event || o->reset_stream == st) {
+		return hipSuccess;
+	}
+	return hipStreamWaitEvent(st, o->reset_event, 0);
 }
 
 // the statistics every reader of an output needs (chunk count, prefix): computed once after a run

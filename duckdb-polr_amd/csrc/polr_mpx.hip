@@ -504,6 +504,7 @@ static int run_begin(RunState &rs, polr_mpx *m, void *stream, uint64_t chunk_beg
 	if (out) {
 		rs.dout = out->dev;
 		out->stats_valid = false;
+		HIPCHK(ctx, out_order_behind_reset(out, st));
 	}
 	const DevPipeline &dp = materialize ? p->host_mat : p->host_count;
 	rs.dpd = materialize ? p->dev_mat : p->dev_count;
@@ -911,6 +912,7 @@ static int enqueue_run(polr_mpx **ms, hipStream_t st, uint32_t n, const Resident
 	if (rq.out) {
 		dout = rq.out->dev;
 		rq.out->stats_valid = false;
+		HIPCHK(ctx, out_order_behind_reset(rq.out, st));
 	}
 	// order this launch behind the pool launches of other streams it must not share the device with
 	int rc = order_pool_launch(ctx, st, share);
@@ -969,6 +971,47 @@ static int run_resident_impl(polr_mpx **ms, void *stream, uint32_t n, const Resi
 		return rc;
 	}
 	return enqueue_run(ms, st, n, rq, sh, pl, share, fill_descriptors(ms, n, rq, pl));
+}
+
+// what run_resident_impl would plan for (ms, n, out, flags), through the same calls; nothing is launched or changed
+int polr_mpx_pool_info(polr_mpx **ms, uint32_t n, polr_out *out, uint32_t flags, polr_pool_info *info) {
+	POLR_ENTRY();
+	if (!ms || n == 0 || !ms[0] || !info) {
+		return POLR_E_INVALID;
+	}
+	polr_pipeline *p = ms[0]->pipe;
+	polr_ctx *ctx = p->ctx;
+	if (n > 4096) {
+		POLR_FAIL(ctx, POLR_E_UNSUPPORTED, "at most 4096 executors per run");
+	}
+	if (out && out->pipe != p) {
+		POLR_FAIL(ctx, POLR_E_INVALID, "output object belongs to another pipeline");
+	}
+	for (uint32_t i = 0; i < n; i++) {
+		if (!ms[i] || ms[i]->pipe != p) {
+			return POLR_E_INVALID;
+		}
+	}
+	HIPCHK(ctx, hipSetDevice(ctx->device));
+	const PoolShape sh = pool_shape(p, out != nullptr, out);
+	uint32_t share;
+	PoolPlan pl;
+	const int rc = plan_run(ctx, sh, n, p->n_tuples, flags, &share, &pl);
+	if (rc) {
+		return rc;
+	}
+	memset(info, 0, sizeof(*info));
+	info->n_blocks = pl.n_blocks;
+	info->pool_waves = pl.pool_waves;
+	info->n_rings = pl.n_rings;
+	info->mixed = pl.mixed ? 1u : 0u;
+	info->share = share;
+	info->units_x = pl.units_x;
+	info->hi_unit = pl.hi_unit;
+	info->hi_tuples = pl.hi_tuples;
+	info->gran = sh.flat ? POLR_POOL_GRAN_FLAT : POLR_POOL_GRAN_GENERIC;
+	info->flat = sh.flat ? 1u : 0u;
+	return POLR_OK;
 }
 
 int polr_mpx_run_resident_ranges(polr_mpx **ms, void *stream, const uint64_t *range_begin, const uint64_t *range_end,

@@ -28,6 +28,8 @@
 #include "polr_pool_common.h"
 #include "polr_flat_device.h"
 
+static_assert(FLAT_STEP0 == POLR_POOL_GRAN_FLAT && FLAT_UNIT_MAX == POLR_POOL_UNIT_MAX, "the plan's unit sizes are the kernel's");
+
 #define PASTE_TL2(a, b) a##b
 #define PASTE_TL(a, b) PASTE_TL2(a, b)
 #if !POLR_FLAT_EMIT

@@ -182,22 +182,17 @@ struct PoolRoundOut {
 __device__ __forceinline__ void polr_pool_size_units(uint64_t tuples64, uint32_t pool_waves, uint32_t n_exec, uint32_t gran,
                                                      uint32_t hi_tuples, uint32_t units_x, uint32_t hi_unit, bool terminal,
                                                      PoolRoundOut &r) {
-	// (32-bit arithmetic: a round is at most 2^32 - 1 tuples, and the device has no integer divider -- a 64-bit
-	// division is a ~150-instruction sequence on the router's single lane; gran is a power of two)
+	// (the arithmetic: polr_pool_plan.h -- plain code a host program checks against known answers; this is
+	// polr_pool_unit_size with the round's queue picked in the same branches)
 	const uint32_t tuples = (uint32_t)tuples64;
 	if (tuples <= hi_tuples) {
 		r.cls = 0;
 		r.unit = hi_unit;
 	} else {
 		r.cls = terminal ? 2u : 1u;
-		uint32_t target = units_x * pool_waves / (n_exec ? n_exec : 1u);
-		target = target < 16u ? 16u : target;
-		uint32_t us = tuples / target + (tuples % target ? 1u : 0u);
-		us = (us + gran - 1u) & ~(gran - 1u);
-		// (never more than 65 536 tuples: the flat pipeline queues 16-bit positions inside the unit)
-		r.unit = us < gran ? gran : (us > 65536u ? 65536u : us);
+		r.unit = polr_pool_big_unit(tuples, pool_waves, n_exec, gran, units_x);
 	}
-	r.n_units = tuples / r.unit + (tuples % r.unit ? 1u : 0u);
+	r.n_units = polr_pool_units_of(tuples, r.unit);
 }
 
 // sum of the 8 arrival shards of a slot (full wave; the same value in every lane)

@@ -15,6 +15,42 @@
 #define POLR_POOL_HI_TUPLES 4096u // rounds up to this many tuples are latency-critical (exploration slices)
 #define POLR_POOL_HI_UNIT 64u // smallest unit of a small round (ring capacities are sized for it)
 
+#define POLR_POOL_GRAN_FLAT 512u   // units of a big round are multiples of this many tuples: the flat kernel (a stage-0 step),
+#define POLR_POOL_GRAN_GENERIC 64u // the generic kernel (one tuple per lane)
+#define POLR_POOL_UNIT_MAX 65536u // most tuples per unit of a big round (the flat pipeline queues 16-bit unit positions)
+
+// host and device: the qualifier is empty under a plain host compiler
+#if defined(__HIPCC__) || defined(__CUDACC__)
+#define POLR_PLAN_HD __host__ __device__ __forceinline__
+#else
+#define POLR_PLAN_HD static inline
+#endif
+
+// How a round of `tuples` tuples is cut into units (the routers: polr_pool_size_units, polr_pool_device.h).  A small
+// round (<= hi_tuples) is cut into units of hi_unit tuples; a big one so that the executors still routing (`active`)
+// each give every probe wave of their share of the pool about units_x units: ceil(tuples / target) tuples with
+// target = max(16, units_x * pool_waves / active), rounded up to a multiple of `gran` (a power of two: 512 flat, 64
+// generic), at most POLR_POOL_UNIT_MAX.
+// (32-bit arithmetic: a round is at most 2^32 - 1 tuples, and the device has no integer divider -- a 64-bit division
+// is a ~150-instruction sequence on the router's single lane)
+// (Two expressions and their composition: the routers call the expressions from the branches in which they also pick
+// the round's queue, which leaves their code as it was when the arithmetic stood there.)
+POLR_PLAN_HD uint32_t polr_pool_big_unit(uint32_t tuples, uint32_t pool_waves, uint32_t active, uint32_t gran, uint32_t units_x) {
+	uint32_t target = units_x * pool_waves / (active ? active : 1u);
+	target = target < 16u ? 16u : target;
+	uint32_t us = tuples / target + (tuples % target ? 1u : 0u);
+	us = (us + gran - 1u) & ~(gran - 1u);
+	return us < gran ? gran : (us > POLR_POOL_UNIT_MAX ? POLR_POOL_UNIT_MAX : us);
+}
+POLR_PLAN_HD uint32_t polr_pool_units_of(uint32_t tuples, uint32_t unit) {
+	return tuples / unit + (tuples % unit ? 1u : 0u);
+}
+POLR_PLAN_HD void polr_pool_unit_size(uint32_t tuples, uint32_t pool_waves, uint32_t active, uint32_t gran, uint32_t hi_tuples,
+                                      uint32_t units_x, uint32_t hi_unit, uint32_t *unit, uint32_t *n_units) {
+	*unit = tuples <= hi_tuples ? hi_unit : polr_pool_big_unit(tuples, pool_waves, active, gran, units_x);
+	*n_units = polr_pool_units_of(tuples, *unit);
+}
+
 static inline uint32_t next_pow2_u32(uint64_t v) {
 	uint32_t p = 1;
 	while (p < v) {

@@ -67,7 +67,7 @@ __global__ __launch_bounds__(64 * POOLG_WAVES, 4) void polr_pool_gen_kernel(cons
 	pool_load_run(run, rh);
 	if (blockIdx.x < rh.n_router_blocks) {
 		// (units of big rounds: multiples of 64 tuples; router wave r uses the LDS of probe wave r)
-		pool_router_wave(execs, run, rh, blockIdx.x * (blockDim.x >> 6) + wave_in_block, k, 64,
+		pool_router_wave(execs, run, rh, blockIdx.x * (blockDim.x >> 6) + wave_in_block, k, POLR_POOL_GRAN_GENERIC,
 		                 lds + (size_t)wave_in_block * lds_per_wave, lds_per_wave);
 		return;
 	}

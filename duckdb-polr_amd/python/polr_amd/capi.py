@@ -47,6 +47,7 @@ EXPORTS = [
     "polr_pipeline_scan_filter_expr",
     "polr_device_bytes_live",
     "polr_out_materialize_strings",
+    "polr_mpx_pool_info",
 ]
 
 
@@ -233,6 +234,12 @@ class LaunchInfo(C.Structure):
                                           "compiled_stages", "tuple_slots", "n_cus", "flat", "lds_tables", "lds_table_bytes", "pad")]
 
 
+class PoolInfo(C.Structure):
+    """polr_pool_info"""
+    _fields_ = [(n, C.c_uint32) for n in ("n_blocks", "pool_waves", "n_rings", "mixed", "share", "units_x", "hi_unit",
+                                          "hi_tuples", "gran", "flat")]
+
+
 class GroupKey(C.Structure):
     _fields_ = [("src_join", C.c_int32), ("src_col", C.c_uint32), ("min_value", C.c_int64), ("n_values", C.c_uint32),
                 ("pad", C.c_uint32)]
@@ -379,6 +386,7 @@ def load():
     L.polr_ht_fetch_dictionary_codes.argtypes = [vp, u32, vp, vp, u64, vp, vp, u64, P(u64)]
     L.polr_out_fused_result.argtypes = [vp, vp, vp, C.c_uint64, vp]
     L.polr_mpx_run_resident.argtypes = [vp, vp, vp, vp, u32, vp, u32]
+    L.polr_mpx_pool_info.argtypes = [vp, u32, vp, u32, P(PoolInfo)]
     L.polr_mpx_run_resident_ranges.argtypes = [vp, vp, vp, vp, u32, u32, vp, u32]
     L.polr_mpx_run_resident_morsels.argtypes = [vp, vp, C.c_uint64, C.c_uint64, u32, u32, vp, u32]
     L.polr_mpx_run_resident_stealing.argtypes = [vp, vp, vp, vp, u32, u32, vp, u32]
@@ -1202,6 +1210,16 @@ def run_resident(mpxs, ranges, out=None, reset=False, finish=False, share=1, str
     e = np.ascontiguousarray([r[1] for r in ranges], dtype=np.uint64)
     ctx.check(ctx.L.polr_mpx_run_resident(hs, stream, b.ctypes.data, e.ctypes.data, n, out.h if out else None,
                                           _run_flags(reset, finish, share)))
+
+
+def pool_info(mpxs, out=None, share=1):
+    """polr_mpx_pool_info: what run_resident*(mpxs, .., out=out, share=share) would plan under the context's tuning (grid,
+    probe waves, the numbers that cut a round into units); launches nothing"""
+    ctx = mpxs[0].ctx
+    i = PoolInfo()
+    ctx.check(ctx.L.polr_mpx_pool_info(_handles(mpxs), len(mpxs), out.h if out else None, _run_flags(False, False, share),
+                                       C.byref(i)))
+    return {f[0]: getattr(i, f[0]) for f in PoolInfo._fields_}
 
 
 def run_resident_ranges(mpxs, range_lists, out=None, reset=False, finish=False, share=1):

@@ -406,6 +406,8 @@ void polr_pipeline_destroy(polr_pipeline *p);
 /* max_chunks must cover outputs/chunk_capacity plus one partially filled chunk per emitting wave (at most the
  * resident waves of the device, <= 8192); too small -> POLR_E_OVERFLOW with exact counters, retry larger. */
 int polr_out_create(polr_pipeline *p, uint32_t chunk_capacity, uint64_t max_chunks, polr_out **out);
+/* Asynchronous on `stream`.  A run that is given this output afterwards is ordered behind the reset on whatever stream
+ * it runs (a run on the same stream by the stream, another by an event): a reset never lands behind the run it precedes. */
 int polr_out_reset(polr_out *o, void *stream);
 int polr_out_stats(polr_out *o, void *stream, uint64_t *n_rows, uint64_t *n_chunks, uint32_t *overflowed);
 /* compacted ids to the host: dst[n_rows][1+k] (slot-major per row) */
@@ -776,6 +778,22 @@ int polr_mpx_run_many(polr_mpx **ms, void **streams, const uint64_t *chunk_begin
 #define POLR_RUN_SHARE(d) (((uint32_t)(d) & 0xFFu) << 8)
 int polr_mpx_run_resident(polr_mpx **ms, void *stream, const uint64_t *chunk_begin, const uint64_t *chunk_end,
                           uint32_t n, polr_out *out, uint32_t flags);
+/* What polr_mpx_run_resident*(ms, .., n, out, flags) would plan for its launch under the context's tuning, by the same
+ * steps (diagnostic; launches nothing, changes nothing): the grid, the probe waves, and the numbers that cut a round
+ * into units -- a round of more than hi_tuples tuples is cut into units of ceil(tuples / target) tuples, target =
+ * max(16, units_x * pool_waves / executors still routing), rounded up to a multiple of gran, at most 65 536; a smaller
+ * round into units of hi_unit tuples.  Refuses what the run would refuse (POLR_E_INVALID / POLR_E_UNSUPPORTED). */
+typedef struct polr_pool_info {
+	uint32_t n_blocks;   /* workgroups of the launch */
+	uint32_t pool_waves; /* probe waves */
+	uint32_t n_rings;    /* unit rings in use */
+	uint32_t mixed;      /* 1: the routers sit in the probe workgroups' first waves */
+	uint32_t share;      /* the launch is sized for 1 / share of the device */
+	uint32_t units_x, hi_unit, hi_tuples;
+	uint32_t gran;       /* 512: the flat pipeline's kernel, 64: the generic one */
+	uint32_t flat;
+} polr_pool_info;
+int polr_mpx_pool_info(polr_mpx **ms, uint32_t n, polr_out *out, uint32_t flags, polr_pool_info *info);
 /* The same with a LIST of chunk ranges per executor (range_begin / range_end: [n][ranges_per_executor], 1..8): executor i
  * routes its ranges one after the other with one multiplexer state -- a worker thread that was handed several morsels
  * up front.  Pairing a range from every part of a skewed table per executor evens out what the executors have to do

@@ -1,7 +1,8 @@
 // tests/poolplan/pool_plan_main.cpp -- the pool launch plan (duckdb-polr_amd/csrc/polr_pool_plan.h) as a stand-alone host
 // program: known answers, worked out from the formulas as they stood inside run_resident_impl before the plan became a
-// function of its own, and the invariants the device code relies on over a sweep of shapes.  Prints one line per
-// check group and "ok"; any mismatch is printed and makes the exit status 1.
+// function of its own, the invariants the device code relies on over a sweep of shapes, and how a round is cut into
+// units (known answers and a fixed table of input -> unit lines).  Prints one line per check group, the table and "ok";
+// any mismatch is printed and makes the exit status 1.
 #include <stdio.h>
 #include <string.h>
 
@@ -190,10 +191,82 @@ static void invariants() {
 	printf("invariants: %u plans, %u refused\n", plans, refused);
 }
 
+// how a round is cut into units (polr_pool_unit_size, the arithmetic of the routers' polr_pool_size_units), worked out
+// by hand from the rule: <= hi_tuples: hi_unit; else ceil(tuples / max(16, units_x * pool_waves / active)) rounded up
+// to gran, at most 65 536
+struct UnitKnown {
+	uint32_t tuples, pool_waves, active, gran, hi_tuples, units_x, hi_unit, unit, n_units;
+};
+
+static const UnitKnown UNIT_KNOWN[] = {
+    // the 4096 boundary
+    {4096, 4095, 1, 512, 4096, 4, 1024, 1024, 4},
+    {4097, 4095, 1, 512, 4096, 4, 1024, 512, 9},
+    {4097, 4095, 1, 64, 4096, 4, 64, 64, 65},
+    {1000, 255, 1, 64, 4096, 4, 64, 64, 16},
+    // ... moved by hi_tuples
+    {1024, 255, 1, 512, 1024, 1, 320, 320, 4},
+    {1025, 255, 1, 512, 1024, 1, 320, 512, 3},
+    {0, 255, 1, 512, 0, 1, 1024, 1024, 0},
+    {1, 255, 1, 512, 0, 1, 1024, 512, 1},
+    // the floor of 16 on target: few probe waves, or many executors
+    {100000, 8, 1, 64, 4096, 1, 64, 6272, 16},
+    {100000, 255, 64, 512, 4096, 4, 1024, 6656, 16},
+    // rounding up to gran 64 and gran 512
+    {600000, 255, 1, 64, 4096, 1, 64, 2368, 254},
+    {600000, 255, 1, 512, 4096, 1, 1024, 2560, 235},
+    {652800, 255, 1, 512, 4096, 1, 1024, 2560, 255}, // (255 x 2560: the most tuples that still give units of 2560)
+    {652801, 255, 1, 512, 4096, 1, 1024, 3072, 213},
+    {652500, 255, 1, 64, 4096, 1, 64, 2560, 255},
+    // the cap
+    {16711680, 255, 1, 512, 4096, 1, 1024, 65536, 255}, // (255 x 65 536)
+    {16781680, 255, 1, 512, 4096, 1, 1024, 65536, 257},
+    {16781680, 255, 1, 64, 4096, 1, 64, 65536, 257},
+    {4000000000u, 4095, 1, 512, 4096, 4, 1024, 65536, 61036},
+    // several executors still routing (none: as one)
+    {200000, 4095, 16, 512, 4096, 4, 1024, 512, 391},
+    {200000, 2040, 8, 64, 4096, 4, 64, 256, 782},
+    {200000, 255, 0, 512, 4096, 1, 1024, 1024, 196},
+};
+
+static void unit_answers() {
+	uint32_t rows = 0;
+	for (const UnitKnown &k : UNIT_KNOWN) {
+		uint32_t unit = 0, n_units = 0;
+		polr_pool_unit_size(k.tuples, k.pool_waves, k.active, k.gran, k.hi_tuples, k.units_x, k.hi_unit, &unit, &n_units);
+		CHECK(unit == k.unit && n_units == k.n_units, "unit row %u: %u x %u, want %u x %u", rows, n_units, unit, k.n_units, k.unit);
+		rows++;
+	}
+	printf("unit answers: %u rows\n", rows);
+	// a fixed table, input -> unit: what tests/poolunits.py (the restatement the GPU tests size their sources with) is
+	// held against, line by line
+	static const uint32_t TUPLES[] = {0,      1,      4095,    4096,     4097,     20000,     130560,    200000,
+	                                  652500, 652800, 652801,  1048576,  16711680, 16781680,  4294967295u};
+	static const uint32_t WAVES[] = {2, 124, 255, 4095}, ACTIVE[] = {1, 3, 8}, GRAN[] = {64, 512}, UNITS_X[] = {1, 4};
+	static const uint32_t HI[][2] = {{4096, 1024}, {4096, 64}, {1024, 320}, {0, 1024}}; // {hi_tuples, hi_unit}
+	uint32_t lines = 0;
+	for (uint32_t t : TUPLES)
+	for (uint32_t w : WAVES)
+	for (uint32_t a : ACTIVE)
+	for (uint32_t g : GRAN)
+	for (uint32_t x : UNITS_X)
+	for (const uint32_t (&h)[2] : HI) {
+		uint32_t unit = 0, n_units = 0;
+		polr_pool_unit_size(t, w, a, g, h[0], x, h[1], &unit, &n_units);
+		CHECK(unit >= 64 && unit <= POLR_POOL_UNIT_MAX && (uint64_t)unit * n_units >= t &&
+		          (n_units == 0 || (uint64_t)unit * (n_units - 1) < t),
+		      "units %u x %u do not cover %u tuples", n_units, unit, t);
+		printf("unit %u %u %u %u %u %u %u -> %u %u\n", t, w, a, g, h[0], x, h[1], unit, n_units);
+		lines++;
+	}
+	printf("unit table: %u lines\n", lines);
+}
+
 int main() {
 	known_answers();
 	tuning_answers();
 	invariants();
+	unit_answers();
 	if (failures) {
 		printf("%d check(s) failed\n", failures);
 		return 1;

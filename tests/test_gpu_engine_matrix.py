@@ -20,6 +20,9 @@ Every pipeline asserts `launch_info(materialize)["flat"]`, so each case records 
                    test_flat_k6_against_k7 (k = 7),      (emitting), test_wrap_around_        1/2/8-byte unique],
                    test_flat_mixed_perfect_and_s8 (emit) clusters[s8] (emitting),             test_wrap_around_clusters[s16-*],
                                                          test_output_chunks[generic]          test_key_types_under_a_selection
+  unit sizes       every source here runs the flat pool in 512-tuple and the generic pool in 64-tuple units (a full
+                   device's probe waves); units of 512 ... 65 536 / 64 ... 8192 tuples, source forms, queue capacity and
+                   the pool tuning: tests/test_gpu_pool_units.py
 The LIP scan's own probe loop: test_wrap_around_clusters (scan_filter with lip_joins=1); every key type and table kind of
 test_key_types, the all-ones key and several joins in one scan: tests/test_gpu_scan_lip.py."""
 import ctypes as C

@@ -1,6 +1,6 @@
 """The plan of a pool launch, the part that needs no GPU: duckdb-polr_amd/csrc/polr_pool_plan.h as a stand-alone host
 program (tests/poolplan/pool_plan_main.cpp: known answers of grid, ring and unit sizing, the effect of every tuning
-field, and the invariants the device code relies on over a sweep of shapes), built with the address +
+field, the invariants the device code relies on over a sweep of shapes, and how a round is cut into units), built with the address +
 undefined-behaviour sanitizers and run directly."""
 import os
 import re
@@ -31,6 +31,10 @@ def test_plan_program_under_sanitizers(tmp_path):
     m = re.match(r"invariants: (\d+) plans, (\d+) refused", lines[2])
     assert m and int(m.group(1)) + int(m.group(2)) == 2 * 2 * 4 * 4 * 8 * 16 * 8, lines[2]
     assert int(m.group(1)) > 0 and int(m.group(2)) > 0
+    # how a round is cut into units: the known answers, and the whole table tests/test_pool_units.py reads
+    assert "unit answers: 22 rows" in lines
+    assert "unit table: %d lines" % (15 * 4 * 3 * 2 * 2 * 4) in lines
+    assert len([l for l in lines if l.startswith("unit ") and " -> " in l]) == 15 * 4 * 3 * 2 * 2 * 4
 
 
 def test_the_plan_header_needs_no_hip():
