@@ -108,6 +108,9 @@ struct polr_ht {
 	DevBuf<uint32_t> idx_row;
 	std::vector<OwnedCol> pcols;
 	std::vector<DevBuf<uint8_t>> heaps; // string heaps of VARCHAR payload columns (polr_ht_set_payload_heap), owned
+	// a table made by polr_ht_from_output: the cells and validity arrays of all its columns in one allocation -- keys and
+	// payload are views of it (their own owners are empty, as for a caller's POLR_COL_DEVICE memory)
+	DevBuf<uint8_t> col_mem;
 	std::vector<DictCol> dicts; // dictionaries of the code columns (polr_ht_encode_dictionary), cells owned
 	uint32_t is_dense = 0, has_null = 0;
 	uint64_t device_bytes = 0;
@@ -329,6 +332,15 @@ void polr_launch_chunk_prefix(hipStream_t st, const uint32_t *chunk_count, uint3
 // ... of 64-bit counts (the chunks' heap bytes, polr_strout.hip): the same kernel, nothing truncated
 void polr_launch_chunk_prefix(hipStream_t st, const uint64_t *chunk_bytes, uint32_t n_chunks, uint64_t *chunk_base,
                               uint64_t *total);
+// the measure and write passes of a VARCHAR output column (polr_strout.hip), over the chunks the output's statistics count
+// (n_chunks > 0).  measure: row_off[n_rows], chunk_bytes[n_chunks], *n_long += the long non-NULL cells; polr_launch_chunk_prefix
+// over chunk_bytes gives chunk_heap_base.  write: heap_dev is where the bytes go, heap_addr the address the cells carry.
+uint32_t polr_strout_block(const polr_out *o); // workgroup size of both, and of the fixed-width gather of polr_fromout.hip
+void polr_launch_strout_measure(hipStream_t st, const polr_out *o, uint32_t slot, DevCol src, uint64_t *row_off,
+                                uint64_t *chunk_bytes, unsigned long long *n_long);
+void polr_launch_strout_write(hipStream_t st, const polr_out *o, uint32_t slot, DevCol src, const uint64_t *row_off,
+                              const uint64_t *chunk_heap_base, uint4 *dst_cells, uint8_t *dst_valid, uint8_t *heap_dev,
+                              uint64_t heap_addr);
 
 // shared between capi and mpx
 int polr_plan_launch(polr_pipeline *p, bool materialize, uint64_t total_tuples, uint32_t *unit_size,

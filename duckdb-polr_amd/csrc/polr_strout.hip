@@ -160,8 +160,24 @@ __global__ __launch_bounds__(256) void polr_strout_write_kernel(DevOut out, cons
 }
 
 // workgroup size of both passes: a wave per 64 rows of a chunk's capacity, four at the most
-static uint32_t strout_block(const polr_out *o) {
+uint32_t polr_strout_block(const polr_out *o) {
 	return std::min<uint32_t>(256u, (o->dev.chunk_capacity + 63u) / 64u * 64u);
+}
+
+// the two passes over the chunks the output's statistics count (polr_out_materialize_strings below; polr_ht_from_output,
+// polr_fromout.hip)
+void polr_launch_strout_measure(hipStream_t st, const polr_out *o, uint32_t slot, DevCol src, uint64_t *row_off,
+                                uint64_t *chunk_bytes, unsigned long long *n_long) {
+	hipLaunchKernelGGL(polr_strout_measure_kernel, dim3(o->n_chunks), dim3(polr_strout_block(o)), 0, st, o->dev,
+	                   o->chunk_base.get(), o->n_chunks, slot, src, row_off, chunk_bytes, n_long);
+}
+
+void polr_launch_strout_write(hipStream_t st, const polr_out *o, uint32_t slot, DevCol src, const uint64_t *row_off,
+                              const uint64_t *chunk_heap_base, uint4 *dst_cells, uint8_t *dst_valid, uint8_t *heap_dev,
+                              uint64_t heap_addr) {
+	hipLaunchKernelGGL(polr_strout_write_kernel, dim3(o->n_chunks), dim3(polr_strout_block(o)), 0, st, o->dev,
+	                   o->chunk_base.get(), o->n_chunks, slot, src, row_off, chunk_heap_base, dst_cells, dst_valid, heap_dev,
+	                   heap_addr, (uint32_t)POLR_STRCOPY_LANE_MAX);
 }
 
 extern "C" int polr_out_materialize_strings(polr_out *o, void *stream, int32_t src_join, uint32_t src_col, void *dst_cells,
@@ -201,14 +217,13 @@ extern "C" int polr_out_materialize_strings(polr_out *o, void *stream, int32_t s
 		return POLR_OK; // (also an output no materialising run has filled: it has no rows)
 	}
 	// measure
-	const uint32_t nc = o->n_chunks, block = strout_block(o);
+	const uint32_t nc = o->n_chunks;
 	DevBuf<uint64_t> row_off, chunk_words; // chunk_words: [nc] byte totals, [nc] their exclusive prefix, the total, the long cells
 	HIPCHK(ctx, row_off.alloc(n));
 	HIPCHK(ctx, chunk_words.alloc(2ull * nc + 2));
 	uint64_t *chunk_bytes = chunk_words.get(), *chunk_heap_base = chunk_bytes + nc, *tail = chunk_heap_base + nc;
 	HIPCHK(ctx, hipMemsetAsync(tail, 0, 16, st));
-	hipLaunchKernelGGL(polr_strout_measure_kernel, dim3(nc), dim3(block), 0, st, o->dev, o->chunk_base.get(), nc, c.slot, c.dev,
-	                   row_off.get(), chunk_bytes, (unsigned long long *)(tail + 1));
+	polr_launch_strout_measure(st, o, c.slot, c.dev, row_off.get(), chunk_bytes, (unsigned long long *)(tail + 1));
 	polr_launch_chunk_prefix(st, (const uint64_t *)chunk_bytes, nc, chunk_heap_base, tail);
 	uint64_t h_tail[2] = {0, 0};
 	HIPCHK(ctx, hipMemcpyAsync(h_tail, tail, 16, hipMemcpyDeviceToHost, st));
@@ -241,8 +256,7 @@ extern "C" int polr_out_materialize_strings(polr_out *o, void *stream, int32_t s
 			d_heap = tmp_heap;
 		}
 	}
-	hipLaunchKernelGGL(polr_strout_write_kernel, dim3(nc), dim3(block), 0, st, o->dev, o->chunk_base.get(), nc, c.slot, c.dev,
-	                   row_off.get(), chunk_heap_base, d_cells, d_valid, d_heap, (uint64_t)dst_heap, (uint32_t)POLR_STRCOPY_LANE_MAX);
+	polr_launch_strout_write(st, o, c.slot, c.dev, row_off.get(), chunk_heap_base, d_cells, d_valid, d_heap, (uint64_t)dst_heap);
 	if (!to_device) {
 		HIPCHK(ctx, hipMemcpyAsync(dst_cells, tmp_cells, n * 16, hipMemcpyDeviceToHost, st));
 		if (dst_valid) {

@@ -48,6 +48,7 @@ EXPORTS = [
     "polr_device_bytes_live",
     "polr_out_materialize_strings",
     "polr_mpx_pool_info",
+    "polr_ht_from_output",
 ]
 
 
@@ -176,6 +177,19 @@ def flatten_filter_expr(expr):
     if expr is not None:
         walk(expr)
     return nodes, values
+
+
+class OutColRef(C.Structure):
+    """polr_out_col_ref"""
+    _fields_ = [("src_join", C.c_int32), ("src_col", C.c_uint32)]
+
+
+def _out_col_refs(cols):
+    """[(src_join, src_col)] -> polr_out_col_ref array"""
+    arr = (OutColRef * max(len(cols), 1))()
+    for i, (sj, sc) in enumerate(cols):
+        arr[i].src_join, arr[i].src_col = sj, sc
+    return arr
 
 
 class HeapRange(C.Structure):
@@ -330,6 +344,7 @@ def load():
                                             C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]
     L.polr_ht_upload_rows.argtypes = [vp, vp, u64, u32, vp, vp, vp, u32, u32, P(vp)]
     L.polr_ht_upload_columns.argtypes = [vp, P(Col), u32, P(Col), u32, u64, P(vp)]
+    L.polr_ht_from_output.argtypes = [vp, vp, P(OutColRef), u32, P(OutColRef), u32, P(vp)]
     L.polr_ht_finalize_hash.argtypes = [vp, vp]
     L.polr_ht_finalize_perfect.argtypes = [vp, i64, i64, vp]
     L.polr_pht_upload.argtypes = [vp, u32, u32, i64, i64, vp, P(Col), u32, P(vp)]
@@ -536,6 +551,18 @@ class HashTable:
         h = C.c_void_p()
         ctx.check(ctx.L.polr_ht_upload_columns(ctx.h, _col_array(key_cols), len(key_cols), _col_array(payload_cols),
                                                len(payload_cols), n_rows, C.byref(h)))
+        return cls(ctx, h)
+
+    @classmethod
+    def from_output(cls, out, keys, payload=(), stream=None):
+        """polr_ht_from_output: the rows of Output `out` as an un-finalized build side, built on the device.  keys / payload:
+        [(src_join, src_col)] as the sinks take them (-1 = probe table).  Build row r of the new table is output row r of
+        `out` (the order of fetch_ids); the table owns all its memory, `out` and its sources may be closed afterwards."""
+        ctx = out.ctx
+        keys, payload = list(keys), list(payload)
+        h = C.c_void_p()
+        ctx.check(ctx.L.polr_ht_from_output(out.h, stream, _out_col_refs(keys), len(keys), _out_col_refs(payload), len(payload),
+                                            C.byref(h)))
         return cls(ctx, h)
 
     def set_key_flags(self, key_col, flags):

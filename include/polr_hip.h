@@ -138,6 +138,42 @@ int polr_ht_upload_rows(polr_ctx *ctx, const void *rows, uint64_t n_rows, uint32
  * column is POLR_KEY_NULL_EQUAL; row ids still refer to the rows as passed. */
 int polr_ht_upload_columns(polr_ctx *ctx, const polr_col *keys, uint32_t n_keys, const polr_col *payload,
                            uint32_t n_payload, uint64_t n_rows, polr_ht **out);
+/* Same from the OUTPUT of another pipeline, on the device: the pipeline whose sink is the build of a hash join
+ * (PhysicalHashJoin::Sink of a child pipeline, physical_hash_join.cpp:217-286; the bushy plans of JOB).  `o` is an output a
+ * materialising run has filled; keys[i] / payload[i] name columns of its pipeline as polr_agg_spec does.
+ * The new table is un-finalized, exactly as polr_ht_upload_columns would return it, with ONE BUILD ROW PER OUTPUT ROW of `o`
+ * in the order of polr_out_fetch_ids / polr_out_materialize (chunk-major): build row id r of the new table is output row r
+ * of `o`, so a pipeline that later probes the new table reports ids that index polr_out_fetch_ids of `o`.
+ * Columns: column i has the width and the POLR_COL_SIGNED flag of its source; every column gets a validity array gathered
+ * from the source's (all rows valid when the source has none); the cell of a NULL row is zero and the source cell of a NULL
+ * row is never read.  Keys: the shapes polr_ht_upload_columns takes -- 1..POLR_MAX_KEYS columns of 1, 2, 4 or 8 bytes (a
+ * 16-byte key: POLR_E_UNSUPPORTED); at most 62 payload columns (what polr_ht_export carries).  The same source column may
+ * be named more than once, also once as a key and once as payload.
+ * Afterwards polr_ht_set_key_flags, the three polr_ht_finalize_* calls, polr_ht_encode_dictionary[_ex], polr_ht_get_info and
+ * -- for a table without VARCHAR columns -- polr_ht_export / polr_ht_alloc_like work as on any uploaded table; rows with a
+ * NULL key are dropped at finalize as always.
+ * VARCHAR payload columns (width 16): the cells are normalised exactly as polr_out_materialize_strings normalises them
+ * (inline strings zero-padded, NULL rows all-zero) and the long strings' bytes are copied into a packed heap THE NEW TABLE
+ * OWNS, one per such column; the column counts as rebased, so a later polr_ht_set_payload_heaps on it is refused.  A source
+ * column the library uploaded whose heap never came is POLR_E_INVALID once a long non-NULL cell is among the output rows
+ * (decided by the measuring pass, before any pointer is followed).
+ * Ownership: when the call returns the new table shares nothing with `o`, its pipeline, the source tables or a caller's
+ * POLR_COL_DEVICE memory -- all of those may be destroyed; it holds a reference to the context as every handle does, and
+ * polr_ht_info::device_bytes and polr_device_bytes_live() account for every byte of it.
+ * Refusals -- nothing is enqueued beyond the output's own statistics, *out = NULL, polr_device_bytes_live() as before:
+ *   POLR_E_INVALID      NULL o, out or keys; NULL payload with n_payload > 0; an output with a fused GROUP BY sink (it holds
+ *                       group cells, no row ids); a column reference out of range
+ *   POLR_E_UNSUPPORTED  n_keys outside 1..POLR_MAX_KEYS, a key wider than 8 bytes, more than 62 payload columns; an output
+ *                       of 2^32 - 16 rows or more (the bound of polr_ht_upload_columns)
+ * An output with no rows, or one no materialising run has filled, gives a valid table of 0 rows: it finalizes, and probing
+ * it matches nothing.  The call returns when the table is complete (it needs the row count on the host, and with a VARCHAR
+ * column the heap totals). */
+typedef struct polr_out_col_ref {
+	int32_t src_join; /* -1 = probe-table column, j >= 0 = payload column of join j (as polr_agg_spec) */
+	uint32_t src_col;
+} polr_out_col_ref;
+int polr_ht_from_output(polr_out *o, void *stream, const polr_out_col_ref *keys, uint32_t n_keys,
+                        const polr_out_col_ref *payload, uint32_t n_payload, polr_ht **out);
 /* Key semantics beyond "same type on both sides, NULL never matches": the reference multiplexes INNER hash joins whose
  * left side is CAST(column) (src/parallel/polar_config.cpp:75-82) and whose comparison is IS NOT DISTINCT FROM
  * (JoinHashTable::null_values_are_equal, src/execution/join_hashtable.cpp:35-36,170-192,642).  Per key column, BEFORE the
