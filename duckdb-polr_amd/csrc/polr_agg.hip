@@ -1590,10 +1590,9 @@ static int aggregate_hashed(polr_out *o, void *stream, const polr_group_key *col
 			}
 		}
 	}
-	uint64_t capacity = 1024;
-	while (capacity < 2 * max_groups) {
-		capacity <<= 1;
-	}
+	PolrCapacityPlan slots_plan; // (max_groups is at most 2^24: never refused)
+	POLR_TRY_PLAN(ctx, slots_plan, polr_build_capacity(max_groups, slots_plan));
+	const uint64_t capacity = slots_plan.capacity;
 	HashAggTable t;
 	memset(&t, 0, sizeof(t));
 	t.mask = capacity - 1;

@@ -153,32 +153,11 @@ int polr_ctx_set_pool_tuning(polr_ctx *ctx, const polr_pool_tuning *t) {
 // ---------------------------------------------------------------------------------------------------
 // helpers
 // ---------------------------------------------------------------------------------------------------
-static bool valid_width(uint32_t w) {
-	return w == 1 || w == 2 || w == 4 || w == 8 || w == 16;
-}
-
-// what polr_ht_upload_* and the other functions that build a handle hold it in: POLR_FAIL / HIPCHK inside them then
-// destroy the half-built handle, and success hands it out with release()
-struct HandleDeleter {
-	void operator()(polr_ht *ht) const {
-		polr_ht_destroy(ht);
-	}
-	void operator()(polr_pipeline *p) const {
-		polr_pipeline_destroy(p);
-	}
-	void operator()(polr_out *o) const {
-		polr_out_destroy(o);
-	}
-};
-template <class T>
-using HandleGuard = std::unique_ptr<T, HandleDeleter>;
-
 // copy (or alias) a caller column to the device; acct: gains the bytes allocated
 static int ingest_col(polr_ctx *ctx, const polr_col *src, uint64_t n_rows, OwnedCol *dst, uint64_t *acct,
                       hipStream_t st) {
-	if (!valid_width(src->width)) {
-		POLR_FAIL(ctx, POLR_E_UNSUPPORTED, "column width %u not supported (1,2,4,8,16)", src->width);
-	}
+	PolrBuildPlan plan;
+	POLR_TRY_PLAN(ctx, plan, polr_build_check_col_width(src->width, plan));
 	if (!src->data && n_rows) {
 		POLR_FAIL(ctx, POLR_E_INVALID, "column data pointer is NULL");
 	}
@@ -218,41 +197,17 @@ static int upload_devcols(polr_ctx *ctx, const std::vector<OwnedCol> &cols, DevB
 	return POLR_OK;
 }
 
-static uint64_t next_pow2_u64(uint64_t v) {
-	uint64_t p = 1;
-	while (p < v) {
-		p <<= 1;
+// the last step of an upload: the key columns are a shape the kernels take, and their device array
+static int accept_keys(polr_ht *ht) {
+	polr_ctx *ctx = ht->ctx;
+	std::vector<uint32_t> widths;
+	for (auto &k : ht->keys) {
+		widths.push_back(k.width);
 	}
-	return p;
-}
-
-static int check_key_shape(polr_ctx *ctx, const std::vector<OwnedCol> &keys) {
-	if (keys.empty() || keys.size() > POLR_MAX_KEYS) {
-		POLR_FAIL(ctx, POLR_E_UNSUPPORTED, "%zu equality keys per join not supported (1..%d)", keys.size(),
-		          POLR_MAX_KEYS);
-	}
-	for (auto &k : keys) {
-		if (k.width > 8) {
-			POLR_FAIL(ctx, POLR_E_UNSUPPORTED, "VARCHAR join keys are outside this path");
-		}
-		if (k.width != 1 && k.width != 2 && k.width != 4 && k.width != 8) {
-			POLR_FAIL(ctx, POLR_E_UNSUPPORTED, "join key of %u bytes", k.width);
-		}
-	}
-	return POLR_OK;
-}
-
-// composite keys outside the plain {key0 | key1 << 32} form are packed exactly (KeyPack)
-static bool needs_key_pack(const polr_ht *ht) {
-	if (ht->n_keys >= 3) {
-		return true;
-	}
-	for (uint32_t c = 0; c < ht->n_keys; c++) {
-		if (ht->key_flags[c]) {
-			return true; // compared by value (a CAST on one side) or NULL = NULL: the packed form does both exactly
-		}
-	}
-	return ht->n_keys == 2 && (ht->keys[0].width > 4 || ht->keys[1].width > 4);
+	PolrBuildPlan plan;
+	POLR_TRY_PLAN(ctx, plan, polr_build_check_keys(widths.size(), widths.data(), plan));
+	ht->key_signed = ht->keys[0].flags & POLR_COL_SIGNED;
+	return upload_devcols(ctx, ht->keys, &ht->keys_dev, ctx->stream);
 }
 
 extern "C" {
@@ -267,27 +222,17 @@ int polr_ht_upload_columns(polr_ctx *ctx, const polr_col *keys, uint32_t n_keys,
 		return POLR_E_INVALID;
 	}
 	*out = nullptr;
-	if (n_rows >= 0xFFFFFFF0ull) {
-		POLR_FAIL(ctx, POLR_E_UNSUPPORTED, "build side of %llu rows exceeds the 32-bit row-id space",
-		          (unsigned long long)n_rows);
-	}
+	PolrBuildPlan plan;
+	POLR_TRY_PLAN(ctx, plan, polr_build_check_rows(n_rows, plan));
 	HIPCHK(ctx, hipSetDevice(ctx->device));
-	HandleGuard<polr_ht> ht(new polr_ht());
-	ht->ctx = polr_ctx_retain(ctx);
-	ht->n_keys = n_keys;
-	ht->n_payload = n_payload;
-	ht->n_rows_in = n_rows;
-	ht->keys.resize(n_keys);
-	ht->payload.resize(n_payload);
+	HandleGuard<polr_ht> ht = polr_ht_new(ctx, n_keys, n_payload, n_rows);
 	for (uint32_t i = 0; i < n_keys; i++) {
 		POLR_TRY(ingest_col(ctx, &keys[i], n_rows, &ht->keys[i], &ht->device_bytes, ctx->stream));
 	}
 	for (uint32_t i = 0; i < n_payload; i++) {
 		POLR_TRY(ingest_col(ctx, &payload[i], n_rows, &ht->payload[i], &ht->device_bytes, ctx->stream));
 	}
-	POLR_TRY(check_key_shape(ctx, ht->keys));
-	ht->key_signed = ht->keys[0].flags & POLR_COL_SIGNED;
-	POLR_TRY(upload_devcols(ctx, ht->keys, &ht->keys_dev, ctx->stream));
+	POLR_TRY(accept_keys(ht.get()));
 	*out = ht.release();
 	return POLR_OK;
 }
@@ -300,28 +245,12 @@ int polr_ht_upload_rows(polr_ctx *ctx, const void *rows, uint64_t n_rows, uint32
 		return POLR_E_INVALID;
 	}
 	*out = nullptr;
-	if (n_rows >= 0xFFFFFFF0ull) {
-		POLR_FAIL(ctx, POLR_E_UNSUPPORTED, "build side of %llu rows exceeds the 32-bit row-id space",
-		          (unsigned long long)n_rows);
-	}
 	const uint32_t ncols = n_keys + n_payload;
-	for (uint32_t c = 0; c < ncols; c++) {
-		if (!valid_width(col_width[c]) || (uint64_t)col_offset[c] + col_width[c] > row_width) {
-			POLR_FAIL(ctx, POLR_E_INVALID, "row layout: column %u (offset %u, width %u) does not fit row width %u", c,
-			          col_offset[c], col_width[c], row_width);
-		}
-	}
-	if ((ncols + 1 + 7) / 8 > row_width) {
-		POLR_FAIL(ctx, POLR_E_INVALID, "row layout: validity bytes exceed row width");
-	}
+	PolrBuildPlan plan;
+	POLR_TRY_PLAN(ctx, plan, polr_build_check_rows(n_rows, plan));
+	POLR_TRY_PLAN(ctx, plan, polr_build_check_row_layout(row_width, ncols, col_offset, col_width, plan));
 	HIPCHK(ctx, hipSetDevice(ctx->device));
-	HandleGuard<polr_ht> ht(new polr_ht());
-	ht->ctx = polr_ctx_retain(ctx);
-	ht->n_keys = n_keys;
-	ht->n_payload = n_payload;
-	ht->n_rows_in = n_rows;
-	ht->keys.resize(n_keys);
-	ht->payload.resize(n_payload);
+	HandleGuard<polr_ht> ht = polr_ht_new(ctx, n_keys, n_payload, n_rows);
 	DevBuf<uint8_t> blob;
 	HIPCHK(ctx, blob.alloc(n_rows * row_width));
 	if (n_rows) {
@@ -339,9 +268,7 @@ int polr_ht_upload_rows(polr_ctx *ctx, const void *rows, uint64_t n_rows, uint32
 		                            col.valid);
 	}
 	HIPCHK(ctx, hipStreamSynchronize(ctx->stream)); // (the row de-serialisation; blob is a local)
-	POLR_TRY(check_key_shape(ctx, ht->keys));
-	ht->key_signed = ht->keys[0].flags & POLR_COL_SIGNED;
-	POLR_TRY(upload_devcols(ctx, ht->keys, &ht->keys_dev, ctx->stream));
+	POLR_TRY(accept_keys(ht.get()));
 	*out = ht.release();
 	return POLR_OK;
 }
@@ -374,8 +301,15 @@ int polr_ht_finalize_hash(polr_ht *ht, void *stream) {
 	HIPCHK(ctx, hipSetDevice(ctx->device));
 	hipStream_t st = polr_stream(ctx, stream);
 	const uint64_t n = ht->n_rows_in;
-	KeyPack pack = KeyPack(); // (built here, stored with everything else once the build has succeeded)
-	if (needs_key_pack(ht)) {
+	uint32_t key_width[POLR_MAX_KEYS] = {}, col_flags[POLR_MAX_KEYS] = {};
+	for (uint32_t c = 0; c < ht->n_keys; c++) {
+		key_width[c] = ht->keys[c].width;
+		col_flags[c] = ht->keys[c].flags;
+	}
+	PolrKeyPackPlan packed; // (built here, stored with everything else once the build has succeeded)
+	packed.pack = KeyPack();
+	const KeyPack &pack = packed.pack;
+	if (polr_build_needs_key_pack(ht->n_keys, key_width, ht->key_flags)) {
 		// per-column [min, max] of the build keys (rows with a NULL key never match and do not count)
 		long long h_mm[2 * POLR_NKEYS];
 		for (uint32_t c = 0; c < POLR_NKEYS; c++) {
@@ -385,45 +319,15 @@ int polr_ht_finalize_hash(polr_ht *ht, void *stream) {
 		DevBuf<long long> mm;
 		HIPCHK(ctx, mm.alloc(2 * POLR_NKEYS));
 		HIPCHK(ctx, hipMemcpyAsync(mm, h_mm, sizeof(h_mm), hipMemcpyHostToDevice, st));
-		uint32_t null_eq = 0;
-		for (uint32_t c = 0; c < ht->n_keys; c++) {
-			null_eq |= (ht->key_flags[c] & POLR_KEY_NULL_EQUAL) ? (1u << c) : 0u;
-		}
-		pack.null_eq = null_eq;
+		const uint32_t null_eq = polr_build_null_eq_mask(ht->n_keys, ht->key_flags);
 		polr_launch_key_minmax(st, ht->keys_dev, ht->n_keys, n, null_eq, mm);
 		HIPCHK(ctx, hipMemcpyAsync(h_mm, mm, sizeof(h_mm), hipMemcpyDeviceToHost, st));
 		HIPCHK(ctx, hipStreamSynchronize(st));
-		uint32_t shift = 0;
-		pack.packed = 1;
-		for (uint32_t c = 0; c < ht->n_keys; c++) {
-			const bool empty = h_mm[2 * c] > h_mm[2 * c + 1]; // no row with valid keys at all
-			const int64_t lo = empty ? 0 : h_mm[2 * c], hi = empty ? 0 : h_mm[2 * c + 1];
-			const uint64_t range = (uint64_t)hi - (uint64_t)lo;
-			// (a NULL = NULL column has one more code, range + 1: NULL)
-			const bool null_eq_col = ((null_eq >> c) & 1u) != 0;
-			const uint64_t top = range + (null_eq_col ? 1u : 0u);
-			uint32_t bits = 0;
-			while (bits < 64 && (top >> bits) != 0) {
-				bits++;
-			}
-			if (shift + bits > 64 || (null_eq_col && top == 0)) {
-				POLR_FAIL(ctx, POLR_E_UNSUPPORTED,
-				          "composite key of %u columns needs more than 64 bits (column %u: range %llu after %u bits)",
-				          ht->n_keys, c, (unsigned long long)range, shift);
-			}
-			pack.shift[c] = shift;
-			pack.sx[c] = (ht->keys[c].flags & 1u) ? 1u : 0u;
-			pack.min[c] = lo;
-			pack.range[c] = range;
-			shift += bits;
-		}
+		POLR_TRY_PLAN(ctx, packed, polr_build_key_pack(ht->n_keys, h_mm, null_eq, col_flags, packed));
 	}
-	// load factor <= 0.5 like PointerTableCapacity (join_hashtable.hpp:265-267), floor 1024 slots
-	const uint64_t capacity = next_pow2_u64(std::max<uint64_t>(2 * n, 1024));
-	if (capacity > (1ull << 31)) {
-		POLR_FAIL(ctx, POLR_E_UNSUPPORTED, "hash table of %llu slots exceeds the 32-bit slot space",
-		          (unsigned long long)capacity);
-	}
+	PolrCapacityPlan slots_plan;
+	POLR_TRY_PLAN(ctx, slots_plan, polr_build_capacity(n, slots_plan));
+	const uint64_t capacity = slots_plan.capacity;
 	const uint64_t n_blocks = (capacity + 1023) / 1024;
 	DevBuf<uint8_t> slots_mem; // [capacity] uint4: the table itself unless it is converted to 8-byte slots
 	DevBuf<uint32_t> slot_of_row, cursor, rowids, block_sums, scalars;
@@ -449,11 +353,9 @@ int polr_ht_finalize_hash(polr_ht *ht, void *stream) {
 	// h_scalars: [0] sentinel rows, [1] longest run, [2] rows with a regular key
 	polr_launch_s16_scatter(st, n, slots, slot_of_row, cursor, rowids, h_scalars[2], scalars + 3);
 	HIPCHK(ctx, hipStreamSynchronize(st));
-	const uint64_t max_run = std::max<uint64_t>(h_scalars[1], h_scalars[0]);
-	if (max_run >= (1ull << 25)) {
-		POLR_FAIL(ctx, POLR_E_UNSUPPORTED, "a build key repeats more than 2^25 times: outside the expansion counter range");
-	}
-	const bool unique32 = max_run <= 1 && ht->n_keys == 1 && ht->keys[0].width == 4 && !pack.packed;
+	PolrKindPlan kind;
+	POLR_TRY_PLAN(ctx, kind, polr_build_hash_kind(h_scalars[1], h_scalars[0], ht->n_keys, key_width[0], pack.packed != 0, kind));
+	const bool unique32 = kind.kind == KIND_S8;
 	DevBuf<uint8_t> s8_mem; // [capacity] uint2
 	if (unique32) {
 		HIPCHK(ctx, s8_mem.alloc(capacity * sizeof(uint2)));
@@ -468,7 +370,7 @@ int polr_ht_finalize_hash(polr_ht *ht, void *stream) {
 	ht->capacity = capacity;
 	ht->sentinel_start = h_scalars[2];
 	ht->sentinel_count = h_scalars[0];
-	ht->max_run = max_run;
+	ht->max_run = kind.max_run;
 	if (unique32) {
 		ht->table_mem = std::move(s8_mem);
 	} else {
@@ -478,7 +380,7 @@ int polr_ht_finalize_hash(polr_ht *ht, void *stream) {
 	}
 	ht->device_bytes += ht->table_mem.bytes();
 	ht->table = ht->table_mem;
-	ht->kind = unique32 ? KIND_S8 : KIND_S16;
+	ht->kind = kind.kind;
 	return POLR_OK;
 }
 
@@ -515,16 +417,11 @@ int polr_ht_finalize_perfect(polr_ht *ht, int64_t min_value, int64_t max_value, 
 		                                   "(the reference plans perfect hash joins for plain equalities only)");
 	}
 	const bool is_signed = ht->key_signed != 0;
-	const uint64_t range = is_signed ? (uint64_t)(max_value - min_value) : (uint64_t)max_value - (uint64_t)min_value;
-	if ((is_signed && max_value < min_value) || (!is_signed && (uint64_t)max_value < (uint64_t)min_value) ||
-	    range >= (1ull << 31)) {
-		POLR_FAIL(ctx, POLR_E_INVALID, "perfect hash range [%lld, %lld] invalid", (long long)min_value,
-		          (long long)max_value);
-	}
+	PolrPerfectPlan plan;
+	POLR_TRY_PLAN(ctx, plan, polr_build_perfect_range(min_value, max_value, is_signed, plan));
 	HIPCHK(ctx, hipSetDevice(ctx->device));
 	hipStream_t st = polr_stream(ctx, stream);
-	const uint64_t size = range + 1;
-	const uint64_t words = (size + 31) / 32;
+	const uint64_t range = plan.range, size = plan.size, words = plan.words;
 	DevBuf<uint8_t> bits_mem; // [words] uint32_t
 	DevBuf<uint32_t> idx_row, flags;
 	DevBuf<unsigned long long> unique;
@@ -579,17 +476,11 @@ int polr_ht_finalize_auto(polr_ht *ht, int64_t min_value, int64_t max_value, voi
 		return POLR_E_INVALID;
 	}
 	int rc = POLR_E_DUPLICATE;
-	const bool is_signed = ht->key_signed != 0;
-	const bool ordered = is_signed ? max_value >= min_value : (uint64_t)max_value >= (uint64_t)min_value;
-	if (ht->kind == KIND_NONE && ht->n_keys == 1 && ordered && ht->n_rows_in > 0 && !ht->key_flags[0]) {
-		const uint64_t range = is_signed ? (uint64_t)(max_value - min_value) : (uint64_t)max_value - (uint64_t)min_value;
-		// dense keys of any range, and -- like the reference's planner, plan_comparison_join.cpp:118,125 -- any key
-		// whose range is at most 1 M values (a 125 KB bit table, however few of its bits are set: a filtered dimension)
-		if (range < (1ull << 31) && (range / POLR_DENSE_FACTOR <= ht->n_rows_in || range <= 1000000ull)) {
-			rc = polr_ht_finalize_perfect(ht, min_value, max_value, stream);
-			if (rc != POLR_OK && rc != POLR_E_DUPLICATE) {
-				return rc;
-			}
+	if (ht->kind == KIND_NONE &&
+	    polr_build_auto_tries_perfect(ht->n_keys, ht->key_flags, ht->n_rows_in, min_value, max_value, ht->key_signed != 0)) {
+		rc = polr_ht_finalize_perfect(ht, min_value, max_value, stream);
+		if (rc != POLR_OK && rc != POLR_E_DUPLICATE) {
+			return rc;
 		}
 	}
 	if (rc == POLR_E_DUPLICATE) {
@@ -609,29 +500,22 @@ int polr_pht_upload(polr_ctx *ctx, uint32_t key_width, uint32_t key_flags, int64
 	}
 	*out = nullptr;
 	const bool is_signed = (key_flags & POLR_COL_SIGNED) != 0;
-	const uint64_t range = is_signed ? (uint64_t)(max_value - min_value) : (uint64_t)max_value - (uint64_t)min_value;
-	if (range >= (1ull << 31) || key_width > 8 || !valid_width(key_width)) {
-		POLR_FAIL(ctx, POLR_E_INVALID, "perfect table shape invalid");
-	}
+	PolrPerfectPlan plan;
+	POLR_TRY_PLAN(ctx, plan, polr_build_pht_upload(key_width, min_value, max_value, is_signed, plan));
 	HIPCHK(ctx, hipSetDevice(ctx->device));
-	const uint64_t size = range + 1;
-	HandleGuard<polr_ht> ht(new polr_ht());
-	ht->ctx = polr_ctx_retain(ctx);
-	ht->n_keys = 1;
-	ht->n_payload = n_payload;
+	const uint64_t range = plan.range, size = plan.size;
+	HandleGuard<polr_ht> ht = polr_ht_new(ctx, 1, n_payload, 0); // (n_rows_in: the bits set, counted below)
 	ht->key_signed = is_signed ? POLR_COL_SIGNED : 0;
-	ht->keys.resize(1);
 	ht->keys[0].width = key_width;
 	ht->keys[0].flags = ht->key_signed;
 	ht->pcols.resize(n_payload);
-	ht->payload.resize(n_payload);
 	for (uint32_t i = 0; i < n_payload; i++) {
 		POLR_TRY(ingest_col(ctx, &payload[i], size, &ht->pcols[i], &ht->device_bytes, ctx->stream));
 		ht->payload[i].width = ht->pcols[i].width;
 	}
 	DevBuf<uint8_t> bytes;
 	HIPCHK(ctx, bytes.alloc(size));
-	HIPCHK(ctx, ht->table_mem.alloc(((size + 31) / 32) * 4));
+	HIPCHK(ctx, ht->table_mem.alloc(plan.words * 4));
 	ht->device_bytes += ht->table_mem.bytes();
 	ht->bits = (uint32_t *)ht->table_mem.get();
 	HIPCHK(ctx, hipMemcpyAsync(bytes, bitmap, size, hipMemcpyHostToDevice, ctx->stream));
@@ -683,79 +567,14 @@ int polr_ht_get_info(const polr_ht *ht, polr_ht_info *info) {
 }
 
 // ---- export / alloc_like: the buffers a build-side broadcast has to move --------------------------
-struct HtMeta {
-	uint32_t magic, kind, n_keys, n_payload, key_signed, is_dense, has_null, sentinel_start, sentinel_count, pad;
-	uint64_t n_rows_in, n_rows, capacity, max_run, range;
-	int64_t min_value, max_value;
-	uint32_t key_width[POLR_MAX_KEYS];
-	uint32_t key_flags[POLR_MAX_KEYS];
-	uint32_t key_sem[POLR_MAX_KEYS]; // POLR_KEY_* (polr_ht_set_key_flags)
-	KeyPack pack;
-	uint32_t payload_width[62];
-	uint32_t payload_flags[62];
-	uint8_t payload_has_valid[62];
-};
-
-// bytes of a buffer of n bytes as polr_ht_export lists it and polr_ht_alloc_like allocates it: what the table that is
-// exported holds (DevBuf::alloc(n): n bytes, 16 for an empty buffer) -- never more, the receiving side copies that many
-static uint64_t export_bytes(uint64_t n) {
-	return n ? n : 16;
+// (PolrHtMeta: polr_build_plan.h, with the list of buffers it implies and the check of a received one)
+static void meta_buffers(const PolrHtMeta &m,std::vector<PolrBuildBuffer> &bufs) {
+	polr_build_buffers(m.kind, m.capacity, m.n_rows_in, m.n_payload, m.payload_width, m.payload_has_valid, bufs);
 }
 
-static void ht_buffers(const polr_ht *ht, std::vector<void *> &ptrs, std::vector<uint64_t> &bytes) {
-	const uint64_t rows = ht->kind == KIND_PERFECT ? ht->capacity : ht->n_rows_in;
-	if (ht->kind == KIND_PERFECT) {
-		ptrs.push_back(ht->bits);
-		bytes.push_back(((ht->capacity + 31) / 32) * 4);
-	} else if (ht->kind == KIND_S8) {
-		ptrs.push_back(ht->table);
-		bytes.push_back(ht->capacity * sizeof(uint2));
-	} else {
-		ptrs.push_back(ht->table);
-		bytes.push_back(ht->capacity * sizeof(uint4));
-		ptrs.push_back(ht->rowids);
-		bytes.push_back(export_bytes(ht->n_rows_in * 4));
-	}
-	for (uint32_t i = 0; i < ht->n_payload; i++) {
-		const OwnedCol &c = build_col(ht, i);
-		ptrs.push_back(c.data);
-		bytes.push_back(export_bytes(rows * c.width));
-		if (c.valid) {
-			ptrs.push_back(c.valid);
-			bytes.push_back(export_bytes(rows));
-		}
-	}
-}
-
-int polr_ht_export(const polr_ht *ht, void *meta, uint64_t *meta_bytes, void **dev_ptrs, uint64_t *dev_bytes,
-                   uint32_t *n_buffers) {
-	POLR_ENTRY();
-	if (!ht || !meta_bytes || !n_buffers) {
-		return POLR_E_INVALID;
-	}
-	polr_ctx *ctx = ht->ctx;
-	if (ht->kind == KIND_NONE) {
-		POLR_FAIL(ctx, POLR_E_INVALID, "table not finalized");
-	}
-	if (ht->n_payload > 62) {
-		POLR_FAIL(ctx, POLR_E_UNSUPPORTED, "more than 62 payload columns");
-	}
-	std::vector<void *> ptrs;
-	std::vector<uint64_t> bytes;
-	ht_buffers(ht, ptrs, bytes);
-	const uint32_t cap_buffers = *n_buffers;
-	const uint64_t cap_meta = *meta_bytes;
-	*n_buffers = (uint32_t)ptrs.size();
-	*meta_bytes = sizeof(HtMeta);
-	if (!meta || !dev_ptrs || !dev_bytes) {
-		return POLR_OK; // size query
-	}
-	if (cap_buffers < ptrs.size() || cap_meta < sizeof(HtMeta)) {
-		POLR_FAIL(ctx, POLR_E_INVALID, "export buffers too small");
-	}
-	HtMeta m;
+static void fill_meta(const polr_ht *ht, PolrHtMeta &m) {
 	memset(&m, 0, sizeof(m));
-	m.magic = 0x504F4C52u;
+	m.magic = POLR_BUILD_META_MAGIC;
 	m.kind = ht->kind;
 	m.n_keys = ht->n_keys;
 	m.n_payload = ht->n_payload;
@@ -783,83 +602,114 @@ int polr_ht_export(const polr_ht *ht, void *meta, uint64_t *meta_bytes, void **d
 		m.payload_flags[i] = c.flags;
 		m.payload_has_valid[i] = c.valid ? 1 : 0;
 	}
+}
+
+// where the table keeps a buffer of the plan's list
+static void *ht_buffer(const polr_ht *ht, const PolrBuildBuffer &b) {
+	switch (b.what) {
+	case POLR_BUF_TABLE:
+		return ht->table;
+	case POLR_BUF_ROWIDS:
+		return ht->rowids;
+	case POLR_BUF_COL_DATA:
+		return build_col(ht, b.col).data;
+	default:
+		return build_col(ht, b.col).valid;
+	}
+}
+
+int polr_ht_export(const polr_ht *ht, void *meta, uint64_t *meta_bytes, void **dev_ptrs, uint64_t *dev_bytes,
+                   uint32_t *n_buffers) {
+	POLR_ENTRY();
+	if (!ht || !meta_bytes || !n_buffers) {
+		return POLR_E_INVALID;
+	}
+	polr_ctx *ctx = ht->ctx;
+	if (ht->kind == KIND_NONE) {
+		POLR_FAIL(ctx, POLR_E_INVALID, "table not finalized");
+	}
+	if (ht->n_payload > POLR_BUILD_MAX_PAYLOAD) {
+		POLR_FAIL(ctx, POLR_E_UNSUPPORTED, "more than %u payload columns", POLR_BUILD_MAX_PAYLOAD);
+	}
+	PolrHtMeta m;
+	fill_meta(ht, m);
+	std::vector<PolrBuildBuffer> bufs;
+	meta_buffers(m, bufs);
+	const uint32_t cap_buffers = *n_buffers;
+	const uint64_t cap_meta = *meta_bytes;
+	*n_buffers = (uint32_t)bufs.size();
+	*meta_bytes = sizeof(PolrHtMeta);
+	if (!meta || !dev_ptrs || !dev_bytes) {
+		return POLR_OK; // size query
+	}
+	if (cap_buffers < bufs.size() || cap_meta < sizeof(PolrHtMeta)) {
+		POLR_FAIL(ctx, POLR_E_INVALID, "export buffers too small");
+	}
 	memcpy(meta, &m, sizeof(m));
-	for (size_t i = 0; i < ptrs.size(); i++) {
-		dev_ptrs[i] = ptrs[i];
-		dev_bytes[i] = bytes[i];
+	for (size_t i = 0; i < bufs.size(); i++) {
+		dev_ptrs[i] = ht_buffer(ht, bufs[i]);
+		dev_bytes[i] = bufs[i].bytes;
 	}
 	return POLR_OK;
 }
 
 int polr_ht_alloc_like(polr_ctx *ctx, const void *meta, uint64_t meta_bytes, polr_ht **out) {
 	POLR_ENTRY();
-	if (!ctx || !meta || !out || meta_bytes < sizeof(HtMeta)) {
+	if (!ctx || !meta || !out || meta_bytes < sizeof(PolrHtMeta)) {
 		return POLR_E_INVALID;
 	}
 	*out = nullptr;
-	HtMeta m;
+	PolrHtMeta m;
 	memcpy(&m, meta, sizeof(m));
-	if (m.magic != 0x504F4C52u || m.n_payload > 62 || m.n_keys > POLR_MAX_KEYS) {
-		POLR_FAIL(ctx, POLR_E_INVALID, "bad table metadata");
-	}
-	if (m.kind != KIND_PERFECT && m.kind != KIND_S8 && m.kind != KIND_S16) {
-		POLR_FAIL(ctx, POLR_E_INVALID, "bad table kind in metadata");
-	}
+	PolrBuildPlan plan;
+	POLR_TRY_PLAN(ctx, plan, polr_build_check_meta(m, plan));
+	std::vector<PolrBuildBuffer> bufs;
+	meta_buffers(m, bufs);
 	HIPCHK(ctx, hipSetDevice(ctx->device));
-	HandleGuard<polr_ht> ht(new polr_ht());
-	ht->ctx = polr_ctx_retain(ctx);
+	HandleGuard<polr_ht> ht = polr_ht_new(ctx, m.n_keys, m.n_payload, m.n_rows_in);
 	ht->kind = m.kind;
-	ht->n_keys = m.n_keys;
-	ht->n_payload = m.n_payload;
 	ht->key_signed = m.key_signed;
 	ht->is_dense = m.is_dense;
 	ht->has_null = m.has_null;
 	ht->sentinel_start = m.sentinel_start;
 	ht->sentinel_count = m.sentinel_count;
-	ht->n_rows_in = m.n_rows_in;
 	ht->n_rows = m.n_rows;
 	ht->capacity = m.capacity;
 	ht->max_run = m.max_run;
 	ht->range = m.range;
 	ht->min_value = m.min_value;
 	ht->max_value = m.max_value;
-	ht->keys.resize(m.n_keys);
 	for (uint32_t i = 0; i < m.n_keys; i++) {
 		ht->keys[i].width = m.key_width[i];
 		ht->keys[i].flags = m.n_keys == 1 ? m.key_signed : m.key_flags[i];
 		ht->key_flags[i] = m.key_sem[i];
 	}
 	ht->pack = m.pack;
-	const uint64_t rows = m.kind == KIND_PERFECT ? m.capacity : m.n_rows_in;
-	if (m.kind == KIND_PERFECT) {
-		HIPCHK(ctx, ht->table_mem.alloc(((m.capacity + 31) / 32) * 4));
-		ht->bits = (uint32_t *)ht->table_mem.get();
-	} else {
-		HIPCHK(ctx, ht->table_mem.alloc(m.capacity * (m.kind == KIND_S8 ? sizeof(uint2) : sizeof(uint4))));
-	}
-	ht->table = ht->table_mem;
-	ht->device_bytes += ht->table_mem.bytes();
-	if (m.kind == KIND_S16) {
-		HIPCHK(ctx, ht->rowids.alloc(m.n_rows_in));
-		ht->device_bytes += ht->rowids.bytes();
-	}
 	std::vector<OwnedCol> &cols = m.kind == KIND_PERFECT ? ht->pcols : ht->payload;
 	cols.resize(m.n_payload);
-	if (m.kind == KIND_PERFECT) {
-		ht->payload.resize(m.n_payload);
-	}
 	for (uint32_t i = 0; i < m.n_payload; i++) {
-		cols[i].width = m.payload_width[i];
+		cols[i].width = ht->payload[i].width = m.payload_width[i];
 		cols[i].flags = m.payload_flags[i];
-		HIPCHK(ctx, cols[i].alloc_data(rows * cols[i].width));
-		ht->device_bytes += cols[i].own_data.bytes();
-		if (m.payload_has_valid[i]) {
-			HIPCHK(ctx, cols[i].alloc_valid(rows));
-			ht->device_bytes += cols[i].own_valid.bytes();
+	}
+	// the buffers the sending side listed, each with the bytes it listed
+	for (const PolrBuildBuffer &b : bufs) {
+		switch (b.what) {
+		case POLR_BUF_TABLE:
+			HIPCHK(ctx, ht->table_mem.alloc(b.bytes));
+			ht->table = ht->table_mem;
+			ht->bits = m.kind == KIND_PERFECT ? (uint32_t *)ht->table_mem.get() : nullptr;
+			break;
+		case POLR_BUF_ROWIDS:
+			HIPCHK(ctx, ht->rowids.alloc(m.n_rows_in));
+			break;
+		case POLR_BUF_COL_DATA:
+			HIPCHK(ctx, cols[b.col].alloc_data(b.bytes));
+			break;
+		default:
+			HIPCHK(ctx, cols[b.col].alloc_valid(b.bytes));
+			break;
 		}
-		if (m.kind == KIND_PERFECT) {
-			ht->payload[i].width = cols[i].width;
-		}
+		ht->device_bytes += b.bytes;
 	}
 	POLR_TRY(upload_devcols(ctx, cols, &ht->payload_dev, ctx->stream));
 	*out = ht.release();

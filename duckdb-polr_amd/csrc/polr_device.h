@@ -18,6 +18,7 @@
 #include <stdint.h>
 
 #include "polr_pipeline_plan.h" // POLR_KMAX, POLR_PMAX, POLR_NKEYS, POLR_NPREDS, KIND_*: shared with the host's plan
+#include "polr_build_plan.h"    // KeyPack: shared with the host's build-side plan
 
 // Device code names the address space of what it loads from: a pointer rebuilt from an integer (descriptors travel as
 // 64-bit words through LDS and scalar registers) is a GENERIC pointer to the compiler, and a generic access is a FLAT
@@ -49,18 +50,6 @@ __device__ __forceinline__ uint4 load_global_x4(const POLR_GLOBAL uint32_t *p) {
 
 #define S8_EMPTY_ROW 0xFFFFFFFFu
 #define S16_EMPTY_KEY 0xFFFFFFFFFFFFFFFFull
-
-// Composite keys that do not fit the plain {key0 | key1 << 32} form: column c contributes (value - min[c]) << shift[c],
-// value sign- or zero-extended by the BUILD column's type; a probe value outside [min, min + range] cannot match.
-struct KeyPack {
-	uint32_t packed; // 0: plain form
-	uint32_t shift[POLR_NKEYS];
-	uint32_t sx[POLR_NKEYS]; // sign-extend column c (the BUILD column; the probe side's: StageExt::key_sx)
-	uint32_t null_eq;        // bit c: IS NOT DISTINCT FROM on column c -- NULL is the code range[c] + 1, on both sides
-	uint32_t pad[2];
-	int64_t min[POLR_NKEYS];
-	uint64_t range[POLR_NKEYS];
-};
 
 struct DevCol {
 	const uint8_t *data;

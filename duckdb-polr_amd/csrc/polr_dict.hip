@@ -477,15 +477,17 @@ extern "C" int polr_ht_encode_dictionary_ex(polr_ht *ht, uint32_t payload_col, u
 			POLR_FAIL(ctx, POLR_E_INVALID, "payload column %u is encoded already (code column %u)", payload_col, d.code_col);
 		}
 	}
-	if (ht->n_payload >= 62) {
-		// (polr_ht_export / polr_ht_alloc_like describe at most 62 payload columns: no table is made that cannot be shipped)
-		POLR_FAIL(ctx, POLR_E_UNSUPPORTED, "the table has %u payload columns already: a code column would be the 63rd, more than "
-		                                   "polr_ht_export carries", ht->n_payload);
+	if (ht->n_payload >= POLR_BUILD_MAX_PAYLOAD) {
+		// (polr_ht_export / polr_ht_alloc_like describe no more payload columns: no table is made that cannot be shipped)
+		POLR_FAIL(ctx, POLR_E_UNSUPPORTED, "the table has %u payload columns already: a code column would be the %urd, more than "
+		                                   "polr_ht_export carries", ht->n_payload, POLR_BUILD_MAX_PAYLOAD + 1);
 	}
 	const uint64_t n = ht->n_rows_in;
-	if (n > (1ull << 30)) {
+	PolrCapacityPlan slots_plan; // the string table: a slot space of its own, the build side's capacity rule
+	if (polr_build_capacity(n, slots_plan)) {
 		POLR_FAIL(ctx, POLR_E_UNSUPPORTED, "a dictionary over %llu build rows exceeds the 32-bit slot space", (unsigned long long)n);
 	}
+	const uint64_t capacity = slots_plan.capacity;
 	HIPCHK(ctx, hipSetDevice(ctx->device));
 	hipStream_t st = polr_stream(ctx, stream);
 	if (st != ctx->stream) {
@@ -493,13 +495,6 @@ extern "C" int polr_ht_encode_dictionary_ex(polr_ht *ht, uint32_t payload_col, u
 		HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
 	}
 	const uint4 *cells = (const uint4 *)src.data;
-	const uint64_t capacity = [&] {
-		uint64_t c = 1024;
-		while (c < 2 * n) {
-			c <<= 1;
-		}
-		return c;
-	}();
 	const uint32_t n_blocks = (uint32_t)std::max<uint64_t>(1, (n + POLR_DICT_BLOCK * POLR_DICT_ITEMS - 1) / (POLR_DICT_BLOCK * POLR_DICT_ITEMS));
 	// one scratch allocation: the table, the per-row and per-block arrays, the scalars
 	const size_t b_rep = capacity * 16, b_hash = capacity * 8, b_state = capacity * 4, b_first = capacity * 4, b_code = capacity * 4,
@@ -509,7 +504,7 @@ extern "C" int polr_ht_encode_dictionary_ex(polr_ht *ht, uint32_t payload_col, u
 	OwnedCol codes;
 	codes.width = 4;
 	codes.flags = 0;
-	const uint64_t acct = std::max<uint64_t>(n * 4, 16); // (what polr_ht_export reports for a column)
+	const uint64_t acct = polr_build_buffer_bytes(n * 4); // (what polr_ht_export reports for the column)
 	HIPCHK(ctx, codes.alloc_data(acct));
 	if ((flags & POLR_DICT_NULL_INVALID) && src.valid) { // the code column's own copy of the validity array
 		HIPCHK(ctx, codes.alloc_valid(n));

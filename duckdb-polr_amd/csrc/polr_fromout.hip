@@ -127,14 +127,6 @@ __global__ __launch_bounds__(256) void polr_fromout_gather_kernel(DevOut out, co
 	}
 }
 
-namespace {
-struct HtDeleter {
-	void operator()(polr_ht *ht) const {
-		polr_ht_destroy(ht);
-	}
-};
-} // namespace
-
 static PolrFromoutColumn fromout_shape(const OutCol &c) {
 	PolrFromoutColumn s;
 	s.resolved = 1;
@@ -221,13 +213,7 @@ extern "C" int polr_ht_from_output(polr_out *o, void *stream, const polr_out_col
 		}
 	}
 	// the table and everything it owns, before the first kernel that writes into it
-	std::unique_ptr<polr_ht, HtDeleter> ht(new polr_ht());
-	ht->ctx = polr_ctx_retain(ctx);
-	ht->n_keys = n_keys;
-	ht->n_payload = n_payload;
-	ht->n_rows_in = n;
-	ht->keys.resize(n_keys);
-	ht->payload.resize(n_payload);
+	HandleGuard<polr_ht> ht = polr_ht_new(ctx, n_keys, n_payload, n);
 	HIPCHK(ctx, ht->col_mem.alloc(plan.table_bytes));
 	ht->device_bytes += ht->col_mem.bytes();
 	for (uint32_t c = 0; c < n_cols; c++) {

@@ -27,9 +27,10 @@
 #include <vector>
 
 #include "../../include/polr_hip.h"
+#include "polr_build_plan.h" // the limits and cell widths of every build side
 
-#define POLR_FROMOUT_MAX_PAYLOAD 62u         // what polr_ht_export carries
-#define POLR_FROMOUT_MAX_ROWS 0xFFFFFFF0ull  // the bound of polr_ht_upload_columns: build row ids are 32-bit
+#define POLR_FROMOUT_MAX_PAYLOAD POLR_BUILD_MAX_PAYLOAD // what polr_ht_export carries
+#define POLR_FROMOUT_MAX_ROWS POLR_BUILD_MAX_ROWS       // the bound of polr_ht_upload_columns: build row ids are 32-bit
 #define POLR_FROMOUT_MAX_SLOTS 9u            // 1 + POLR_MAX_JOINS: the probe row and a build row per join
 
 struct PolrFromoutColumn { // a column reference as polr_out_col resolved it
@@ -84,9 +85,7 @@ struct PolrFromoutPlan {
 
 #define POLR_FROMOUT_ALIGN 256ull // of every array inside the table's allocation
 
-static inline uint64_t polr_fromout_alloc_bytes(uint64_t bytes) { // DevBuf::alloc
-	return bytes ? bytes : 16;
-}
+#define polr_fromout_alloc_bytes polr_build_buffer_bytes // DevBuf::alloc
 
 // what can be refused before a column reference is looked at -> POLR_OK, or POLR_E_* with pl.err set
 static inline int polr_fromout_check(const PolrFromoutRequest &rq, PolrFromoutPlan &pl) {
@@ -133,7 +132,7 @@ static inline int polr_fromout_plan(const PolrFromoutRequest &rq, const PolrFrom
 		if (is_key && w > 8) {
 			POLR_FO_REFUSE(POLR_E_UNSUPPORTED, "key %u: VARCHAR join keys are outside this path", idx);
 		}
-		if (w != 1 && w != 2 && w != 4 && w != 8 && (is_key || w != 16)) {
+		if (is_key ? !polr_build_key_width_ok(w) : !polr_build_cell_width_ok(w)) {
 			POLR_FO_REFUSE(POLR_E_UNSUPPORTED, "%s %u: cells of %u bytes", what, idx, w);
 		}
 	}

@@ -6,6 +6,7 @@
 #include <stdint.h>
 
 #include <atomic>
+#include <memory>
 #include <string>
 #include <vector>
 
@@ -204,11 +205,49 @@ struct polr_out {
 		}                                                                                                              \
 	} while (0)
 
+// a refusal of a host plan (polr_build_plan.h: the code returned, the text in plan.err) becomes the context's error
+#define POLR_TRY_PLAN(ctx_, plan_, call_)                                                                              \
+	do {                                                                                                               \
+		const int rc_ = (call_);                                                                                       \
+		if (rc_) {                                                                                                     \
+			POLR_FAIL(ctx_, rc_, "%s", (plan_).err);                                                                   \
+		}                                                                                                              \
+	} while (0)
+
 // Diagnostic (POLR_DEBUG_HIP_ERRORS=1 in the environment): every C-ABI entry point reports a HIP error that an
 // EARLIER call left in the thread's last-error slot, naming the entry point that ran before -- how a swallowed
 // HIP status is tracked down.  Off: one predictable branch.
 void polr_trace_stale(const char *where);
 #define POLR_ENTRY() polr_trace_stale(__func__)
+
+// what the functions that build a handle hold it in: POLR_FAIL / HIPCHK inside them then destroy the half-built handle, and
+// success hands it out with release()
+struct HandleDeleter {
+	void operator()(polr_ht *ht) const {
+		polr_ht_destroy(ht);
+	}
+	void operator()(polr_pipeline *p) const {
+		polr_pipeline_destroy(p);
+	}
+	void operator()(polr_out *o) const {
+		polr_out_destroy(o);
+	}
+};
+template <class T>
+using HandleGuard = std::unique_ptr<T, HandleDeleter>;
+
+// the skeleton of a new build side, behind every route to one: the context retained, the counts set, a column record per
+// key and payload column
+static inline HandleGuard<polr_ht> polr_ht_new(polr_ctx *ctx, uint32_t n_keys, uint32_t n_payload, uint64_t n_rows_in) {
+	HandleGuard<polr_ht> ht(new polr_ht());
+	ht->ctx = polr_ctx_retain(ctx);
+	ht->n_keys = n_keys;
+	ht->n_payload = n_payload;
+	ht->n_rows_in = n_rows_in;
+	ht->keys.resize(n_keys);
+	ht->payload.resize(n_payload);
+	return ht;
+}
 
 static inline hipStream_t polr_stream(polr_ctx *ctx, void *stream) {
 	return stream ? (hipStream_t)stream : ctx->stream;

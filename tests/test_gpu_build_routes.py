@@ -422,6 +422,7 @@ def test_uploaded_perfect_table_refusals(gpu_ctx):
 
     no_leak(gpu_ctx, capi.E_INVALID, upload(4, 0, 2**31))         # a range of 2^31
     no_leak(gpu_ctx, capi.E_INVALID, upload(8, -2**62, 2**62))    # ... and far beyond
+    no_leak(gpu_ctx, capi.E_INVALID, upload(8, 2**63 - 1, -2**63))  # max < min in the key's own order (a wrapped range of 1)
     no_leak(gpu_ctx, capi.E_INVALID, upload(3, 0, 63))
     no_leak(gpu_ctx, capi.E_INVALID, upload(16, 0, 63))
     live = capi.device_bytes_live()
@@ -523,19 +524,21 @@ def test_clone(gpu_ctx, name):
 
 
 def test_clone_metadata_refusals(gpu_ctx):
-    """a metadata blob cut short, with another magic, a table kind that does not exist or too many payload columns"""
+    """a metadata blob cut short, with another magic, a table kind that does not exist, too many payload columns, a payload
+    column of 3 bytes or a hash table of 1000 slots"""
     ht = capi.HashTable.from_columns(gpu_ctx, [np.arange(100, dtype=np.int32)], [np.arange(100, dtype=np.int16)]).finalize_hash()
     meta, _ = ht.export()
     ht.close()
     words = np.frombuffer(meta, dtype=np.uint32)
     assert words[0] == 0x504F4C52 and words[1] == 2 and words[2] == 1 and words[3] == 1  # magic, kind, n_keys, n_payload
+    assert words[14] == 1024 and words[15] == 0 and words[64] == 2  # capacity (64-bit), the payload column's width
 
     def patched(word, value):
         w = words.copy()
         w[word] = value
         return w.tobytes()
 
-    for bad in (meta[:-1], patched(0, 0x504F4C53), patched(1, 0), patched(1, 7), patched(3, 63)):
+    for bad in (meta[:-1], patched(0, 0x504F4C53), patched(1, 0), patched(1, 7), patched(3, 63), patched(64, 3), patched(14, 1000)):
         no_leak(gpu_ctx, capi.E_INVALID, lambda: capi.HashTable.alloc_like(gpu_ctx, bad))
     capi.HashTable.alloc_like(gpu_ctx, meta).close()
 
