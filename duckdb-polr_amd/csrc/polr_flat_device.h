@@ -15,12 +15,15 @@
 //     190-350 G lookups/s for an L2-resident table, tools/micro/gather_bench.hip);
 //   * between stages the survivors wait in per-wave LDS queues (what CacheJoinChunk does for 1024-row chunks,
 //     polar_pipeline_executor.cpp:166-195) as 16-bit positions inside the unit (a unit is at most 65 536 tuples);
-//   * the deeper stages run as ONE SWEEP: when some deeper stage has a full step, up to 512 (256 beyond four joins)
-//     entries are popped from
-//     EVERY deeper queue at once, all their key gathers are issued together (8 / 4 per lane and stage), then all their
-//     table lookups, then the survivors are pushed on, deepest stage first.  A wave is bound by dependent memory
-//     round trips (measured: 67 % of its cycles waiting with one stage at a time), and a sweep pays two of them for
-//     all stages instead of two per stage;
+//   * the deeper stages run as ONE SWEEP: when some deeper stage has a full step, up to 512 (256 beyond two joins)
+//     entries are popped from EVERY deeper queue at once, all their key gathers are issued together (8 / 4 per lane
+//     and stage), then all their table lookups, then the survivors are pushed on, deepest stage first.  A wave is
+//     bound by dependent memory round trips (measured: 67 % of its cycles waiting with one stage at a time), and a
+//     sweep pays two of them for all stages instead of two per stage.  "Issued together" is a property of the
+//     COMPILED code, not of the order of the statements: until the gather and table phases were written as
+//     straight-line code (flat_sweep) every load stood under a per-element branch and waited for the one before it --
+//     a sweep at K = 4 paid up to 12 round trips, not two.  tools/mlp_report.py counts the waits between the marker
+//     comments of the two phases (profiles/mlp_report.txt; tests/test_mlp_report.py pins them at zero for K = 4);
 //   * the k stage descriptors of the current join order sit in scalar registers (loaded when the order changes).
 #pragma once
 
@@ -82,6 +85,7 @@ struct FlatCtx {
 	uint32_t k, lane;
 	FlatStage st[K]; // the current join order, statically indexed (SGPRs)
 	const POLR_GLOBAL uint32_t *sel;
+	bool plain; // no selection vector and no validity column on a deeper stage of the current order (flat_set_plain)
 	const POLR_LDS uint32_t *lds_tables; // the workgroup's LDS-resident bit tables
 	POLR_LDS uint16_t *q;                // this wave's queues
 	uint32_t qsize[K], cnt[K];
@@ -98,32 +102,33 @@ struct FlatCtx {
 
 // ---- membership test in two halves: issue (addresses + loads in flight), then resolve -------------------------
 // perfect table: 32-bit modular arithmetic, exact for signed and unsigned 4-byte keys while [min, max] lies inside the
-// key type's domain (checked on the host).  w = the loaded bit word (0 where the key is out of range / inactive).
+// key type's domain (checked on the host).  Every element loads a word, with no branch around the load: an element
+// whose key is out of range reads the table's last word, and its word counts for nothing -- idx says so (an inactive
+// element gets FLAT_NO_IDX, beyond every range: a table spans less than 2^31 values).  (A load under a per-element
+// branch makes the compiler wait for every load before it issues the next.  The index is clamped, not chosen with a
+// select, and no flag lives across the load: flags are scalar register pairs, and with them K = 4 spilled 15 VGPRs.)
+#define FLAT_NO_IDX 0xFFFFFFFFu
 template <int F>
 __device__ __forceinline__ void flat_perfect_issue(const FlatStage &s, const POLR_LDS uint32_t *lds_tables, const uint32_t (&key)[F],
                                                    const bool (&act)[F], uint32_t (&idx)[F], uint32_t (&w)[F]) {
 	const uint32_t lds_off1 = s.kind_lds >> 8;
-	bool in[F];
+	uint32_t at[F];
 #pragma unroll
 	for (int i = 0; i < F; i++) {
-		idx[i] = key[i] - s.a;
-		in[i] = act[i] && idx[i] <= s.b;
-		w[i] = 0;
+		idx[i] = act[i] ? key[i] - s.a : FLAT_NO_IDX;
+		at[i] = (idx[i] < s.b ? idx[i] : s.b) >> 5;
 	}
+	// (one address space per stage, wave-uniform: DS_READ or GLOBAL_LOAD, never a generic access)
 	if (lds_off1) {
 		const POLR_LDS uint32_t *bits = lds_tables + (lds_off1 - 1u);
 #pragma unroll
 		for (int i = 0; i < F; i++) {
-			if (in[i]) {
-				w[i] = bits[idx[i] >> 5];
-			}
+			w[i] = bits[at[i]];
 		}
 	} else {
 #pragma unroll
 		for (int i = 0; i < F; i++) {
-			if (in[i]) {
-				w[i] = s.table[idx[i] >> 5];
-			}
+			w[i] = s.table[at[i]];
 		}
 	}
 }
@@ -194,7 +199,7 @@ __device__ __forceinline__ void flat_lookup(const FlatStage &s, const POLR_LDS u
 		flat_perfect_issue<F>(s, lds_tables, key, act, idx, w);
 #pragma unroll
 		for (int i = 0; i < F; i++) {
-			hit[i] = (w[i] >> (idx[i] & 31u)) & 1u;
+			hit[i] = idx[i] <= s.b && ((w[i] >> (idx[i] & 31u)) & 1u) != 0;
 		}
 	} else {
 		flat_hash_lookup<F>(s, key, act, hit);
@@ -406,30 +411,50 @@ __device__ __forceinline__ void flat_stage0(FlatCtx<K> &c) {
 		}
 		return;
 	}
+	// the lane-per-tuple step: 256 tuples at a time in (up to) two batches of loads -- the rows of a selection vector,
+	// then keys and validity bytes together.  No load stands under a per-element branch: a slot past the end of the
+	// step reads what the step's first tuple reads and stays inactive; a stage without validity column reads byte 0 of
+	// its key column for every slot, and the byte counts for nothing.
 	c.pf_pos = ~0ull;
 	const uint64_t pos0 = c.in_pos;
 	c.in_pos += n;
+	const bool has_valid = s.valid != nullptr;
+	const POLR_GLOBAL uint8_t *vbytes = has_valid ? s.valid : (const POLR_GLOBAL uint8_t *)s.keys;
+	const uint32_t vmask = has_valid ? 0xFFFFFFFFu : 0u;
+	const uint32_t no_valid = has_valid ? 0u : 1u; // (every byte is looked at either way: no load is left unwaited)
 #pragma unroll 1
 	for (uint32_t h = 0; h * 256u < n; h++) {
-		uint32_t pos[F], row[F], key[F];
+		uint32_t pos[F], row[F], key[F], vb[F];
 		bool act[F], hit[F];
+		asm volatile("; polr-stage0-slow-begin" ::: "memory");
 #pragma unroll
 		for (int i = 0; i < F; i++) {
 			const uint32_t off = h * 256u + c.lane + 64u * i;
 			act[i] = off < n;
 			pos[i] = upos + off;
-			const uint64_t tp = pos0 + off;
-			row[i] = act[i] ? (c.sel ? c.sel[tp] : (uint32_t)tp) : 0u;
+			row[i] = act[i] ? off : 0u; // (still the offset inside the step)
+		}
+		if (c.sel) {
+#pragma unroll
+			for (int i = 0; i < F; i++) {
+				row[i] = c.sel[pos0 + row[i]];
+			}
+			__builtin_amdgcn_s_waitcnt(0x0F70); // vmcnt(0): one wait for the batch, not one in front of every key's load
+		} else {
+#pragma unroll
+			for (int i = 0; i < F; i++) {
+				row[i] += (uint32_t)pos0;
+			}
 		}
 #pragma unroll
 		for (int i = 0; i < F; i++) {
-			key[i] = act[i] ? s.keys[row[i]] : 0u;
+			key[i] = s.keys[row[i]];
+			vb[i] = vbytes[row[i] & vmask];
 		}
-		if (s.valid) {
+		asm volatile("; polr-stage0-slow-end" ::: "memory");
 #pragma unroll
-			for (int i = 0; i < F; i++) {
-				act[i] = act[i] && s.valid[row[i]] != 0; // NULL never matches (join_hashtable.cpp:170-192)
-			}
+		for (int i = 0; i < F; i++) {
+			act[i] = act[i] && (vb[i] | no_valid) != 0; // NULL never matches (join_hashtable.cpp:170-192)
 		}
 		flat_lookup<F>(s, c.lds_tables, key, act, hit);
 		flat_emit<K, 0, F>(c, pos, hit);
@@ -452,107 +477,177 @@ __device__ __forceinline__ void flat_static_for_down(Fn &&fn) { // I = N-1 ... 1
 	}
 }
 
-// All deeper stages at once.  Per stage three registers per tuple live across the memory round trips: its position in
-// the unit, its key (after the lookup: the bit to test), the table word (hash stages: the hit flag).
+#define FLAT_INACTIVE 0xFFFFFFFFu // the position of a sweep slot that holds no tuple (no unit position is that large)
+
+// take up to one sweep from the queue that feeds stage P.  Every slot reads the queue -- a slot beyond the entries taken
+// reads the first one taken (an allocated entry even when the queue is empty) and becomes FLAT_INACTIVE: no branch
+// stands around a read
+template <int K, int P, int F>
+__device__ __forceinline__ void flat_pop(FlatCtx<K> &c, uint32_t (&pos)[F]) {
+	const uint32_t qs = c.qsize[P];
+	const uint32_t n = qs < (uint32_t)(64 * F) ? qs : (uint32_t)(64 * F);
+	const uint32_t base = qs - n;
+	const POLR_LDS uint16_t *qq = c.q + flat_qoff<K>(P);
+#pragma unroll
+	for (int i = 0; i < F; i++) {
+		const uint32_t off = c.lane + 64u * i;
+		const uint32_t e = qq[base + (off < n ? off : 0u)];
+		pos[i] = off < n ? e : FLAT_INACTIVE;
+	}
+	c.qsize[P] = base;
+}
+
+// the values are in their registers when this point is reached: loads that write them have come back
+template <int F>
+__device__ __forceinline__ void flat_await(const uint32_t (&v)[F]) {
+	static_assert(F == 4 || F == 8, "sweep widths");
+	if constexpr (F == 4) {
+		asm volatile("; polr-sweep-await" ::"v"(v[0]), "v"(v[1]), "v"(v[2]), "v"(v[3]));
+	} else {
+		asm volatile("; polr-sweep-await" ::"v"(v[0]), "v"(v[1]), "v"(v[2]), "v"(v[3]), "v"(v[4]), "v"(v[5]), "v"(v[6]), "v"(v[7]));
+	}
+}
+
+// All deeper stages at once.  Per stage two registers per tuple live across the memory round trips: its position in
+// the unit (from phase 2 on with the bit to test in its upper half) and its key, later the table word (hash stages:
+// the hit flag).  (With a third register for the bit, K = 6 and K = 8 spill inside the two phases.)
 //   1. pop up to one sweep from EVERY deeper queue and request the keys    -> all key gathers in flight together
 //   2. bit-table stages: request the bit words                             -> all table loads in flight together
 //      hash stages: probe
 //   3. push the survivors on, deepest stage first (the queue a stage pushes into has just been popped: it has room)
+// "In flight together" has to be written, it does not follow from the order of the statements: a load under a
+// per-element branch (`if (active) key = keys[row]`) or a wave-uniform branch between two loads makes the compiler
+// wait for ALL loads in flight (s_waitcnt vmcnt(0)) before the next one -- the sweep as first written paid one round
+// trip per load, up to 12 at K = 4.  So phases 1 and 2 are straight-line code:
+//   * every slot loads.  An inactive slot (FLAT_INACTIVE: beyond the queue's entries, NULL key, key outside the table's
+//     range) reads what the unit's FIRST tuple reads -- a row of the same column, one request for all such lanes -- or
+//     some word of the table, and the value counts for nothing: it never counts, pushes or emits (phase 3 asks the
+//     position);
+//   * a stage beyond the pipeline's last join (k < K) has an empty queue: all its slots are inactive, it reads stage 0's
+//     key column;
+//   * whether there is a selection vector or a validity column is decided ONCE per sweep (c.plain), not per stage.
+// The marker comments are read by tools/mlp_report.py, which counts loads and waits between them.
 template <int K>
 __device__ __forceinline__ void flat_sweep(FlatCtx<K> &c) {
 	constexpr int F = flat_sweep_f<K>();
 	if constexpr (K > 1) {
-		uint32_t pos[K - 1][F], key[K - 1][F], w[K - 1][F];
-		flat_static_for<1, K>([&](auto P) {
-			constexpr int p = decltype(P)::value;
-			if (p < (int)c.k) {
-				const FlatStage &s = c.st[p];
-				const uint32_t qs = c.qsize[p];
-				const uint32_t n = qs < (uint32_t)(64 * F) ? qs : (uint32_t)(64 * F);
-				const uint32_t base = qs - n;
-				const POLR_LDS uint16_t *qq = c.q + flat_qoff<K>(p);
-				uint32_t row[F];
+		// pos: the position in the unit (bits 0-15; after phase 2 the bit to test in bits 16-20), FLAT_INACTIVE when the slot
+		// is out of the running; key: the key, after phase 2 the table word (hash stages: the hit flag)
+		uint32_t pos[K - 1][F], key[K - 1][F];
+		if (c.plain) {
+			asm volatile("; polr-sweep-keys-begin" ::: "memory");
+			flat_static_for<1, K>([&](auto P) {
+				constexpr int p = decltype(P)::value;
+				// (the unit's rows as a scalar base + a 16-bit position: one address register per gather)
+				const POLR_GLOBAL uint32_t *keys = (p < (int)c.k ? c.st[p].keys : c.st[0].keys) + (uint32_t)c.unit_begin;
+				flat_pop<K, p, F>(c, pos[p - 1]);
 #pragma unroll
 				for (int i = 0; i < F; i++) {
-					const uint32_t off = c.lane + 64u * i;
-					// (an inactive slot keeps an impossible position: its key is never loaded, its word stays 0)
-					pos[p - 1][i] = off < n ? (uint32_t)qq[base + off] : 0xFFFFFFFFu;
+					key[p - 1][i] = keys[pos[p - 1][i] != FLAT_INACTIVE ? pos[p - 1][i] : 0u];
 				}
-				c.qsize[p] = base;
-				if (c.sel) {
-#pragma unroll
-					for (int i = 0; i < F; i++) {
-						row[i] = pos[p - 1][i] != 0xFFFFFFFFu ? c.sel[c.unit_begin + pos[p - 1][i]] : 0u;
-					}
-				} else {
-#pragma unroll
-					for (int i = 0; i < F; i++) {
-						row[i] = (uint32_t)c.unit_begin + pos[p - 1][i];
-					}
-				}
+			});
+			asm volatile("; polr-sweep-keys-end" ::: "memory");
+		} else {
+			// two batches: the rows (a selection vector's entries), ONE wait, then keys and validity bytes together (a stage
+			// without validity column reads byte 0 of its key column for every slot)
+			uint32_t vb[K - 1][F];
+			asm volatile("; polr-sweep-sel-keys-begin" ::: "memory");
+			flat_static_for<1, K>([&](auto P) {
+				constexpr int p = decltype(P)::value;
+				flat_pop<K, p, F>(c, pos[p - 1]);
 #pragma unroll
 				for (int i = 0; i < F; i++) {
-					key[p - 1][i] = pos[p - 1][i] != 0xFFFFFFFFu ? s.keys[row[i]] : 0u;
+					key[p - 1][i] = pos[p - 1][i] != FLAT_INACTIVE ? pos[p - 1][i] : 0u; // (the row, from here to its key's load)
 				}
-				if (s.valid) {
+			});
+			if (c.sel) {
+				flat_static_for<1, K>([&](auto P) {
+					constexpr int p = decltype(P)::value;
 #pragma unroll
 					for (int i = 0; i < F; i++) {
-						if (pos[p - 1][i] != 0xFFFFFFFFu && s.valid[row[i]] == 0) {
-							pos[p - 1][i] = 0xFFFFFFFFu; // NULL never matches
-						}
+						key[p - 1][i] = c.sel[c.unit_begin + key[p - 1][i]];
 					}
-				}
+				});
+				__builtin_amdgcn_s_waitcnt(0x0F70); // vmcnt(0): the one wait, here and not load by load further down
+			} else {
+				flat_static_for<1, K>([&](auto P) {
+					constexpr int p = decltype(P)::value;
+#pragma unroll
+					for (int i = 0; i < F; i++) {
+						key[p - 1][i] += (uint32_t)c.unit_begin;
+					}
+				});
 			}
-		});
+			flat_static_for<1, K>([&](auto P) {
+				constexpr int p = decltype(P)::value;
+				const bool live = p < (int)c.k;
+				const POLR_GLOBAL uint32_t *keys = live ? c.st[p].keys : c.st[0].keys;
+				const bool has_valid = live && c.st[p].valid != nullptr;
+				const POLR_GLOBAL uint8_t *vbytes = has_valid ? c.st[p].valid : (const POLR_GLOBAL uint8_t *)keys;
+				const uint32_t vmask = has_valid ? 0xFFFFFFFFu : 0u;
+#pragma unroll
+				for (int i = 0; i < F; i++) {
+					const uint32_t row = key[p - 1][i];
+					vb[p - 1][i] = vbytes[row & vmask];
+					key[p - 1][i] = keys[row];
+				}
+			});
+			asm volatile("; polr-sweep-sel-keys-end" ::: "memory");
+			flat_static_for<1, K>([&](auto P) {
+				constexpr int p = decltype(P)::value;
+				// (every byte is looked at, with or without validity column: a load nobody waits for would be waited for at
+				// the next sweep's first register write -- with the source's prefetch, which that wait would force home)
+				const uint32_t no_valid = p < (int)c.k && c.st[p].valid != nullptr ? 0u : 1u;
+#pragma unroll
+				for (int i = 0; i < F; i++) {
+					pos[p - 1][i] = (vb[p - 1][i] | no_valid) != 0 ? pos[p - 1][i] : FLAT_INACTIVE; // NULL never matches
+				}
+			});
+		}
+		flat_static_for<1, K>([&](auto P) { flat_await<F>(key[decltype(P)::value - 1]); });
+		asm volatile("; polr-sweep-tables-begin" ::: "memory");
 		flat_static_for<1, K>([&](auto P) {
 			constexpr int p = decltype(P)::value;
 			if (p < (int)c.k && (c.st[p].kind_lds & 0xFFu) == KIND_PERFECT) {
 				const FlatStage &s = c.st[p];
 				const uint32_t lds_off1 = s.kind_lds >> 8;
-				bool in[F];
+				uint32_t at[F];
 #pragma unroll
 				for (int i = 0; i < F; i++) {
 					const uint32_t idx = key[p - 1][i] - s.a;
-					in[i] = pos[p - 1][i] != 0xFFFFFFFFu && idx <= s.b;
-					key[p - 1][i] = idx; // (the bit to test is idx & 31, taken when the word is there)
-					w[p - 1][i] = 0;
+					const bool in = pos[p - 1][i] != FLAT_INACTIVE && idx <= s.b;
+					// (the bit to test rides in the position's upper half: two registers per tuple wait for the word, not three)
+					pos[p - 1][i] = in ? pos[p - 1][i] | ((idx & 31u) << 16) : FLAT_INACTIVE;
+					at[i] = (idx < s.b ? idx : s.b) >> 5; // (out of range: the table's last word, for nothing)
 				}
 				// (one address space per stage, wave-uniform: DS_READ or GLOBAL_LOAD, never a generic access)
 				if (lds_off1) {
 					const POLR_LDS uint32_t *bits = c.lds_tables + (lds_off1 - 1u);
 #pragma unroll
 					for (int i = 0; i < F; i++) {
-						if (in[i]) {
-							w[p - 1][i] = bits[key[p - 1][i] >> 5];
-						}
+						key[p - 1][i] = bits[at[i]];
 					}
 				} else {
 #pragma unroll
 					for (int i = 0; i < F; i++) {
-						if (in[i]) {
-							w[p - 1][i] = s.table[key[p - 1][i] >> 5];
-						}
+						key[p - 1][i] = s.table[at[i]];
 					}
-				}
-#pragma unroll
-				for (int i = 0; i < F; i++) {
-					key[p - 1][i] &= 31u;
 				}
 			}
 		});
+		asm volatile("; polr-sweep-tables-end" ::: "memory");
 		flat_static_for<1, K>([&](auto P) {
 			constexpr int p = decltype(P)::value;
 			if (p < (int)c.k && (c.st[p].kind_lds & 0xFFu) != KIND_PERFECT) {
 				bool act[F], hit[F];
 #pragma unroll
 				for (int i = 0; i < F; i++) {
-					act[i] = pos[p - 1][i] != 0xFFFFFFFFu;
+					act[i] = pos[p - 1][i] != FLAT_INACTIVE;
 				}
 				flat_hash_lookup<F>(c.st[p], key[p - 1], act, hit);
 #pragma unroll
 				for (int i = 0; i < F; i++) {
-					w[p - 1][i] = hit[i] ? 1u : 0u;
-					key[p - 1][i] = 0;
+					key[p - 1][i] = hit[i] ? 1u : 0u; // (bit 0: the position's upper half is 0)
 				}
 			}
 		});
@@ -562,12 +657,25 @@ __device__ __forceinline__ void flat_sweep(FlatCtx<K> &c) {
 				bool hit[F];
 #pragma unroll
 				for (int i = 0; i < F; i++) {
-					hit[i] = (w[p - 1][i] >> key[p - 1][i]) & 1u;
+					hit[i] = pos[p - 1][i] != FLAT_INACTIVE && ((key[p - 1][i] >> ((pos[p - 1][i] >> 16) & 31u)) & 1u) != 0;
+					pos[p - 1][i] &= 0xFFFFu;
 				}
 				flat_emit<K, p, F>(c, pos[p - 1], hit);
 			}
 		});
 	}
+}
+
+// whether a sweep takes its straight path: no selection vector, and no deeper stage of the current join order reads a
+// validity column (set when the join order changes)
+template <int K>
+__device__ __forceinline__ void flat_set_plain(FlatCtx<K> &c) {
+	bool plain = c.sel == nullptr;
+#pragma unroll
+	for (int p = 1; p < K; p++) {
+		plain = plain && !(p < (int)c.k && c.st[p].valid != nullptr);
+	}
+	c.plain = plain;
 }
 
 // One unit [in_pos, in_end) in two phases, so that the caller can look for its next unit in between:

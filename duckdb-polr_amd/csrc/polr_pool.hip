@@ -111,6 +111,7 @@ __global__ __launch_bounds__(1024) void polr_pool_flat_kernel(const DevPipeline 
 	c.k = k;
 	c.lane = threadIdx.x & 63;
 	c.sel = as_global(uniptr(pipe->sel));
+	c.plain = false; // (set with the first join order)
 	c.lds_tables = as_lds((const uint32_t *)lds);
 	c.q = as_lds((uint16_t *)(lds + table_dwords + (size_t)wave_in_block * lds_per_wave));
 #pragma unroll
@@ -150,6 +151,7 @@ __global__ __launch_bounds__(1024) void polr_pool_flat_kernel(const DevPipeline 
 					c.st[p] = flat_load_stage(stages + (uint64_t)u.path * POLR_KMAX + p, uni(pipe->paths[u.path].order[p]));
 				}
 			}
+			flat_set_plain<K>(c);
 			cur_path = u.path;
 		}
 #if POLR_FLAT_EMIT
