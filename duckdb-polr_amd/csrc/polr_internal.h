@@ -59,8 +59,11 @@ struct OwnedCol {
 	uint32_t flags = 0;
 	bool strings_rebased = false; // string cells point into a device heap (set_string_heaps): a second upload is refused
 	DevBuf<uint8_t> own_data, own_valid;
+	// cells the library uploaded that polr_ht_filter compacted into the table's one allocation: the owners are empty, but
+	// the column still counts as the library's own for the heap-never-came guards (a long cell's pointer may be the host's)
+	bool lib_cells = false;
 	bool owned() const {
-		return own_data.get() != nullptr;
+		return own_data.get() != nullptr || lib_cells;
 	}
 	hipError_t alloc_data(uint64_t bytes) {
 		const hipError_t e = own_data.alloc(bytes);
@@ -112,6 +115,10 @@ struct polr_ht {
 	// a table made by polr_ht_from_output: the cells and validity arrays of all its columns in one allocation -- keys and
 	// payload are views of it (their own owners are empty, as for a caller's POLR_COL_DEVICE memory)
 	DevBuf<uint8_t> col_mem;
+	// polr_ht_filter ran: col_mem holds the kept rows of every column and, behind them, the uploaded row number of every
+	// build row (filter_rows, n_rows_in entries: polr_ht_fetch_filter_rows) and the copy descriptors
+	bool filtered = false;
+	uint32_t *filter_rows = nullptr;
 	std::vector<DictCol> dicts; // dictionaries of the code columns (polr_ht_encode_dictionary), cells owned
 	uint32_t is_dense = 0, has_null = 0;
 	uint64_t device_bytes = 0;

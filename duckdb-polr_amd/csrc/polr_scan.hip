@@ -40,6 +40,7 @@
 #include <vector>
 
 #include "polr_filter_plan.h"
+#include "polr_fx_device.h" // int_cmp_holds, DevFxProg, fx_row_true
 #include "polr_internal.h"
 #include "polr_like.h"
 #include "polr_strcmp.h"
@@ -152,26 +153,6 @@ __device__ __forceinline__ bool lip_contains(const DevLip &f, uint64_t row) {
 
 #define PACK_SHIFT 40 // low 40 bits: tuples, high 24: non-empty vectors
 #define PACK_MASK ((1ull << PACK_SHIFT) - 1)
-
-// value OP constant on integers: the six comparisons of a ConstantFilter, in the column's signedness
-__device__ __forceinline__ bool int_cmp_holds(uint64_t v, int64_t constant, uint32_t op, bool is_signed) {
-	if (is_signed) {
-		const int64_t a = (int64_t)v, c = constant;
-		return op == POLR_CMP_EQ   ? a == c
-		       : op == POLR_CMP_NE ? a != c
-		       : op == POLR_CMP_LT ? a < c
-		       : op == POLR_CMP_GT ? a > c
-		       : op == POLR_CMP_LE ? a <= c
-		                           : a >= c;
-	}
-	const uint64_t c = (uint64_t)constant; // (host: constant >= 0 for unsigned columns)
-	return op == POLR_CMP_EQ   ? v == c
-	       : op == POLR_CMP_NE ? v != c
-	       : op == POLR_CMP_LT ? v < c
-	       : op == POLR_CMP_GT ? v > c
-	       : op == POLR_CMP_LE ? v <= c
-	                           : v >= c;
-}
 
 __device__ __forceinline__ bool row_passes_filters(const DevFilterSet &fs, uint64_t row) {
 	bool ok = true;
@@ -358,113 +339,8 @@ __global__ __launch_bounds__(1024) void polr_tscan_apply_kernel(unsigned long lo
 }
 
 // ---- expression filters (polr_pipeline_scan_filter_expr): what the reference evaluates in a PhysicalFilter behind the scan
-// -- OR / NOT trees, IN lists, LIKE -- as a postfix program (lowered by polr_filter_plan.h).  The program is wave-uniform: the
-// nodes travel in the kernel argument, leaves / values / segments / constant bytes in one buffer of the pipeline read at
-// uniform addresses; only the evaluation of a leaf is per lane.  A row first evaluates the leaves column by column -- the cell
-// of a column is loaded once, a NULL row's cell never -- into one bit per leaf and one NULL bit per column, then walks the
-// nodes over an operand stack of two 32-bit words per lane (true bits, NULL bits; a NULL's true bit is 0).
-struct DevFxCol {
-	const uint8_t *data;
-	const uint8_t *valid;
-	uint32_t width, is_signed;
-	uint32_t first_leaf, n_leaves;
-	uint32_t needs_cell, pad;
-};
-struct DevFxProg {
-	DevFxCol col[POLR_FX_MAX_COLS];
-	uint32_t nodes[POLR_MAX_FILTER_NODES];
-	const PolrFxLeaf *leaves;
-	const PolrFxValue *values;
-	const polr_like_seg *segs;
-	const uint8_t *bytes;
-	uint32_t n_cols, n_nodes;
-};
-
-// does the integer v compare (op) with one of the leaf's constants?  (CMP: one constant; IN: op is EQ)
-__device__ __forceinline__ bool fx_leaf_int(const DevFxProg &px, const PolrFxLeaf lf, uint64_t v, bool is_signed) {
-	bool r = false;
-	for (uint32_t i = lf.first_value; i < lf.first_value + lf.n_values; i++) {
-		r = r || int_cmp_holds(v, px.values[i].constant, lf.op, is_signed);
-	}
-	return r;
-}
-
-__device__ __forceinline__ bool fx_leaf_str(const DevFxProg &px, const PolrFxLeaf lf, const uint4 cell) {
-	if (lf.kind == POLR_FX_LIKE) {
-		return polr_like_match(cell.x, cell.y, cell.z, cell.w, px.values[lf.first_value].pat, px.segs, px.bytes);
-	}
-	bool r = false;
-	for (uint32_t i = lf.first_value; i < lf.first_value + lf.n_values && !r; i++) {
-		const polr_str_const c = px.values[i].c;
-		if (lf.op == POLR_CMP_EQ && c.len != cell.x) {
-			continue; // (equal strings have equal lengths: most IN members end here)
-		}
-		r = polr_str_cmp_holds(polr_str_cmp3(cell.x, cell.y, cell.z, cell.w, c, px.bytes + px.values[i].bytes_off + 12u), lf.op);
-	}
-	return r;
-}
-
-// is the root TRUE for the row?
-__device__ __forceinline__ bool fx_row_true(const DevFxProg &px, uint64_t row) {
-	unsigned long long leaf_true = 0;
-	uint32_t col_null = 0;
-	for (uint32_t c = 0; c < px.n_cols; c++) {
-		const DevFxCol &col = px.col[c];
-		const bool valid = !(col.valid && !as_global(col.valid)[row]);
-		col_null |= valid ? 0u : 1u << c;
-		uint4 cell = make_uint4(0, 0, 0, 0);
-		uint64_t v = 0;
-		if (valid && col.needs_cell) {
-			if (col.width == 16) {
-				cell = load_global_x4(as_global((const uint32_t *)col.data) + row * 4);
-			} else {
-				v = load_cell(as_global(col.data) + row * col.width, col.width, col.is_signed != 0);
-			}
-		}
-		for (uint32_t l = col.first_leaf; l < col.first_leaf + col.n_leaves; l++) {
-			const PolrFxLeaf lf = px.leaves[l];
-			bool t;
-			if (lf.kind == POLR_FX_CMP && lf.op >= POLR_CMP_IS_NULL) {
-				t = (lf.op == POLR_CMP_IS_NULL) != valid;
-			} else if (!valid) {
-				t = false; // NULL: the node takes the column's NULL bit
-			} else if (col.width == 16) {
-				t = fx_leaf_str(px, lf, cell);
-			} else {
-				t = fx_leaf_int(px, lf, v, col.is_signed != 0);
-			}
-			leaf_true |= (unsigned long long)t << l;
-		}
-	}
-	uint32_t T = 0, N = 0; // the operand stack: bit 0 is the top
-	for (uint32_t i = 0; i < px.n_nodes; i++) {
-		const uint32_t nd = px.nodes[i];
-		const uint32_t kind = nd & 0xFFu;
-		if (kind <= POLR_FX_LIKE) {
-			const uint32_t n = (nd & POLR_FX_NEVER_NULL) ? 0u : (col_null >> ((nd >> 16) & 0xFFu)) & 1u;
-			const uint32_t t = (uint32_t)(leaf_true >> ((nd >> 8) & 0xFFu)) & 1u & ~n;
-			T = (T << 1) | t;
-			N = (N << 1) | n;
-		} else if (kind == POLR_FX_NOT) {
-			T ^= ~N & 1u; // NOT NULL = NULL
-		} else {
-			const uint32_t ta = (T >> 1) & 1u, tb = T & 1u, na = (N >> 1) & 1u, nb = N & 1u;
-			uint32_t rt, rn;
-			if (kind == POLR_FX_AND) {
-				const uint32_t rf = (~(ta | na) | ~(tb | nb)) & 1u; // one side FALSE: FALSE, whatever the other is
-				rt = ta & tb;
-				rn = (na | nb) & ~rf;
-			} else {
-				rt = ta | tb; // one side TRUE: TRUE
-				rn = (na | nb) & ~rt;
-			}
-			T = ((T >> 2) << 1) | rt;
-			N = ((N >> 2) << 1) | rn;
-		}
-	}
-	return px.n_nodes == 0 || (T & 1u);
-}
-
+// -- OR / NOT trees, IN lists, LIKE -- as a postfix program (lowered by polr_filter_plan.h).  The evaluator, fx_row_true, and
+// the program's device form stand in polr_fx_device.h: the filter of a build side (polr_htfilter.hip) runs the same one.
 __global__ __launch_bounds__(256) void polr_tscan_count_expr_kernel(DevFxProg px, DevLipSet lip, uint64_t n_rows, uint32_t V,
                                                                    uint64_t n_vec, unsigned long long *__restrict__ packed,
                                                                    unsigned long long *__restrict__ pass_bits) {
@@ -892,43 +768,14 @@ static int scan_filter_expr_run(polr_pipeline *p, void *stream, const polr_filte
 			}
 		}
 	}
-	// the program buffer: values | leaves | segments | bytes (8 spare bytes behind: never empty)
-	const size_t values_at = 0, leaves_at = values_at + pl.values.size() * sizeof(PolrFxValue);
-	const size_t segs_at = leaves_at + pl.n_leaves * sizeof(PolrFxLeaf), bytes_at = segs_at + pl.segs.size() * sizeof(polr_like_seg);
-	std::vector<uint8_t> blob(bytes_at + pl.bytes.size() + 8, 0);
-	if (!pl.values.empty()) {
-		memcpy(blob.data() + values_at, pl.values.data(), pl.values.size() * sizeof(PolrFxValue));
-	}
-	memcpy(blob.data() + leaves_at, pl.leaves, pl.n_leaves * sizeof(PolrFxLeaf));
-	if (!pl.segs.empty()) {
-		memcpy(blob.data() + segs_at, pl.segs.data(), pl.segs.size() * sizeof(polr_like_seg));
-	}
-	if (!pl.bytes.empty()) {
-		memcpy(blob.data() + bytes_at, pl.bytes.data(), pl.bytes.size());
-	}
-	HIPCHK(ctx, p->scan_expr_prog.ensure(std::max<size_t>(blob.size(), 8192)));
+	// the program buffer (polr_fx_device.h lays it out)
+	PolrFxBlob blob;
+	polr_fx_blob_make(pl, blob);
+	HIPCHK(ctx, p->scan_expr_prog.ensure(std::max<size_t>(blob.bytes.size(), 8192)));
 	// (no scan kernel is in flight: every scan call ends with a synchronisation of its stream)
-	HIPCHK(ctx, hipMemcpy(p->scan_expr_prog, blob.data(), blob.size(), hipMemcpyHostToDevice));
+	HIPCHK(ctx, hipMemcpy(p->scan_expr_prog, blob.bytes.data(), blob.bytes.size(), hipMemcpyHostToDevice));
 	DevFxProg px;
-	memset(&px, 0, sizeof(px));
-	px.n_cols = pl.n_cols;
-	px.n_nodes = pl.n_nodes;
-	memcpy(px.nodes, pl.nodes, sizeof(uint32_t) * pl.n_nodes);
-	for (uint32_t g = 0; g < pl.n_cols; g++) {
-		const OwnedCol &c = p->probe_cols[pl.cols[g].col];
-		DevFxCol &d = px.col[g];
-		d.data = c.data;
-		d.valid = c.valid;
-		d.width = c.width;
-		d.is_signed = c.flags & 1u;
-		d.first_leaf = pl.cols[g].first_leaf;
-		d.n_leaves = pl.cols[g].n_leaves;
-		d.needs_cell = pl.cols[g].needs_cell;
-	}
-	px.values = (const PolrFxValue *)(p->scan_expr_prog + values_at);
-	px.leaves = (const PolrFxLeaf *)(p->scan_expr_prog + leaves_at);
-	px.segs = (const polr_like_seg *)(p->scan_expr_prog + segs_at);
-	px.bytes = p->scan_expr_prog + bytes_at;
+	polr_fx_prog_make(pl, blob, p->scan_expr_prog.get(), [&](uint32_t c) -> const OwnedCol & { return p->probe_cols[c]; }, px);
 	return scan_run(p, st, vector_size, lip, n_selected, n_chunks,
 	                [&](uint32_t grid, const DevLipSet &l, uint64_t n_rows, uint64_t n_vec, unsigned long long *packed, unsigned long long *bits) {
 		                hipLaunchKernelGGL(polr_tscan_count_expr_kernel, dim3(grid), dim3(256), 0, st, px, l, n_rows, vector_size, n_vec,

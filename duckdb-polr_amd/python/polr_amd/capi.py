@@ -49,6 +49,7 @@ EXPORTS = [
     "polr_out_materialize_strings",
     "polr_mpx_pool_info",
     "polr_ht_from_output",
+    "polr_ht_filter", "polr_ht_fetch_filter_rows",
 ]
 
 
@@ -177,6 +178,22 @@ def flatten_filter_expr(expr):
     if expr is not None:
         walk(expr)
     return nodes, values
+
+
+def _filter_arrays(nodes, values):
+    """nodes = [(kind, col, op, first_value, n_values)], values = [(constant, bytes or None, str_len)] -> the
+    polr_filter_node and polr_filter_value arrays, and the buffers that keep the values' bytes alive"""
+    na, va, keep = (FilterNode * max(len(nodes), 1))(), (FilterValue * max(len(values), 1))(), []
+    for i, (kind, col, op, first, n) in enumerate(nodes):
+        na[i].kind, na[i].col, na[i].op = FX[kind] if isinstance(kind, str) else kind, col, CMP[op] if isinstance(op, str) else op
+        na[i].first_value, na[i].n_values = first, n
+    for i, (const, b, blen) in enumerate(values):
+        va[i].constant, va[i].str_len = int(const or 0), blen
+        if b is not None:
+            buf = C.create_string_buffer(bytes(b), max(len(b), 1))
+            keep.append(buf)
+            va[i].str = C.addressof(buf)
+    return na, va, keep
 
 
 class OutColRef(C.Structure):
@@ -345,6 +362,8 @@ def load():
     L.polr_ht_upload_rows.argtypes = [vp, vp, u64, u32, vp, vp, vp, u32, u32, P(vp)]
     L.polr_ht_upload_columns.argtypes = [vp, P(Col), u32, P(Col), u32, u64, P(vp)]
     L.polr_ht_from_output.argtypes = [vp, vp, P(OutColRef), u32, P(OutColRef), u32, P(vp)]
+    L.polr_ht_filter.argtypes = [vp, vp, P(FilterNode), u32, P(FilterValue), u32, P(u64)]
+    L.polr_ht_fetch_filter_rows.argtypes = [vp, vp, vp, u64]
     L.polr_ht_finalize_hash.argtypes = [vp, vp]
     L.polr_ht_finalize_perfect.argtypes = [vp, i64, i64, vp]
     L.polr_pht_upload.argtypes = [vp, u32, u32, i64, i64, vp, P(Col), u32, P(vp)]
@@ -564,6 +583,31 @@ class HashTable:
         ctx.check(ctx.L.polr_ht_from_output(out.h, stream, _out_col_refs(keys), len(keys), _out_col_refs(payload), len(payload),
                                             C.byref(h)))
         return cls(ctx, h)
+
+    def filter(self, expr, stream=None):
+        """polr_ht_filter (before encode_dictionary and finalize): keep the rows for which `expr` is TRUE and compact the
+        table on the device -> the kept count.  expr: the nested tuples of Pipeline.scan_filter_expr; its columns number the
+        table's, keys first, then payload.  None keeps every row.  Build row r is afterwards the r-th kept row:
+        filter_rows() maps build ids back to the rows as uploaded."""
+        nodes, values = flatten_filter_expr(expr)
+        return self.filter_raw(nodes, values, stream)
+
+    def filter_raw(self, nodes, values, stream=None, n_nodes=None, n_values=None):
+        """polr_ht_filter with the struct fields as given (Pipeline.scan_filter_expr_raw) -> the kept count"""
+        na, va, keep = _filter_arrays(nodes, values)
+        kept = C.c_uint64()
+        self.ctx.check(self.ctx.L.polr_ht_filter(self.h, stream, na if nodes else None, len(nodes) if n_nodes is None else n_nodes,
+                                                 va if values else None, len(values) if n_values is None else n_values,
+                                                 C.byref(kept)))
+        self._n_kept = kept.value
+        return kept.value
+
+    def filter_rows(self, stream=None):
+        """polr_ht_fetch_filter_rows: the uploaded row number of every build row of a filtered table, ascending"""
+        n = getattr(self, "_n_kept", 0)  # (not filtered through this object: the call refuses)
+        rows = np.zeros((max(n, 1),), dtype=np.uint32)
+        self.ctx.check(self.ctx.L.polr_ht_fetch_filter_rows(self.h, stream, rows.ctypes.data, n))
+        return rows[:n]
 
     def set_key_flags(self, key_col, flags):
         """polr_ht_set_key_flags (before finalize): KEY_BY_VALUE = the probe side may read another integer type (a CAST'ed
@@ -830,16 +874,7 @@ class Pipeline:
         """polr_pipeline_scan_filter_expr with the struct fields as given: nodes = [(kind, col, op, first_value,
         n_values)], values = [(constant, bytes or None, str_len)]; n_nodes / n_values: the counts to pass, when they are
         not the lists' lengths -- the edges of the contract"""
-        na, va, keep = (FilterNode * max(len(nodes), 1))(), (FilterValue * max(len(values), 1))(), []
-        for i, (kind, col, op, first, n) in enumerate(nodes):
-            na[i].kind, na[i].col, na[i].op = FX[kind] if isinstance(kind, str) else kind, col, CMP[op] if isinstance(op, str) else op
-            na[i].first_value, na[i].n_values = first, n
-        for i, (const, b, blen) in enumerate(values):
-            va[i].constant, va[i].str_len = int(const or 0), blen
-            if b is not None:
-                buf = C.create_string_buffer(bytes(b), max(len(b), 1))
-                keep.append(buf)
-                va[i].str = C.addressof(buf)
+        na, va, keep = _filter_arrays(nodes, values)
         ns, nc = C.c_uint64(), C.c_uint64()
         self.ctx.check(self.ctx.L.polr_pipeline_scan_filter_expr(
             self.h, stream, na if nodes else None, len(nodes) if n_nodes is None else n_nodes, va if values else None,

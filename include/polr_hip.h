@@ -174,6 +174,48 @@ typedef struct polr_out_col_ref {
 } polr_out_col_ref;
 int polr_ht_from_output(polr_out *o, void *stream, const polr_out_col_ref *keys, uint32_t n_keys,
                         const polr_out_col_ref *payload, uint32_t n_payload, polr_ht **out);
+/* Filter the rows of an UN-FINALIZED table and compact it, on the device: the filtered dimension scan in front of
+ * PhysicalHashJoin::Sink (physical_hash_join.cpp:217-286) -- the PhysicalFilter, or the TableFilterSet pushed into the scan,
+ * that nearly every build pipeline of SSB and JOB carries (c_region = 'AMERICA', k.keyword LIKE '%sequel%').  Call it after
+ * the upload and before polr_ht_encode_dictionary[_ex] and polr_ht_finalize_*: the perfect range, the hash capacity and the
+ * dictionary codes are then those of the surviving rows.
+ * Program: exactly a polr_pipeline_scan_filter_expr program (below) -- postfix nodes[] / values[] under SQL three-valued
+ * logic, CMP incl. IS [NOT] NULL, IN, LIKE, NOT / AND / OR; a row is kept iff the root is TRUE; n_nodes == 0 keeps every
+ * row.  nodes[i].col numbers the table's columns as polr_ht_upload_rows does, keys first, then payload: col < n_keys is key
+ * column col, otherwise payload column col - n_keys.  The limits are those of the scan call (POLR_MAX_FILTER_*, 8 distinct
+ * columns, no NUL in a pattern) and every refusal of that call's program check passes through with its message behind
+ * "filter expression: ".  A CMP, IN or LIKE leaf on a NULL row is NULL and the row's cell is never read.
+ * Tables: any un-finalized table -- from polr_ht_upload_columns (host or POLR_COL_DEVICE columns), polr_ht_upload_rows or
+ * polr_ht_from_output.  POLR_E_INVALID, checked in this order before anything is enqueued: NULL ht; a finalized table (also
+ * polr_pht_upload, polr_ht_alloc_like); a table with a dictionary-encoded column (filter first, then encode); a table
+ * filtered before (once per table); then the program's refusals, `col` beyond the table's columns among them.  n_kept may
+ * be NULL.
+ * Result: the table holds exactly the kept rows, in ascending order of the rows as uploaded: build row r is now the r-th
+ * kept row, and every build id reported later indexes polr_ht_fetch_filter_rows, which returns the uploaded row number of
+ * every build row (dst_rows >= the kept count, else POLR_E_OVERFLOW; POLR_E_INVALID on a table that was never filtered).
+ * Like the dictionary strings the row list stays with the table that was filtered: polr_ht_export / polr_ht_alloc_like /
+ * polr_bcast_build do not carry it.  Widths, POLR_COL_SIGNED, key flags and the payload count are unchanged; a column has
+ * a validity array afterwards iff it had one before; the cell of a kept NULL row is zero (its source is not read), a kept
+ * valid cell is copied bit for bit.
+ * VARCHAR columns: cells are copied as they are and keep pointing into the heap the table already owns (or, for
+ * POLR_COL_DEVICE cells, into the caller's HBM).  polr_ht_set_payload_heaps may come before or after the call for a column no
+ * leaf reads; afterwards it checks and rebases the kept cells only.  A column some CMP / IN / LIKE leaf reads needs its
+ * heap first: a column the library uploaded whose heap never came and that holds a non-NULL cell longer than 12 bytes is
+ * POLR_E_INVALID, from a pass over the length words before a kernel that follows a pointer is enqueued.
+ * Ownership: after the call the table owns the cells and validity arrays of ALL its columns in ONE allocation (with the row
+ * list); a caller's POLR_COL_DEVICE buffers are never written and no longer referenced -- except that the VARCHAR cells of
+ * such a column still point into the caller's heap, which must outlive the table.  The buffers the table owned before are
+ * freed before the call returns; polr_ht_info::device_bytes and polr_device_bytes_live() account for the new state.  A
+ * refused or failed call leaves the table, its columns and the live byte count exactly as they were.
+ * Stream: as polr_ht_encode_dictionary -- the call waits for the context's stream and returns when the table is complete
+ * (it needs the kept count on the host once, between its counting and its compaction pass).
+ * Not provided: filtering a finalized table; repacking the string heaps (the bytes of dropped rows stay); composing several
+ * filter calls on one table; LIP on build sides; shipping the row list through polr_bcast_build; pipelines of zero joins. */
+struct polr_filter_node; /* (defined with polr_pipeline_scan_filter_expr, below) */
+struct polr_filter_value;
+int polr_ht_filter(polr_ht *ht, void *stream, const struct polr_filter_node *nodes, uint32_t n_nodes,
+                   const struct polr_filter_value *values, uint32_t n_values, uint64_t *n_kept);
+int polr_ht_fetch_filter_rows(polr_ht *ht, void *stream, uint32_t *dst, uint64_t dst_rows);
 /* Key semantics beyond "same type on both sides, NULL never matches": the reference multiplexes INNER hash joins whose
  * left side is CAST(column) (src/parallel/polar_config.cpp:75-82) and whose comparison is IS NOT DISTINCT FROM
  * (JoinHashTable::null_values_are_equal, src/execution/join_hashtable.cpp:35-36,170-192,642).  Per key column, BEFORE the
