@@ -778,6 +778,22 @@ static PipePlanJoin plan_join(const polr_join_desc &jd) {
 	return t;
 }
 
+// the joins and join orders of a request as the plan sees them: everything of a PipePlanInput but the probe side
+// (polr_pipeline_create below; polr_pipeline_from_output, polr_pipesrc.hip)
+void polr_pipeline_plan_joins(polr_ctx *ctx, const polr_join_desc *joins, uint32_t k, const int32_t *paths, uint32_t n_paths,
+                              PipePlanInput &in) {
+	in.joins.clear();
+	in.joins.reserve(k <= POLR_MAX_JOINS ? k : 0);
+	in.device = ctx->device;
+	in.k = k;
+	in.n_paths = n_paths;
+	for (uint32_t j = 0; j < k && k <= POLR_MAX_JOINS; j++) { // (any other k is refused before a join is looked at)
+		in.joins.push_back(plan_join(joins[j]));
+	}
+	in.paths = paths;
+	in.flat_wave_bytes = polr_pool_flat_wave_bytes(k);
+}
+
 // resolve every (join order, position) of a pipeline variant into a StageDesc (see polr_device.h)
 // ext: extension records of the stages that need one (appended; StageDesc::ext holds the INDEX + 1 until the records
 // have their device address, see polr_pipeline_create)
@@ -868,19 +884,11 @@ int polr_pipeline_create(polr_ctx *ctx, const polr_col *probe_cols, uint32_t n_p
 	*out = nullptr;
 	PipePlanInput in;
 	in.probe_cols.reserve(n_probe_cols);
-	in.joins.reserve(k <= POLR_MAX_JOINS ? k : 0);
 	for (uint32_t i = 0; i < n_probe_cols; i++) {
 		in.probe_cols.push_back(PipeCol {probe_cols[i].width, probe_cols[i].flags & POLR_COL_SIGNED});
 	}
 	in.n_probe_rows = n_probe_rows;
-	in.device = ctx->device;
-	in.k = k;
-	in.n_paths = n_paths;
-	for (uint32_t j = 0; j < k && k <= POLR_MAX_JOINS; j++) { // (any other k is refused before a join is looked at)
-		in.joins.push_back(plan_join(joins[j]));
-	}
-	in.paths = paths;
-	in.flat_wave_bytes = polr_pool_flat_wave_bytes(k);
+	polr_pipeline_plan_joins(ctx, joins, k, paths, n_paths, in);
 	PipePlan plan;
 	if (polr_pipeline_plan(in, plan)) {
 		POLR_FAIL(ctx, plan.code, "%s", plan.msg);

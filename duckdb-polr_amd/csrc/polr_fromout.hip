@@ -25,6 +25,10 @@
 // first kernel write into the table.  The cells and validity arrays of ALL columns and the gather's descriptors share one
 // allocation (polr_ht::col_mem; the plan places them), and the string passes share one scratch allocation: nothing but
 // that scratch is freed inside the call.
+//
+// The device part -- measuring the VARCHAR columns, the gather launch, the string write passes -- is shared with
+// polr_pipeline_from_output (polr_pipesrc.hip), whose columns become the probe side of a new pipeline instead of a table:
+// polr_fromout_measure / polr_fromout_fill below, declared in polr_fromout_gather.h.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <string.h>
@@ -32,8 +36,7 @@
 #include <memory>
 #include <vector>
 
-#include "polr_fromout_plan.h"
-#include "polr_internal.h"
+#include "polr_fromout_gather.h"
 
 #define POLR_CONST __attribute__((address_space(4)))
 
@@ -127,7 +130,7 @@ __global__ __launch_bounds__(256) void polr_fromout_gather_kernel(DevOut out, co
 	}
 }
 
-static PolrFromoutColumn fromout_shape(const OutCol &c) {
+PolrFromoutColumn polr_fromout_shape(const OutCol &c) {
 	PolrFromoutColumn s;
 	s.resolved = 1;
 	s.slot = c.slot;
@@ -137,6 +140,65 @@ static PolrFromoutColumn fromout_shape(const OutCol &c) {
 	s.owned = c.col->owned();
 	s.rebased = c.col->strings_rebased;
 	return s;
+}
+
+int polr_fromout_measure(polr_out *o, hipStream_t st, const PolrFromoutPlan &plan, const OutCol *src, uint64_t n, uint32_t nc,
+                         FromoutStrings &fs) {
+	polr_ctx *ctx = o->ctx;
+	const size_t ns = plan.strings.size();
+	const uint64_t cw = 2ull * nc; // chunk_words, per column: [nc] byte totals, [nc] their exclusive prefix
+	fs.h_tails.assign(2 * ns, 0);
+	if (!ns || !n) {
+		return POLR_OK;
+	}
+	HIPCHK(ctx, fs.scratch.alloc(plan.row_off_words + plan.chunk_words + plan.tail_words));
+	fs.row_off = fs.scratch.get();
+	fs.chunk_words = fs.row_off + plan.row_off_words;
+	fs.tails = fs.chunk_words + plan.chunk_words;
+	HIPCHK(ctx, hipMemsetAsync(fs.tails, 0, plan.tail_words * 8, st));
+	for (size_t s = 0; s < ns; s++) {
+		uint64_t *chunk_bytes = fs.chunk_words + s * cw, *chunk_heap_base = chunk_bytes + nc, *tail = fs.tails + 2 * s;
+		polr_launch_strout_measure(st, o, plan.strings[s].slot, src[plan.strings[s].col].dev, fs.row_off + s * n, chunk_bytes,
+		                           (unsigned long long *)(tail + 1));
+		polr_launch_chunk_prefix(st, (const uint64_t *)chunk_bytes, nc, chunk_heap_base, tail);
+	}
+	HIPCHK(ctx, hipMemcpyAsync(fs.h_tails.data(), fs.tails, plan.tail_words * 8, hipMemcpyDeviceToHost, st));
+	HIPCHK(ctx, hipStreamSynchronize(st));
+	return POLR_OK;
+}
+
+int polr_fromout_fill(polr_out *o, hipStream_t st, const PolrFromoutPlan &plan, const OutCol *src, uint64_t n, uint32_t nc,
+                      const FromoutStrings &fs, uint8_t *mem, const std::vector<DevBuf<uint8_t>> &heaps,
+                      std::vector<PolrFromoutDesc> &h_desc) {
+	polr_ctx *ctx = o->ctx;
+	if (!n) {
+		return POLR_OK;
+	}
+	h_desc.resize(plan.fixed.size());
+	FromoutCol *desc = (FromoutCol *)(mem + plan.desc_off);
+	for (size_t i = 0; i < plan.fixed.size(); i++) {
+		const uint32_t c = plan.fixed[i].col;
+		h_desc[i] = FromoutCol{src[c].dev.data, src[c].dev.valid, mem + plan.data_off[c], mem + plan.valid_off[c], plan.fixed[i].width,
+		                       plan.fixed[i].slot};
+	}
+	if (!h_desc.empty()) {
+		HIPCHK(ctx, hipMemcpyAsync(desc, h_desc.data(), h_desc.size() * sizeof(FromoutCol), hipMemcpyHostToDevice, st));
+		FromoutGroups groups = {};
+		for (uint32_t g = 0; g <= plan.n_slots; g++) {
+			groups.first[g] = plan.group_first[g];
+		}
+		hipLaunchKernelGGL(polr_fromout_gather_kernel, dim3(nc, plan.n_slots), dim3(polr_strout_block(o)), 0, st, o->dev,
+		                   o->chunk_base.get(), nc, desc, groups);
+	}
+	const uint64_t cw = 2ull * nc;
+	for (size_t s = 0; s < plan.strings.size(); s++) {
+		const uint32_t c = plan.strings[s].col;
+		const uint64_t *chunk_heap_base = fs.chunk_words + s * cw + nc;
+		uint8_t *heap = heaps[s].get();
+		polr_launch_strout_write(st, o, plan.strings[s].slot, src[c].dev, fs.row_off + s * n, chunk_heap_base,
+		                         (uint4 *)(mem + plan.data_off[c]), mem + plan.valid_off[c], heap, (uint64_t)heap);
+	}
+	return POLR_OK;
 }
 
 extern "C" int polr_ht_from_output(polr_out *o, void *stream, const polr_out_col_ref *keys, uint32_t n_keys,
@@ -171,7 +233,7 @@ extern "C" int polr_ht_from_output(polr_out *o, void *stream, const polr_out_col
 		const bool is_key = c < n_keys;
 		const polr_out_col_ref &r = is_key ? keys[c] : payload[c - n_keys];
 		POLR_TRY(polr_out_col(p, r.src_join, r.src_col, &src[c], is_key ? "key" : "payload column", is_key ? c : c - n_keys));
-		shapes[c] = fromout_shape(src[c]);
+		shapes[c] = polr_fromout_shape(src[c]);
 	}
 	HIPCHK(ctx, hipSetDevice(ctx->device));
 	hipStream_t st = polr_stream(ctx, stream);
@@ -186,30 +248,13 @@ extern "C" int polr_ht_from_output(polr_out *o, void *stream, const polr_out_col
 	}
 	// VARCHAR columns: measure all of them, read back once, decide the guard
 	const size_t ns = plan.strings.size();
-	const uint64_t cw = 2ull * nc; // chunk_words, per column: [nc] byte totals, [nc] their exclusive prefix
-	DevBuf<uint64_t> scratch; // one allocation: row offsets, chunk words, tails (per column: the heap bytes, the long cells)
-	uint64_t *row_off = nullptr, *chunk_words = nullptr, *tails = nullptr;
-	std::vector<uint64_t> h_tails(2 * ns, 0);
-	if (ns && n) {
-		HIPCHK(ctx, scratch.alloc(plan.row_off_words + plan.chunk_words + plan.tail_words));
-		row_off = scratch.get();
-		chunk_words = row_off + plan.row_off_words;
-		tails = chunk_words + plan.chunk_words;
-		HIPCHK(ctx, hipMemsetAsync(tails, 0, plan.tail_words * 8, st));
-		for (size_t s = 0; s < ns; s++) {
-			uint64_t *chunk_bytes = chunk_words + s * cw, *chunk_heap_base = chunk_bytes + nc, *tail = tails + 2 * s;
-			polr_launch_strout_measure(st, o, plan.strings[s].slot, src[plan.strings[s].col].dev, row_off + s * n, chunk_bytes,
-			                           (unsigned long long *)(tail + 1));
-			polr_launch_chunk_prefix(st, (const uint64_t *)chunk_bytes, nc, chunk_heap_base, tail);
-		}
-		HIPCHK(ctx, hipMemcpyAsync(h_tails.data(), tails, plan.tail_words * 8, hipMemcpyDeviceToHost, st));
-		HIPCHK(ctx, hipStreamSynchronize(st));
-		for (size_t s = 0; s < ns; s++) {
-			const uint64_t n_long = h_tails[2 * s + 1];
-			if (n_long && plan.strings[s].needs_heap_guard) {
-				// (the library's own upload, never rebased onto a device heap: the pointers of its long cells are the host's)
-				POLR_FAIL_HEAP_NEVER_CAME(ctx, "payload column", plan.strings[s].col - n_keys, n_long);
-			}
+	FromoutStrings fs;
+	POLR_TRY(polr_fromout_measure(o, st, plan, src.data(), n, nc, fs));
+	for (size_t s = 0; s < ns; s++) {
+		const uint64_t n_long = fs.h_tails[2 * s + 1];
+		if (n_long && plan.strings[s].needs_heap_guard) {
+			// (the library's own upload, never rebased onto a device heap: the pointers of its long cells are the host's)
+			POLR_FAIL_HEAP_NEVER_CAME(ctx, "payload column", plan.strings[s].col - n_keys, n_long);
 		}
 	}
 	// the table and everything it owns, before the first kernel that writes into it
@@ -226,7 +271,7 @@ extern "C" int polr_ht_from_output(polr_out *o, void *stream, const polr_out_col
 	ht->heaps.reserve(ns);
 	for (size_t s = 0; s < ns; s++) {
 		DevBuf<uint8_t> heap;
-		HIPCHK(ctx, heap.alloc(h_tails[2 * s]));
+		HIPCHK(ctx, heap.alloc(fs.h_tails[2 * s]));
 		ht->device_bytes += heap.bytes();
 		ht->heaps.push_back(std::move(heap));
 		ht->payload[plan.strings[s].col - n_keys].strings_rebased = true;
@@ -238,33 +283,10 @@ extern "C" int polr_ht_from_output(polr_out *o, void *stream, const polr_out_col
 	}
 	HIPCHK(ctx, ht->keys_dev.alloc(n_keys));
 	ht->device_bytes += ht->keys_dev.bytes();
-	std::vector<FromoutCol> h_desc(plan.fixed.size());
-	FromoutCol *desc = (FromoutCol *)(ht->col_mem.get() + plan.desc_off);
-	for (size_t i = 0; i < plan.fixed.size(); i++) {
-		const uint32_t c = plan.fixed[i].col;
-		const OwnedCol &col = c < n_keys ? ht->keys[c] : ht->payload[c - n_keys];
-		h_desc[i] = FromoutCol{src[c].dev.data, src[c].dev.valid, col.data, col.valid, plan.fixed[i].width, plan.fixed[i].slot};
-	}
 	// fill it
+	std::vector<FromoutCol> h_desc;
 	HIPCHK(ctx, hipMemcpyAsync(ht->keys_dev.get(), h_keys.data(), n_keys * sizeof(DevCol), hipMemcpyHostToDevice, st));
-	if (n) {
-		if (!h_desc.empty()) {
-			HIPCHK(ctx, hipMemcpyAsync(desc, h_desc.data(), h_desc.size() * sizeof(FromoutCol), hipMemcpyHostToDevice, st));
-			FromoutGroups groups = {};
-			for (uint32_t g = 0; g <= plan.n_slots; g++) {
-				groups.first[g] = plan.group_first[g];
-			}
-			hipLaunchKernelGGL(polr_fromout_gather_kernel, dim3(nc, plan.n_slots), dim3(polr_strout_block(o)), 0, st, o->dev,
-			                   o->chunk_base.get(), nc, desc, groups);
-		}
-		for (size_t s = 0; s < ns; s++) {
-			const uint64_t *chunk_heap_base = chunk_words + s * cw + nc;
-			OwnedCol &col = ht->payload[plan.strings[s].col - n_keys];
-			uint8_t *heap = ht->heaps[s].get();
-			polr_launch_strout_write(st, o, plan.strings[s].slot, src[plan.strings[s].col].dev, row_off + s * n, chunk_heap_base,
-			                         (uint4 *)col.data, col.valid, heap, (uint64_t)heap);
-		}
-	}
+	POLR_TRY(polr_fromout_fill(o, st, plan, src.data(), n, nc, fs, ht->col_mem.get(), ht->heaps, h_desc));
 	HIPCHK(ctx, hipStreamSynchronize(st)); // (the table is complete; the staged descriptors and the scratch are locals)
 	*out = ht.release();
 	return POLR_OK;

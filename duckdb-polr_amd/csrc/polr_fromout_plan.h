@@ -108,14 +108,57 @@ static inline int polr_fromout_check(const PolrFromoutRequest &rq, PolrFromoutPl
 	return POLR_OK;
 }
 
-// cols[n_keys + n_payload]: the keys, then the payload -> POLR_OK, or POLR_E_* with pl.err set
-static inline int polr_fromout_plan(const PolrFromoutRequest &rq, const PolrFromoutColumn *cols, PolrFromoutPlan &pl) {
+static inline void polr_fromout_clear(PolrFromoutPlan &pl) {
 	pl.fixed.clear();
 	pl.strings.clear();
 	pl.data_off.clear();
 	pl.valid_off.clear();
 	pl.n_slots = 0;
 	pl.table_bytes = pl.desc_off = pl.row_off_words = pl.chunk_words = pl.tail_words = 0;
+}
+
+// The layout alone, for n_cols columns whose widths are cell widths (1, 2, 4, 8, 16) and fewer than 2^32 rows: fixed[] by
+// slot and the slot groups, strings[], every column's place in the one allocation, the descriptors behind them, the scratch
+// of the string passes.  Shared by polr_fromout_plan() below and by polr_pipeline_from_output (polr_pipesrc_plan.h), whose
+// columns are all of one kind.
+static inline int polr_fromout_layout(uint64_t n_rows, uint64_t n_chunks, const PolrFromoutColumn *cols, uint32_t n_cols,
+                                      PolrFromoutPlan &pl) {
+	pl.data_off.resize(n_cols);
+	pl.valid_off.resize(n_cols);
+	uint64_t at = 0; // (at most 66 columns of fewer than 2^32 rows and 17 bytes a row: far from 2^64)
+	for (uint32_t c = 0; c < n_cols; c++) {
+		pl.data_off[c] = at;
+		at += (n_rows * cols[c].width + POLR_FROMOUT_ALIGN - 1) / POLR_FROMOUT_ALIGN * POLR_FROMOUT_ALIGN;
+		pl.valid_off[c] = at;
+		at += (n_rows + POLR_FROMOUT_ALIGN - 1) / POLR_FROMOUT_ALIGN * POLR_FROMOUT_ALIGN;
+		if (cols[c].width == 16) {
+			pl.strings.push_back(PolrFromoutString{c, cols[c].slot, cols[c].owned && !cols[c].rebased ? 1u : 0u});
+		} else {
+			pl.fixed.push_back(PolrFromoutFixed{c, cols[c].slot, cols[c].width});
+		}
+	}
+	std::stable_sort(pl.fixed.begin(), pl.fixed.end(),
+	                 [](const PolrFromoutFixed &a, const PolrFromoutFixed &b) { return a.slot < b.slot; });
+	for (size_t i = 0; i < pl.fixed.size(); i++) {
+		if (i == 0 || pl.fixed[i].slot != pl.fixed[i - 1].slot) {
+			if (pl.n_slots == POLR_FROMOUT_MAX_SLOTS) {
+				POLR_FO_REFUSE(POLR_E_INVALID, "columns from more than %u slots of row ids", POLR_FROMOUT_MAX_SLOTS);
+			}
+			pl.group_first[pl.n_slots++] = (uint32_t)i;
+		}
+	}
+	pl.group_first[pl.n_slots] = (uint32_t)pl.fixed.size();
+	pl.desc_off = at;
+	pl.table_bytes = polr_fromout_alloc_bytes(at + pl.fixed.size() * sizeof(PolrFromoutDesc));
+	pl.row_off_words = (uint64_t)pl.strings.size() * n_rows;
+	pl.chunk_words = (uint64_t)pl.strings.size() * 2ull * n_chunks;
+	pl.tail_words = (uint64_t)pl.strings.size() * 2ull;
+	return POLR_OK;
+}
+
+// cols[n_keys + n_payload]: the keys, then the payload -> POLR_OK, or POLR_E_* with pl.err set
+static inline int polr_fromout_plan(const PolrFromoutRequest &rq, const PolrFromoutColumn *cols, PolrFromoutPlan &pl) {
+	polr_fromout_clear(pl);
 	const int rc = polr_fromout_check(rq, pl);
 	if (rc) {
 		return rc;
@@ -139,35 +182,5 @@ static inline int polr_fromout_plan(const PolrFromoutRequest &rq, const PolrFrom
 	if (rq.n_rows >= POLR_FROMOUT_MAX_ROWS) {
 		POLR_FO_REFUSE(POLR_E_UNSUPPORTED, "build side of %llu rows exceeds the 32-bit row-id space", (unsigned long long)rq.n_rows);
 	}
-	pl.data_off.resize(n_cols);
-	pl.valid_off.resize(n_cols);
-	uint64_t at = 0; // (at most 66 columns of fewer than 2^32 rows and 17 bytes a row: far from 2^64)
-	for (uint32_t c = 0; c < n_cols; c++) {
-		pl.data_off[c] = at;
-		at += (rq.n_rows * cols[c].width + POLR_FROMOUT_ALIGN - 1) / POLR_FROMOUT_ALIGN * POLR_FROMOUT_ALIGN;
-		pl.valid_off[c] = at;
-		at += (rq.n_rows + POLR_FROMOUT_ALIGN - 1) / POLR_FROMOUT_ALIGN * POLR_FROMOUT_ALIGN;
-		if (cols[c].width == 16) {
-			pl.strings.push_back(PolrFromoutString{c, cols[c].slot, cols[c].owned && !cols[c].rebased ? 1u : 0u});
-		} else {
-			pl.fixed.push_back(PolrFromoutFixed{c, cols[c].slot, cols[c].width});
-		}
-	}
-	std::stable_sort(pl.fixed.begin(), pl.fixed.end(),
-	                 [](const PolrFromoutFixed &a, const PolrFromoutFixed &b) { return a.slot < b.slot; });
-	for (size_t i = 0; i < pl.fixed.size(); i++) {
-		if (i == 0 || pl.fixed[i].slot != pl.fixed[i - 1].slot) {
-			if (pl.n_slots == POLR_FROMOUT_MAX_SLOTS) {
-				POLR_FO_REFUSE(POLR_E_INVALID, "columns from more than %u slots of row ids", POLR_FROMOUT_MAX_SLOTS);
-			}
-			pl.group_first[pl.n_slots++] = (uint32_t)i;
-		}
-	}
-	pl.group_first[pl.n_slots] = (uint32_t)pl.fixed.size();
-	pl.desc_off = at;
-	pl.table_bytes = polr_fromout_alloc_bytes(at + pl.fixed.size() * sizeof(PolrFromoutDesc));
-	pl.row_off_words = (uint64_t)pl.strings.size() * rq.n_rows;
-	pl.chunk_words = (uint64_t)pl.strings.size() * 2ull * rq.n_chunks;
-	pl.tail_words = (uint64_t)pl.strings.size() * 2ull;
-	return POLR_OK;
+	return polr_fromout_layout(rq.n_rows, rq.n_chunks, cols, n_cols, pl);
 }

@@ -132,6 +132,9 @@ struct polr_pipeline {
 	std::vector<OwnedCol> probe_cols;
 	std::vector<DevBuf<uint8_t>> heaps; // string heaps of VARCHAR probe columns (polr_pipeline_set_probe_heap), owned
 	DevBuf<DevCol> probe_cols_dev;
+	// a pipeline made by polr_pipeline_from_output: the cells and validity arrays of all its probe columns in one allocation
+	// -- probe_cols are views of it (their own owners are empty, lib_cells is set)
+	DevBuf<uint8_t> col_mem;
 	uint32_t *sel_dev = nullptr; // the selection in use: a view of sel_upload, of scan_sel, or of the caller's device memory
 	DevBuf<uint32_t> sel_upload; // a selection uploaded from the host (polr_pipeline_set_selection)
 	// result of polr_pipeline_scan_filter: boundaries of the (non-empty) source chunks in selection positions
@@ -387,6 +390,10 @@ void polr_launch_strout_measure(hipStream_t st, const polr_out *o, uint32_t slot
 void polr_launch_strout_write(hipStream_t st, const polr_out *o, uint32_t slot, DevCol src, const uint64_t *row_off,
                               const uint64_t *chunk_heap_base, uint4 *dst_cells, uint8_t *dst_valid, uint8_t *heap_dev,
                               uint64_t heap_addr);
+
+// the joins and join orders of a pipeline request described to polr_pipeline_plan() (polr_capi.hip)
+extern "C" void polr_pipeline_plan_joins(polr_ctx *ctx, const polr_join_desc *joins, uint32_t k, const int32_t *paths,
+                                         uint32_t n_paths, PipePlanInput &in);
 
 // shared between capi and mpx
 int polr_plan_launch(polr_pipeline *p, bool materialize, uint64_t total_tuples, uint32_t *unit_size,

@@ -50,6 +50,7 @@ EXPORTS = [
     "polr_mpx_pool_info",
     "polr_ht_from_output",
     "polr_ht_filter", "polr_ht_fetch_filter_rows",
+    "polr_pipeline_from_output",
 ]
 
 
@@ -363,6 +364,7 @@ def load():
     L.polr_ht_upload_columns.argtypes = [vp, P(Col), u32, P(Col), u32, u64, P(vp)]
     L.polr_ht_from_output.argtypes = [vp, vp, P(OutColRef), u32, P(OutColRef), u32, P(vp)]
     L.polr_ht_filter.argtypes = [vp, vp, P(FilterNode), u32, P(FilterValue), u32, P(u64)]
+    L.polr_pipeline_from_output.argtypes = [vp, vp, P(OutColRef), u32, P(JoinDesc), u32, vp, u32, P(vp)]
     L.polr_ht_fetch_filter_rows.argtypes = [vp, vp, vp, u64]
     L.polr_ht_finalize_hash.argtypes = [vp, vp]
     L.polr_ht_finalize_perfect.argtypes = [vp, i64, i64, vp]
@@ -771,8 +773,20 @@ class Pipeline:
         pv = probe_valid or [None] * len(probe_cols)
         pc = [c if isinstance(c, Col) else _np_col(c, v) for c, v in zip(probe_cols, pv)]
         self.k = len(joins)
-        jd = (JoinDesc * self.k)()
         self._hts = [j[0] for j in joins]
+        jd = self._join_descs(joins)
+        paths = np.ascontiguousarray(np.asarray(paths, dtype=np.int32).reshape(-1, self.k))
+        self.n_paths = len(paths)
+        h = C.c_void_p()
+        ctx.check(ctx.L.polr_pipeline_create(ctx.h, _col_array(pc), len(pc), n_probe_rows, jd, self.k,
+                                             paths.ctypes.data, self.n_paths, C.byref(h)))
+        self.h = h
+        self.scan = (0, 0)  # (n_selected, n_chunks) of the last scan_filter: what fetch_scan sizes its arrays by
+
+    @staticmethod
+    def _join_descs(joins):
+        """[(HashTable, [(src_join, src_col)])] -> polr_join_desc array"""
+        jd = (JoinDesc * max(len(joins), 1))()
         for i, (ht, key_src) in enumerate(joins):
             jd[i].ht = ht.h
             jd[i].n_keys = len(key_src)
@@ -788,13 +802,30 @@ class Pipeline:
                 jd[i].pred_src_join[c] = sj
                 jd[i].pred_src_col[c] = sc
                 jd[i].pred_build_col[c] = bc
-        paths = np.ascontiguousarray(np.asarray(paths, dtype=np.int32).reshape(-1, self.k))
+        return jd
+
+    @classmethod
+    def from_output(cls, out, cols, joins, paths, stream=None):
+        """polr_pipeline_from_output: the rows of Output `out` as the source of a new pipeline, gathered on the device.
+        cols: [(src_join, src_col)] as the sinks take them (-1 = probe table) -- cols[i] becomes probe column i; joins and
+        paths as for Pipeline().  Probe row r of the new pipeline is output row r of `out` (the order of fetch_ids), so slot 0
+        of its outputs indexes out.fetch_ids().  The pipeline owns its columns: `out`, its pipeline and that pipeline's
+        tables may be closed afterwards."""
+        ctx = out.ctx
+        self = cls.__new__(cls)
+        self.ctx = ctx
+        cols, joins = list(cols), list(joins)
+        self.k = len(joins)
+        self._hts = [j[0] for j in joins]
+        paths = np.ascontiguousarray(np.asarray(paths, dtype=np.int32).reshape(-1, max(self.k, 1)))
         self.n_paths = len(paths)
+        self.h = None
         h = C.c_void_p()
-        ctx.check(ctx.L.polr_pipeline_create(ctx.h, _col_array(pc), len(pc), n_probe_rows, jd, self.k,
-                                             paths.ctypes.data, self.n_paths, C.byref(h)))
+        ctx.check(ctx.L.polr_pipeline_from_output(out.h, stream, _out_col_refs(cols), len(cols), cls._join_descs(joins), self.k,
+                                                  paths.ctypes.data, self.n_paths, C.byref(h)))
         self.h = h
-        self.scan = (0, 0)  # (n_selected, n_chunks) of the last scan_filter: what fetch_scan sizes its arrays by
+        self.scan = (0, 0)
+        return self
 
     def set_probe_heap(self, probe_col, heap):
         """polr_pipeline_set_probe_heap: the string heap the cells of probe column `probe_col` point into"""

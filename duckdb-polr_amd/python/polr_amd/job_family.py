@@ -17,6 +17,10 @@ the query's join graph --
   * tables are synthetic at the IMDB cardinalities: dense ids, foreign keys power-law distributed over the parent's
     ids, filters thinned to a selectivity that depends only on the kinds of predicates the query puts on the table.
 
+A query of more than 8 joins keeps all its tables in the CHAINED plan (chained_plan, run_chain_device): the same
+breadth-first order cut into stages of at most 8 joins, the rows a stage emits being the source of the next
+(polr_pipeline_from_output).  workload() and what bench.py runs are unchanged: the first eight joins.
+
 Every pipeline is independent (own tables, own multiplexers): whole queries are dealt round-robin to the GPUs
 (polr_amd.dist.shard_queries), nothing is exchanged.
 """
@@ -147,9 +151,11 @@ def _find(parent, x):
     return x
 
 
-def pipeline_shape(q):
+def pipeline_shape(q, max_joins=MAX_JOINS):
     """the multiplexed pipeline of one query shape: probe alias, its columns, and the ordered joins
-    [(alias, build key column, key source ('probe', column) | (join index, column))]"""
+    [(alias, build key column, key source ('probe', column) | (join index, column))]; max_joins=None: every table of
+    the query, in the same breadth-first order (chained_plan cuts that order into pipelines)"""
+    max_joins = len(q["tables"]) if max_joins is None else max_joins
     tables, joins = q["tables"], q["joins"]
     cols = sorted({(a, c) for j in joins for a, c in (tuple(j[0]), tuple(j[1]))})
     parent = {x: x for x in cols}
@@ -164,7 +170,7 @@ def pipeline_shape(q):
     placed = {probe: -1}
     order = []
     frontier = True
-    while frontier and len(order) < MAX_JOINS:
+    while frontier and len(order) < max_joins:
         frontier = False
         cands = []
         for cl in classes.values():
@@ -178,7 +184,7 @@ def pipeline_shape(q):
                 cands.append((0 if src[0] == probe else 1, placed[src[0]], b[0], b[1], src))
         seen = set()
         for pri, _p, alias, bcol, src in sorted(cands):
-            if alias in seen or alias in placed or len(order) >= MAX_JOINS:
+            if alias in seen or alias in placed or len(order) >= max_joins:
                 continue
             seen.add(alias)
             order.append((alias, bcol, src))
@@ -298,3 +304,194 @@ def _reference_form(probe, probe_cols, flt, order, joins, select=(), probe_strin
         out["query_select"] = sql.replace("SELECT COUNT(*)", "SELECT " + ", ".join(
             "MIN(%s)" % cname(aliases[1 + sj], c) for sj, c in select))
     return out
+
+
+# ---- chained plan: a query of more than MAX_JOINS joins as several pipelines --------------------------------------------------
+def chained_plan(q, max_joins=MAX_JOINS):
+    """The whole query as STAGES of at most max_joins joins each, in the family's breadth-first order: stage 0 probes the
+    query's largest table, the rows a stage emits are the source of the next (polr_pipeline_from_output), so every table of
+    the query is joined.  Each stage is multiplexed on its own.  ->
+      {"probe": alias, "order": [(alias, build key column, (source alias, column))] over all joins, "select": [(alias, col)],
+       "stages": [{"joins":   indices into order,
+                   "source":  [(alias, column, "int" | "str")] the stage's probe-side columns -- columns of the probe table
+                              for stage 0, the columns carried out of the previous stage otherwise,
+                   "key_src": per join (-1, source column index) or (local join index, payload column index),
+                   "payload": per join [(column, "int" | "str")] the build columns it carries,
+                   "carry":   [(-1 | local join index, column index)] the columns handed to the next stage, in the order of
+                              its "source"; for the last stage the select-list columns}],
+       "final": [(alias, column, "str")] what the last stage's "carry" names: the select list, each column once, sorted}
+    Carried are the key columns of later stages (probe columns or build columns of earlier joins) and the select-list
+    columns ("str": VARCHAR).  A query of at most max_joins joins is one stage whose joins and keys are pipeline_shape's."""
+    probe, order = pipeline_shape(q, None)
+    select = [(a, c) for a, c in q.get("select", []) if a == probe or any(a == o[0] for o in order)]
+    stage_of = {probe: -1}
+    for i, (alias, _b, _s) in enumerate(order):
+        stage_of[alias] = i // max_joins
+    n_stages = max((len(order) + max_joins - 1) // max_joins, 1)
+    # what is read of every alias, and by the stage that reads it last: keys (int) and select-list columns (str, read "after" the last stage)
+    needs = {}
+    for i, (_alias, _b, src) in enumerate(order):
+        needs.setdefault((src[0], src[1], "int"), []).append(i // max_joins)
+    for a, c in select:
+        needs.setdefault((a, c, "str"), []).append(n_stages)
+    stages = []
+    source = sorted(x for x in needs if x[0] == probe)
+    for s in range(n_stages):
+        idx = list(range(s * max_joins, min((s + 1) * max_joins, len(order))))
+        local = {order[i][0]: j for j, i in enumerate(idx)}
+        payload = [sorted((c, kd) for (a, c, kd), users in needs.items() if a == order[i][0] and max(users) >= s) for i in idx]
+        key_src = []
+        for i in idx:
+            a, c = order[i][2]
+            key_src.append((-1, source.index((a, c, "int"))) if stage_of[a] < s else (local[a], payload[local[a]].index((c, "int"))))
+        nxt = sorted(x for x, users in needs.items() if stage_of[x[0]] <= s and max(users) > s)
+        carry = [(-1, source.index(x)) if stage_of[x[0]] < s else (local[x[0]], payload[local[x[0]]].index((x[1], x[2]))) for x in nxt]
+        stages.append({"joins": idx, "source": source, "key_src": key_src, "payload": payload, "carry": carry})
+        source = nxt
+    return {"probe": probe, "order": order, "select": select, "stages": stages, "final": source}
+
+
+def chain_data(plan, tables, q, sel_floor=0.0):
+    """the tables of a chained plan over the synthetic instance: the probe table's columns and filter selection, and per
+    join the rows its filters keep, its key and the columns it carries -- exactly as workload() thins them.  sel_floor: no
+    table's filters keep less than this fraction of its rows -- for reduced instances, where the product of a dozen
+    selectivities over tables of a thousand rows would leave no row at all"""
+    probe = plan["probe"]
+    ptable = q["tables"][probe]
+    n_probe = tables.rows(ptable)
+    psel = max(selectivity(ptable, n_probe, q["filters"].get(probe, [])), sel_floor)
+    sel = None
+    if psel < 1.0:
+        f = (_mix32(np.arange(n_probe, dtype=np.int64), 17) * 1000).astype(np.int32)
+        sel = np.nonzero(f < max(int(round(psel * 1000)), 1))[0].astype(np.uint32)
+    src0 = []
+    for a, c, kd in plan["stages"][0]["source"]:
+        src0.append(tables.column(ptable, c) if kd == "int" else tables.strings(ptable, c))
+    joins = []
+    for st in plan["stages"]:
+        for i, pay in zip(st["joins"], st["payload"]):
+            alias, bcol, _src = plan["order"][i]
+            t = q["tables"][alias]
+            n = tables.rows(t)
+            s = max(selectivity(t, n, q["filters"].get(alias, [])), sel_floor)
+            keep = np.ones(n, dtype=bool) if s >= 1.0 else (_mix32(np.arange(n, dtype=np.int64), _salt(alias)) < s)
+            if not keep.any():
+                keep[0] = True
+            rows = np.nonzero(keep)[0]
+            joins.append({"alias": alias, "table": t, "kept_rows": rows, "key": tables.column(t, bcol)[keep],
+                          "payload": [tables.column(t, c)[keep] if kd == "int" else tables.strings(t, c, rows=rows) for c, kd in pay]})
+    return {"n_probe": n_probe, "sel": sel, "source": src0, "joins": joins}
+
+
+def run_chain_host(plan, data, run_stage):
+    """the stages one by one on the host: run_stage(int source columns, [(build key, [int payload columns], (src_join,
+    src_col))], selection or None) -> (rows [n_out, 1 + k]: source row and the build row of every join, intermediates) runs one
+    pipeline (the tests pass the oracle); the carried columns are gathered in numpy between the stages ->
+    {"count": COUNT(*), "mins": the select list's MINs in the order of plan["final"] (bytes, None without a row),
+     "int_mins": MIN of every integer source column of the last stage -- the carried keys -- over the result rows,
+     "intermediates": per stage, "stage_rows": output rows per stage}"""
+    source = [np.asarray(c, dtype=object) if isinstance(c, list) else c for c in data["source"]]
+    sel = data["sel"]
+    inter, stage_rows = [], []
+    for st in plan["stages"]:
+        kinds = [kd for _a, _c, kd in st["source"]]
+        int_at = [i for i, kd in enumerate(kinds) if kd == "int"]  # the pipeline sees the integer columns only
+        int_pay = [[x for x, (_n, kd) in enumerate(pay) if kd == "int"] for pay in st["payload"]]
+        joins = []
+        for j, i in enumerate(st["joins"]):
+            d = data["joins"][i]
+            sj, sc = st["key_src"][j]
+            joins.append((d["key"], [d["payload"][x] for x in int_pay[j]],
+                          (-1, int_at.index(sc)) if sj < 0 else (sj, int_pay[sj].index(sc))))
+        rows, n_inter = run_stage([source[i] for i in int_at], joins, sel)
+        inter.append(int(n_inter))
+        stage_rows.append(len(rows))
+        nxt = []
+        for sj, sc in st["carry"]:
+            if sj < 0:
+                nxt.append(source[sc][rows[:, 0]])
+            else:
+                col = data["joins"][st["joins"][sj]]["payload"][sc]
+                col = np.asarray(col, dtype=object) if isinstance(col, list) else col
+                nxt.append(col[rows[:, 1 + sj]])
+        if st is plan["stages"][-1]:
+            int_mins = [int(source[i][rows[:, 0]].min()) if len(rows) else None for i in int_at]
+        source, sel = nxt, None
+    mins = [min(c.tolist()) if len(c) else None for c in source]
+    return {"count": stage_rows[-1], "mins": mins, "int_mins": int_mins, "intermediates": inter, "stage_rows": stage_rows}
+
+
+def run_chain_device(ctx, plan, data, chunk_capacity=1024):
+    """the stages on the device: stage 0 is an ordinary pipeline over the probe table, every later stage is
+    Pipeline.from_output of the stage before it over its carried columns; the select list's MINs come from the string sink of
+    the last stage's output.  Each stage runs its first join order over all its tuples (polr_probe_rounds): once counting,
+    which sizes the output, once emitting.  -> as run_chain_host, plus "flat": polr_pipeline_launch_info per stage"""
+    from . import capi
+    out = pipe = None
+    hts = []
+    keep = []
+    n_tuples = len(data["sel"]) if data["sel"] is not None else data["n_probe"]
+    inter, stage_rows, flat = [], [], []
+    for s, st in enumerate(plan["stages"]):
+        joins = []
+        for j, i in enumerate(st["joins"]):
+            d = data["joins"][i]
+            cols, heaps = [], {}
+            for x, (c, (_n, kd)) in enumerate(zip(d["payload"], st["payload"][j])):
+                if kd == "str":
+                    cells, heap = capi.string_cells(c)
+                    keep.append((cells, heap))
+                    heaps[x] = heap
+                    c = cells
+                cols.append(c)
+            ht = capi.HashTable.from_columns(ctx, [d["key"]], cols)
+            for x, heap in heaps.items():
+                ht.set_payload_heap(x, heap)
+            ht.finalize_auto(int(d["key"].min()), int(d["key"].max()))
+            joins.append((ht, [st["key_src"][j]]))
+        k = len(joins)
+        paths = [list(range(k))]
+        if s == 0:
+            cols, heaps = [], {}
+            for x, c in enumerate(data["source"]):
+                if isinstance(c, list):
+                    cells, heap = capi.string_cells(c)
+                    keep.append((cells, heap))
+                    heaps[x] = heap
+                    c = cells
+                cols.append(c)
+            new = capi.Pipeline(ctx, cols, data["n_probe"], joins, paths)
+            for x, heap in heaps.items():
+                new.set_probe_heap(x, heap)
+            if data["sel"] is not None:
+                new.set_selection(data["sel"])
+        else:
+            new = capi.Pipeline.from_output(out, plan["stages"][s - 1]["carry"], joins, paths)
+            # the stage before it is done with: the new pipeline owns its source
+            out.close()
+            pipe.close()
+            for h in hts:
+                h.close()
+        pipe, hts = new, [h for h, _ in joins]
+        flat.append(pipe.launch_info()["flat"])
+        n_out = n_inter = 0
+        if n_tuples:
+            counts = pipe.probe_rounds([(0, n_tuples, 0, 0)])
+            n_out, n_inter = int(counts[0][k - 1]), int(counts.sum())
+        out = capi.Output(pipe, chunk_capacity, n_out // chunk_capacity + 1 + 8192)  # (a partly filled chunk per emitting wave)
+        if n_tuples:
+            pipe.probe_rounds([(0, n_tuples, 0, 1)], out=out)
+        if out.stats()[0] != n_out:
+            raise RuntimeError("stage %d: %d rows emitted, %d counted" % (s, out.stats()[0], n_out))
+        inter.append(n_inter)
+        stage_rows.append(n_out)
+        n_tuples = n_out
+    mins = [out.aggregate_string("min", sj, sc) if n_tuples else None for sj, sc in plan["stages"][-1]["carry"]]
+    ints = [("min", -1, i) for i, (_a, _c, kd) in enumerate(plan["stages"][-1]["source"]) if kd == "int"]
+    int_mins = out.aggregate(ints) if n_tuples and ints else [None] * len(ints)
+    out.close()
+    pipe.close()
+    for h in hts:
+        h.close()
+    return {"count": stage_rows[-1], "mins": mins, "int_mins": int_mins, "intermediates": inter, "stage_rows": stage_rows,
+            "flat": flat}

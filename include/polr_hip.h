@@ -316,6 +316,57 @@ typedef struct polr_join_desc {
 int polr_pipeline_create(polr_ctx *ctx, const polr_col *probe_cols, uint32_t n_probe_cols, uint64_t n_probe_rows,
                          const polr_join_desc *joins, uint32_t k, const int32_t *paths /* n_paths x k */,
                          uint32_t n_paths, polr_pipeline **out);
+/* A pipeline whose SOURCE is the output of another pipeline, gathered on the device: the probe-side hand-over between two
+ * pipelines of one query.  A pipeline holds at most POLR_MAX_JOINS joins; the reference runs a longer query as several
+ * pipelines, the rows one emits being the source of the next.  `o` is an output a materialising run has filled; cols[i] names
+ * a column of its pipeline as polr_ht_from_output does, and becomes PROBE COLUMN i of the new pipeline.  joins, k, paths and
+ * n_paths are exactly polr_pipeline_create's: key_src_join = -1 (and pred_src_join = -1) now names a gathered column.
+ * Rows and row ids: the new pipeline has ONE PROBE ROW PER OUTPUT ROW of `o`, in the order of polr_out_fetch_ids /
+ * polr_out_materialize (chunk-major, partially filled chunks included).  Probe row r of the new pipeline is output row r of
+ * `o`; so slot 0 of any output of the new pipeline indexes polr_out_fetch_ids(o), whose slots in turn name the probe row and
+ * the build rows of the first pipeline: row ids compose across the cut through that one array, and through nothing else.
+ * Columns: column i has the width and the POLR_COL_SIGNED flag of its source; every column gets a validity array gathered
+ * from its source's (all rows valid where the source has none); the cell of a NULL row is zero and the source cell of a NULL
+ * row is never read; the same source column may be named more than once.  At most 66 columns.
+ * VARCHAR columns (width 16): the cells are normalised exactly as polr_out_materialize_strings normalises them (inline
+ * strings zero-padded, NULL rows all-zero) and the long strings' bytes go into a packed heap THE NEW PIPELINE OWNS, one per
+ * such column; the column counts as rebased, so a later polr_pipeline_set_probe_heaps on it is refused.  A source column
+ * the library uploaded whose heap never came is POLR_E_INVALID once a long non-NULL cell is among the output rows (decided by
+ * the measuring pass, before any pointer is followed).
+ * Ownership: when the call returns the new pipeline shares nothing with `o`, with o's pipeline, with that pipeline's tables or
+ * with a caller's POLR_COL_DEVICE memory -- all of those may be destroyed.  It borrows the tables named in `joins`, as every
+ * pipeline does.  All cells, all validity arrays and the gather's descriptors are ONE allocation; polr_device_bytes_live()
+ * accounts for every byte.
+ * Afterwards the pipeline is an ordinary one: polr_pipeline_set_selection, the four scan-filter calls (also over columns that
+ * came from different tables of the first pipeline), LIP, polr_pipeline_update_probe, polr_out_create, every run kind, every
+ * sink, polr_ht_from_output and polr_pipeline_from_output of its outputs.
+ * Refusals -- nothing is enqueued beyond the output's own statistics, *out = NULL, polr_device_bytes_live() as before --
+ * checked in this order:
+ *   1. POLR_E_INVALID      NULL o, out, cols, joins or paths
+ *   2. POLR_E_INVALID      n_cols == 0
+ *   3. POLR_E_UNSUPPORTED  more than 66 columns
+ *   4. POLR_E_INVALID      an output with a fused GROUP BY sink (it holds group cells, no row ids)
+ *   5. POLR_E_INVALID      a column reference out of range (the first one, in the order of cols)
+ *   6. POLR_E_UNSUPPORTED  an output of 2^32 - 16 rows or more (the bound of polr_pipeline_create)
+ *   7. every refusal of polr_pipeline_create over the gathered columns, with its own code and message: k outside
+ *      1..POLR_MAX_JOINS (nine joins), n_paths outside 1..POLR_MAX_PATHS, a table that is not finalized, a path that is no
+ *      permutation or probes a join before the one that provides its key, a key or condition column out of range or of the
+ *      wrong width, ...
+ * (the heap-never-came refusal comes after these and after the measuring passes; it too leaves *out = NULL and the live
+ * bytes as before).
+ * An output with no rows, or one no materialising run has filled, behaves exactly as polr_pipeline_create with
+ * n_probe_rows = 0: a valid pipeline of zero probe rows and zero tuples, planned and launched like any other (the same
+ * polr_pipeline_launch_info); there is no row to select, probe or emit, and polr_pipeline_update_probe of a single row is
+ * refused as it is there.
+ * Stream: the gather runs on `stream` (NULL: the context's); the call returns when the pipeline is complete (it needs the row
+ * count on the host, and with a VARCHAR column the heap totals).
+ * Not provided: sinks that address columns of an EARLIER pipeline through composed row ids -- select-list columns are carried
+ * forward as columns instead, and a fan-out join copies a string once per output row, as polr_out_materialize_strings does;
+ * zero-copy probe columns (views of the first pipeline's tables); more than POLR_MAX_JOINS joins in one pipeline; routing
+ * across a cut (each pipeline is multiplexed on its own). */
+int polr_pipeline_from_output(polr_out *o, void *stream, const polr_out_col_ref *cols, uint32_t n_cols,
+                              const polr_join_desc *joins, uint32_t k, const int32_t *paths /* n_paths x k */,
+                              uint32_t n_paths, polr_pipeline **out);
 /* The tuples entering the multiplexer, in scan order, when an upstream filter thinned the source
  * chunks (DICTIONARY/sliced vectors, vector.hpp:36-140): sel[i] = probe-table row.  NULL resets
  * to "all rows".  flags: POLR_COL_DEVICE if sel is a device pointer. */
