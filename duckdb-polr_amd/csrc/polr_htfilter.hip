@@ -169,6 +169,13 @@ __global__ __launch_bounds__(256) void polr_htfilter_compact_kernel(const unsign
 	}
 }
 
+// (n_tiles > 0) -- behind polr_ht_filter and polr_ht_semi_filter (polr_htsemi.hip), which counts with a kernel of its own
+void polr_launch_htfilter_compact(hipStream_t st, const unsigned long long *pass_bits, const uint64_t *tile_base, uint64_t n_tiles,
+                                  const PolrHtFilterDesc *cols, uint32_t n_cols, uint32_t *rows) {
+	hipLaunchKernelGGL(polr_htfilter_compact_kernel, dim3((unsigned)n_tiles), dim3(256), 0, st, pass_bits, tile_base, n_tiles, cols,
+	                   n_cols, rows);
+}
+
 // the guard of a VARCHAR filter column whose cells were never rebased onto a device heap: its non-NULL cells longer than 12
 // bytes -- their pointers are the host's.  Reads the validity byte and the length word of a cell, nothing else.
 __global__ __launch_bounds__(256) void polr_htfilter_count_long_kernel(const uint8_t *__restrict__ cells_,
@@ -301,8 +308,7 @@ extern "C" int polr_ht_filter(polr_ht *ht, void *stream, const polr_filter_node 
 	HIPCHK(ctx, hipMemcpyAsync(keys_dev.get(), h_keys.data(), ht->n_keys * sizeof(DevCol), hipMemcpyHostToDevice, st));
 	if (kept) {
 		HIPCHK(ctx, hipMemcpyAsync(desc, h_desc.data(), n_cols * sizeof(HtfCol), hipMemcpyHostToDevice, st));
-		hipLaunchKernelGGL(polr_htfilter_compact_kernel, dim3((unsigned)plan.n_tiles), dim3(256), 0, st, (const unsigned long long *)bits,
-		                   (const uint64_t *)tile_base, plan.n_tiles, (const HtfCol *)desc, n_cols, rows);
+		polr_launch_htfilter_compact(st, bits, tile_base, plan.n_tiles, desc, n_cols, rows);
 		HIPCHK(ctx, hipGetLastError());
 	}
 	HIPCHK(ctx, hipStreamSynchronize(st)); // (the table is complete; the staged arrays and the scratch are locals)

@@ -381,6 +381,11 @@ void polr_launch_chunk_prefix(hipStream_t st, const uint32_t *chunk_count, uint3
 // ... of 64-bit counts (the chunks' heap bytes, polr_strout.hip): the same kernel, nothing truncated
 void polr_launch_chunk_prefix(hipStream_t st, const uint64_t *chunk_bytes, uint32_t n_chunks, uint64_t *chunk_base,
                               uint64_t *total);
+// the compaction pass of polr_ht_filter (polr_htfilter.hip: polr_htfilter_compact_kernel, a workgroup per tile), n_tiles > 0:
+// every column of cols[n_cols] (a device array) and the row list, from the pass bits and the tiles' first output rows
+struct PolrHtFilterDesc;
+void polr_launch_htfilter_compact(hipStream_t st, const unsigned long long *pass_bits, const uint64_t *tile_base, uint64_t n_tiles,
+                                  const PolrHtFilterDesc *cols, uint32_t n_cols, uint32_t *rows);
 // the measure and write passes of a VARCHAR output column (polr_strout.hip), over the chunks the output's statistics count
 // (n_chunks > 0).  measure: row_off[n_rows], chunk_bytes[n_chunks], *n_long += the long non-NULL cells; polr_launch_chunk_prefix
 // over chunk_bytes gives chunk_heap_base.  write: heap_dev is where the bytes go, heap_addr the address the cells carry.

@@ -107,6 +107,19 @@ static inline bool pipe_int_width(uint32_t w) {
 	return w == 1 || w == 2 || w == 4 || w == 8;
 }
 
+// Can a column of `probe_width` bytes be compared with a build key of `build_width` bytes that carries `build_flags`
+// (POLR_KEY_*)?  JoinHashTable asserts left/right key types equal (join_hashtable.cpp:24): the reference's left side is then
+// CAST(column) (polar_config.cpp:75-82).  An integer cast is a comparison by VALUE, which a table whose key column carries
+// POLR_KEY_BY_VALUE does on the device -- no materialised copy of the probe column.  The one rule behind a join's keys
+// (pipe_plan_validate) and the columns of a SEMI / ANTI filter (polr_htsemi_plan.h); each caller words its own refusal.
+enum { PIPE_KEYS_PAIR = 0, PIPE_KEYS_WIDTHS_DIFFER = 1, PIPE_KEYS_NO_INTEGER = 2 };
+static inline int pipe_key_pairing(uint32_t probe_width, uint32_t build_width, uint32_t build_flags) {
+	if (probe_width != build_width && !(build_flags & POLR_KEY_BY_VALUE)) {
+		return PIPE_KEYS_WIDTHS_DIFFER;
+	}
+	return pipe_int_width(probe_width) ? PIPE_KEYS_PAIR : PIPE_KEYS_NO_INTEGER;
+}
+
 // the join (-1: the probe table) source c of a join reads: its keys first, then the left sides of its conditions
 static inline int32_t pipe_src_join(const polr_join_desc &d, uint32_t c) {
 	return c < d.n_keys ? d.key_src_join[c] : d.pred_src_join[c - d.n_keys];
@@ -196,16 +209,14 @@ static inline int pipe_plan_validate(const PipePlanInput &in, PipePlan &pl) {
 			if (pipe_plan_resolve(in, pl, j, "key", c, d.key_src_join[c], d.key_src_col[c], s)) {
 				return pl.code;
 			}
-			// JoinHashTable asserts left/right key types equal (join_hashtable.cpp:24): the reference's left side is then
-			// CAST(column) (polar_config.cpp:75-82).  An integer cast is a comparison by VALUE, which a table whose key
-			// column carries POLR_KEY_BY_VALUE does on the device -- no materialised copy of the probe column
-			if (s.width != t.key_width[c] && !(t.key_flags[c] & POLR_KEY_BY_VALUE)) {
+			const int pairing = pipe_key_pairing(s.width, t.key_width[c], t.key_flags[c]);
+			if (pairing == PIPE_KEYS_WIDTHS_DIFFER) {
 				return pipe_plan_refuse(pl, POLR_E_INVALID,
 				                        "join %u key %u: probe key is %u bytes, build key %u bytes (a CAST'ed key: "
 				                        "polr_ht_set_key_flags(..., POLR_KEY_BY_VALUE) before the table is finalized)",
 				                        j, c, s.width, t.key_width[c]);
 			}
-			if (!pipe_int_width(s.width)) {
+			if (pairing == PIPE_KEYS_NO_INTEGER) {
 				return pipe_plan_refuse(pl, POLR_E_UNSUPPORTED, "join %u key %u: probe key of %u bytes", j, c, s.width);
 			}
 		}

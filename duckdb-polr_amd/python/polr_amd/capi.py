@@ -51,6 +51,7 @@ EXPORTS = [
     "polr_ht_from_output",
     "polr_ht_filter", "polr_ht_fetch_filter_rows",
     "polr_pipeline_from_output",
+    "polr_ht_semi_filter",
 ]
 
 
@@ -106,6 +107,14 @@ class FilterNode(C.Structure):
     """polr_filter_node"""
     _fields_ = [("kind", C.c_uint32), ("col", C.c_uint32), ("op", C.c_uint32), ("first_value", C.c_uint32),
                 ("n_values", C.c_uint32), ("pad", C.c_uint32)]
+
+
+SEMI_ANTI, MAX_SEMI_FILTERS = 1, 4  # POLR_SEMI_ANTI, POLR_MAX_SEMI_FILTERS
+
+
+class SemiFilter(C.Structure):
+    """polr_semi_filter"""
+    _fields_ = [("by", C.c_void_p), ("n_cols", C.c_uint32), ("cols", C.c_uint32 * MAX_KEYS), ("flags", C.c_uint32)]
 
 
 FX = {"cmp": 0, "in": 1, "like": 2, "not": 3, "and": 4, "or": 5}  # POLR_FX_*
@@ -364,6 +373,7 @@ def load():
     L.polr_ht_upload_columns.argtypes = [vp, P(Col), u32, P(Col), u32, u64, P(vp)]
     L.polr_ht_from_output.argtypes = [vp, vp, P(OutColRef), u32, P(OutColRef), u32, P(vp)]
     L.polr_ht_filter.argtypes = [vp, vp, P(FilterNode), u32, P(FilterValue), u32, P(u64)]
+    L.polr_ht_semi_filter.argtypes = [vp, vp, P(SemiFilter), u32, P(u64)]
     L.polr_pipeline_from_output.argtypes = [vp, vp, P(OutColRef), u32, P(JoinDesc), u32, vp, u32, P(vp)]
     L.polr_ht_fetch_filter_rows.argtypes = [vp, vp, vp, u64]
     L.polr_ht_finalize_hash.argtypes = [vp, vp]
@@ -601,6 +611,25 @@ class HashTable:
         self.ctx.check(self.ctx.L.polr_ht_filter(self.h, stream, na if nodes else None, len(nodes) if n_nodes is None else n_nodes,
                                                  va if values else None, len(values) if n_values is None else n_values,
                                                  C.byref(kept)))
+        self._n_kept = kept.value
+        return kept.value
+
+    def semi_filter(self, filters, stream=None):
+        """polr_ht_semi_filter (before encode_dictionary and finalize): thin the table by SEMI / ANTI joins against finalized
+        tables and compact it on the device -> the kept count.  filters: [(by, cols, anti)] -- `by` a finalized HashTable, cols
+        the columns of this table (keys first, then payload) paired with by's keys, anti True keeps the rows WITHOUT a match
+        (NOT EXISTS; rows whose key is NULL among them).  A row is kept iff every filter keeps it; [] keeps every row.
+        Allowed after filter() or another semi_filter(): filter_rows() is then the composed list."""
+        fl = [SemiFilter(by.h if by is not None else None, len(cols), (C.c_uint32 * MAX_KEYS)(*list(cols)[:MAX_KEYS]),
+                         (SEMI_ANTI if anti is True else int(anti))) for by, cols, anti in filters]
+        return self.semi_filter_raw(fl, stream)
+
+    def semi_filter_raw(self, filters, stream=None, n_filters=None):
+        """polr_ht_semi_filter with SemiFilter structs as given -> the kept count"""
+        arr = (SemiFilter * max(len(filters), 1))(*filters)
+        kept = C.c_uint64()
+        self.ctx.check(self.ctx.L.polr_ht_semi_filter(self.h, stream, arr if filters else None,
+                                                      len(filters) if n_filters is None else n_filters, C.byref(kept)))
         self._n_kept = kept.value
         return kept.value
 

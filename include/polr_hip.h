@@ -209,13 +209,61 @@ int polr_ht_from_output(polr_out *o, void *stream, const polr_out_col_ref *keys,
  * refused or failed call leaves the table, its columns and the live byte count exactly as they were.
  * Stream: as polr_ht_encode_dictionary -- the call waits for the context's stream and returns when the table is complete
  * (it needs the kept count on the host once, between its counting and its compaction pass).
- * Not provided: filtering a finalized table; repacking the string heaps (the bytes of dropped rows stay); composing several
- * filter calls on one table; LIP on build sides; shipping the row list through polr_bcast_build; pipelines of zero joins. */
+ * Not provided: filtering a finalized table; repacking the string heaps (the bytes of dropped rows stay); a second
+ * polr_ht_filter on one table (thinning by other tables composes: polr_ht_semi_filter, below); shipping the row list through
+ * polr_bcast_build; pipelines of zero joins. */
 struct polr_filter_node; /* (defined with polr_pipeline_scan_filter_expr, below) */
 struct polr_filter_value;
 int polr_ht_filter(polr_ht *ht, void *stream, const struct polr_filter_node *nodes, uint32_t n_nodes,
                    const struct polr_filter_value *values, uint32_t n_values, uint64_t *n_kept);
 int polr_ht_fetch_filter_rows(polr_ht *ht, void *stream, uint32_t *dst, uint64_t dst_rows);
+/* Thin an UN-FINALIZED table by SEMI / ANTI joins against other, finalized tables and compact it, on the device: the SEMI /
+ * ANTI / MARK hash joins inside a build subtree that ExtractInfoLinear walks through as predicates on the base table
+ * (src/parallel/polar_enumeration_algo.cpp:192-205; ScanStructure::NextSemiJoin / NextAntiJoin,
+ * src/execution/join_hashtable.cpp:589-627) -- a dimension restricted by k IN (SELECT ...), EXISTS or NOT EXISTS -- and the
+ * semi-join reduction of a large build side by the keys of a small filtered table.  It is LIP for build sides: the index of
+ * `by` is the filter, without false positives.
+ * Match rule: a row MATCHES filter f iff its key, read from the columns cols[] of `ht`, would find at least one build row of
+ * f.by if it were a probe tuple of a join on f.by.  So: a NULL in a key column never matches unless that key column of `by`
+ * carries POLR_KEY_NULL_EQUAL (then it matches iff `by` kept a NULL key there); a value outside the range of a
+ * POLR_KEY_BY_VALUE / packed column never matches; a key that repeats in `by` counts once; the all-ones 8-byte key is found
+ * through the side entry a run hash table keeps for it.
+ * Kept rows: flags == 0 (SEMI) keeps the matching rows; POLR_SEMI_ANTI keeps the rest -- rows whose key is NULL among them.
+ * That is NOT EXISTS (NextSemiOrAntiJoin<false>: NULL keys never enter the match selection).  NOT IN over a NULL-free
+ * subquery is polr_ht_filter(key IS NOT NULL) followed by an ANTI filter; the NULL propagation of a MARK join whose subquery
+ * holds NULLs stays with the engine.
+ * Several filters: a row is kept iff every filter keeps it (the device tests the smallest `by` first; the order changes the
+ * work, never the survivors).  n_filters == 0 keeps every row but still compacts and sets the row list.
+ * Columns: cols[] numbers the columns of `ht` as a polr_ht_filter program does, keys first, then payload; column cols[c]
+ * is compared with key c of `by` under the rule of a join's keys: same width unless that key carries POLR_KEY_BY_VALUE,
+ * integer widths only.  `by` may be any finalized table: a perfect table, a unique-key or a run hash table, its key in the
+ * plain form (one key, or two of <= 32 bits) or the packed form (up to four keys, by value, NULL = NULL).  Nothing verifies
+ * strings or wide composites here: a cols[] entry that names a 16-byte column is POLR_E_UNSUPPORTED, and a `by` keyed by a
+ * hash of strings is compared ON THE HASH ALONE.
+ * Composition: the call is allowed on a table polr_ht_filter or an earlier polr_ht_semi_filter has filtered;
+ * polr_ht_fetch_filter_rows then returns the composed list -- the row numbers AS UPLOADED of the rows that are left.
+ * polr_ht_filter after this call stays refused ("filtered already"): constant filters go first.
+ * Everything else is as polr_ht_filter: the result is compacted in upload order into one allocation the table owns (a table
+ * filtered before also keeps, unused, the 4-byte list of this pass); a caller's POLR_COL_DEVICE buffers are never written;
+ * VARCHAR cells are copied as they are; a column has a validity array afterwards iff it had one; device_bytes and
+ * polr_device_bytes_live() account for the new state; the call waits for the context's stream and returns when the table is
+ * complete.  `by` is only read and may be destroyed after the call returns.
+ * Refusals, checked in this order before anything is enqueued -- the table, its columns and the live byte count stay exactly
+ * as they were: NULL ht; a finalized ht; a dictionary-encoded ht (POLR_E_INVALID); n_filters > POLR_MAX_SEMI_FILTERS
+ * (POLR_E_UNSUPPORTED); NULL filters with n_filters > 0; then per filter, in order: NULL by; by not finalized; by == ht; by
+ * on another device or context; unknown flag bits; n_cols != by's key count; and per key a cols[] entry beyond the table's
+ * columns (all POLR_E_INVALID), a 16-byte column (POLR_E_UNSUPPORTED), the pairing rule.  n_kept may be NULL.
+ * Not provided: non-equality or verifying conditions; MARK columns as output; filtering a finalized table; shipping the row
+ * list through polr_bcast_build. */
+#define POLR_SEMI_ANTI 1u /* keep the rows WITHOUT a match (NOT EXISTS); 0: keep the rows WITH one */
+#define POLR_MAX_SEMI_FILTERS 4
+typedef struct polr_semi_filter {
+	const polr_ht *by;            /* a FINALIZED table on the same device */
+	uint32_t n_cols;              /* == by's key count */
+	uint32_t cols[POLR_MAX_KEYS]; /* columns of `ht`, numbered as polr_ht_filter numbers them: keys first, then payload */
+	uint32_t flags;               /* 0 or POLR_SEMI_ANTI */
+} polr_semi_filter;
+int polr_ht_semi_filter(polr_ht *ht, void *stream, const polr_semi_filter *filters, uint32_t n_filters, uint64_t *n_kept);
 /* Key semantics beyond "same type on both sides, NULL never matches": the reference multiplexes INNER hash joins whose
  * left side is CAST(column) (src/parallel/polar_config.cpp:75-82) and whose comparison is IS NOT DISTINCT FROM
  * (JoinHashTable::null_values_are_equal, src/execution/join_hashtable.cpp:35-36,170-192,642).  Per key column, BEFORE the
