@@ -52,6 +52,7 @@ EXPORTS = [
     "polr_ht_filter", "polr_ht_fetch_filter_rows",
     "polr_pipeline_from_output",
     "polr_ht_semi_filter",
+    "polr_ht_column_stats", "polr_pipeline_column_stats", "polr_ht_finalize_auto_stats", "polr_col_stats_plan_info",
 ]
 
 
@@ -115,6 +116,25 @@ SEMI_ANTI, MAX_SEMI_FILTERS = 1, 4  # POLR_SEMI_ANTI, POLR_MAX_SEMI_FILTERS
 class SemiFilter(C.Structure):
     """polr_semi_filter"""
     _fields_ = [("by", C.c_void_p), ("n_cols", C.c_uint32), ("cols", C.c_uint32 * MAX_KEYS), ("flags", C.c_uint32)]
+
+
+MAX_STATS_COLS, STATS_SELECTED = 16, 1  # POLR_MAX_STATS_COLS, POLR_STATS_SELECTED
+
+
+class ColStats(C.Structure):
+    """polr_col_stats"""
+    _fields_ = [("min_value", C.c_int64), ("max_value", C.c_int64), ("n_rows", C.c_uint64), ("n_valid", C.c_uint64),
+                ("n_long", C.c_uint64), ("long_bytes", C.c_uint64), ("width", C.c_uint32), ("flags", C.c_uint32)]
+
+
+class ColStatsPlan(C.Structure):
+    """polr_col_stats_plan"""
+    _fields_ = [("cells_per_load", C.c_uint32), ("loads_in_flight", C.c_uint32), ("tile_rows", C.c_uint32),
+                ("n_workgroups", C.c_uint32), ("stride_rows", C.c_uint64), ("scratch_bytes", C.c_uint64)]
+
+
+def _stats_dicts(arr, n):
+    return [{f[0]: getattr(arr[i], f[0]) for f in ColStats._fields_} for i in range(n)]
 
 
 FX = {"cmp": 0, "in": 1, "like": 2, "not": 3, "and": 4, "or": 5}  # POLR_FX_*
@@ -375,6 +395,10 @@ def load():
     L.polr_ht_filter.argtypes = [vp, vp, P(FilterNode), u32, P(FilterValue), u32, P(u64)]
     L.polr_ht_semi_filter.argtypes = [vp, vp, P(SemiFilter), u32, P(u64)]
     L.polr_pipeline_from_output.argtypes = [vp, vp, P(OutColRef), u32, P(JoinDesc), u32, vp, u32, P(vp)]
+    L.polr_ht_column_stats.argtypes = [vp, vp, P(u32), u32, P(ColStats)]
+    L.polr_pipeline_column_stats.argtypes = [vp, vp, P(u32), u32, u32, P(ColStats)]
+    L.polr_ht_finalize_auto_stats.argtypes = [vp, vp, P(u32), P(ColStats)]
+    L.polr_col_stats_plan_info.argtypes = [u64, u32, P(ColStatsPlan)]
     L.polr_ht_fetch_filter_rows.argtypes = [vp, vp, vp, u64]
     L.polr_ht_finalize_hash.argtypes = [vp, vp]
     L.polr_ht_finalize_perfect.argtypes = [vp, i64, i64, vp]
@@ -453,6 +477,16 @@ def load():
 def device_bytes_live():
     """polr_device_bytes_live: bytes of device memory the library owns right now, over all contexts and handles"""
     return int(load().polr_device_bytes_live())
+
+
+def col_stats_plan_info(n_rows, width):
+    """polr_col_stats_plan_info: what a statistics call plans for one aligned column of n_rows rows (launches nothing)"""
+    L = load()
+    i = ColStatsPlan()
+    rc = L.polr_col_stats_plan_info(int(n_rows), int(width), C.byref(i))
+    if rc != OK:
+        raise PolrError(rc, "polr_col_stats_plan_info(%d, %d)" % (n_rows, width))
+    return {f[0]: getattr(i, f[0]) for f in ColStatsPlan._fields_}
 
 
 def _np_col(arr, valid=None):
@@ -760,6 +794,27 @@ class HashTable:
         self.ctx.check(self.ctx.L.polr_ht_finalize_auto(self.h, int(min_value), int(max_value), stream, C.byref(kind)))
         return kind.value
 
+    def column_stats(self, cols, stream=None):
+        """polr_ht_column_stats (before finalize): min / max / counts of the table's columns cols[] -- keys first, then
+        payload, as filter() numbers them -- in one pass on the device -> a list of dicts with the fields of polr_col_stats.
+        A VARCHAR column: min / max of the LENGTHS, n_long / long_bytes of the strings beyond 12 bytes."""
+        cols = list(cols)
+        return self.column_stats_raw(cols, len(cols), stream)
+
+    def column_stats_raw(self, cols, n_cols, stream=None, stats=None):
+        """polr_ht_column_stats with cols (a list or None) and n_cols as given; stats: a ColStats array to fill"""
+        ca = (C.c_uint32 * max(len(cols), 1))(*cols) if cols is not None else None
+        st = (ColStats * max(n_cols, 1))() if stats is None else stats
+        self.ctx.check(self.ctx.L.polr_ht_column_stats(self.h, stream, ca, n_cols, st))
+        return _stats_dicts(st, n_cols)
+
+    def finalize_auto_stats(self, stream=None):
+        """polr_ht_finalize_auto_stats: finalize_auto with the min / max of key column 0 taken on the device -> (kind,
+        key_stats: the dict of column_stats for key column 0)"""
+        kind, st = C.c_uint32(), (ColStats * 1)()
+        self.ctx.check(self.ctx.L.polr_ht_finalize_auto_stats(self.h, stream, C.byref(kind), st))
+        return kind.value, _stats_dicts(st, 1)[0]
+
     def info(self):
         i = HtInfo()
         self.ctx.check(self.ctx.L.polr_ht_get_info(self.h, C.byref(i)))
@@ -875,6 +930,19 @@ class Pipeline:
         else:
             sel = np.ascontiguousarray(sel, dtype=np.uint32)
             self.ctx.check(self.ctx.L.polr_pipeline_set_selection(self.h, sel.ctypes.data, len(sel), 0))
+
+    def column_stats(self, cols, selected=False, stream=None):
+        """polr_pipeline_column_stats: min / max / counts of the probe columns cols[] in one pass on the device, over all
+        probe rows or, selected=True, over the rows of the selection in force -> a list of dicts (polr_col_stats)"""
+        cols = list(cols)
+        return self.column_stats_raw(cols, len(cols), STATS_SELECTED if selected else 0, stream)
+
+    def column_stats_raw(self, cols, n_cols, flags=0, stream=None, stats=None):
+        """polr_pipeline_column_stats with cols (a list or None), n_cols and flags as given; stats: a ColStats array to fill"""
+        ca = (C.c_uint32 * max(len(cols), 1))(*cols) if cols is not None else None
+        st = (ColStats * max(n_cols, 1))() if stats is None else stats
+        self.ctx.check(self.ctx.L.polr_pipeline_column_stats(self.h, stream, ca, n_cols, flags, st))
+        return _stats_dicts(st, n_cols)
 
     def launch_info(self, materialize=False):
         i = LaunchInfo()

@@ -293,6 +293,70 @@ int polr_ht_finalize_perfect(polr_ht *ht, int64_t min_value, int64_t max_value, 
  * (may be NULL) tells which build-id convention applies (see polr_ht_get_info). */
 #define POLR_DENSE_FACTOR 8
 int polr_ht_finalize_auto(polr_ht *ht, int64_t min_value, int64_t max_value, void *stream, uint32_t *kind_out);
+/* Column statistics on the device: what the reference's planner carries as NumericStatistics min / max into
+ * PerfectHashJoinStats (build_min / build_max / probe_min / probe_max, plan_comparison_join.cpp:63-133) and into the group
+ * domains of PhysicalPerfectHashAggregate, for columns that never were on the host -- a table made by polr_ht_from_output or
+ * thinned by polr_ht_filter / polr_ht_semi_filter, a pipeline made by polr_pipeline_from_output.  One call is one pass over
+ * the named columns; min_value / max_value are what polr_ht_finalize_perfect / polr_ht_finalize_auto take, and min_value and
+ * max_value - min_value + 1 are the min_value / n_values of a polr_group_key.
+ * Values: a POLR_COL_SIGNED column is compared and returned sign-extended, any other column zero-extended; an unsigned
+ * 8-byte column is compared as unsigned and returned as its bit pattern (the convention of polr_ht_finalize_auto: the two
+ * numbers can be handed on unchanged).  With n_valid == 0, min_value and max_value are both 0: look at n_valid.
+ * NULL rows: a row whose validity byte is 0 takes no part, whatever its cell holds.
+ * VARCHAR columns (width 16): min_value / max_value are the minimum and maximum LENGTH in bytes of the non-NULL strings,
+ * n_long counts those longer than 12 bytes and long_bytes sums their lengths (what a packed heap of them takes).  Only the
+ * length word of a cell is read and no pointer is followed: the call needs no heap and never refuses for one that never came.
+ * polr_ht_column_stats: cols[] numbers the table's columns as a polr_ht_filter program does, keys first, then payload
+ * (dictionary code columns are ordinary 4-byte payload columns); the same column may be named more than once.  Any
+ * UN-FINALIZED table, whatever its route (polr_ht_upload_columns with host or POLR_COL_DEVICE columns, polr_ht_upload_rows,
+ * polr_ht_from_output), also after polr_ht_filter, polr_ht_semi_filter and polr_ht_encode_dictionary*: the statistics
+ * describe the rows the table holds now.
+ * polr_pipeline_column_stats: cols[] are probe columns, over all n_probe_rows; with POLR_STATS_SELECTED only over the rows of
+ * the selection in force (polr_pipeline_set_selection or one of the scan-filter calls; with none in force: all rows).  Any
+ * pipeline, from polr_pipeline_create (host or device columns) or polr_pipeline_from_output.
+ * Zero rows -- a table or pipeline of none, an empty selection --: n_rows = n_valid = 0 for every column, nothing is
+ * launched.
+ * Refusals, checked in this order -- nothing is enqueued, stats is untouched, the live bytes are as before: a NULL handle,
+ * cols or stats; n_cols == 0 (POLR_E_INVALID); n_cols > POLR_MAX_STATS_COLS (POLR_E_UNSUPPORTED); a finalized table, also one
+ * from polr_pht_upload or polr_ht_alloc_like / unknown flag bits of the pipeline call; a cols[] entry beyond the columns, the
+ * first one in order (POLR_E_INVALID).
+ * The calls wait for the context's stream and return when the numbers are on the host (as polr_ht_encode_dictionary);
+ * the scratch -- one partial record per workgroup -- is allocated and freed inside the call: polr_device_bytes_live() is
+ * afterwards what it was; a caller's POLR_COL_DEVICE memory is only read.
+ * polr_ht_finalize_auto_stats: polr_ht_finalize_auto with the statistics taken here.  One plain key (n_keys == 1, no key
+ * flags): the statistics of key column 0, NULL keys apart -- the rows that enter the table --; with at least one non-NULL key
+ * exactly polr_ht_finalize_auto(ht, min_value, max_value, stream, kind_out): same index kind, same build-id convention, same
+ * polr_ht_get_info, same fallback to a hash table on a duplicate; with none polr_ht_finalize_hash.  Several keys or a flagged
+ * key: polr_ht_finalize_hash as in polr_ht_finalize_auto, and no statistics pass unless key_stats is given.  key_stats may be
+ * NULL; when given it is filled for key column 0 in every case.  Refusals: those of polr_ht_finalize_auto.
+ * Not provided: statistics of a finalized table or of output rows (polr_out_aggregate MIN / MAX covers those); distinct
+ * counts or uniqueness. */
+#define POLR_MAX_STATS_COLS 16
+#define POLR_STATS_SELECTED 1u   /* pipeline call: only the rows of the selection in force */
+typedef struct polr_col_stats {
+	int64_t  min_value, max_value; /* integer column: over the non-NULL rows, in the column's own order */
+	uint64_t n_rows;               /* rows looked at */
+	uint64_t n_valid;              /* of them non-NULL */
+	uint64_t n_long;               /* VARCHAR: non-NULL strings longer than 12 bytes (0 for integer columns) */
+	uint64_t long_bytes;           /* VARCHAR: sum of their lengths (what a packed heap of them takes) */
+	uint32_t width, flags;         /* of the column: 1/2/4/8/16, POLR_COL_SIGNED */
+} polr_col_stats;
+int polr_ht_column_stats(polr_ht *ht, void *stream, const uint32_t *cols, uint32_t n_cols, polr_col_stats *stats);
+int polr_pipeline_column_stats(polr_pipeline *p, void *stream, const uint32_t *cols, uint32_t n_cols, uint32_t flags,
+                               polr_col_stats *stats);
+int polr_ht_finalize_auto_stats(polr_ht *ht, void *stream, uint32_t *kind_out, polr_col_stats *key_stats);
+/* Diagnostic, launches nothing: what a statistics call plans for ONE column of n_rows rows and `width` bytes whose cells
+ * start at a 16-byte boundary and are not read through a selection (POLR_E_INVALID: NULL info or a width that is none of
+ * 1/2/4/8/16). */
+typedef struct polr_col_stats_plan {
+	uint32_t cells_per_load;  /* cells one 16-byte load of a lane brings */
+	uint32_t loads_in_flight; /* independent loads a lane issues together */
+	uint32_t tile_rows;       /* rows of a workgroup tile */
+	uint32_t n_workgroups;    /* workgroups launched (0: no rows, nothing launched) */
+	uint64_t stride_rows;     /* rows the grid covers before a workgroup takes its second tile */
+	uint64_t scratch_bytes;   /* the partial records */
+} polr_col_stats_plan;
+int polr_col_stats_plan_info(uint64_t n_rows, uint32_t width, polr_col_stats_plan *info);
 /* Upload a perfect table the reference already built (PerfectHashJoinExecutor members
  * perfect_hash_table / bitmap_build_idx, perfect_hash_join_executor.hpp): bitmap has range+1
  * bools, each payload column has range+1 cells. */
