@@ -447,6 +447,7 @@ static int aggregate_ungrouped(polr_out *o, void *stream, SinkAggs &aggs, polr_a
 	}
 	polr_pipeline *p = o->pipe;
 	polr_ctx *ctx = p->ctx;
+	POLR_REFUSE_AGG_CELLS(ctx, o);
 	if (n_aggs > POLR_MAX_AGGS) {
 		POLR_FAIL(ctx, POLR_E_UNSUPPORTED, "at most %d aggregates per call", POLR_MAX_AGGS);
 	}
@@ -644,6 +645,7 @@ static int aggregate_grouped(polr_out *o, void *stream, const polr_group_key *ke
 	}
 	polr_pipeline *p = o->pipe;
 	polr_ctx *ctx = p->ctx;
+	POLR_REFUSE_AGG_CELLS(ctx, o);
 	if (n_keys > POLR_MAX_GROUP_KEYS || n_aggs > POLR_MAX_AGGS) {
 		POLR_FAIL(ctx, POLR_E_UNSUPPORTED, "at most %d group columns and %d aggregates", POLR_MAX_GROUP_KEYS, POLR_MAX_AGGS);
 	}
@@ -737,7 +739,7 @@ extern "C" int polr_out_aggregate_grouped_expr(polr_out *o, void *stream, const 
 
 // ---- the GROUP BY sink fused into an emitting flat pipeline (FusedSink, polr_device.h; polr_flat_device.h) -------------
 static_assert(POLR_AGG_COUNT_STAR == POLR_DEV_AGG_COUNT_STAR && POLR_AGG_COUNT == POLR_DEV_AGG_COUNT &&
-                  POLR_AGG_SUM == POLR_DEV_AGG_SUM,
+                  POLR_AGG_SUM == POLR_DEV_AGG_SUM && POLR_AGG_MIN == POLR_DEV_AGG_MIN && POLR_AGG_MAX == POLR_DEV_AGG_MAX,
               "aggregate function codes");
 #define POLR_FUSED_TABLES 256u // one table of group cells per workgroup (modulo): the adds of a workgroup stay among themselves
 
@@ -785,7 +787,7 @@ extern "C" int polr_out_fuse_grouped(polr_out *o, const polr_group_key *keys, ui
 		          "a GROUP BY sink is fused into FLAT pipelines whose joins are all perfect tables (polr_pipeline_launch_info); "
 		          "others: polr_out_aggregate_grouped over the emitted row ids");
 	}
-	if (o->fused_dev) {
+	if (out_has_fused_sink(o)) { // (at most one of the two sinks: polr_out_fuse_aggregate)
 		POLR_FAIL(ctx, POLR_E_INVALID, "the output object already has a fused sink");
 	}
 	FusedSink fs;
@@ -884,6 +886,164 @@ extern "C" int polr_out_fused_result(polr_out *o, void *stream, polr_agg_value *
 	}
 	if (n_dropped) {
 		*n_dropped = dropped;
+	}
+	return POLR_OK;
+}
+
+// ---- the UNGROUPED sink fused into the generic pool kernel (FusedAggSink, polr_device.h; the fold: polr_gen_device.h) ----
+// What is refused, the cell layout, the reset values and the decode are polr_fuseagg_plan.h; here the output and its columns
+// are described to the plan, and what it says is allocated and launched.
+struct FuseAggWords { // the plan's per-word kinds and reset values, as a kernel argument
+	uint8_t kind[POLR_FUSEAGG_MAX_WORDS];
+	unsigned long long reset[POLR_FUSEAGG_MAX_WORDS];
+};
+static FuseAggWords fuseagg_words(const PolrFuseAggPlan &pl) {
+	FuseAggWords w;
+	memset(&w, 0, sizeof(w));
+	for (uint32_t i = 0; i < pl.words_per_table; i++) {
+		w.kind[i] = pl.kind[i];
+		w.reset[i] = pl.reset[i];
+	}
+	return w;
+}
+
+// cells[t][w] = reset[w] for the n_tables tables (and the one behind them)
+__global__ __launch_bounds__(256) void polr_fuseagg_fill_kernel(unsigned long long *__restrict__ cells, uint32_t n_tables,
+                                                                uint32_t words, FuseAggWords ww) {
+	const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+	if (i < (n_tables + 1u) * words) {
+		cells[i] = ww.reset[i % words];
+	}
+}
+
+// cells[n_tables][w] = the tables' cells[t][w] combined by the word's rule: one wave per word, a lane takes the tables
+// lane, lane + 64, ...
+__global__ __launch_bounds__(64) void polr_fuseagg_combine_kernel(unsigned long long *__restrict__ cells, uint32_t n_tables,
+                                                                  uint32_t words, FuseAggWords ww) {
+	const uint32_t w = blockIdx.x;
+	const uint32_t kind = ww.kind[w];
+	unsigned long long v = ww.reset[w];
+	for (uint32_t t = threadIdx.x; t < n_tables; t += 64u) {
+		const unsigned long long c = cells[(size_t)t * words + w];
+		v = kind == POLR_FUSEAGG_ADD ? v + c : (kind == POLR_FUSEAGG_MIN ? (c < v ? c : v) : (c > v ? c : v));
+	}
+#pragma unroll
+	for (int d = 32; d > 0; d >>= 1) {
+		const unsigned long long c = __shfl_xor(v, d, 64);
+		v = kind == POLR_FUSEAGG_ADD ? v + c : (kind == POLR_FUSEAGG_MIN ? (c < v ? c : v) : (c > v ? c : v));
+	}
+	if (threadIdx.x == 0) {
+		cells[(size_t)n_tables * words + w] = v;
+	}
+}
+
+void polr_launch_fuseagg_fill(hipStream_t st, const polr_out *o) {
+	const PolrFuseAggPlan &pl = o->agg_plan;
+	const uint32_t n = (pl.n_tables + 1u) * pl.words_per_table;
+	hipLaunchKernelGGL(polr_fuseagg_fill_kernel, dim3((n + 255u) / 256u), dim3(256), 0, st, o->agg_cells.get(), pl.n_tables,
+	                   pl.words_per_table, fuseagg_words(pl));
+}
+
+extern "C" int polr_out_fuse_aggregate(polr_out *o, const polr_agg_spec *specs, uint32_t n_aggs) {
+	POLR_ENTRY();
+	PolrFuseAggRequest rq;
+	memset(&rq, 0, sizeof(rq));
+	PolrFuseAggPlan pl;
+	PolrFuseAggArg args[POLR_FUSEAGG_MAX_AGGS];
+	memset(args, 0, sizeof(args));
+	rq.has_out = o != nullptr;
+	rq.has_specs = specs != nullptr;
+	rq.n_aggs = n_aggs;
+	rq.args = args;
+	if (!o) {
+		return polr_fuseagg_plan(rq, &pl); // (no context to leave a message in)
+	}
+	polr_pipeline *p = o->pipe;
+	polr_ctx *ctx = p->ctx;
+	rq.already_fused = out_has_fused_sink(o);
+	for (uint32_t a = 0; specs && a < n_aggs && a < POLR_FUSEAGG_MAX_AGGS; a++) {
+		PolrFuseAggArg &g = args[a];
+		g.fn = specs[a].fn;
+		g.src_join = specs[a].src_join;
+		g.src_col = specs[a].src_col;
+		if (g.src_join < 0) {
+			g.col_in_range = g.src_col < p->n_probe_cols;
+		} else {
+			g.col_in_range = (uint32_t)g.src_join < p->k && g.src_col < p->hts[g.src_join]->n_payload;
+		}
+		if (g.col_in_range) {
+			const OwnedCol &c = g.src_join < 0 ? p->probe_cols[g.src_col] : build_col(p->hts[g.src_join], g.src_col);
+			g.width = c.width;
+			g.flags = c.flags;
+		}
+	}
+	POLR_TRY_PLAN(ctx, pl, polr_fuseagg_plan(rq, &pl));
+	HIPCHK(ctx, hipSetDevice(ctx->device));
+	if (pl.unfuse) { // the output object collects row ids again
+		if (o->agg_dev) {
+			HIPCHK(ctx, hipDeviceSynchronize());
+			o->agg_dev.reset();
+			o->agg_cells.reset();
+			o->dev.agg = nullptr;
+		}
+		return POLR_OK;
+	}
+	FusedAggSink fs;
+	memset(&fs, 0, sizeof(fs));
+	fs.aggs.n = n_aggs;
+	for (uint32_t a = 0; a < n_aggs; a++) { // (the plan has accepted every column: build_agg refuses nothing here)
+		POLR_TRY(build_agg(p, specs[a], a, &fs.aggs.a[a]));
+	}
+	fs.n_tables = pl.n_tables;
+	fs.words_per_table = pl.words_per_table;
+	// built in locals and moved into the output at the point of success: nothing half-made stays behind
+	DevBuf<unsigned long long> cells;
+	DevBuf<FusedAggSink> dev;
+	HIPCHK(ctx, cells.alloc(pl.cell_words));
+	HIPCHK(ctx, dev.alloc(1));
+	fs.cells = cells;
+	HIPCHK(ctx, hipMemcpyAsync(dev, &fs, sizeof(fs), hipMemcpyHostToDevice, ctx->stream));
+	o->agg_plan = pl;
+	o->agg_cells = std::move(cells);
+	polr_launch_fuseagg_fill(ctx->stream, o);
+	hipError_t e = hipStreamSynchronize(ctx->stream);
+	if (e != hipSuccess) {
+		o->agg_cells.reset();
+		POLR_FAIL(ctx, POLR_E_HIP, "fused aggregate sink set-up failed: %s", hipGetErrorString(e));
+	}
+	o->agg_dev = std::move(dev);
+	o->dev.agg = o->agg_dev;
+	return POLR_OK;
+}
+
+extern "C" int polr_out_fused_aggregate_result(polr_out *o, void *stream, polr_agg_value *results, uint32_t n_aggs) {
+	POLR_ENTRY();
+	if (!o || !results) {
+		return POLR_E_INVALID;
+	}
+	polr_ctx *ctx = o->pipe->ctx;
+	if (!o->agg_dev) {
+		POLR_FAIL(ctx, POLR_E_INVALID, "the output object has no fused aggregate sink (polr_out_fuse_aggregate)");
+	}
+	const PolrFuseAggPlan &pl = o->agg_plan;
+	if (n_aggs != pl.n_aggs) {
+		POLR_FAIL(ctx, POLR_E_INVALID, "results hold %u aggregates, the sink %u", n_aggs, pl.n_aggs);
+	}
+	HIPCHK(ctx, hipSetDevice(ctx->device));
+	hipStream_t st = polr_stream(ctx, stream);
+	const uint32_t words = pl.words_per_table;
+	hipLaunchKernelGGL(polr_fuseagg_combine_kernel, dim3(words), dim3(64), 0, st, o->agg_cells.get(), pl.n_tables, words,
+	                   fuseagg_words(pl));
+	uint64_t host[POLR_FUSEAGG_MAX_WORDS];
+	hipError_t e = hipMemcpyAsync(host, o->agg_cells + (size_t)pl.n_tables * words, (size_t)words * 8u, hipMemcpyDeviceToHost, st);
+	e = e == hipSuccess ? hipStreamSynchronize(st) : e;
+	if (e != hipSuccess) {
+		POLR_FAIL(ctx, POLR_E_HIP, "fused aggregate read-out failed: %s", hipGetErrorString(e));
+	}
+	char err[256];
+	const int rc = polr_fuseagg_decode(pl.fn, pl.n_aggs, host, results, err, sizeof(err));
+	if (rc) {
+		POLR_FAIL(ctx, rc, "%s", err);
 	}
 	return POLR_OK;
 }
@@ -1204,6 +1364,7 @@ int polr_out_aggregate_string(polr_out *o, void *stream, uint32_t fn, int32_t sr
 	}
 	polr_pipeline *p = o->pipe;
 	polr_ctx *ctx = p->ctx;
+	POLR_REFUSE_AGG_CELLS(ctx, o);
 	if (fn != POLR_AGG_MIN && fn != POLR_AGG_MAX) {
 		POLR_FAIL(ctx, POLR_E_UNSUPPORTED, "string aggregate %u (MIN or MAX)", fn);
 	}
@@ -1548,6 +1709,7 @@ static int aggregate_hashed(polr_out *o, void *stream, const polr_group_key *col
 	}
 	polr_pipeline *p = o->pipe;
 	polr_ctx *ctx = p->ctx;
+	POLR_REFUSE_AGG_CELLS(ctx, o);
 	if (n_cols > POLR_MAX_GROUP_KEYS || n_aggs > POLR_MAX_AGGS || max_groups > (1ull << 24)) {
 		POLR_FAIL(ctx, POLR_E_UNSUPPORTED, "at most %d group columns, %d aggregates and 2^24 groups", POLR_MAX_GROUP_KEYS,
 		          POLR_MAX_AGGS);

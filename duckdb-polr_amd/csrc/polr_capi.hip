@@ -1102,6 +1102,9 @@ int polr_out_reset(polr_out *o, void *stream) {
 		                           (size_t)o->fused_tables * o->fused_groups * (1u + 2u * o->fused_aggs) * 8u, st));
 		HIPCHK(ctx, hipMemsetAsync(o->fused_dropped, 0, 8, st));
 	}
+	if (o->agg_cells) { // (a fused ungrouped sink: its cells go back to "no rows" -- MIN's identity is not 0)
+		polr_launch_fuseagg_fill(st, o);
+	}
 	// (runs that write this output on another stream wait for these memsets: out_order_behind_reset)
 	if (!o->reset_event) {
 		HIPCHK(ctx, hipEventCreateWithFlags(&o->reset_event, hipEventDisableTiming));
@@ -1150,6 +1153,7 @@ int polr_out_fetch_ids(polr_out *o, void *stream, uint32_t *dst, uint64_t dst_ro
 		return POLR_E_INVALID;
 	}
 	polr_ctx *ctx = o->pipe->ctx;
+	POLR_REFUSE_AGG_CELLS(ctx, o);
 	hipStream_t st = polr_stream(ctx, stream);
 	int rc = out_ensure_stats(o, stream);
 	if (rc) {
@@ -1178,6 +1182,7 @@ int polr_out_materialize(polr_out *o, void *stream, int32_t src_join, uint32_t s
 	}
 	polr_pipeline *p = o->pipe;
 	polr_ctx *ctx = p->ctx;
+	POLR_REFUSE_AGG_CELLS(ctx, o);
 	hipStream_t st = polr_stream(ctx, stream);
 	int rc = out_ensure_stats(o, stream);
 	if (rc) {

@@ -19,6 +19,7 @@
 
 #include "polr_pipeline_plan.h" // POLR_KMAX, POLR_PMAX, POLR_NKEYS, POLR_NPREDS, KIND_*: shared with the host's plan
 #include "polr_build_plan.h"    // KeyPack: shared with the host's build-side plan
+#include "polr_fuseagg_plan.h"  // POLR_FUSEAGG_*: the cell layout of the fused ungrouped sink, shared with its host plan
 
 // Device code names the address space of what it loads from: a pointer rebuilt from an integer (descriptors travel as
 // 64-bit words through LDS and scalar registers) is a GENERIC pointer to the compiler, and a generic access is a FLAT
@@ -213,6 +214,7 @@ struct DevRound {
 
 // chunked output (a DataChunk stream of row ids)
 struct FusedSink;
+struct FusedAggSink;
 struct DevOut {
 	uint32_t *ids;          // [W_out][max_chunks * chunk_capacity]
 	uint32_t *chunk_count;  // [max_chunks]
@@ -223,6 +225,7 @@ struct DevOut {
 	uint32_t W_out;
 	uint32_t pad;
 	const FusedSink *fused; // nullptr: row ids are written (see FusedSink below)
+	const FusedAggSink *agg; // the generic pool kernel's ungrouped sink (FusedAggSink below); at most one of the two is set
 };
 
 // ---- aggregate sinks (polr_agg.hip; the flat pipeline's fused GROUP BY, polr_flat_device.h) ---------------------------
@@ -260,11 +263,24 @@ struct DevGroupSet {
 #define POLR_DEV_AGG_COUNT_STAR 0u // (= POLR_AGG_COUNT_STAR / _COUNT / _SUM of polr_hip.h: static_assert in polr_agg.hip)
 #define POLR_DEV_AGG_COUNT 1u
 #define POLR_DEV_AGG_SUM 2u
+#define POLR_DEV_AGG_MIN 3u // (the ungrouped sink of the generic kernel, FusedAggSink below, takes these two as well)
+#define POLR_DEV_AGG_MAX 4u
 struct FusedSink {
 	DevGroupSet groups;
 	DevAggSet aggs;
 	unsigned long long *cells;
 	unsigned long long *dropped;
+	uint32_t n_tables, words_per_table;
+};
+
+// Ungrouped aggregates FUSED into the generic pool kernel (polr_out_fuse_aggregate): where a final tuple would leave as row
+// ids (gen_out_write, polr_gen_device.h) its wave folds it into the cells of its workgroup's table instead --
+// [n_tables][1 + 3 n_aggs] 64-bit words in global memory (layout, combining rule and reset values: polr_fuseagg_plan.h),
+// updated with atomics nobody waits for; the tables are combined when the result is read.
+static_assert(POLR_MAX_AGGS == POLR_FUSEAGG_MAX_AGGS, "aggregates per sink");
+struct FusedAggSink {
+	DevAggSet aggs;
+	unsigned long long *cells;
 	uint32_t n_tables, words_per_table;
 };
 

@@ -218,7 +218,7 @@ extern "C" int polr_ht_from_output(polr_out *o, void *stream, const polr_out_col
 	rq.has_result = out != nullptr;
 	rq.has_keys = keys != nullptr;
 	rq.has_payload = payload != nullptr;
-	rq.fused = o->fused_dev.get() != nullptr;
+	rq.fused = out_has_fused_sink(o);
 	rq.n_keys = n_keys;
 	rq.n_payload = n_payload;
 	PolrFromoutPlan plan;

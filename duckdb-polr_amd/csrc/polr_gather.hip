@@ -132,6 +132,13 @@ hipError_t polr_launch_poolg_kernel(uint32_t W, uint32_t k, uint32_t n_blocks, h
                                     const ResidentExec *execs, PoolRun *run, DevOut out);
 hipError_t polr_launch_poolg_kernelx(uint32_t W, uint32_t k, uint32_t n_blocks, hipStream_t stream, const DevPipeline *pipe,
                                      const ResidentExec *execs, PoolRun *run, DevOut out);
+// ... and the builds that fold into a fused ungrouped aggregate sink (POLR_FUSE_AGG = 1: ...a, ...ax)
+int polr_poolg_occupancya(uint32_t k, uint32_t W);
+int polr_poolg_occupancyax(uint32_t k, uint32_t W);
+hipError_t polr_launch_poolg_kernela(uint32_t W, uint32_t k, uint32_t n_blocks, hipStream_t stream, const DevPipeline *pipe,
+                                     const ResidentExec *execs, PoolRun *run, DevOut out);
+hipError_t polr_launch_poolg_kernelax(uint32_t W, uint32_t k, uint32_t n_blocks, hipStream_t stream, const DevPipeline *pipe,
+                                      const ResidentExec *execs, PoolRun *run, DevOut out);
 #define DECL_POOL_K(KK)                                                                                                \
 	size_t polr_pool_flat_lds_bytes_k##KK(uint32_t waves_per_block, uint32_t table_dwords);                           \
 	size_t polr_pool_flat_wave_bytes_k##KK();                                                                         \
@@ -224,13 +231,21 @@ extern "C++" size_t polr_pool_lds_bytes(uint32_t k, uint32_t W) {
 }
 
 // ext: the pipeline has stages with an extension record (DevPipeline::ext) -> the POLR_EXT build of the kernel
-extern "C++" int polr_pool_occupancy(uint32_t k, uint32_t W, bool ext) {
+// agg: the launch's output has a fused ungrouped aggregate sink (DevOut::agg) -> the POLR_FUSE_AGG build
+extern "C++" int polr_pool_occupancy(uint32_t k, uint32_t W, bool ext, bool agg) {
+	if (agg) {
+		return ext ? polr_poolg_occupancyax(k, W) : polr_poolg_occupancya(k, W);
+	}
 	return ext ? polr_poolg_occupancyx(k, W) : polr_poolg_occupancy(k, W);
 }
 
 extern "C++" hipError_t polr_launch_pool_kernel(uint32_t W, uint32_t k, uint32_t n_blocks, hipStream_t stream,
                                                 const DevPipeline *pipe, const ResidentExec *execs, PoolRun *run,
                                                 DevOut out, bool ext) {
+	if (out.agg) { // (the row-id kernels have no fold: a fused ungrouped sink is filled by its own build)
+		return ext ? polr_launch_poolg_kernelax(W, k, n_blocks, stream, pipe, execs, run, out)
+		           : polr_launch_poolg_kernela(W, k, n_blocks, stream, pipe, execs, run, out);
+	}
 	return ext ? polr_launch_poolg_kernelx(W, k, n_blocks, stream, pipe, execs, run, out)
 	           : polr_launch_poolg_kernel(W, k, n_blocks, stream, pipe, execs, run, out);
 }

@@ -47,6 +47,9 @@
 #ifndef POLR_EXT
 #define POLR_EXT 1
 #endif
+#ifndef POLR_FUSE_AGG
+#define POLR_FUSE_AGG 0 // 1: final tuples are folded into a fused ungrouped aggregate sink (FusedAggSink), no row id is written
+#endif
 
 #define POLR_CONST __attribute__((address_space(4)))
 
@@ -126,6 +129,9 @@ struct GenCtx {
 	// output (row ids)
 	DevOut out;
 	OutState os;
+#if POLR_FUSE_AGG == 2
+	unsigned long long v_agg; // the wave's own aggregate cells: lane w = word w of a cell table (gen_agg_init / gen_agg_flush)
+#endif
 };
 
 // ---- keys --------------------------------------------------------------------------------------------------------------
@@ -311,6 +317,180 @@ __device__ __forceinline__ void gen_lookup_s16(const GenStage &s, const uint64_t
 }
 
 // ---- output --------------------------------------------------------------------------------------------------------------
+// The fused ungrouped sink (FusedAggSink, polr_device.h; polr_out_fuse_aggregate): one batch of final tuples is folded
+// into the aggregate cells of the workgroup's table -- PhysicalUngroupedAggregate::Sink over the chunk the batch would
+// have been.  Per aggregate: the row id in the argument's slot, the validity byte, the cell; one reduction over the wave;
+// the reduced value goes to the cell word (GenAggCells), in the end through relaxed agent-scope atomics whose results
+// nobody reads.  No LDS: every run kind, every W and the pieces work sharing hands over come through here.
+// The fold lives in a BUILD of its own (POLR_FUSE_AGG = 1: polr_poolg.hip is compiled once more per POLR_EXT, exported names
+// end in 'a'): as a run-time branch in gen_out_write, inlined or called, it cost the row-id kernels 3 to 13 VGPR spills
+// at W = 3 .. 6 (tools/spill_report.py) -- this way their code is what it was, and the fused kernels drop the chunk claims.
+// POLR_FUSE_AGG = 2 is the shape the library ships: the wave keeps a cell table of its own in ONE 64-bit vector register
+// -- lane w holds word w, as the stage state of GenCtx lives in lanes --, a batch adds its reduced values there with a
+// compare and a select, and the table goes to global memory once, where the wave leaves its loop beside out_close: one
+// atomic instruction per word kind and wave.  POLR_FUSE_AGG = 1 (make fuseagg-ab, tools/bench_fused_aggregate.py --ab) is
+// the other shape, kept as a measurement build: lane 0 updates the workgroup's table with one atomic per word and batch.
+// It lost by 0.2 - 0.4 ms on 8 ms runs (README.md, "Fused ungrouped aggregates").
+#if POLR_FUSE_AGG
+// where one reduced value of a batch goes: word w of the workgroup's table in global memory (lane 0; shape 1), or lane w
+// of the wave's own table (shape 2)
+struct GenAggCells {
+	POLR_GLOBAL unsigned long long *cells;
+	uint32_t lane;
+#if POLR_FUSE_AGG == 2
+	unsigned long long acc;
+#endif
+	__device__ __forceinline__ void add(uint32_t w, unsigned long long v) {
+#if POLR_FUSE_AGG == 2
+		acc = lane == w ? acc + v : acc;
+#else
+		if (lane == 0) {
+			__hip_atomic_fetch_add(&cells[w], v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+		}
+#endif
+	}
+	__device__ __forceinline__ void umin(uint32_t w, unsigned long long v) {
+#if POLR_FUSE_AGG == 2
+		acc = (lane == w && v < acc) ? v : acc;
+#else
+		if (lane == 0) {
+			__hip_atomic_fetch_min(&cells[w], v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+		}
+#endif
+	}
+	__device__ __forceinline__ void umax(uint32_t w, unsigned long long v) {
+#if POLR_FUSE_AGG == 2
+		acc = (lane == w && v > acc) ? v : acc;
+#else
+		if (lane == 0) {
+			__hip_atomic_fetch_max(&cells[w], v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+		}
+#endif
+	}
+};
+
+template <int W>
+__device__ __forceinline__ void gen_fold_aggregates(const FusedAggSink *sink, const Tuple<W> &t, bool valid, GenAggCells &to) {
+	const POLR_GLOBAL FusedAggSink *f = as_global(sink);
+	const uint32_t rows = (uint32_t)__popcll(__ballot(valid));
+	if (rows == 0u) {
+		return;
+	}
+	to.add(POLR_FUSEAGG_ROWS, (unsigned long long)rows);
+	const uint32_t n_aggs = uni(f->aggs.n);
+	for (uint32_t a = 0; a < n_aggs; a++) {
+		const uint32_t fn = uni(f->aggs.a[a].fn);
+		if (fn == POLR_DEV_AGG_COUNT_STAR) {
+			continue; // (the folded tuples: word 0)
+		}
+		DevCol src;
+		src.data = (const uint8_t *)uni64((uint64_t)f->aggs.a[a].src.data);
+		src.valid = (const uint8_t *)uni64((uint64_t)f->aggs.a[a].src.valid);
+		src.width = uni(f->aggs.a[a].src.width);
+		src.flags = uni(f->aggs.a[a].src.flags);
+		const uint32_t row = tuple_slot<W>(t, (int32_t)uni(f->aggs.a[a].slot));
+		// (inactive lanes carry arbitrary ids: nothing is read for them)
+		const bool part = valid && !(src.valid && !as_global(src.valid)[row]);
+		const long long v = part ? load_col_cell(src, row) : 0ll;
+		const uint32_t n = (uint32_t)__popcll(__ballot(part));
+		if (n == 0u) {
+			continue; // NULL arguments take no part
+		}
+		if (fn == POLR_DEV_AGG_SUM) {
+			// two limbs, so that plain 64-bit adds stay exact for 2^32 rows: the low 32 bits, and the (signed) rest
+			const unsigned long long lo = wave_sum64((unsigned long long)v & 0xFFFFFFFFull);
+			const unsigned long long hi = wave_sum64((unsigned long long)(v >> 32));
+			to.add(POLR_FUSEAGG_A(a), lo);
+			to.add(POLR_FUSEAGG_B(a), hi);
+		} else if (fn == POLR_DEV_AGG_MIN || fn == POLR_DEV_AGG_MAX) {
+			// signed order as unsigned order; a lane that takes no part holds the identity
+			const bool is_min = fn == POLR_DEV_AGG_MIN;
+			unsigned long long x = part ? ((unsigned long long)v ^ POLR_FUSEAGG_SIGN) : (is_min ? ~0ull : 0ull);
+#pragma unroll
+			for (int d = 32; d > 0; d >>= 1) {
+				const unsigned long long o = __shfl_xor(x, d, 64);
+				x = is_min ? (o < x ? o : x) : (o > x ? o : x);
+			}
+			if (is_min) {
+				to.umin(POLR_FUSEAGG_A(a), x);
+			} else {
+				to.umax(POLR_FUSEAGG_A(a), x);
+			}
+		}
+		to.add(POLR_FUSEAGG_N(a), (unsigned long long)n);
+	}
+}
+
+// this workgroup's cell table
+__device__ __forceinline__ POLR_GLOBAL unsigned long long *gen_agg_table(const FusedAggSink *sink) {
+	const POLR_GLOBAL FusedAggSink *f = as_global(sink);
+	return as_global((unsigned long long *)uni64((uint64_t)f->cells)) + (size_t)(blockIdx.x % uni(f->n_tables)) * uni(f->words_per_table);
+}
+
+#if POLR_FUSE_AGG == 2
+// how word w of a cell table is combined (polr_fuseagg_word_kind, restated per lane from the sink's functions)
+__device__ __forceinline__ uint32_t gen_agg_lane_kind(const FusedAggSink *sink, uint32_t w) {
+	const POLR_GLOBAL FusedAggSink *f = as_global(sink);
+	uint32_t kind = POLR_FUSEAGG_ADD;
+	if (w >= 1u && w < uni(f->words_per_table) && (w - 1u) % POLR_FUSEAGG_WORDS_PER_AGG == 0u) {
+		const uint32_t fn = f->aggs.a[(w - 1u) / POLR_FUSEAGG_WORDS_PER_AGG].fn;
+		kind = fn == POLR_DEV_AGG_MIN ? POLR_FUSEAGG_MIN : (fn == POLR_DEV_AGG_MAX ? POLR_FUSEAGG_MAX : POLR_FUSEAGG_ADD);
+	}
+	return kind;
+}
+// the wave's own table starts at "no rows" ...
+template <int W>
+__device__ __forceinline__ void gen_agg_init(GenCtx<W> &c) {
+	c.v_agg = 0ull;
+	if (c.out.agg && gen_agg_lane_kind(c.out.agg, c.lane) == POLR_FUSEAGG_MIN) {
+		c.v_agg = ~0ull;
+	}
+}
+// ... and is added to the workgroup's table when the wave leaves its loop: lane w updates word w, one atomic at most
+template <int W>
+__device__ __forceinline__ void gen_agg_flush(GenCtx<W> &c) {
+	if (c.out.agg == nullptr) {
+		return;
+	}
+	const uint32_t words = uni(as_global(c.out.agg)->words_per_table);
+	const uint32_t kind = gen_agg_lane_kind(c.out.agg, c.lane);
+	POLR_GLOBAL unsigned long long *cells = gen_agg_table(c.out.agg);
+	if (c.lane < words) {
+		if (kind == POLR_FUSEAGG_MIN) {
+			if (c.v_agg != ~0ull) {
+				__hip_atomic_fetch_min(&cells[c.lane], c.v_agg, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+			}
+		} else if (c.v_agg != 0ull) {
+			if (kind == POLR_FUSEAGG_MAX) {
+				__hip_atomic_fetch_max(&cells[c.lane], c.v_agg, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+			} else {
+				__hip_atomic_fetch_add(&cells[c.lane], c.v_agg, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+			}
+		}
+	}
+}
+#endif
+
+// ... gen_out_write of that build: the final tuples of the wave's current unit are folded, nothing is claimed or written
+template <int W>
+__device__ __forceinline__ void gen_out_write(GenCtx<W> &c, const Tuple<W> &t, bool valid) {
+	// (c.os.emit is the unit's flag alone here: no chunk is claimed, so nothing can overflow and clear it)
+	if (!c.os.emit || c.out.agg == nullptr) {
+		return;
+	}
+	GenAggCells to;
+	to.lane = c.lane;
+#if POLR_FUSE_AGG == 2
+	to.cells = nullptr;
+	to.acc = c.v_agg;
+	gen_fold_aggregates<W>(c.out.agg, t, valid, to);
+	c.v_agg = to.acc;
+#else
+	to.cells = gen_agg_table(c.out.agg);
+	gen_fold_aggregates<W>(c.out.agg, t, valid, to);
+#endif
+}
+#else
 // the final tuples of the wave's current unit go to its current output chunk (a DataChunk stream of row ids)
 template <int W>
 __device__ __forceinline__ void gen_out_write(GenCtx<W> &c, const Tuple<W> &t, bool valid) {
@@ -358,6 +538,7 @@ __device__ __forceinline__ void gen_out_write(GenCtx<W> &c, const Tuple<W> &t, b
 		done += take;
 	}
 }
+#endif
 
 // one sub-batch of (tuple, build id) pairs leaves stage `pos`: conditions, counter, next queue or output.
 // qs_next: fill of the next queue (updated); returns the number of tuples that passed (the sum of their multiplicities)

@@ -188,7 +188,17 @@ struct polr_out {
 	uint32_t fused_tables = 0, fused_groups = 0, fused_aggs = 0;
 	uint32_t fused_fn[8] = {};
 	bool fused_has_valid[8] = {};
+	// a fused UNGROUPED aggregate sink (polr_out_fuse_aggregate): the device descriptor, its cell tables (the plan's
+	// n_tables, and one more where the read-out combines them), and the plan the reset and the result follow
+	DevBuf<FusedAggSink> agg_dev;
+	DevBuf<unsigned long long> agg_cells;
+	PolrFuseAggPlan agg_plan = {};
 };
+
+// the output carries a fused sink of either kind: it holds cells, no row ids
+static inline bool out_has_fused_sink(const polr_out *o) {
+	return o->fused_dev.get() != nullptr || o->agg_dev.get() != nullptr;
+}
 
 #define POLR_FAIL(ctx_, code_, ...)                                                                                    \
 	do {                                                                                                               \
@@ -318,7 +328,7 @@ int polr_out_int_col(polr_pipeline *p, int32_t src_join, uint32_t src_col, OutCo
 
 // Only the flat pool kernel folds tuples into a fused GROUP BY sink (DevOut::fused).  The entry points that launch the
 // per-round path kernel refuse such an output before they enqueue anything: that kernel would write row ids instead and
-// leave the group cells empty.
+// leave the group cells empty.  The same holds for the generic pool kernel's ungrouped sink (DevOut::agg).
 #define POLR_REFUSE_FUSED(ctx_, out_)                                                                                  \
 	do {                                                                                                               \
 		if ((out_) && (out_)->fused_dev) {                                                                             \
@@ -326,6 +336,22 @@ int polr_out_int_col(polr_pipeline *p, int32_t src_join, uint32_t src_col, OutCo
 			          "%s: the output has a fused GROUP BY sink, which only the pool launch fills "                     \
 			          "(polr_mpx_run_resident*, polr_mpx_run_backpressure)",                                           \
 			          __func__);                                                                                       \
+		}                                                                                                              \
+		if ((out_) && (out_)->agg_dev) {                                                                               \
+			POLR_FAIL(ctx_, POLR_E_UNSUPPORTED,                                                                        \
+			          "%s: the output has a fused aggregate sink, which only the pool launch fills "                    \
+			          "(polr_mpx_run_resident*, polr_mpx_run_backpressure)",                                           \
+			          __func__);                                                                                       \
+		}                                                                                                              \
+	} while (0)
+
+// An output with a fused ungrouped sink holds aggregate cells and no row ids: the calls that read row ids refuse it
+#define POLR_REFUSE_AGG_CELLS(ctx_, out_)                                                                              \
+	do {                                                                                                               \
+		if ((out_)->agg_dev) {                                                                                         \
+			POLR_FAIL(ctx_, POLR_E_INVALID,                                                                            \
+			          "the output has a fused aggregate sink: it holds aggregate cells, no row ids "                    \
+			          "(polr_out_fused_aggregate_result)");                                                            \
 		}                                                                                                              \
 	} while (0)
 
@@ -340,7 +366,7 @@ hipError_t polr_launch_path_kernel(uint32_t W, uint32_t k, uint32_t n_blocks, ui
 struct PoolRun;
 uint32_t polr_pool_waves_per_block(uint32_t k, uint32_t W); // 0: does not fit at all
 size_t polr_pool_lds_bytes(uint32_t k, uint32_t W);
-int polr_pool_occupancy(uint32_t k, uint32_t W, bool ext);
+int polr_pool_occupancy(uint32_t k, uint32_t W, bool ext, bool agg = false); // agg: the build that fills a fused ungrouped sink
 hipError_t polr_launch_pool_kernel(uint32_t W, uint32_t k, uint32_t n_blocks, hipStream_t stream, const DevPipeline *pipe,
                                    const ResidentExec *execs, PoolRun *run, DevOut out, bool ext);
 size_t polr_pool_flat_lds_bytes(uint32_t k, uint32_t waves_per_block, uint32_t table_dwords);
@@ -356,6 +382,8 @@ void polr_launch_gather(hipStream_t stream, DevOut out, const uint64_t *chunk_ba
                         DevCol src, uint8_t *dst_data, uint8_t *dst_valid);
 void polr_launch_compact_ids(hipStream_t stream, DevOut out, const uint64_t *chunk_base, uint32_t n_chunks,
                              uint32_t *dst);
+// every cell table of the output's fused ungrouped sink back to "no rows" (polr_agg.hip; o->agg_cells is set)
+void polr_launch_fuseagg_fill(hipStream_t st, const polr_out *o);
 void polr_launch_reduce_counts(hipStream_t stream, const unsigned long long *src, uint64_t n_rounds, uint32_t k,
                                unsigned long long *dst);
 void polr_launch_deserialize_col(hipStream_t st, const uint8_t *rows, uint64_t n_rows, uint32_t row_width, uint32_t col,

@@ -380,7 +380,10 @@ static PoolShape pool_shape(polr_pipeline *p, bool materialize, const polr_out *
 	PoolShape sh;
 	// a bank of single-key unique-match joins takes the flat pipeline -- counting runs always, emitting runs when every
 	// join is a perfect table (polr_flat_device.h); it runs on the counting variant's descriptors either way
-	sh.flat = p->host_count.flat != 0 && (!materialize || p->flat_emit);
+	// (an output with a fused UNGROUPED sink is filled by the generic kernel alone -- gen_out_write is where its tuples
+	// are folded --, over the materialising descriptors, whatever the pipeline's emitting runs would otherwise take)
+	const bool agg_sink = materialize && out && out->agg_dev;
+	sh.flat = p->host_count.flat != 0 && (!materialize || p->flat_emit) && !agg_sink;
 	const DevPipeline &dp = (materialize && !sh.flat) ? p->host_mat : p->host_count;
 	sh.dp = &dp;
 	sh.wq = dp.W + (dp.mult ? 1u : 0u);
@@ -398,7 +401,7 @@ static PoolShape pool_shape(polr_pipeline *p, bool materialize, const polr_out *
 	}
 	sh.occ = sh.wpb == 0 ? 0
 	                     : (sh.flat ? polr_pool_flat_occupancy(dp.k, sh.wpb, dp.lds_table_dwords, materialize, sh.fused_words)
-	                                : polr_pool_occupancy(dp.k, sh.wq, dp.ext != 0));
+	                                : polr_pool_occupancy(dp.k, sh.wq, dp.ext != 0, agg_sink));
 	sh.router_areas = sh.flat && sh.occ >= 1 ? polr_pool_flat_router_areas(dp.k, sh.wpb, dp.lds_table_dwords) : 0u;
 	return sh;
 }

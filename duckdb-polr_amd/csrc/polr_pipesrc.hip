@@ -43,7 +43,7 @@ extern "C" int polr_pipeline_from_output(polr_out *o, void *stream, const polr_o
 	rq.has_cols = cols != nullptr;
 	rq.has_joins = joins != nullptr;
 	rq.has_paths = paths != nullptr;
-	rq.fused = o->fused_dev.get() != nullptr;
+	rq.fused = out_has_fused_sink(o);
 	rq.n_cols = n_cols;
 	auto plan_holder = std::make_unique<PolrPipesrcPlan>();
 	PolrPipesrcPlan &plan = *plan_holder;

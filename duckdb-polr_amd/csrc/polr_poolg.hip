@@ -2,11 +2,13 @@
 // pipeline's kernel (polr_gen_device.h: any key source, repeated build keys, composite keys, conditions, row-id output).
 // The flat pipeline's kernel: polr_pool.hip.  Protocol between routers and probe waves: polr_pool_device.h.
 //
-//   polr_pool_gen_kernel<W, POLR_EXT>    W = tuple slots carried between joins (1 = the probe row only ... 1 + k: every build id,
+//   polr_pool_gen_kernel<W, POOLG_VARIANT>    W = tuple slots carried between joins (1 = the probe row only ... 1 + k: every build id,
 //                              materialising runs); the number of joins k is a run-time value (<= 8).  512-thread
 //                              workgroups, two per CU when the queues allow it.
 // Built twice: POLR_EXT = 0 for the pipelines without packed composite keys or non-equality conditions, POLR_EXT = 1 for
-// those that have any (exported names end in 'x').
+// those that have any (exported names end in 'x').  And once more for each with POLR_FUSE_AGG = 2 (1: the measurement build): the kernels that fold
+// their final tuples into a fused ungrouped aggregate sink where the others write row ids (gen_out_write, polr_gen_device.h;
+// exported names end in 'a' / 'ax').  POOLG_VARIANT = POLR_EXT + 2 POLR_FUSE_AGG is the kernel template's second argument.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <stddef.h>
@@ -17,11 +19,19 @@
 #ifndef POLR_EXT
 #error "compile with -DPOLR_EXT=0|1"
 #endif
+#ifndef POLR_FUSE_AGG
+#define POLR_FUSE_AGG 0
+#endif
+#define POOLG_VARIANT (POLR_EXT + 2 * POLR_FUSE_AGG)
 
 #include "polr_pool_common.h"
 #include "polr_gen_device.h"
 
-#if POLR_EXT
+#if POLR_FUSE_AGG && POLR_EXT
+POOL_DIAG_ENTRY(polr_diag_router_gax, polr_diag_timeline_set_gax)
+#elif POLR_FUSE_AGG
+POOL_DIAG_ENTRY(polr_diag_router_ga, polr_diag_timeline_set_ga)
+#elif POLR_EXT
 POOL_DIAG_ENTRY(polr_diag_router_gx, polr_diag_timeline_set_gx)
 #else
 POOL_DIAG_ENTRY(polr_diag_router_g, polr_diag_timeline_set_g)
@@ -55,8 +65,8 @@ __device__ __forceinline__ void poolg_arrive(const ResidentExec *execs, const Po
 	v_cnt_lo = v_cnt_hi = 0;
 }
 
-// (EXT is part of the kernel's name: the two builds of this file are linked into one library)
-template <int W, int EXT>
+// (VARIANT is part of the kernel's name: the builds of this file are linked into one library)
+template <int W, int VARIANT>
 __global__ __launch_bounds__(64 * POOLG_WAVES, 4) void polr_pool_gen_kernel(const DevPipeline *__restrict__ pipe,
                                                                              const ResidentExec *__restrict__ execs, PoolRun *run,
                                                                              DevOut out, uint32_t lds_per_wave, uint32_t qcap) {
@@ -88,6 +98,9 @@ __global__ __launch_bounds__(64 * POOLG_WAVES, 4) void polr_pool_gen_kernel(cons
 	c.in_pos = c.in_end = 0;
 	c.out = out;
 	c.os = out_state_init();
+#if POLR_FUSE_AGG == 2
+	gen_agg_init<W>(c);
+#endif
 	const POLR_CONST StageDesc *stages = (const POLR_CONST StageDesc *)uni64((uint64_t)pipe->stages);
 	c.stages = stages;
 	PoolUnit u;
@@ -259,11 +272,18 @@ __global__ __launch_bounds__(64 * POOLG_WAVES, 4) void polr_pool_gen_kernel(cons
 		poolg_arrive(execs, u, ring, k, c.v_cnt_lo, c.v_cnt_hi, c.lane, POLR_POOL_TOKENS >> u.level);
 		TL_DONE(u)
 	}
+#if POLR_FUSE_AGG == 2
+	gen_agg_flush<W>(c); // (the wave's own aggregate cells go to the workgroup's table: polr_gen_device.h)
+#endif
 	out_close(out, c.os, c.lane);
 }
 
 // ---- launch ------------------------------------------------------------------------------------
-#if POLR_EXT
+#if POLR_FUSE_AGG && POLR_EXT
+#define POOLG_FN(stem) stem##ax
+#elif POLR_FUSE_AGG
+#define POOLG_FN(stem) stem##a
+#elif POLR_EXT
 #define POOLG_FN(stem) stem##x
 #else
 #define POOLG_FN(stem) stem
@@ -288,7 +308,7 @@ template <int W>
 static hipError_t poolg_prepare(size_t lds) {
 	static size_t lds_set = 0;
 	if (lds > lds_set) {
-		hipError_t e = hipFuncSetAttribute((const void *)polr_pool_gen_kernel<W, POLR_EXT>, hipFuncAttributeMaxDynamicSharedMemorySize,
+		hipError_t e = hipFuncSetAttribute((const void *)polr_pool_gen_kernel<W, POOLG_VARIANT>, hipFuncAttributeMaxDynamicSharedMemorySize,
 		                                   (int)lds);
 		if (e != hipSuccess) {
 			return e;
@@ -302,7 +322,7 @@ template <int W>
 static int poolg_occupancy_w(size_t lds, uint32_t waves) {
 	int blocks = 0;
 	if (poolg_prepare<W>(lds) != hipSuccess ||
-	    hipOccupancyMaxActiveBlocksPerMultiprocessor(&blocks, (const void *)polr_pool_gen_kernel<W, POLR_EXT>, (int)(64 * waves), lds) !=
+	    hipOccupancyMaxActiveBlocksPerMultiprocessor(&blocks, (const void *)polr_pool_gen_kernel<W, POOLG_VARIANT>, (int)(64 * waves), lds) !=
 	        hipSuccess) {
 		return 0;
 	}
@@ -318,7 +338,7 @@ static hipError_t poolg_launch_w(dim3 grid, dim3 block, size_t lds, hipStream_t 
 	}
 	void *args[] = {(void *)&pipe, (void *)&execs, (void *)&run, (void *)&out, (void *)&lds_per_wave, (void *)&qcap};
 	// (hipLaunchKernel returns the status of THIS launch: nothing is read from the thread's last-error slot)
-	return hipLaunchKernel((const void *)polr_pool_gen_kernel<W, POLR_EXT>, grid, block, args, lds, stream);
+	return hipLaunchKernel((const void *)polr_pool_gen_kernel<W, POOLG_VARIANT>, grid, block, args, lds, stream);
 }
 
 #define POOLG_FOR_EACH_W(M) M(1) M(2) M(3) M(4) M(5) M(6) M(7) M(8) M(9)

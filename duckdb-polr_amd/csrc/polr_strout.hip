@@ -194,6 +194,7 @@ extern "C" int polr_out_materialize_strings(polr_out *o, void *stream, int32_t s
 	if (o->fused_dev) {
 		POLR_FAIL(ctx, POLR_E_INVALID, "the output has a fused GROUP BY sink: it holds group cells, no row ids to materialise");
 	}
+	POLR_REFUSE_AGG_CELLS(ctx, o);
 	if (!dst_heap && heap_cap) {
 		POLR_FAIL(ctx, POLR_E_INVALID, "a heap of %llu bytes at NULL", (unsigned long long)heap_cap);
 	}

@@ -53,6 +53,7 @@ EXPORTS = [
     "polr_pipeline_from_output",
     "polr_ht_semi_filter",
     "polr_ht_column_stats", "polr_pipeline_column_stats", "polr_ht_finalize_auto_stats", "polr_col_stats_plan_info",
+    "polr_out_fuse_aggregate", "polr_out_fused_aggregate_result",
 ]
 
 
@@ -455,6 +456,8 @@ def load():
     L.polr_ht_encode_dictionary_ex.argtypes = [vp, u32, u32, vp, P(u32), P(u32), P(u32)]
     L.polr_ht_fetch_dictionary_codes.argtypes = [vp, u32, vp, vp, u64, vp, vp, u64, P(u64)]
     L.polr_out_fused_result.argtypes = [vp, vp, vp, C.c_uint64, vp]
+    L.polr_out_fuse_aggregate.argtypes = [vp, vp, u32]
+    L.polr_out_fused_aggregate_result.argtypes = [vp, vp, vp, u32]
     L.polr_mpx_run_resident.argtypes = [vp, vp, vp, vp, u32, vp, u32]
     L.polr_mpx_pool_info.argtypes = [vp, u32, vp, u32, P(PoolInfo)]
     L.polr_mpx_run_resident_ranges.argtypes = [vp, vp, vp, vp, u32, u32, vp, u32]
@@ -1060,6 +1063,7 @@ class Output:
         h = C.c_void_p()
         self.ctx.check(self.ctx.L.polr_out_create(pipe.h, chunk_capacity, max_chunks, C.byref(h)))
         self.h = h
+        self._fused_aggs = 0  # aggregates of the fused ungrouped sink attached through fuse_aggregate (0: none)
 
     def reset(self, stream=None):
         self.ctx.check(self.ctx.L.polr_out_reset(self.h, stream))
@@ -1187,6 +1191,24 @@ class Output:
         ka, n_groups = _group_keys(keys)
         self.ctx.check(self.ctx.L.polr_out_fuse_grouped(self.h, ka, len(keys), _agg_specs(specs), len(specs)))
         self._fused = (n_groups, len(specs))
+
+    def fuse_aggregate(self, specs):
+        """polr_out_fuse_aggregate: fold the join result into ungrouped aggregate cells inside the run (any pipeline; the
+        generic pool kernel; COUNT(*) / COUNT / SUM / MIN / MAX over integer columns).  specs as in aggregate(); specs=None
+        un-fuses.  reset() returns the cells to "no rows"; every pool run with this output adds to them."""
+        if not specs:
+            self.ctx.check(self.ctx.L.polr_out_fuse_aggregate(self.h, None, 0))
+            self._fused_aggs = 0
+            return
+        self.ctx.check(self.ctx.L.polr_out_fuse_aggregate(self.h, _agg_specs(specs), len(specs)))
+        self._fused_aggs = len(specs)
+
+    def fused_aggregate_result(self, stream=None):
+        """polr_out_fused_aggregate_result -> [python int or None], as aggregate()"""
+        na = self._fused_aggs  # (0, no sink attached through this object: the call refuses)
+        res = (AggValue * max(na, 1))()
+        self.ctx.check(self.ctx.L.polr_out_fused_aggregate_result(self.h, stream, res, na))
+        return [_agg_int(r) for r in res[:na]]
 
     def fused_result(self, stream=None):
         """polr_out_fused_result -> (values[n_groups][n_aggs], counts[n_groups][n_aggs], n_dropped), as aggregate_grouped"""

@@ -306,6 +306,66 @@ def _reference_form(probe, probe_cols, flt, order, joins, select=(), probe_strin
     return out
 
 
+# ---- the query's own sink, fused into the run ------------------------------------------------------------------------------------
+def fused_select_on_build_sides(wl):
+    """the whole select list of the workload lies on build sides (a probe-side VARCHAR column has no code column: such a
+    query keeps the materialising route and polr_out_aggregate_string)"""
+    return all(sj >= 0 for sj, _c in wl["select"])
+
+
+def run_fused_device(ctx, wl, paths, routing="adaptive_reinit", chunk_capacity=1024):
+    """SELECT COUNT(*), MIN(a), MIN(b), ... of a workload whose select list lies on build sides, in ONE pool launch and
+    without an output to size: every select column becomes a sorted dictionary code column of its build side (DICT_SORTED |
+    DICT_NULL_INVALID: the order of the codes is the order of the strings, a NULL string an invalid code), the output
+    carries a fused ungrouped sink -- COUNT(*) and MIN(code column) per select column --, one resident run fills it, and
+    the winning codes are turned back into strings (HashTable.dictionary_strings).
+    -> {"count_star": int, "select_min": [bytes or None] in the order of wl["select"], "rows_written": rows of the output}"""
+    from . import capi
+    if not fused_select_on_build_sides(wl):
+        raise ValueError("the select list names a probe-side column: polr_out_aggregate_string over emitted row ids")
+    # (the caller's workload stays as it is: the joins are shallow copies that carry the dictionary request)
+    wl = dict(wl, joins=[dict(j) for j in wl["joins"]])
+    for j in wl["joins"]:
+        j["dictionary"] = list(j.get("dictionary") or [])
+        j["dictionary_flags"] = dict(j.get("dictionary_flags") or {})
+    for sj, col in wl["select"]:
+        j = wl["joins"][sj]
+        if col not in j["dictionary"]:
+            j["dictionary"].append(col)
+        j["dictionary_flags"][col] = capi.DICT_SORTED | capi.DICT_NULL_INVALID
+    handles = []  # everything made here, closed in reverse order whatever happens
+    try:
+        joins = capi.build_joins(ctx, wl, auto=True)
+        handles += [ht for ht, _ in joins]
+        cols = list(wl["probe"]["cols"].values())
+        names = list(wl["probe"]["cols"].keys())
+        pipe = capi.Pipeline(ctx, cols, len(cols[0]), joins, paths)
+        handles.append(pipe)
+        flt = wl["probe"].get("filter")
+        if flt:
+            _n, n_chunks = pipe.scan_filter([(names.index(c), op, const) for c, op, const in flt])
+        else:
+            n_chunks = (len(cols[0]) + 1023) // 1024
+        out = capi.Output(pipe, chunk_capacity, 1)  # (nothing is written: the smallest output there is)
+        handles.append(out)
+        code_cols = [capi.dictionary_payload_index(wl["joins"][sj], col)[0] for sj, col in wl["select"]]
+        out.fuse_aggregate([("count_star", -1, 0)] + [("min", sj, cc) for (sj, _c), cc in zip(wl["select"], code_cols)])
+        mpx = capi.DeviceMultiplexer(pipe, routing)
+        handles.append(mpx)
+        if flt:
+            mpx.use_scan_chunks()
+        capi.run_resident([mpx], [(0, n_chunks)], out=out, reset=True, finish=True)
+        mpx.finish()
+        res = out.fused_aggregate_result()
+        mins = []
+        for (sj, _c), cc, code in zip(wl["select"], code_cols, res[1:]):
+            mins.append(None if code is None else joins[sj][0].dictionary_strings(cc, [code])[0])
+        return {"count_star": res[0], "select_min": mins, "rows_written": out.stats()[0]}
+    finally:
+        for h in reversed(handles):
+            h.close()
+
+
 # ---- chained plan: a query of more than MAX_JOINS joins as several pipelines --------------------------------------------------
 def chained_plan(q, max_joins=MAX_JOINS):
     """The whole query as STAGES of at most max_joins joins each, in the family's breadth-first order: stage 0 probes the

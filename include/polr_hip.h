@@ -829,6 +829,38 @@ int polr_out_aggregate_hashed_expr(polr_out *o, void *stream, const polr_group_k
 int polr_out_fuse_grouped(polr_out *o, const polr_group_key *keys, uint32_t n_keys, const polr_agg_spec *specs,
                           uint32_t n_aggs);
 int polr_out_fused_result(polr_out *o, void *stream, polr_agg_value *results, uint64_t n_groups, uint64_t *n_dropped);
+/* PhysicalUngroupedAggregate FUSED into the run, for ANY pipeline (every JOB query ends in SELECT MIN(a), MIN(b), ...;
+ * SSB flight 1 is ungrouped too): an output object with this sink makes the GENERIC pool kernel fold every final tuple
+ * into aggregate cells where it would have written the tuple's row ids -- no row id is written, no output has to be sized,
+ * no second pass reads the result back.
+ *  - polr_out_fuse_aggregate attaches 1..8 aggregates (COUNT(*), COUNT, SUM, MIN, MAX; polr_agg_spec as for
+ *    polr_out_aggregate) over integer columns of the probe table or of any build side, of 1, 2, 4 or 8 bytes.  Refused, in
+ *    this order: NULL o (POLR_E_INVALID); more than 8 aggregates (POLR_E_UNSUPPORTED); an output that carries a fused sink
+ *    already, this one or polr_out_fuse_grouped's -- an output carries at most one of the two (POLR_E_INVALID); then per
+ *    aggregate, in order, exactly the column rule of polr_out_aggregate with its wording: an unknown function, a column
+ *    out of range (POLR_E_INVALID), a VARCHAR or unsigned 8-byte column (POLR_E_UNSUPPORTED).  A VARCHAR column of a build
+ *    side goes through its sorted code column (polr_ht_encode_dictionary_ex with POLR_DICT_SORTED | POLR_DICT_NULL_INVALID:
+ *    MIN of the codes is the code of the MIN string; polr_ht_fetch_dictionary_codes turns it back).
+ *    specs == NULL or n_aggs == 0 un-fuses: the output collects row ids again.
+ *  - any pipeline is accepted.  While the sink is attached an emitting pool launch with this `out` runs on the generic kernel
+ *    over the materialising descriptors, also where the pipeline's emitting runs would take the flat kernel;
+ *    polr_pipeline_launch_info is not affected.
+ *  - the results are those of polr_out_aggregate over the rows the same run would have emitted: NULL arguments take no part,
+ *    COUNT is never NULL, SUM / MIN / MAX over no rows are is_null, SUM is exact in 128 bits; routing, the number of
+ *    executors and the run kind change nothing.
+ *  - every run with this `out` adds to the cells; polr_out_reset returns them to "no rows"; polr_out_fused_aggregate_result
+ *    reads them (n_aggs must be the sink's, else POLR_E_INVALID, as is an output without the sink) and may be called
+ *    repeatedly.  Only the pool launch fills the cells (polr_mpx_run_resident*, _ranges, _morsels, _stealing,
+ *    polr_mpx_run_backpressure): polr_probe_rounds, polr_probe_rounds_async, polr_mpx_run and polr_mpx_run_many return
+ *    POLR_E_UNSUPPORTED for such an `out` and enqueue nothing.
+ *  - the output holds no row ids: polr_out_fetch_ids, polr_out_materialize*, polr_out_aggregate* (every form),
+ *    polr_ht_from_output and polr_pipeline_from_output return POLR_E_INVALID; polr_out_stats reports no rows.
+ *  - the SUM cells are exact while fewer than 2^32 tuples have been folded since the last reset: with 2^32 or more and a SUM
+ *    in the sink the result call returns POLR_E_RANGE and leaves `results` untouched.
+ * Not provided: `left OP right` arguments, VARCHAR arguments (probe-side strings: polr_out_aggregate_string over emitted row
+ * ids), GROUP BY (polr_out_fuse_grouped on flat pipelines, polr_out_aggregate_grouped / _hashed elsewhere). */
+int polr_out_fuse_aggregate(polr_out *o, const polr_agg_spec *specs, uint32_t n_aggs);
+int polr_out_fused_aggregate_result(polr_out *o, void *stream, polr_agg_value *results, uint32_t n_aggs);
 /* ---- VARCHAR columns and their sink (every JOB query ends in MIN of a VARCHAR: benchmark/imdb_plan_cost/queries/18a.sql:1-3) --------
  * A width-16 column holds string_t cells (src/include/duckdb/common/types/string_type.hpp:23-28: 4-byte length; up to 12
  * characters inline; longer: a 4-byte prefix and an 8-byte pointer into a string heap).  RowOperations::Gather copies such

@@ -38,6 +38,12 @@ for _k in (2, 4, 6, 8):
     BUILDS["e_k%d" % _k] = ("polr_pool.hip", ["-DPOLR_K=%d" % _k, "-DPOLR_FLAT_EMIT=1"])
 BUILDS["g"] = ("polr_poolg.hip", ["-DPOLR_EXT=0"])
 BUILDS["g_x"] = ("polr_poolg.hip", ["-DPOLR_EXT=1"])
+# ... and the builds that fold into a fused ungrouped aggregate sink instead of writing row ids (the shipped shape of the fold)
+BUILDS["g_a"] = ("polr_poolg.hip", ["-DPOLR_EXT=0", "-DPOLR_FUSE_AGG=2"])
+BUILDS["g_ax"] = ("polr_poolg.hip", ["-DPOLR_EXT=1", "-DPOLR_FUSE_AGG=2"])
+# ... and the measurement build of the fold's other shape (make fuseagg-ab)
+BUILDS["g_a1"] = ("polr_poolg.hip", ["-DPOLR_EXT=0", "-DPOLR_FUSE_AGG=1"])
+BUILDS["g_ax1"] = ("polr_poolg.hip", ["-DPOLR_EXT=1", "-DPOLR_FUSE_AGG=1"])
 
 ROUTER_ENTRY = re.compile(r"^\s*s_setprio\s+3\b")
 STEPS_BEGIN = "polr-router-steps-begin"
