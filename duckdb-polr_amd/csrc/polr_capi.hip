@@ -960,6 +960,19 @@ int polr_pipeline_create(polr_ctx *ctx, const polr_col *probe_cols, uint32_t n_p
 	HIPCHK(ctx, hipMemcpy(p->stages_count, sd_count.data(), sd_count.size() * sizeof(StageDesc), hipMemcpyHostToDevice));
 	m.stages = p->stages_mat;
 	c.stages = p->stages_count;
+	if (plan.flat) {
+		// the counting variant's stages once more, in the flat kernel's own form (positions >= k stay zero: inert stages)
+		std::vector<FlatStageRec> fs((size_t)n_paths * POLR_KMAX);
+		memset(fs.data(), 0, fs.size() * sizeof(FlatStageRec));
+		for (uint32_t q = 0; q < n_paths; q++) {
+			for (uint32_t pos = 0; pos < k; pos++) {
+				fs[(size_t)q * POLR_KMAX + pos] = flat_stage_rec(sd_count[(size_t)q * POLR_KMAX + pos], (uint32_t)paths[q * k + pos]);
+			}
+		}
+		HIPCHK(ctx, p->stages_flat.alloc(fs.size()));
+		HIPCHK(ctx, hipMemcpy(p->stages_flat, fs.data(), fs.size() * sizeof(FlatStageRec), hipMemcpyHostToDevice));
+		c.flat_stages = p->stages_flat;
+	}
 	HIPCHK(ctx, p->dev_mat.alloc(1));
 	HIPCHK(ctx, p->dev_count.alloc(1));
 	HIPCHK(ctx, hipMemcpy(p->dev_mat, &m, sizeof(DevPipeline), hipMemcpyHostToDevice));

@@ -28,6 +28,7 @@
 #if defined(__HIPCC__) || defined(__HIP_DEVICE_COMPILE__)
 #define POLR_GLOBAL __attribute__((address_space(1)))
 #define POLR_LDS __attribute__((address_space(3)))
+#define POLR_CONST __attribute__((address_space(4))) // constant memory: a wave-uniform address is read through the scalar cache
 template <class T>
 __device__ __forceinline__ POLR_GLOBAL T *as_global(T *p) {
 	return (POLR_GLOBAL T *)p;
@@ -178,6 +179,38 @@ struct StageDesc {
 };
 #define STAGE_DESC_DWORDS (sizeof(StageDesc) / 4)
 
+// One stage of one join order as the FLAT pool kernel keeps it in scalar registers: exactly the words of a FlatStage
+// (polr_flat_device.h), written by the host when the pipeline is created (the descriptors are constant for the pipeline's
+// life) so that a probe wave whose next unit belongs to another join order fetches the K records of that order with
+// 16-byte-aligned loads issued back to back -- nothing to select, nothing to chase.  A record beyond the pipeline's last
+// join (position >= k) is all zero: an inert stage.
+struct FlatStageRec {
+	const uint32_t *keys;
+	const uint8_t *valid;
+	const uint32_t *table;
+	uint32_t kind_lds; // kind | lds_off1 << 8
+	uint32_t a, b;     // perfect: min, range (32-bit modular); hash: slot mask, range (unused)
+	uint32_t out_slot; // 1 + the join's index in the original order
+	uint32_t pad[2];
+};
+#define FLAT_STAGE_WORDS 10u // the dwords of a record that a FlatStage holds
+static_assert(sizeof(FlatStageRec) == 48 && sizeof(FlatStageRec) % 16 == 0, "three 16-byte granules per record");
+static_assert(offsetof(FlatStageRec, kind_lds) == 24 && offsetof(FlatStageRec, pad) == 4 * FLAT_STAGE_WORDS, "FlatStageRec layout");
+
+// the record of one resolved stage (host and device agree on it here, once)
+inline FlatStageRec flat_stage_rec(const StageDesc &d, uint32_t join_index) {
+	FlatStageRec r;
+	r.keys = (const uint32_t *)d.key_data[0];
+	r.valid = d.key_valid[0];
+	r.table = (const uint32_t *)d.table;
+	r.kind_lds = d.kind | (d.lds_off1 << 8);
+	r.a = d.kind == KIND_PERFECT ? (uint32_t)d.min_value : (uint32_t)d.mask;
+	r.b = (uint32_t)d.range;
+	r.out_slot = 1u + join_index;
+	r.pad[0] = r.pad[1] = 0;
+	return r;
+}
+
 struct DevPipeline {
 	uint32_t k;
 	uint32_t n_paths;
@@ -202,6 +235,7 @@ struct DevPipeline {
 	const uint32_t *lds_table_src[POLR_KMAX]; // HBM source of LDS table t
 	uint32_t lds_table_off[POLR_KMAX];        // dword offset in the LDS table area
 	uint32_t lds_table_len[POLR_KMAX];        // dwords
+	const FlatStageRec *flat_stages;          // [n_paths][POLR_KMAX]: `stages` in the flat kernel's own form
 };
 
 // one routed slice; must match polr_round in include/polr_hip.h

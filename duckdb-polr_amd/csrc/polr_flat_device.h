@@ -56,7 +56,7 @@ __device__ __host__ constexpr int flat_per_wave_dwords() {
 	return K <= 1 ? 0 : ((K - 1) * (flat_qcap<K>() + 1) * 2 + 3) / 4;
 }
 
-// scalar view of one stage (SGPRs; loaded from the StageDesc array in global memory through the scalar cache)
+// scalar view of one stage (SGPRs; loaded from the FlatStageRec array in global memory through the scalar cache)
 struct FlatStage {
 	const POLR_GLOBAL uint32_t *keys;
 	const POLR_GLOBAL uint8_t *valid;
@@ -66,18 +66,41 @@ struct FlatStage {
 	uint32_t out_slot;     // emitting runs: the output slot of this join's build id (1 + its index in the original order)
 };
 
-__device__ __forceinline__ FlatStage flat_load_stage(const StageDesc *d_generic, uint32_t join_index) {
-	const POLR_GLOBAL StageDesc *d = as_global(d_generic);
-	FlatStage s;
-	s.out_slot = 1u + join_index;
-	s.keys = as_global(uniptr((const uint32_t *)d->key_data[0]));
-	s.valid = as_global(uniptr(d->key_valid[0]));
-	s.table = as_global(uniptr((const uint32_t *)d->table));
-	const uint32_t kind = uni(d->kind);
-	s.kind_lds = kind | (uni(d->lds_off1) << 8);
-	s.a = kind == KIND_PERFECT ? uni((uint32_t)d->min_value) : uni((uint32_t)d->mask);
-	s.b = uni((uint32_t)d->range);
-	return s;
+// The join-order switch: the K records of join order `path` (FlatStageRec, polr_device.h: the host wrote exactly the
+// words of a FlatStage when the pipeline was created), ALL requested before the first is waited for -- 3 * K 16-byte
+// granules at a wave-uniform address of constant memory, so the requests go through the scalar cache straight into
+// scalar registers, with no branch between them: a position beyond the pipeline's last join reads its all-zero record
+// and stays inert.  (As first written every field of every StageDesc was a vector load of its own behind `p < k` and
+// `kind == KIND_PERFECT ? min : mask`, each waited for before the next: about 20 dependent round trips per switch at
+// K = 4.)  tools/mlp_report.py counts the requests and the waits between the two marker comments.
+template <int K>
+__device__ __forceinline__ void flat_load_stages(FlatStage (&st)[K], const FlatStageRec *recs_generic, uint32_t path) {
+	path = uni(path);
+	asm volatile("; polr-path-switch-begin" : "+s"(path)); // (the addresses hang on the marker: no request moves in front of it)
+	const POLR_CONST polr_u32x4 *src = (const POLR_CONST polr_u32x4 *)((uint64_t)recs_generic) + (size_t)path * (POLR_KMAX * 3);
+	polr_u32x4 w[K][3];
+#pragma unroll
+	for (int p = 0; p < K; p++) {
+#pragma unroll
+		for (int g = 0; g < 3; g++) {
+			w[p][g] = src[p * 3 + g];
+		}
+	}
+#pragma unroll
+	for (int p = 0; p < K; p++) {
+		asm volatile("" ::"s"(w[p][2].x), "s"(w[p][2].y)); // (the records' last words are asked for in front of the end marker too)
+	}
+	asm volatile("; polr-path-switch-end" ::: "memory");
+#pragma unroll
+	for (int p = 0; p < K; p++) {
+		st[p].keys = (const POLR_GLOBAL uint32_t *)(((uint64_t)w[p][0].y << 32) | w[p][0].x);
+		st[p].valid = (const POLR_GLOBAL uint8_t *)(((uint64_t)w[p][0].w << 32) | w[p][0].z);
+		st[p].table = (const POLR_GLOBAL uint32_t *)(((uint64_t)w[p][1].y << 32) | w[p][1].x);
+		st[p].kind_lds = w[p][1].z;
+		st[p].a = w[p][1].w;
+		st[p].b = w[p][2].x;
+		st[p].out_slot = w[p][2].y;
+	}
 }
 
 template <int K>
@@ -593,6 +616,7 @@ __device__ __forceinline__ void flat_sweep(FlatCtx<K> &c) {
 				}
 			});
 			asm volatile("; polr-sweep-sel-keys-end" ::: "memory");
+			__builtin_amdgcn_sched_barrier(0); // (what looks at the bytes stays behind the batch: its first wait is not part of it)
 			flat_static_for<1, K>([&](auto P) {
 				constexpr int p = decltype(P)::value;
 				// (every byte is looked at, with or without validity column: a load nobody waits for would be waited for at

@@ -38,7 +38,6 @@
 
 #include "polr_fromout_gather.h"
 
-#define POLR_CONST __attribute__((address_space(4)))
 
 typedef PolrFromoutDesc FromoutCol;
 

@@ -51,7 +51,6 @@
 #define POLR_FUSE_AGG 0 // 1: final tuples are folded into a fused ungrouped aggregate sink (FusedAggSink), no row id is written
 #endif
 
-#define POLR_CONST __attribute__((address_space(4)))
 
 #ifndef GEN_F
 #define GEN_F 2                 // candidates per lane and step

@@ -39,7 +39,6 @@
 #include "polr_htfilter_plan.h"
 #include "polr_internal.h"
 
-#define POLR_CONST __attribute__((address_space(4)))
 #define HTF_R 4u // words of a tile a wave of the compaction kernel serves: a lane has one row of each
 
 typedef PolrHtFilterDesc HtfCol;

@@ -155,6 +155,7 @@ struct polr_pipeline {
 	DevPipeline host_count, host_mat; // count-only (narrow tuples) and materialising (all ids) variants
 	DevBuf<DevPipeline> dev_count, dev_mat;
 	DevBuf<StageDesc> stages_count, stages_mat; // [n_paths][POLR_KMAX] each
+	DevBuf<FlatStageRec> stages_flat; // flat pipelines: stages_count as the flat pool kernel reads it
 	DevBuf<StageExt> stage_ext; // extension records of both variants (those stages that have one)
 	int blocks_per_cu_count = 0, blocks_per_cu_mat = 0;       // measured residency of the path kernel
 	uint32_t wpb_count = 0, wpb_mat = 0;                      // waves per workgroup (4, or fewer when the LDS queues are wide)

@@ -133,7 +133,7 @@ __global__ __launch_bounds__(1024) void polr_pool_flat_kernel(const DevPipeline 
 	c.pf_pos = ~0ull;
 	c.pf0 = make_uint4(0, 0, 0, 0);
 	c.pf1 = make_uint4(0, 0, 0, 0);
-	const StageDesc *stages = uniptr(pipe->stages);
+	const FlatStageRec *flat_stages = uniptr(pipe->flat_stages);
 	uint32_t cur_path = 0xFFFFFFFFu;
 	PoolUnit u, nxt;
 	PoolPoller pp;
@@ -143,17 +143,14 @@ __global__ __launch_bounds__(1024) void polr_pool_flat_kernel(const DevPipeline 
 	bool have = polr_pool_next_unit(pp, u, c.lane);
 	while (have) {
 		TL_GOT
+		const PoolArrival arrival = pool_arrival_of(execs, u, ring); // (asked for now, used when the unit is done)
 		if (u.path != cur_path) {
 			c.pf_pos = ~0ull; // (a prefetch belongs to one join order)
-#pragma unroll
-			for (int p = 0; p < K; p++) {
-				if (p < (int)k) {
-					c.st[p] = flat_load_stage(stages + (uint64_t)u.path * POLR_KMAX + p, uni(pipe->paths[u.path].order[p]));
-				}
-			}
+			flat_load_stages<K>(c.st, flat_stages, u.path);
 			flat_set_plain<K>(c);
 			cur_path = u.path;
 		}
+		TL_SWITCHED
 #if POLR_FLAT_EMIT
 		c.os.emit = u.emit != 0 && out.ids != nullptr && !c.os.overflow;
 #endif
@@ -164,16 +161,18 @@ __global__ __launch_bounds__(1024) void polr_pool_flat_kernel(const DevPipeline 
 			c.pf_pos = ~0ull;
 		}
 		flat_run_source<K>(c);
+		TL_SOURCED
 		// the source of this unit is used up: ONE look for the next unit before the queues drain, so that its claim and
 		// the first keys of its source travel while this unit's last sweeps do (a unit's fixed cost is mostly dependent
 		// round trips: measured 12.5 us + 6.3 ns per tuple)
-		const uint32_t peek = polr_pool_poll(pp, nxt, c.lane);
+		const uint32_t peek = polr_pool_look(pp, nxt);
+		TL_LOOKED
 		if (peek == POLR_POLL_WORK && nxt.path == cur_path) {
 			flat_prefetch_unit<K>(c, nxt.begin, nxt.count);
 		}
 		flat_run_drain<K>(c);
 		TL_RUN
-		pool_arrive<K>(execs, u, ring, c.k, c.cnt, c.lane);
+		pool_arrive<K>(arrival, c.k, c.cnt);
 		TL_DONE(u)
 		if (peek == POLR_POLL_NONE) {
 			have = polr_pool_next_unit(pp, nxt, c.lane);

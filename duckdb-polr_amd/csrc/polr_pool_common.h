@@ -110,17 +110,25 @@ __device__ __forceinline__ void pool_router_wave(const ResidentExec *execs, Pool
 }
 
 // diagnostic build only (-DPOLR_DIAG_TIMELINE, `make diag`; never compiled into the product): every probe wave writes
-// {began waiting, got the unit, finished it, exec << 40 | path << 32 | count} per unit, 100 MHz wall clock
+// {began waiting, got the unit, finished it, probing << 56 | exec << 40 | path << 32 | parts | count} per unit, 100 MHz wall
+// clock; parts (flat kernel): three saturating 5-bit fields of quarter microseconds -- the join-order switch, the look for
+// the next unit, the arrival -- so that probing - switch - look is the source and the drain (tools/diag_timeline.py)
 #ifdef POLR_DIAG_TIMELINE
 static __device__ unsigned long long *polr_diag_tl;
 static __device__ uint32_t polr_diag_tl_cap;
 #define TL_BEGIN(pool_wave_)                                                                                           \
 	unsigned long long tl_wait = wall_clock64();                                                                       \
-	unsigned long long tl_got = 0, tl_run = 0;                                                                         \
+	unsigned long long tl_got = 0, tl_run = 0, tl_sw = 0, tl_src = 0, tl_look = 0;                                     \
 	uint32_t tl_n = 0;                                                                                                 \
 	const uint32_t tl_wave = (pool_wave_);
 #define TL_GOT tl_got = wall_clock64();
 #define TL_RUN tl_run = wall_clock64();
+// (flat kernel) the unit's time in parts: .. join-order switch done .. source used up .. looked for the next unit
+#define TL_SWITCHED tl_sw = wall_clock64();
+#define TL_SOURCED tl_src = wall_clock64();
+#define TL_LOOKED tl_look = wall_clock64();
+/* a saturating 5-bit field of quarter microseconds (0 where the kernel does not take the two times) */
+#define TL_Q5(from_, to_) ((from_) && (to_) > (from_) ? (((to_) - (from_)) / 25ull > 31ull ? 31ull : ((to_) - (from_)) / 25ull) : 0ull)
 #define TL_DONE(u_)                                                                                                    \
 	if (polr_diag_tl && tl_n < polr_diag_tl_cap && (threadIdx.x & 63) == 0) {                                          \
 		unsigned long long *r_ = polr_diag_tl + ((size_t)tl_wave * polr_diag_tl_cap + tl_n) * 4;                       \
@@ -128,8 +136,10 @@ static __device__ uint32_t polr_diag_tl_cap;
 		r_[1] = tl_got;                                                                                                \
 		r_[2] = wall_clock64();                                                                                        \
 		const unsigned long long q_ = (tl_run - tl_got) / 25ull; /* quarter microseconds spent probing, 8 bits */      \
+		/* word 3: probing:8 | exec:16 | path:8 | arrival:5 | look:5 | switch:5 | count:17 (a unit is <= 65 536 tuples) */ \
 		r_[3] = ((q_ > 255ull ? 255ull : q_) << 56) | ((unsigned long long)((u_).exec & 0xFFFFu) << 40) |              \
-		        ((unsigned long long)(u_).path << 32) | (u_).count;                                                    \
+		        ((unsigned long long)(u_).path << 32) | (TL_Q5(tl_run, r_[2]) << 27) | (TL_Q5(tl_src, tl_look) << 22) | \
+		        (TL_Q5(tl_got, tl_sw) << 17) | ((u_).count & 0x1FFFFu);                                               \
 	}                                                                                                                  \
 	tl_n++;                                                                                                            \
 	tl_wait = wall_clock64();
@@ -153,30 +163,50 @@ static __device__ uint32_t polr_diag_tl_cap;
 #define TL_BEGIN(pool_wave_)
 #define TL_GOT
 #define TL_RUN
+#define TL_SWITCHED
+#define TL_SOURCED
+#define TL_LOOKED
 #define TL_DONE(u_)
 #endif
 
-// a probe wave reports a finished unit: its stage counters (returning atomics), then the arrival
+// Where a probe wave reports a unit: its counter bank [slot][ring & 7] and its arrival word.  Both hang on two pointers of
+// the executor's descriptor, which are asked for when the unit is TAKEN (wave-uniform words of constant memory: scalar
+// registers) -- they are home long before the unit ends, not one more round trip in front of its arrival.
+struct PoolArrival {
+	POLR_GLOBAL unsigned long long *bank;
+	POLR_GLOBAL unsigned long long *arrived;
+};
+__device__ __forceinline__ PoolArrival pool_arrival_of(const ResidentExec *execs, const PoolUnit &u, uint32_t ring) {
+	const POLR_CONST ResidentExec *xp = (const POLR_CONST ResidentExec *)uni64((uint64_t)execs) + uni(u.exec);
+	const uint32_t shard = uni(ring) & (POLR_POOL_SHARDS - 1u), slot = uni(u.slot);
+	PoolArrival a;
+	a.bank = as_global(xp->counts) + (size_t)slot * POLR_NSHARD * POLR_KMAX + (size_t)shard * POLR_KMAX;
+	a.arrived = as_global(&xp->sync->arrived[slot][shard].v);
+	return a;
+}
+
+// a probe wave reports a finished unit: its stage counters, then the arrival -- ONE round trip for the counters: lane p
+// adds counter p with one returning atomic instruction for all stages (a zero counter is left out by the lane mask), and
+// the arrival consumes what came back, so it is issued after the adds have been performed.  (As first written lane 0
+// issued up to K adds one after the other, each under its own branch and each waited for.)
 template <int K>
-__device__ __forceinline__ void pool_arrive(const ResidentExec *execs, const PoolUnit &u, uint32_t ring, uint32_t k,
-                                            uint32_t (&cnt)[K], uint32_t lane) {
-	const POLR_GLOBAL ResidentExec *xp = as_global(execs) + u.exec;
-	POLR_GLOBAL unsigned long long *bank = as_global((unsigned long long *)uni64((uint64_t)xp->counts)) +
-	                                       (size_t)u.slot * POLR_NSHARD * POLR_KMAX +
-	                                       (size_t)(ring & (POLR_POOL_SHARDS - 1u)) * POLR_KMAX;
-	POLR_GLOBAL ResidentSync *sync = as_global((ResidentSync *)uni64((uint64_t)xp->sync));
-	if (lane == 0) {
-		unsigned long long seen = 0;
+__device__ __forceinline__ void pool_arrive(const PoolArrival &at, uint32_t k, uint32_t (&cnt)[K]) {
+	const uint32_t lane = pool_lane_now(); // (asked for here: no lane mask of an arrival is worth a register pair across the unit)
+	uint32_t mine = 0;
 #pragma unroll
-		for (int p = 0; p < K; p++) {
-			if (p < (int)k && cnt[p]) {
-				// returning form: the arrival below consumes `seen`, so it is issued after the adds have been performed
-				seen |= __hip_atomic_fetch_add(&bank[p], (unsigned long long)cnt[p], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-			}
-		}
-		__hip_atomic_fetch_add(&sync->arrived[u.slot][ring & (POLR_POOL_SHARDS - 1u)].v, POLR_POOL_TOKENS + (seen >> 63), __ATOMIC_RELAXED,
-		                       __HIP_MEMORY_SCOPE_AGENT);
+	for (int p = 0; p < K; p++) {
+		mine = lane == (uint32_t)p ? cnt[p] : mine; // (the counters are wave-uniform: lane p gets counter p)
 	}
+	asm volatile("; polr-arrive-begin" ::: "memory");
+	unsigned long long seen = 0;
+	if (lane < k && mine) {
+		seen = __hip_atomic_fetch_add(&at.bank[lane], (unsigned long long)mine, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+	}
+	const unsigned long long late = __ballot((seen >> 63) != 0) != 0ull ? 1ull : 0ull;
+	if (lane == 0) {
+		__hip_atomic_fetch_add(at.arrived, POLR_POOL_TOKENS + late, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+	}
+	asm volatile("; polr-arrive-end" ::: "memory");
 #pragma unroll
 	for (int p = 0; p < K; p++) {
 		cnt[p] = 0;

@@ -23,9 +23,13 @@
 //               g1 = tag:16 | exec:16 | count:32
 //   tickets   mid, lo: a wave takes the next ticket with one returning atomic add on the queue's head and looks for the
 //             entry of that ticket (tickets past the tail are simply not written yet; it keeps the ticket while it
-//             serves other queues); hi: never waited on -- taken with a CAS on hi_head only while hi_head < hi_tail,
-//             and only by the waves whose number matches the ticket's in the low `lottery` bits.  heads/tails are
-//             monotonic across runs (tags never repeat within 65535 laps).
+//             serves other queues).  A wave of the flat kernel that has used up a unit's source takes the tickets it
+//             lacks together and then looks at the ring with ONE load -- hi_head, hi_tail and the two granules of both
+//             tickets' entries, a lane per word (polr_pool_look); an idle wave, and every wave of the generic kernel,
+//             goes through the queues one after the other (polr_pool_poll).
+//             hi: never waited on -- taken with a CAS on hi_head only while hi_head < hi_tail, and only by the waves
+//             whose number matches the ticket's in the low `lottery` bits.  heads/tails are monotonic across runs (tags
+//             never repeat within 65535 laps).
 //   slots     POLR_SLOTS (4) rounds of one executor can be in flight: the front one decided, the others rehearsed
 //             ahead on a shadow of the state while their decisions cannot depend on intermediates still outstanding
 //             (polr_can_speculate); each slot has its own counter bank and arrival counters.
@@ -146,7 +150,9 @@ struct PoolRun {
 };
 
 __device__ __forceinline__ uint32_t polr_pool_tag(unsigned long long ticket, uint32_t cap) {
-	return (uint32_t)((ticket / cap) % 65535ull) + 1u;
+	// (cap is a power of two: the lap is a shift -- a 64-bit division by a run-time value is a long routine, and every look
+	// of every probe wave computes two tags)
+	return (uint32_t)((ticket >> __builtin_ctz(cap)) % 65535ull) + 1u;
 }
 
 __device__ __forceinline__ unsigned long long polr_pool_g0(uint32_t tag, uint32_t kind, uint32_t slot, uint32_t emit,
@@ -323,6 +329,22 @@ __device__ __forceinline__ bool polr_pool_decode(unsigned long long g0, unsigned
 	return true;
 }
 
+// This lane's number, computed where it is asked for.  Inside a loop every phase asks again: addresses and lane masks
+// derived from a lane number that is computed once in front of the loop are loop invariants the compiler keeps alive
+// across everything else the loop does -- in the router's step loop the last values it spilled, in the probe loop (a
+// look's six addresses, hoisted out of all its inlined copies) the difference between 0 and 148 spilled registers.
+__device__ __forceinline__ uint32_t pool_lane_now() {
+	uint32_t l;
+	asm volatile("v_mbcnt_lo_u32_b32 %0, -1, 0\n\tv_mbcnt_hi_u32_b32 %0, -1, %0" : "=v"(l));
+	return l;
+}
+
+// lane `src`'s 8-byte value, in scalar registers
+__device__ __forceinline__ unsigned long long polr_lane64(unsigned long long v, int src) {
+	return ((unsigned long long)(uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)(v >> 32), src) << 32) |
+	       (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)v, src);
+}
+
 // one lane: take a ticket of a non-blocking queue if it has one (compare-and-swap on its head while head < tail) and
 // read its entry (being written by the router that reserved it)
 __device__ __forceinline__ bool polr_pool_try_claim(POLR_GLOBAL unsigned long long *head, POLR_GLOBAL unsigned long long *tail,
@@ -356,6 +378,61 @@ __device__ __forceinline__ bool polr_pool_try_claim(POLR_GLOBAL unsigned long lo
 	return true;
 }
 
+// the whole wave, head `hh` and tail `ht` of a non-blocking queue as the look saw them (wave-uniform): take ticket hh if
+// the queue has one for this wave (compare-and-swap on its head while head < tail) and read its entry (being written by
+// the router that reserved it).  g0 / g1 / tag come back wave-uniform.
+__device__ __forceinline__ bool polr_pool_claim_at(POLR_GLOBAL unsigned long long *head, unsigned long long hh, unsigned long long ht,
+                                                    POLR_GLOBAL PoolEntry *entries, uint32_t cap, uint32_t wave_in_ring,
+                                                    uint32_t lottery, bool anybody, unsigned long long timeout_ticks, uint32_t lane,
+                                                    unsigned long long &g0, unsigned long long &g1, uint32_t &tag) {
+	// the lottery keeps the compare-and-swap storm of a published unit small; `anybody` lifts it for a wave that has been
+	// idle for a while: the waves a ticket is meant for may not be on the device (another launch is holding their
+	// slots -- two full-size launches side by side), and a ticket nobody may take blocks every entry behind it
+	if (hh >= ht || (!anybody && (((uint32_t)hh ^ wave_in_ring) & (lottery - 1u)) != 0)) {
+		return false;
+	}
+	// the swap (lane 0) and the entry at the observed head (lanes 1 and 2, a granule each) travel together: one round
+	// trip.  The entry counts only if the swap succeeded -- then ticket hh is this wave's, and an entry that carries
+	// hh's lap tag in both granules is the one written for it.
+	POLR_GLOBAL PoolEntry *e = entries + (hh & (cap - 1u));
+	tag = polr_pool_tag(hh, cap);
+	POLR_GLOBAL unsigned long long *ea = (POLR_GLOBAL unsigned long long *)((uint64_t)e + ((lane & 2u) << 2)); // lane 1: g0, lane 2: g1
+	unsigned long long ev = 0;
+	uint32_t won = 0;
+	if (lane == 1 || lane == 2) {
+		ev = __hip_atomic_load(ea, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+	}
+	if (lane == 0) {
+		unsigned long long expect = hh;
+		won = __hip_atomic_compare_exchange_strong(head, &expect, hh + 1, __ATOMIC_RELAXED, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)
+		          ? 1u
+		          : 0u;
+	}
+	if (!__builtin_amdgcn_readfirstlane(won)) {
+		return false;
+	}
+	g0 = polr_lane64(ev, 1);
+	g1 = polr_lane64(ev, 2);
+	if ((uint32_t)(g0 >> 48) != tag || (uint32_t)(g1 >> 48) != tag) {
+		// still being written by the router that reserved it: lane 0 looks again until it is there (or the watchdog's time
+		// is up: the caller finds the tags wrong)
+		if (lane == 0) {
+			const unsigned long long t1 = wall_clock64();
+			while (true) {
+				g0 = __hip_atomic_load(&e->g0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+				g1 = __hip_atomic_load(&e->g1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+				if (((uint32_t)(g0 >> 48) == tag && (uint32_t)(g1 >> 48) == tag) || wall_clock64() - t1 > timeout_ticks) {
+					break;
+				}
+				__builtin_amdgcn_s_sleep(1);
+			}
+		}
+		g0 = uni64(g0);
+		g1 = uni64(g1);
+	}
+	return true;
+}
+
 // What a probe wave knows about its ring between polls: the queue bases and the tickets it holds (a wave that holds a
 // not-yet-written mid / lo ticket serves hi units meanwhile, so the tickets are kept across calls).
 // (all accesses name the global address space: a probe wave polls between LDS-heavy units, see polr_device.h)
@@ -365,7 +442,17 @@ struct PoolPoller {
 	POLR_GLOBAL PoolEntry *hi_q, *mid_q, *lo_q;
 	uint32_t lo_cap, hi_cap, wave_in_ring, lottery, idle_sleep;
 	uint32_t idle_polls;                      // polls since this wave last had a unit
-	unsigned long long lo_ticket, mid_ticket; // ~0ull: none
+	// The tickets (lane 0's value counts; ~0ull: none).  A ticket is taken by the look that needs it, never while the wave
+	// is busy with a unit's source: an entry published for a ticket waits for the holder's current unit, so a ticket taken
+	// the moment the last one is consumed -- held through the whole next unit while idle waves sit on later tickets --
+	// is head-of-line blocking where few units are in flight.  Invariants, whichever of the two looks below is used:
+	//   * every wave leaves holding exactly ONE mid ticket and NO lo ticket (a look takes the mid ticket before it can meet
+	//     the EXIT entry on lo, and the EXIT entry consumes the lo ticket): polr_pool_publish_exit accounts for exactly
+	//     that -- one EXIT entry on lo and one skipped ticket on mid per probe wave of the ring;
+	//   * a ticket whose entry is not written yet stays held, whatever else the wave serves meanwhile;
+	//   * a wave that leaves on `abort` or a watchdog leaves tickets behind: the rings of a run that was given up are
+	//     zeroed by the host before the next one.
+	unsigned long long lo_ticket, mid_ticket;
 	unsigned long long timeout_ticks;
 };
 
@@ -373,6 +460,10 @@ __device__ __forceinline__ void polr_pool_poller_init(PoolPoller &pp, PoolRun *r
                                                       uint32_t ring, uint32_t lo_cap, uint32_t hi_cap,
                                                       uint32_t wave_in_ring, uint32_t lottery, uint32_t idle_sleep,
                                                       unsigned long long timeout_ticks) {
+	// (a wave's ring and its number in the ring are wave-uniform, but they come from the thread number: said here, so that
+	// what a look decides from them -- and with it the unit it hands out -- stays in scalar registers)
+	ring = uni(ring);
+	wave_in_ring = uni(wave_in_ring);
 	pp.run = as_global(run_generic);
 	pp.ctl = as_global(&sync_generic->ctl[ring]);
 	pp.hi_q = as_global(polr_pool_hi(sync_generic, ring, lo_cap, hi_cap));
@@ -445,6 +536,77 @@ __device__ __forceinline__ uint32_t polr_pool_poll(PoolPoller &pp, PoolUnit &u, 
 	g1 = ((unsigned long long)__builtin_amdgcn_readfirstlane((uint32_t)(g1 >> 32)) << 32) |
 	     __builtin_amdgcn_readfirstlane((uint32_t)g1);
 	tag = __builtin_amdgcn_readfirstlane(tag);
+	if (!polr_pool_decode(g0, g1, tag, u)) {
+		return POLR_POLL_LEAVE; // (a hi entry that never arrived: watchdog)
+	}
+	return u.kind == POLR_POOL_KIND_EXIT ? POLR_POLL_LEAVE : POLR_POLL_WORK;
+}
+
+// The same look for a wave that has just used up a unit's source and looks ONCE before its queues drain (the flat kernel's
+// peek): two round trips instead of polr_pool_poll's three to five.  First the tickets it does not hold, both adds together
+// (a wave that took a lo unit last time holds none for lo; polr_pool_poll would take it only after hi and mid gave
+// nothing -- this look takes it at once, and holds it as polr_pool_poll holds a ticket whose entry is not written).  Then
+// everything it wants to see has a known address: lane 0 asks for hi_head, lane 1 for hi_tail, lanes 2 / 3 for the two
+// granules of the mid ticket's entry, lanes 4 / 5 for those of the lo ticket's -- one load instruction, a lane per word --
+// and the priority hi > mid > lo is applied to what came back.  A hi claim sends its compare-and-swap and the load of the
+// entry at the observed head together.  An idle wave goes on with polr_pool_poll (polr_pool_next_unit): its looks stay as
+// far apart as they were.  tools/mlp_report.py counts loads and waits between the two markers.
+__device__ __forceinline__ uint32_t polr_pool_look(PoolPoller &pp, PoolUnit &u) {
+	static_assert(offsetof(PoolRingCtl, hi_tail) == offsetof(PoolRingCtl, hi_head) + 8 && offsetof(PoolEntry, g1) == 8, "a lane per word");
+	const uint32_t l = pool_lane_now(); // (asked for here: nothing of a look is to be kept in registers from unit to unit)
+	asm volatile("; polr-poll-begin" ::: "memory");
+	if (l == 0) {
+		if (pp.mid_ticket == ~0ull) {
+			pp.mid_ticket = __hip_atomic_fetch_add(&pp.ctl->mid_head, 1ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+		}
+		if (pp.lo_ticket == ~0ull) {
+			pp.lo_ticket = __hip_atomic_fetch_add(&pp.ctl->lo_head, 1ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+		}
+	}
+	const unsigned long long mt = uni64(pp.mid_ticket), lt = uni64(pp.lo_ticket);
+	const uint32_t mid_tag = polr_pool_tag(mt, pp.lo_cap), lo_tag = polr_pool_tag(lt, pp.lo_cap);
+	POLR_GLOBAL PoolEntry *me = pp.mid_q + (mt & (pp.lo_cap - 1u));
+	POLR_GLOBAL PoolEntry *le = pp.lo_q + (lt & (pp.lo_cap - 1u));
+	const uint64_t words = l < 2 ? (uint64_t)&pp.ctl->hi_head : (l < 4 ? (uint64_t)me : (uint64_t)le);
+	POLR_GLOBAL unsigned long long *at = (POLR_GLOBAL unsigned long long *)(words + ((l & 1u) << 3));
+	unsigned long long v = 0;
+	if (l < 6) {
+		v = __hip_atomic_load(at, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+	}
+	const uint64_t tagged = __ballot(l >= 2 && l < 6 && (uint32_t)(v >> 48) == (l < 4 ? mid_tag : lo_tag));
+	asm volatile("; polr-poll-end" ::"s"(tagged) : "memory"); // (the tickets' adds, their wait, the load and its wait lie in front of this)
+	unsigned long long g0 = 0, g1 = 0;
+	uint32_t tag = 0, got = 0;
+	if (polr_pool_claim_at(&pp.ctl->hi_head, polr_lane64(v, 0), polr_lane64(v, 1), pp.hi_q, pp.hi_cap, pp.wave_in_ring, pp.lottery,
+	                       pp.idle_polls >= POLR_POOL_LOTTERY_PATIENCE && (pp.idle_polls & 15u) == 15u, pp.timeout_ticks, l, g0, g1,
+	                       tag)) {
+		got = 1;
+	} else if ((tagged & 0xCull) == 0xCull) {
+		got = 3;
+		g0 = polr_lane64(v, 2);
+		g1 = polr_lane64(v, 3);
+		tag = mid_tag;
+		pp.mid_ticket = ~0ull;
+	} else if ((tagged & 0x30ull) == 0x30ull) {
+		got = 2;
+		g0 = polr_lane64(v, 4);
+		g1 = polr_lane64(v, 5);
+		tag = lo_tag;
+		pp.lo_ticket = ~0ull;
+	}
+	// Nothing of a look is in flight behind it (everything it asked for has been looked at), and the compiler is told so:
+	// a load it had to assume pending on some path through the look's branches made it wait for ALL loads in the middle
+	// of the next sweep's gathers, the prefetched keys of the next unit among them (tests/test_mlp_report.py).
+	__builtin_amdgcn_s_waitcnt(0x0F70); // vmcnt(0)
+	got = uni(got);
+	if (!got) {
+		pp.idle_polls++;
+		return POLR_POLL_NONE;
+	}
+	pp.idle_polls = 0;
+	g0 = uni64(g0); // (wave-uniform already; said where the three ways meet, so that the unit's fields stay scalar)
+	g1 = uni64(g1);
+	tag = uni(tag);
 	if (!polr_pool_decode(g0, g1, tag, u)) {
 		return POLR_POLL_LEAVE; // (a hi entry that never arrived: watchdog)
 	}
@@ -526,15 +688,6 @@ static __device__ __forceinline__ void polr_pool_route_lane0(POLR_LDS uint32_t *
 		round->path = path_plus1 - 1u;
 		m->last_path = path_plus1 - 1u;
 	}
-}
-
-// This lane's number, computed where it is asked for.  Inside the step loop every phase asks again: addresses derived
-// from a lane number that is computed once in front of the loop are loop invariants the compiler keeps alive across
-// the routing arithmetic -- the last values it spilled there.
-__device__ __forceinline__ uint32_t pool_lane_now() {
-	uint32_t l;
-	asm volatile("v_mbcnt_lo_u32_b32 %0, -1, 0\n\tv_mbcnt_hi_u32_b32 %0, -1, %0" : "=v"(l));
-	return l;
 }
 
 // Stealing mode (polr_steal.h): this executor's grant is used up (or it has none yet).  Full wave.  Claim the next

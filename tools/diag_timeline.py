@@ -1,7 +1,10 @@
 """diagnostic: reads the per-unit records of one instrumented pass (POLR_DIAG_TIMELINE=<file.npz> python bench.py ...,
 library from `make -C duckdb-polr_amd diag`) and prints where the probe waves' time went.
 
-records per wave: [began waiting, got the unit, finished it, exec << 40 | path << 32 | count], 100 MHz wall clock"""
+records per wave: [began waiting, got the unit, finished it, probing << 56 | exec << 40 | path << 32 | parts | count],
+100 MHz wall clock.  parts (flat kernel; zero in records of older builds and of the generic kernel): three saturating 5-bit
+fields of quarter microseconds -- arrival << 27 | look for the next unit << 22 | join-order switch << 17 -- and count in
+the low 17 bits (a unit is at most 65 536 tuples)."""
 import sys
 
 import numpy as np
@@ -12,7 +15,10 @@ waves = np.nonzero(used)[0]
 print("probe waves that ran units: %d of %d; units: %d" % (len(waves), len(used), int(used.sum())))
 rec = np.concatenate([tl[w, :used[w]] for w in waves]).astype(np.int64)
 wait0, got, done, meta = rec[:, 0], rec[:, 1], rec[:, 2], rec[:, 3]
-count = meta & 0xFFFFFFFF
+count = meta & 0x1FFFF
+switch_q = (meta >> 17) & 0x1F  # quarter microseconds, saturating at 7.75 us
+look_q = (meta >> 22) & 0x1F
+arrive_q = (meta >> 27) & 0x1F
 path = (meta >> 32) & 0xFF
 probe_q = (meta >> 56) & 0xFF  # quarter microseconds between "got the unit" and "pipeline empty" (saturates at 63.75)
 t0 = wait0.min()
@@ -34,6 +40,19 @@ for lo, hi in ((0, 512), (512, 4096), (4096, 16384), (16384, 1 << 30)):
               "counters + arrival), ns/tuple %.3f" %
               (lo, hi, m.sum(), count[m].sum(), 100 * d.sum() / busy, d.mean(), probe_q[m].mean() / 4.0,
                1e3 * d.sum() / count[m].sum()))
+# the fixed cost in parts: units of up to 512 tuples (exploration slices: almost all fixed cost)
+m = (count > 0) & (count <= 512)
+if m.any() and (switch_q | look_q | arrive_q).any():
+    sw = switch_q[m] > 0
+    print("units of up to 512 tuples, mean us: probing %.2f = switch %.2f (%.0f%% of them switch: %.2f each) + look %.2f + source "
+          "and drain %.2f; arrival %.2f; saturated fields: switch %d look %d arrival %d of %d" %
+          (probe_q[m].mean() / 4.0, switch_q[m].mean() / 4.0, 100.0 * sw.mean(), switch_q[m][sw].mean() / 4.0 if sw.any() else 0.0,
+           look_q[m].mean() / 4.0, (probe_q[m] - switch_q[m] - look_q[m]).mean() / 4.0, arrive_q[m].mean() / 4.0,
+           int((switch_q[m] == 31).sum()), int((look_q[m] == 31).sum()), int((arrive_q[m] == 31).sum()), int(m.sum())))
+    allm = count > 0
+    print("all units, mean us: switch %.2f look %.2f arrival %.2f; sum over all units as a share of busy time: %.1f%%" %
+          (switch_q[allm].mean() / 4.0, look_q[allm].mean() / 4.0, arrive_q[allm].mean() / 4.0,
+           100.0 * (switch_q[allm] + look_q[allm] + arrive_q[allm]).sum() / 4.0 / busy))
 for p in np.unique(path):
     m = (path == p) & (count >= 4096)
     if m.any():
