@@ -10,6 +10,11 @@
 // column: one pass gathers x by row id and reduces it -- thread-local, wave shuffle, one partial per
 // workgroup -- and only the per-workgroup partials (a few KB) leave the device; the host adds them up in
 // 128-bit arithmetic.  Algorithmic bytes: 4 (row id) + width [+ 1 validity] per output row and aggregate.
+//
+// What a sink refuses, in which order and with which words, is polr_agg_plan.h (host code without HIP): every sink here
+// resolves the columns its request names, describes them to its plan, and builds its device structs from what the plan
+// accepted.  Behind the plan a sink fails only for HIP errors and for what the device alone can tell: arguments out of
+// range, too many groups, a string arena too small, a string column whose heap never came (polr_strheap.hip).
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <string.h>
@@ -19,6 +24,7 @@
 #include <vector>
 
 #include "polr_internal.h"
+#include "polr_strcmp.h" // str_byte
 
 struct AggPartial {
 	unsigned long long sum_lo; // two's complement 128-bit sum, low limb
@@ -206,112 +212,44 @@ __global__ __launch_bounds__(256) void polr_agg_kernel(DevOut out, uint32_t n_ch
 	}
 }
 
-int polr_out_col(polr_pipeline *p, int32_t src_join, uint32_t src_col, OutCol *c, const char *what, uint32_t idx) {
-	if (src_join < 0) {
-		if (src_col >= p->n_probe_cols) {
-			POLR_FAIL(p->ctx, POLR_E_INVALID, "%s %u: probe column %u out of range", what, idx, src_col);
-		}
-		c->col = &p->probe_cols[src_col];
-		c->slot = 0;
-	} else {
-		if ((uint32_t)src_join >= p->k || src_col >= p->hts[src_join]->n_payload) {
-			POLR_FAIL(p->ctx, POLR_E_INVALID, "%s %u: build column (%d,%u) out of range", what, idx, src_join, src_col);
-		}
-		c->col = &build_col(p->hts[src_join], src_col);
-		c->slot = 1 + (uint32_t)src_join;
+static_assert(POLR_MAX_AGGS == POLR_AGG_MAX_AGGS && POLR_MAX_GROUP_KEYS == POLR_AGG_MAX_GROUP_KEYS, "the sinks' plan: polr_agg_plan.h");
+
+// a sink's plan (polr_agg_plan.h): its NULL-argument refusals carry no message and leave the context's error as it was
+#define POLR_TRY_SINK_PLAN(ctx_, plan_, call_)                                                                         \
+	do {                                                                                                               \
+		const int sink_rc_ = (call_);                                                                                  \
+		if (sink_rc_ && !(plan_).err[0]) {                                                                             \
+			return sink_rc_;                                                                                           \
+		}                                                                                                              \
+		POLR_TRY_PLAN(ctx_, plan_, sink_rc_);                                                                          \
+	} while (0)
+
+PolrAggCol polr_out_describe_col(polr_pipeline *p, int32_t src_join, uint32_t src_col, OutCol *c) {
+	PolrAggCol d = {false, 0, 0};
+	if (src_join < 0 ? src_col >= p->n_probe_cols : ((uint32_t)src_join >= p->k || src_col >= p->hts[src_join]->n_payload)) {
+		return d;
 	}
+	c->col = src_join < 0 ? &p->probe_cols[src_col] : &build_col(p->hts[src_join], src_col);
+	c->slot = src_join < 0 ? 0 : 1 + (uint32_t)src_join;
 	c->dev = dev_col(*c->col);
-	return POLR_OK;
+	d.in_range = true;
+	d.width = c->dev.width;
+	d.flags = c->dev.flags;
+	return d;
 }
 
-int polr_out_int_col(polr_pipeline *p, int32_t src_join, uint32_t src_col, OutCol *c, const char *what, uint32_t idx) {
-	int rc = polr_out_col(p, src_join, src_col, c, what, idx);
-	if (!rc && (c->dev.width > 8 || (c->dev.width == 8 && !(c->dev.flags & 1u)))) {
-		POLR_FAIL(p->ctx, POLR_E_UNSUPPORTED, "%s %u: only integer columns of up to 8 bytes (signed if 8)", what, idx);
-	}
-	return rc;
-}
-
-// one aggregate as the sink kernels read it: POLR_E_INVALID for an unknown function or a column out of range,
-// POLR_E_UNSUPPORTED for a column other than an integer of up to 8 bytes
-static int build_agg(polr_pipeline *p, const polr_agg_spec &s, uint32_t a, DevAgg *ag) {
-	if (s.fn > POLR_AGG_MAX) {
-		POLR_FAIL(p->ctx, POLR_E_INVALID, "aggregate %u: unknown function %u", a, s.fn);
-	}
-	ag->fn = s.fn;
-	if (s.fn == POLR_AGG_COUNT_STAR) {
-		return POLR_OK;
-	}
-	OutCol c;
-	int rc = polr_out_int_col(p, s.src_join, s.src_col, &c, "aggregate", a);
-	if (rc) {
-		return rc;
-	}
-	ag->src = c.dev;
-	ag->slot = c.slot;
-	return POLR_OK;
-}
-
-// the expression form: POLR_E_INVALID for an unknown function or operator, a column out of range, a result width other than
-// 1 / 2 / 4 / 8 and a result type that cannot hold an operand type; POLR_E_UNSUPPORTED for operand columns other than integers
-// of up to 8 bytes (signed if 8) and for an unsigned 8-byte result
-static int build_expr_agg(polr_pipeline *p, const polr_agg_expr &s, uint32_t a, DevExprAgg *ag) {
-	if (s.fn > POLR_AGG_MAX) {
-		POLR_FAIL(p->ctx, POLR_E_INVALID, "aggregate %u: unknown function %u", a, s.fn);
-	}
-	ag->fn = s.fn;
-	ag->op = POLR_ARG_COLUMN;
-	if (s.fn == POLR_AGG_COUNT_STAR) {
-		return POLR_OK;
-	}
-	if (s.op > POLR_ARG_MUL) {
-		POLR_FAIL(p->ctx, POLR_E_INVALID, "aggregate %u: unknown operator %u", a, s.op);
-	}
-	ag->op = s.op;
-	const uint32_t n_operands = s.op == POLR_ARG_COLUMN ? 1u : 2u;
-	for (uint32_t x = 0; x < n_operands; x++) {
-		OutCol c;
-		int rc = polr_out_int_col(p, s.src_join[x], s.src_col[x], &c, "aggregate", a);
-		if (rc) {
-			return rc;
-		}
-		ag->src[x] = c.dev;
-		ag->slot[x] = c.slot;
-	}
-	if (s.op == POLR_ARG_COLUMN) {
-		ag->src[1] = ag->src[0];
-		ag->slot[1] = ag->slot[0];
-		return POLR_OK;
-	}
-	const uint32_t rw = s.result_width;
-	const bool rsigned = (s.result_flags & POLR_COL_SIGNED) != 0;
-	if (rw != 1 && rw != 2 && rw != 4 && rw != 8) {
-		POLR_FAIL(p->ctx, POLR_E_INVALID, "aggregate %u: result width %u (1, 2, 4 or 8 bytes)", a, rw);
-	}
-	if (rw == 8 && !rsigned) {
-		POLR_FAIL(p->ctx, POLR_E_UNSUPPORTED, "aggregate %u: an 8-byte result type must be signed", a);
-	}
-	for (uint32_t x = 0; x < 2; x++) { // (lossless implicit casts only: same signedness and no narrower, or unsigned into a wider signed)
-		const uint32_t w = ag->src[x].width;
-		const bool sgn = (ag->src[x].flags & 1u) != 0;
-		const bool holds = sgn == rsigned ? w <= rw : (!sgn && w < rw);
-		if (!holds) {
-			POLR_FAIL(p->ctx, POLR_E_INVALID, "aggregate %u: a %ssigned %u-byte result cannot hold every value of its %s operand (%ssigned, %u bytes)",
-			          a, rsigned ? "" : "un", rw, x ? "right" : "left", sgn ? "" : "un", w);
-		}
-	}
-	if (rsigned) {
-		ag->hi = (long long)(0x7FFFFFFFFFFFFFFFull >> (64u - 8u * rw));
-		ag->lo = -ag->hi - 1;
-	} else {
-		ag->lo = 0;
-		ag->hi = (long long)(0xFFFFFFFFFFFFFFFFull >> (64u - 8u * rw));
+int polr_out_col(polr_pipeline *p, int32_t src_join, uint32_t src_col, OutCol *c, const char *what, uint32_t idx) {
+	if (!polr_out_describe_col(p, src_join, src_col, c).in_range) {
+		char err[256];
+		const int rc = polr_agg_col_out_of_range(src_join, src_col, what, idx, err);
+		POLR_FAIL(p->ctx, rc, "%s", err);
 	}
 	return POLR_OK;
 }
 
-// The aggregates of one sink call, in the form the call was made in: the function codes agg_value / cell_value need and the
-// device set of that form.  The entry point names the specs; the sink builds them where its refusals have their turn.
+// The aggregates of one sink call, in the form the call was made in: the function codes polr_agg_decode / cell_value need and the
+// device set of that form.  The entry point names the specs; the sink resolves their columns and describes them to its
+// plan (describe_sink), and builds the device set from what the plan accepted (build_sink_aggs).
 struct SinkAggs {
 	SinkAggs(const polr_agg_spec *specs, uint32_t n_aggs) : n(n_aggs), expr(false), specs(specs) {
 	}
@@ -323,22 +261,86 @@ struct SinkAggs {
 	uint32_t fn[POLR_MAX_AGGS];
 	DevAggSet cols;      // !expr
 	DevExprAggSet exprs; // expr
+	PolrAggArg args[POLR_MAX_AGGS]; // as described to the plan
+	OutCol src[POLR_MAX_AGGS][2];   // the operand columns, resolved where they are in range
 };
 
-// (n <= POLR_MAX_AGGS: the caller has checked)
-static int build_sink_aggs(polr_pipeline *p, SinkAggs *s) {
+// The head of every sink's request: the output, and the aggregates with their operand columns resolved and described.
+// -> the context, or nullptr for a NULL output (which every plan refuses first, without a message)
+static polr_ctx *describe_sink(polr_out *o, SinkAggs *s, PolrAggRequest *rq) {
+	if (!o) {
+		return nullptr;
+	}
+	rq->has_out = true;
+	rq->agg_cells = o->agg_dev.get() != nullptr;
+	rq->already_fused = out_has_fused_sink(o);
+	rq->has_specs = s->specs != nullptr;
+	rq->n_aggs = s->n;
+	rq->args = s->args;
+	for (uint32_t a = 0; s->specs && a < s->n && a < POLR_MAX_AGGS; a++) {
+		PolrAggArg &g = s->args[a];
+		g = s->expr ? polr_agg_arg_of(((const polr_agg_expr *)s->specs)[a]) : polr_agg_arg_of(((const polr_agg_spec *)s->specs)[a]);
+		for (uint32_t x = 0; x < 2; x++) {
+			g.col[x] = polr_out_describe_col(o->pipe, g.src_join[x], g.src_col[x], &s->src[a][x]);
+		}
+	}
+	return o->pipe->ctx;
+}
+
+// ... and the device set of the call's form, from the plan that accepted them
+static void build_sink_aggs(const PolrAggArgPlan *accepted, SinkAggs *s) {
 	memset(&s->cols, 0, sizeof(s->cols));
 	memset(&s->exprs, 0, sizeof(s->exprs));
 	s->cols.n = s->exprs.n = s->n;
 	for (uint32_t a = 0; a < s->n; a++) {
-		int rc = s->expr ? build_expr_agg(p, ((const polr_agg_expr *)s->specs)[a], a, &s->exprs.a[a])
-		                 : build_agg(p, ((const polr_agg_spec *)s->specs)[a], a, &s->cols.a[a]);
-		if (rc) {
-			return rc;
+		const PolrAggArgPlan &ap = accepted[a];
+		const uint32_t n_operands = polr_agg_n_operands(ap);
+		const OutCol *c = s->src[a];
+		DevExprAgg &e = s->exprs.a[a];
+		s->fn[a] = s->cols.a[a].fn = e.fn = ap.fn;
+		e.op = ap.op;
+		e.lo = ap.lo;
+		e.hi = ap.hi;
+		for (uint32_t x = 0; x < 2 && n_operands; x++) { // (POLR_ARG_COLUMN: the one operand stands for both)
+			e.src[x] = c[x < n_operands ? x : 0].dev;
+			e.slot[x] = c[x < n_operands ? x : 0].slot;
 		}
-		s->fn[a] = s->expr ? s->exprs.a[a].fn : s->cols.a[a].fn;
+		if (n_operands) {
+			s->cols.a[a].src = c[0].dev;
+			s->cols.a[a].slot = c[0].slot;
+		}
 	}
-	return POLR_OK;
+}
+
+// the group columns of a grouped sink's request, resolved and described
+struct SinkGroups {
+	PolrAggGroupCol cols[POLR_MAX_GROUP_KEYS];
+	OutCol src[POLR_MAX_GROUP_KEYS];
+};
+static void describe_sink_groups(polr_out *o, const polr_group_key *keys, uint32_t n_keys, SinkGroups *g, PolrAggRequest *rq) {
+	rq->has_keys = keys != nullptr;
+	rq->n_keys = n_keys;
+	rq->keys = g->cols;
+	for (uint32_t q = 0; o && keys && q < n_keys && q < POLR_MAX_GROUP_KEYS; q++) {
+		g->cols[q].src_join = keys[q].src_join;
+		g->cols[q].src_col = keys[q].src_col;
+		g->cols[q].n_values = keys[q].n_values;
+		g->cols[q].col = polr_out_describe_col(o->pipe, keys[q].src_join, keys[q].src_col, &g->src[q]);
+	}
+}
+// ... and as the sink kernels read them (domain: the perfect-hash sinks'; the hashed sink ignores it)
+static DevGroupSet dev_group_set(const polr_group_key *keys, uint32_t n_keys, const SinkGroups &g, uint64_t n_groups) {
+	DevGroupSet gs;
+	memset(&gs, 0, sizeof(gs));
+	gs.n = n_keys;
+	gs.n_groups = (uint32_t)n_groups;
+	for (uint32_t q = 0; q < n_keys; q++) {
+		gs.k[q].src = g.src[q].dev;
+		gs.k[q].slot = g.src[q].slot;
+		gs.k[q].n_values = keys[q].n_values;
+		gs.k[q].min_value = keys[q].min_value;
+	}
+	return gs;
 }
 
 // f(the device set of the call's form): where a sink's kernel is instantiated per set type
@@ -399,65 +401,18 @@ struct SinkCounters {
 	unsigned long long host[MAX_OWN + POLR_MAX_AGGS] = {0};
 };
 
-// a group column as the sink kernels read it (domain: the perfect-hash sinks'; the hashed sink ignores it)
-static DevGroupKey dev_group_key(const polr_group_key &k, const OutCol &c) {
-	DevGroupKey g;
-	memset(&g, 0, sizeof(g));
-	g.src = c.dev;
-	g.slot = c.slot;
-	g.n_values = k.n_values;
-	g.min_value = k.min_value;
-	return g;
-}
-
-// what the C ABI reports for an aggregate: COUNT is never NULL; the others are NULL when no row took part
-static polr_agg_value agg_value(uint32_t fn, __int128 sum, long long mn, long long mx, unsigned long long count) {
-	polr_agg_value v;
-	memset(&v, 0, sizeof(v));
-	v.count = count;
-	switch (fn) {
-	case POLR_AGG_COUNT_STAR:
-	case POLR_AGG_COUNT:
-		v.lo = (int64_t)count;
-		break;
-	case POLR_AGG_SUM:
-		v.is_null = count == 0;
-		v.lo = (int64_t)(unsigned long long)sum;
-		v.hi = (int64_t)(sum >> 64);
-		break;
-	case POLR_AGG_MIN:
-		v.is_null = count == 0;
-		v.lo = count ? mn : 0;
-		v.hi = (count && mn < 0) ? -1 : 0;
-		break;
-	default:
-		v.is_null = count == 0;
-		v.lo = count ? mx : 0;
-		v.hi = (count && mx < 0) ? -1 : 0;
-		break;
-	}
-	return v;
-}
-
 // (n_out_of_range: the expression form's, may be NULL)
 static int aggregate_ungrouped(polr_out *o, void *stream, SinkAggs &aggs, polr_agg_value *results, uint64_t *n_out_of_range) {
 	const uint32_t n_aggs = aggs.n;
-	if (!o || !aggs.specs || !results || n_aggs == 0) {
-		return POLR_E_INVALID;
-	}
-	polr_pipeline *p = o->pipe;
-	polr_ctx *ctx = p->ctx;
-	POLR_REFUSE_AGG_CELLS(ctx, o);
-	if (n_aggs > POLR_MAX_AGGS) {
-		POLR_FAIL(ctx, POLR_E_UNSUPPORTED, "at most %d aggregates per call", POLR_MAX_AGGS);
-	}
-	int rc = build_sink_aggs(p, &aggs);
-	if (rc) {
-		return rc;
-	}
+	PolrAggRequest rq = {};
+	PolrAggPlan pl;
+	rq.has_results = results != nullptr;
+	polr_ctx *ctx = describe_sink(o, &aggs, &rq);
+	POLR_TRY_SINK_PLAN(ctx, pl, polr_agg_plan_ungrouped(rq, &pl));
+	build_sink_aggs(pl.agg, &aggs);
 	HIPCHK(ctx, hipSetDevice(ctx->device));
 	hipStream_t st = polr_stream(ctx, stream);
-	rc = out_ensure_stats(o, stream);
+	int rc = out_ensure_stats(o, stream);
 	if (rc) {
 		return rc;
 	}
@@ -492,7 +447,7 @@ static int aggregate_ungrouped(polr_out *o, void *stream, SinkAggs &aggs, polr_a
 			mx = r.mx > mx ? r.mx : mx;
 			n_rows += r.count;
 		}
-		results[a] = agg_value(aggs.fn[a], sum, mn, mx, n_rows);
+		results[a] = polr_agg_decode(aggs.fn[a], sum, mn, mx, n_rows);
 	}
 	return POLR_OK;
 }
@@ -634,56 +589,29 @@ __global__ __launch_bounds__(256) void polr_group_agg_kernel(DevOut out, uint32_
 }
 
 static polr_agg_value cell_value(const GroupCell &c, uint32_t fn) {
-	return agg_value(fn, ((__int128)c.hi32 << 32) + (__int128)c.lo32, c.mn, c.mx, c.count);
+	return polr_agg_decode(fn, ((__int128)c.hi32 << 32) + (__int128)c.lo32, c.mn, c.mx, c.count);
 }
 
 static int aggregate_grouped(polr_out *o, void *stream, const polr_group_key *keys, uint32_t n_keys, SinkAggs &aggs,
                              polr_agg_value *results, uint64_t n_groups, uint64_t *n_dropped, uint64_t *n_out_of_range) {
 	const uint32_t n_aggs = aggs.n;
-	if (!o || !keys || !aggs.specs || !results || n_keys == 0 || n_aggs == 0) {
-		return POLR_E_INVALID;
-	}
-	polr_pipeline *p = o->pipe;
-	polr_ctx *ctx = p->ctx;
-	POLR_REFUSE_AGG_CELLS(ctx, o);
-	if (n_keys > POLR_MAX_GROUP_KEYS || n_aggs > POLR_MAX_AGGS) {
-		POLR_FAIL(ctx, POLR_E_UNSUPPORTED, "at most %d group columns and %d aggregates", POLR_MAX_GROUP_KEYS, POLR_MAX_AGGS);
-	}
-	DevGroupSet gs;
-	memset(&gs, 0, sizeof(gs));
-	gs.n = n_keys;
-	uint64_t groups = 1;
-	for (uint32_t q = 0; q < n_keys; q++) {
-		OutCol c;
-		int rc = polr_out_int_col(p, keys[q].src_join, keys[q].src_col, &c, "group column", q);
-		if (rc) {
-			return rc;
-		}
-		if (keys[q].n_values == 0) {
-			POLR_FAIL(ctx, POLR_E_INVALID, "group column %u: empty domain", q);
-		}
-		groups *= keys[q].n_values;
-		if (groups > (1u << 20)) {
-			POLR_FAIL(ctx, POLR_E_UNSUPPORTED, "more than 2^20 groups: not a perfect-hash aggregate");
-		}
-		gs.k[q] = dev_group_key(keys[q], c);
-	}
-	if (groups != n_groups) {
-		POLR_FAIL(ctx, POLR_E_INVALID, "results hold %llu groups, the domains span %llu", (unsigned long long)n_groups,
-		          (unsigned long long)groups);
-	}
-	gs.n_groups = (uint32_t)groups;
-	int rc = build_sink_aggs(p, &aggs);
-	if (rc) {
-		return rc;
-	}
+	PolrAggRequest rq = {};
+	PolrAggPlan pl;
+	SinkGroups cols;
+	rq.has_results = results != nullptr;
+	rq.n_groups = n_groups;
+	polr_ctx *ctx = describe_sink(o, &aggs, &rq);
+	describe_sink_groups(o, keys, n_keys, &cols, &rq);
+	POLR_TRY_SINK_PLAN(ctx, pl, polr_agg_plan_grouped(rq, &pl));
+	const DevGroupSet gs = dev_group_set(keys, n_keys, cols, pl.n_groups);
+	build_sink_aggs(pl.agg, &aggs);
 	HIPCHK(ctx, hipSetDevice(ctx->device));
 	hipStream_t st = polr_stream(ctx, stream);
-	rc = out_ensure_stats(o, stream);
+	int rc = out_ensure_stats(o, stream);
 	if (rc) {
 		return rc;
 	}
-	const uint32_t n_cells = (uint32_t)groups * n_aggs;
+	const uint32_t n_cells = gs.n_groups * n_aggs;
 	std::vector<GroupCell> host(n_cells);
 	SinkCounters cnt(aggs, 1); // [0] dropped rows
 	DevBuf<GroupCell> table_mem;
@@ -763,13 +691,16 @@ __global__ __launch_bounds__(256) void polr_fused_reduce_kernel(const unsigned l
 extern "C" int polr_out_fuse_grouped(polr_out *o, const polr_group_key *keys, uint32_t n_keys, const polr_agg_spec *specs,
                                      uint32_t n_aggs) {
 	POLR_ENTRY();
-	if (!o) {
-		return POLR_E_INVALID;
-	}
-	polr_pipeline *p = o->pipe;
-	polr_ctx *ctx = p->ctx;
+	SinkAggs aggs(specs, n_aggs);
+	PolrAggRequest rq = {};
+	PolrAggPlan pl;
+	SinkGroups cols;
+	polr_ctx *ctx = describe_sink(o, &aggs, &rq);
+	describe_sink_groups(o, keys, n_keys, &cols, &rq);
+	rq.flat_emit = o && o->pipe->host_count.flat && o->pipe->flat_emit;
+	POLR_TRY_SINK_PLAN(ctx, pl, polr_agg_plan_fuse_grouped(rq, &pl));
 	HIPCHK(ctx, hipSetDevice(ctx->device));
-	if (!keys || n_keys == 0) { // un-fuse: the output object collects row ids again
+	if (pl.unfuse) { // the output object collects row ids again
 		if (o->fused_dev) {
 			HIPCHK(ctx, hipDeviceSynchronize());
 			o->fused_dev.reset();
@@ -779,52 +710,12 @@ extern "C" int polr_out_fuse_grouped(polr_out *o, const polr_group_key *keys, ui
 		}
 		return POLR_OK;
 	}
-	if (!specs || n_aggs == 0 || n_keys > POLR_MAX_GROUP_KEYS || n_aggs > POLR_MAX_AGGS) {
-		POLR_FAIL(ctx, POLR_E_INVALID, "1..%d group columns and 1..%d aggregates", POLR_MAX_GROUP_KEYS, POLR_MAX_AGGS);
-	}
-	if (!p->host_count.flat || !p->flat_emit) {
-		POLR_FAIL(ctx, POLR_E_UNSUPPORTED,
-		          "a GROUP BY sink is fused into FLAT pipelines whose joins are all perfect tables (polr_pipeline_launch_info); "
-		          "others: polr_out_aggregate_grouped over the emitted row ids");
-	}
-	if (out_has_fused_sink(o)) { // (at most one of the two sinks: polr_out_fuse_aggregate)
-		POLR_FAIL(ctx, POLR_E_INVALID, "the output object already has a fused sink");
-	}
+	build_sink_aggs(pl.agg, &aggs);
 	FusedSink fs;
 	memset(&fs, 0, sizeof(fs));
-	fs.groups.n = n_keys;
-	uint64_t groups = 1;
-	for (uint32_t q = 0; q < n_keys; q++) {
-		OutCol c;
-		int rc = polr_out_int_col(p, keys[q].src_join, keys[q].src_col, &c, "group column", q);
-		if (rc) {
-			return rc;
-		}
-		groups *= keys[q].n_values;
-		if (keys[q].n_values == 0 || groups > 4096) {
-			POLR_FAIL(ctx, POLR_E_UNSUPPORTED, "group column %u: a fused sink holds at most 4096 groups", q);
-		}
-		fs.groups.k[q] = dev_group_key(keys[q], c);
-	}
-	fs.groups.n_groups = (uint32_t)groups;
-	fs.aggs.n = n_aggs;
-	for (uint32_t a = 0; a < n_aggs; a++) { // (per aggregate, in this order: the first refusal decides the return code)
-		if (specs[a].fn > POLR_AGG_SUM) {
-			POLR_FAIL(ctx, POLR_E_UNSUPPORTED, "aggregate %u: a fused sink computes COUNT(*), COUNT and SUM", a);
-		}
-		const DevAgg &ag = fs.aggs.a[a];
-		int rc = build_agg(p, specs[a], a, &fs.aggs.a[a]);
-		if (rc) {
-			return rc;
-		}
-		if (ag.fn == POLR_AGG_SUM && ag.src.width > 4) {
-			// (the cells hold plain 64-bit sums: exact for 2^32 rows of values below 2^31)
-			POLR_FAIL(ctx, POLR_E_UNSUPPORTED, "aggregate %u: a fused SUM takes columns of at most 4 bytes", a);
-		}
-		o->fused_fn[a] = ag.fn;
-		o->fused_has_valid[a] = ag.src.valid != nullptr;
-	}
-	const uint32_t words = (uint32_t)groups * (1u + 2u * n_aggs);
+	fs.groups = dev_group_set(keys, n_keys, cols, pl.n_groups);
+	fs.aggs = aggs.cols;
+	const uint32_t groups = fs.groups.n_groups, words = groups * polr_fused_group_words(n_aggs);
 	fs.n_tables = POLR_FUSED_TABLES;
 	fs.words_per_table = words;
 	const size_t bytes = (size_t)(POLR_FUSED_TABLES + 1u) * words * 8u; // (+ 1: where the read-out sums the tables)
@@ -844,8 +735,12 @@ extern "C" int polr_out_fuse_grouped(polr_out *o, const polr_group_key *keys, ui
 	o->fused_dropped = std::move(dropped);
 	o->fused_dev = std::move(dev);
 	o->fused_tables = POLR_FUSED_TABLES;
-	o->fused_groups = (uint32_t)groups;
+	o->fused_groups = groups;
 	o->fused_aggs = n_aggs;
+	for (uint32_t a = 0; a < n_aggs; a++) {
+		o->fused_fn[a] = fs.aggs.a[a].fn;
+		o->fused_has_valid[a] = fs.aggs.a[a].src.valid != nullptr;
+	}
 	o->dev.fused = o->fused_dev;
 	return POLR_OK;
 }
@@ -864,7 +759,7 @@ extern "C" int polr_out_fused_result(polr_out *o, void *stream, polr_agg_value *
 	}
 	HIPCHK(ctx, hipSetDevice(ctx->device));
 	hipStream_t st = polr_stream(ctx, stream);
-	const uint32_t n_aggs = o->fused_aggs, words = o->fused_groups * (1u + 2u * n_aggs);
+	const uint32_t n_aggs = o->fused_aggs, words = o->fused_groups * polr_fused_group_words(n_aggs);
 	unsigned long long *sum = o->fused_cells + (size_t)o->fused_tables * words; // (one more table behind the workgroups')
 	HIPCHK(ctx, hipMemsetAsync(sum, 0, (size_t)words * 8u, st));
 	hipLaunchKernelGGL(polr_fused_reduce_kernel, dim3((words + 255) / 256, 16), dim3(256), 0, st, o->fused_cells, o->fused_tables,
@@ -878,10 +773,10 @@ extern "C" int polr_out_fused_result(polr_out *o, void *stream, polr_agg_value *
 		POLR_FAIL(ctx, POLR_E_HIP, "fused aggregate read-out failed: %s", hipGetErrorString(e));
 	}
 	for (uint32_t g = 0; g < o->fused_groups; g++) {
-		const unsigned long long *c = &host[(size_t)g * (1u + 2u * n_aggs)];
+		const unsigned long long *c = &host[(size_t)g * polr_fused_group_words(n_aggs)];
 		for (uint32_t a = 0; a < n_aggs; a++) {
 			const uint64_t count = o->fused_fn[a] == POLR_AGG_COUNT_STAR || !o->fused_has_valid[a] ? c[0] : c[2u + 2u * a];
-			results[(size_t)g * n_aggs + a] = agg_value(o->fused_fn[a], (int64_t)c[1u + 2u * a], 0, 0, count);
+			results[(size_t)g * n_aggs + a] = polr_agg_decode(o->fused_fn[a], (int64_t)c[1u + 2u * a], 0, 0, count);
 		}
 	}
 	if (n_dropped) {
@@ -946,36 +841,12 @@ void polr_launch_fuseagg_fill(hipStream_t st, const polr_out *o) {
 
 extern "C" int polr_out_fuse_aggregate(polr_out *o, const polr_agg_spec *specs, uint32_t n_aggs) {
 	POLR_ENTRY();
-	PolrFuseAggRequest rq;
-	memset(&rq, 0, sizeof(rq));
+	SinkAggs aggs(specs, n_aggs);
+	PolrFuseAggRequest rq = {};
 	PolrFuseAggPlan pl;
-	PolrFuseAggArg args[POLR_FUSEAGG_MAX_AGGS];
-	memset(args, 0, sizeof(args));
-	rq.has_out = o != nullptr;
-	rq.has_specs = specs != nullptr;
-	rq.n_aggs = n_aggs;
-	rq.args = args;
+	polr_ctx *ctx = describe_sink(o, &aggs, &rq);
 	if (!o) {
 		return polr_fuseagg_plan(rq, &pl); // (no context to leave a message in)
-	}
-	polr_pipeline *p = o->pipe;
-	polr_ctx *ctx = p->ctx;
-	rq.already_fused = out_has_fused_sink(o);
-	for (uint32_t a = 0; specs && a < n_aggs && a < POLR_FUSEAGG_MAX_AGGS; a++) {
-		PolrFuseAggArg &g = args[a];
-		g.fn = specs[a].fn;
-		g.src_join = specs[a].src_join;
-		g.src_col = specs[a].src_col;
-		if (g.src_join < 0) {
-			g.col_in_range = g.src_col < p->n_probe_cols;
-		} else {
-			g.col_in_range = (uint32_t)g.src_join < p->k && g.src_col < p->hts[g.src_join]->n_payload;
-		}
-		if (g.col_in_range) {
-			const OwnedCol &c = g.src_join < 0 ? p->probe_cols[g.src_col] : build_col(p->hts[g.src_join], g.src_col);
-			g.width = c.width;
-			g.flags = c.flags;
-		}
 	}
 	POLR_TRY_PLAN(ctx, pl, polr_fuseagg_plan(rq, &pl));
 	HIPCHK(ctx, hipSetDevice(ctx->device));
@@ -988,12 +859,10 @@ extern "C" int polr_out_fuse_aggregate(polr_out *o, const polr_agg_spec *specs, 
 		}
 		return POLR_OK;
 	}
+	build_sink_aggs(pl.agg, &aggs);
 	FusedAggSink fs;
 	memset(&fs, 0, sizeof(fs));
-	fs.aggs.n = n_aggs;
-	for (uint32_t a = 0; a < n_aggs; a++) { // (the plan has accepted every column: build_agg refuses nothing here)
-		POLR_TRY(build_agg(p, specs[a], a, &fs.aggs.a[a]));
-	}
+	fs.aggs = aggs.cols;
 	fs.n_tables = pl.n_tables;
 	fs.words_per_table = pl.words_per_table;
 	// built in locals and moved into the output at the point of success: nothing half-made stays behind
@@ -1047,381 +916,6 @@ extern "C" int polr_out_fused_aggregate_result(polr_out *o, void *stream, polr_a
 	}
 	return POLR_OK;
 }
-
-// ---- VARCHAR: string heaps on the device and the MIN / MAX sink over string_t cells -------------------------------------
-// (string_type.hpp:23-28: {u32 length, char inlined[12]} or {u32 length, char prefix[4], char *ptr})
-// one host range of a heap and where its copy lives on the device; a column's ranges sorted by host_base, disjoint
-struct HeapRange {
-	uint64_t host_base, bytes, dev_base;
-};
-
-// the range that holds all of [ptr, ptr + len), or -1 (ranges sorted and disjoint: at most one can)
-__device__ __forceinline__ int find_heap_range(const HeapRange *r, uint32_t n, uint64_t ptr, uint32_t len) {
-	uint32_t lo = 0, hi = n; // -> the first range whose host_base lies above ptr
-	while (lo < hi) {
-		const uint32_t mid = (lo + hi) / 2;
-		if (r[mid].host_base <= ptr) {
-			lo = mid + 1;
-		} else {
-			hi = mid;
-		}
-	}
-	if (lo == 0) {
-		return -1;
-	}
-	const HeapRange &h = r[lo - 1];
-	return (len <= h.bytes && ptr - h.host_base <= h.bytes - len) ? (int)(lo - 1) : -1; // (no wrap-around at 2^64)
-}
-
-// rewrite = 0: count the non-NULL long cells that no range holds; rewrite = 1 (after a count of 0): rebase those cells onto
-// the device copies and zero the cells of NULL rows (the reference leaves them uninitialised: nothing may follow them)
-__global__ __launch_bounds__(256) void polr_rebase_strings_kernel(uint4 *cells, const uint8_t *__restrict__ valid, uint64_t n,
-                                                                  const HeapRange *__restrict__ ranges, uint32_t n_ranges,
-                                                                  int rewrite, unsigned long long *outside) {
-	const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
-	if (i >= n) {
-		return;
-	}
-	if (valid && !valid[i]) {
-		if (rewrite) {
-			cells[i] = make_uint4(0, 0, 0, 0);
-		}
-		return;
-	}
-	uint4 c = cells[i];
-	if (c.x <= 12u) {
-		return;
-	}
-	const uint64_t ptr = ((uint64_t)c.w << 32) | c.z;
-	const int r = find_heap_range(ranges, n_ranges, ptr, c.x);
-	if (r < 0) {
-		if (!rewrite) {
-			atomicAdd(outside, 1ull); // (a cell pointing outside the heap it was said to live in)
-		}
-		return;
-	}
-	if (rewrite) {
-		const uint64_t moved = ptr - ranges[r].host_base + ranges[r].dev_base;
-		c.z = (uint32_t)moved;
-		c.w = (uint32_t)(moved >> 32);
-		cells[i] = c;
-	}
-}
-
-__device__ __forceinline__ uint32_t str_byte(const uint4 &c, uint32_t i) {
-	if (c.x <= 12u) {
-		const uint32_t w = i < 4 ? c.y : (i < 8 ? c.z : c.w);
-		return (w >> (8u * (i & 3u))) & 0xFFu;
-	}
-	if (i < 4) {
-		return (c.y >> (8u * i)) & 0xFFu;
-	}
-	const uint8_t *p = (const uint8_t *)(((uint64_t)c.w << 32) | c.z);
-	return p[i];
-}
-
-// a < b in the order of the reference's string comparison: unsigned bytes, a proper prefix first
-__device__ __forceinline__ bool str_less(const uint4 &a, const uint4 &b) {
-	const uint32_t n = a.x < b.x ? a.x : b.x;
-	// the first four characters sit in the same place in both forms
-	const uint32_t pa = __builtin_bswap32(a.y), pb = __builtin_bswap32(b.y);
-	if (n >= 4 && pa != pb) {
-		return pa < pb;
-	}
-	for (uint32_t i = 0; i < n; i++) {
-		const uint32_t x = str_byte(a, i), y = str_byte(b, i);
-		if (x != y) {
-			return x < y;
-		}
-	}
-	return a.x < b.x;
-}
-
-struct StrPartial {
-	uint4 cell;
-	uint32_t have;
-	uint32_t pad[3];
-};
-
-// phase 1: per workgroup the extreme of its share of the output rows; phase 2 (one workgroup, n_in partials): the extreme
-__global__ __launch_bounds__(256) void polr_agg_string_kernel(DevOut out, uint32_t n_chunks, DevCol src, uint32_t slot, int want_max,
-                                                              const StrPartial *__restrict__ in, uint32_t n_in,
-                                                              StrPartial *__restrict__ partials) {
-	__shared__ StrPartial wave_part[4];
-	const uint32_t lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-	uint4 best = make_uint4(0, 0, 0, 0);
-	bool have = false;
-	auto offer = [&](const uint4 &c) {
-		if (!have || (want_max ? str_less(best, c) : str_less(c, best))) {
-			best = c;
-			have = true;
-		}
-	};
-	if (in) {
-		for (uint32_t i = threadIdx.x; i < n_in; i += blockDim.x) {
-			if (in[i].have) {
-				offer(in[i].cell);
-			}
-		}
-	} else {
-		for (uint32_t chunk = blockIdx.x; chunk < n_chunks; chunk += gridDim.x) {
-			const uint32_t n = out.chunk_count[chunk];
-			const uint32_t *ids = out.ids + (uint64_t)slot * out.slot_stride + (uint64_t)chunk * out.chunk_capacity;
-			for (uint32_t i = threadIdx.x; i < n; i += blockDim.x) {
-				const uint32_t row = ids[i];
-				if (src.valid && !src.valid[row]) {
-					continue; // NULLs take no part
-				}
-				offer(((const uint4 *)src.data)[row]);
-			}
-		}
-	}
-	for (int d = 32; d > 0; d >>= 1) {
-		uint4 o;
-		o.x = __shfl_down(best.x, d, 64);
-		o.y = __shfl_down(best.y, d, 64);
-		o.z = __shfl_down(best.z, d, 64);
-		o.w = __shfl_down(best.w, d, 64);
-		const bool ohave = __shfl_down(have ? 1 : 0, d, 64) != 0;
-		if (ohave && (int)lane + d < 64) {
-			offer(o);
-		}
-	}
-	if (lane == 0) {
-		wave_part[wave].cell = best;
-		wave_part[wave].have = have ? 1u : 0u;
-	}
-	__syncthreads();
-	if (threadIdx.x == 0) {
-		have = false;
-		for (uint32_t w = 0; w < (blockDim.x >> 6); w++) {
-			if (wave_part[w].have) {
-				offer(wave_part[w].cell);
-			}
-		}
-		StrPartial r;
-		r.cell = best;
-		r.have = have ? 1u : 0u;
-		r.pad[0] = r.pad[1] = r.pad[2] = 0;
-		partials[blockIdx.x] = r;
-	}
-}
-
-// the guard of a VARCHAR column whose cells were never rebased onto a device heap: the non-NULL cells among the output rows
-// that are longer than 12 bytes -- their pointers are the host's.  Reads the length word of a cell and nothing else.
-__global__ __launch_bounds__(256) void polr_count_long_cells_kernel(DevOut out, uint32_t n_chunks, DevCol src, uint32_t slot,
-                                                                    unsigned long long *__restrict__ n_long) {
-	unsigned long long mine = 0;
-	for (uint32_t chunk = blockIdx.x; chunk < n_chunks; chunk += gridDim.x) {
-		const uint32_t n = out.chunk_count[chunk];
-		const uint32_t *ids = out.ids + (uint64_t)slot * out.slot_stride + (uint64_t)chunk * out.chunk_capacity;
-		for (uint32_t i = threadIdx.x; i < n; i += blockDim.x) {
-			const uint32_t row = ids[i];
-			if (src.valid && !src.valid[row]) {
-				continue;
-			}
-			mine += *(const uint32_t *)(src.data + (uint64_t)row * 16u) > 12u ? 1u : 0u;
-		}
-	}
-	mine = wave_sum64(mine);
-	if ((threadIdx.x & 63u) == 0 && mine) {
-		atomicAdd(n_long, mine);
-	}
-}
-
-// POLR_OK when the column may be read by a kernel that follows string pointers
-static int check_string_col_on_device(polr_out *o, hipStream_t st, const OutCol &c, const char *what, uint32_t idx) {
-	polr_ctx *ctx = o->pipe->ctx;
-	if (c.col->strings_rebased || !c.col->owned() || o->n_chunks == 0) {
-		return POLR_OK; // (rebased here; or the caller's own device memory, whose cells point into HBM by contract)
-	}
-	DevBuf<unsigned long long> n_long;
-	unsigned long long h_long = 0;
-	HIPCHK(ctx, n_long.alloc(1));
-	HIPCHK(ctx, hipMemsetAsync(n_long, 0, 8, st));
-	const uint32_t n_blocks = std::max<uint32_t>(1, std::min<uint32_t>(o->n_chunks, (uint32_t)ctx->n_cus * 4));
-	hipLaunchKernelGGL(polr_count_long_cells_kernel, dim3(n_blocks), dim3(256), 0, st, o->dev, o->n_chunks, c.dev, c.slot, n_long.get());
-	HIPCHK(ctx, hipMemcpyAsync(&h_long, n_long, 8, hipMemcpyDeviceToHost, st));
-	HIPCHK(ctx, hipStreamSynchronize(st));
-	if (h_long) {
-		POLR_FAIL_HEAP_NEVER_CAME(ctx, what, idx, h_long);
-	}
-	return POLR_OK;
-}
-
-// all or nothing: the ranges are checked, copied and every cell validated before any cell is rewritten; on an error the
-// column is as it was and no device memory is kept
-static int set_string_heaps(polr_ctx *ctx, OwnedCol *c, uint64_t n_rows, const polr_heap_range *ranges, uint32_t n_ranges,
-                            std::vector<DevBuf<uint8_t>> &owner) {
-	if (!ranges || n_ranges == 0) {
-		POLR_FAIL(ctx, POLR_E_INVALID, "a string heap needs at least one range");
-	}
-	if (c->width != 16) {
-		POLR_FAIL(ctx, POLR_E_INVALID, "a string heap belongs to a column of 16-byte string cells (this one: %u bytes)", c->width);
-	}
-	if (c->strings_rebased) {
-		POLR_FAIL(ctx, POLR_E_INVALID, "the column's string cells point into a device heap already");
-	}
-	std::vector<HeapRange> hr(n_ranges);
-	std::vector<uint32_t> order(n_ranges);
-	uint64_t total = 0;
-	for (uint32_t r = 0; r < n_ranges; r++) {
-		const uint64_t base = (uint64_t)ranges[r].base, bytes = ranges[r].bytes;
-		if (!base || bytes == 0 || base + bytes < base) {
-			POLR_FAIL(ctx, POLR_E_INVALID, "heap range %u: empty, NULL or past the end of the address space", r);
-		}
-		order[r] = r;
-		total += bytes;
-	}
-	std::sort(order.begin(), order.end(),
-	          [&](uint32_t a, uint32_t b) { return (uint64_t)ranges[a].base < (uint64_t)ranges[b].base; });
-	uint64_t at = 0;
-	for (uint32_t r = 0; r < n_ranges; r++) {
-		const polr_heap_range &x = ranges[order[r]];
-		if (r && (uint64_t)x.base < hr[r - 1].host_base + hr[r - 1].bytes) {
-			POLR_FAIL(ctx, POLR_E_INVALID, "heap ranges %u and %u overlap", order[r - 1], order[r]);
-		}
-		hr[r].host_base = (uint64_t)x.base;
-		hr[r].bytes = x.bytes;
-		hr[r].dev_base = at; // (offset for now: the device address once the copy exists)
-		at += x.bytes;
-	}
-	HIPCHK(ctx, hipSetDevice(ctx->device));
-	DevBuf<uint8_t> heap;
-	DevBuf<HeapRange> d_ranges;
-	DevBuf<unsigned long long> outside;
-	HIPCHK(ctx, heap.alloc(total));
-	HIPCHK(ctx, d_ranges.alloc(n_ranges));
-	HIPCHK(ctx, outside.alloc(1));
-	for (uint32_t r = 0; r < n_ranges; r++) {
-		HIPCHK(ctx, hipMemcpyAsync(heap + hr[r].dev_base, (const void *)hr[r].host_base, hr[r].bytes, hipMemcpyHostToDevice, ctx->stream));
-		hr[r].dev_base += (uint64_t)heap.get();
-	}
-	HIPCHK(ctx, hipMemcpyAsync(d_ranges, hr.data(), n_ranges * sizeof(HeapRange), hipMemcpyHostToDevice, ctx->stream));
-	HIPCHK(ctx, hipMemsetAsync(outside, 0, 8, ctx->stream));
-	const dim3 grid((unsigned)((n_rows + 255) / 256));
-	if (n_rows) {
-		hipLaunchKernelGGL(polr_rebase_strings_kernel, grid, dim3(256), 0, ctx->stream, (uint4 *)c->data, c->valid, n_rows,
-		                   d_ranges.get(), n_ranges, 0, outside.get());
-	}
-	unsigned long long bad = 0;
-	HIPCHK(ctx, hipMemcpyAsync(&bad, outside, 8, hipMemcpyDeviceToHost, ctx->stream));
-	HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
-	if (bad) {
-		POLR_FAIL(ctx, POLR_E_INVALID, "%llu non-NULL string cells point outside the heap ranges given for their column", bad);
-	}
-	if (n_rows) {
-		hipLaunchKernelGGL(polr_rebase_strings_kernel, grid, dim3(256), 0, ctx->stream, (uint4 *)c->data, c->valid, n_rows,
-		                   d_ranges.get(), n_ranges, 1, outside.get());
-		HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
-	}
-	owner.push_back(std::move(heap)); // (only now: a refused call keeps nothing)
-	c->strings_rebased = true;
-	return POLR_OK;
-}
-
-extern "C" {
-
-int polr_ht_set_payload_heaps(polr_ht *ht, uint32_t payload_col, const polr_heap_range *ranges, uint32_t n_ranges) {
-	POLR_ENTRY();
-	if (!ht || payload_col >= ht->n_payload) {
-		return POLR_E_INVALID;
-	}
-	if (ht->kind != KIND_NONE) {
-		// (a finalized perfect table keeps a re-ordered copy of every payload column: rebase before finalizing)
-		POLR_FAIL(ht->ctx, POLR_E_INVALID, "set the string heap of a payload column before the table is finalized");
-	}
-	return set_string_heaps(ht->ctx, &ht->payload[payload_col], ht->n_rows_in, ranges, n_ranges, ht->heaps);
-}
-
-int polr_ht_set_payload_heap(polr_ht *ht, uint32_t payload_col, const void *heap_base, uint64_t heap_bytes) {
-	const polr_heap_range r = {heap_base, heap_bytes};
-	return polr_ht_set_payload_heaps(ht, payload_col, &r, 1);
-}
-
-int polr_pipeline_set_probe_heaps(polr_pipeline *p, uint32_t probe_col, const polr_heap_range *ranges, uint32_t n_ranges) {
-	POLR_ENTRY();
-	if (!p || probe_col >= p->n_probe_cols) {
-		return POLR_E_INVALID;
-	}
-	if (!p->probe_cols[probe_col].owned()) {
-		POLR_FAIL(p->ctx, POLR_E_INVALID, "probe column %u lives in the caller's device memory: its cells must point into HBM already",
-		          probe_col);
-	}
-	return set_string_heaps(p->ctx, &p->probe_cols[probe_col], p->n_probe_rows, ranges, n_ranges, p->heaps);
-}
-
-int polr_pipeline_set_probe_heap(polr_pipeline *p, uint32_t probe_col, const void *heap_base, uint64_t heap_bytes) {
-	const polr_heap_range r = {heap_base, heap_bytes};
-	return polr_pipeline_set_probe_heaps(p, probe_col, &r, 1);
-}
-
-int polr_out_aggregate_string(polr_out *o, void *stream, uint32_t fn, int32_t src_join, uint32_t src_col, char *dst,
-                              uint32_t dst_cap, uint32_t *len, uint32_t *is_null) {
-	POLR_ENTRY();
-	if (!o || !len || !is_null || (!dst && dst_cap)) {
-		return POLR_E_INVALID;
-	}
-	polr_pipeline *p = o->pipe;
-	polr_ctx *ctx = p->ctx;
-	POLR_REFUSE_AGG_CELLS(ctx, o);
-	if (fn != POLR_AGG_MIN && fn != POLR_AGG_MAX) {
-		POLR_FAIL(ctx, POLR_E_UNSUPPORTED, "string aggregate %u (MIN or MAX)", fn);
-	}
-	OutCol c;
-	int rc = polr_out_col(p, src_join, src_col, &c, "string aggregate, column", src_col);
-	if (rc) {
-		return rc;
-	}
-	if (c.dev.width != 16) {
-		POLR_FAIL(ctx, POLR_E_INVALID, "not a VARCHAR column (%u-byte cells)", c.dev.width);
-	}
-	HIPCHK(ctx, hipSetDevice(ctx->device));
-	hipStream_t st = polr_stream(ctx, stream);
-	rc = out_ensure_stats(o, stream);
-	if (rc) {
-		return rc;
-	}
-	*len = 0;
-	*is_null = 1;
-	if (o->n_chunks == 0) {
-		return POLR_OK;
-	}
-	// a column whose heap never came may hold inline strings only: refused before a pointer is followed
-	rc = check_string_col_on_device(o, st, c, "string aggregate, column", src_col);
-	if (rc) {
-		return rc;
-	}
-	const uint32_t n_blocks = std::max<uint32_t>(1, std::min<uint32_t>(o->n_chunks, (uint32_t)ctx->n_cus * 4));
-	DevBuf<StrPartial> part_mem;
-	HIPCHK(ctx, part_mem.alloc((size_t)n_blocks + 1));
-	StrPartial *part = part_mem;
-	hipLaunchKernelGGL(polr_agg_string_kernel, dim3(n_blocks), dim3(256), 0, st, o->dev, o->n_chunks, c.dev, c.slot,
-	                   fn == POLR_AGG_MAX ? 1 : 0, (const StrPartial *)nullptr, 0u, part);
-	hipLaunchKernelGGL(polr_agg_string_kernel, dim3(1), dim3(256), 0, st, o->dev, 0u, c.dev, c.slot, fn == POLR_AGG_MAX ? 1 : 0,
-	                   (const StrPartial *)part, n_blocks, part + n_blocks);
-	StrPartial win;
-	hipError_t e = hipMemcpyAsync(&win, part + n_blocks, sizeof(win), hipMemcpyDeviceToHost, st);
-	e = e == hipSuccess ? hipStreamSynchronize(st) : e;
-	if (e == hipSuccess && win.have) {
-		*is_null = 0;
-		*len = win.cell.x;
-		const uint32_t take = std::min<uint32_t>(win.cell.x, dst_cap);
-		if (win.cell.x <= 12) {
-			const uint32_t words[3] = {win.cell.y, win.cell.z, win.cell.w};
-			memcpy(dst, words, take);
-		} else if (take) {
-			e = hipMemcpy(dst, (const void *)(((uint64_t)win.cell.w << 32) | win.cell.z), take, hipMemcpyDeviceToHost);
-		}
-	}
-	if (e != hipSuccess) {
-		POLR_FAIL(ctx, POLR_E_HIP, "string aggregate failed: %s", hipGetErrorString(e));
-	}
-	return POLR_OK;
-}
-
-} // extern "C"
-
 
 // ---- the general GROUP BY sink: group columns of any integer domain or VARCHAR (PhysicalHashAggregate,
 // src/execution/operator/aggregate/physical_hash_aggregate.cpp -- the plan when the group columns' statistics do not allow
@@ -1703,44 +1197,30 @@ static int aggregate_hashed(polr_out *o, void *stream, const polr_group_key *col
                             uint64_t *n_groups, bool strings, uint8_t *str_bytes, uint64_t str_cap, uint64_t *str_used,
                             uint64_t *n_out_of_range) {
 	const uint32_t n_aggs = aggs.n;
-	if (!o || !cols || !aggs.specs || !group_keys || !group_nulls || !results || !n_groups || n_cols == 0 || n_aggs == 0 ||
-	    max_groups == 0 || (strings && (!str_used || (!str_bytes && str_cap)))) {
-		return POLR_E_INVALID;
-	}
-	polr_pipeline *p = o->pipe;
-	polr_ctx *ctx = p->ctx;
-	POLR_REFUSE_AGG_CELLS(ctx, o);
-	if (n_cols > POLR_MAX_GROUP_KEYS || n_aggs > POLR_MAX_AGGS || max_groups > (1ull << 24)) {
-		POLR_FAIL(ctx, POLR_E_UNSUPPORTED, "at most %d group columns, %d aggregates and 2^24 groups", POLR_MAX_GROUP_KEYS,
-		          POLR_MAX_AGGS);
-	}
-	if (strings) {
+	PolrAggRequest rq = {};
+	PolrAggPlan pl;
+	SinkGroups gcols;
+	rq.has_results = results != nullptr;
+	rq.has_group_outputs = group_keys && group_nulls && n_groups;
+	rq.max_groups = max_groups;
+	rq.strings = strings;
+	rq.has_str_used = str_used != nullptr;
+	rq.has_str_bytes = str_bytes != nullptr;
+	rq.str_cap = str_cap;
+	polr_ctx *ctx = describe_sink(o, &aggs, &rq);
+	describe_sink_groups(o, cols, n_cols, &gcols, &rq);
+	const int refused = polr_agg_plan_hashed(rq, &pl);
+	if (strings && pl.head_passed) {
 		*str_used = 0;
 	}
-	DevGroupSet gs;
-	memset(&gs, 0, sizeof(gs));
-	gs.n = n_cols;
-	OutCol gcol[POLR_MAX_GROUP_KEYS];
-	uint32_t str_mask = 0;
-	for (uint32_t q = 0; q < n_cols; q++) {
-		int rc = polr_out_col(p, cols[q].src_join, cols[q].src_col, &gcol[q], "group column", q);
-		if (!rc && strings && gcol[q].dev.width == 16) {
-			str_mask |= 1u << q;
-		} else if (!rc) {
-			rc = polr_out_int_col(p, cols[q].src_join, cols[q].src_col, &gcol[q], "group column", q);
-		}
-		if (rc) {
-			return rc;
-		}
-		gs.k[q] = dev_group_key(cols[q], gcol[q]);
-	}
-	int rc = build_sink_aggs(p, &aggs);
-	if (rc) {
-		return rc;
-	}
+	POLR_TRY_SINK_PLAN(ctx, pl, refused);
+	const OutCol *gcol = gcols.src;
+	const uint32_t str_mask = pl.str_mask;
+	const DevGroupSet gs = dev_group_set(cols, n_cols, gcols, 0);
+	build_sink_aggs(pl.agg, &aggs);
 	HIPCHK(ctx, hipSetDevice(ctx->device));
 	hipStream_t st = polr_stream(ctx, stream);
-	rc = out_ensure_stats(o, stream);
+	int rc = out_ensure_stats(o, stream);
 	if (rc) {
 		return rc;
 	}
@@ -1759,41 +1239,26 @@ static int aggregate_hashed(polr_out *o, void *stream, const polr_group_key *col
 	memset(&t, 0, sizeof(t));
 	t.mask = capacity - 1;
 	t.max_groups = max_groups;
-	// one allocation: state, nulls, counters, keys, representative cells (VARCHAR only), group cells, and the compacted
-	// outputs behind them
-	const size_t rep_bytes = str_mask ? 16 : 0;
+	// one allocation (polr_hashagg_layout): the table, and the compacted outputs behind it
 	SinkCounters hc(aggs, SinkCounters::MAX_OWN); // [0] groups, [1] overflow, [2] compaction cursor
-	const size_t b_state = capacity * 4, b_nulls = capacity * 4, b_cnt = sizeof(hc.host), b_keys = capacity * n_cols * 8,
-	             b_reps = capacity * n_cols * rep_bytes, b_cells = capacity * n_aggs * sizeof(GroupCell),
-	             b_okeys = (max_groups * n_cols * 8 + 15) & ~(size_t)15, // (the uint4 cells behind it stay 16-byte aligned)
-	             b_oreps = max_groups * n_cols * rep_bytes, b_onulls = (max_groups * 4 + 15) & ~(size_t)15,
-	             b_ocells = max_groups * n_aggs * sizeof(GroupCell);
+	PolrHashAggLayout lo;
+	polr_hashagg_layout(capacity, max_groups, n_cols, n_aggs, str_mask != 0, sizeof(GroupCell), sizeof(hc.host), &lo);
 	DevBuf<uint8_t> base;
-	HIPCHK(ctx, base.alloc(b_state + b_nulls + b_cnt + b_keys + b_reps + b_cells + b_okeys + b_oreps + b_onulls + b_ocells));
-	uint8_t *at = base;
-	t.state = (uint32_t *)at;
-	at += b_state;
-	t.nulls = (uint32_t *)at;
-	at += b_nulls;
-	unsigned long long *cnt = (unsigned long long *)at;
-	at += b_cnt;
+	HIPCHK(ctx, base.alloc(lo.total));
+	t.state = (uint32_t *)(base + lo.state);
+	t.nulls = (uint32_t *)(base + lo.nulls);
+	unsigned long long *cnt = (unsigned long long *)(base + lo.counters);
 	hc.place(cnt, &aggs);
 	t.n_groups = cnt;
 	t.overflow = cnt + 1;
-	t.keys = (long long *)at;
-	at += b_keys;
-	uint4 *reps = str_mask ? (uint4 *)at : nullptr;
-	at += b_reps;
-	t.cells = (GroupCell *)at;
-	at += b_cells;
-	long long *okeys = (long long *)at;
-	at += b_okeys;
-	uint4 *oreps = str_mask ? (uint4 *)at : nullptr;
-	at += b_oreps;
-	uint32_t *onulls = (uint32_t *)at;
-	at += b_onulls;
-	GroupCell *ocells = (GroupCell *)at;
-	hipError_t e = hipMemsetAsync(base, 0, b_state + b_nulls + b_cnt, st); // (the counters with the table's state)
+	t.keys = (long long *)(base + lo.keys);
+	uint4 *reps = str_mask ? (uint4 *)(base + lo.reps) : nullptr;
+	t.cells = (GroupCell *)(base + lo.cells);
+	long long *okeys = (long long *)(base + lo.okeys);
+	uint4 *oreps = str_mask ? (uint4 *)(base + lo.oreps) : nullptr;
+	uint32_t *onulls = (uint32_t *)(base + lo.onulls);
+	GroupCell *ocells = (GroupCell *)(base + lo.ocells);
+	hipError_t e = hipMemsetAsync(base, 0, lo.zero_bytes, st); // (the counters with the table's state)
 	const unsigned long long *h_cnt = hc.host;
 	if (e == hipSuccess) {
 		hipLaunchKernelGGL(polr_group_init_kernel, dim3(256), dim3(256), 0, st, t.cells, capacity * n_aggs);

@@ -1112,7 +1112,7 @@ int polr_out_reset(polr_out *o, void *stream) {
 	HIPCHK(ctx, hipMemsetAsync(o->dev.cursor, 0, 8, st));
 	if (o->fused_cells) { // (a fused GROUP BY sink: its cells start from zero, too)
 		HIPCHK(ctx, hipMemsetAsync(o->fused_cells, 0,
-		                           (size_t)o->fused_tables * o->fused_groups * (1u + 2u * o->fused_aggs) * 8u, st));
+		                           (size_t)o->fused_tables * o->fused_groups * polr_fused_group_words(o->fused_aggs) * 8u, st));
 		HIPCHK(ctx, hipMemsetAsync(o->fused_dropped, 0, 8, st));
 	}
 	if (o->agg_cells) { // (a fused ungrouped sink: its cells go back to "no rows" -- MIN's identity is not 0)

@@ -1,8 +1,8 @@
 // duckdb-polr_amd/csrc/polr_fuseagg_plan.h -- the fused UNGROUPED aggregate sink of the generic pool kernel
 // (polr_out_fuse_aggregate / polr_out_fused_aggregate_result, include/polr_hip.h), as plain host code.  No HIP in here:
-// polr_agg.hip describes the output and the columns, allocates what the plan says and launches; the kernels
-// (polr_gen_device.h: the fold; polr_agg.hip: fill and combine) take the word positions and kinds from the macros below; a
-// stand-alone host program drives the header alone (tests/fuseagg/fuseagg_plan_main.cpp).
+// polr_agg.hip describes the output and the columns (PolrAggArg, polr_agg_plan.h), allocates what the plan says and launches;
+// the kernels (polr_gen_device.h: the fold; polr_agg.hip: fill and combine) take the word positions and kinds from the macros
+// below; a stand-alone host program drives the header alone (tests/fuseagg/fuseagg_plan_main.cpp).
 //
 // The plan:
 //   * every refusal of polr_out_fuse_aggregate, in this order, each with its message:
@@ -10,7 +10,7 @@
 //          (specs == NULL or n_aggs == 0: un-fuse, never refused)
 //       2. more than POLR_MAX_AGGS aggregates                       POLR_E_UNSUPPORTED
 //       3. the output carries a fused sink already (either kind)    POLR_E_INVALID
-//       4. per aggregate, in order -- the rule of polr_out_aggregate, word for word:
+//       4. per aggregate, in order -- the rule of polr_out_aggregate itself (polr_agg_arg_rule, polr_agg_plan.h):
 //            an unknown function                                    POLR_E_INVALID
 //            a column out of range                                  POLR_E_INVALID
 //            a VARCHAR or unsigned 8-byte column                    POLR_E_UNSUPPORTED
@@ -22,7 +22,8 @@
 //       word 3 + 3a       aggregate a: the rows that took part (non-NULL arguments)
 //     every word is combined by ADD but the MIN word (unsigned min, "no rows" = all ones) and the MAX word (unsigned max,
 //     "no rows" = 0): polr_fuseagg_word_kind / polr_fuseagg_reset_value;
-//   * the decode of a combined table into polr_agg_value (polr_fuseagg_decode): the SUM is hi * 2^32 + lo in 128 bits --
+//   * the decode of a combined table into polr_agg_value (polr_fuseagg_decode; the value itself: polr_agg_decode,
+//     polr_agg_plan.h): the SUM is hi * 2^32 + lo in 128 bits --
 //     exact while fewer than 2^32 tuples were folded (lo < 2^64, |hi| < 2^63); at 2^32 or more with a SUM in the sink the
 //     call is POLR_E_RANGE and writes nothing.
 #pragma once
@@ -32,8 +33,9 @@
 #include <string.h>
 
 #include "../../include/polr_hip.h"
+#include "polr_agg_plan.h"
 
-#define POLR_FUSEAGG_MAX_AGGS 8u     // (= POLR_MAX_AGGS of polr_device.h: static_assert there)
+#define POLR_FUSEAGG_MAX_AGGS POLR_AGG_MAX_AGGS // (= POLR_MAX_AGGS of polr_device.h: static_assert there)
 #define POLR_FUSEAGG_TABLES 256u     // cell tables a launch's workgroups spread over
 #define POLR_FUSEAGG_WORDS_PER_AGG 3u
 #define POLR_FUSEAGG_MAX_WORDS (1u + POLR_FUSEAGG_WORDS_PER_AGG * POLR_FUSEAGG_MAX_AGGS)
@@ -45,25 +47,15 @@
 #define POLR_FUSEAGG_ROW_LIMIT (1ull << 32)     // folded tuples below which the SUM cells are exact
 enum { POLR_FUSEAGG_ADD = 0, POLR_FUSEAGG_MIN = 1, POLR_FUSEAGG_MAX = 2 };
 
-struct PolrFuseAggArg { // one aggregate as requested, its column described
-	uint32_t fn;
-	int32_t src_join;
-	uint32_t src_col;
-	bool col_in_range;      // (src_join, src_col) names a column of the pipeline
-	uint32_t width, flags;  // of that column (flags: POLR_COL_SIGNED)
-};
-struct PolrFuseAggRequest {
-	bool has_out;
-	bool has_specs;
-	uint32_t n_aggs;
-	bool already_fused; // the output carries a grouped or an ungrouped fused sink
-	const PolrFuseAggArg *args; // [n_aggs] (read only when the count is in range)
-};
+// the sinks' request (polr_agg_plan.h); read here: has_out, has_specs, n_aggs, already_fused, and args[n_aggs] -- the column
+// form, and only when the count is in range
+typedef PolrAggRequest PolrFuseAggRequest;
 struct PolrFuseAggPlan {
 	char err[256];
 	bool unfuse;
 	uint32_t n_aggs;
 	uint32_t fn[POLR_FUSEAGG_MAX_AGGS];
+	PolrAggArgPlan agg[POLR_FUSEAGG_MAX_AGGS]; // the aggregates as the argument rule accepted them
 	uint32_t n_tables, words_per_table;
 	uint64_t cell_words;                      // of the allocation: (n_tables + 1) tables
 	uint8_t kind[POLR_FUSEAGG_MAX_WORDS];     // POLR_FUSEAGG_ADD / _MIN / _MAX per word
@@ -111,22 +103,11 @@ static inline int polr_fuseagg_plan(const PolrFuseAggRequest &rq, PolrFuseAggPla
 	pl->words_per_table = 1u + POLR_FUSEAGG_WORDS_PER_AGG * rq.n_aggs;
 	pl->cell_words = (uint64_t)(pl->n_tables + 1u) * pl->words_per_table;
 	for (uint32_t a = 0; a < rq.n_aggs; a++) {
-		const PolrFuseAggArg &g = rq.args[a];
-		if (g.fn > POLR_AGG_MAX) {
-			POLR_FA_REFUSE(POLR_E_INVALID, "aggregate %u: unknown function %u", a, g.fn);
+		const PolrAggArg &g = rq.args[a];
+		if (const int rc = polr_agg_arg_rule(g, a, &pl->agg[a], pl->err)) {
+			return rc;
 		}
 		pl->fn[a] = g.fn;
-		if (g.fn != POLR_AGG_COUNT_STAR) {
-			if (!g.col_in_range) {
-				if (g.src_join < 0) {
-					POLR_FA_REFUSE(POLR_E_INVALID, "aggregate %u: probe column %u out of range", a, g.src_col);
-				}
-				POLR_FA_REFUSE(POLR_E_INVALID, "aggregate %u: build column (%d,%u) out of range", a, g.src_join, g.src_col);
-			}
-			if (g.width > 8 || (g.width == 8 && !(g.flags & POLR_COL_SIGNED))) {
-				POLR_FA_REFUSE(POLR_E_UNSUPPORTED, "aggregate %u: only integer columns of up to 8 bytes (signed if 8)", a);
-			}
-		}
 		pl->has_sum = pl->has_sum || g.fn == POLR_AGG_SUM;
 		for (uint32_t w = 0; w < POLR_FUSEAGG_WORDS_PER_AGG; w++) {
 			pl->kind[POLR_FUSEAGG_A(a) + w] = (uint8_t)polr_fuseagg_word_kind(g.fn, w);
@@ -152,32 +133,11 @@ static inline int polr_fuseagg_decode(const uint32_t *fn, uint32_t n_aggs, const
 		}
 	}
 	for (uint32_t a = 0; a < n_aggs; a++) {
-		polr_agg_value v;
-		memset(&v, 0, sizeof(v));
 		const uint64_t n = fn[a] == POLR_AGG_COUNT_STAR ? rows : cells[POLR_FUSEAGG_N(a)];
-		v.count = n;
-		switch (fn[a]) {
-		case POLR_AGG_COUNT_STAR:
-		case POLR_AGG_COUNT:
-			v.lo = (int64_t)n;
-			break;
-		case POLR_AGG_SUM: {
-			v.is_null = n == 0;
-			const __int128 sum = (__int128)(int64_t)cells[POLR_FUSEAGG_B(a)] * ((__int128)1 << 32) +
-			                     (__int128)(unsigned __int128)cells[POLR_FUSEAGG_A(a)];
-			v.lo = (int64_t)(uint64_t)(unsigned __int128)sum;
-			v.hi = (int64_t)(sum >> 64);
-			break;
-		}
-		default: { // MIN, MAX
-			v.is_null = n == 0;
-			const int64_t x = (int64_t)(cells[POLR_FUSEAGG_A(a)] ^ POLR_FUSEAGG_SIGN);
-			v.lo = n ? x : 0;
-			v.hi = (n && x < 0) ? -1 : 0;
-			break;
-		}
-		}
-		results[a] = v;
+		const __int128 sum = (__int128)(int64_t)cells[POLR_FUSEAGG_B(a)] * ((__int128)1 << 32) +
+		                     (__int128)(unsigned __int128)cells[POLR_FUSEAGG_A(a)]; // (read for a SUM)
+		const int64_t x = (int64_t)(cells[POLR_FUSEAGG_A(a)] ^ POLR_FUSEAGG_SIGN);     // (read for MIN, MAX)
+		results[a] = polr_agg_decode(fn[a], sum, x, x, n);
 	}
 	return POLR_OK;
 }

@@ -307,7 +307,7 @@ static inline int out_ensure_stats(polr_out *o, void *stream) {
 	return o->stats_valid ? POLR_OK : polr_out_stats(o, stream, nullptr, nullptr, nullptr);
 }
 
-// column (src_join, src_col) of a pipeline's output, as a sink reads it (polr_agg.hip)
+// column (src_join, src_col) of a pipeline's output, as a sink reads it (polr_agg.hip, polr_strheap.hip)
 struct OutCol {
 	const OwnedCol *col;
 	uint32_t slot; // the output's row ids that index it: 0 probe, 1 + j join j
@@ -315,11 +315,15 @@ struct OutCol {
 };
 // POLR_E_INVALID for a column out of range ("<what> <idx>: ..." in the context's error)
 int polr_out_col(polr_pipeline *p, int32_t src_join, uint32_t src_col, OutCol *c, const char *what, uint32_t idx);
-// ... and POLR_E_UNSUPPORTED for anything but an integer column of up to 8 bytes (signed if 8): what cell-valued sinks read
-int polr_out_int_col(polr_pipeline *p, int32_t src_join, uint32_t src_col, OutCol *c, const char *what, uint32_t idx);
+// the same column described to the sinks' host plan (polr_agg_plan.h); in range: *c is resolved, as by polr_out_col
+PolrAggCol polr_out_describe_col(polr_pipeline *p, int32_t src_join, uint32_t src_col, OutCol *c);
+// POLR_OK when the VARCHAR column may be read by a kernel that follows string pointers: rebased onto a device heap, the
+// caller's own device memory, or without a non-NULL cell longer than 12 bytes among the output rows (polr_strheap.hip;
+// counts on stream st and waits for it); else the refusal below
+int check_string_col_on_device(polr_out *o, hipStream_t st, const OutCol &c, const char *what, uint32_t idx);
 
 // The refusal of a VARCHAR column the library uploaded whose heap never came, once a non-NULL cell longer than 12 bytes
-// turns up among the output rows (check_string_col_on_device of polr_agg.hip; polr_out_materialize_strings counts such
+// turns up among the output rows (check_string_col_on_device of polr_strheap.hip; polr_out_materialize_strings counts such
 // cells in its measuring pass): one message for every sink.
 #define POLR_FAIL_HEAP_NEVER_CAME(ctx_, what_, idx_, n_long_)                                                          \
 	POLR_FAIL(ctx_, POLR_E_INVALID,                                                                                    \
@@ -350,9 +354,7 @@ int polr_out_int_col(polr_pipeline *p, int32_t src_join, uint32_t src_col, OutCo
 #define POLR_REFUSE_AGG_CELLS(ctx_, out_)                                                                              \
 	do {                                                                                                               \
 		if ((out_)->agg_dev) {                                                                                         \
-			POLR_FAIL(ctx_, POLR_E_INVALID,                                                                            \
-			          "the output has a fused aggregate sink: it holds aggregate cells, no row ids "                    \
-			          "(polr_out_fused_aggregate_result)");                                                            \
+			POLR_FAIL(ctx_, POLR_E_INVALID, POLR_AGG_CELLS_TEXT);                                                      \
 		}                                                                                                              \
 	} while (0)
 

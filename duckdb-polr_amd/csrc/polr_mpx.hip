@@ -394,7 +394,7 @@ static PoolShape pool_shape(polr_pipeline *p, bool materialize, const polr_out *
 	// its routers' executors with it.)
 	sh.fused_words = 0;
 	if (sh.flat && sh.wpb && out && out->fused_dev) {
-		const uint64_t words = (uint64_t)out->fused_groups * (1u + 2u * out->fused_aggs);
+		const uint64_t words = (uint64_t)out->fused_groups * polr_fused_group_words(out->fused_aggs);
 		if (polr_pool_flat_lds_bytes(dp.k, sh.wpb, dp.lds_table_dwords) + 8 + words * 8 <= 160u * 1024u) {
 			sh.fused_words = (uint32_t)words;
 		}

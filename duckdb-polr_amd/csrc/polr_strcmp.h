@@ -4,7 +4,7 @@
 // Reference: StringComparisonOperators / templated_string_compare_op (src/include/duckdb/common/operator/
 // comparison_operators.hpp:157-227): memcmp over the shorter of the two lengths, bytes unsigned; on a tie the shorter
 // string is the smaller one (:203-208); equality is "same length, same bytes".  '\0' and 0x80-0xFF are ordinary bytes, no
-// collation.  str_less of polr_agg.hip (the string MIN / MAX sink) is the byte-loop form of the same order between two
+// collation.  str_less of polr_strheap.hip (the string MIN / MAX sink) is the byte-loop form of the same order between two
 // cells: both implement comparison_operators.hpp:203-208.
 //
 // A cell (string_type.hpp:23-28) is four little-endian words: the length, then either up to 12 characters (length <= 12;
@@ -150,6 +150,22 @@ POLR_STRCMP_HD int polr_str_cell_cmp3(uint32_t alen, uint32_t a0, uint32_t a1, u
 	}
 	return by_length;
 }
+
+#if defined(__HIPCC__)
+// byte i (i < length) of the string of a cell held as a uint4: what str_less (polr_strheap.hip) compares and the hashed
+// GROUP BY sink writes out (polr_group_strings_kernel, polr_agg.hip)
+__device__ __forceinline__ uint32_t str_byte(const uint4 &c, uint32_t i) {
+	if (c.x <= 12u) {
+		const uint32_t w = i < 4 ? c.y : (i < 8 ? c.z : c.w);
+		return (w >> (8u * (i & 3u))) & 0xFFu;
+	}
+	if (i < 4) {
+		return (c.y >> (8u * i)) & 0xFFu;
+	}
+	const uint8_t *p = (const uint8_t *)(((uint64_t)c.w << 32) | c.z);
+	return p[i];
+}
+#endif
 
 // does a three-way result satisfy a comparison code of include/polr_hip.h (POLR_CMP_EQ = 0 .. POLR_CMP_GE = 5)?
 POLR_STRCMP_HD bool polr_str_cmp_holds(int r, uint32_t op) {

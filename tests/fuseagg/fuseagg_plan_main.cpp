@@ -35,15 +35,15 @@ int main(int argc, char **argv) {
 			int has_out, has_specs, already;
 			uint32_t n_aggs;
 			ls >> has_out >> has_specs >> n_aggs >> already;
-			std::vector<PolrFuseAggArg> args;
+			std::vector<PolrAggArg> args;
 			while (std::getline(in, line) && line != "end") {
 				std::istringstream as(line);
 				std::string tag;
-				PolrFuseAggArg g;
+				PolrAggArg g; // (the column form: op = POLR_ARG_COLUMN, one operand)
 				memset(&g, 0, sizeof(g));
 				int in_range;
-				as >> tag >> g.fn >> g.src_join >> g.src_col >> in_range >> g.width >> g.flags;
-				g.col_in_range = in_range != 0;
+				as >> tag >> g.fn >> g.src_join[0] >> g.src_col[0] >> in_range >> g.col[0].width >> g.col[0].flags;
+				g.col[0].in_range = in_range != 0;
 				args.push_back(g);
 			}
 			PolrFuseAggRequest rq;
