@@ -24,7 +24,7 @@
 #include <vector>
 
 #include "polr_internal.h"
-#include "polr_strcmp.h" // str_byte
+#include "polr_strrec_plan.h" // the groups' strings leave as records (polr_fetch_str_records)
 
 struct AggPartial {
 	unsigned long long sum_lo; // two's complement 128-bit sum, low limb
@@ -588,7 +588,8 @@ __global__ __launch_bounds__(256) void polr_group_agg_kernel(DevOut out, uint32_
 	}
 }
 
-static polr_agg_value cell_value(const GroupCell &c, uint32_t fn) {
+// (always inlined: the decode loops over up to 2^24 groups store straight into the caller's results)
+static inline __attribute__((always_inline)) polr_agg_value cell_value(const GroupCell &c, uint32_t fn) {
 	return polr_agg_decode(fn, ((__int128)c.hi32 << 32) + (__int128)c.lo32, c.mn, c.mx, c.count);
 }
 
@@ -1149,33 +1150,6 @@ __global__ __launch_bounds__(256) void polr_hash_agg_compact_kernel(HashAggTable
 	}
 }
 
-// the groups' strings as records {u32 length, bytes} at the offsets the host laid out (offsets[g * n_cols + c])
-__global__ __launch_bounds__(256) void polr_group_strings_kernel(const uint4 *__restrict__ reps, const uint32_t *__restrict__ nulls,
-                                                                 const long long *__restrict__ offsets, uint64_t n_groups,
-                                                                 uint32_t n_cols, uint32_t str_mask, uint8_t *__restrict__ arena,
-                                                                 uint64_t arena_bytes) {
-	const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
-	if (i >= n_groups * n_cols) {
-		return;
-	}
-	const uint32_t q = (uint32_t)(i % n_cols);
-	if (!((str_mask >> q) & 1u) || ((nulls[i / n_cols] >> q) & 1u)) {
-		return;
-	}
-	const uint4 c = reps[i];
-	const uint64_t off = (uint64_t)offsets[i];
-	if (off > arena_bytes || arena_bytes - off < 4ull + c.x) {
-		return; // (never past the arena, whatever the offsets say)
-	}
-	uint8_t *dst = arena + off;
-	for (uint32_t j = 0; j < 4; j++) {
-		dst[j] = (uint8_t)(c.x >> (8u * j));
-	}
-	for (uint32_t j = 0; j < c.x; j++) {
-		dst[4 + j] = (uint8_t)str_byte(c, j);
-	}
-}
-
 extern "C" int polr_out_column_width(polr_out *o, int32_t src_join, uint32_t src_col, uint32_t *width) {
 	POLR_ENTRY();
 	if (!o || !width) {
@@ -1281,49 +1255,56 @@ static int aggregate_hashed(polr_out *o, void *stream, const polr_group_key *col
 	const bool too_many = h_cnt[1] || h_cnt[0] > max_groups;
 	const bool out_of_range = hc.out_of_range() != 0; // (the reference's query fails: nothing is copied to the caller)
 	const uint64_t g_n = too_many || out_of_range ? 0 : h_cnt[0];
+	if (e != hipSuccess) {
+		POLR_FAIL(ctx, POLR_E_HIP, "hash aggregate failed: %s", hipGetErrorString(e));
+	}
 	std::vector<GroupCell> hcells(g_n * n_aggs);
-	// integer columns only: keys and NULL bits go to the caller's arrays at once; with VARCHAR columns they are staged here
-	// until the strings' records fit, so that an arena too small leaves the caller's arrays as they were
-	std::vector<uint4> hreps(str_mask ? g_n * n_cols : 0);
-	std::vector<long long> skeys(str_mask ? g_n * n_cols : 0);
+	// integer columns only: keys and NULL bits go to the caller's arrays at once; with VARCHAR columns the NULL bits are staged
+	// and the keys stay on the device until the strings' records fit, so that an arena too small leaves the caller's arrays
+	// as they were
+	const uint64_t n_rec = str_mask ? g_n * n_cols : 0;
+	std::vector<uint4> hreps(n_rec);
+	std::vector<uint64_t> offs(n_rec); // the records' offsets
 	std::vector<uint32_t> snulls(str_mask ? g_n : 0);
-	long long *hkeys = str_mask ? skeys.data() : (long long *)group_keys;
 	uint32_t *hnulls = str_mask ? snulls.data() : group_nulls;
 	uint64_t used = 0;
-	if (e == hipSuccess && g_n) {
-		e = hipMemcpy(hkeys, okeys, g_n * n_cols * 8, hipMemcpyDeviceToHost);
-		e = e == hipSuccess ? hipMemcpy(hnulls, onulls, g_n * 4, hipMemcpyDeviceToHost) : e;
-		e = e == hipSuccess && str_mask ? hipMemcpy(hreps.data(), oreps, g_n * n_cols * 16, hipMemcpyDeviceToHost) : e;
-		e = e == hipSuccess ? hipMemcpy(hcells.data(), ocells, g_n * n_aggs * sizeof(GroupCell), hipMemcpyDeviceToHost) : e;
-		// lay the records out: a VARCHAR column's key word becomes the offset of its record (0 for NULL)
-		for (uint64_t g = 0; g < g_n && e == hipSuccess && str_mask; g++) {
-			for (uint32_t q = 0; q < n_cols; q++) {
-				if (!((str_mask >> q) & 1u)) {
-					continue;
-				}
-				long long &k = hkeys[g * n_cols + q];
-				k = 0;
-				if (!((hnulls[g] >> q) & 1u)) {
-					k = (long long)used;
-					used += 4ull + hreps[g * n_cols + q].x;
+	int records = POLR_OK;
+	if (g_n) {
+		if (!str_mask) {
+			HIPCHK(ctx, hipMemcpy(group_keys, okeys, g_n * n_cols * 8, hipMemcpyDeviceToHost));
+		}
+		HIPCHK(ctx, hipMemcpy(hnulls, onulls, g_n * 4, hipMemcpyDeviceToHost));
+		HIPCHK(ctx, hipMemcpy(hcells.data(), ocells, g_n * n_aggs * sizeof(GroupCell), hipMemcpyDeviceToHost));
+	}
+	if (n_rec) {
+		// the strings' records, group-major, then column: none for an integer column or a NULL value.  The offsets go up into
+		// the table's own keys, which nothing reads after the compaction (capacity >= 2 x max_groups slots)
+		HIPCHK(ctx, hipMemcpy(hreps.data(), oreps, n_rec * 16, hipMemcpyDeviceToHost));
+		uint64_t g = 0;
+		uint32_t q = 0;
+		used = polr_strrec_layout(n_rec, [&](uint64_t i) { // (i = g * n_cols + q, without the division)
+			const bool record = ((str_mask >> q) & 1u) && !((hnulls[g] >> q) & 1u);
+			if (++q == n_cols) {
+				q = 0;
+				g++;
+			}
+			return record ? (uint64_t)hreps[i].x : POLR_STRREC_NONE;
+		}, offs.data());
+		records = polr_fetch_str_records(ctx, st, oreps, nullptr, n_rec, offs.data(), used, n_rec, (uint64_t *)t.keys, str_bytes, str_cap);
+		if (records != POLR_OK && records != POLR_E_OVERFLOW) {
+			return records;
+		}
+	}
+	if (n_rec && records == POLR_OK) { // (with groups to report, only the arena can still be too small: it was not)
+		HIPCHK(ctx, hipMemcpy(group_keys, okeys, n_rec * 8, hipMemcpyDeviceToHost));
+		for (uint64_t g = 0, i = 0; g < g_n; g++) { // a VARCHAR column's key word is the offset of its record (0 for NULL)
+			for (uint32_t q = 0; q < n_cols; q++, i++) {
+				if ((str_mask >> q) & 1u) {
+					group_keys[i] = offs[i] == POLR_STRREC_NONE ? 0 : (int64_t)offs[i];
 				}
 			}
 		}
-	}
-	DevBuf<uint8_t> arena;
-	if (e == hipSuccess && g_n && used && used <= str_cap) {
-		e = arena.alloc(used);
-		e = e == hipSuccess ? hipMemcpyAsync(okeys, hkeys, g_n * n_cols * 8, hipMemcpyHostToDevice, st) : e;
-		if (e == hipSuccess) {
-			const uint64_t n_rec = g_n * n_cols;
-			hipLaunchKernelGGL(polr_group_strings_kernel, dim3((unsigned)((n_rec + 255) / 256)), dim3(256), 0, st, (const uint4 *)oreps,
-			                   (const uint32_t *)onulls, (const long long *)okeys, g_n, n_cols, str_mask, arena.get(), used);
-			e = hipMemcpyAsync(str_bytes, arena, used, hipMemcpyDeviceToHost, st);
-			e = e == hipSuccess ? hipStreamSynchronize(st) : e;
-		}
-	}
-	if (e != hipSuccess) {
-		POLR_FAIL(ctx, POLR_E_HIP, "hash aggregate failed: %s", hipGetErrorString(e));
+		memcpy(group_nulls, hnulls, g_n * 4);
 	}
 	rc = hc.check_range(ctx, n_out_of_range);
 	if (rc) {
@@ -1337,13 +1318,9 @@ static int aggregate_hashed(polr_out *o, void *stream, const polr_group_key *col
 	if (strings) {
 		*str_used = used;
 	}
-	if (used > str_cap) { // (nothing was written: group_keys, group_nulls, results and str_bytes are as they were)
+	if (records == POLR_E_OVERFLOW) { // (nothing was written: group_keys, group_nulls, results and str_bytes are as they were)
 		POLR_FAIL(ctx, POLR_E_OVERFLOW, "the groups' strings take %llu bytes, the caller made room for %llu", (unsigned long long)used,
 		          (unsigned long long)str_cap);
-	}
-	if (str_mask && g_n) {
-		memcpy(group_keys, hkeys, g_n * n_cols * 8);
-		memcpy(group_nulls, hnulls, g_n * 4);
 	}
 	for (uint64_t g = 0; g < g_n; g++) {
 		for (uint32_t a = 0; a < n_aggs; a++) {

@@ -30,15 +30,19 @@
 //   renumber  rank[old code] = sorted position, the representative cells in sorted order; assign writes rank[...].
 // Workgroups meet at kernel boundaries only; every loop is bounded by the tile size, log2(n_codes) or a string's length.
 // Distinct values never compare equal, so the result is unique whatever the network does with the padding records.
+//
+// The host side follows polr_dict_plan.h: the refusals of a request, what the device's answer means, the layout of the
+// scratch and of the sort's, the tile sizes.  The dictionary's strings leave the device as the records of
+// polr_strrec_plan.h, by polr_fetch_str_records (polr_strheap.hip).
 #include <algorithm>
 #include <cstring>
 
+#include "polr_dict_plan.h"
 #include "polr_internal.h"
 #include "polr_strcmp.h"
+#include "polr_strrec_plan.h"
 
 #define POLR_DICT_NO_SLOT 0xFFFFFFFFu
-#define POLR_DICT_BLOCK 256u
-#define POLR_DICT_ITEMS 4u // rows per thread of the rank step: 1024 rows per workgroup
 
 struct DictTable {
 	uint32_t *state;     // [capacity] 0 empty / 1 being written / 2 ready
@@ -241,7 +245,6 @@ __global__ __launch_bounds__(256) void polr_dict_reps_kernel(const uint4 *__rest
 }
 
 // ---- POLR_DICT_SORTED: the sort of the representative cells -----------------------------------------------------------------
-#define POLR_DICT_SORT_TILE 1024u // records a workgroup sorts or merges in LDS: 16 KB of the CU's 160
 #define POLR_DICT_SORT_ITEMS (POLR_DICT_SORT_TILE / POLR_DICT_BLOCK) // records a thread merges
 #define POLR_DICT_PAD 0xFFFFFFFFu // the code of a padding record: behind every string
 static_assert(POLR_DICT_SORT_TILE * 16u <= 32u * 1024u, "a tile is at most 32 KB of LDS");
@@ -253,6 +256,7 @@ struct alignas(16) DictRec {
 	uint32_t code; // first-appearance code
 	uint32_t len;
 };
+static_assert(sizeof(DictRec) == POLR_DICT_REC_BYTES, "polr_dict_sort_layout lays out records of this size");
 
 // a < b in the order of polr_strcmp.h.  rep_old: the cell of every first-appearance code
 __device__ __forceinline__ bool dict_rec_less(const DictRec &a, const DictRec &b, const uint4 *__restrict__ rep_old) {
@@ -410,37 +414,6 @@ __global__ __launch_bounds__(256) void polr_dict_lens_kernel(const uint4 *__rest
 	}
 }
 
-// the dictionary's strings as records {u32 length, bytes} at the offsets the host laid out: record c is the string of code
-// codes[c] (each below the dictionary's size: the host checked), or of code c where there is no list
-__global__ __launch_bounds__(256) void polr_dict_records_kernel(const uint4 *__restrict__ reps, const uint32_t *__restrict__ codes,
-                                                                const uint64_t *__restrict__ offsets, uint32_t n_records,
-                                                                uint8_t *__restrict__ arena, uint64_t arena_bytes) {
-	const uint32_t c = blockIdx.x * blockDim.x + threadIdx.x;
-	if (c >= n_records) {
-		return;
-	}
-	const uint4 cell = reps[codes ? codes[c] : c];
-	const uint64_t off = offsets[c];
-	if (off > arena_bytes || arena_bytes - off < 4ull + cell.x) {
-		return; // (never past the arena, whatever the offsets say)
-	}
-	uint8_t *dst = arena + off;
-	for (uint32_t j = 0; j < 4; j++) {
-		dst[j] = (uint8_t)(cell.x >> (8u * j));
-	}
-	if (cell.x <= 12u) {
-		const uint32_t w[3] = {cell.y, cell.z, cell.w};
-		for (uint32_t j = 0; j < cell.x; j++) {
-			dst[4 + j] = (uint8_t)(w[j >> 2] >> (8u * (j & 3u)));
-		}
-	} else {
-		const uint8_t *p = (const uint8_t *)(((uint64_t)cell.w << 32) | cell.z);
-		for (uint32_t j = 0; j < cell.x; j++) {
-			dst[4 + j] = p[j];
-		}
-	}
-}
-
 static uint32_t dict_grid(uint64_t n, int n_cus) {
 	return (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>((n + 255) / 256, (uint64_t)n_cus * 8));
 }
@@ -457,183 +430,140 @@ extern "C" int polr_ht_encode_dictionary_ex(polr_ht *ht, uint32_t payload_col, u
 		return POLR_E_INVALID;
 	}
 	polr_ctx *ctx = ht->ctx;
-	if (flags & ~(POLR_DICT_SORTED | POLR_DICT_NULL_INVALID)) {
-		POLR_FAIL(ctx, POLR_E_INVALID, "dictionary flags 0x%x: only POLR_DICT_SORTED and POLR_DICT_NULL_INVALID are defined", flags);
-	}
-	const bool sorted = (flags & POLR_DICT_SORTED) != 0;
-	if (ht->kind != KIND_NONE) {
-		// (a finalized perfect table keeps a re-ordered copy of every payload column, and the engines hold the column array)
-		POLR_FAIL(ctx, POLR_E_INVALID, "a payload column is dictionary-encoded before the table is finalized");
-	}
-	if (payload_col >= ht->n_payload) {
-		POLR_FAIL(ctx, POLR_E_INVALID, "payload column %u of %u", payload_col, ht->n_payload);
-	}
+	// the request, and what the plan says to it
+	const DictCol *prior = polr_dict_of_src_col(ht, payload_col);
+	PolrDictRequest rq = {};
+	rq.flags = flags;
+	rq.payload_col = payload_col;
+	rq.finalized = ht->kind != KIND_NONE;
+	rq.n_payload = ht->n_payload;
+	rq.width = payload_col < ht->n_payload ? ht->payload[payload_col].width : 0;
+	rq.encoded = prior != nullptr;
+	rq.encoded_as = prior ? prior->code_col : 0;
+	rq.n_rows = ht->n_rows_in;
+	PolrDictPlan pl;
+	POLR_TRY_PLAN(ctx, pl, polr_dict_plan_encode(rq, &pl));
 	const OwnedCol &src = ht->payload[payload_col]; // (not read after the code column is appended)
-	if (src.width != 16) {
-		POLR_FAIL(ctx, POLR_E_INVALID, "a dictionary is made of a column of 16-byte string cells (this one: %u bytes)", src.width);
-	}
-	for (const DictCol &d : ht->dicts) {
-		if (d.src_col == payload_col) {
-			POLR_FAIL(ctx, POLR_E_INVALID, "payload column %u is encoded already (code column %u)", payload_col, d.code_col);
-		}
-	}
-	if (ht->n_payload >= POLR_BUILD_MAX_PAYLOAD) {
-		// (polr_ht_export / polr_ht_alloc_like describe no more payload columns: no table is made that cannot be shipped)
-		POLR_FAIL(ctx, POLR_E_UNSUPPORTED, "the table has %u payload columns already: a code column would be the %urd, more than "
-		                                   "polr_ht_export carries", ht->n_payload, POLR_BUILD_MAX_PAYLOAD + 1);
-	}
-	const uint64_t n = ht->n_rows_in;
-	PolrCapacityPlan slots_plan; // the string table: a slot space of its own, the build side's capacity rule
-	if (polr_build_capacity(n, slots_plan)) {
-		POLR_FAIL(ctx, POLR_E_UNSUPPORTED, "a dictionary over %llu build rows exceeds the 32-bit slot space", (unsigned long long)n);
-	}
-	const uint64_t capacity = slots_plan.capacity;
+	const uint64_t n = rq.n_rows;
+	const uint4 *cells = (const uint4 *)src.data;
+	const uint8_t *valid = src.valid;
 	HIPCHK(ctx, hipSetDevice(ctx->device));
 	hipStream_t st = polr_stream(ctx, stream);
 	if (st != ctx->stream) {
 		// (the column's cells were uploaded, and rebased onto their heap, on the context's stream)
 		HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
 	}
-	const uint4 *cells = (const uint4 *)src.data;
-	const uint32_t n_blocks = (uint32_t)std::max<uint64_t>(1, (n + POLR_DICT_BLOCK * POLR_DICT_ITEMS - 1) / (POLR_DICT_BLOCK * POLR_DICT_ITEMS));
-	// one scratch allocation: the table, the per-row and per-block arrays, the scalars
-	const size_t b_rep = capacity * 16, b_hash = capacity * 8, b_state = capacity * 4, b_first = capacity * 4, b_code = capacity * 4,
-	             b_slot = (n * 4 + 15) & ~(size_t)15, b_roc = (n * 4 + 15) & ~(size_t)15, b_sums = ((size_t)n_blocks * 4 + 15) & ~(size_t)15,
-	             b_scalars = 64;
-	DevBuf<uint8_t> base;
+	// allocate: the code column and one scratch allocation.  Everything up to the commit lives in this scope: a failure
+	// frees it and leaves the table exactly as it was
 	OwnedCol codes;
 	codes.width = 4;
 	codes.flags = 0;
-	const uint64_t acct = polr_build_buffer_bytes(n * 4); // (what polr_ht_export reports for the column)
-	HIPCHK(ctx, codes.alloc_data(acct));
-	if ((flags & POLR_DICT_NULL_INVALID) && src.valid) { // the code column's own copy of the validity array
+	HIPCHK(ctx, codes.alloc_data(polr_build_buffer_bytes(n * 4))); // (what polr_ht_export reports for the column)
+	const bool copy_valid = pl.null_invalid && valid; // the code column's own copy of the validity array
+	if (copy_valid) {
 		HIPCHK(ctx, codes.alloc_valid(n));
 		if (n) {
-			HIPCHK(ctx, hipMemcpyAsync(codes.valid, src.valid, n, hipMemcpyDeviceToDevice, st));
+			HIPCHK(ctx, hipMemcpyAsync(codes.valid, valid, n, hipMemcpyDeviceToDevice, st));
 		}
 	}
-	hipError_t e = base.alloc(b_rep + b_hash + b_state + b_first + b_code + b_slot + b_roc + b_sums + b_scalars);
+	PolrDictLayout lo;
+	polr_dict_layout(pl.capacity, n, &lo);
+	DevBuf<uint8_t> base;
+	HIPCHK(ctx, base.alloc(lo.total));
 	DictTable t;
-	memset(&t, 0, sizeof(t));
-	uint8_t *at = base;
-	t.rep = (uint4 *)at;
-	at += b_rep;
-	t.hash = (uint64_t *)at;
-	at += b_hash;
-	t.state = (uint32_t *)at;
-	at += b_state;
-	t.first_row = (uint32_t *)at;
-	at += b_first;
-	t.code = (uint32_t *)at;
-	at += b_code;
-	uint32_t *slot_of_row = (uint32_t *)at;
-	at += b_slot;
-	uint32_t *row_of_code = (uint32_t *)at;
-	at += b_roc;
-	uint32_t *block_sums = (uint32_t *)at;
-	at += b_sums;
-	uint32_t *scalars = (uint32_t *)at;
-	t.mask = capacity - 1;
-	uint32_t h_scalars[DICT_SCALARS] = {0, 0, 0, 0};
-	unsigned long long h_long = 0;
-	if (e == hipSuccess && n && src.owned() && !src.strings_rebased) {
-		// the library uploaded the column and its heap never came: inline strings only, checked before a pointer is followed
-		unsigned long long *n_long = (unsigned long long *)(scalars + 8);
-		e = hipMemsetAsync(n_long, 0, 8, st);
-		if (e == hipSuccess) {
-			hipLaunchKernelGGL(polr_dict_count_long_kernel, dim3(dict_grid(n, ctx->n_cus)), dim3(256), 0, st, cells,
-			                   (const uint8_t *)src.valid, n, n_long);
-			e = hipMemcpyAsync(&h_long, n_long, 8, hipMemcpyDeviceToHost, st);
-			e = e == hipSuccess ? hipStreamSynchronize(st) : e;
-		}
+	t.rep = (uint4 *)(base + lo.rep);
+	t.hash = (uint64_t *)(base + lo.hash);
+	t.state = (uint32_t *)(base + lo.state);
+	t.first_row = (uint32_t *)(base + lo.first_row);
+	t.code = (uint32_t *)(base + lo.code);
+	t.mask = pl.capacity - 1;
+	uint32_t *slot_of_row = (uint32_t *)(base + lo.slot_of_row);
+	uint32_t *row_of_code = (uint32_t *)(base + lo.row_of_code);
+	uint32_t *block_sums = (uint32_t *)(base + lo.block_sums);
+	uint32_t *scalars = (uint32_t *)(base + lo.scalars);
+	// heap guard: the library uploaded the column and its heap never came: inline strings only, checked before a pointer is
+	// followed
+	if (n && src.owned() && !src.strings_rebased) {
+		unsigned long long *n_long = (unsigned long long *)(base + lo.n_long), h_long = 0;
+		HIPCHK(ctx, hipMemsetAsync(n_long, 0, 8, st));
+		hipLaunchKernelGGL(polr_dict_count_long_kernel, dim3(dict_grid(n, ctx->n_cus)), dim3(256), 0, st, cells, valid, n, n_long);
+		HIPCHK(ctx, hipMemcpyAsync(&h_long, n_long, 8, hipMemcpyDeviceToHost, st));
+		HIPCHK(ctx, hipStreamSynchronize(st));
+		POLR_TRY_PLAN(ctx, pl, polr_dict_plan_outcome(nullptr, h_long, false, payload_col, &pl));
 	}
-	if (e == hipSuccess && !h_long) {
-		e = hipMemsetAsync(scalars, 0, DICT_SCALARS * 4, st);
-	}
-	if (e == hipSuccess && !h_long && n) {
-		hipLaunchKernelGGL(polr_dict_init_kernel, dim3(dict_grid(capacity, ctx->n_cus)), dim3(256), 0, st, t);
-		hipLaunchKernelGGL(polr_dict_insert_kernel, dim3(dict_grid(n, ctx->n_cus)), dim3(256), 0, st, cells, (const uint8_t *)src.valid, n, t,
-		                   slot_of_row, scalars);
-		hipLaunchKernelGGL(polr_dict_rank_reduce_kernel, dim3(n_blocks), dim3(POLR_DICT_BLOCK), 0, st, t, (const uint32_t *)slot_of_row, n,
-		                   block_sums);
-		polr_launch_scan_blocksums(st, block_sums, n_blocks, &scalars[DICT_N_CODES]);
-		hipLaunchKernelGGL(polr_dict_rank_apply_kernel, dim3(n_blocks), dim3(POLR_DICT_BLOCK), 0, st, t, (const uint32_t *)slot_of_row, n,
-		                   (const uint32_t *)block_sums, row_of_code);
-		if (!sorted) {
+	// build: insert and rank; first-appearance codes are assigned at once
+	HIPCHK(ctx, hipMemsetAsync(scalars, 0, DICT_SCALARS * 4, st));
+	if (n) {
+		hipLaunchKernelGGL(polr_dict_init_kernel, dim3(dict_grid(pl.capacity, ctx->n_cus)), dim3(256), 0, st, t);
+		hipLaunchKernelGGL(polr_dict_insert_kernel, dim3(dict_grid(n, ctx->n_cus)), dim3(256), 0, st, cells, valid, n, t, slot_of_row,
+		                   scalars);
+		hipLaunchKernelGGL(polr_dict_rank_reduce_kernel, dim3(lo.n_blocks), dim3(POLR_DICT_BLOCK), 0, st, t, (const uint32_t *)slot_of_row,
+		                   n, block_sums);
+		polr_launch_scan_blocksums(st, block_sums, lo.n_blocks, &scalars[DICT_N_CODES]);
+		hipLaunchKernelGGL(polr_dict_rank_apply_kernel, dim3(lo.n_blocks), dim3(POLR_DICT_BLOCK), 0, st, t, (const uint32_t *)slot_of_row,
+		                   n, (const uint32_t *)block_sums, row_of_code);
+		if (!pl.sorted) {
 			hipLaunchKernelGGL(polr_dict_assign_kernel, dim3(dict_grid(n, ctx->n_cus)), dim3(256), 0, st, t, (const uint32_t *)slot_of_row, n,
 			                   (const uint32_t *)scalars, (const uint32_t *)nullptr, (uint32_t *)codes.data);
 		}
 	}
-	if (e == hipSuccess && !h_long) { // the final count
-		e = hipMemcpyAsync(h_scalars, scalars, sizeof(h_scalars), hipMemcpyDeviceToHost, st);
-		e = e == hipSuccess ? hipStreamSynchronize(st) : e;
-	}
+	// count: the one read-back of the scalars
+	uint32_t h_scalars[DICT_SCALARS] = {0, 0, 0, 0};
+	hipError_t e = hipMemcpyAsync(h_scalars, scalars, sizeof(h_scalars), hipMemcpyDeviceToHost, st);
+	e = e == hipSuccess ? hipStreamSynchronize(st) : e;
+	POLR_TRY_PLAN(ctx, pl,
+	              polr_dict_plan_outcome(e != hipSuccess ? hipGetErrorString(e) : nullptr, 0, h_scalars[DICT_FULL] != 0, payload_col, &pl));
 	DictCol d;
 	d.src_col = payload_col;
 	d.code_col = ht->n_payload;
 	d.n_codes = h_scalars[DICT_N_CODES];
 	d.has_null = h_scalars[DICT_HAS_NULL];
-	const bool ok = e == hipSuccess && !h_long && !h_scalars[DICT_FULL];
-	// sorted codes, two values or more: per distinct value two records (ping and pong), a copy of its cell, its rank
-	const bool sort = ok && sorted && d.n_codes > 1;
-	const uint64_t nc = d.n_codes;
+	// sort (sorted codes, two values or more) or representatives
 	DevBuf<uint8_t> sort_mem;
 	const uint32_t *rank = nullptr;
-	if (ok && d.n_codes) {
-		e = d.cells.alloc(d.n_codes);
-		if (e == hipSuccess && sort) {
-			e = sort_mem.alloc(nc * (2 * sizeof(DictRec) + 16 + 4));
-		}
-		if (e == hipSuccess && sort) {
-			DictRec *from = (DictRec *)sort_mem.get(), *to = from + nc;
-			uint4 *rep_old = (uint4 *)(to + nc);
-			uint32_t *rank_of = (uint32_t *)(rep_old + nc);
-			const uint32_t n_tiles = (uint32_t)((nc + POLR_DICT_SORT_TILE - 1) / POLR_DICT_SORT_TILE);
-			hipLaunchKernelGGL(polr_dict_sort_keys_kernel, dim3((d.n_codes + 255) / 256), dim3(256), 0, st, cells,
-			                   (const uint32_t *)row_of_code, d.n_codes, rep_old, from);
-			hipLaunchKernelGGL(polr_dict_sort_tile_kernel, dim3(n_tiles), dim3(POLR_DICT_BLOCK), 0, st, from, d.n_codes,
-			                   (const uint4 *)rep_old);
-			for (uint64_t run = POLR_DICT_SORT_TILE; run < nc; run <<= 1) {
-				hipLaunchKernelGGL(polr_dict_sort_merge_kernel, dim3(n_tiles), dim3(POLR_DICT_BLOCK), 0, st, (const DictRec *)from, to,
-				                   d.n_codes, (uint32_t)run, (const uint4 *)rep_old);
-				std::swap(from, to);
-			}
-			hipLaunchKernelGGL(polr_dict_renumber_kernel, dim3((d.n_codes + 255) / 256), dim3(256), 0, st, (const DictRec *)from,
-			                   (const uint4 *)rep_old, d.n_codes, d.cells.get(), rank_of);
-			rank = rank_of;
-		} else if (e == hipSuccess) {
-			hipLaunchKernelGGL(polr_dict_reps_kernel, dim3((d.n_codes + 255) / 256), dim3(256), 0, st, cells, (const uint32_t *)row_of_code,
-			                   d.n_codes, d.cells.get());
-		}
+	if (d.n_codes) {
+		HIPCHK(ctx, d.cells.alloc(d.n_codes));
 	}
-	if (ok && e == hipSuccess && sorted && n) { // (sorted codes are assigned once their ranks are known)
+	if (pl.sorted && d.n_codes > 1) {
+		PolrDictSortLayout so;
+		polr_dict_sort_layout(d.n_codes, &so);
+		HIPCHK(ctx, sort_mem.alloc(so.total));
+		DictRec *from = (DictRec *)(sort_mem + so.ping), *to = (DictRec *)(sort_mem + so.pong);
+		uint4 *rep_old = (uint4 *)(sort_mem + so.rep_old);
+		uint32_t *rank_of = (uint32_t *)(sort_mem + so.rank);
+		hipLaunchKernelGGL(polr_dict_sort_keys_kernel, dim3((d.n_codes + 255) / 256), dim3(256), 0, st, cells, (const uint32_t *)row_of_code,
+		                   d.n_codes, rep_old, from);
+		hipLaunchKernelGGL(polr_dict_sort_tile_kernel, dim3(so.n_tiles), dim3(POLR_DICT_BLOCK), 0, st, from, d.n_codes,
+		                   (const uint4 *)rep_old);
+		for (uint32_t p = 0; p < so.n_merge_passes; p++) {
+			hipLaunchKernelGGL(polr_dict_sort_merge_kernel, dim3(so.n_tiles), dim3(POLR_DICT_BLOCK), 0, st, (const DictRec *)from, to,
+			                   d.n_codes, POLR_DICT_SORT_TILE << p, (const uint4 *)rep_old);
+			std::swap(from, to);
+		}
+		hipLaunchKernelGGL(polr_dict_renumber_kernel, dim3((d.n_codes + 255) / 256), dim3(256), 0, st, (const DictRec *)from,
+		                   (const uint4 *)rep_old, d.n_codes, d.cells.get(), rank_of);
+		rank = rank_of;
+	} else if (d.n_codes) {
+		hipLaunchKernelGGL(polr_dict_reps_kernel, dim3((d.n_codes + 255) / 256), dim3(256), 0, st, cells, (const uint32_t *)row_of_code,
+		                   d.n_codes, d.cells.get());
+	}
+	// assign (sorted codes: once their ranks are known)
+	if (pl.sorted && n) {
 		hipLaunchKernelGGL(polr_dict_assign_kernel, dim3(dict_grid(n, ctx->n_cus)), dim3(256), 0, st, t, (const uint32_t *)slot_of_row, n,
 		                   (const uint32_t *)scalars, rank, (uint32_t *)codes.data);
 	}
-	if (ok && e == hipSuccess && (d.n_codes || sorted)) {
-		e = hipStreamSynchronize(st);
+	if (d.n_codes || pl.sorted) {
+		HIPCHK(ctx, hipStreamSynchronize(st));
 	}
-	if (!ok || e != hipSuccess) { // the table is exactly as it was: codes, d.cells and the scratch go with this scope
-		if (e != hipSuccess) {
-			POLR_FAIL(ctx, POLR_E_HIP, "dictionary encoding failed: %s", hipGetErrorString(e));
-		}
-		if (h_long) {
-			POLR_FAIL(ctx, POLR_E_INVALID,
-			          "payload column %u: %llu build rows hold strings longer than 12 bytes, but the column's heap was never put on the "
-			          "device (polr_ht_set_payload_heaps)",
-			          payload_col, h_long);
-		}
-		POLR_FAIL(ctx, POLR_E_HIP, "dictionary encoding failed: the string table filled up");
-	}
-	// from here on an ordinary payload column: 4 bytes, unsigned, no validity array but the one POLR_DICT_NULL_INVALID copied
-	const uint64_t valid_bytes = codes.own_valid.bytes();
-	ht->payload.push_back(std::move(codes));
-	ht->n_payload++;
-	ht->device_bytes += acct + valid_bytes + (uint64_t)d.n_codes * 16;
-	ht->dicts.push_back(std::move(d));
+	// commit: nothing can fail from here on.  The code column is an ordinary payload column: 4 bytes, unsigned, no validity
+	// array but the one POLR_DICT_NULL_INVALID copied
 	*code_col = d.code_col;
 	*n_codes = d.n_codes;
 	*has_null = d.has_null;
+	ht->device_bytes += polr_dict_device_bytes(n, copy_valid, d.n_codes);
+	ht->payload.push_back(std::move(codes));
+	ht->n_payload++;
+	ht->dicts.push_back(std::move(d));
 	return POLR_OK;
 }
 
@@ -644,45 +574,27 @@ extern "C" int polr_ht_fetch_dictionary(polr_ht *ht, uint32_t code_col, void *st
 		return POLR_E_INVALID;
 	}
 	polr_ctx *ctx = ht->ctx;
-	const DictCol *d = nullptr;
-	for (const DictCol &x : ht->dicts) {
-		if (x.code_col == code_col) {
-			d = &x;
-		}
-	}
-	if (!d) {
-		// (also a table made by polr_ht_alloc_like / received by polr_bcast_build: it carries the codes, not the strings)
-		POLR_FAIL(ctx, POLR_E_INVALID, "payload column %u is not a code column whose dictionary this table holds", code_col);
-	}
+	const DictCol *d = polr_dict_of_code_col(ht, code_col);
+	PolrDictPlan pl;
+	POLR_TRY_PLAN(ctx, pl, polr_dict_plan_fetch(d != nullptr, code_col, 0, nullptr, 0, &pl));
 	*str_used = 0;
 	if (d->n_codes == 0) {
 		return POLR_OK;
 	}
 	HIPCHK(ctx, hipSetDevice(ctx->device));
 	hipStream_t st = polr_stream(ctx, stream);
-	std::vector<uint4> reps(d->n_codes);
+	std::vector<uint4> reps(d->n_codes); // (their first words are the lengths)
 	HIPCHK(ctx, hipMemcpyAsync(reps.data(), d->cells, (size_t)d->n_codes * 16, hipMemcpyDeviceToHost, st));
 	HIPCHK(ctx, hipStreamSynchronize(st));
-	std::vector<uint64_t> offs(d->n_codes);
-	uint64_t used = 0;
-	for (uint32_t c = 0; c < d->n_codes; c++) {
-		offs[c] = used;
-		used += 4ull + reps[c].x;
-	}
-	*str_used = used;
-	if (used > str_cap || n_offsets < d->n_codes) { // (nothing was written: offsets and str_bytes are as they were)
+	std::vector<uint64_t> offs(d->n_codes); // code after code
+	*str_used = polr_strrec_layout(d->n_codes, [&](uint64_t c) { return (uint64_t)reps[c].x; }, offs.data());
+	const int rc = polr_fetch_str_records(ctx, st, d->cells, nullptr, d->n_codes, offs.data(), *str_used, n_offsets, nullptr, str_bytes,
+	                                      str_cap);
+	if (rc == POLR_E_OVERFLOW) { // (nothing was written: offsets and str_bytes are as they were)
 		POLR_FAIL(ctx, POLR_E_OVERFLOW, "the dictionary has %u strings in %llu bytes, the caller made room for %llu and %llu", d->n_codes,
-		          (unsigned long long)used, (unsigned long long)n_offsets, (unsigned long long)str_cap);
+		          (unsigned long long)*str_used, (unsigned long long)n_offsets, (unsigned long long)str_cap);
 	}
-	DevBuf<uint8_t> arena;
-	DevBuf<uint64_t> d_offs;
-	HIPCHK(ctx, arena.alloc(used));
-	HIPCHK(ctx, d_offs.alloc(d->n_codes));
-	HIPCHK(ctx, hipMemcpyAsync(d_offs, offs.data(), (size_t)d->n_codes * 8, hipMemcpyHostToDevice, st));
-	hipLaunchKernelGGL(polr_dict_records_kernel, dim3((d->n_codes + 255) / 256), dim3(256), 0, st, (const uint4 *)d->cells.get(),
-	                   (const uint32_t *)nullptr, (const uint64_t *)d_offs.get(), d->n_codes, arena.get(), used);
-	HIPCHK(ctx, hipMemcpyAsync(str_bytes, arena, used, hipMemcpyDeviceToHost, st));
-	HIPCHK(ctx, hipStreamSynchronize(st));
+	POLR_TRY(rc);
 	memcpy(offsets, offs.data(), (size_t)d->n_codes * 8);
 	return POLR_OK;
 }
@@ -694,24 +606,9 @@ extern "C" int polr_ht_fetch_dictionary_codes(polr_ht *ht, uint32_t code_col, vo
 		return POLR_E_INVALID;
 	}
 	polr_ctx *ctx = ht->ctx;
-	const DictCol *d = nullptr;
-	for (const DictCol &x : ht->dicts) {
-		if (x.code_col == code_col) {
-			d = &x;
-		}
-	}
-	if (!d) {
-		POLR_FAIL(ctx, POLR_E_INVALID, "payload column %u is not a code column whose dictionary this table holds", code_col);
-	}
-	if (n > (1ull << 30)) {
-		POLR_FAIL(ctx, POLR_E_UNSUPPORTED, "a list of %llu codes: at most 2^30 strings are fetched by one call", (unsigned long long)n);
-	}
-	for (uint64_t i = 0; i < n; i++) {
-		if (codes[i] >= d->n_codes) { // (nothing was written, *str_used included)
-			POLR_FAIL(ctx, POLR_E_INVALID, "code %u at position %llu of the list: the dictionary has %u strings (the NULL code is none)",
-			          codes[i], (unsigned long long)i, d->n_codes);
-		}
-	}
+	const DictCol *d = polr_dict_of_code_col(ht, code_col);
+	PolrDictPlan pl;
+	POLR_TRY_PLAN(ctx, pl, polr_dict_plan_fetch(d != nullptr, code_col, d ? d->n_codes : 0, codes, n, &pl));
 	*str_used = 0;
 	if (n == 0) {
 		return POLR_OK;
@@ -719,7 +616,7 @@ extern "C" int polr_ht_fetch_dictionary_codes(polr_ht *ht, uint32_t code_col, vo
 	HIPCHK(ctx, hipSetDevice(ctx->device));
 	hipStream_t st = polr_stream(ctx, stream);
 	const uint32_t n32 = (uint32_t)n;
-	DevBuf<uint32_t> d_codes, d_lens;
+	DevBuf<uint32_t> d_codes, d_lens; // (the lengths come from the device: the cells stay there)
 	HIPCHK(ctx, d_codes.alloc(n));
 	HIPCHK(ctx, d_lens.alloc(n));
 	HIPCHK(ctx, hipMemcpyAsync(d_codes, codes, (size_t)n * 4, hipMemcpyHostToDevice, st));
@@ -728,26 +625,14 @@ extern "C" int polr_ht_fetch_dictionary_codes(polr_ht *ht, uint32_t code_col, vo
 	std::vector<uint32_t> lens(n);
 	HIPCHK(ctx, hipMemcpyAsync(lens.data(), d_lens, (size_t)n * 4, hipMemcpyDeviceToHost, st));
 	HIPCHK(ctx, hipStreamSynchronize(st));
-	std::vector<uint64_t> offs(n);
-	uint64_t used = 0;
-	for (uint64_t i = 0; i < n; i++) {
-		offs[i] = used;
-		used += 4ull + lens[i];
-	}
-	*str_used = used;
-	if (used > str_cap) { // (nothing was written: offsets and str_bytes are as they were)
+	std::vector<uint64_t> offs(n); // list order, a record per duplicate
+	*str_used = polr_strrec_layout(n, [&](uint64_t i) { return (uint64_t)lens[i]; }, offs.data());
+	const int rc = polr_fetch_str_records(ctx, st, d->cells, d_codes, n, offs.data(), *str_used, n, nullptr, str_bytes, str_cap);
+	if (rc == POLR_E_OVERFLOW) { // (nothing was written: offsets and str_bytes are as they were)
 		POLR_FAIL(ctx, POLR_E_OVERFLOW, "the %llu listed strings take %llu bytes, the caller made room for %llu", (unsigned long long)n,
-		          (unsigned long long)used, (unsigned long long)str_cap);
+		          (unsigned long long)*str_used, (unsigned long long)str_cap);
 	}
-	DevBuf<uint8_t> arena;
-	DevBuf<uint64_t> d_offs;
-	HIPCHK(ctx, arena.alloc(used));
-	HIPCHK(ctx, d_offs.alloc(n));
-	HIPCHK(ctx, hipMemcpyAsync(d_offs, offs.data(), (size_t)n * 8, hipMemcpyHostToDevice, st));
-	hipLaunchKernelGGL(polr_dict_records_kernel, dim3((n32 + 255) / 256), dim3(256), 0, st, (const uint4 *)d->cells.get(),
-	                   (const uint32_t *)d_codes.get(), (const uint64_t *)d_offs.get(), n32, arena.get(), used);
-	HIPCHK(ctx, hipMemcpyAsync(str_bytes, arena, used, hipMemcpyDeviceToHost, st));
-	HIPCHK(ctx, hipStreamSynchronize(st));
+	POLR_TRY(rc);
 	memcpy(offsets, offs.data(), (size_t)n * 8);
 	return POLR_OK;
 }

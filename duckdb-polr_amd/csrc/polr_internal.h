@@ -124,6 +124,24 @@ struct polr_ht {
 	uint64_t device_bytes = 0;
 };
 
+// the dictionary whose code column / whose VARCHAR source column is payload column `col`, or nullptr
+static inline const DictCol *polr_dict_of_code_col(const polr_ht *ht, uint32_t col) {
+	for (const DictCol &d : ht->dicts) {
+		if (d.code_col == col) {
+			return &d;
+		}
+	}
+	return nullptr;
+}
+static inline const DictCol *polr_dict_of_src_col(const polr_ht *ht, uint32_t col) {
+	for (const DictCol &d : ht->dicts) {
+		if (d.src_col == col) {
+			return &d;
+		}
+	}
+	return nullptr;
+}
+
 struct polr_pipeline {
 	polr_ctx *ctx = nullptr;
 	uint32_t k = 0, n_paths = 0, n_probe_cols = 0;
@@ -321,6 +339,17 @@ PolrAggCol polr_out_describe_col(polr_pipeline *p, int32_t src_join, uint32_t sr
 // caller's own device memory, or without a non-NULL cell longer than 12 bytes among the output rows (polr_strheap.hip;
 // counts on stream st and waits for it); else the refusal below
 int check_string_col_on_device(polr_out *o, hipStream_t st, const OutCol &c, const char *what, uint32_t idx);
+
+// Strings leave the device as records (polr_strrec_plan.h), by one path (polr_strheap.hip): entry i of n is the string of
+// cell d_cells[d_index ? d_index[i] : i] (device memory), at offs[i] (host memory, as polr_strrec_layout laid them out:
+// POLR_STRREC_NONE = no record), `used` bytes in all.  Where they fit the caller's room (polr_strrec_fits) the records are
+// written on the device into an arena of exactly `used` bytes and that is copied to str_bytes; waits for the stream.
+// d_offs: device memory of n words for the offsets that the caller owns and no longer needs, or NULL (allocated here).
+// POLR_E_OVERFLOW where they do not fit: nothing was written, and the context's error is left to the caller, whose
+// wording it is.
+int polr_fetch_str_records(polr_ctx *ctx, hipStream_t st, const uint4 *d_cells, const uint32_t *d_index, uint64_t n,
+                           const uint64_t *offs, uint64_t used, uint64_t n_offsets, uint64_t *d_offs, uint8_t *str_bytes,
+                           uint64_t str_cap);
 
 // The refusal of a VARCHAR column the library uploaded whose heap never came, once a non-NULL cell longer than 12 bytes
 // turns up among the output rows (check_string_col_on_device of polr_strheap.hip; polr_out_materialize_strings counts such

@@ -152,8 +152,8 @@ POLR_STRCMP_HD int polr_str_cell_cmp3(uint32_t alen, uint32_t a0, uint32_t a1, u
 }
 
 #if defined(__HIPCC__)
-// byte i (i < length) of the string of a cell held as a uint4: what str_less (polr_strheap.hip) compares and the hashed
-// GROUP BY sink writes out (polr_group_strings_kernel, polr_agg.hip)
+// byte i (i < length) of the string of a cell held as a uint4: what str_less compares and the string records are written
+// from (polr_str_records_kernel; both polr_strheap.hip)
 __device__ __forceinline__ uint32_t str_byte(const uint4 &c, uint32_t i) {
 	if (c.x <= 12u) {
 		const uint32_t w = i < 4 ? c.y : (i < 8 ? c.z : c.w);

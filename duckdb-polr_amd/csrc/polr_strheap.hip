@@ -1,6 +1,7 @@
 // duckdb-polr_amd/csrc/polr_strheap.hip -- VARCHAR columns on the device: the upload of their string heaps
 // (polr_ht_set_payload_heap(s), polr_pipeline_set_probe_heap(s)), the guard of a column whose heap never came
-// (check_string_col_on_device, polr_internal.h) and the MIN / MAX sink over string_t cells (polr_out_aggregate_string).
+// (check_string_col_on_device, polr_internal.h), the MIN / MAX sink over string_t cells (polr_out_aggregate_string) and the
+// one path by which strings leave the device as records (polr_fetch_str_records, polr_internal.h; polr_strrec_plan.h).
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <string.h>
@@ -10,6 +11,7 @@
 
 #include "polr_internal.h"
 #include "polr_strcmp.h"
+#include "polr_strrec_plan.h"
 
 // ---- VARCHAR: string heaps on the device and the MIN / MAX sink over string_t cells -------------------------------------
 // (string_type.hpp:23-28: {u32 length, char inlined[12]} or {u32 length, char prefix[4], char *ptr})
@@ -197,6 +199,69 @@ int check_string_col_on_device(polr_out *o, hipStream_t st, const OutCol &c, con
 	if (h_long) {
 		POLR_FAIL_HEAP_NEVER_CAME(ctx, what, idx, h_long);
 	}
+	return POLR_OK;
+}
+
+// ---- string records: how strings leave the device (polr_strrec_plan.h) -------------------------------------------------
+// the bytes of the string of cell c through str_byte.  INLINE says which form the cell has (length <= 12, or prefix and
+// pointer), so that the loop is compiled once per form -- str_byte folds to the word shift or to the pointer read --
+// instead of deciding it for every byte
+template <bool INLINE>
+__device__ __forceinline__ void str_record_bytes(uint8_t *__restrict__ dst, const uint4 &c) {
+	__builtin_assume(INLINE ? c.x <= 12u : c.x > 12u);
+	for (uint32_t j = 0; j < c.x; j++) {
+		dst[j] = (uint8_t)str_byte(c, j);
+	}
+}
+
+// record i {u32 length, bytes} of the string of cell cells[index ? index[i] : i], at the offset the host laid out
+__global__ __launch_bounds__(256) void polr_str_records_kernel(const uint4 *__restrict__ cells, const uint32_t *__restrict__ index,
+                                                               const uint64_t *__restrict__ offsets, uint64_t n,
+                                                               uint8_t *__restrict__ arena, uint64_t arena_bytes) {
+	const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+	if (i >= n) {
+		return;
+	}
+	const uint64_t off = offsets[i];
+	if (off == POLR_STRREC_NONE) {
+		return; // (no record: the cell may hold anything and is not read)
+	}
+	const uint4 c = cells[index ? index[i] : i];
+	if (off > arena_bytes || arena_bytes - off < 4ull + c.x) {
+		return; // (never past the arena, whatever the offsets say)
+	}
+	uint8_t *dst = arena + off;
+	for (uint32_t j = 0; j < 4; j++) {
+		dst[j] = (uint8_t)(c.x >> (8u * j));
+	}
+	if (c.x <= 12u) {
+		str_record_bytes<true>(dst + 4, c);
+	} else {
+		str_record_bytes<false>(dst + 4, c);
+	}
+}
+
+int polr_fetch_str_records(polr_ctx *ctx, hipStream_t st, const uint4 *d_cells, const uint32_t *d_index, uint64_t n,
+                           const uint64_t *offs, uint64_t used, uint64_t n_offsets, uint64_t *d_offs, uint8_t *str_bytes,
+                           uint64_t str_cap) {
+	if (!polr_strrec_fits(used, str_cap, n, n_offsets)) {
+		return POLR_E_OVERFLOW;
+	}
+	if (used == 0) {
+		return POLR_OK; // (no entry has a record)
+	}
+	DevBuf<uint8_t> arena;
+	DevBuf<uint64_t> own_offs;
+	HIPCHK(ctx, arena.alloc(used));
+	if (!d_offs) {
+		HIPCHK(ctx, own_offs.alloc(n));
+		d_offs = own_offs;
+	}
+	HIPCHK(ctx, hipMemcpyAsync(d_offs, offs, n * 8, hipMemcpyHostToDevice, st));
+	hipLaunchKernelGGL(polr_str_records_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, d_cells, d_index,
+	                   (const uint64_t *)d_offs, n, arena.get(), used);
+	HIPCHK(ctx, hipMemcpyAsync(str_bytes, arena, used, hipMemcpyDeviceToHost, st));
+	HIPCHK(ctx, hipStreamSynchronize(st));
 	return POLR_OK;
 }
 

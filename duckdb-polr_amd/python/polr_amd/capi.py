@@ -252,6 +252,25 @@ def _heap_ranges(blocks):
     return arr
 
 
+def _record(raw, at):
+    """the string record at offset `at` of a byte arena, {u32 length, little endian; the bytes} (polr_strrec_plan.h) -> bytes"""
+    ln = int.from_bytes(raw[at:at + 4], "little")
+    return raw[at + 4:at + 4 + ln]
+
+
+def _fetch_records(call, cap):
+    """call(str_bytes, str_cap, byref(str_used)) -> rc with a byte arena of `cap` bytes (a first guess), repeated once with
+    the exact size when the guess was too small -> (rc of the last call, the arena as bytes)"""
+    used = C.c_uint64()
+    for attempt in (0, 1):
+        arena = np.zeros((max(cap, 1),), dtype=np.uint8)
+        rc = call(arena.ctypes.data, cap, C.byref(used))
+        if not (rc == E_OVERFLOW and attempt == 0 and used.value > cap):
+            break
+        cap = used.value
+    return rc, arena.tobytes()
+
+
 class AggSpec(C.Structure):
     _fields_ = [("fn", C.c_uint32), ("src_join", C.c_int32), ("src_col", C.c_uint32)]
 
@@ -717,46 +736,22 @@ class HashTable:
         it), [bytes] indexed by code.  The byte arena is sized here (str_cap: a first guess) and the call repeated once
         with the exact size when the guess was too small."""
         n_codes = getattr(self, "_n_codes", {}).get(code_col, 0)  # (not encoded through this object: the call refuses)
-        used = C.c_uint64()
-        for attempt in (0, 1):
-            offs = np.zeros((max(n_codes, 1),), dtype=np.uint64)
-            arena = np.zeros((max(str_cap, 1),), dtype=np.uint8)
-            rc = self.ctx.L.polr_ht_fetch_dictionary(self.h, code_col, stream, offs.ctypes.data, n_codes, arena.ctypes.data,
-                                                     str_cap, C.byref(used))
-            if rc == E_OVERFLOW and attempt == 0 and used.value > str_cap:
-                str_cap = used.value
-                continue
-            self.ctx.check(rc)
-            break
-        raw = arena.tobytes()
-        out = []
-        for at in offs[:n_codes].tolist():
-            ln = int.from_bytes(raw[at:at + 4], "little")
-            out.append(raw[at + 4:at + 4 + ln])
-        return out
+        offs = np.zeros((max(n_codes, 1),), dtype=np.uint64)
+        rc, raw = _fetch_records(lambda *arena: self.ctx.L.polr_ht_fetch_dictionary(self.h, code_col, stream, offs.ctypes.data,
+                                                                                    n_codes, *arena), str_cap)
+        self.ctx.check(rc)
+        return [_record(raw, at) for at in offs[:n_codes].tolist()]
 
     def dictionary_strings(self, code_col, codes, str_cap=4096, stream=None):
         """polr_ht_fetch_dictionary_codes: the strings of the listed codes of code column `code_col`, [bytes] in list order
         (duplicates included); one retry with the exact size when str_cap was too small"""
         codes = np.ascontiguousarray(codes, dtype=np.uint32)
         n = len(codes)
-        used = C.c_uint64()
-        for attempt in (0, 1):
-            offs = np.zeros((max(n, 1),), dtype=np.uint64)
-            arena = np.zeros((max(str_cap, 1),), dtype=np.uint8)
-            rc = self.ctx.L.polr_ht_fetch_dictionary_codes(self.h, code_col, stream, codes.ctypes.data, n, offs.ctypes.data,
-                                                           arena.ctypes.data, str_cap, C.byref(used))
-            if rc == E_OVERFLOW and attempt == 0 and used.value > str_cap:
-                str_cap = used.value
-                continue
-            self.ctx.check(rc)
-            break
-        raw = arena.tobytes()
-        out = []
-        for at in offs[:n].tolist():
-            ln = int.from_bytes(raw[at:at + 4], "little")
-            out.append(raw[at + 4:at + 4 + ln])
-        return out
+        offs = np.zeros((max(n, 1),), dtype=np.uint64)
+        rc, raw = _fetch_records(lambda *arena: self.ctx.L.polr_ht_fetch_dictionary_codes(self.h, code_col, stream, codes.ctypes.data,
+                                                                                          n, offs.ctypes.data, *arena), str_cap)
+        self.ctx.check(rc)
+        return [_record(raw, at) for at in offs[:n].tolist()]
 
     @classmethod
     def from_rows(cls, ctx, rows, n_rows, row_width, col_offset, col_width, col_signed, n_keys, n_payload):
@@ -1117,18 +1112,15 @@ class Output:
         keys = np.zeros((max_groups, nk), dtype=np.int64)
         nulls = np.zeros((max_groups,), dtype=np.uint32)
         res = (AggValue * (max_groups * na))()
-        n, used, oor = C.c_uint64(), C.c_uint64(), C.c_uint64()
+        n, oor = C.c_uint64(), C.c_uint64()
         cap = (max(4096, 24 * max_groups) if str_cap is None else int(str_cap)) if strings else 0
-        for attempt in (0, 1):
-            arena = np.zeros((cap,), dtype=np.uint8)
-            tail = ((arena.ctypes.data, cap, C.byref(used)) if strings else ()) + ((C.byref(oor),) if ranged else ())
-            rc = entry(self.h, stream, ka, nk, sa, na, max_groups, keys.ctypes.data, nulls.ctypes.data, res, C.byref(n), *tail)
-            if rc == E_OVERFLOW and attempt == 0 and used.value > cap:  # (the strings did not fit; the groups did)
-                cap = used.value
-                continue
-            self.ctx.check_range(rc, oor)
-            break
-        raw = arena.tobytes()
+
+        def call(*arena):  # (repeated where the strings did not fit; the groups did)
+            tail = (arena if strings else ()) + ((C.byref(oor),) if ranged else ())
+            return entry(self.h, stream, ka, nk, sa, na, max_groups, keys.ctypes.data, nulls.ctypes.data, res, C.byref(n), *tail)
+
+        rc, raw = _fetch_records(call, cap)
+        self.ctx.check_range(rc, oor)
         is_str = [strings and self._col_width(sj, sc) == 16 for sj, sc in cols]
         out = {}
         for g in range(n.value):
@@ -1137,9 +1129,7 @@ class Output:
                 if (nulls[g] >> c) & 1:
                     key.append(None)
                 elif is_str[c]:
-                    at = int(keys[g, c])
-                    ln = int.from_bytes(raw[at:at + 4], "little")
-                    key.append(raw[at + 4:at + 4 + ln])
+                    key.append(_record(raw, int(keys[g, c])))
                 else:
                     key.append(int(keys[g, c]))
             out[tuple(key)] = [_agg_int(res[g * na + a]) for a in range(na)]

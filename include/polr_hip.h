@@ -751,8 +751,10 @@ int polr_out_aggregate_hashed(polr_out *o, void *stream, const polr_group_key *c
  * a NULL row is never read.  The aggregates are those of polr_out_aggregate over integer columns.  With integer columns only
  * the call IS polr_out_aggregate_hashed (and *str_used = 0).
  * Results as for polr_out_aggregate_hashed, except that for a VARCHAR column group_keys[g * n_cols + c] is the byte offset
- * in str_bytes of the record {uint32 length (little endian), bytes} of the group's string (0, and to be ignored, when the
- * column's group_nulls bit is set).  *str_used = the bytes the records take.  str_cap < *str_used: POLR_E_OVERFLOW with
+ * in str_bytes of the STRING RECORD of the group's string (0, and to be ignored, when the column's group_nulls bit is set).
+ * A string record is {uint32 length (little endian), bytes}; records follow each other without padding, and none is written
+ * unless all fit.  It is the one format in which strings leave the device, here and in polr_ht_fetch_dictionary[_codes]
+ * below.  *str_used = the bytes the records take.  str_cap < *str_used: POLR_E_OVERFLOW with
  * *n_groups and *str_used exact and group_keys, group_nulls, results and str_bytes untouched -- one retry with str_cap =
  * *str_used succeeds.  More than max_groups groups: POLR_E_OVERFLOW as for polr_out_aggregate_hashed, *str_used = 0.
  * The strings of a VARCHAR column longer than 12 bytes are read through the cells' pointers, so they must be on the device:
@@ -915,7 +917,7 @@ int polr_pipeline_set_probe_heap(polr_pipeline *p, uint32_t probe_col, const voi
  *    table of 2 to 4 slots per build row, plus 8 bytes per build row -- up to about 150 bytes per build row, freed before
  *    it returns: sized for dimension tables; POLR_E_HIP (table untouched) when the device cannot give that much.
  * The table keeps one representative string_t cell per code (pointing into the heap it owns); polr_ht_fetch_dictionary
- * reads them: offsets[c] = byte offset in str_bytes of the record {uint32 length (little endian), bytes} of code c,
+ * reads them: offsets[c] = byte offset in str_bytes of the string record (polr_out_aggregate_hashed_str above) of code c,
  * c < n_codes; *str_used = the bytes the records take.  str_cap < *str_used or n_offsets < n_codes: POLR_E_OVERFLOW with
  * *str_used exact and offsets / str_bytes untouched -- one retry with *str_used succeeds.  POLR_E_INVALID for a column that
  * is not a code column of this table, a table that was never encoded, and a table made by polr_ht_alloc_like / received
@@ -942,7 +944,7 @@ int polr_pipeline_set_probe_heap(polr_pipeline *p, uint32_t probe_col, const voi
  *    SQL (NULLs take no part), the perfect-hash sink counts NULL-key rows in *n_dropped as for any NULL group key, and the
  *    hashed sink makes NULL a group of its own.  Without the flag, or for a source column without validity: no validity
  *    array, as above.
- * polr_ht_fetch_dictionary_codes returns the records {uint32 length, bytes} of the `n` listed codes, in list order, instead
+ * polr_ht_fetch_dictionary_codes returns the string records of the `n` listed codes, in list order, instead
  * of the whole dictionary: offsets[i] = byte offset of the record of codes[i], duplicates get a record each, *str_used =
  * the bytes the records take.  n = 0: POLR_OK, *str_used = 0.  A listed code >= n_codes (the NULL code is not a string):
  * POLR_E_INVALID, nothing written.  str_cap < *str_used: POLR_E_OVERFLOW with *str_used exact and offsets / str_bytes
