@@ -1,5 +1,6 @@
 // duckdb-polr_amd/csrc/polr_dict.hip -- dictionary encoding of a VARCHAR payload column of a build side
-// (polr_ht_encode_dictionary[_ex] / polr_ht_fetch_dictionary[_codes] of include/polr_hip.h).
+// or of a probe column of a pipeline (polr_ht_encode_dictionary[_ex] / polr_ht_fetch_dictionary[_codes],
+// polr_pipeline_encode_dictionary / polr_pipeline_fetch_dictionary[_codes] of include/polr_hip.h).
 //
 // A group column that is a payload column of a build side has at most as many distinct values as the build side has rows,
 // and the build side is uploaded once: the strings are hashed and compared ONCE PER BUILD ROW here, at build time, and the
@@ -31,14 +32,23 @@
 // Workgroups meet at kernel boundaries only; every loop is bounded by the tile size, log2(n_codes) or a string's length.
 // Distinct values never compare equal, so the result is unique whatever the network does with the padding records.
 //
-// The host side follows polr_dict_plan.h: the refusals of a request, what the device's answer means, the layout of the
-// scratch and of the sort's, the tile sizes.  The dictionary's strings leave the device as the records of
-// polr_strrec_plan.h, by polr_fetch_str_records (polr_strheap.hip).
+// A VARCHAR PROBE column is encoded by the same steps (polr_pipeline_encode_dictionary), and becomes an ordinary 4-byte
+// probe column of its pipeline.  Probe tables are the large ones and their sources are usually filtered, so the call has a
+// mode over the selection in force (POLR_DICT_SELECTED): the insert step and the heap guard read r = sel[i] for the
+// positions of the selection and no other row, the string table is sized by the selected count, and slot_of_row starts as
+// "no slot" everywhere, so that rank and assign -- which run over the table's rows -- give the rows outside the selection
+// the NULL code.  A selection may be in any order and name a row twice: the insert lowers first_row by a wave reduction
+// over the lanes on a slot, not by the lowest lane.
+//
+// The host side follows polr_dict_plan.h and polr_pdict_plan.h: the refusals of a request, what the device's answer means,
+// the layout of the scratch and of the sort's, the tile sizes.  The dictionary's strings leave the device as the records
+// of polr_strrec_plan.h, by polr_fetch_str_records (polr_strheap.hip).
 #include <algorithm>
 #include <cstring>
 
 #include "polr_dict_plan.h"
 #include "polr_internal.h"
+#include "polr_pdict_plan.h"
 #include "polr_strcmp.h"
 #include "polr_strrec_plan.h"
 
@@ -64,12 +74,16 @@ __global__ __launch_bounds__(256) void polr_dict_init_kernel(DictTable t) {
 }
 
 // the guard of a column whose cells were never rebased onto a device heap: its non-NULL cells longer than 12 bytes (their
-// pointers are the host's).  Reads the length word of a cell and nothing else.
+// pointers are the host's).  Reads the length word of a cell and nothing else.  SEL: the rows are those of sel[0 .. n), a row
+// counted once per position that lists it.
+template <bool SEL>
 __global__ __launch_bounds__(256) void polr_dict_count_long_kernel(const uint4 *__restrict__ cells, const uint8_t *__restrict__ valid,
-                                                                   uint64_t n, unsigned long long *__restrict__ n_long) {
+                                                                   const uint32_t *__restrict__ sel, uint64_t n_rows, uint64_t n,
+                                                                   unsigned long long *__restrict__ n_long) {
 	unsigned long long mine = 0;
-	for (uint64_t r = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; r < n; r += (uint64_t)gridDim.x * blockDim.x) {
-		if (valid && !valid[r]) {
+	for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (uint64_t)gridDim.x * blockDim.x) {
+		const uint64_t r = SEL ? sel[i] : i;
+		if (r >= n_rows || (valid && !valid[r])) { // (a position that names no row of the table selects nothing)
 			continue;
 		}
 		mine += *(const uint32_t *)(cells + r) > 12u ? 1u : 0u;
@@ -94,19 +108,51 @@ __device__ __forceinline__ bool dict_first_of_equals(uint32_t v, bool want, uint
 	return first;
 }
 
+__device__ __forceinline__ uint32_t wave_min32(uint32_t v) { // the same minimum in every lane
+#pragma unroll
+	for (int d = 32; d > 0; d >>= 1) {
+		v = min(v, (uint32_t)__shfl_xor((int)v, d, 64));
+	}
+	return v;
+}
+
+// of every set of lanes that `want` it and hold the same value v: the minimum of their x, returned in the lowest lane of the
+// set; 0xFFFFFFFF in every other lane (x is below that: a row number).  To be called by all lanes of the wave.  One
+// reduction per distinct value among those lanes.
+__device__ __forceinline__ uint32_t dict_min_of_equals(uint32_t v, uint32_t x, bool want) {
+	const uint32_t lane = threadIdx.x & 63u;
+	uint64_t todo = __ballot(want);
+	uint32_t out = 0xFFFFFFFFu;
+	while (todo) {
+		const int l = __builtin_ctzll(todo);
+		const uint32_t lv = (uint32_t)__builtin_amdgcn_readlane((int)v, l);
+		const bool mine = want && v == lv;
+		const uint32_t low = wave_min32(mine ? x : 0xFFFFFFFFu);
+		out = lane == (uint32_t)l ? low : out;
+		todo &= ~__ballot(mine);
+	}
+	return out;
+}
+
 // insert: the claim protocol of the general GROUP BY sink (polr_hash_agg_kernel, polr_agg.hip): a row claims an empty slot
 // with a compare-and-swap, writes hash and cell, and publishes them with a release store of state 2; every other row reads
 // the state with an acquire load.  A lane that meets a slot "being written" does not wait inside the iteration -- the writer
 // may be a lane of its own wave, which runs in lockstep -- it looks again in the next iteration of the loop all lanes share.
 // Few distinct values is the common shape (5 nations over millions of customers): hash + one slot read + one comparison.
+//
+// SEL: position i of sel[0 .. n) inserts table row sel[i] (the selection in force: a scan's result ascends, a host's list
+// is in any order and may name a row twice); rows the selection does not name are never read, and their slot_of_row is what
+// the host put there.
+template <bool SEL>
 __global__ __launch_bounds__(256) void polr_dict_insert_kernel(const uint4 *__restrict__ cells, const uint8_t *__restrict__ valid,
-                                                               uint64_t n, DictTable t, uint32_t *__restrict__ slot_of_row,
-                                                               uint32_t *__restrict__ scalars) {
+                                                               const uint32_t *__restrict__ sel, uint64_t n_rows, uint64_t n, DictTable t,
+                                                               uint32_t *__restrict__ slot_of_row, uint32_t *__restrict__ scalars) {
 	const uint32_t lane = threadIdx.x & 63u;
 	// (every thread of a workgroup makes the same number of trips: the probe loop below is a workgroup-wide one)
 	for (uint64_t base = (uint64_t)blockIdx.x * blockDim.x; base < n; base += (uint64_t)gridDim.x * blockDim.x) {
-		const uint64_t r = base + threadIdx.x;
-		const bool in_range = r < n;
+		const uint64_t i = base + threadIdx.x;
+		const uint64_t r = SEL ? (i < n ? (uint64_t)sel[i] : n_rows) : i;
+		const bool in_range = SEL ? r < n_rows : r < n; // (a position that names no row of the table selects nothing)
 		const bool is_null = in_range && valid && !valid[r];
 		const bool active = in_range && !is_null;
 		uint4 cell = make_uint4(0, 0, 0, 0);
@@ -156,8 +202,17 @@ __global__ __launch_bounds__(256) void polr_dict_insert_kernel(const uint4 *__re
 		// wave and distinct slot at most, whatever the distribution (every row on one slot: one per wave).
 		const bool below = s32 != POLR_DICT_NO_SLOT &&
 		                   (uint32_t)r < __hip_atomic_load(&t.first_row[s32], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-		if (dict_first_of_equals(s32, below, lane)) {
-			atomicMin(&t.first_row[s32], (uint32_t)r);
+		if (!SEL) {
+			if (dict_first_of_equals(s32, below, lane)) {
+				atomicMin(&t.first_row[s32], (uint32_t)r);
+			}
+		} else {
+			// through a selection the rows do NOT rise with the lane: the lanes on a slot are reduced to their lowest row, which
+			// the first of them sends -- still one atomic per wave and distinct slot at most
+			const uint32_t low = dict_min_of_equals(s32, (uint32_t)r, below);
+			if (low != 0xFFFFFFFFu) {
+				atomicMin(&t.first_row[s32], low);
+			}
 		}
 	}
 }
@@ -241,6 +296,18 @@ __global__ __launch_bounds__(256) void polr_dict_reps_kernel(const uint4 *__rest
 	const uint32_t c = blockIdx.x * blockDim.x + threadIdx.x;
 	if (c < n_codes) {
 		reps[c] = cells[row_of_code[c]];
+	}
+}
+
+// POLR_DICT_SELECTED | POLR_DICT_NULL_INVALID: the code column's validity array is `valid AND selected`.  The host has
+// written zeros; every position of the selection writes its row's validity (1 where the source has no array).
+__global__ __launch_bounds__(256) void polr_dict_sel_valid_kernel(const uint8_t *__restrict__ valid, const uint32_t *__restrict__ sel,
+                                                                  uint64_t n_rows, uint64_t n, uint8_t *__restrict__ out) {
+	for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (uint64_t)gridDim.x * blockDim.x) {
+		const uint64_t r = sel[i];
+		if (r < n_rows) {
+			out[r] = valid ? valid[r] : (uint8_t)1;
+		}
 	}
 }
 
@@ -418,56 +485,61 @@ static uint32_t dict_grid(uint64_t n, int n_cus) {
 	return (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>((n + 255) / 256, (uint64_t)n_cus * 8));
 }
 
-extern "C" int polr_ht_encode_dictionary(polr_ht *ht, uint32_t payload_col, void *stream, uint32_t *code_col, uint32_t *n_codes,
-                                         uint32_t *has_null) {
-	return polr_ht_encode_dictionary_ex(ht, payload_col, 0u, stream, code_col, n_codes, has_null);
+// What the two encode calls ask of the encoder they share (dict_encode): the plan's answer and the column.  sel: the
+// positions inserted (POLR_DICT_SELECTED with a selection in force), NULL: every row.
+struct DictJob {
+	const PolrDictPlan *pl;  // sorted, null_invalid, capacity
+	const OwnedCol *src;     // the VARCHAR column, of n_rows rows
+	uint64_t n_rows;
+	const uint32_t *sel;     // device, n_insert positions
+	uint64_t n_insert;       // sel == NULL: n_rows
+	uint32_t col;            // the column's number, for the refusals
+	bool probe;              // a probe column: the refusals in the pipeline's words (polr_pdict_plan.h)
+};
+
+static int dict_outcome(const DictJob &job, const char *hip_error, unsigned long long n_long, bool full, PolrPDictPlan *pl) {
+	return job.probe ? polr_pdict_plan_outcome(hip_error, n_long, full, job.col, pl) : polr_dict_plan_outcome(hip_error, n_long, full, job.col, pl);
 }
 
-extern "C" int polr_ht_encode_dictionary_ex(polr_ht *ht, uint32_t payload_col, uint32_t flags, void *stream, uint32_t *code_col,
-                                            uint32_t *n_codes, uint32_t *has_null) {
-	POLR_ENTRY();
-	if (!ht || !code_col || !n_codes || !has_null) {
-		return POLR_E_INVALID;
-	}
-	polr_ctx *ctx = ht->ctx;
-	// the request, and what the plan says to it
-	const DictCol *prior = polr_dict_of_src_col(ht, payload_col);
-	PolrDictRequest rq = {};
-	rq.flags = flags;
-	rq.payload_col = payload_col;
-	rq.finalized = ht->kind != KIND_NONE;
-	rq.n_payload = ht->n_payload;
-	rq.width = payload_col < ht->n_payload ? ht->payload[payload_col].width : 0;
-	rq.encoded = prior != nullptr;
-	rq.encoded_as = prior ? prior->code_col : 0;
-	rq.n_rows = ht->n_rows_in;
-	PolrDictPlan pl;
-	POLR_TRY_PLAN(ctx, pl, polr_dict_plan_encode(rq, &pl));
-	const OwnedCol &src = ht->payload[payload_col]; // (not read after the code column is appended)
-	const uint64_t n = rq.n_rows;
+// The encoder: the code column (and its validity array, where it gets one) into `codes`, the counts and the representative
+// cells into `d`.  Allocates, launches and waits; touches no handle -- the caller commits what it returns, or nothing.
+static int dict_encode(polr_ctx *ctx, hipStream_t st, const DictJob &job, OwnedCol &codes, DictCol &d) {
+	PolrPDictPlan pl = PolrPDictPlan(); // (the text of a refusal of the device's answer)
+	pl.sorted = job.pl->sorted;
+	pl.null_invalid = job.pl->null_invalid;
+	pl.capacity = job.pl->capacity;
+	const OwnedCol &src = *job.src;
+	const uint64_t n = job.n_rows, n_insert = job.n_insert;
 	const uint4 *cells = (const uint4 *)src.data;
 	const uint8_t *valid = src.valid;
-	HIPCHK(ctx, hipSetDevice(ctx->device));
-	hipStream_t st = polr_stream(ctx, stream);
-	if (st != ctx->stream) {
-		// (the column's cells were uploaded, and rebased onto their heap, on the context's stream)
-		HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
-	}
-	// allocate: the code column and one scratch allocation.  Everything up to the commit lives in this scope: a failure
-	// frees it and leaves the table exactly as it was
-	OwnedCol codes;
+	const uint32_t *sel = job.sel;
+	// allocate: the code column and one scratch allocation.  Everything lives in the caller's scope or in this one: a
+	// failure frees it
 	codes.width = 4;
 	codes.flags = 0;
 	HIPCHK(ctx, codes.alloc_data(polr_build_buffer_bytes(n * 4))); // (what polr_ht_export reports for the column)
-	const bool copy_valid = pl.null_invalid && valid; // the code column's own copy of the validity array
-	if (copy_valid) {
+	if (pl.null_invalid && sel) {
+		// through a selection: `valid AND selected`, also for a source without a validity array
+		HIPCHK(ctx, codes.alloc_valid(n));
+		if (n) {
+			HIPCHK(ctx, hipMemsetAsync(codes.valid, 0, n, st));
+		}
+		if (n_insert) {
+			hipLaunchKernelGGL(polr_dict_sel_valid_kernel, dim3(dict_grid(n_insert, ctx->n_cus)), dim3(256), 0, st, valid, sel, n, n_insert,
+			                   codes.valid);
+		}
+	} else if (pl.null_invalid && valid) { // the code column's own copy of the validity array
 		HIPCHK(ctx, codes.alloc_valid(n));
 		if (n) {
 			HIPCHK(ctx, hipMemcpyAsync(codes.valid, valid, n, hipMemcpyDeviceToDevice, st));
 		}
 	}
 	PolrDictLayout lo;
-	polr_dict_layout(pl.capacity, n, &lo);
+	if (sel) {
+		polr_pdict_layout(pl.capacity, n, n_insert, &lo);
+	} else {
+		polr_dict_layout(pl.capacity, n, &lo);
+	}
 	DevBuf<uint8_t> base;
 	HIPCHK(ctx, base.alloc(lo.total));
 	DictTable t;
@@ -483,20 +555,33 @@ extern "C" int polr_ht_encode_dictionary_ex(polr_ht *ht, uint32_t payload_col, u
 	uint32_t *scalars = (uint32_t *)(base + lo.scalars);
 	// heap guard: the library uploaded the column and its heap never came: inline strings only, checked before a pointer is
 	// followed
-	if (n && src.owned() && !src.strings_rebased) {
+	if (n_insert && src.owned() && !src.strings_rebased) {
 		unsigned long long *n_long = (unsigned long long *)(base + lo.n_long), h_long = 0;
 		HIPCHK(ctx, hipMemsetAsync(n_long, 0, 8, st));
-		hipLaunchKernelGGL(polr_dict_count_long_kernel, dim3(dict_grid(n, ctx->n_cus)), dim3(256), 0, st, cells, valid, n, n_long);
+		if (sel) {
+			hipLaunchKernelGGL(polr_dict_count_long_kernel<true>, dim3(dict_grid(n_insert, ctx->n_cus)), dim3(256), 0, st, cells, valid, sel, n,
+			                   n_insert, n_long);
+		} else {
+			hipLaunchKernelGGL(polr_dict_count_long_kernel<false>, dim3(dict_grid(n, ctx->n_cus)), dim3(256), 0, st, cells, valid,
+			                   (const uint32_t *)nullptr, n, n, n_long);
+		}
 		HIPCHK(ctx, hipMemcpyAsync(&h_long, n_long, 8, hipMemcpyDeviceToHost, st));
 		HIPCHK(ctx, hipStreamSynchronize(st));
-		POLR_TRY_PLAN(ctx, pl, polr_dict_plan_outcome(nullptr, h_long, false, payload_col, &pl));
+		POLR_TRY_PLAN(ctx, pl, dict_outcome(job, nullptr, h_long, false, &pl));
 	}
-	// build: insert and rank; first-appearance codes are assigned at once
+	// build: insert and rank; first-appearance codes are assigned at once.  Through a selection the rows it does not name
+	// start, and stay, without a slot: the rank and assign steps run over the table's rows as they are
 	HIPCHK(ctx, hipMemsetAsync(scalars, 0, DICT_SCALARS * 4, st));
 	if (n) {
 		hipLaunchKernelGGL(polr_dict_init_kernel, dim3(dict_grid(pl.capacity, ctx->n_cus)), dim3(256), 0, st, t);
-		hipLaunchKernelGGL(polr_dict_insert_kernel, dim3(dict_grid(n, ctx->n_cus)), dim3(256), 0, st, cells, valid, n, t, slot_of_row,
-		                   scalars);
+		if (sel) {
+			HIPCHK(ctx, hipMemsetAsync(slot_of_row, 0xFF, n * 4, st)); // (POLR_DICT_NO_SLOT)
+			hipLaunchKernelGGL(polr_dict_insert_kernel<true>, dim3(dict_grid(n_insert, ctx->n_cus)), dim3(256), 0, st, cells, valid, sel, n,
+			                   n_insert, t, slot_of_row, scalars);
+		} else {
+			hipLaunchKernelGGL(polr_dict_insert_kernel<false>, dim3(dict_grid(n, ctx->n_cus)), dim3(256), 0, st, cells, valid,
+			                   (const uint32_t *)nullptr, n, n, t, slot_of_row, scalars);
+		}
 		hipLaunchKernelGGL(polr_dict_rank_reduce_kernel, dim3(lo.n_blocks), dim3(POLR_DICT_BLOCK), 0, st, t, (const uint32_t *)slot_of_row,
 		                   n, block_sums);
 		polr_launch_scan_blocksums(st, block_sums, lo.n_blocks, &scalars[DICT_N_CODES]);
@@ -511,11 +596,7 @@ extern "C" int polr_ht_encode_dictionary_ex(polr_ht *ht, uint32_t payload_col, u
 	uint32_t h_scalars[DICT_SCALARS] = {0, 0, 0, 0};
 	hipError_t e = hipMemcpyAsync(h_scalars, scalars, sizeof(h_scalars), hipMemcpyDeviceToHost, st);
 	e = e == hipSuccess ? hipStreamSynchronize(st) : e;
-	POLR_TRY_PLAN(ctx, pl,
-	              polr_dict_plan_outcome(e != hipSuccess ? hipGetErrorString(e) : nullptr, 0, h_scalars[DICT_FULL] != 0, payload_col, &pl));
-	DictCol d;
-	d.src_col = payload_col;
-	d.code_col = ht->n_payload;
+	POLR_TRY_PLAN(ctx, pl, dict_outcome(job, e != hipSuccess ? hipGetErrorString(e) : nullptr, 0, h_scalars[DICT_FULL] != 0, &pl));
 	d.n_codes = h_scalars[DICT_N_CODES];
 	d.has_null = h_scalars[DICT_HAS_NULL];
 	// sort (sorted codes, two values or more) or representatives
@@ -555,28 +636,140 @@ extern "C" int polr_ht_encode_dictionary_ex(polr_ht *ht, uint32_t payload_col, u
 	if (d.n_codes || pl.sorted) {
 		HIPCHK(ctx, hipStreamSynchronize(st));
 	}
+	return POLR_OK;
+}
+
+extern "C" int polr_ht_encode_dictionary(polr_ht *ht, uint32_t payload_col, void *stream, uint32_t *code_col, uint32_t *n_codes,
+                                         uint32_t *has_null) {
+	return polr_ht_encode_dictionary_ex(ht, payload_col, 0u, stream, code_col, n_codes, has_null);
+}
+
+extern "C" int polr_ht_encode_dictionary_ex(polr_ht *ht, uint32_t payload_col, uint32_t flags, void *stream, uint32_t *code_col,
+                                            uint32_t *n_codes, uint32_t *has_null) {
+	POLR_ENTRY();
+	if (!ht || !code_col || !n_codes || !has_null) {
+		return POLR_E_INVALID;
+	}
+	polr_ctx *ctx = ht->ctx;
+	// the request, and what the plan says to it
+	const DictCol *prior = polr_dict_of_src_col(ht, payload_col);
+	PolrDictRequest rq = {};
+	rq.flags = flags;
+	rq.payload_col = payload_col;
+	rq.finalized = ht->kind != KIND_NONE;
+	rq.n_payload = ht->n_payload;
+	rq.width = payload_col < ht->n_payload ? ht->payload[payload_col].width : 0;
+	rq.encoded = prior != nullptr;
+	rq.encoded_as = prior ? prior->code_col : 0;
+	rq.n_rows = ht->n_rows_in;
+	PolrDictPlan pl;
+	POLR_TRY_PLAN(ctx, pl, polr_dict_plan_encode(rq, &pl));
+	HIPCHK(ctx, hipSetDevice(ctx->device));
+	hipStream_t st = polr_stream(ctx, stream);
+	if (st != ctx->stream) {
+		// (the column's cells were uploaded, and rebased onto their heap, on the context's stream)
+		HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+	}
+	// everything up to the commit lives in this scope: a failure frees it and leaves the table exactly as it was
+	const DictJob job = {&pl, &ht->payload[payload_col], rq.n_rows, nullptr, rq.n_rows, payload_col, false};
+	OwnedCol codes;
+	DictCol d;
+	d.src_col = payload_col;
+	d.code_col = ht->n_payload;
+	POLR_TRY(dict_encode(ctx, st, job, codes, d));
 	// commit: nothing can fail from here on.  The code column is an ordinary payload column: 4 bytes, unsigned, no validity
 	// array but the one POLR_DICT_NULL_INVALID copied
 	*code_col = d.code_col;
 	*n_codes = d.n_codes;
 	*has_null = d.has_null;
-	ht->device_bytes += polr_dict_device_bytes(n, copy_valid, d.n_codes);
+	ht->device_bytes += polr_dict_device_bytes(rq.n_rows, codes.valid != nullptr, d.n_codes);
 	ht->payload.push_back(std::move(codes));
 	ht->n_payload++;
 	ht->dicts.push_back(std::move(d));
 	return POLR_OK;
 }
 
-extern "C" int polr_ht_fetch_dictionary(polr_ht *ht, uint32_t code_col, void *stream, uint64_t *offsets, uint64_t n_offsets,
-                                        uint8_t *str_bytes, uint64_t str_cap, uint64_t *str_used) {
+// Appends the code column to the pipeline's probe columns.  Pointers into polr_pipeline::probe_cols live inside one call
+// only (OutCol::col, polr_out_describe_col: resolved and dropped by every sink call; the scan and the statistics likewise),
+// and the device never reads the column descriptors of an output or a multiplexer through the pipeline -- their sinks hold
+// DevCol copies -- so handles made before the call run on as they did.  The new descriptors are built aside and swapped in
+// at the commit.
+extern "C" int polr_pipeline_encode_dictionary(polr_pipeline *p, uint32_t probe_col, uint32_t flags, void *stream, uint32_t *code_col,
+                                               uint32_t *n_codes, uint32_t *has_null) {
 	POLR_ENTRY();
-	if (!ht || !str_used || (!offsets && n_offsets) || (!str_bytes && str_cap)) {
+	if (!p || !code_col || !n_codes || !has_null) {
 		return POLR_E_INVALID;
 	}
-	polr_ctx *ctx = ht->ctx;
-	const DictCol *d = polr_dict_of_code_col(ht, code_col);
-	PolrDictPlan pl;
-	POLR_TRY_PLAN(ctx, pl, polr_dict_plan_fetch(d != nullptr, code_col, 0, nullptr, 0, &pl));
+	polr_ctx *ctx = p->ctx;
+	// the request, and what the plan says to it
+	const DictCol *prior = polr_dict_of_src_col(p->dicts, probe_col);
+	PolrPDictRequest rq = {};
+	rq.flags = flags;
+	rq.probe_col = probe_col;
+	rq.n_probe_cols = p->n_probe_cols;
+	rq.width = probe_col < p->n_probe_cols ? p->probe_cols[probe_col].width : 0;
+	rq.encoded = prior != nullptr;
+	rq.encoded_as = prior ? prior->code_col : 0;
+	rq.is_code_col = polr_dict_of_code_col(p->dicts, probe_col) != nullptr;
+	rq.n_rows = p->n_probe_rows;
+	rq.has_selection = p->sel_dev != nullptr; // (the selection in force: what POLR_STATS_SELECTED reads)
+	rq.n_selected = p->n_tuples;
+	PolrPDictPlan pl;
+	POLR_TRY_PLAN(ctx, pl, polr_pdict_plan_encode(rq, &pl));
+	HIPCHK(ctx, hipSetDevice(ctx->device));
+	hipStream_t st = polr_stream(ctx, stream);
+	if (st != ctx->stream) {
+		// (the column's cells were uploaded, and rebased onto their heap, on the context's stream)
+		HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+	}
+	// (room for the commit's two appends first: moving the records changes nothing a caller can see)
+	p->probe_cols.reserve((size_t)p->n_probe_cols + 1);
+	p->dicts.reserve(p->dicts.size() + 1);
+	// everything up to the commit lives in this scope: a failure frees it and leaves the pipeline exactly as it was
+	const DictJob job = {&pl, &p->probe_cols[probe_col], rq.n_rows, pl.selected ? p->sel_dev : nullptr, pl.n_insert, probe_col, true};
+	OwnedCol codes;
+	DictCol d;
+	d.src_col = probe_col;
+	d.code_col = p->n_probe_cols;
+	POLR_TRY(dict_encode(ctx, st, job, codes, d));
+	// the descriptors with one more column: the device array of the probe columns and both variants of the pipeline
+	std::vector<DevCol> cols((size_t)p->n_probe_cols + 1);
+	for (uint32_t c = 0; c < p->n_probe_cols; c++) {
+		cols[c] = dev_col(p->probe_cols[c]);
+	}
+	cols[p->n_probe_cols] = dev_col(codes);
+	DevBuf<DevCol> cols_dev;
+	DevBuf<DevPipeline> dev_mat, dev_count;
+	HIPCHK(ctx, cols_dev.alloc(cols.size()));
+	HIPCHK(ctx, dev_mat.alloc(1));
+	HIPCHK(ctx, dev_count.alloc(1));
+	DevPipeline host_mat = p->host_mat, host_count = p->host_count;
+	host_mat.n_probe_cols = host_count.n_probe_cols = p->n_probe_cols + 1;
+	host_mat.probe_cols = host_count.probe_cols = cols_dev;
+	HIPCHK(ctx, hipMemcpy(cols_dev, cols.data(), cols.size() * sizeof(DevCol), hipMemcpyHostToDevice));
+	HIPCHK(ctx, hipMemcpy(dev_mat, &host_mat, sizeof(DevPipeline), hipMemcpyHostToDevice));
+	HIPCHK(ctx, hipMemcpy(dev_count, &host_count, sizeof(DevPipeline), hipMemcpyHostToDevice));
+	// commit: nothing can fail from here on.  The code column is an ordinary probe column: 4 bytes, unsigned
+	*code_col = d.code_col;
+	*n_codes = d.n_codes;
+	*has_null = d.has_null;
+	p->probe_cols.push_back(std::move(codes));
+	p->n_probe_cols++;
+	p->dicts.push_back(std::move(d));
+	p->probe_cols_dev = std::move(cols_dev);
+	p->host_mat = host_mat;
+	p->host_count = host_count;
+	p->dev_mat = std::move(dev_mat);
+	p->dev_count = std::move(dev_count);
+	return POLR_OK;
+}
+
+// the whole dictionary `d` (NULL: none is held) as string records; probe: the pipeline's call
+static int dict_fetch(polr_ctx *ctx, const DictCol *d, bool probe, uint32_t code_col, void *stream, uint64_t *offsets,
+                      uint64_t n_offsets, uint8_t *str_bytes, uint64_t str_cap, uint64_t *str_used) {
+	PolrPDictPlan pl;
+	POLR_TRY_PLAN(ctx, pl, probe ? polr_pdict_plan_fetch(d != nullptr, code_col, 0, nullptr, 0, &pl)
+	                             : polr_dict_plan_fetch(d != nullptr, code_col, 0, nullptr, 0, &pl));
 	*str_used = 0;
 	if (d->n_codes == 0) {
 		return POLR_OK;
@@ -599,16 +792,12 @@ extern "C" int polr_ht_fetch_dictionary(polr_ht *ht, uint32_t code_col, void *st
 	return POLR_OK;
 }
 
-extern "C" int polr_ht_fetch_dictionary_codes(polr_ht *ht, uint32_t code_col, void *stream, const uint32_t *codes, uint64_t n,
-                                              uint64_t *offsets, uint8_t *str_bytes, uint64_t str_cap, uint64_t *str_used) {
-	POLR_ENTRY();
-	if (!ht || !str_used || (n && (!codes || !offsets)) || (!str_bytes && str_cap)) {
-		return POLR_E_INVALID;
-	}
-	polr_ctx *ctx = ht->ctx;
-	const DictCol *d = polr_dict_of_code_col(ht, code_col);
-	PolrDictPlan pl;
-	POLR_TRY_PLAN(ctx, pl, polr_dict_plan_fetch(d != nullptr, code_col, d ? d->n_codes : 0, codes, n, &pl));
+// ... and the strings of the n listed codes
+static int dict_fetch_codes(polr_ctx *ctx, const DictCol *d, bool probe, uint32_t code_col, void *stream, const uint32_t *codes,
+                            uint64_t n, uint64_t *offsets, uint8_t *str_bytes, uint64_t str_cap, uint64_t *str_used) {
+	PolrPDictPlan pl;
+	POLR_TRY_PLAN(ctx, pl, probe ? polr_pdict_plan_fetch(d != nullptr, code_col, d ? d->n_codes : 0, codes, n, &pl)
+	                             : polr_dict_plan_fetch(d != nullptr, code_col, d ? d->n_codes : 0, codes, n, &pl));
 	*str_used = 0;
 	if (n == 0) {
 		return POLR_OK;
@@ -635,4 +824,44 @@ extern "C" int polr_ht_fetch_dictionary_codes(polr_ht *ht, uint32_t code_col, vo
 	POLR_TRY(rc);
 	memcpy(offsets, offs.data(), (size_t)n * 8);
 	return POLR_OK;
+}
+
+extern "C" int polr_ht_fetch_dictionary(polr_ht *ht, uint32_t code_col, void *stream, uint64_t *offsets, uint64_t n_offsets,
+                                        uint8_t *str_bytes, uint64_t str_cap, uint64_t *str_used) {
+	POLR_ENTRY();
+	if (!ht || !str_used || (!offsets && n_offsets) || (!str_bytes && str_cap)) {
+		return POLR_E_INVALID;
+	}
+	return dict_fetch(ht->ctx, polr_dict_of_code_col(ht, code_col), false, code_col, stream, offsets, n_offsets, str_bytes, str_cap,
+	                  str_used);
+}
+
+extern "C" int polr_ht_fetch_dictionary_codes(polr_ht *ht, uint32_t code_col, void *stream, const uint32_t *codes, uint64_t n,
+                                              uint64_t *offsets, uint8_t *str_bytes, uint64_t str_cap, uint64_t *str_used) {
+	POLR_ENTRY();
+	if (!ht || !str_used || (n && (!codes || !offsets)) || (!str_bytes && str_cap)) {
+		return POLR_E_INVALID;
+	}
+	return dict_fetch_codes(ht->ctx, polr_dict_of_code_col(ht, code_col), false, code_col, stream, codes, n, offsets, str_bytes,
+	                        str_cap, str_used);
+}
+
+extern "C" int polr_pipeline_fetch_dictionary(polr_pipeline *p, uint32_t code_col, void *stream, uint64_t *offsets, uint64_t n_offsets,
+                                              uint8_t *str_bytes, uint64_t str_cap, uint64_t *str_used) {
+	POLR_ENTRY();
+	if (!p || !str_used || (!offsets && n_offsets) || (!str_bytes && str_cap)) {
+		return POLR_E_INVALID;
+	}
+	return dict_fetch(p->ctx, polr_dict_of_code_col(p->dicts, code_col), true, code_col, stream, offsets, n_offsets, str_bytes, str_cap,
+	                  str_used);
+}
+
+extern "C" int polr_pipeline_fetch_dictionary_codes(polr_pipeline *p, uint32_t code_col, void *stream, const uint32_t *codes, uint64_t n,
+                                                    uint64_t *offsets, uint8_t *str_bytes, uint64_t str_cap, uint64_t *str_used) {
+	POLR_ENTRY();
+	if (!p || !str_used || (n && (!codes || !offsets)) || (!str_bytes && str_cap)) {
+		return POLR_E_INVALID;
+	}
+	return dict_fetch_codes(p->ctx, polr_dict_of_code_col(p->dicts, code_col), true, code_col, stream, codes, n, offsets, str_bytes,
+	                        str_cap, str_used);
 }

@@ -124,22 +124,29 @@ struct polr_ht {
 	uint64_t device_bytes = 0;
 };
 
-// the dictionary whose code column / whose VARCHAR source column is payload column `col`, or nullptr
-static inline const DictCol *polr_dict_of_code_col(const polr_ht *ht, uint32_t col) {
-	for (const DictCol &d : ht->dicts) {
+// the dictionary whose code column / whose VARCHAR source column is column `col` (a payload column of a table, a probe
+// column of a pipeline), or nullptr
+static inline const DictCol *polr_dict_of_code_col(const std::vector<DictCol> &dicts, uint32_t col) {
+	for (const DictCol &d : dicts) {
 		if (d.code_col == col) {
 			return &d;
 		}
 	}
 	return nullptr;
 }
-static inline const DictCol *polr_dict_of_src_col(const polr_ht *ht, uint32_t col) {
-	for (const DictCol &d : ht->dicts) {
+static inline const DictCol *polr_dict_of_src_col(const std::vector<DictCol> &dicts, uint32_t col) {
+	for (const DictCol &d : dicts) {
 		if (d.src_col == col) {
 			return &d;
 		}
 	}
 	return nullptr;
+}
+static inline const DictCol *polr_dict_of_code_col(const polr_ht *ht, uint32_t col) {
+	return polr_dict_of_code_col(ht->dicts, col);
+}
+static inline const DictCol *polr_dict_of_src_col(const polr_ht *ht, uint32_t col) {
+	return polr_dict_of_src_col(ht->dicts, col);
 }
 
 struct polr_pipeline {
@@ -150,6 +157,9 @@ struct polr_pipeline {
 	std::vector<OwnedCol> probe_cols;
 	std::vector<DevBuf<uint8_t>> heaps; // string heaps of VARCHAR probe columns (polr_pipeline_set_probe_heap), owned
 	DevBuf<DevCol> probe_cols_dev;
+	// dictionaries of the code columns polr_pipeline_encode_dictionary appended (polr_dict.hip), cells owned; they point into
+	// the heaps above, or into the caller's
+	std::vector<DictCol> dicts;
 	// a pipeline made by polr_pipeline_from_output: the cells and validity arrays of all its probe columns in one allocation
 	// -- probe_cols are views of it (their own owners are empty, lib_cells is set)
 	DevBuf<uint8_t> col_mem;

@@ -54,6 +54,7 @@ EXPORTS = [
     "polr_ht_semi_filter",
     "polr_ht_column_stats", "polr_pipeline_column_stats", "polr_ht_finalize_auto_stats", "polr_col_stats_plan_info",
     "polr_out_fuse_aggregate", "polr_out_fused_aggregate_result",
+    "polr_pipeline_encode_dictionary", "polr_pipeline_fetch_dictionary", "polr_pipeline_fetch_dictionary_codes",
 ]
 
 
@@ -70,6 +71,7 @@ class Col(C.Structure):
 
 KEY_BY_VALUE, KEY_NULL_EQUAL = 1, 2  # polr_ht_set_key_flags
 DICT_SORTED, DICT_NULL_INVALID = 1, 2  # polr_ht_encode_dictionary_ex
+DICT_SELECTED = 4  # polr_pipeline_encode_dictionary only
 
 
 class PoolTuning(C.Structure):
@@ -474,6 +476,9 @@ def load():
     L.polr_ht_fetch_dictionary.argtypes = [vp, u32, vp, vp, u64, vp, u64, P(u64)]
     L.polr_ht_encode_dictionary_ex.argtypes = [vp, u32, u32, vp, P(u32), P(u32), P(u32)]
     L.polr_ht_fetch_dictionary_codes.argtypes = [vp, u32, vp, vp, u64, vp, vp, u64, P(u64)]
+    L.polr_pipeline_encode_dictionary.argtypes = [vp, u32, u32, vp, P(u32), P(u32), P(u32)]
+    L.polr_pipeline_fetch_dictionary.argtypes = [vp, u32, vp, vp, u64, vp, u64, P(u64)]
+    L.polr_pipeline_fetch_dictionary_codes.argtypes = [vp, u32, vp, vp, u64, vp, vp, u64, P(u64)]
     L.polr_out_fused_result.argtypes = [vp, vp, vp, C.c_uint64, vp]
     L.polr_out_fuse_aggregate.argtypes = [vp, vp, u32]
     L.polr_out_fused_aggregate_result.argtypes = [vp, vp, vp, u32]
@@ -928,6 +933,39 @@ class Pipeline:
         else:
             sel = np.ascontiguousarray(sel, dtype=np.uint32)
             self.ctx.check(self.ctx.L.polr_pipeline_set_selection(self.h, sel.ctypes.data, len(sel), 0))
+
+    def encode_dictionary(self, probe_col, sorted=False, null_invalid=False, selected=False, stream=None, flags=None):
+        """polr_pipeline_encode_dictionary: VARCHAR probe column `probe_col` -> one more probe column of 4-byte codes, by the
+        rules of HashTable.encode_dictionary -> (code_col, n_codes, has_null).  selected (DICT_SELECTED): only the rows of the
+        selection in force are read and coded; every other row gets n_codes.  `flags`: the word itself."""
+        col, n, null = C.c_uint32(), C.c_uint32(), C.c_uint32()
+        if flags is None:
+            flags = (DICT_SORTED if sorted else 0) | (DICT_NULL_INVALID if null_invalid else 0) | (DICT_SELECTED if selected else 0)
+        self.ctx.check(self.ctx.L.polr_pipeline_encode_dictionary(self.h, probe_col, flags, stream, C.byref(col), C.byref(n),
+                                                                  C.byref(null)))
+        self.__dict__.setdefault("_n_codes", {})[col.value] = n.value  # (dictionary() sizes its offsets by it)
+        return col.value, n.value, null.value
+
+    def dictionary(self, code_col, str_cap=4096, stream=None):
+        """polr_pipeline_fetch_dictionary: the strings of code column `code_col`, [bytes] indexed by code; one retry with the
+        exact size when str_cap was too small"""
+        n_codes = getattr(self, "_n_codes", {}).get(code_col, 0)  # (not encoded through this object: the call refuses)
+        offs = np.zeros((max(n_codes, 1),), dtype=np.uint64)
+        rc, raw = _fetch_records(lambda *arena: self.ctx.L.polr_pipeline_fetch_dictionary(self.h, code_col, stream, offs.ctypes.data,
+                                                                                          n_codes, *arena), str_cap)
+        self.ctx.check(rc)
+        return [_record(raw, at) for at in offs[:n_codes].tolist()]
+
+    def dictionary_strings(self, code_col, codes, str_cap=4096, stream=None):
+        """polr_pipeline_fetch_dictionary_codes: the strings of the listed codes of code column `code_col`, [bytes] in list
+        order (duplicates included); one retry with the exact size when str_cap was too small"""
+        codes = np.ascontiguousarray(codes, dtype=np.uint32)
+        n = len(codes)
+        offs = np.zeros((max(n, 1),), dtype=np.uint64)
+        rc, raw = _fetch_records(lambda *arena: self.ctx.L.polr_pipeline_fetch_dictionary_codes(
+            self.h, code_col, stream, codes.ctypes.data, n, offs.ctypes.data, *arena), str_cap)
+        self.ctx.check(rc)
+        return [_record(raw, at) for at in offs[:n].tolist()]
 
     def column_stats(self, cols, selected=False, stream=None):
         """polr_pipeline_column_stats: min / max / counts of the probe columns cols[] in one pass on the device, over all

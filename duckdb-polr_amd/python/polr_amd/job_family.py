@@ -313,15 +313,19 @@ def fused_select_on_build_sides(wl):
     return all(sj >= 0 for sj, _c in wl["select"])
 
 
-def run_fused_device(ctx, wl, paths, routing="adaptive_reinit", chunk_capacity=1024):
+def run_fused_device(ctx, wl, paths, routing="adaptive_reinit", chunk_capacity=1024, probe_dictionary=False):
     """SELECT COUNT(*), MIN(a), MIN(b), ... of a workload whose select list lies on build sides, in ONE pool launch and
     without an output to size: every select column becomes a sorted dictionary code column of its build side (DICT_SORTED |
     DICT_NULL_INVALID: the order of the codes is the order of the strings, a NULL string an invalid code), the output
     carries a fused ungrouped sink -- COUNT(*) and MIN(code column) per select column --, one resident run fills it, and
     the winning codes are turned back into strings (HashTable.dictionary_strings).
+    probe_dictionary=True: a select column of the PROBE table is uploaded as a string probe column and, after the scan
+    filter, encoded over the selection in force (Pipeline.encode_dictionary: DICT_SORTED | DICT_NULL_INVALID |
+    DICT_SELECTED); its MIN is the MIN of that code column, turned back by Pipeline.dictionary_strings.  Without it such a
+    workload is refused, as before.
     -> {"count_star": int, "select_min": [bytes or None] in the order of wl["select"], "rows_written": rows of the output}"""
     from . import capi
-    if not fused_select_on_build_sides(wl):
+    if not probe_dictionary and not fused_select_on_build_sides(wl):
         raise ValueError("the select list names a probe-side column: polr_out_aggregate_string over emitted row ids")
     # (the caller's workload stays as it is: the joins are shallow copies that carry the dictionary request)
     wl = dict(wl, joins=[dict(j) for j in wl["joins"]])
@@ -329,6 +333,8 @@ def run_fused_device(ctx, wl, paths, routing="adaptive_reinit", chunk_capacity=1
         j["dictionary"] = list(j.get("dictionary") or [])
         j["dictionary_flags"] = dict(j.get("dictionary_flags") or {})
     for sj, col in wl["select"]:
+        if sj < 0:
+            continue
         j = wl["joins"][sj]
         if col not in j["dictionary"]:
             j["dictionary"].append(col)
@@ -339,16 +345,22 @@ def run_fused_device(ctx, wl, paths, routing="adaptive_reinit", chunk_capacity=1
         handles += [ht for ht, _ in joins]
         cols = list(wl["probe"]["cols"].values())
         names = list(wl["probe"]["cols"].keys())
-        pipe = capi.Pipeline(ctx, cols, len(cols[0]), joins, paths)
+        # the probe table's select columns: string_t cells behind the key columns, and their heaps
+        pstr = {c: capi.string_cells(wl["probe"]["strings"][c]) for c in dict.fromkeys(c for sj, c in wl["select"] if sj < 0)}
+        pipe = capi.Pipeline(ctx, cols + [cells for cells, _h in pstr.values()], len(cols[0]), joins, paths)
         handles.append(pipe)
+        for i, (_cells, heap) in enumerate(pstr.values()):
+            pipe.set_probe_heap(len(cols) + i, heap)
         flt = wl["probe"].get("filter")
         if flt:
             _n, n_chunks = pipe.scan_filter([(names.index(c), op, const) for c, op, const in flt])
         else:
             n_chunks = (len(cols[0]) + 1023) // 1024
+        # ... encoded over the rows the filter kept, and no others
+        pcode = {c: pipe.encode_dictionary(len(cols) + i, sorted=True, null_invalid=True, selected=True)[0] for i, c in enumerate(pstr)}
         out = capi.Output(pipe, chunk_capacity, 1)  # (nothing is written: the smallest output there is)
         handles.append(out)
-        code_cols = [capi.dictionary_payload_index(wl["joins"][sj], col)[0] for sj, col in wl["select"]]
+        code_cols = [pcode[col] if sj < 0 else capi.dictionary_payload_index(wl["joins"][sj], col)[0] for sj, col in wl["select"]]
         out.fuse_aggregate([("count_star", -1, 0)] + [("min", sj, cc) for (sj, _c), cc in zip(wl["select"], code_cols)])
         mpx = capi.DeviceMultiplexer(pipe, routing)
         handles.append(mpx)
@@ -359,7 +371,8 @@ def run_fused_device(ctx, wl, paths, routing="adaptive_reinit", chunk_capacity=1
         res = out.fused_aggregate_result()
         mins = []
         for (sj, _c), cc, code in zip(wl["select"], code_cols, res[1:]):
-            mins.append(None if code is None else joins[sj][0].dictionary_strings(cc, [code])[0])
+            holder = pipe if sj < 0 else joins[sj][0]
+            mins.append(None if code is None else holder.dictionary_strings(cc, [code])[0])
         return {"count_star": res[0], "select_min": mins, "rows_written": out.stats()[0]}
     finally:
         for h in reversed(handles):
@@ -555,3 +568,113 @@ def run_chain_device(ctx, plan, data, chunk_capacity=1024):
         h.close()
     return {"count": stage_rows[-1], "mins": mins, "int_mins": int_mins, "intermediates": inter, "stage_rows": stage_rows,
             "flat": flat}
+
+
+def run_chain_fused_device(ctx, plan, data, chunk_capacity=1024, routing="adaptive_reinit"):
+    """run_chain_device with the LAST stage fused: its carried select columns become sorted code columns (DICT_SORTED |
+    DICT_NULL_INVALID) -- a column of one of the stage's build sides through HashTable.encode_dictionary before the table is
+    finalized, a column carried into the stage through Pipeline.encode_dictionary on the pipeline from_output made -- and
+    the stage's output carries a fused ungrouped sink: COUNT(*) and MIN(code column) per select column.  ONE pool launch
+    runs that stage: no counting run, no sized output, no string sink.  The stages before it run as in run_chain_device.
+    -> {"count", "mins" in the order of plan["final"], "stage_rows" (the last: COUNT(*)), "intermediates" (of the last stage:
+    what the multiplexer counted), "rows_written": rows in the last stage's output (0)}"""
+    from . import capi
+    last = len(plan["stages"]) - 1
+    if 1 + len(plan["stages"][-1]["carry"]) > 8:
+        raise ValueError("a fused sink holds 8 aggregates: COUNT(*) and at most 7 select columns")
+    out = pipe = None
+    hts, keep = [], []
+    n_tuples = len(data["sel"]) if data["sel"] is not None else data["n_probe"]
+    inter, stage_rows = [], []
+    try:
+        for s, st in enumerate(plan["stages"]):
+            fused = s == last
+            encode = {sj: {} for sj, _sc in st["carry"] if sj >= 0} if fused else {}  # join -> {payload column: code column}
+            joins = []
+            for j, i in enumerate(st["joins"]):
+                d = data["joins"][i]
+                cols, heaps = [], {}
+                for x, (c, (_n, kd)) in enumerate(zip(d["payload"], st["payload"][j])):
+                    if kd == "str":
+                        cells, heap = capi.string_cells(c)
+                        keep.append((cells, heap))
+                        heaps[x] = heap
+                        c = cells
+                    cols.append(c)
+                ht = capi.HashTable.from_columns(ctx, [d["key"]], cols)
+                hts.append(ht)
+                for x, heap in heaps.items():
+                    ht.set_payload_heap(x, heap)
+                for sj, sc in st["carry"] if fused else ():
+                    if sj == j and sc not in encode[j]:
+                        encode[j][sc] = ht.encode_dictionary(sc, sorted=True, null_invalid=True)[0]
+                ht.finalize_auto(int(d["key"].min()), int(d["key"].max()))
+                joins.append((ht, [st["key_src"][j]]))
+            k = len(joins)
+            paths = [list(range(k))]
+            if s == 0:
+                cols, heaps = [], {}
+                for x, c in enumerate(data["source"]):
+                    if isinstance(c, list):
+                        cells, heap = capi.string_cells(c)
+                        keep.append((cells, heap))
+                        heaps[x] = heap
+                        c = cells
+                    cols.append(c)
+                new = capi.Pipeline(ctx, cols, data["n_probe"], joins, paths)
+                for x, heap in heaps.items():
+                    new.set_probe_heap(x, heap)
+                if data["sel"] is not None:
+                    new.set_selection(data["sel"])
+            else:
+                new = capi.Pipeline.from_output(out, plan["stages"][s - 1]["carry"], joins, paths)
+                # the stage before it is done with: the new pipeline owns its source
+                out.close()
+                pipe.close()
+                for h in hts[:-k]:
+                    h.close()
+                hts = hts[-k:]
+            pipe, out = new, None
+            if not fused:
+                n_out = n_inter = 0
+                if n_tuples:
+                    counts = pipe.probe_rounds([(0, n_tuples, 0, 0)])
+                    n_out, n_inter = int(counts[0][k - 1]), int(counts.sum())
+                out = capi.Output(pipe, chunk_capacity, n_out // chunk_capacity + 1 + 8192)  # (a partly filled chunk per emitting wave)
+                if n_tuples:
+                    pipe.probe_rounds([(0, n_tuples, 0, 1)], out=out)
+                if out.stats()[0] != n_out:
+                    raise RuntimeError("stage %d: %d rows emitted, %d counted" % (s, out.stats()[0], n_out))
+                inter.append(n_inter)
+                stage_rows.append(n_out)
+                n_tuples = n_out
+                continue
+            # the last stage: the carried select columns as code columns, COUNT(*) and their MINs folded inside one launch
+            if not n_tuples:  # (no row reached it: nothing to launch)
+                return {"count": 0, "mins": [None] * len(st["carry"]), "intermediates": inter + [0], "stage_rows": stage_rows + [0],
+                        "rows_written": 0}
+            pcode = {}
+            for sj, sc in st["carry"]:
+                if sj < 0 and sc not in pcode:
+                    pcode[sc] = pipe.encode_dictionary(sc, sorted=True, null_invalid=True, selected=True)[0]
+            code_cols = [pcode[sc] if sj < 0 else encode[sj][sc] for sj, sc in st["carry"]]
+            out = capi.Output(pipe, chunk_capacity, 1)  # (nothing is written: the smallest output there is)
+            out.fuse_aggregate([("count_star", -1, 0)] + [("min", sj, cc) for (sj, _sc), cc in zip(st["carry"], code_cols)])
+            mpx = capi.DeviceMultiplexer(pipe, routing)
+            try:
+                capi.run_resident([mpx], [(0, (n_tuples + 1023) // 1024)], out=out, reset=True, finish=True)
+                inter.append(int(mpx.finish()["num_intermediates"]))
+            finally:
+                mpx.close()
+            res = out.fused_aggregate_result()
+            mins = []
+            for (sj, _sc), cc, code in zip(st["carry"], code_cols, res[1:]):
+                holder = pipe if sj < 0 else joins[sj][0]
+                mins.append(None if code is None else holder.dictionary_strings(cc, [code])[0])
+            stage_rows.append(int(res[0]))
+            return {"count": stage_rows[-1], "mins": mins, "intermediates": inter, "stage_rows": stage_rows,
+                    "rows_written": out.stats()[0]}
+    finally:
+        for h in [out, pipe] + hts:
+            if h is not None:
+                h.close()

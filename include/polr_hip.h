@@ -948,8 +948,7 @@ int polr_pipeline_set_probe_heap(polr_pipeline *p, uint32_t probe_col, const voi
  * of the whole dictionary: offsets[i] = byte offset of the record of codes[i], duplicates get a record each, *str_used =
  * the bytes the records take.  n = 0: POLR_OK, *str_used = 0.  A listed code >= n_codes (the NULL code is not a string):
  * POLR_E_INVALID, nothing written.  str_cap < *str_used: POLR_E_OVERFLOW with *str_used exact and offsets / str_bytes
- * untouched -- one retry succeeds.  POLR_E_INVALID for the same tables as polr_ht_fetch_dictionary.
- * Not provided: dictionaries of probe-side columns. */
+ * untouched -- one retry succeeds.  POLR_E_INVALID for the same tables as polr_ht_fetch_dictionary. */
 #define POLR_DICT_SORTED       1u
 #define POLR_DICT_NULL_INVALID 2u
 int polr_ht_encode_dictionary(polr_ht *ht, uint32_t payload_col, void *stream, uint32_t *code_col, uint32_t *n_codes,
@@ -960,6 +959,46 @@ int polr_ht_fetch_dictionary(polr_ht *ht, uint32_t code_col, void *stream, uint6
                              uint8_t *str_bytes, uint64_t str_cap, uint64_t *str_used);
 int polr_ht_fetch_dictionary_codes(polr_ht *ht, uint32_t code_col, void *stream, const uint32_t *codes, uint64_t n,
                                    uint64_t *offsets, uint8_t *str_bytes, uint64_t str_cap, uint64_t *str_used);
+/* ---- dictionary codes for VARCHAR PROBE columns (JOB: title.title, the carried select list of a chained plan) ------
+ * polr_pipeline_encode_dictionary encodes VARCHAR probe column `probe_col` of a pipeline on the device and appends ONE
+ * probe column to it: index *code_col = the pipeline's probe column count before the call, 4 bytes wide, unsigned.  From
+ * then on it is an ordinary integer probe column for every consumer: polr_out_aggregate* in all forms,
+ * polr_out_fuse_aggregate and polr_out_fuse_grouped (MIN(varchar) is MIN(code) inside the pool launch, GROUP BY a probe
+ * string is GROUP BY its code), polr_out_materialize, polr_out_column_width (4), polr_pipeline_column_stats, the three
+ * scan-filter entry points, and polr_pipeline_from_output, which carries it forward as a plain 4-byte column (the strings
+ * stay with the pipeline that encoded).
+ *  - The code rules are those of polr_ht_encode_dictionary_ex above, word for word, with "table row" for "build row": equal
+ *    strings get equal codes; without POLR_DICT_SORTED codes count first appearances by table row, with it they ascend with
+ *    the strings; a NULL row gets *n_codes and its cell is never read; POLR_DICT_NULL_INVALID copies the validity array;
+ *    the heap-never-came guard (POLR_E_INVALID; polr_pipeline_set_probe_heaps, then encode) runs before any pointer is
+ *    followed; 0 rows encode to *n_codes = 0.
+ *  - POLR_DICT_SELECTED (this call only; polr_ht_encode_dictionary_ex refuses the bit): only the rows of the selection in
+ *    force take part -- what POLR_STATS_SELECTED reads: the result of the last scan filter or polr_pipeline_set_selection;
+ *    with no selection the flag means all rows.  A row outside the selection is not read; its code is *n_codes, and with
+ *    POLR_DICT_NULL_INVALID it is invalid: the code column then gets a validity array of `valid AND selected`, also when the
+ *    source column has none.  *has_null, *n_codes and first appearance speak of the selected rows only; first appearance is
+ *    the lowest table row among the selected, whatever the order of the selection, and a row listed twice counts once.  The
+ *    string table and every scratch array that need not be indexed by table row are sized by the selected count: 36 bytes
+ *    per slot of a table of 2 to 4 slots per SELECTED position plus 4 bytes per selected position, and 4 bytes per table
+ *    row (plus what the sort takes per distinct value).  THE CODES HOLD FOR RUNS OVER THAT SELECTION OR A SUBSET OF IT: the
+ *    library does not track later changes of the selection -- after a wider one, rows that were outside read as NULL.
+ *  - Outputs and multiplexers created before the call stay valid, and a run with them afterwards returns what it returned
+ *    before.  The call waits for the context's own stream first and returns after the codes are complete; it must not be
+ *    called while a run of the pipeline is in flight.
+ *  - Refusals, in this order, each leaving the pipeline exactly as it was (column count included): a flag other than the
+ *    three, no such probe column, a column that is not 16 bytes wide, a column that is encoded already, a code column as
+ *    source: POLR_E_INVALID; a slot space beyond 32 bits: POLR_E_UNSUPPORTED; then a HIP error (POLR_E_HIP) and the heap
+ *    guard (POLR_E_INVALID).
+ * polr_pipeline_fetch_dictionary / _codes: the sizing and POLR_E_OVERFLOW protocol of their polr_ht_ twins.  POLR_E_INVALID
+ * for a column that is not a code column whose dictionary this pipeline holds.
+ * Not provided: dictionaries of probe-side columns shared with a build column; re-encoding after a new selection. */
+#define POLR_DICT_SELECTED 4u /* pipeline call only */
+int polr_pipeline_encode_dictionary(polr_pipeline *p, uint32_t probe_col, uint32_t flags, void *stream, uint32_t *code_col,
+                                    uint32_t *n_codes, uint32_t *has_null);
+int polr_pipeline_fetch_dictionary(polr_pipeline *p, uint32_t code_col, void *stream, uint64_t *offsets, uint64_t n_offsets,
+                                   uint8_t *str_bytes, uint64_t str_cap, uint64_t *str_used);
+int polr_pipeline_fetch_dictionary_codes(polr_pipeline *p, uint32_t code_col, void *stream, const uint32_t *codes, uint64_t n,
+                                         uint64_t *offsets, uint8_t *str_bytes, uint64_t str_cap, uint64_t *str_used);
 /* MIN / MAX (fn = POLR_AGG_MIN / POLR_AGG_MAX) of a VARCHAR column over the pipeline's output rows, reduced on the
  * device (src/function/aggregate/distributive/minmax.cpp over string_t: bytes compared as unsigned, a proper prefix
  * sorts first; NULLs take no part).  The winning string's bytes go to dst (at most dst_cap of them), *len = its whole

@@ -44,6 +44,8 @@ BUILDS["g_ax"] = ("polr_poolg.hip", ["-DPOLR_EXT=1", "-DPOLR_FUSE_AGG=2"])
 # ... and the measurement build of the fold's other shape (make fuseagg-ab)
 BUILDS["g_a1"] = ("polr_poolg.hip", ["-DPOLR_EXT=0", "-DPOLR_FUSE_AGG=1"])
 BUILDS["g_ax1"] = ("polr_poolg.hip", ["-DPOLR_EXT=1", "-DPOLR_FUSE_AGG=1"])
+# ... and the dictionary encoder's kernels (no router: only the first five columns say something)
+BUILDS["dict"] = ("polr_dict.hip", [])
 
 ROUTER_ENTRY = re.compile(r"^\s*s_setprio\s+3\b")
 STEPS_BEGIN = "polr-router-steps-begin"
